@@ -23,6 +23,14 @@ rank 0.  For N > 1 it is launched under ``torch.distributed.run`` with one rank 
 * ``cpu_baseline``: the reference's own patchworkpp.cpp (oracle/_ref, "reference") or the
   restatement ("port"), frame-parallel on the host cores, on a bounded sample.
 * ``latency``: BASELINE.json configs[1], one frame end to end on one GPU (launch-bound).
+
+A plain run sets up, warms up, times the K steps and prints the line (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration and the per-rank figures).  Everything
+else -- the self-checks and the parity anchor, ``synchronous``, ``exact_moments_off``, the per-kernel times
+and ``roofline``, ``latency``, ``reference_order``, ``ingest``, ``dense``, ``distinct``, ``streams`` and
+``cpu_baseline`` -- runs only with ``--full`` (the ``--skip-*`` / ``--no-*`` options still switch parts of it
+off).  ``--dump-outputs DIR`` writes what the timed path returned in its last step as .npy files
+(dump_outputs below).
 """
 import argparse
 import json
@@ -196,15 +204,15 @@ def ingest_leg(pwpp_hip, src, gpu_index, chunk=256, chunks=8):
 def estimate_memory_gb(args):
     """What one rank's GPU must hold (checked before RCCL is initialised): the input buffers of every batch in flight and the workspaces
     of the handles -- per point 16 B of input and ~26 B of workspace per handle (bin-ordered planes at ~1.5 slots per point, index
-    lists, codes), frames of ~125 k points (64-beam) or ~480 k (dense); the extra legs of a single-GPU run (1024 dense frames on two
-    handles) are the larger item there."""
+    lists, codes), frames of ~125 k points (64-beam) or ~480 k (dense); the extra legs of a single-GPU --full run (1024 dense frames on
+    two handles) are the larger item there."""
     pts = 480e3 if args.workload == "dense" else 125e3
     handles = 1 + max(1, min(4, args.in_flight))
     if args.workload == "streams":
         return (6 * args.frames * pts * 16 + args.frames * pts * 30) / 1e9 + 1.0
     main = args.frames * pts * (16.0 * max(1, min(4, args.in_flight)) + 30.0 * handles)
     extras = 0.0
-    if args.gpus == 1 and not args.skip_extras and args.workload == "kitti":
+    if args.gpus == 1 and args.full and not args.skip_extras and args.workload == "kitti":
         # (measured, round 6: 1024 dense frames from 64 clouds hold 48 GB per handle -- the segments follow every part's largest count over
         # all clouds -- 1024 varied 64-beam frames 15 GB; both legs keep two handles)
         extras = max(args.dense_frames * 480e3 * (16.0 + 2 * 100.0), args.distinct_frames * 125e3 * (2 * 16.0 + 2 * 125.0 + 2 * 36.0))
@@ -231,6 +239,45 @@ def mask_sha256(n, ground_idx):
     m = np.zeros(n, np.uint8)
     m[np.asarray(ground_idx)] = 1
     return hashlib.sha256(np.packbits(m).tobytes()).hexdigest()
+
+
+def dump_outputs(h, ns, out_dir, label_bytes=40 << 20, max_frames=64):
+    """--dump-outputs: what the timed path's last step returned to its caller, read from the handle `h` that ran it (ns: the points of
+    its frames, or of its streams' frames), as .npy files in `out_dir`:
+      counts.npy        (frames, 6) float64  n_ground, n_nonground, n_patches, n_rnr, n_out_of_range, n_dropped of every frame
+      state.npy         (frames, 9) float64  sensor_height, elevation_thr[4], flatness_thr[4] after the step (per frame / per stream)
+      sample_frames.npy (k,) float64         a fixed sample of the frames (seeded, within `label_bytes` of labels), ascending
+      labels.npy        (sum n,) float32     the sample's points in cloud order: 1 in the ground list, 0 in the non-ground list, -1 in
+                                             neither -- the index lists as sets (their order inside a patch is the binning atomics')
+      normals.npy, centers.npy (sum n_patches, 3) float32  the sample's plane normals and centres, bin traversal order
+    The sample depends on the frame sizes alone, so two builds given the same arguments dump the same frames."""
+    os.makedirs(out_dir, exist_ok=True)
+    F = len(ns)
+    counts = h.all_counts()[:F, :6].astype(np.float64)
+    state = np.zeros((F, 9), np.float64)
+    for i in range(F):
+        s = h.state(i)
+        state[i] = [s.sensor_height] + list(s.elevation_thr) + list(s.flatness_thr)
+    sample, used = [], 0
+    for i in np.random.default_rng(0).permutation(F):
+        if len(sample) == max_frames or (sample and used + 4 * ns[i] > label_bytes):
+            break
+        sample.append(int(i))
+        used += 4 * ns[i]
+    sample.sort()
+    labels, normals, centers = [], [], []
+    for i in sample:
+        lab = np.full(ns[i], -1.0, np.float32)
+        lab[h.nonground_indices(i)] = 0.0
+        lab[h.ground_indices(i)] = 1.0
+        labels.append(lab)
+        normals.append(h.normals(i))
+        centers.append(h.centers(i))
+    out = {"counts": counts, "state": state, "sample_frames": np.asarray(sample, np.float64), "labels": np.concatenate(labels),
+           "normals": np.concatenate(normals).reshape(-1, 3), "centers": np.concatenate(centers).reshape(-1, 3)}
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def hash_spot_check(h, kind, frame_of, ns):
@@ -532,19 +579,22 @@ def streams_workload(args, pwpp_hip, pwpp_dist, torch, dev, gpu_index, backend, 
         return t
 
     t = step()
-    counts = h.all_counts()
-    for s in range(S):
-        assert counts[s, 0] + counts[s, 1] + counts[s, 5] == ns_t[t][s], "partition property violated in stream %d" % s
+    if args.full:
+        counts = h.all_counts()
+        for s in range(S):
+            assert counts[s, 0] + counts[s, 1] + counts[s, 5] == ns_t[t][s], "partition property violated in stream %d" % s
     for _ in range(max(args.warmup, 1)):
-        step()
+        t = step()
     pwpp_dist.barrier(dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        t = step()
     torch.cuda.synchronize()
     pwpp_dist.barrier(dev)
     my_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(h, ns_t[t], args.dump_outputs)
     elapsed, total = pwpp_dist.aggregate(my_elapsed, S * args.steps, dev if backend == "nccl" else None)
     per_gpu = pwpp_dist.gather_values(S * args.steps / my_elapsed, dev if backend == "nccl" else None)
     heights = pwpp_dist.gather_values(h.state(0).sensor_height, dev if backend == "nccl" else None)
@@ -587,6 +637,13 @@ def main():
     ap.add_argument("--distinct-frames", type=int, default=1024, help="frames of the non-replayed leg (outside the timed region, N = 1 only; 0 = skip)")
     ap.add_argument("--skip-latency", action="store_true")
     ap.add_argument("--skip-extras", action="store_true", help="no parity_check / reference_order / ingest legs (all of them run outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the self-checks and every leg outside the timed region (parity anchor, synchronous, exact_moments_off, "
+                         "per-kernel times and roofline, latency, reference_order, ingest, dense, distinct, streams, cpu_baseline); "
+                         "a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (counts, state, a fixed sample of the frames' "
+                         "ground / non-ground labels, normals, centres) as DIR/<name>.npy, rank 0")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -663,29 +720,34 @@ def main():
         h.synchronize()
 
     held = {}  # which of the D batches each pipe handle processed last
+    last = [(h, 0)]  # the handle that ran the last step, and which of the D batches it was
 
     def run_steps(n):
         """n steps with up to D batches in flight; returns with every batch landed."""
         if D == 1:
             for _ in range(n):
                 step()
+            last[0] = (h, 0)
             return
         for k in range(n):
             holder = pipe.submit_device_batch(batches[k % D], cols=4)  # (waits for the batch this handle launched D submits ago)
             held[holder._h.value] = k % D
+            last[0] = (holder, k % D)
         pipe.drain()
 
+    selfcheck = args.full and not os.environ.get("PWPP_BENCH_NO_SELFCHECK")  # (perf-only experiments with deliberately wrong kernels)
     step()  # (one step for the checks below; the W warm-up steps run right in front of the timed region, after the host-side checks)
     # self-check: replays of the same source frame must produce identical counts, and
     # ground + non-ground must partition the frame (no reference data needed on the GPU box)
     counts = h.all_counts()
     n_patches = counts[:, 2]
-    for i in range(F if not os.environ.get("PWPP_BENCH_NO_SELFCHECK") else 0):  # (perf-only experiments with deliberately wrong kernels)
-        assert counts[i, 0] + counts[i, 1] + counts[i, 5] == ns[i], "partition property violated in frame %d" % i
-    by_src = {}
-    for i in range(F):
-        by_src.setdefault(which[i], set()).add(tuple(int(v) for v in counts[i, :3]))
-    assert os.environ.get("PWPP_BENCH_NO_SELFCHECK") or all(len(v) == 1 for v in by_src.values()), "replayed frames disagree: %r" % by_src
+    if selfcheck:
+        for i in range(F):
+            assert counts[i, 0] + counts[i, 1] + counts[i, 5] == ns[i], "partition property violated in frame %d" % i
+        by_src = {}
+        for i in range(F):
+            by_src.setdefault(which[i], set()).add(tuple(int(v) for v in counts[i, :3]))
+        assert all(len(v) == 1 for v in by_src.values()), "replayed frames disagree: %r" % by_src
 
     # Batches IN FLIGHT (round 5): the timed region keeps D = --in-flight batches enqueued -- D handles, each with its own input
     # buffers, workspace and stream, every one a full batch of F frames; step k goes to handle k mod D, which first waits for the
@@ -694,7 +756,7 @@ def main():
     # batch for the synchronous step with the in-handle overlap schedule (profiles/r05_pipelined_batches.txt).  Each handle runs
     # the plain single-stream schedule (the in-handle overlap schedule on top is slower: 2.83 ms).  D = 1: rounds 1-4's step.
     D = max(1, min(4, args.in_flight)) if F >= 128 and not args.no_overlap else 1
-    batches, inputs = [batch], [big]
+    batches, inputs, batch_ns = [batch], [big], [ns]
     for d in range(1, D):
         which_d = pwpp_dist.shard_sources(len(src), F, rank + d)  # (the same frames in another rotation: other buffers, other addresses)
         ns_d = [src[j].shape[0] for j in which_d]
@@ -703,18 +765,18 @@ def main():
         for i in range(F):
             big_d[offs_d[i]:offs_d[i + 1]].copy_(src_dev[which_d[i]])
         inputs.append(big_d)
+        batch_ns.append(ns_d)
         batches.append(h.make_device_batch([big_d.data_ptr() + int(offs_d[i]) * 16 for i in range(F)], ns_d))
     # the library's own pipe (pwpp_pipe_*: D handles, single-stream schedule each); H = [the first handle of the legs, the pipe's handles]
     pipe = pwpp_hip.Pipe(params, device=gpu_index, depth=D) if D > 1 else None
     H = [h] + ([pipe.handle(i) for i in range(D)] if pipe else [])
     torch.cuda.synchronize()
-    selfcheck = not os.environ.get("PWPP_BENCH_NO_SELFCHECK")
     # oracle anchor (outside the timed region): the ground masks and plane normals of batch frames 0-5 and
     # of one frame of the second frame range against the committed goldens, which tests/golden/make_golden.py generated
     # from the reference's own patchworkpp.cpp (oracle/_ref, eigen-f32 build).  Nothing under oracle/ is touched here.
     parity = None
     gpath = os.path.join(ROOT, "tests", "golden", "kitti_golden.npz")
-    if args.workload == "kitti" and data_name.startswith("kitti") and os.path.exists(gpath) and not args.skip_extras:
+    if args.full and args.workload == "kitti" and data_name.startswith("kitti") and os.path.exists(gpath) and not args.skip_extras:
         gold = np.load(gpath)
         picks = sorted(set(i for i in list(range(6)) + [F - 1 - (F // 4)] if 0 <= i < F))
         iou_min, dn_max = 1.0, 0.0
@@ -746,7 +808,9 @@ def main():
     elapsed = time.perf_counter() - t0
     my_elapsed = elapsed
     elapsed, total_frames = pwpp_dist.aggregate(elapsed, F * args.steps, dev if backend == "nccl" else None)  # MAX time, SUM frames over ranks
-    if D > 1:  # every handle's last batch is complete and equal to the first handle's first one, frame for frame of the same source
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0][0], batch_ns[last[0][1]], args.dump_outputs)
+    if D > 1 and selfcheck:  # every handle's last batch is complete and equal to the first handle's first one, frame for frame of the same source
         for d in range(D):
             if H[1 + d]._h.value not in held:
                 continue
@@ -755,10 +819,10 @@ def main():
             for i in range(F):
                 first_of.setdefault(which[i], i)
             for i in range(0, F, 37):
-                assert not selfcheck or tuple(cd[i, :3]) == tuple(counts[first_of[wd[i]], :3]), "handle %d frame %d differs from handle 0" % (d, i)
+                assert tuple(cd[i, :3]) == tuple(counts[first_of[wd[i]], :3]), "handle %d frame %d differs from handle 0" % (d, i)
     # the synchronous step of rounds 1-4 (launch, wait; the library's in-handle overlap schedule), for comparison across rounds
     sync_leg = None
-    if D > 1:
+    if D > 1 and args.full:
         for _ in range(3):
             step()
         torch.cuda.synchronize()
@@ -773,7 +837,7 @@ def main():
     # The same schedule with the plane-fit sums on rounds 3-5's 2^-21 m grid (option exact_moments = 0): what contract v4 -- sums exact
     # on the reference's own floats, the default -- costs.  Outside the timed region.
     exact_off = None
-    if D > 1 and not args.skip_extras:
+    if D > 1 and args.full and not args.skip_extras:
         p0 = pwpp_hip.Pipe(params, device=gpu_index, depth=D)
         for d in range(D):
             p0.handle(d).set_option("exact_moments", "0")
@@ -793,7 +857,7 @@ def main():
                              "reference by 1-31 indices on 0.2 % of varied frames (profiles/r06_parity_statistics_10k.json); the headline runs the default, exact_moments = 1"}
         p0.close()
     prof, prof_all = {}, {}
-    if not args.no_profile_events:  # kernel times of the single-stream schedule, outside the timed region
+    if args.full and not args.no_profile_events:  # kernel times of the single-stream schedule, outside the timed region
         # Two untimed steps first, then the MEDIAN of the steps' own values per kernel: the first launches of a kernel with scratch
         # memory on a stream that has not run it yet can take several milliseconds (queue-side scratch set-up) -- twice in five
         # runs of this round the small-patch fit kernel read 1.3-1.6 instead of 0.7 ms as a mean over five steps and became the
@@ -817,7 +881,7 @@ def main():
     # frame 0 alone was the best case) -- median of 30 calls per source, GPU time between HIP events on the library's stream
     lat_rows = []
     seen_src = []
-    for i in range(F):
+    for i in range(F if args.full and not args.skip_latency else 0):
         if which[i] not in seen_src:
             seen_src.append(which[i])
             one = h.make_device_batch(ptrs[i:i + 1], ns[i:i + 1])
@@ -845,7 +909,7 @@ def main():
 
     # reference-order output mode: the same batch with every sub-list in the reference's z-sorted order
     ref_order = None
-    if not args.skip_extras:
+    if args.full and not args.skip_extras:
         h.set_output_order(True)
         for _ in range(2):
             step()
@@ -861,28 +925,28 @@ def main():
     # ingest (PCIe-inclusive, never `value`): chunks of 256 frames from page-locked host slabs, two handles
     # double-buffered (H2D + pipeline of one chunk under the D2H of the other's index lists), rank 0 at N = 1 only
     ingest = None
-    if world == 1 and args.workload == "kitti" and not args.skip_extras:
+    if args.full and world == 1 and args.workload == "kitti" and not args.skip_extras:
         try:
             ingest = ingest_leg(pwpp_hip, src, gpu_index)
         except Exception as e:
             ingest = {"frames_per_s": None, "error": str(e)}
 
     dense = None
-    if world == 1 and args.workload == "kitti" and not args.skip_extras:
+    if args.full and world == 1 and args.workload == "kitti" and not args.skip_extras:
         try:
             dense = dense_leg(pwpp_hip, torch, dev, gpu_index, frames=args.dense_frames, distinct=args.dense_distinct)
         except Exception as e:
             dense = {"frames_per_s": None, "error": str(e)}
 
     distinct = None
-    if world == 1 and args.workload == "kitti" and not args.skip_extras and args.distinct_frames > 0:
+    if args.full and world == 1 and args.workload == "kitti" and not args.skip_extras and args.distinct_frames > 0:
         try:
             distinct = distinct_leg(pwpp_hip, torch, dev, gpu_index, frames=args.distinct_frames)
         except Exception as e:
             distinct = {"frames_per_s": None, "error": str(e)}
 
     streams = None
-    if world == 1 and args.workload == "kitti" and not args.skip_extras:
+    if args.full and world == 1 and args.workload == "kitti" and not args.skip_extras:
         try:
             streams = streams_leg(pwpp_hip, torch, dev, gpu_index, src_dev, [a.shape[0] for a in src])
         except Exception as e:
@@ -908,7 +972,8 @@ def main():
                                     ("%d batches in flight through the library's pipe (pwpp_pipe_*: one handle, workspace and stream per batch in flight; every step = one "
                                      "whole batch of %d frames; a handle's results stay readable until its next launch); each handle: one stream" % (D, F) if D > 1 else
                                      "library default: two frame ranges, binning and lists on the main stream, each range's plane fits on its own"))
-                                   + "; kernel_ms / roofline.kernel_ms: median over a separate single-stream pass of %d steps (after 2 untimed ones) outside the timed region" % args.profile_steps},
+                                   + ("; kernel_ms / roofline.kernel_ms: median over a separate single-stream pass of %d steps (after 2 untimed ones) outside the timed region"
+                                      % args.profile_steps if prof else "")},
             "binning": {"one_pass_batches": h.one_pass_stats()[0], "redone_two_pass": h.one_pass_stats()[1],
                         "one_pass_frames": h.redo_stats()[0], "redone_frames": h.redo_stats()[1],
                         "frames_with_parts_moved_into_the_arena": sum(hh.arena_stats()[0] for hh in H),
@@ -968,7 +1033,7 @@ def main():
                                "pipeline_frac_of_achievable": b_alg * args.steps / elapsed / 1e9 / 6290.0}
             out["kernel_ms"] = {k: v[0] / max(v[1], 1) for k, v in prof.items()}
             out["kernel_ms_min_max"] = {k: [v[0], v[-1]] for k, v in prof_all.items() if v and v[-1] > 0.02}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(src[:6])
             except Exception as e:  # the checker libs are optional at bench time

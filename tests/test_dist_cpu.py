@@ -87,8 +87,12 @@ def test_bench_memory_estimate_is_checked_before_any_collective():
     spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    a = types.SimpleNamespace(workload="kitti", in_flight=2, frames=1024, gpus=1, skip_extras=False, dense_frames=1024, distinct_frames=1024)
+    a = types.SimpleNamespace(workload="kitti", in_flight=2, frames=1024, gpus=1, full=True, skip_extras=False, dense_frames=1024,
+                              distinct_frames=1024)
     one = bench.estimate_memory_gb(a)
+    a.full = False  # a plain run holds the headline's buffers and handles only
+    assert 10.0 < bench.estimate_memory_gb(a) < 30.0
+    a.full = True
     a.gpus = 8
     eight = bench.estimate_memory_gb(a)
     assert 60.0 < one < 288.0 and 10.0 < eight < 30.0

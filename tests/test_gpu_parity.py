@@ -1605,7 +1605,7 @@ def test_bench_two_ranks_on_one_gpu():
         assert len(lines) == 1, out.stdout  # rank 0 alone prints
         return json.loads(lines[0])
 
-    d = run(192, [])
+    d = run(192, ["--full"])  # (parity_check, reference_order and the self-checks are --full legs)
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["scaling"] == "weak"
     assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 2 * 192) < 1e-6 * 2 * 192  # whole-job frames per step / max time
     assert "cpu_baseline" not in d and d["config"]["frames_per_gpu"] == 192
@@ -1625,6 +1625,53 @@ def test_bench_two_ranks_on_one_gpu():
     d = run(16, ["--workload", "dense", "--skip-extras"])
     assert d["n_gpus"] == 2 and d["config"]["frames_per_gpu"] == 16 and d["config"]["points_per_frame"] > 400000
     assert len(d["per_gpu"]) == 2 and "parity_check" not in d
+
+
+def test_bench_plain_run_and_dumped_outputs(golden, tmp_path):
+    """`bench.py --gpus 1` without --full prints the headline line and runs none of the legs outside the timed region; with
+    --dump-outputs it writes the last timed step's results as float .npy files (at most 64 MB): the same files from two runs with
+    the same arguments, the sampled frames' ground labels equal to the reference's masks of their source frames, and counts, labels
+    and patch rows that agree with each other."""
+    import json
+    import subprocess
+    import sys
+    import pwpp_dist
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    frames, steps = 256, 3
+    legs = {"parity_check", "synchronous", "exact_moments_off", "kernel_ms", "roofline", "latency", "reference_order", "ingest",
+            "dense", "distinct", "streams", "cpu_baseline"}
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--frames", str(frames), "--dump-outputs", str(out_dir)], cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"]
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - frames) < 1e-6 * frames
+        assert not legs & set(d) and d["selfcheck"] is False
+        a = {p.name[:-4]: np.load(p) for p in out_dir.glob("*.npy")}
+        assert set(a) == {"counts", "state", "sample_frames", "labels", "normals", "centers"}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+        dumps.append(a)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name], equal_nan=True), name
+    a = dumps[0]
+    counts, sample = a["counts"].astype(np.int64), a["sample_frames"].astype(np.int64)
+    assert counts.shape == (frames, 6) and a["state"].shape == (frames, 9) and 0 < len(sample) <= 64
+    # two batches in flight: step k ran batch k mod 2, whose buffers replay the six sources in rotation k mod 2
+    which = pwpp_dist.shard_sources(6, frames, (steps - 1) % 2)
+    at = 0
+    for i in sample:
+        n = int(counts[i, 0] + counts[i, 1] + counts[i, 5])
+        lab = a["labels"][at:at + n]
+        at += n
+        assert (lab == 1).sum() == counts[i, 0] and (lab == 0).sum() == counts[i, 1] and (lab == -1).sum() == counts[i, 5]
+        assert np.array_equal((lab == 1).astype(np.uint8), np.unpackbits(golden["f32/fresh/%d/ground_mask" % which[i]])[:n])
+    assert at == len(a["labels"])
+    assert a["normals"].shape == a["centers"].shape == (int(counts[sample, 2].sum()), 3)
 
 
 def test_bench_eight_ranks_on_one_gpu():

@@ -18,7 +18,9 @@ build, the product follows the reference's floats: equal to BOTH float builds (s
 The report goes to gpurun_out/ref_consensus.json (tracked copy: profiles/r04_ref_consensus.json).
 
 CPU part (-m "not gpu"): the same consensus logic on 12 frames with the CPU restatement of the contract standing in for the HIP
-path, so that the harness itself is covered where there is no GPU."""
+path, so that the harness itself is covered where there is no GPU; where oracle/_ref has not been built, against the three builds'
+ground sets recorded in tests/golden/ref_consensus_12.npz (tests/golden/make_ref_consensus.py)."""
+import hashlib
 import json
 import os
 
@@ -46,12 +48,20 @@ def reference_sets(pts):
     return out
 
 
-def judge(frames, product_sets):
-    """The consensus bookkeeping: returns the report; raises on a frame where the product leaves the reference's consensus."""
+def recorded_sets(i, pts):
+    """reference_sets(pts) of consensus_frame(i), i < 12, as tests/golden/make_ref_consensus.py recorded them from oracle/_ref."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_consensus_12.npz"))
+    assert g["md5"][i] == hashlib.md5(pts.tobytes()).hexdigest(), "consensus_frame(%d) is not the frame that was recorded" % i
+    return {name: np.flatnonzero(np.unpackbits(g["%s/%d" % (name, i)])[:pts.shape[0]]) for name, _ in FLAVOURS}
+
+
+def judge(frames, product_sets, sets=None):
+    """The consensus bookkeeping: returns the report; raises on a frame where the product leaves the reference's consensus.
+    sets(i, pts): the three builds' ground sets of frame i (default: run them, reference_sets)."""
     rep = {"frames": len(frames), "points": int(sum(f.shape[0] for f in frames)), "consensus_frames": 0, "split_frames": [],
            "product_equals_consensus": 0, "product_equals_exact_on_split_frames": 0, "consensus_misses": []}
     for i, (pts, mine) in enumerate(zip(frames, product_sets)):
-        ref = reference_sets(pts)
+        ref = sets(i, pts) if sets else reference_sets(pts)
         agree = np.array_equal(ref["eigen_f32"], ref["f32_packet4"]) and np.array_equal(ref["eigen_f32"], ref["exact_f64"])
         if agree:
             rep["consensus_frames"] += 1
@@ -80,7 +90,11 @@ def test_consensus_harness_with_the_restatement(oracle_built):
     frames = [consensus_frame(i) for i in range(12)]
     lib = ol.restatement()
     mine = [np.sort(ol.Estimator(lib, arith=ol.ARITH_FXP).run(f).ground_idx) for f in frames]
-    rep = judge(frames, mine)
+    built = all(ol.reference(arith) is not None for _, arith in FLAVOURS)
+    if built:  # the recorded sets are the builds' own
+        for i in (0, 6):
+            assert all(np.array_equal(a, b) for a, b in zip(recorded_sets(i, frames[i]).values(), reference_sets(frames[i]).values()))
+    rep = judge(frames, mine, None if built else recorded_sets)
     assert rep["consensus_frames"] + len(rep["split_frames"]) == 12
     assert all(min(d["product_vs_exact"], max(d["product_vs_f32"], d["product_vs_pk4"])) == 0 for d in rep["split_frames"]), rep
     assert rep["consensus_misses"] == [] and rep["product_equals_consensus"] == rep["consensus_frames"], rep["consensus_misses"]  # (frame 6 was v3's miss)
