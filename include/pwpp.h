@@ -201,7 +201,9 @@ PWPP_API int pwpp_get_counts(pwpp_handle *h, int frame, int32_t *n_ground, int32
 PWPP_API int pwpp_get_ground_indices(pwpp_handle *h, int frame, int32_t *out);
 PWPP_API int pwpp_get_nonground_indices(pwpp_handle *h, int frame, int32_t *out);
 /* getGround()/getNonground(), reference patchworkpp.h:157-158: row-major (count,3) float32,
- * rows aligned with the index getters above. */
+ * rows aligned with the index getters above.  The rows are gathered from the frame's input when these getters are
+ * called: after a PWPP_MEM_DEVICE call that input is the caller's device buffer, which must therefore still hold the
+ * frame (unchanged, not freed) when they run.  The index getters have no such need. */
 PWPP_API int pwpp_get_ground_xyz(pwpp_handle *h, int frame, float *out);
 PWPP_API int pwpp_get_nonground_xyz(pwpp_handle *h, int frame, float *out);
 /* getCenters()/getNormals(), reference patchworkpp.h:162-163: row-major (n_patches,3), bin traversal order */

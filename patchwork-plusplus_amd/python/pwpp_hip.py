@@ -79,6 +79,7 @@ def load():
         L.pwpp_estimate_ground.argtypes = [vp, vp, ci, ci, ci]
         L.pwpp_estimate_ground_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci]
         L.pwpp_estimate_ground_fields.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci]
+        L.pwpp_estimate_ground_fields_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci]
         L.pwpp_synchronize.argtypes = [vp]
         L.pwpp_set_num_streams.argtypes = [vp, ci]
         L.pwpp_get_counts.argtypes = [vp, ci, vp, vp, vp]
@@ -236,6 +237,15 @@ class Handle:
         self._keep = (cp, cn)
         self._check(self._L.pwpp_estimate_ground_batch(self._h, cp, cn, k, cols, layout, MEM_DEVICE, mode))
 
+    def submit_batch(self, ptrs, ns, cols, layout, mem, mode=MODE_FRESH):
+        """pwpp_estimate_ground_batch as it stands: frames by address (ints) in any layout and memory kind.  The memory must stay
+        valid and unchanged until synchronize() unless mem is MEM_HOST."""
+        k = len(ptrs)
+        cp = (ctypes.c_void_p * k)(*ptrs)
+        cn = (ctypes.c_int32 * k)(*ns)
+        self._keep = (cp, cn)
+        self._check(self._L.pwpp_estimate_ground_batch(self._h, cp, cn, k, cols, layout, mem, mode))
+
     def make_device_batch(self, ptrs, ns):
         """Pre-built ctypes argument arrays for repeated launches of the same batch."""
         k = len(ptrs)
@@ -310,6 +320,23 @@ class Handle:
         buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
         self._keep = buf
         self._check(self._L.pwpp_estimate_ground_fields(self._h, _vp(buf), n, point_step, off_x, off_y, off_z, off_intensity))
+
+    def estimate_ground_fields_batch(self, datas, ns, point_step, off_x, off_y, off_z, off_intensity=-1, mem=MEM_HOST,
+                                     mode=MODE_FRESH):
+        """Many PointCloud2 data blobs in one call (pwpp_estimate_ground_fields_batch).  MEM_HOST / MEM_HOST_PINNED: `datas` are
+        numpy byte buffers (pinned_empty for MEM_HOST_PINNED); MEM_DEVICE: device addresses (ints), as in
+        estimate_ground_batch_device.  Asynchronous unless mem is MEM_HOST: synchronize() before reading results."""
+        k = len(datas)
+        if mem == MEM_DEVICE:
+            addrs = [int(d) for d in datas]
+        else:
+            datas = [np.frombuffer(d, np.uint8) if not isinstance(d, np.ndarray) else d for d in datas]
+            addrs = [d.ctypes.data for d in datas]
+        cp = (ctypes.c_void_p * k)(*addrs)
+        cn = (ctypes.c_int32 * k)(*ns)
+        self._keep = (cp, cn, datas)
+        self._check(self._L.pwpp_estimate_ground_fields_batch(self._h, cp, cn, k, point_step, off_x, off_y, off_z, off_intensity,
+                                                              mem, mode))
 
     def set_history(self, stream, which, ring, values):
         v = np.ascontiguousarray(values, np.float64)

@@ -28,8 +28,10 @@ PLANS = ["", "", "", "W16:1023,W64.2:65535", "W16.16:1023,S64:65535", "S16:255,S
          "W16.32:511,W64.4:65535", "H64:255", "S16:100", "W16:255,W64.8:65535"]
 
 
-def random_params(rng):
-    p = pwpp_hip.default_params()
+def random_params(rng, p=None):
+    """Draws a parameter set into `p` (default: pwpp_hip.default_params(); any structure with the same field names will do,
+    e.g. the oracle's, where the HIP library is not there)."""
+    p = pwpp_hip.default_params() if p is None else p
     if rng.random() < 0.3:
         p.enable_RNR = int(rng.integers(0, 2))
     if rng.random() < 0.3:
