@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define PWPP_VERSION_MAJOR 0
-#define PWPP_VERSION_MINOR 2 /* round 6: pwpp_pipe_submit takes a mode; pwpp_pipe_set_num_streams, pwpp_get_arena_stats; options exact_moments, split_k5 */
+#define PWPP_VERSION_MINOR 3 /* per-point labels (pwpp_set_labels, pwpp_get_*labels), PWPP_ORDER_CLOUD */
 
 typedef enum pwpp_status {
     PWPP_OK = 0,
@@ -304,8 +304,21 @@ PWPP_API int pwpp_get_fxp_origins(pwpp_handle *h, float *out_xy, int capacity_bi
  *                        the rest, each ascending in z; small bins / RNR / out-of-range in cloud order.
  *                        Equal z: cloud order (the reference's std::sort leaves ties unspecified).
  * Applies to the batches launched after the call. */
-enum { PWPP_ORDER_SCATTER = 0, PWPP_ORDER_REFERENCE = 1 };
+enum { PWPP_ORDER_SCATTER = 0, PWPP_ORDER_REFERENCE = 1, PWPP_ORDER_CLOUD = 2 };
 PWPP_API int pwpp_set_output_order(pwpp_handle *h, int order);
+/*   PWPP_ORDER_CLOUD     both lists in ascending cloud index (no per-patch layout): a function of the input alone.
+ *                        Implies labels (below).  Every list getter, pwpp_get_all_indices and the device view follow it. */
+
+/* ---- per-point labels (batches launched after pwpp_set_labels(h, 1) or with PWPP_ORDER_CLOUD) --------------------------
+ * One byte per point, cloud order, laid out like the index lists (frame f at frame_base[f]).  UNCLASSIFIED = in neither
+ * list: the reference's skip marker z == FLT_MIN (n_dropped).  RNR and out-of-range points are NONGROUND.  Computed on the
+ * device behind the lists; their time counts in the k_emit slot of the kernel profile.  The getters return PWPP_E_STATE
+ * when the last call ran without labels.  A pipe's handles take this and the order through pwpp_pipe_handle. */
+enum { PWPP_LABEL_NONGROUND = 0, PWPP_LABEL_GROUND = 1, PWPP_LABEL_UNCLASSIFIED = 2 };
+PWPP_API int pwpp_set_labels(pwpp_handle *h, int on);
+PWPP_API int pwpp_get_labels(pwpp_handle *h, int frame, uint8_t *out);          /* n bytes of frame `frame` */
+PWPP_API int pwpp_get_all_labels(pwpp_handle *h, uint8_t *out);                 /* the whole batch in ONE copy */
+PWPP_API int pwpp_get_device_labels(pwpp_handle *h, const uint8_t **out);      /* device pointer; frame_base as in the device view */
 
 /* Overlap mode (ON by default): batches of 128 frames or more are processed as two frame ranges -- binning
  * and index lists of both on the handle's main stream, each range's plane fits on a stream of its own -- so

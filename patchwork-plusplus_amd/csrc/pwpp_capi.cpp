@@ -190,6 +190,10 @@ struct pwpp_handle {
     DevBuf<unsigned long long> d_ord_a, d_ord_b;  // scratch of the reference-order mode (long sub-lists)
     DevBuf<uint32_t> d_ord_work;                  // ... and its work lists: the sub-lists above 256 entries of every frame
     int output_order = PWPP_ORDER_SCATTER;
+    bool labels = false;            // pwpp_set_labels (PWPP_ORDER_CLOUD implies them)
+    bool labels_last = false;       // the last call ran with labels
+    DevBuf<uint8_t> d_labels;       // [total points + 16] one PWPP_LABEL_* per point, laid out like d_out
+    DevBuf<uint32_t> d_label_tiles; // PWPP_ORDER_CLOUD: [frames][tiles per frame] counts of the compaction (PwppBatch.label_tiles)
     DevBuf<uint32_t> d_bins;   // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
     DevBuf<uint32_t> d_parts;  // TWO copies of 3 slabs of frames*(2B+2): part_count, part_off, part_cursor (pwpp_dev.h: a bin is stored in two
                                // parts); a call works on one copy while its K5 zeroes the other for the next call (PwppBatch.next_part_count)
@@ -480,6 +484,9 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt);
 // on a 16-byte boundary too (3 x frames x parts + 4 is 8 mod 16 bytes for a single frame of the default CZM).
 inline size_t counters_copy_words(size_t slab_words) { return (3 * slab_words + 4 + 3) & ~(size_t)3; }
 
+bool labels_on(const pwpp_handle *h) { return h->labels || h->output_order == PWPP_ORDER_CLOUD; }
+int64_t label_tile_stride(int max_n) { return ((int64_t)max_n + 15 + PWPP_LABEL_TILE - 1) / PWPP_LABEL_TILE; }
+
 int read_observed(pwpp_handle *h) {
     const size_t NB = (size_t)PWPP_NUM_PARTS(h->dp.num_bins);
     h->observed.resize(NB);
@@ -607,6 +614,15 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt) {
     bt.results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
     bt.results_host = h->h_results.p;  // hipHostMalloc'ed: the same address on the device
     bt.dbg = h->d_dbg.p;
+    if (labels_on(h)) {
+        bt.labels = h->d_labels.p;
+        bt.label_first = 0;
+        bt.label_count = h->h_base.p[h->frames];
+        if (h->output_order == PWPP_ORDER_CLOUD) {
+            bt.label_tiles = h->d_label_tiles.p;
+            bt.label_tile_stride = (int32_t)label_tile_stride(h->max_n);
+        }
+    }
 
     bt.bin_max = h->d_bin_max.p;
     bt.arena_base = 0xffffffffu;  // (launch_prepared sets the arena of a one-pass batch)
@@ -663,6 +679,11 @@ PwppBatch frame_range(const pwpp_handle *h, const PwppBatch &bt, int f0, int nf)
     v.results_host += f0;
     if (v.order_work) v.order_work += (size_t)f0 * (size_t)(1 + 2 * NB);
     if (v.arena_tag) v.arena_tag += (size_t)f0 * v.arena_spill;
+    if (v.labels) {
+        v.label_first = h->h_base.p[f0];
+        v.label_count = h->h_base.p[f0 + nf] - h->h_base.p[f0];
+    }
+    if (v.label_tiles) v.label_tiles += (size_t)f0 * (size_t)v.label_tile_stride;
     v.next_part_count += (size_t)f0 * NP;  // (the other copy: same frame, same slab stride)
     v.next_results += f0;
     return v;
@@ -1394,6 +1415,11 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
         if ((rc = h->d_ord_b.ensure(tp))) return rc;
         if ((rc = h->d_ord_work.ensure((size_t)frames * (size_t)(1 + 2 * NB)))) return rc;
     }
+    if (labels_on(h)) {  // (16 bytes of slack: the label kernels read whole 16-byte pieces)
+        if ((rc = h->d_labels.ensure(tp + 16))) return rc;
+        if (h->output_order == PWPP_ORDER_CLOUD && (rc = h->d_label_tiles.ensure((size_t)frames * (size_t)label_tile_stride(max_n)))) return rc;
+    }
+    h->labels_last = labels_on(h);
     if ((rc = h->d_bins.ensure((size_t)frames * NB * 4))) return rc;
     if ((rc = h->d_parts.ensure(2 * counters_copy_words((size_t)frames * NP)))) return rc;  // two copies
     if ((rc = h->d_recs.ensure((size_t)frames * B))) return rc;
@@ -2028,7 +2054,8 @@ int64_t pwpp_get_workspace_bytes(pwpp_handle *h) {
            b(h->d_recs.cap, sizeof(PwppPatchRec)) + b(h->d_centers.cap, 4) + b(h->d_normals.cap, 4) + b(h->d_results.cap, sizeof(PwppFrameResult)) +
            b(h->d_xyz.cap, 4) + b(h->d_dbg.cap, 8) + b(h->d_st_stream.cap, sizeof(PwppStateScalar)) + b(h->d_st_fresh.cap, sizeof(PwppStateScalar)) +
            b(h->d_st_snap.cap, sizeof(PwppStateScalar)) + b(h->d_hist_stream.cap, 8) + b(h->d_hist_fresh.cap, 8) + b(h->d_hist_snap.cap, 8) +
-           b(h->d_pl_stream.cap, sizeof(PwppPlaneState)) + b(h->d_pl_fresh.cap, sizeof(PwppPlaneState)) + b(h->d_pl_snap.cap, sizeof(PwppPlaneState));
+           b(h->d_pl_stream.cap, sizeof(PwppPlaneState)) + b(h->d_pl_fresh.cap, sizeof(PwppPlaneState)) + b(h->d_pl_snap.cap, sizeof(PwppPlaneState)) +
+           b(h->d_labels.cap, 1) + b(h->d_label_tiles.cap, 4);
 }
 
 int pwpp_trim_workspace(pwpp_handle *h) {
@@ -2050,6 +2077,8 @@ int pwpp_trim_workspace(pwpp_handle *h) {
     h->d_ord_a.release();
     h->d_ord_b.release();
     h->d_ord_work.release();
+    h->d_labels.release();
+    h->d_label_tiles.release();
     h->d_xyz.release();
     h->d_frames.release();
     h->d_frames_probe.release();
@@ -2075,11 +2104,57 @@ int pwpp_trim_workspace(pwpp_handle *h) {
 
 int pwpp_set_output_order(pwpp_handle *h, int order) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
-    if (order != PWPP_ORDER_SCATTER && order != PWPP_ORDER_REFERENCE) return fail(PWPP_E_ARG, "bad order %d", order);
+    if (order != PWPP_ORDER_SCATTER && order != PWPP_ORDER_REFERENCE && order != PWPP_ORDER_CLOUD) return fail(PWPP_E_ARG, "bad order %d", order);
     int rc = use_device(h);
     if (rc) return rc;
     if ((rc = finish_pending(h))) return rc;
     h->output_order = order;
+    return PWPP_OK;
+}
+
+int pwpp_set_labels(pwpp_handle *h, int on) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    int rc = use_device(h);
+    if (rc) return rc;
+    if ((rc = finish_pending(h))) return rc;
+    h->labels = on != 0;
+    return PWPP_OK;
+}
+
+// the labels of the last call: its results, and labels among them
+static int check_labels(pwpp_handle *h) {
+    if (!h->labels_last) return fail(PWPP_E_STATE, "the last call ran without labels (pwpp_set_labels, PWPP_ORDER_CLOUD)");
+    return PWPP_OK;
+}
+
+int pwpp_get_labels(pwpp_handle *h, int frame, uint8_t *out) {
+    int rc = check_frame(h, frame);
+    if (rc || (rc = check_labels(h))) return rc;
+    const int64_t base = h->h_base.p[frame], n = h->h_base.p[frame + 1] - base;
+    if (n > 0) {
+        if (!out) return fail(PWPP_E_ARG, "null output");
+        HIPCHK(hipMemcpy(out, h->d_labels.p + base, (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return PWPP_OK;
+}
+
+int pwpp_get_all_labels(pwpp_handle *h, uint8_t *out) {
+    int rc = check_frame(h, 0);
+    if (rc || (rc = check_labels(h))) return rc;
+    const int64_t total = h->h_base.p[h->frames];
+    if (total > 0) {
+        if (!out) return fail(PWPP_E_ARG, "null output");
+        HIPCHK(hipMemcpyAsync(out, h->d_labels.p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return PWPP_OK;
+}
+
+int pwpp_get_device_labels(pwpp_handle *h, const uint8_t **out) {
+    if (!h || !out) return fail(PWPP_E_ARG, "null argument");
+    int rc = check_frame(h, 0);
+    if (rc || (rc = check_labels(h))) return rc;
+    *out = h->d_labels.p;
     return PWPP_OK;
 }
 

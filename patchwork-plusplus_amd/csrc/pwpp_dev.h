@@ -44,6 +44,7 @@
 // live PWPP_MEMBER_PAD * parts bytes further on in the membership plane (the moved parts are placed in part order, so the plane's
 // "slot / 8 + pad * part" addressing stays collision-free): pwpp_member_offset.
 #define PWPP_MAX_RELOC 64
+#define PWPP_LABEL_TILE 4096      // labels per tile of the cloud-order compaction (256 lanes x 16 bytes)
 #define PWPP_EMIT_LONG_BLOCKS 8   // blocks of 512 list entries the main wave of a "long" bin copies in k_emit; the rest goes to the extra waves
 #define PWPP_EMIT_LONG_MIN 8192   // a bin whose count has exceeded this in some frame of the handle is "long"
 
@@ -201,7 +202,13 @@ struct PwppBatch {
     int fuse_scan;               // a few frames: K2 inside K1' (the last workgroup of a frame to take a ticket scans) instead of a kernel of its own
     int k5_split;                // K5 in two launches (k_gle_tgr PART 1 / 2): the second on the handle's other stream, joined by the host before the next call
     unsigned long long *dbg;     // [64] timing probes, only written when debug & 4
+    // Per-point labels (pwpp_set_labels, PWPP_ORDER_CLOUD), written behind the lists of this launch's frames; null = off
+    uint8_t *labels;             // [total points] laid out like out_idx: PWPP_LABEL_* of point i of frame f at fd.base + i
+    uint32_t *label_tiles;       // PWPP_ORDER_CLOUD: [frames][label_tile_stride] ground | non-ground << 16 of every tile of
+                                 // PWPP_LABEL_TILE labels (tile 0 starts at fd.base rounded down to 16); null = no reordering
+    int32_t label_tile_stride;   // tiles per frame of the whole call (its largest frame)
     // host side only (the kernels never read these)
+    int64_t label_first, label_count;  // the slots of this launch's frames (contiguous: the memset to UNCLASSIFIED)
     const char *fit_plan;        // option "fit_plan": overrides the plan pwpp_launch_fit would choose; null or empty = automatic
     int32_t plan_frames;         // frames the automatic fit plan is chosen for: the WHOLE call's when this batch is one of its frame ranges (0: num_frames)
     int32_t fit_concurrent;      // option "fit_concurrent": the classes of a plan side by side on two streams

@@ -16,6 +16,7 @@
 //   K6  k_emit             ground / non-ground index lists                       (ref :28-31, :18-26);
 //                          mirrors the frame counters into pinned host memory
 //   K7  k_order_sublists   optional: the reference's order inside every part of the lists
+//   K8  k_label_*          optional: per-point labels from the final lists; cloud-order lists from the labels
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -2576,7 +2577,169 @@ __global__ __launch_bounds__(kBlock) void k_gather_xyz(PwppFrameDesc fd, const i
     out[(size_t)j * 3 + 2] = z;
 }
 
+// ------------------------------------------------------------------------------------------
+// K8 (optional)  per-point labels and the cloud-order lists (pwpp_set_labels, PWPP_ORDER_CLOUD)
+// ------------------------------------------------------------------------------------------
+// Behind the final lists of a launch's frames: fill their label bytes with UNCLASSIFIED, scatter the two lists into them,
+// and for cloud order rewrite the lists from the labels in two launches -- ground / non-ground counts per tile of
+// PWPP_LABEL_TILE labels, then every tile adds up the tiles in front of it and writes its entries.  No atomics and no
+// workgroup waits for another (a look-back would need an agent-scope release per tile: the XCDs' L2s are not coherent),
+// so the lists are a function of the labels alone.  A frame whose lists are not written yet (K5 left it for the host's
+// fix-up, or it is binned again after a segment overflow) gets labels from whatever its slots hold: every index and
+// every position is bounds-checked against the frame, and the frame is labelled again when its lists are written.
+constexpr int kLabelBlock = 256;
+static_assert(PWPP_LABEL_TILE == kLabelBlock * 16, "a tile is 16 labels per lane");
+
+// the slots [first, first + count) of the launch's frames (contiguous) = UNCLASSIFIED; 16 bytes per lane
+__global__ __launch_bounds__(kLabelBlock) void k_label_fill(uint8_t *labels, int64_t first, int64_t count) {
+    const int64_t end = first + count, p0 = (first & ~(int64_t)15) + 16 * ((int64_t)blockIdx.x * kLabelBlock + threadIdx.x);
+    if (p0 >= end) return;
+    if (p0 >= first && p0 + 16 <= end) {
+        const uint32_t u = 0x01010101u * PWPP_LABEL_UNCLASSIFIED;
+        *reinterpret_cast<uint4 *>(labels + p0) = make_uint4(u, u, u, u);
+    } else {
+        for (int k = 0; k < 16; ++k)
+            if (p0 + k >= first && p0 + k < end) labels[p0 + k] = (uint8_t)PWPP_LABEL_UNCLASSIFIED;
+    }
+}
+
+// n_ground / n_nonground of a frame, clamped to the frame (see above)
+__device__ __forceinline__ void label_counts(const PwppBatch &Bt, int f, int64_t n, int64_t &ng, int64_t &nn) {
+    const PwppFrameResult r = Bt.results[f];
+    ng = r.n_ground < 0 ? 0 : (r.n_ground > n ? n : (int64_t)r.n_ground);
+    nn = r.n_nonground < 0 ? 0 : (r.n_nonground > n - ng ? n - ng : (int64_t)r.n_nonground);
+}
+
+// labels[base + idx] for every entry of the two lists: 16-byte loads of the lists (from base rounded down to 4 entries)
+__global__ __launch_bounds__(kLabelBlock) void k_label_scatter(PwppBatch Bt) {
+    const int f = blockIdx.y;
+    const PwppFrameDesc fd = Bt.frames[f];
+    const int64_t n = fd.n;
+    int64_t ng, nn;
+    label_counts(Bt, f, n, ng, nn);
+    const int64_t lo = fd.base, hi = fd.base + ng + nn, a4 = lo & ~(int64_t)3;
+    uint8_t *lab = Bt.labels + fd.base;
+    int v[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t p0 = a4 + 4 * ((int64_t)(blockIdx.x * 4 + u) * kLabelBlock + threadIdx.x);
+        if (p0 >= lo && p0 + 4 <= hi) {
+            const int4 q = *reinterpret_cast<const int4 *>(Bt.out_idx + p0);
+            v[u][0] = q.x;
+            v[u][1] = q.y;
+            v[u][2] = q.z;
+            v[u][3] = q.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[u][k] = p0 + k >= lo && p0 + k < hi ? Bt.out_idx[p0 + k] : -1;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t p0 = a4 + 4 * ((int64_t)(blockIdx.x * 4 + u) * kLabelBlock + threadIdx.x);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (v[u][k] >= 0 && v[u][k] < n && p0 + k >= lo)
+                lab[v[u][k]] = (uint8_t)(p0 + k - lo < ng ? PWPP_LABEL_GROUND : PWPP_LABEL_NONGROUND);
+    }
+}
+
+// the 16 labels of a lane at p0 (16-byte aligned) as two bit masks: bit k = point p0 + k of the frame [lo, end) is ground / non-ground
+__device__ __forceinline__ void label_masks(const uint8_t *labels, int64_t p0, int64_t lo, int64_t end, unsigned &gm, unsigned &nm) {
+    gm = nm = 0u;
+    if (p0 >= end) return;
+    const uint4 q = *reinterpret_cast<const uint4 *>(labels + p0);
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const unsigned b = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        const bool in = p0 + k >= lo && p0 + k < end;
+        gm |= (unsigned)(in && b == PWPP_LABEL_GROUND) << k;
+        nm |= (unsigned)(in && b == PWPP_LABEL_NONGROUND) << k;
+    }
+}
+
+// cloud order, launch 1: ground | non-ground << 16 of every tile of a frame (tile t = PWPP_LABEL_TILE labels from base rounded
+// down to 16, + t tiles)
+__global__ __launch_bounds__(kLabelBlock) void k_label_tiles(PwppBatch Bt) {
+    __shared__ unsigned s_tot[kLabelBlock / 64];
+    const int f = blockIdx.y, t = blockIdx.x;
+    const PwppFrameDesc fd = Bt.frames[f];
+    const int64_t lo = fd.base, end = fd.base + fd.n;
+    unsigned gm, nm;
+    label_masks(Bt.labels, (lo & ~(int64_t)15) + (int64_t)t * PWPP_LABEL_TILE + 16 * threadIdx.x, lo, end, gm, nm);
+    const unsigned s = wave_sum_u32((unsigned)__popc(gm) | ((unsigned)__popc(nm) << 16));  // (at most 4096 each: no carry)
+    if (lane_id() == 0) s_tot[wave_id()] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) Bt.label_tiles[(size_t)f * Bt.label_tile_stride + t] = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+}
+
+// cloud order, launch 2: every wave takes 1024 labels of its tile (16 per lane), ranks its entries with a prefix sum over the
+// lanes, stages them in LDS (ground from the front, non-ground from the back) and writes both runs as whole lines to
+// out_idx[base + ground before], out_idx[base + n_ground + non-ground before].  Rewrites the lists in place: it reads only labels.
+__global__ __launch_bounds__(kLabelBlock) void k_label_compact(PwppBatch Bt) {
+    __shared__ unsigned s_tot[kLabelBlock / 64];
+    __shared__ int s_stage[kLabelBlock / 64][1024];
+    const int f = blockIdx.y, t = blockIdx.x;
+    const PwppFrameDesc fd = Bt.frames[f];
+    const int64_t n = fd.n, lo = fd.base, end = fd.base + fd.n;
+    const int64_t tile0 = (lo & ~(int64_t)15) + (int64_t)t * PWPP_LABEL_TILE;
+    if (tile0 >= end) return;  // (the whole workgroup: beyond the frame)
+    int64_t ng_total, nn_total;
+    label_counts(Bt, f, n, ng_total, nn_total);
+    const int w = wave_id(), L = lane_id();
+    unsigned gb = 0u, nb = 0u;  // the tiles in front of this one
+    for (int j = L; j < t; j += 64) {
+        const unsigned c = Bt.label_tiles[(size_t)f * Bt.label_tile_stride + j];
+        gb += c & 0xffffu;
+        nb += c >> 16;
+    }
+    gb = wave_sum_u32(gb);
+    nb = wave_sum_u32(nb);
+    const int64_t p0 = tile0 + (int64_t)w * 1024 + 16 * L;
+    unsigned gm, nm;
+    label_masks(Bt.labels, p0, lo, end, gm, nm);
+    const unsigned c = (unsigned)__popc(gm) | ((unsigned)__popc(nm) << 16);
+    const unsigned incl = wave_incl_scan(c), tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+    unsigned gr = (incl - c) & 0xffffu, nr = (incl - c) >> 16;
+    int *stage = s_stage[w];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (gm >> k & 1u) stage[gr++] = (int)(p0 + k - lo);
+        else if (nm >> k & 1u) stage[1023u - (nr++)] = (int)(p0 + k - lo);
+    }
+    if (L == 0) s_tot[w] = tot;
+    __syncthreads();
+    for (int j = 0; j < w; ++j) {
+        gb += s_tot[j] & 0xffffu;
+        nb += s_tot[j] >> 16;
+    }
+    int *out = Bt.out_idx + lo;
+    const unsigned my_g = tot & 0xffffu, my_n = tot >> 16;
+    for (unsigned i = L; i < my_g; i += 64)
+        if ((int64_t)gb + i < n) out[(int64_t)gb + i] = stage[i];
+    for (unsigned i = L; i < my_n; i += 64)
+        if (ng_total + nb + i < n) out[ng_total + nb + i] = stage[1023u - i];
+}
+
 }  // namespace
+
+// the labels of the launch's frames, behind their final lists (and the cloud order of the lists when B.label_tiles is set)
+static void launch_labels(const PwppBatch &B, hipStream_t stream) {
+    const int F = B.num_frames;
+    if (B.label_count > 0) {
+        const int64_t lanes = ((B.label_first & 15) + B.label_count + 15) / 16;
+        hipLaunchKernelGGL(k_label_fill, dim3((unsigned)((lanes + kLabelBlock - 1) / kLabelBlock)), dim3(kLabelBlock), 0, stream,
+                           B.labels, B.label_first, B.label_count);
+    }
+    const unsigned gs = (unsigned)(((int64_t)B.max_n + 3 + 4 * 4 * kLabelBlock - 1) / (4 * 4 * kLabelBlock));
+    hipLaunchKernelGGL(k_label_scatter, dim3(gs, F), dim3(kLabelBlock), 0, stream, B);
+    if (B.label_tiles) {
+        const unsigned gt = (unsigned)(((int64_t)B.max_n + 15 + PWPP_LABEL_TILE - 1) / PWPP_LABEL_TILE);
+        hipLaunchKernelGGL(k_label_tiles, dim3(gt, F), dim3(kLabelBlock), 0, stream, B);
+        hipLaunchKernelGGL(k_label_compact, dim3(gt, F), dim3(kLabelBlock), 0, stream, B);
+    }
+}
 
 extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, int count, float *out, hipStream_t stream) {
     if (count <= 0) return 0;
@@ -2645,7 +2808,7 @@ extern "C" int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream)
     return (int)hipGetLastError();
 }
 
-// stages: bit 0 = binning (K0-K3), bit 1 = plane fits + K5, bit 2 = index lists (K6, K7); the overlap schedule of
+// stages: bit 0 = binning (K0-K3), bit 1 = plane fits + K5, bit 2 = index lists (K6, K7, K8); the overlap schedule of
 // pwpp_capi.cpp launches the stages of a frame range on different streams.  Bit 3 (with bit 1): k_fit_fixup instead of the
 // fit kernels -- the host finishing a frame whose patches needed the plane fitted before them (batch->fixup_run set).
 extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev /* PWPP_NUM_KERNELS + 1 events or null */,
@@ -2734,13 +2897,17 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
             if (order_a) hipLaunchKernelGGL((k_emit<false, true>), lgrid, dim3(kEmitBlock), 0, stream, L, order_a);
             else hipLaunchKernelGGL((k_emit<false, false>), lgrid, dim3(kEmitBlock), 0, stream, L, order_a);
         }
-        if (ev) (void)hipEventRecord(ev[11], stream);
+        if (ev && !B.labels) (void)hipEventRecord(ev[11], stream);
         if (order_a) {
             hipLaunchKernelGGL((k_order_sublists<64, 256, 0>), dim3(NB, F), dim3(64), 0, stream, B, order_a, order_b);
             // the lists above 256 entries: a work list per frame, then one workgroup per item (at most points / 257 + the two a bin can add)
             const unsigned max_items = (unsigned)(B.max_n / 257 + 2) < 2u * (unsigned)NB ? (unsigned)(B.max_n / 257 + 2) : 2u * (unsigned)NB;
             hipLaunchKernelGGL(k_order_worklist, dim3(F), dim3(kBlock), 0, stream, B, 256);
             hipLaunchKernelGGL((k_order_sublists<PWPP_ORDER_BLOCK, 4096, 256>), dim3(max_items, F), dim3(PWPP_ORDER_BLOCK), 0, stream, B, order_a, order_b);
+        }
+        if (B.labels) {  // behind the final lists (K7's, in reference order); profiled in k_emit's slot
+            launch_labels(B, stream);
+            if (ev) (void)hipEventRecord(ev[11], stream);
         }
     }
     return (int)hipGetLastError();

@@ -153,6 +153,19 @@ private:
     std::vector<int32_t> v_;
 };
 
+// one PWPP_LABEL_* byte per point (getLabels without Eigen)
+class Labels {
+public:
+    Labels() {}
+    explicit Labels(int rows) : v_((size_t)rows) {}
+    int rows() const { return (int)v_.size(); }
+    uint8_t operator()(int i) const { return v_[(size_t)i]; }
+    uint8_t *data() { return v_.data(); }
+    const uint8_t *data() const { return v_.data(); }
+private:
+    std::vector<uint8_t> v_;
+};
+
 // reference patchworkpp.h:114-163
 class PatchWorkpp {
 public:
@@ -215,6 +228,21 @@ public:
     // extension: true = the points of a patch come out in the reference's own order (bins sorted by z,
     // patchworkpp.cpp:199) instead of the scatter order; same sets either way (pwpp.h, pwpp_set_output_order)
     void setReferenceOrder(bool on) { check(pwpp_set_output_order(h_, on ? PWPP_ORDER_REFERENCE : PWPP_ORDER_SCATTER)); }
+    // extension: true = both index lists in ascending cloud index (implies labels); false = scatter order
+    void setCloudOrder(bool on) { check(pwpp_set_output_order(h_, on ? PWPP_ORDER_CLOUD : PWPP_ORDER_SCATTER)); }
+    // extension: one PWPP_LABEL_* per point of the frames estimated afterwards (getLabels)
+    void setLabels(bool on) { check(pwpp_set_labels(h_, on ? 1 : 0)); }
+#if defined(PWPP_HAVE_EIGEN) && defined(EIGEN_WORLD_VERSION)  // (a partial Eigen API without Eigen::Matrix gets Labels)
+    Eigen::Matrix<uint8_t, Eigen::Dynamic, 1> getLabels() {
+        const Labels l = labels();
+        Eigen::Matrix<uint8_t, Eigen::Dynamic, 1> m(l.rows());
+        for (int i = 0; i < l.rows(); ++i) m(i) = l(i);
+        return m;
+    }
+#else
+    Labels getLabels() { return labels(); }
+#endif
+    Labels labelList() { return labels(); }
 
 #ifdef PWPP_HAVE_EIGEN
     // the reference's return types (fresh objects on every call, as the reference's toEigenCloud / toIndices, :8-26)
@@ -286,6 +314,13 @@ private:
         Indices v(ground ? g : n);
         check(ground ? pwpp_get_ground_indices(h_, 0, v.data()) : pwpp_get_nonground_indices(h_, 0, v.data()));
         return v;
+    }
+    Labels labels() {
+        pwpp_device_view v;
+        check(pwpp_get_device_view(h_, &v));
+        Labels l((int)(v.frame_base[1] - v.frame_base[0]));
+        check(pwpp_get_labels(h_, 0, l.data()));
+        return l;
     }
     Cloud rows(bool centers) {
         int32_t g, n, p;

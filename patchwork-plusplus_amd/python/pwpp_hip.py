@@ -18,6 +18,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 MODE_FRESH, MODE_STREAMS = 0, 1
 MEM_HOST_PINNED = 2
 NUM_KERNELS = 11
+ORDER_SCATTER, ORDER_REFERENCE, ORDER_CLOUD = 0, 1, 2
+LABEL_NONGROUND, LABEL_GROUND, LABEL_UNCLASSIFIED = 0, 1, 2
 
 DEC_NAMES = {1: "not_upright", 2: "far_ground", 3: "heading", 4: "ground", 5: "tgr_reject", 6: "tgr_revert"}
 
@@ -126,6 +128,10 @@ def load():
         L.pwpp_pipe_destroy.argtypes = [vp]
         L.pwpp_set_output_order.argtypes = [vp, ci]
         L.pwpp_set_overlap.argtypes = [vp, ci]
+        L.pwpp_set_labels.argtypes = [vp, ci]
+        L.pwpp_get_labels.argtypes = [vp, ci, vp]
+        L.pwpp_get_all_labels.argtypes = [vp, vp]
+        L.pwpp_get_device_labels.argtypes = [vp, ctypes.POINTER(vp)]
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
@@ -447,6 +453,42 @@ class Handle:
     def set_output_order(self, reference):
         """True: the points of a patch come out in the reference's order (z-sorted bins); False: scatter order."""
         self._check(self._L.pwpp_set_output_order(self._h, 1 if reference else 0))
+
+    def set_order(self, order):
+        """ORDER_SCATTER (default), ORDER_REFERENCE or ORDER_CLOUD (both lists in ascending cloud index; implies labels)."""
+        self._check(self._L.pwpp_set_output_order(self._h, int(order)))
+
+    def set_labels(self, on):
+        """True: the batches launched afterwards also write one LABEL_* byte per point (cloud order)."""
+        self._check(self._L.pwpp_set_labels(self._h, 1 if on else 0))
+
+    def labels(self, frame=0):
+        """(n,) uint8 LABEL_* of the frame's points, in cloud order."""
+        base = self.frame_base()
+        n = int(base[frame + 1] - base[frame]) if 0 <= frame < len(base) - 1 else 0
+        out = np.empty(max(n, 1), np.uint8)
+        self._check(self._L.pwpp_get_labels(self._h, frame, _vp(out)))
+        return out[:n]
+
+    def all_labels(self, out=None):
+        """Every frame's labels in one device-to-host copy: (labels, frame_base), frame f at labels[frame_base[f]:frame_base[f + 1]]."""
+        base = self.frame_base()
+        total = int(base[-1])
+        if out is None:
+            out = np.empty(max(total, 1), np.uint8)
+        self._check(self._L.pwpp_get_all_labels(self._h, _vp(out)))
+        return out[:total], base
+
+    def device_labels(self):
+        """Device address of the last call's labels (frame f at frame_base[f] of device_view())."""
+        p = ctypes.c_void_p()
+        self._check(self._L.pwpp_get_device_labels(self._h, ctypes.byref(p)))
+        return int(p.value or 0)
+
+    def frame_base(self):
+        """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""
+        v = self.device_view()
+        return np.ctypeslib.as_array(v.frame_base, shape=(v.frames + 1,)).copy()
 
     def set_overlap(self, on):
         """True: batches of 128+ frames run as two frame ranges on the handle's two streams (same results)."""

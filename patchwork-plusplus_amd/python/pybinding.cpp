@@ -24,6 +24,11 @@ py::array_t<float> to_numpy(const patchwork::Cloud &c) {
     if (c.rows() > 0) std::memcpy(out.mutable_data(), c.data(), (size_t)c.rows() * 3 * sizeof(float));
     return out;
 }
+py::array_t<uint8_t> to_numpy(const patchwork::Labels &v) {
+    py::array_t<uint8_t> out((py::ssize_t)v.rows());
+    if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows());
+    return out;
+}
 py::array_t<int32_t> to_numpy(const patchwork::Indices &v) {
     py::array_t<int32_t> out((py::ssize_t)v.rows());
     if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows() * sizeof(int32_t));
@@ -96,6 +101,9 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def("getHeight", &PatchWorkpp::getHeight)
         .def("getTimeTaken", &PatchWorkpp::getTimeTaken)
         .def("setReferenceOrder", &PatchWorkpp::setReferenceOrder, py::arg("on"))
+        .def("setCloudOrder", &PatchWorkpp::setCloudOrder, py::arg("on"))
+        .def("setLabels", &PatchWorkpp::setLabels, py::arg("on"))
+        .def("getLabels", [](PatchWorkpp &s) { return to_numpy(s.labelList()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
         .def("getNonground", [](PatchWorkpp &s) { return to_numpy(s.getNonground()); })
         .def("getCenters", [](PatchWorkpp &s) { return to_numpy(s.getCenters()); })
