@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define PWPP_VERSION_MAJOR 0
-#define PWPP_VERSION_MINOR 3 /* per-point labels (pwpp_set_labels, pwpp_get_*labels), PWPP_ORDER_CLOUD */
+#define PWPP_VERSION_MINOR 4 /* per-point patch rows and plane distances (pwpp_set_point_planes, pwpp_get_*point_*) */
 
 typedef enum pwpp_status {
     PWPP_OK = 0,
@@ -319,6 +319,33 @@ PWPP_API int pwpp_set_labels(pwpp_handle *h, int on);
 PWPP_API int pwpp_get_labels(pwpp_handle *h, int frame, uint8_t *out);          /* n bytes of frame `frame` */
 PWPP_API int pwpp_get_all_labels(pwpp_handle *h, uint8_t *out);                 /* the whole batch in ONE copy */
 PWPP_API int pwpp_get_device_labels(pwpp_handle *h, const uint8_t **out);      /* device pointer; frame_base as in the device view */
+
+/* ---- per-point patch rows and plane distances (batches launched after pwpp_set_point_planes(h, 1)) ---------------------
+ * Two arrays, cloud order, laid out like the labels (frame f at frame_base[f]); independent of labels and of the output order.
+ *   patch     int32: the row p of the point's patch in pwpp_get_patch_records / pwpp_get_centers / pwpp_get_normals, or -1.  A
+ *             point belongs to patch p if the reference's pc2czm puts it into the bin of record p: its ground points, its
+ *             regionwise non-ground points, the points R-VPF stripped and its TGR candidates (reverted or not).  -1: points of
+ *             bins with fewer than num_min_pts points, RNR points, points outside (min_range, max_range], and the skip marker
+ *             z == FLT_MIN (PWPP_LABEL_UNCLASSIFIED).  With num_min_pts <= 0 empty bins are patches (rows) that own no points.
+ *   distance  float: the signed distance of the point to its patch's REPORTED plane -- the record's normal and d, i.e. the
+ *             final estimate_plane of the patch (patchworkpp.cpp:541), which is what pwpp_get_normals shows -- or NaN where
+ *             patch is -1.  The reference's calc_point_to_plane_d (:551-554) in its own operation order, rounded once:
+ *                 s = fl32(fl32(fl32(n0 * x) + fl32(n1 * y)) + fl32(n2 * z));   dist = (float)((double)s + d)
+ *             with x, y, z the input floats.  The normal has n2 >= 0, so a positive distance is above the plane.  This is
+ *             not necessarily the plane of the last R-GPF round that made the ground / non-ground test; in a patch decided
+ *             NOT_UPRIGHT it is a distance to a wall, not a height.  A patch with an inherited plane (num_min_pts <= 0, or a
+ *             first fit set that was empty) gets that plane, as its record does; a patch whose ground set was clamped
+ *             (pwpp_get_clamped_frames) gets the plane of the clamped heights.  A NaN or inf coordinate gives what IEEE
+ *             arithmetic gives.
+ * Computed on the device behind the lists; their time counts in the k_emit slot of the kernel profile.  The getters return
+ * PWPP_E_STATE when the last call ran without point planes.  A pipe's handles take the setting through pwpp_pipe_handle. */
+PWPP_API int pwpp_set_point_planes(pwpp_handle *h, int on);
+PWPP_API int pwpp_get_point_patches(pwpp_handle *h, int frame, int32_t *out);       /* n entries of frame `frame` */
+PWPP_API int pwpp_get_point_distances(pwpp_handle *h, int frame, float *out);       /* n entries of frame `frame` */
+PWPP_API int pwpp_get_all_point_patches(pwpp_handle *h, int32_t *out);              /* the whole batch in ONE copy */
+PWPP_API int pwpp_get_all_point_distances(pwpp_handle *h, float *out);              /* the whole batch in ONE copy */
+/* device pointers (either may be NULL); frame_base as in the device view */
+PWPP_API int pwpp_get_device_point_planes(pwpp_handle *h, const int32_t **patches, const float **distances);
 
 /* Overlap mode (ON by default): batches of 128 frames or more are processed as two frame ranges -- binning
  * and index lists of both on the handle's main stream, each range's plane fits on a stream of its own -- so

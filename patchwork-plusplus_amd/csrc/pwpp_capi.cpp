@@ -194,6 +194,11 @@ struct pwpp_handle {
     bool labels_last = false;       // the last call ran with labels
     DevBuf<uint8_t> d_labels;       // [total points + 16] one PWPP_LABEL_* per point, laid out like d_out
     DevBuf<uint32_t> d_label_tiles; // PWPP_ORDER_CLOUD: [frames][tiles per frame] counts of the compaction (PwppBatch.label_tiles)
+    bool point_planes = false;      // pwpp_set_point_planes
+    bool point_planes_last = false; // the last call ran with them
+    DevBuf<int32_t> d_pt_patch;     // [total points] the row of every point's patch (-1: none), laid out like d_out
+    DevBuf<float> d_pt_dist;        // [total points] its signed distance to that patch's plane (NaN: none)
+    DevBuf<int32_t> d_pt_rows;      // [frames][B] K9's bin -> row table (PwppBatch.pt_rows)
     DevBuf<uint32_t> d_bins;   // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
     DevBuf<uint32_t> d_parts;  // TWO copies of 3 slabs of frames*(2B+2): part_count, part_off, part_cursor (pwpp_dev.h: a bin is stored in two
                                // parts); a call works on one copy while its K5 zeroes the other for the next call (PwppBatch.next_part_count)
@@ -614,10 +619,17 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt) {
     bt.results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
     bt.results_host = h->h_results.p;  // hipHostMalloc'ed: the same address on the device
     bt.dbg = h->d_dbg.p;
+    if (labels_on(h) || h->point_planes) {
+        bt.point_first = 0;
+        bt.point_count = h->h_base.p[h->frames];
+    }
+    if (h->point_planes) {
+        bt.pt_patch = h->d_pt_patch.p;
+        bt.pt_dist = h->d_pt_dist.p;
+        bt.pt_rows = h->d_pt_rows.p;
+    }
     if (labels_on(h)) {
         bt.labels = h->d_labels.p;
-        bt.label_first = 0;
-        bt.label_count = h->h_base.p[h->frames];
         if (h->output_order == PWPP_ORDER_CLOUD) {
             bt.label_tiles = h->d_label_tiles.p;
             bt.label_tile_stride = (int32_t)label_tile_stride(h->max_n);
@@ -679,10 +691,11 @@ PwppBatch frame_range(const pwpp_handle *h, const PwppBatch &bt, int f0, int nf)
     v.results_host += f0;
     if (v.order_work) v.order_work += (size_t)f0 * (size_t)(1 + 2 * NB);
     if (v.arena_tag) v.arena_tag += (size_t)f0 * v.arena_spill;
-    if (v.labels) {
-        v.label_first = h->h_base.p[f0];
-        v.label_count = h->h_base.p[f0 + nf] - h->h_base.p[f0];
+    if (v.labels || v.pt_patch) {
+        v.point_first = h->h_base.p[f0];
+        v.point_count = h->h_base.p[f0 + nf] - h->h_base.p[f0];
     }
+    if (v.pt_rows) v.pt_rows += (size_t)f0 * B;
     if (v.label_tiles) v.label_tiles += (size_t)f0 * (size_t)v.label_tile_stride;
     v.next_part_count += (size_t)f0 * NP;  // (the other copy: same frame, same slab stride)
     v.next_results += f0;
@@ -1420,6 +1433,12 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
         if (h->output_order == PWPP_ORDER_CLOUD && (rc = h->d_label_tiles.ensure((size_t)frames * (size_t)label_tile_stride(max_n)))) return rc;
     }
     h->labels_last = labels_on(h);
+    if (h->point_planes) {
+        if ((rc = h->d_pt_patch.ensure(tp))) return rc;
+        if ((rc = h->d_pt_dist.ensure(tp))) return rc;
+        if ((rc = h->d_pt_rows.ensure((size_t)frames * B))) return rc;
+    }
+    h->point_planes_last = h->point_planes;
     if ((rc = h->d_bins.ensure((size_t)frames * NB * 4))) return rc;
     if ((rc = h->d_parts.ensure(2 * counters_copy_words((size_t)frames * NP)))) return rc;  // two copies
     if ((rc = h->d_recs.ensure((size_t)frames * B))) return rc;
@@ -2055,7 +2074,7 @@ int64_t pwpp_get_workspace_bytes(pwpp_handle *h) {
            b(h->d_xyz.cap, 4) + b(h->d_dbg.cap, 8) + b(h->d_st_stream.cap, sizeof(PwppStateScalar)) + b(h->d_st_fresh.cap, sizeof(PwppStateScalar)) +
            b(h->d_st_snap.cap, sizeof(PwppStateScalar)) + b(h->d_hist_stream.cap, 8) + b(h->d_hist_fresh.cap, 8) + b(h->d_hist_snap.cap, 8) +
            b(h->d_pl_stream.cap, sizeof(PwppPlaneState)) + b(h->d_pl_fresh.cap, sizeof(PwppPlaneState)) + b(h->d_pl_snap.cap, sizeof(PwppPlaneState)) +
-           b(h->d_labels.cap, 1) + b(h->d_label_tiles.cap, 4);
+           b(h->d_labels.cap, 1) + b(h->d_label_tiles.cap, 4) + b(h->d_pt_patch.cap, 4) + b(h->d_pt_dist.cap, 4) + b(h->d_pt_rows.cap, 4);
 }
 
 int pwpp_trim_workspace(pwpp_handle *h) {
@@ -2079,6 +2098,9 @@ int pwpp_trim_workspace(pwpp_handle *h) {
     h->d_ord_work.release();
     h->d_labels.release();
     h->d_label_tiles.release();
+    h->d_pt_patch.release();
+    h->d_pt_dist.release();
+    h->d_pt_rows.release();
     h->d_xyz.release();
     h->d_frames.release();
     h->d_frames_probe.release();
@@ -2155,6 +2177,56 @@ int pwpp_get_device_labels(pwpp_handle *h, const uint8_t **out) {
     int rc = check_frame(h, 0);
     if (rc || (rc = check_labels(h))) return rc;
     *out = h->d_labels.p;
+    return PWPP_OK;
+}
+
+int pwpp_set_point_planes(pwpp_handle *h, int on) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    int rc = use_device(h);
+    if (rc) return rc;
+    if ((rc = finish_pending(h))) return rc;
+    h->point_planes = on != 0;
+    return PWPP_OK;
+}
+
+// the point planes of the last call: its results, and point planes among them
+static int check_point_planes(pwpp_handle *h) {
+    if (!h->point_planes_last) return fail(PWPP_E_STATE, "the last call ran without point planes (pwpp_set_point_planes)");
+    return PWPP_OK;
+}
+
+// one frame of one of the two arrays (`elem` bytes per point), or the whole batch in one copy
+static int copy_point_planes(pwpp_handle *h, int frame, bool whole_batch, void *out, const void *src_all, size_t elem) {
+    int rc = check_frame(h, frame);
+    if (rc || (rc = check_point_planes(h))) return rc;
+    const int64_t first = whole_batch ? 0 : h->h_base.p[frame], end = h->h_base.p[whole_batch ? h->frames : frame + 1];
+    if (end > first) {
+        if (!out) return fail(PWPP_E_ARG, "null output");
+        HIPCHK(hipMemcpyAsync(out, static_cast<const char *>(src_all) + (size_t)first * elem, (size_t)(end - first) * elem, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return PWPP_OK;
+}
+
+int pwpp_get_point_patches(pwpp_handle *h, int frame, int32_t *out) {
+    return copy_point_planes(h, frame, false, out, h ? h->d_pt_patch.p : nullptr, sizeof(int32_t));
+}
+int pwpp_get_point_distances(pwpp_handle *h, int frame, float *out) {
+    return copy_point_planes(h, frame, false, out, h ? h->d_pt_dist.p : nullptr, sizeof(float));
+}
+int pwpp_get_all_point_patches(pwpp_handle *h, int32_t *out) {
+    return copy_point_planes(h, 0, true, out, h ? h->d_pt_patch.p : nullptr, sizeof(int32_t));
+}
+int pwpp_get_all_point_distances(pwpp_handle *h, float *out) {
+    return copy_point_planes(h, 0, true, out, h ? h->d_pt_dist.p : nullptr, sizeof(float));
+}
+
+int pwpp_get_device_point_planes(pwpp_handle *h, const int32_t **patches, const float **distances) {
+    if (!h || (!patches && !distances)) return fail(PWPP_E_ARG, "null argument");
+    int rc = check_frame(h, 0);
+    if (rc || (rc = check_point_planes(h))) return rc;
+    if (patches) *patches = h->d_pt_patch.p;
+    if (distances) *distances = h->d_pt_dist.p;
     return PWPP_OK;
 }
 

@@ -207,8 +207,12 @@ struct PwppBatch {
     uint32_t *label_tiles;       // PWPP_ORDER_CLOUD: [frames][label_tile_stride] ground | non-ground << 16 of every tile of
                                  // PWPP_LABEL_TILE labels (tile 0 starts at fd.base rounded down to 16); null = no reordering
     int32_t label_tile_stride;   // tiles per frame of the whole call (its largest frame)
+    // Per-point patch rows and plane distances (pwpp_set_point_planes), written behind the lists of this launch's frames; null = off
+    int32_t *pt_patch;           // [total points] laid out like out_idx: the row of the point's patch in the frame's patch records, -1 = none
+    float *pt_dist;              // same slots: the signed distance of the point to that patch's reported plane, NaN = none
+    int32_t *pt_rows;            // [frames][B] scratch: the row of every bin that is a patch, -1 for the others
     // host side only (the kernels never read these)
-    int64_t label_first, label_count;  // the slots of this launch's frames (contiguous: the memset to UNCLASSIFIED)
+    int64_t point_first, point_count;  // the per-point slots of this launch's frames (contiguous: the fills of labels and point planes)
     const char *fit_plan;        // option "fit_plan": overrides the plan pwpp_launch_fit would choose; null or empty = automatic
     int32_t plan_frames;         // frames the automatic fit plan is chosen for: the WHOLE call's when this batch is one of its frame ranges (0: num_frames)
     int32_t fit_concurrent;      // option "fit_concurrent": the classes of a plan side by side on two streams

@@ -17,6 +17,7 @@
 //                          mirrors the frame counters into pinned host memory
 //   K7  k_order_sublists   optional: the reference's order inside every part of the lists
 //   K8  k_label_*          optional: per-point labels from the final lists; cloud-order lists from the labels
+//   K9  k_pp_*             optional: per-point patch row and signed distance to the patch's plane  (ref :551-554)
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -2722,15 +2723,138 @@ __global__ __launch_bounds__(kLabelBlock) void k_label_compact(PwppBatch Bt) {
         if (ng_total + nb + i < n) out[ng_total + nb + i] = stage[1023u - i];
 }
 
+// ------------------------------------------------------------------------------------------
+// K9 (optional)  per-point patch row and signed distance to the patch's plane (pwpp_set_point_planes)
+// ------------------------------------------------------------------------------------------
+// Behind the final lists of a launch's frames, like K8.  k_pp_prep fills the launch's slots with -1 / NaN and, in one more
+// workgroup per frame, ranks the patch bins (the rows of pwpp_get_patch_records: bins in ascending order, those with at least
+// num_min_pts points).  k_pp_patch then walks every patch's slots in the bin-ordered planes as k_emit does -- both parts, a part
+// moved into the overflow arena included -- and writes row and distance to base + cloud index.  The bin a point was BINNED into
+// is what counts: recomputing it from the cloud would miss RNR, whose test used the sensor height K5 has moved since.
+// The distance is the reference's calc_point_to_plane_d (:551-554) against the patch record's plane (the final estimate_plane of
+// :541): float products and sums left to right, then + d in double, rounded once to float.  A point R-VPF stripped carries the
+// round in place of its z (strip_point, pwpp_fit.hip): its z is fetched from the cloud.  A frame whose lists are not written yet
+// (k_fit_fixup, redo) keeps the fill; every index is checked against the frame, and the frame is written again with its lists.
+constexpr int kPpBlock = 256;
+constexpr int kPpWave = 64;
+
+// blocks [0, fill_blocks): the slots [first, first + count) = -1 / NaN, 16 bytes per lane and array; then one block per frame: the
+// bin -> row table (pt_rows)
+__global__ __launch_bounds__(kPpBlock) void k_pp_prep(PwppBatch Bt, int64_t first, int64_t count, unsigned fill_blocks) {
+    if (blockIdx.x < fill_blocks) {
+        const int64_t end = first + count, p0 = (first & ~(int64_t)3) + 4 * ((int64_t)blockIdx.x * kPpBlock + threadIdx.x);
+        if (p0 >= end) return;
+        const float qnan = __uint_as_float(0x7fc00000u);
+        if (p0 >= first && p0 + 4 <= end) {
+            *reinterpret_cast<int4 *>(Bt.pt_patch + p0) = make_int4(-1, -1, -1, -1);
+            *reinterpret_cast<float4 *>(Bt.pt_dist + p0) = make_float4(qnan, qnan, qnan, qnan);
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (p0 + k >= first && p0 + k < end) {
+                    Bt.pt_patch[p0 + k] = -1;
+                    Bt.pt_dist[p0 + k] = qnan;
+                }
+        }
+        return;
+    }
+    __shared__ unsigned s_tot[kPpBlock / 64];
+    const int f = (int)(blockIdx.x - fill_blocks);
+    const PwppDevParams &P = Bt.P;
+    const int B = P.num_bins, NB = B + 2;
+    constexpr int kPer = (PWPP_MAX_BINS + kPpBlock - 1) / kPpBlock;
+    const int per = (B + kPpBlock - 1) / kPpBlock, b0 = (int)threadIdx.x * per;
+    const uint32_t *cnt = Bt.bin_count + (size_t)f * NB;
+    unsigned is_patch = 0u;  // bit j: bin b0 + j is a patch
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+        if (j < per && b0 + j < B && (uint64_t)cnt[b0 + j] >= P.min_pts) is_patch |= 1u << j;
+    const unsigned c = (unsigned)__popc(is_patch), incl = wave_incl_scan(c);
+    if (lane_id() == 63) s_tot[wave_id()] = incl;
+    __syncthreads();
+    unsigned row = incl - c;
+    for (int w = 0; w < wave_id(); ++w) row += s_tot[w];
+    int32_t *rows = Bt.pt_rows + (size_t)f * B;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+        if (j < per && b0 + j < B) rows[b0 + j] = (is_patch >> j & 1u) ? (int32_t)(row++) : -1;
+}
+
+// one wave per (patch bin, frame), gridDim.z waves per bin share its slots in steps of 256 (four per lane: 16-byte loads)
+__global__ __launch_bounds__(kPpWave, 8) void k_pp_patch(PwppBatch Bt) {
+    const int f = blockIdx.y, seg = blockIdx.x;
+    const PwppDevParams &P = Bt.P;
+    const int B = P.num_bins, NB = B + 2;
+    const unsigned n = Bt.bin_count[(size_t)f * NB + seg];
+    if (n == 0u || (uint64_t)n < P.min_pts) return;  // (no points, or not a patch: the fill stands)
+    if (Bt.dst_a[(size_t)f * NB + seg] == kAwaitsFixup) return;  // (the frame awaits k_fit_fixup: written again behind its lists)
+    const int row = Bt.pt_rows[(size_t)f * B + seg];
+    if (row < 0) return;
+    const PwppFrameDesc fd = Bt.frames[f];
+    const unsigned off = Bt.bin_off[(size_t)f * NB + seg];
+    unsigned n_lo = n, off_hi = off;
+    if (seg < P.split_end) {  // (the bin's high part, pwpp_dev.h: `n_lo` points at `off`, the others at `off_hi`)
+        n_lo = Bt.part_count[(size_t)f * PWPP_NUM_PARTS(B) + PWPP_PART_LO(seg)];
+        off_hi = Bt.part_off[(size_t)f * PWPP_NUM_PARTS(B) + PWPP_PART_HI(seg)];
+        n_lo = n_lo < n ? n_lo : n;
+    }
+    const PwppPatchRec *rec = Bt.recs + (size_t)f * B + seg;
+    const float n0 = rec->normal[0], n1 = rec->normal[1], n2 = rec->normal[2];
+    const double d = rec->d;
+    int32_t *pat = Bt.pt_patch + fd.base;
+    float *dist = Bt.pt_dist + fd.base;
+    const unsigned step = gridDim.z * (kPpWave * 4u);
+#pragma unroll 1
+    for (int hi = 0; hi < 2; ++hi) {
+        const unsigned pn = hi ? n - n_lo : n_lo;
+        const int64_t s0 = fd.sbase + (hi ? off_hi : off);  // (a part starts at a multiple of PWPP_SLOT_ALIGN slots, and is padded to one)
+        const int *pidx = Bt.sorted_idx + s0;
+        const float *pz = Bt.sorted_z + s0;
+        const float2 *pxy = Bt.sorted_xy + s0;
+        for (unsigned p0 = (blockIdx.z * kPpWave + threadIdx.x) * 4u; p0 < pn; p0 += step) {
+            const int4 v = *reinterpret_cast<const int4 *>(pidx + p0);
+            const float4 z4 = *reinterpret_cast<const float4 *>(pz + p0);
+            const float4 xy01 = *reinterpret_cast<const float4 *>(pxy + p0);
+            const float4 xy23 = *reinterpret_cast<const float4 *>(pxy + p0 + 2);
+            const int vi[4] = {v.x, v.y, v.z, v.w};
+            const float zs[4] = {z4.x, z4.y, z4.z, z4.w};
+            const float xs[4] = {xy01.x, xy01.z, xy23.x, xy23.z};
+            const float ys[4] = {xy01.y, xy01.w, xy23.y, xy23.w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int i = vi[t];
+                if (p0 + (unsigned)t >= pn || (unsigned)i >= (unsigned)fd.n) continue;
+                float z = zs[t];
+                if ((int)__float_as_uint(z) > 0x7fc00000) {  // stripped by R-VPF (a NaN of the cloud is the plain 0x7fc00000)
+                    float x_, y_, w_;
+                    load_point(fd, i, x_, y_, z, w_);
+                }
+                // ref :553 in its own operations: float products and sums, left to right (-ffp-contract=off: no FMA), + d in double
+                const float s = n0 * xs[t] + n1 * ys[t] + n2 * z;
+                pat[i] = row;
+                dist[i] = (float)((double)s + d);
+            }
+        }
+    }
+}
+
 }  // namespace
+
+// the per-point patch rows and plane distances of the launch's frames, behind their final lists
+static void launch_point_planes(const PwppBatch &B, hipStream_t stream) {
+    const int F = B.num_frames;
+    const int64_t lanes = B.point_count > 0 ? ((B.point_first & 3) + B.point_count + 3) / 4 : 0;
+    const unsigned fill_blocks = (unsigned)((lanes + kPpBlock - 1) / kPpBlock);
+    hipLaunchKernelGGL(k_pp_prep, dim3(fill_blocks + (unsigned)F), dim3(kPpBlock), 0, stream, B, B.point_first, B.point_count, fill_blocks);
+    hipLaunchKernelGGL(k_pp_patch, dim3(B.P.num_bins, F, B.emit_parts > 1 ? B.emit_parts : 1), dim3(kPpWave), 0, stream, B);
+}
 
 // the labels of the launch's frames, behind their final lists (and the cloud order of the lists when B.label_tiles is set)
 static void launch_labels(const PwppBatch &B, hipStream_t stream) {
     const int F = B.num_frames;
-    if (B.label_count > 0) {
-        const int64_t lanes = ((B.label_first & 15) + B.label_count + 15) / 16;
+    if (B.point_count > 0) {
+        const int64_t lanes = ((B.point_first & 15) + B.point_count + 15) / 16;
         hipLaunchKernelGGL(k_label_fill, dim3((unsigned)((lanes + kLabelBlock - 1) / kLabelBlock)), dim3(kLabelBlock), 0, stream,
-                           B.labels, B.label_first, B.label_count);
+                           B.labels, B.point_first, B.point_count);
     }
     const unsigned gs = (unsigned)(((int64_t)B.max_n + 3 + 4 * 4 * kLabelBlock - 1) / (4 * 4 * kLabelBlock));
     hipLaunchKernelGGL(k_label_scatter, dim3(gs, F), dim3(kLabelBlock), 0, stream, B);
@@ -2808,7 +2932,7 @@ extern "C" int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream)
     return (int)hipGetLastError();
 }
 
-// stages: bit 0 = binning (K0-K3), bit 1 = plane fits + K5, bit 2 = index lists (K6, K7, K8); the overlap schedule of
+// stages: bit 0 = binning (K0-K3), bit 1 = plane fits + K5, bit 2 = index lists (K6, K7, K8, K9); the overlap schedule of
 // pwpp_capi.cpp launches the stages of a frame range on different streams.  Bit 3 (with bit 1): k_fit_fixup instead of the
 // fit kernels -- the host finishing a frame whose patches needed the plane fitted before them (batch->fixup_run set).
 extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev /* PWPP_NUM_KERNELS + 1 events or null */,
@@ -2897,7 +3021,7 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
             if (order_a) hipLaunchKernelGGL((k_emit<false, true>), lgrid, dim3(kEmitBlock), 0, stream, L, order_a);
             else hipLaunchKernelGGL((k_emit<false, false>), lgrid, dim3(kEmitBlock), 0, stream, L, order_a);
         }
-        if (ev && !B.labels) (void)hipEventRecord(ev[11], stream);
+        if (ev && !B.labels && !B.pt_patch) (void)hipEventRecord(ev[11], stream);
         if (order_a) {
             hipLaunchKernelGGL((k_order_sublists<64, 256, 0>), dim3(NB, F), dim3(64), 0, stream, B, order_a, order_b);
             // the lists above 256 entries: a work list per frame, then one workgroup per item (at most points / 257 + the two a bin can add)
@@ -2905,8 +3029,9 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
             hipLaunchKernelGGL(k_order_worklist, dim3(F), dim3(kBlock), 0, stream, B, 256);
             hipLaunchKernelGGL((k_order_sublists<PWPP_ORDER_BLOCK, 4096, 256>), dim3(max_items, F), dim3(PWPP_ORDER_BLOCK), 0, stream, B, order_a, order_b);
         }
-        if (B.labels) {  // behind the final lists (K7's, in reference order); profiled in k_emit's slot
-            launch_labels(B, stream);
+        if (B.labels || B.pt_patch) {  // behind the final lists (K7's, in reference order); profiled in k_emit's slot
+            if (B.labels) launch_labels(B, stream);
+            if (B.pt_patch) launch_point_planes(B, stream);
             if (ev) (void)hipEventRecord(ev[11], stream);
         }
     }

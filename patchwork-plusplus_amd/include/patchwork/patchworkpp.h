@@ -166,6 +166,19 @@ private:
     std::vector<uint8_t> v_;
 };
 
+// one float per point (getPointDistances without Eigen)
+class Distances {
+public:
+    Distances() {}
+    explicit Distances(int rows) : v_((size_t)rows) {}
+    int rows() const { return (int)v_.size(); }
+    float operator()(int i) const { return v_[(size_t)i]; }
+    float *data() { return v_.data(); }
+    const float *data() const { return v_.data(); }
+private:
+    std::vector<float> v_;
+};
+
 // reference patchworkpp.h:114-163
 class PatchWorkpp {
 public:
@@ -243,6 +256,28 @@ public:
     Labels getLabels() { return labels(); }
 #endif
     Labels labelList() { return labels(); }
+    // extension: per point of the frames estimated afterwards, the row of its patch in getCenters() / getNormals() (-1: none)
+    // and its signed distance to that patch's plane (NaN: none); pwpp.h, pwpp_set_point_planes
+    void setPointPlanes(bool on) { check(pwpp_set_point_planes(h_, on ? 1 : 0)); }
+#ifdef PWPP_HAVE_EIGEN
+    Eigen::VectorXi getPointPatches() {
+        const Indices v = pointPatches();
+        Eigen::VectorXi m(v.rows());
+        for (int i = 0; i < v.rows(); ++i) m(i) = v(i);
+        return m;
+    }
+    Eigen::VectorXf getPointDistances() {
+        const Distances v = pointDistances();
+        Eigen::VectorXf m(v.rows());
+        for (int i = 0; i < v.rows(); ++i) m(i) = v(i);
+        return m;
+    }
+#else
+    Indices getPointPatches() { return pointPatches(); }
+    Distances getPointDistances() { return pointDistances(); }
+#endif
+    Indices pointPatchList() { return pointPatches(); }
+    Distances pointDistanceList() { return pointDistances(); }
 
 #ifdef PWPP_HAVE_EIGEN
     // the reference's return types (fresh objects on every call, as the reference's toEigenCloud / toIndices, :8-26)
@@ -321,6 +356,21 @@ private:
         Labels l((int)(v.frame_base[1] - v.frame_base[0]));
         check(pwpp_get_labels(h_, 0, l.data()));
         return l;
+    }
+    int frame_points() {
+        pwpp_device_view v;
+        check(pwpp_get_device_view(h_, &v));
+        return (int)(v.frame_base[1] - v.frame_base[0]);
+    }
+    Indices pointPatches() {
+        Indices v(frame_points());
+        check(pwpp_get_point_patches(h_, 0, v.data()));
+        return v;
+    }
+    Distances pointDistances() {
+        Distances v(frame_points());
+        check(pwpp_get_point_distances(h_, 0, v.data()));
+        return v;
     }
     Cloud rows(bool centers) {
         int32_t g, n, p;

@@ -132,6 +132,12 @@ def load():
         L.pwpp_get_labels.argtypes = [vp, ci, vp]
         L.pwpp_get_all_labels.argtypes = [vp, vp]
         L.pwpp_get_device_labels.argtypes = [vp, ctypes.POINTER(vp)]
+        L.pwpp_set_point_planes.argtypes = [vp, ci]
+        for name in ("pwpp_get_point_patches", "pwpp_get_point_distances"):
+            getattr(L, name).argtypes = [vp, ci, vp]
+        for name in ("pwpp_get_all_point_patches", "pwpp_get_all_point_distances"):
+            getattr(L, name).argtypes = [vp, vp]
+        L.pwpp_get_device_point_planes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
@@ -484,6 +490,50 @@ class Handle:
         p = ctypes.c_void_p()
         self._check(self._L.pwpp_get_device_labels(self._h, ctypes.byref(p)))
         return int(p.value or 0)
+
+    def set_point_planes(self, on):
+        """True: the batches launched afterwards also write, per point, the row of its patch and its signed distance to the
+        patch's plane (cloud order; include/pwpp.h)."""
+        self._check(self._L.pwpp_set_point_planes(self._h, 1 if on else 0))
+
+    def _point_frame(self, fn, frame, dtype):
+        base = self.frame_base()
+        n = int(base[frame + 1] - base[frame]) if 0 <= frame < len(base) - 1 else 0
+        out = np.empty(max(n, 1), dtype)
+        self._check(fn(self._h, frame, _vp(out)))
+        return out[:n]
+
+    def _point_batch(self, fn, out, dtype):
+        base = self.frame_base()
+        total = int(base[-1])
+        if out is None:
+            out = np.empty(max(total, 1), dtype)
+        if out.dtype != dtype or not out.flags.c_contiguous or out.size < total:
+            raise ValueError("out: a contiguous %s array of at least %d entries expected" % (np.dtype(dtype).name, total))
+        self._check(fn(self._h, _vp(out)))
+        return out[:total], base
+
+    def point_patches(self, frame=0):
+        """(n,) int32: the row of every point's patch in patch_records / centers / normals of the frame, -1 = none."""
+        return self._point_frame(self._L.pwpp_get_point_patches, frame, np.int32)
+
+    def point_distances(self, frame=0):
+        """(n,) float32: every point's signed distance to its patch's plane, NaN where point_patches is -1."""
+        return self._point_frame(self._L.pwpp_get_point_distances, frame, np.float32)
+
+    def all_point_patches(self, out=None):
+        """Every frame's point_patches in one device-to-host copy: (patches, frame_base)."""
+        return self._point_batch(self._L.pwpp_get_all_point_patches, out, np.int32)
+
+    def all_point_distances(self, out=None):
+        """Every frame's point_distances in one device-to-host copy: (distances, frame_base)."""
+        return self._point_batch(self._L.pwpp_get_all_point_distances, out, np.float32)
+
+    def device_point_planes(self):
+        """Device addresses (patches, distances) of the last call's point planes (frame f at frame_base[f])."""
+        p, d = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._L.pwpp_get_device_point_planes(self._h, ctypes.byref(p), ctypes.byref(d)))
+        return int(p.value or 0), int(d.value or 0)
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

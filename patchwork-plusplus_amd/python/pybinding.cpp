@@ -29,6 +29,11 @@ py::array_t<uint8_t> to_numpy(const patchwork::Labels &v) {
     if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows());
     return out;
 }
+py::array_t<float> to_numpy(const patchwork::Distances &v) {
+    py::array_t<float> out((py::ssize_t)v.rows());
+    if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows() * sizeof(float));
+    return out;
+}
 py::array_t<int32_t> to_numpy(const patchwork::Indices &v) {
     py::array_t<int32_t> out((py::ssize_t)v.rows());
     if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows() * sizeof(int32_t));
@@ -104,6 +109,9 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def("setCloudOrder", &PatchWorkpp::setCloudOrder, py::arg("on"))
         .def("setLabels", &PatchWorkpp::setLabels, py::arg("on"))
         .def("getLabels", [](PatchWorkpp &s) { return to_numpy(s.labelList()); })
+        .def("setPointPlanes", &PatchWorkpp::setPointPlanes, py::arg("on"))
+        .def("getPointPatches", [](PatchWorkpp &s) { return to_numpy(s.pointPatchList()); })
+        .def("getPointDistances", [](PatchWorkpp &s) { return to_numpy(s.pointDistanceList()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
         .def("getNonground", [](PatchWorkpp &s) { return to_numpy(s.getNonground()); })
         .def("getCenters", [](PatchWorkpp &s) { return to_numpy(s.getCenters()); })
