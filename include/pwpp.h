@@ -395,9 +395,8 @@ PWPP_API pwpp_handle *pwpp_pipe_handle(pwpp_pipe *pipe, int index);
 PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
 
 /* Tuning and test switches (no reference counterpart).  The environment variables PWPP_DEBUG_FLAGS,
- * PWPP_FIT_PLAN, PWPP_FIT_CONCURRENT, PWPP_NO_ONE_PASS, PWPP_ONE_PASS_MIN_FRAMES, PWPP_ONE_PASS_SCALE,
- * PWPP_OVERLAP, PWPP_OVERLAP_MODE, PWPP_OVERLAP_RANGES, PWPP_FIT_STREAMS, PWPP_BIN_BLOCK, PWPP_HI_SPLIT,
- * PWPP_HI_SPLIT_ZONES and PWPP_EXACT_MOMENTS set the same options ONCE, in pwpp_create (which says so on stderr); nothing reads the
+ * PWPP_FIT_PLAN, PWPP_NO_ONE_PASS, PWPP_ONE_PASS_MIN_FRAMES, PWPP_ONE_PASS_SCALE, PWPP_OVERLAP,
+ * PWPP_OVERLAP_RANGES, PWPP_FIT_STREAMS, PWPP_HI_SPLIT, PWPP_HI_SPLIT_ZONES and PWPP_EXACT_MOMENTS set the same options ONCE, in pwpp_create (which says so on stderr); nothing reads the
  * environment afterwards.  None of them changes a result, except the one that says so:
  *   "exact_moments"       "1" (default): the plane-fit sums of 4+ points exact on the reference's floats (2^-30 m grid, contract v4);
  *                         "0": rounds 3-5's 2^-21 m grid -- 7 % faster, off the reference by a few indices on 0.2 % of varied frames
@@ -407,11 +406,7 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         in the reference's order) run on the handle's second stream, under K6 and the host's turn-around: one stream in steady
  *                         state 108 -> 100 us per frame.  "2": the second launch starts only when the lists are written (not beside K6): the
  *                         lists another ~4-5 us earlier, the state ~15 us later (a caller that steps the stream again at once waits for it there).  "0": one kernel
- *   "fuse_scan"           "1": fewer than eight frames run the part scan (K2) inside the binning kernel -- the workgroup that takes a frame's
- *                         last ticket scans (rounds 4-5's default).  "0" (default): a kernel of its own -- 1-2 us faster per frame since the
- *                         ticket is an agent-scope acquire-release
  *   "fit_plan"            which fit kernel handles which patch sizes, e.g. "W16:1023,W64.2:65535"; "" = automatic
- *   "fit_concurrent"      "1": the classes of a plan side by side on two streams
  *   "one_pass"            "0": always the two-pass binning
  *   "redo_whole_batch"    "1": a segment overflow of the one-pass binning redoes every frame of the batch (rounds 1-4) instead of
  *                         the frames that overflowed
@@ -420,13 +415,8 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *   "one_pass_scale"      scales the head-room of the one-pass segments (default 4 = 1.0625 x the largest count seen + 2 sqrt + 16 slots; tests
  *                         use small values to force overflows: first the arena, then the host's redo)
  *   "overlap_ranges"      frame ranges of the overlap mode (default 2; more were slower: 3.38 ms vs 2.86 ms with 4)
- *   "overlap_mode"        "1" (default): binning and lists on the main stream, the ranges' fits on "fit_streams" more;
- *                         "0": every range as a whole pipeline, alternating between two streams
- *   "fit_streams"         streams the ranges' fit stages are dealt to (1..8, default 2)
- *   "cu_split"            "N" or "N:mode" (experiment, default "0" = off): the overlap schedule's memory stream on N of the 256 CUs
- *                         and its fit streams on the others (hipExtStreamCreateWithCUMask).  Slower in every configuration
- *                         measured (profiles/r05_cu_mask_sweep.txt)
- *   "bin_block"           threads per workgroup of the one-pass binning kernel (128 / 256 / 512 / 1024, default 256)
+ *   "fit_streams"         streams the ranges' fit stages are dealt to (1..8, default 2): binning and lists of the overlap
+ *                         mode run on the main stream
  *   "hi_split"            metres above the ground level (-sensor_height) where the "high" part of a bin begins
  *                         (default 0.6; 1e30 = no high parts): the fit passes skip a high part whenever they can
  *                         prove that none of its points can enter the pass
@@ -434,8 +424,6 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);
- *                         256: fewer than eight frames: the scan as a kernel of its own (by default the last workgroup of the
- *                         binning kernel to finish a frame runs it in place);
  *                         64: before a call that skips the clearing kernel (the last call's K5 zeroed this call's counters),
  *                         read the counters back and fail with PWPP_E_STATE unless every word is zero;
  *                         2048: no overflow arena (a full segment sends its frame back to the host, as in rounds 2-5);

@@ -115,25 +115,16 @@ struct pwpp_handle {
     bool k5_tail_unjoined = false;  // the last call left K5's second part on aux_stream (aux_join recorded behind it): the main stream has not waited for it yet
     bool k5_tail_unsynced = false;  // ... and neither has the host
     bool hist_check_due = false;    // the fill of the streams' histories after the last call has not been looked at yet (settle_k5_tail)
-    int fuse_scan = 0;              // option "fuse_scan": K2 inside K1' for fewer than eight frames (rounds 4-5's default)
     int split_k5 = 1;               // option "split_k5": a few stateful streams run K5 in two launches (k_gle_tgr PART 1 / 2)
     bool overlap = true;   // pwpp_set_overlap: big batches as a pipeline of frame ranges over the two streams (default on)
     int overlap_ranges = 2;  // (more ranges were slower at every setting tried: each range's fit kernels end with the tail of their
                              // longest waves -- docs/history/design_through_round4.md section 9)
-    int overlap_mode = 1;  // option "overlap_mode": 1 = memory stream / fit stream pipeline, 0 = whole ranges alternating between the streams
     std::vector<hipEvent_t> ev_ranges;  // two per frame range: binned, fitted
-    int bin_block = 256;                // option "bin_block": threads per workgroup of the one-pass binning kernel
     int num_fit_streams = 2;            // option "fit_streams": streams the ranges' fit stages are dealt to (aux_stream + extra_streams)
     std::vector<hipStream_t> extra_streams;
-    // option "cu_split" (round 5 experiment): the overlap schedule's memory stream and fit streams on disjoint
-    // sets of CUs (hipExtStreamCreateWithCUMask).  cu_split_mem = CUs of the memory stream (0 = off), cu_split_mode: which bits.
-    int cu_split_mem = 0, cu_split_mode = 0;
-    hipStream_t masked_mem = nullptr;
-    std::vector<hipStream_t> masked_fit;
     // tuning / test options (pwpp_set_option; the PWPP_* environment variables are read ONCE, in pwpp_create)
     int debug_flags = 0;
     std::string fit_plan;
-    bool fit_concurrent = false;
     bool no_one_pass = false;
     int one_pass_min_frames = 1;     // stream batches (round 4: the state a redo starts from is copied by extra workgroups of k_czm_scan, no
                                      // copy commands in front of the pipeline any more: one stream 112.8 -> 106.9 us of GPU time, 139 -> 131 us per call)
@@ -408,8 +399,6 @@ void sync_all_streams(pwpp_handle *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->aux_stream) (void)hipStreamSynchronize(h->aux_stream);
     for (hipStream_t st : h->extra_streams) (void)hipStreamSynchronize(st);
-    if (h->masked_mem) (void)hipStreamSynchronize(h->masked_mem);
-    for (hipStream_t st : h->masked_fit) (void)hipStreamSynchronize(st);
 }
 
 // the stream history slabs [stream][2][4][cap] re-laid out for a larger cap (contents kept)
@@ -439,8 +428,8 @@ int build_capacity_table(pwpp_handle *h, int max_n) {
     const PwppDevParams &P = h->dp;
     const int NB = PWPP_NUM_PARTS(P.num_bins);  // one segment per part
     // A FEW frames per call (a single sensor's stream, the reference's own use): memory is no concern there (2 048 slots more per part
-    // are 40 MB per frame), but every overflow is a frame binned twice (the fused binning + scan kernel of fewer than eight frames has
-    // no arena), and a handle that has seen a handful of frames knows little about its bins -- 3.75 x the largest count + 2048.
+    // are 40 MB per frame), but every overflow is a frame binned twice (these calls get no arena), and a handle that has seen a
+    // handful of frames knows little about its bins -- 3.75 x the largest count + 2048.
     const bool few = h->frames <= 16 && h->one_pass_scale >= 1.0;
     h->cap_few = few;
     const double scale = (few ? 3.75 : 1.0625) * h->one_pass_scale / 4.0;
@@ -575,8 +564,6 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt) {
     bt.debug = h->debug_flags;
     bt.fit_plan = h->fit_plan.empty() ? nullptr : h->fit_plan.c_str();
     bt.plan_frames = 0;
-    bt.fit_concurrent = h->fit_concurrent ? 1 : 0;
-    bt.bin_block = h->bin_block;
     if (h->mode == PWPP_MODE_FRESH) {
         bt.P.hist_cap = h->fresh_hist_cap;
         bt.st_scalar = h->d_st_fresh.p;
@@ -749,7 +736,6 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
     const bool split_k5 = h->split_k5 != 0 && h->mode == PWPP_MODE_STREAMS && frames <= 64 && !h->profiling && bt.debug == 0 &&
                           h->output_order != PWPP_ORDER_REFERENCE && h->dp.min_pts != 0;
     bt.k5_split = split_k5 ? h->split_k5 : 0;
-    bt.fuse_scan = h->fuse_scan;
     bt.cap_off = one_pass ? h->d_cap_off.p : nullptr;
     if (one_pass) {
         bt.arena_base = h->arena_base;
@@ -805,76 +791,53 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
             first[(size_t)r] = f1 > frames ? frames : f1;
         }
         lrc = pre_cleared ? 0 : pwpp_launch_clear(&bt, h->stream);
-        if (h->overlap_mode == 1) {
-            // A software pipeline over the two streams: the MEMORY stream bins range r + 2 and then writes the lists of
-            // range r, the FIT stream runs the plane fits (and K5) of range r + 1 meanwhile -- the streams never run the
-            // same kind of stage at the same time (two whole-range pipelines side by side start in lock step: both
-            // binning, then both fitting).  Events: range binned -> its fits may start; range fitted -> its lists.
-            while (h->ev_ranges.size() < 2 * (size_t)R) {
-                hipEvent_t e = nullptr;
-                HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                h->ev_ranges.push_back(e);
-            }
-            auto stage = [&](int r, int stages, hipStream_t st) {
-                if (lrc != 0 || first[(size_t)r + 1] <= first[(size_t)r]) return;
-                const PwppBatch v = range(first[(size_t)r], first[(size_t)r + 1] - first[(size_t)r]);
-                lrc = pwpp_launch_pipeline(&v, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stages);
-            };
-            // (the fit stages go round a few streams: a fit kernel ends with the tail of its longest waves, and the next
-            // range's kernels fill the machine meanwhile)
-            while ((int)h->extra_streams.size() + 1 < h->num_fit_streams) {
-                hipStream_t st = nullptr;
-                HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-                h->extra_streams.push_back(st);
-            }
-            hipStream_t mem = h->stream;
-            const bool masked = h->masked_mem != nullptr && (int)h->masked_fit.size() >= h->num_fit_streams;
-            if (masked) {  // the CU-partitioned streams: fork from the main stream (descriptor copy, k_clear), join at the end
-                mem = h->masked_mem;
-                HIPCHK(hipEventRecord(h->aux_fork, h->stream));
-                HIPCHK(hipStreamWaitEvent(mem, h->aux_fork, 0));
-            }
-            // (every record / wait is checked: a failed one would leave the fit streams unordered against binning and
-            // k_emit, and the batch would "succeed" with racy results -- ADVICE r02)
-            auto ordered_ok = [&](hipError_t e) {
-                if (e != hipSuccess && lrc == 0) lrc = (int)e;
-            };
-            auto bin = [&](int r) {
-                const int k = r % h->num_fit_streams;
-                hipStream_t fit = masked ? h->masked_fit[(size_t)k] : (k == 0 ? h->aux_stream : h->extra_streams[(size_t)k - 1]);
-                stage(r, 1, mem);
-                if (lrc == 0) ordered_ok(hipEventRecord(h->ev_ranges[2 * (size_t)r], mem));
-                if (lrc == 0) ordered_ok(hipStreamWaitEvent(fit, h->ev_ranges[2 * (size_t)r], 0));
-                stage(r, 2, fit);
-                if (lrc == 0) ordered_ok(hipEventRecord(h->ev_ranges[2 * (size_t)r + 1], fit));
-            };
-            auto lists = [&](int r) {
-                if (lrc == 0) ordered_ok(hipStreamWaitEvent(mem, h->ev_ranges[2 * (size_t)r + 1], 0));
-                stage(r, 4, mem);
-            };
-            bin(0);
-            if (R > 1) bin(1);
-            for (int r = 0; r < R; ++r) {
-                lists(r);
-                if (r + 2 < R) bin(r + 2);
-            }
-            // (the memory stream ends with the lists of the last range, which wait for its fits: h->stream is the join)
-            if (masked && lrc == 0) {
-                ordered_ok(hipEventRecord(h->aux_join, mem));
-                ordered_ok(hipStreamWaitEvent(h->stream, h->aux_join, 0));
-            }
-        } else {
-            // whole ranges alternating between the two streams
-            HIPCHK(hipEventRecord(h->aux_fork, h->stream));
-            HIPCHK(hipStreamWaitEvent(h->aux_stream, h->aux_fork, 0));
-            for (int r = 0; r < R && lrc == 0; ++r)
-                if (first[(size_t)r + 1] > first[(size_t)r]) {
-                    const PwppBatch v = range(first[(size_t)r], first[(size_t)r + 1] - first[(size_t)r]);
-                    lrc = pwpp_launch_pipeline(&v, (r & 1) ? h->aux_stream : h->stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 7);
-                }
-            HIPCHK(hipEventRecord(h->aux_join, h->aux_stream));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->aux_join, 0));
+        // A software pipeline over the two streams: the MEMORY stream bins range r + 2 and then writes the lists of
+        // range r, the FIT stream runs the plane fits (and K5) of range r + 1 meanwhile -- the streams never run the
+        // same kind of stage at the same time (two whole-range pipelines side by side start in lock step: both
+        // binning, then both fitting).  Events: range binned -> its fits may start; range fitted -> its lists.
+        while (h->ev_ranges.size() < 2 * (size_t)R) {
+            hipEvent_t e = nullptr;
+            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            h->ev_ranges.push_back(e);
         }
+        auto stage = [&](int r, int stages, hipStream_t st) {
+            if (lrc != 0 || first[(size_t)r + 1] <= first[(size_t)r]) return;
+            const PwppBatch v = range(first[(size_t)r], first[(size_t)r + 1] - first[(size_t)r]);
+            lrc = pwpp_launch_pipeline(&v, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stages);
+        };
+        // (the fit stages go round a few streams: a fit kernel ends with the tail of its longest waves, and the next
+        // range's kernels fill the machine meanwhile)
+        while ((int)h->extra_streams.size() + 1 < h->num_fit_streams) {
+            hipStream_t st = nullptr;
+            HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            h->extra_streams.push_back(st);
+        }
+        const hipStream_t mem = h->stream;
+        // (every record / wait is checked: a failed one would leave the fit streams unordered against binning and
+        // k_emit, and the batch would "succeed" with racy results -- ADVICE r02)
+        auto ordered_ok = [&](hipError_t e) {
+            if (e != hipSuccess && lrc == 0) lrc = (int)e;
+        };
+        auto bin = [&](int r) {
+            const int k = r % h->num_fit_streams;
+            hipStream_t fit = k == 0 ? h->aux_stream : h->extra_streams[(size_t)k - 1];
+            stage(r, 1, mem);
+            if (lrc == 0) ordered_ok(hipEventRecord(h->ev_ranges[2 * (size_t)r], mem));
+            if (lrc == 0) ordered_ok(hipStreamWaitEvent(fit, h->ev_ranges[2 * (size_t)r], 0));
+            stage(r, 2, fit);
+            if (lrc == 0) ordered_ok(hipEventRecord(h->ev_ranges[2 * (size_t)r + 1], fit));
+        };
+        auto lists = [&](int r) {
+            if (lrc == 0) ordered_ok(hipStreamWaitEvent(mem, h->ev_ranges[2 * (size_t)r + 1], 0));
+            stage(r, 4, mem);
+        };
+        bin(0);
+        if (R > 1) bin(1);
+        for (int r = 0; r < R; ++r) {
+            lists(r);
+            if (r + 2 < R) bin(r + 2);
+        }
+        // (the memory stream ends with the lists of the last range, which wait for its fits: h->stream is the join)
     } else {
         lrc = pwpp_launch_pipeline(&bt, h->stream, h->profiling ? h->ev_k : nullptr, h->aux_stream, h->aux_fork, h->aux_join,
                                    ordered ? h->d_ord_a.p : nullptr, ordered ? h->d_ord_b.p : nullptr, 7);
@@ -1208,12 +1171,9 @@ int pwpp_create(const pwpp_params *p, int device, pwpp_handle **out) {
         std::fprintf(stderr, "pwpp: PWPP_DEBUG_FLAGS has both timing-probe sets (4 and 8), which share one array: 8 dropped\n");
     }
     if (const char *e = std::getenv("PWPP_FIT_PLAN")) h->fit_plan = e;
-    h->fit_concurrent = std::getenv("PWPP_FIT_CONCURRENT") != nullptr;
     h->no_one_pass = std::getenv("PWPP_NO_ONE_PASS") != nullptr;
     if (const char *e = std::getenv("PWPP_ONE_PASS_MIN_FRAMES")) h->one_pass_min_frames = h->one_pass_min_fresh = std::atoi(e);
     if (const char *e = std::getenv("PWPP_OVERLAP_RANGES")) h->overlap_ranges = std::atoi(e) < 2 ? 2 : std::atoi(e);
-    if (const char *e = std::getenv("PWPP_OVERLAP_MODE")) h->overlap_mode = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PWPP_BIN_BLOCK")) h->bin_block = std::atoi(e) == 128 ? 128 : (std::atoi(e) == 512 ? 512 : (std::atoi(e) == 1024 ? 1024 : 256));
     if (const char *e = std::getenv("PWPP_FIT_STREAMS")) h->num_fit_streams = std::atoi(e) < 1 ? 1 : (std::atoi(e) > 8 ? 8 : std::atoi(e));
     if (const char *e = std::getenv("PWPP_HI_SPLIT")) h->dp.hi_split = (float)std::atof(e);
     if (const char *e = std::getenv("PWPP_HI_SPLIT_ZONES")) h->dp.split_end = h->dp.bin_base[std::atoi(e) < 0 ? 0 : (std::atoi(e) > 4 ? 4 : std::atoi(e))];
@@ -1223,12 +1183,12 @@ int pwpp_create(const pwpp_params *p, int device, pwpp_handle **out) {
         else std::fprintf(stderr, "pwpp: ignoring PWPP_ONE_PASS_SCALE=%s (a positive number up to 1024 expected)\n", e);
     }
     if (std::getenv("PWPP_EXACT_MOMENTS")) std::fprintf(stderr, "pwpp: exact_moments=%d taken from the environment (PWPP_EXACT_MOMENTS)\n", h->dp.fxp_wide);
-    if (h->debug_flags || !h->fit_plan.empty() || h->fit_concurrent || h->no_one_pass || std::getenv("PWPP_ONE_PASS_MIN_FRAMES") ||
+    if (h->debug_flags || !h->fit_plan.empty() || h->no_one_pass || std::getenv("PWPP_ONE_PASS_MIN_FRAMES") ||
         std::getenv("PWPP_ONE_PASS_SCALE") || std::getenv("PWPP_OVERLAP") || std::getenv("PWPP_OVERLAP_RANGES") || std::getenv("PWPP_HI_SPLIT") ||
         std::getenv("PWPP_HI_SPLIT_ZONES"))
-        std::fprintf(stderr, "pwpp: tuning options taken from the environment (PWPP_*): debug_flags=%d fit_plan='%s' fit_concurrent=%d "
+        std::fprintf(stderr, "pwpp: tuning options taken from the environment (PWPP_*): debug_flags=%d fit_plan='%s' "
                              "no_one_pass=%d one_pass_min_frames=%d one_pass_scale=%g overlap=%d hi_split=%g (first %d bins)\n", h->debug_flags,
-                     h->fit_plan.c_str(), (int)h->fit_concurrent, (int)h->no_one_pass, h->one_pass_min_frames, h->one_pass_scale,
+                     h->fit_plan.c_str(), (int)h->no_one_pass, h->one_pass_min_frames, h->one_pass_scale,
                      std::getenv("PWPP_OVERLAP") ? std::atoi(std::getenv("PWPP_OVERLAP")) : 1, (double)h->dp.hi_split, h->dp.split_end);
     const int storage = p->max_elevation_storage > p->max_flatness_storage ? p->max_elevation_storage : p->max_flatness_storage;
     h->stream_hist_cap = (storage + max_near_sectors + 1024 + 1) & ~1;  // (even: k_gle_tgr fetches the histories two entries at a time)
@@ -1326,8 +1286,6 @@ int pwpp_destroy(pwpp_handle *h) {
         if (h->ev_k[k]) (void)hipEventDestroy(h->ev_k[k]);
     for (hipEvent_t e : h->ev_ranges) (void)hipEventDestroy(e);
     for (hipStream_t st : h->extra_streams) (void)hipStreamDestroy(st);
-    for (hipStream_t st : h->masked_fit) (void)hipStreamDestroy(st);
-    if (h->masked_mem) (void)hipStreamDestroy(h->masked_mem);
     if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
     if (h->aux_join) (void)hipEventDestroy(h->aux_join);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
@@ -1950,50 +1908,8 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         for (const char *c = value; *c; ++c)
             if (!std::strchr("SWBH0123456789.:,", *c)) return fail(PWPP_E_ARG, "fit_plan '%s': unexpected character '%c'", value, *c);
         h->fit_plan = value;
-    } else if (k == "fit_concurrent") {
-        h->fit_concurrent = std::atoi(value) != 0;
     } else if (k == "one_pass") {
         h->no_one_pass = std::atoi(value) == 0;
-    } else if (k == "cu_split") {
-        // "N" or "N:mode": the overlap schedule's memory stream (binning, index lists) on N of the 256 CUs, the fit streams on the
-        // others.  mode 0: the N lowest bits of the mask; mode 1: the bits i with (i mod 8) < N / 32 (whichever of the two is "whole
-        // XCDs" depends on how the driver numbers the CUs of the eight XCDs in a queue's mask).  "0": off.
-        int n = 0, mode = 0;
-        if (std::sscanf(value, "%d:%d", &n, &mode) < 1 || n < 0 || n >= 256 || (mode != 0 && mode != 1))
-            return fail(PWPP_E_ARG, "cu_split=%s: N or N:mode with 0 <= N < 256, mode 0 or 1 expected", value);
-        //  mode 1 deals whole groups of 32 CUs: (i mod 8) < N / 32 is empty below 32 and everything at 256 -- an all-zero
-        // CU mask is not a stream the runtime can create
-        if (mode == 1 && n != 0 && (n % 32 != 0 || n < 32 || n > 224))
-            return fail(PWPP_E_ARG, "cu_split=%s: mode 1 takes N = 32, 64, ... 224 (whole groups of 32 CUs)", value);
-        sync_all_streams(h);
-        for (hipStream_t st : h->masked_fit) (void)hipStreamDestroy(st);
-        h->masked_fit.clear();
-        if (h->masked_mem) (void)hipStreamDestroy(h->masked_mem);
-        h->masked_mem = nullptr;
-        h->cu_split_mem = n;
-        h->cu_split_mode = mode;
-        if (n > 0) {
-            uint32_t mm[8] = {}, mf[8] = {};
-            for (int i = 0; i < 256; ++i) {
-                const bool to_mem = mode == 0 ? i < n : (i % 8) < n / 32;
-                (to_mem ? mm : mf)[i / 32] |= 1u << (i % 32);
-            }
-            bool mem_empty = true, fit_empty = true;
-            for (int w = 0; w < 8; ++w) {
-                mem_empty = mem_empty && mm[w] == 0u;
-                fit_empty = fit_empty && mf[w] == 0u;
-            }
-            if (mem_empty || fit_empty) {
-                h->cu_split_mem = 0;
-                return fail(PWPP_E_ARG, "cu_split=%s: one of the two CU masks comes out empty", value);
-            }
-            HIPCHK(hipExtStreamCreateWithCUMask(&h->masked_mem, 8, mm));
-            for (int k2 = 0; k2 < 8; ++k2) {
-                hipStream_t st = nullptr;
-                HIPCHK(hipExtStreamCreateWithCUMask(&st, 8, mf));
-                h->masked_fit.push_back(st);
-            }
-        }
     } else if (k == "exact_moments") {
         // the width of the plane-fit sums (include/pwpp.h): "1" = contract v4, a 2^-30 m grid; "0" = rounds 3-5's 2^-21 m grid.
         // The per-bin origins do not depend on it; shift and z half-range do.
@@ -2002,8 +1918,6 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         std::vector<float2> origin;
         h->dp.fxp_wide = v;
         h->dp.fxp_zr = (float)fxp_geometry(h->dp, origin, h->dp.fxp_shift, v != 0);
-    } else if (k == "fuse_scan") {
-        h->fuse_scan = std::atoi(value) != 0;
     } else if (k == "split_k5") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "split_k5=%s: 0, 1 or 2 expected", value);
@@ -2019,18 +1933,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         if (!(v > 0.0 && v <= 1024.0)) return fail(PWPP_E_ARG, "one_pass_scale=%s: a positive number up to 1024 expected", value);
         h->one_pass_scale = v;
         h->table_stale = true;  // rebuild the capacity table
-    } else if (k == "bin_block") {
-        const int v = std::atoi(value);
-        if (v != 128 && v != 256 && v != 512 && v != 1024) return fail(PWPP_E_ARG, "bin_block=%s: 128, 256, 512 or 1024 expected", value);
-        h->bin_block = v;
     } else if (k == "fit_streams") {
         const int v = std::atoi(value);
         if (v < 1 || v > 8) return fail(PWPP_E_ARG, "fit_streams=%s: 1..8 expected", value);
         h->num_fit_streams = v;
-    } else if (k == "overlap_mode") {
-        const int v = std::atoi(value);
-        if (v != 0 && v != 1) return fail(PWPP_E_ARG, "overlap_mode=%s: 0 (whole ranges side by side) or 1 (memory / fit pipeline) expected", value);
-        h->overlap_mode = v;
     } else if (k == "overlap_ranges") {
         const int v = std::atoi(value);
         if (v < 2 || v > 64) return fail(PWPP_E_ARG, "overlap_ranges=%s: 2..64 expected", value);

@@ -134,8 +134,7 @@ __host__ __device__ inline uint32_t pwpp_member_offset(uint32_t off, int part, u
 struct PwppFrameResult {
     int32_t n_ground, n_nonground, n_patches, n_rnr, n_oor, n_dropped;
     int32_t hist_state;  // (entries of the fullest A-GLE history after this frame << 1) | a push found its slab full
-    int32_t overflow;  // (bits 8..: scratch of the binning kernels -- the fused scan's tickets, or the cursor of the frame's overflow arena;
-                       // zero again when k_czm_scan is done)
+    int32_t overflow;  // (bits 8..: the cursor of the frame's overflow arena, written by k_czm_bin_scatter; zero again when k_czm_scan is done)
                        // bit 0: one-pass binning: some bin of this frame outgrew its segment AND the arena (the batch is redone on the two-pass
                        // path); bit 1: some patch of the frame needs the plane fitted before it (PwppPatchRec.valid bit 2): K5 and K6
                        // leave the frame alone and the host runs k_fit_fixup + K5 + K6 for it when the batch lands; bit 2: the final
@@ -199,7 +198,6 @@ struct PwppBatch {
     float *normals;              // [frames][B][3]
     PwppFrameResult *results;    // [frames]
     PwppFrameResult *results_host;  // [frames] pinned host mirror, written by K6 (no D2H copy command behind the pipeline)
-    int fuse_scan;               // a few frames: K2 inside K1' (the last workgroup of a frame to take a ticket scans) instead of a kernel of its own
     int k5_split;                // K5 in two launches (k_gle_tgr PART 1 / 2): the second on the handle's other stream, joined by the host before the next call
     unsigned long long *dbg;     // [64] timing probes, only written when debug & 4
     // Per-point labels (pwpp_set_labels, PWPP_ORDER_CLOUD), written behind the lists of this launch's frames; null = off
@@ -215,7 +213,6 @@ struct PwppBatch {
     int64_t point_first, point_count;  // the per-point slots of this launch's frames (contiguous: the fills of labels and point planes)
     const char *fit_plan;        // option "fit_plan": overrides the plan pwpp_launch_fit would choose; null or empty = automatic
     int32_t plan_frames;         // frames the automatic fit plan is chosen for: the WHOLE call's when this batch is one of its frame ranges (0: num_frames)
-    int32_t fit_concurrent;      // option "fit_concurrent": the classes of a plan side by side on two streams
     int32_t emit_parts;          // waves per bin in k_emit (1..8, from the largest bin seen so far)
     // Big batches (round 5): one wave per bin, and the FEW bins that have held long lists so far (pseudo-bins of a sensor that sees
     // beyond max_range or its own vehicle, the near bins of a dense cloud) get extra waves from a second, small launch -- not every
@@ -225,7 +222,6 @@ struct PwppBatch {
     int32_t emit_long_n;
     int32_t emit_long_parts;     // waves per listed bin of the second launch
     int32_t emit_long_pass;      // set in the copy of the batch the second launch gets
-    int32_t bin_block;           // option "bin_block": threads per workgroup of k_czm_bin_scatter (256, 512, 1024; four points each)
     // The counters a call starts from (part_count [+ part_off, part_cursor], results) exist TWICE; a call works on one copy
     // and its K5 zeroes the frame's share of the OTHER copy, so that the next call of the same shape needs no clearing
     // kernel in front of its binning (a single frame: k_clear and the dispatch gap behind it were 5-7 of 105 us).

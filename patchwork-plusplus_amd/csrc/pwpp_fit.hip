@@ -2650,9 +2650,7 @@ extern "C" const char *pwpp_big_batch_plan(int max_n, int num_bins, int wide) {
 }
 #define PWPP_LATENCY_FIT_PLAN "H64:511"  // (round 6, both grids: four waves from 512 points up -- frames 4 and 5 of the KITTI samples 102 -> 94 and 144 -> 123 us,
                                          // the others unchanged: profiles/r06_latency_plans.txt; rounds 3-5: from 1024 up)
-// `aux` (optional): a second stream + two events, for the fit_concurrent option (classes of a plan side by side).
-extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev, hipStream_t aux,
-                               hipEvent_t aux_fork, hipEvent_t aux_join) {
+extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev) {
     const PwppBatch &B = *batch;
     const int F = B.num_frames, nb = B.P.num_bins;
     const unsigned min_pts = B.P.min_pts < 1 ? 1u : (unsigned)(B.P.min_pts > 0xffffffffull ? 0xffffffffu : B.P.min_pts);
@@ -2703,16 +2701,6 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
     }
     int k_lo = 0, slot = 0;
     unsigned n_lo = 1;
-    // The classes of a plan are independent of each other: the fit_concurrent option runs the later ones on
-    // the aux stream beside the first (fork after K3, join before K5; +3.5 % on the 1024-frame batch;
-    // off by default: the per-kernel times bench.py reports would lose their meaning).
-    const bool concurrent = aux != nullptr && !ev && B.fit_concurrent != 0;
-    const bool fork = concurrent;
-    if (fork) {  // every class only depends on K3
-        hipError_t e = hipEventRecord(aux_fork, stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(aux, aux_fork, 0);
-        if (e != hipSuccess) return (int)e;  // (unordered classes would race with K3: nothing has been launched yet)
-    }
     const char *p = plan;
     while (*p && slot < 5) {
         char mode = p[0];
@@ -2732,21 +2720,20 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
         const int k_hi = pwpp_size_bucket(upper + 1u);
         if (k_hi > k_lo) {
             if (ev) (void)hipEventRecord(ev[slot], stream);
-            const hipStream_t ls = (concurrent && slot >= 1) ? aux : stream;  // later classes beside the first one
             const unsigned patches = cap(n_lo);
             const dim3 grid(F, (patches * (unsigned)g + kBlock - 1) / kBlock);
             // (every kernel exists for both widths of the arithmetic contract, PwppDevParams.fxp_wide)
 #define PWPP_LAUNCH2(kern, ...) do { if (B.P.fxp_wide) hipLaunchKernelGGL((kern<true>), __VA_ARGS__); else hipLaunchKernelGGL((kern<false>), __VA_ARGS__); } while (0)
 #define PWPP_LAUNCH_T(kern, a, ...) do { if (B.P.fxp_wide) hipLaunchKernelGGL((kern<a, true>), __VA_ARGS__); else hipLaunchKernelGGL((kern<a, false>), __VA_ARGS__); } while (0)
 #define PWPP_LAUNCH_W(a, b, ...) do { if (B.P.fxp_wide) hipLaunchKernelGGL((k_fit_w64<a, b, true>), __VA_ARGS__); else hipLaunchKernelGGL((k_fit_w64<a, b, false>), __VA_ARGS__); } while (0)
-            if (mode == 'S' && g == 8) PWPP_LAUNCH_T(k_fit_srows, 8, grid, dim3(kBlock), 0, ls, B, k_lo, k_hi);
-            else if (mode == 'S' && g == 16) PWPP_LAUNCH_T(k_fit_srows, 16, grid, dim3(kBlock), 0, ls, B, k_lo, k_hi);
-            else if (mode == 'S' && g == 32) PWPP_LAUNCH_T(k_fit_srows, 32, grid, dim3(kBlock), 0, ls, B, k_lo, k_hi);
-            else if (mode == 'S' && g == 64) PWPP_LAUNCH_T(k_fit_srows, 64, grid, dim3(kBlock), 0, ls, B, k_lo, k_hi);
+            if (mode == 'S' && g == 8) PWPP_LAUNCH_T(k_fit_srows, 8, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
+            else if (mode == 'S' && g == 16) PWPP_LAUNCH_T(k_fit_srows, 16, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
+            else if (mode == 'S' && g == 32) PWPP_LAUNCH_T(k_fit_srows, 32, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
+            else if (mode == 'S' && g == 64) PWPP_LAUNCH_T(k_fit_srows, 64, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
             else if (mode == 'H') {  // "H64:<n>": up to n points a wave per patch, four waves above (up to 2^19 - 1 points), everything in one launch
                 const int k_top = pwpp_size_bucket(2023u * 256u + 1u);
                 const unsigned nb_big = cap(pwpp_bucket_floor(k_hi));
-                PWPP_LAUNCH2(k_fit_hybrid, dim3(F, nb_big + (patches + kWaves - 1) / kWaves), dim3(kBlock), 0, ls, B, k_hi, k_top, nb_big);
+                PWPP_LAUNCH2(k_fit_hybrid, dim3(F, nb_big + (patches + kWaves - 1) / kWaves), dim3(kBlock), 0, stream, B, k_hi, k_top, nb_big);
                 k_lo = k_top;
                 n_lo = pwpp_bucket_floor(k_top);
                 ++slot;
@@ -2754,17 +2741,17 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
                 if (*p == ',') ++p;
                 continue;
             }
-            else if (mode == 'B') PWPP_LAUNCH2(k_fit_brows, dim3(F, patches), dim3(kBlock), 0, ls, B, k_lo, k_hi);
+            else if (mode == 'B') PWPP_LAUNCH2(k_fit_brows, dim3(F, patches), dim3(kBlock), 0, stream, B, k_lo, k_hi);
             else if (mode == 'W') {  // "W<lanes per patch>.<patches per wave>"
                 if (pw == 0) pw = 64;
                 const dim3 wgrid(F, (patches + (unsigned)pw - 1) / (unsigned)pw), wblock(64);  // one wave per workgroup
-                if (g == 16 && pw == 64) PWPP_LAUNCH_W(16, 64, wgrid, wblock, 0, ls, B, k_lo, k_hi);
-                else if (g == 16 && pw == 32) PWPP_LAUNCH_W(16, 32, wgrid, wblock, 0, ls, B, k_lo, k_hi);
-                else if (g == 16 && pw == 16) PWPP_LAUNCH_W(16, 16, wgrid, wblock, 0, ls, B, k_lo, k_hi);
-                else if (g == 64 && pw == 16) PWPP_LAUNCH_W(64, 16, wgrid, wblock, 0, ls, B, k_lo, k_hi);
-                else if (g == 64 && pw == 8) PWPP_LAUNCH_W(64, 8, wgrid, wblock, 0, ls, B, k_lo, k_hi);
-                else if (g == 64 && pw == 4) PWPP_LAUNCH_W(64, 4, wgrid, wblock, 0, ls, B, k_lo, k_hi);
-                else if (g == 64 && pw == 2) PWPP_LAUNCH_W(64, 2, wgrid, wblock, 0, ls, B, k_lo, k_hi);
+                if (g == 16 && pw == 64) PWPP_LAUNCH_W(16, 64, wgrid, wblock, 0, stream, B, k_lo, k_hi);
+                else if (g == 16 && pw == 32) PWPP_LAUNCH_W(16, 32, wgrid, wblock, 0, stream, B, k_lo, k_hi);
+                else if (g == 16 && pw == 16) PWPP_LAUNCH_W(16, 16, wgrid, wblock, 0, stream, B, k_lo, k_hi);
+                else if (g == 64 && pw == 16) PWPP_LAUNCH_W(64, 16, wgrid, wblock, 0, stream, B, k_lo, k_hi);
+                else if (g == 64 && pw == 8) PWPP_LAUNCH_W(64, 8, wgrid, wblock, 0, stream, B, k_lo, k_hi);
+                else if (g == 64 && pw == 4) PWPP_LAUNCH_W(64, 4, wgrid, wblock, 0, stream, B, k_lo, k_hi);
+                else if (g == 64 && pw == 2) PWPP_LAUNCH_W(64, 2, wgrid, wblock, 0, stream, B, k_lo, k_hi);
                 else return (int)hipErrorInvalidValue;
             }
             else return (int)hipErrorInvalidValue;
@@ -2780,19 +2767,7 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
     if (ev) (void)hipEventRecord(ev[5], stream);
     // whatever is larger than the plan's last class: a workgroup per patch (none can exist when the largest
     // frame of the batch is smaller than that class's upper bound -- one launch less on the latency path)
-    const bool rest_possible = (unsigned)B.max_n >= n_lo;
-    if (!rest_possible) {
-        // nothing left
-    } else if (fork) {
-        PWPP_LAUNCH2(k_fit_stream, dim3(F, cap(n_lo)), dim3(kBlock), 0, aux, B, k_lo);
-    } else {
-        PWPP_LAUNCH2(k_fit_stream, dim3(F, cap(n_lo)), dim3(kBlock), 0, stream, B, k_lo);
-    }
-    if (fork) {
-        hipError_t e = hipEventRecord(aux_join, aux);
-        if (e == hipSuccess) e = hipStreamWaitEvent(stream, aux_join, 0);
-        if (e != hipSuccess) return (int)e;  // (the caller synchronises every stream on an error: pwpp_capi.cpp)
-    }
+    if ((unsigned)B.max_n >= n_lo) PWPP_LAUNCH2(k_fit_stream, dim3(F, cap(n_lo)), dim3(kBlock), 0, stream, B, k_lo);
     if (ev) (void)hipEventRecord(ev[6], stream);
     return (int)hipGetLastError();
 }

@@ -295,11 +295,9 @@ __global__ __launch_bounds__(kBlock) void k_czm_bin(PwppBatch Bt) {
 // ------------------------------------------------------------------------------------------
 // K2  exclusive scan of the per-frame histogram
 // ------------------------------------------------------------------------------------------
-// The body of K2 for frame f (yblock 0: the scan; 1..8: the snapshot workgroups of a stream frame).  A kernel of its own
-// (k_czm_scan, below K1') for batches; for fewer than eight frames the LAST workgroup of K1' to finish a frame runs it in place
-// (FUSED: no kernel boundary between binning and scan, 2.5-3 us of a single frame's chain).
-template <bool FUSED>
-__device__ __forceinline__ void czm_scan_frame(const PwppBatch &Bt, const int f, const int yblock) {
+// blockIdx.x: the frame; blockIdx.y 0: the scan, 1..8: the snapshot workgroups of a stream frame.
+__global__ __launch_bounds__(kBlock) void k_czm_scan(PwppBatch Bt) {
+    const int f = blockIdx.x, yblock = blockIdx.y;
     __shared__ unsigned s_part[kBlock];
     // the frame's part counts and offsets stay in LDS for the second half of the kernel (reading back what other
     // threads just wrote to global memory is a round trip of its own, and a single frame waits for this chain)
@@ -351,7 +349,7 @@ __device__ __forceinline__ void czm_scan_frame(const PwppBatch &Bt, const int f,
     __shared__ unsigned s_nov, s_reloc_fail;
     __shared__ unsigned short s_ovp[PWPP_MAX_RELOC];
     __shared__ unsigned s_ovoff[PWPP_MAX_RELOC];
-    const bool arena = !FUSED && Bt.cap_off && Bt.arena_slots > 0u;
+    const bool arena = Bt.cap_off && Bt.arena_slots > 0u;
     if (threadIdx.x == 0) s_nov = s_reloc_fail = 0u;
     if (arena) __syncthreads();
     if (Bt.cap_off) {  // one-pass binning: fixed segments; a part never reports more points than its segment holds
@@ -367,8 +365,7 @@ __device__ __forceinline__ void czm_scan_frame(const PwppBatch &Bt, const int f,
                 if (p < NP) {
                     seg[q] = Bt.cap_off[p];
                     nxt[q] = Bt.cap_off[p + 1];
-                    // (FUSED: the counts are other workgroups' device-scope atomics of THIS kernel -- read them where those were performed)
-                    c[q] = FUSED ? __hip_atomic_load(&pcnt[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : pcnt[p];
+                    c[q] = pcnt[p];
                     mx[q] = Bt.bin_max[p];
                 }
             }
@@ -388,7 +385,7 @@ __device__ __forceinline__ void czm_scan_frame(const PwppBatch &Bt, const int f,
                     } else {
                         c[q] = cap;
                         pcnt[p] = cap;
-                        atomicOr((unsigned *)&Bt.results[f].overflow, 1u);  // (other workgroups of a fused launch touch this word with atomics)
+                        atomicOr((unsigned *)&Bt.results[f].overflow, 1u);  // (the binning kernel sets bit 0 of this word with atomics too)
                     }
                 }
                 s_pc[p] = c[q];
@@ -601,12 +598,9 @@ __device__ __forceinline__ void czm_scan_frame(const PwppBatch &Bt, const int f,
 // frame's overflow flag (points beyond the segment are not written); the host then redoes the
 // batch on the exact two-pass path, so the result never depends on the capacities.
 // ------------------------------------------------------------------------------------------
-// BLOCK threads, four points each.  The per-workgroup set-up (zeroing the counters, fetching the segment table, the
-// reservation atomics) does not depend on the tile size, so a larger workgroup halves it per point.
-template <int BLOCK, bool FUSE = false>
-__global__ __launch_bounds__(BLOCK, FUSE ? 2 : 8) void k_czm_bin_scatter(PwppBatch Bt, int tiles_per_frame) {
-    constexpr int kBlock = BLOCK;
-    constexpr int kOnePassPts = 4 * BLOCK;  // points per workgroup
+// kBlock threads, four points each.
+__global__ __launch_bounds__(kBlock, 8) void k_czm_bin_scatter(PwppBatch Bt, int tiles_per_frame) {
+    constexpr int kOnePassPts = 4 * kBlock;  // points per workgroup
     extern __shared__ unsigned s_dyn[];  // sized at launch (binning_lds_bytes): 8 KB for the default model
     const int NB = PWPP_NUM_PARTS(Bt.P.num_bins);
     unsigned *s_cnt = s_dyn;             // [parts] points of this workgroup per part, then its first slot in the part
@@ -620,22 +614,11 @@ __global__ __launch_bounds__(BLOCK, FUSE ? 2 : 8) void k_czm_bin_scatter(PwppBat
     const bool spread = tiles_per_frame < 0;
     if (spread) tiles_per_frame = -tiles_per_frame;
     const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
-    if constexpr (FUSE) {  // (few frames only: spread) the workgroups behind the tiles copy the streams' state (K2's snapshot workgroups)
-        static_assert(BLOCK == kBlock, "czm_scan_frame is written for kBlock threads");
-        const int tiles = tiles_per_frame * Bt.num_frames;
-        if (lin >= tiles) {
-            czm_scan_frame<true>(Bt, (lin - tiles) / 8, 1 + (lin - tiles) % 8);
-            return;
-        }
-    }
     const int f = spread ? lin / tiles_per_frame : xcd + 8 * (slot / tiles_per_frame);
     if (f >= Bt.num_frames) return;
     const PwppFrameDesc fd = Bt.frames[f];
     const int first = ((spread ? lin : slot) % tiles_per_frame) * kOnePassPts;
-    if (first >= fd.n) {
-        if (FUSE && fd.n == 0 && first == 0) czm_scan_frame<true>(Bt, f, 0);  // an empty frame: nobody takes a ticket
-        return;
-    }
+    if (first >= fd.n) return;
     const PwppDevParams &P = Bt.P;
     constexpr int kPer = kOnePassPts / kBlock;
     unsigned pc[kPer];  // code | rank inside the workgroup << 16
@@ -741,7 +724,7 @@ __global__ __launch_bounds__(BLOCK, FUSE ? 2 : 8) void k_czm_bin_scatter(PwppBat
             }
         }
     }
-    if (FUSE || Bt.arena_slots == 0u) {  // no arena (a few frames: generous segments, and the fused scan's tickets live where the arena's cursor would)
+    if (Bt.arena_slots == 0u) {  // no arena (a few frames: generous segments)
         if (__any(over) && lane_id() == 0) atomicOr((unsigned *)&Bt.results[f].overflow, 1u);
     } else if (__syncthreads_or(over ? 1 : 0)) {
         // The overflow arena (pwpp_dev.h): the workgroup's spilled points take a run of the frame's arena -- one atomic on the cursor
@@ -779,30 +762,7 @@ __global__ __launch_bounds__(BLOCK, FUSE ? 2 : 8) void k_czm_bin_scatter(PwppBat
     }
     probe();  // 4: stores issued
     if ((Bt.debug & 8) && threadIdx.x == 0) atomicMax(&Bt.dbg[8], wall_clock64());
-    if constexpr (FUSE) {
-        // K2 in place: every workgroup takes a ticket (bits 8.. of the frame's overflow word, zero when the kernel starts); the one
-        // that takes the frame's last runs the scan.  Its inputs are the part counts -- device-scope atomics whose results this
-        // workgroup's threads have all waited for (they needed the reserved ranges) before the barrier above, so they were
-        // performed before the ticket is taken; the scan reads them with device-scope loads.  What the scan writes is read by
-        // the NEXT kernel.
-        __shared__ int s_last;
-        if (threadIdx.x == 0) {
-            const unsigned tiles = (unsigned)((fd.n + kOnePassPts - 1) / kOnePassPts);
-            // (release what this workgroup did -- its count atomics, its overflow flag -- and acquire what the others did, at
-            // agent scope, instead of relying on the order in which gfx950 happens to perform relaxed atomics)
-            const unsigned old = __hip_atomic_fetch_add((unsigned *)&Bt.results[f].overflow, 256u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = (old >> 8) + 1u == tiles;
-            if (s_last) (void)__hip_atomic_fetch_and((unsigned *)&Bt.results[f].overflow, 255u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (s_last) czm_scan_frame<true>(Bt, f, 0);
-    }
 }
-
-// ------------------------------------------------------------------------------------------
-// K2 as a kernel of its own (batches; the two-pass path)
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_czm_scan(PwppBatch Bt) { czm_scan_frame<false>(Bt, blockIdx.x, blockIdx.y); }
 
 // ------------------------------------------------------------------------------------------
 // K3  scatter into bin order
@@ -2874,8 +2834,7 @@ extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, i
 // ------------------------------------------------------------------------------------------
 // host-side launcher used by pwpp_capi.cpp
 // ------------------------------------------------------------------------------------------
-extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev, hipStream_t aux,
-                               hipEvent_t aux_fork, hipEvent_t aux_join);
+extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev);
 extern "C" int pwpp_launch_fixup(const PwppBatch *batch, hipStream_t stream);
 
 // K0: the per-launch zeroing (histogram / cursor slabs and the frame counters) in ONE dispatch; two
@@ -2948,32 +2907,14 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
         if (!B.no_clear) launch_clear(B, stream);
         if (ev) (void)hipEventRecord(ev[0], stream);
         if (B.cap_off) {  // one-pass binning (fixed bin segments)
-            const int bb = B.bin_block == 1024 ? 1024 : (B.bin_block == 512 ? 512 : (B.bin_block == 128 ? 128 : 256));
-            const unsigned gx1 = (unsigned)((B.max_n + 4 * bb - 1) / (4 * bb));
+            const unsigned gx1 = (unsigned)((B.max_n + 4 * kBlock - 1) / (4 * kBlock));
             const bool spread = F < 8;  // (see the kernel: a few frames are dealt over all XCDs)
             const dim3 grid(gx1 * (unsigned)(spread ? F : (F + 7) / 8 * 8));
             const int tpf = spread ? -(int)gx1 : (int)gx1;
-            // K2 inside K1' (option fuse_scan; debug 256 selects the OTHER variant; 128 is taken by K5's statistics).  Rounds 4-5: the default for
-            // a few frames -- no kernel boundary in a single frame's chain.  Round 6: off -- since the ticket that elects the scanning
-            // workgroup is an agent-scope acquire-release it costs what the boundary cost (the L2 write-back of a release:
-            // ~3 us), and the two kernels are 1-2 us FASTER on every KITTI sample.
-            const bool fused = spread && gx1 > 0 && bb == kBlock && ((B.fuse_scan != 0) != ((B.debug & 256) != 0));
-            if (fused) {
-                const dim3 fgrid(gx1 * (unsigned)F + (B.snap_scalar ? 8u * (unsigned)F : 0u));
-                hipLaunchKernelGGL((k_czm_bin_scatter<kBlock, true>), fgrid, dim3(kBlock), binning_lds_bytes(B, 2), stream, B, tpf);
-                if (ev) (void)hipEventRecord(ev[1], stream);
-                if (ev) (void)hipEventRecord(ev[2], stream);
-            } else {
-            if (gx1 > 0) {
-                if (bb == 128) hipLaunchKernelGGL(k_czm_bin_scatter<128>, grid, dim3(128), binning_lds_bytes(B, 2), stream, B, tpf);
-                else if (bb == 256) hipLaunchKernelGGL(k_czm_bin_scatter<256>, grid, dim3(256), binning_lds_bytes(B, 2), stream, B, tpf);
-                else if (bb == 512) hipLaunchKernelGGL(k_czm_bin_scatter<512>, grid, dim3(512), binning_lds_bytes(B, 2), stream, B, tpf);
-                else hipLaunchKernelGGL(k_czm_bin_scatter<1024>, grid, dim3(1024), binning_lds_bytes(B, 2), stream, B, tpf);
-            }
+            if (gx1 > 0) hipLaunchKernelGGL(k_czm_bin_scatter, grid, dim3(kBlock), binning_lds_bytes(B, 2), stream, B, tpf);
             if (ev) (void)hipEventRecord(ev[1], stream);
             hipLaunchKernelGGL(k_czm_scan, dim3(F, B.snap_scalar ? 9 : 1), dim3(kBlock), 0, stream, B);  // (+ eight snapshot workgroups per frame)
             if (ev) (void)hipEventRecord(ev[2], stream);
-            }
         } else {
             if (gx > 0) hipLaunchKernelGGL(k_czm_bin, dim3(gx, F), dim3(kBlock), binning_lds_bytes(B, 1), stream, B);
             if (ev) (void)hipEventRecord(ev[1], stream);
@@ -2984,7 +2925,7 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
     }
     if (stages & 2) {
         const int frc = (stages & 8) ? pwpp_launch_fixup(batch, stream)
-                                     : pwpp_launch_fit(batch, stream, ev ? ev + 3 : nullptr, aux, aux_fork, aux_join);  // records ev[3..9]
+                                     : pwpp_launch_fit(batch, stream, ev ? ev + 3 : nullptr);  // records ev[3..9]
         if (frc) return frc;
         if (B.P.min_pts == 0)
             hipLaunchKernelGGL(k_gle_tgr_seq, dim3(F), dim3(64), 0, stream, B);  // empty bins inherit planes: serial

@@ -444,9 +444,9 @@ class Handle:
         return out[:b].copy()
 
     def set_option(self, name, value):
-        """Tuning / test switches (pwpp_set_option): fit_plan, fit_concurrent, one_pass, one_pass_min_frames,
-        one_pass_scale, overlap_mode, overlap_ranges, fit_streams, bin_block, hi_split, hi_split_zones, debug_flags.
-        None of them changes a result."""
+        """Tuning / test switches (pwpp_set_option): fit_plan, one_pass, exact_moments, split_k5, redo_whole_batch,
+        one_pass_min_frames, one_pass_scale, fit_streams, overlap_ranges, hi_split, hi_split_zones, debug_flags.
+        None of them changes a result except exact_moments (include/pwpp.h)."""
         self._check(self._L.pwpp_set_option(self._h, name.encode(), str(value).encode()))
 
     def workspace_bytes(self):

@@ -143,22 +143,20 @@ def test_device_labels_pointer(kitti):
     assert np.array_equal(labs2, labs) and not out[int(base[-1]):].any()
 
 
-def test_cloud_order_is_deterministic_on_big_batches_and_through_a_pipe(kitti, oracle):
+def test_cloud_order_is_deterministic_on_the_overlap_schedule_and_through_a_pipe(kitti, oracle):
     """128+ frames take the overlap schedule (cloud order does not force the single-stream one): two runs are byte-identical
-    without sorting, in both overlap modes; a pipe of depth 2 too."""
+    without sorting; a pipe of depth 2 too."""
     F = 132
     frames = [kitti[i % 6] for i in range(F)]
     refs = [ol.Estimator(oracle, arith=ol.ARITH_FXP).run(p) for p in kitti]
-    for mode in (1, 0):
-        h = pwpp_hip.Handle()
-        h.set_option("overlap_mode", mode)
-        h.set_order(pwpp_hip.ORDER_CLOUD)
-        h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
-        first = lists_of(h, F)
-        for i in (0, 1, 63, 64, 65, 66, 67, 127, 128, F - 1):
-            check_labels(h, i, frames[i].shape[0], refs[i % 6], cloud=True)
-        h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
-        assert lists_of(h, F) == first
+    h = pwpp_hip.Handle()
+    h.set_order(pwpp_hip.ORDER_CLOUD)
+    h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
+    first = lists_of(h, F)
+    for i in (0, 1, 63, 64, 65, 66, 67, 127, 128, F - 1):
+        check_labels(h, i, frames[i].shape[0], refs[i % 6], cloud=True)
+    h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
+    assert lists_of(h, F) == first
     import torch
     dev = torch.device("cuda", 0)
     tens = [torch.from_numpy(f).to(dev) for f in kitti]

@@ -1158,19 +1158,19 @@ def test_error_reporting_on_the_device(kitti):
             pwpp_hip.Handle(p)
     with pytest.raises(pwpp_hip.PwppError, match="share one probe array"):   # (the two sets of timing probes)
         h.set_option("debug_flags", 4 | 8)
-    with pytest.raises(pwpp_hip.PwppError, match="cu_split"):
-        h.set_option("cu_split", "300")
+    for removed in ("fuse_scan", "cu_split", "fit_concurrent", "overlap_mode", "bin_block"):
+        with pytest.raises(pwpp_hip.PwppError, match="unknown option"):
+            h.set_option(removed, "1")
     h.estimate_ground(kitti[0])   # still usable
     assert h.counts(0)[0] + h.counts(0)[1] == kitti[0].shape[0]
     with pytest.raises(pwpp_hip.PwppError, match="out of range"):
         h.ground_indices(3)
 
 
-def test_schedules_and_binning_variants_give_one_result(kitti, oracle):
-    """The same 136-frame batch through every schedule the library has -- one stream, the in-handle overlap schedule, that schedule
-    on CU-partitioned streams (option cu_split, round 5's experiment), four frame ranges, the scan inside the binning kernel for a
-    single frame (debug 256, or option fuse_scan: rounds 4-5's default for fewer than eight frames) -- and two handles with a batch each in
-    flight: identical counts everywhere, spot frames identical to the oracle."""
+def test_schedules_give_one_result(kitti, oracle):
+    """The same 136-frame batch through every schedule the library has -- one stream, the in-handle overlap schedule, four frame
+    ranges -- and two handles with a batch each in flight: identical counts everywhere, spot frames identical to the oracle; and
+    single frames of a default handle identical to the oracle."""
     refs = [ol.Estimator(oracle, arith=ol.ARITH_FXP).run(k) for k in kitti]
     F = 136
     frames = [kitti[i % 6] for i in range(F)]
@@ -1179,8 +1179,7 @@ def test_schedules_and_binning_variants_give_one_result(kitti, oracle):
     want = h.all_counts().copy()
     for i in (0, 67, 135):
         assert_frame_equal(h, i, refs[i % 6], frames[i].shape[0], check_state=False)
-    for setup in (lambda: h.set_overlap(False), lambda: h.set_overlap(True), lambda: h.set_option("cu_split", "96:0"), lambda: h.set_option("cu_split", "64:1"),
-                  lambda: (h.set_option("cu_split", "0"), h.set_option("overlap_ranges", 4))):
+    for setup in (lambda: h.set_overlap(False), lambda: h.set_overlap(True), lambda: h.set_option("overlap_ranges", 4)):
         setup()
         h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
         assert np.array_equal(h.all_counts(), want)
@@ -1222,13 +1221,7 @@ def test_schedules_and_binning_variants_give_one_result(kitti, oracle):
     with pytest.raises(pwpp_hip.PwppError):  #  a view of a closed pipe's handle fails, it does not touch the freed handle
         view.counts(0)
     one = pwpp_hip.Handle()
-    for flags in (0, 256, 0):
-        one.set_option("debug_flags", flags)
-        for k in (2, 5):
-            one.estimate_ground_batch([kitti[k]], mode=pwpp_hip.MODE_FRESH)
-            assert_frame_equal(one, 0, refs[k], kitti[k].shape[0])
-    one.set_option("fuse_scan", 1)
-    for k in (1, 4):
+    for k in (1, 2, 4, 5):
         one.estimate_ground_batch([kitti[k]], mode=pwpp_hip.MODE_FRESH)
         assert_frame_equal(one, 0, refs[k], kitti[k].shape[0])
 

@@ -357,19 +357,18 @@ def _outputs(h, frames):
     return [(h.point_patches(i).tobytes(), h.point_distances(i).tobytes()) for i in range(frames)]
 
 
-def test_deterministic_on_big_batches_and_through_a_pipe(kitti, oracle):
-    F = 132  # (128+ frames: the overlap schedule, both modes)
+def test_deterministic_on_the_overlap_schedule_and_through_a_pipe(kitti, oracle):
+    F = 132  # (128+ frames: the overlap schedule)
     frames = [kitti[i % 6] for i in range(F)]
     refs = [ol.Estimator(oracle, arith=ol.ARITH_FXP).run(pts) for pts in kitti]
     op = oracle.default_params()
-    for mode in (1, 0):
-        h = handle(overlap_mode=mode)
-        h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
-        first = _outputs(h, F)
-        for i in (0, 1, 63, 64, 65, 66, 67, 127, 128, F - 1):
-            check_point_planes(h, i, frames[i], refs[i % 6], op)
-        h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
-        assert _outputs(h, F) == first, "point planes differ from run to run"
+    h = handle()
+    h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
+    first = _outputs(h, F)
+    for i in (0, 1, 63, 64, 65, 66, 67, 127, 128, F - 1):
+        check_point_planes(h, i, frames[i], refs[i % 6], op)
+    h.estimate_ground_batch(frames, mode=pwpp_hip.MODE_FRESH)
+    assert _outputs(h, F) == first, "point planes differ from run to run"
     import torch
     dev = torch.device("cuda", 0)
     tens = [torch.from_numpy(f).to(dev) for f in frames]
