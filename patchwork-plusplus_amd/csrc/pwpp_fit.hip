@@ -24,7 +24,7 @@
 // The bin-ordered records are planes (pwpp_dev.h): the lowest-point pass streams z alone (4 B per
 // point), every other pass z and {x, y} (12 B); the cloud-index plane is k_emit's (and the tiny-fit gather's), not the passes'.
 // The split of a patch is a bit per slot in the MEMBERSHIP PLANE (pwpp_dev.h), left by every R-GPF round that can be the last, and
-// a patch whose integer totals repeat from one round to the next stops there (exact early termination: k_fit_w64, phase B).
+// a patch whose integer totals repeat from one round to the next stops there (exact early termination: round_converged).
 // A near-zone bin is stored in two parts, below and above a split height: every pass skips the high part
 // when it can prove that none of its points can enter (stage_needs_hi).
 // DESIGN.md section 3 has the measurements that led here (and the variants that were dropped: points
@@ -51,9 +51,6 @@ constexpr int kPPT = 8;  // points per lane held in registers
 #endif
 #ifndef PWPP_W16_WIDE_OCC
 #define PWPP_W16_WIDE_OCC 3  // ... on the wide grid (contract v4): sixteen totals per patch in LDS (12.4 KB per wave) allow three waves per SIMD anyway
-#endif
-#ifndef PWPP_FIT_PREFETCH
-#define PWPP_FIT_PREFETCH 0
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -497,6 +494,96 @@ __device__ __forceinline__ float stage_threshold(int kind, double d, double th_d
     return kind == ST_ITER ? plane_test_threshold(d, th_dist) : plane_test_threshold(0.0, thr_seed);
 }
 
+// ------------------------------------------------------------------------------------------
+// THE CHAIN POLICY (ref :467-554), stated once for fit_srows_body, k_fit_w64 and fit_brows_body: which stage a patch starts
+// with, what the coming pass tests, when an R-GPF round has converged, whether a stage solves, the verticality test and the
+// step to the next stage.  Plain values in and out: every body keeps its state where it likes (locals, W64Owner) and its
+// own points loops, reductions, totals -> mean / covariance and lowest-point selection.  fit_stream_patch shares only the
+// per-frame preamble: its chain is the reference's, point by point, ON PURPOSE -- it is the cross-check of this block.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int first_stage(const PwppDevParams &P, int zone, bool alive = true) {
+    return !alive ? ST_DONE : ((P.enable_RVPF != 0 && zone == 0) ? ST_VPF : ST_SEED);
+}
+// The tests of the coming pass of a patch at stage `kind`, round `it`.  `dual`: the pass of an R-VPF round also sums the band up to
+// the R-GPF seed threshold (dual seed pass, k_fit_w64 / fit_brows_body): thr_seed is then the smaller of the two thresholds and
+// thr_band the larger one, whichever stage they belong to.
+struct PassTests {
+    // seed stages: z < lpr + th_seeds(_v) (ref :108,145); the band's upper end; the largest height threshold of the pass (stage_needs_hi)
+    double thr_seed, thr_band, thr_max;
+    // last: the last R-GPF round (ref :516); wbits: the pass leaves its set in the membership plane (an R-GPF round whose set may be the
+    // final one); comparable: an R-GPF round with a round before it, whose totals gave the plane in force (early termination)
+    bool last, wbits, comparable;
+    float T, T_band;  // the tests in float (lane_stage_accum): the stage's own, the band's
+};
+// (which of the two seed thresholds of a dual pass is the larger one)
+__device__ __forceinline__ bool seeds_v_is_hi(const PwppDevParams &P) { return P.th_seeds_v >= P.th_seeds; }
+__device__ __forceinline__ PassTests pass_tests(const PwppDevParams &P, int kind, int it, double lpr, double plane_d, bool dual) {
+    const bool v_is_hi = seeds_v_is_hi(P);
+    PassTests t;
+    t.thr_seed = lpr + (dual ? (v_is_hi ? P.th_seeds : P.th_seeds_v) : ((kind == ST_VPF || kind == ST_LAZY) ? P.th_seeds_v : P.th_seeds));
+    t.thr_band = lpr + (v_is_hi ? P.th_seeds_v : P.th_seeds);
+    t.thr_max = dual && t.thr_band > t.thr_seed ? t.thr_band : t.thr_seed;
+    t.last = kind == ST_ITER && it == P.num_iter - 1;
+    t.wbits = kind == ST_ITER && (t.last || it >= 1);
+    t.comparable = kind == ST_ITER && !t.last && it >= 1;
+    t.T = stage_threshold(kind, plane_d, P.th_dist, t.thr_seed);
+    t.T_band = dual ? plane_test_threshold(0.0, t.thr_band) : 0.0f;
+    return t;
+}
+// EARLY TERMINATION (exact): the plane is a function of the ten integer totals.  If an R-GPF round's totals equal those of the
+// round before -- which gave the plane this round tested with -- the next plane is this plane bit for bit, hence every later
+// round selects this round's set again and the final plane (ref :537-542) is the one in force: the patch is finished, its
+// split is what this round left in the membership plane (PassTests.wbits).  1-3 points: the tiny-fit path, never compared.
+__device__ __forceinline__ bool round_converged(bool comparable, long long cnt, bool same_totals) { return comparable && cnt > 3 && same_totals; }
+// empty set: the plane in force stays (ref :49); converged: the solve would return the plane in force
+__device__ __forceinline__ bool stage_solves(long long cnt, bool conv) { return cnt > 0 && !conv; }
+// ref :489: the R-VPF round's plane is too steep, the points around it leave the working set
+__device__ __forceinline__ bool plane_is_vertical(const PwppDevParams &P, int kind, float nz) { return kind == ST_VPF && (double)nz < P.uprightness_thr; }
+// VPF -> SEED -> [LAZY] -> ITER -> DONE.  `cnt`: points of this stage's set.  Returns true when the patch is finished: the caller
+// writes its record (write_record; rounds = `it` on return), because who writes differs from kernel to kernel.
+__device__ __forceinline__ bool next_stage(const PwppDevParams &P, int zone, int &kind, int &it, bool vertical, long long cnt, bool last, bool conv) {
+    if (kind == ST_VPF) {
+        ++it;
+        if (!vertical || it >= P.num_iter) {  // ref :506 / loop end
+            kind = ST_SEED;
+            it = 0;
+        }
+    } else if (kind == ST_SEED) {
+        kind = (cnt == 0 && P.enable_RVPF != 0 && zone != 0) ? ST_LAZY : ST_ITER;
+    } else if (kind == ST_LAZY) {
+        kind = ST_ITER;
+    } else if (kind == ST_ITER) {
+        ++it;
+        if (last || conv) {
+            kind = ST_DONE;
+            return true;
+        }
+    }
+    return false;
+}
+// log2 of the lanes of the rows that left a split in the membership plane (write_record's member_lg)
+template <int G>
+__device__ __forceinline__ constexpr int member_lg() { return G == 64 ? 6 : (G == 32 ? 5 : (G == 16 ? 4 : 3)); }
+// what every fit kernel needs of its frame
+struct FrameCtx {
+    PwppFrameDesc fd;
+    uint8_t *member;  // the frame's share of the membership plane
+    // the stream's estimate or the parameter; the zone-0 cut-off (ref :90); fixed-point scale of the sums
+    double sensor_height, cutoff, scale;
+    float zs;  // split height of the near-zone bins' two parts
+};
+__device__ __forceinline__ FrameCtx frame_ctx(const PwppBatch &Bt, int f) {
+    const PwppDevParams &P = Bt.P;
+    FrameCtx c;
+    c.fd = Bt.frames[f];
+    c.member = Bt.member + c.fd.mbase;
+    c.sensor_height = c.fd.state_in >= 0 ? Bt.st_scalar[c.fd.state_in].sensor_height : P.sensor_height;
+    c.cutoff = P.margin * c.sensor_height;
+    c.zs = hi_split_z(P, c.sensor_height);
+    c.scale = (double)(1 << P.fxp_shift);
+    return c;
+}
+
 // The points of this lane that the R-VPF plane removes (ref :495-503): |double(s) + d| < th_dist_v, i.e.
 // t_lo < s < t_hi with t_hi = plane_test_threshold(d, th_dist_v) and t_lo = -plane_test_threshold(-d, th_dist_v)
 // (negation is exact and rounding symmetric).  A point removed before is a NaN and is not hit again.
@@ -719,6 +806,25 @@ __device__ __forceinline__ double row16_sum_f64(double v) {
     step([](int x) { return PWPP_DPP(x, PWPP_DPP_MIR); });
     return v;
 }
+// The sorted-keys shortcut of the lowest-point passes: this lane holds elements 4 * lane + 0..3 of the sorted keys (`lane_in`: its
+// registers are part of the sorted run at all); `part` = the sum of its heights among the keff lowest.  Returns whether every one of
+// those is 0 or has 2^-12 <= |z| < 2^8: multiples of 2^-35 whose partial sums stay below 2^14, so the keff heights add up exactly in
+// a double IN ANY ORDER -- equal to the reference's ascending sum, ref :99-101.  Anything else among the lowest (a denormal, a height of
+// a kilometre, inf, the INF of a row that kept fewer than keff keys) sends the caller to its extraction loop.
+__device__ __forceinline__ bool lowest_keys_sum_exact(unsigned k0, unsigned k1, unsigned k2, unsigned k3, bool lane_in, int lane, int keff, double &part) {
+    const unsigned kk[4] = {k0, k1, k2, k3};
+    part = 0.0;
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const bool sel = lane_in && 4 * lane + r < keff;
+        const float zv = key_z(kk[r]);
+        const unsigned e = (__float_as_uint(zv) >> 23) & 0xffu;
+        ok = ok && (!sel || zv == 0.0f || (e >= 115u && e < 135u));
+        part += sel ? (double)zv : 0.0;
+    }
+    return ok;
+}
 
 // LPR (ref :84-103) of streamed rows, normally in ONE pass over the points: every lane keeps its
 // four smallest eligible keys and the smallest key it had to drop.  The keff smallest of the
@@ -744,11 +850,7 @@ __device__ double srow_lpr(const PatchRef &pts, bool need, bool use_cutoff, doub
     // (the pass is a pure latency chain -- eight loads, ~100 instructions -- so the next chunk's z values are requested
     // before this chunk's are ranked: eight registers, in a phase that is far from the kernels' register peak)
     auto rank_part = [&](unsigned off, unsigned n, unsigned nchunks, const ChunkZ *pre) {
-        PartSel sel;
-        sel.off = off;
-        sel.n = n;
-        sel.c = 0u;
-        sel.moff = 0u;
+        PartSel sel = {off, n, 0u, 0u};
         ChunkZ cp;
         if (pre) cp = *pre;
         else if (nchunks > 0u) load_chunk_z<G>(cp, pts, sel);
@@ -784,23 +886,12 @@ __device__ double srow_lpr(const PatchRef &pts, bool need, bool use_cutoff, doub
     bool quick = false;  // (row-uniform) the sorted-row shortcut below has delivered sum and T
     if constexpr (G == 16) {
         // Round 6: SORT the row's 64 kept keys (row16_sort64) instead of extracting the lowest one by one.  The keff lowest are then
-        // elements 0 .. keff - 1, T is element keff - 1, and their sum is order-free -- hence equal to the reference's ascending sum,
-        // ref :99-101 -- whenever every one of them is 0 or has 2^-12 <= |z| < 2^8: multiples of 2^-35 whose partial sums stay below
-        // 2^14, exact in a double in any order.  Anything else among the lowest (a denormal, a height of a kilometre, inf, the INF of
-        // a row that kept fewer than keff keys) takes the extraction loop below, which works on the sorted registers just as well.
+        // elements 0 .. keff - 1, T is element keff - 1, and their sum is order-free wherever lowest_keys_sum_exact says so.  Anything
+        // else takes the extraction loop below, which works on the sorted registers just as well.
         if (__any(need && keff > 0 && keff <= 64)) {
             row16_sort64(k0, k1, k2, k3);
-            const unsigned kk[4] = {k0, k1, k2, k3};
-            double part = 0.0;
-            bool ok = true;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool sel = 4 * j + r < keff;
-                const float zv = key_z(kk[r]);
-                const unsigned e = (__float_as_uint(zv) >> 23) & 0xffu;
-                ok = ok && (!sel || zv == 0.0f || (e >= 115u && e < 135u));
-                part += sel ? (double)zv : 0.0;
-            }
+            double part;
+            const bool ok = lowest_keys_sum_exact(k0, k1, k2, k3, true, j, keff, part);
             quick = need && keff > 0 && keff <= 64 && Row<G>::ballot(!ok) == 0ull;
             const double s = row16_sum_f64(part);
             const int last = keff > 0 ? keff - 1 : 0;
@@ -818,17 +909,8 @@ __device__ double srow_lpr(const PatchRef &pts, bool need, bool use_cutoff, doub
         if (need && keff > 0 && keff <= 32) {
             const unsigned o0 = k0, o1 = k1, o2 = k2, o3 = k3;
             row64_lowest32(k0, k1, k2, k3);
-            const unsigned kk[4] = {k0, k1, k2, k3};
-            double part = 0.0;
-            bool ok = true;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool sel = j < 8 && 4 * j + r < keff;
-                const float zv = key_z(kk[r]);
-                const unsigned e = (__float_as_uint(zv) >> 23) & 0xffu;
-                ok = ok && (!sel || zv == 0.0f || (e >= 115u && e < 135u));
-                part += sel ? (double)zv : 0.0;
-            }
+            double part;
+            const bool ok = lowest_keys_sum_exact(k0, k1, k2, k3, j < 8, j, keff, part);
             quick = __ballot(!ok) == 0ull;
             const double s = row16_sum_f64(part);  // (lanes 0-15: the sum of lanes 0-7's parts)
             const int last = keff - 1;
@@ -1061,17 +1143,12 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
     const PatchCtx pc = patch_ctx(Bt, f, slot, alive);
     const int bin = pc.bin, zone = pc.zone;
     const unsigned n = pc.n;
-    const PwppFrameDesc fd = Bt.frames[f];
-    const PatchRef pts = patch_ref(Bt, fd, pc);
-    uint8_t *frame_member = Bt.member + fd.mbase;
-    const double sensor_height = fd.state_in >= 0 ? Bt.st_scalar[fd.state_in].sensor_height : P.sensor_height;
-    const double cutoff = P.margin * sensor_height;
-    const float zs = hi_split_z(P, sensor_height);
+    const FrameCtx fc = frame_ctx(Bt, f);
+    const PatchRef pts = patch_ref(Bt, fc.fd, pc);
     const float4 bb = Bt.bin_bbox[bin];
     const bool use_cutoff = zone == 0;
-    const double scale = (double)(1 << P.fxp_shift);
     const bool wide = WIDE || __any(n > 2047u);  // wave-uniform: some row's second moments may leave int64 in the cross-lane sum
-    // the totals of the row's last R-GPF round (early termination, see k_fit_w64): n, S1[3], S2[6] as two 64-bit halves each
+    // the totals of the row's last R-GPF round (early termination, round_converged): n, S1[3], S2[6] as two 64-bit halves each
     __shared__ long long s_prev[kBlock / G][16];
     long long(&prev)[16] = s_prev[threadIdx.x / G];
 
@@ -1080,8 +1157,8 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
     double lpr = 0.0;
     bool lpr_valid = false, z0_set = false;
     float z0 = 0.0f;
-    FxpOrg org = fxp_org(pc.ox, pc.oy, 0.0f, scale, P.fxp_zr);
-    int kind = !alive ? ST_DONE : ((P.enable_RVPF != 0 && zone == 0) ? ST_VPF : ST_SEED);  // row-uniform
+    FxpOrg org = fxp_org(pc.ox, pc.oy, 0.0f, fc.scale, P.fxp_zr);
+    int kind = first_stage(P, zone, alive);  // row-uniform
     int it = 0;
     bool fitted = false;  // a plane of this patch's own exists
 
@@ -1089,26 +1166,22 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
         if (!__any(kind != ST_DONE)) break;
         const bool need_lpr = (kind == ST_VPF || kind == ST_SEED) && !lpr_valid;
         if (__any(need_lpr)) {
-            const double l = srow_lpr<G>(pts, need_lpr, use_cutoff, cutoff, P.num_lpr, (Bt.debug >> 14) & 3);
+            const double l = srow_lpr<G>(pts, need_lpr, use_cutoff, fc.cutoff, P.num_lpr, (Bt.debug >> 14) & 3);
             if (need_lpr) {
                 lpr = l;
                 lpr_valid = true;
                 if (!z0_set) {  // the z origin of this patch's sums: its first lowest-point representative
                     z0 = fxp_z_origin(l);
                     z0_set = true;
-                    org = fxp_org(pc.ox, pc.oy, z0, scale, P.fxp_zr);
+                    org = fxp_org(pc.ox, pc.oy, z0, fc.scale, P.fxp_zr);
                 }
             }
         }
-        const double thr_seed = lpr + ((kind == ST_VPF || kind == ST_LAZY) ? P.th_seeds_v : P.th_seeds);
-        const bool last = kind == ST_ITER && it == P.num_iter - 1;
+        const PassTests t = pass_tests(P, kind, it, lpr, pl.d, false);
+        const bool last = t.last, wbits = t.wbits;
         const bool on = kind != ST_DONE;
-        const bool use_hi = on && stage_needs_hi(kind, pc.n_hi, thr_seed, P.th_dist, pl, bb, zs);  // row-uniform
+        const bool use_hi = on && stage_needs_hi(kind, pc.n_hi, t.thr_max, P.th_dist, pl, bb, fc.zs);  // row-uniform
         const unsigned nchunk_max = wave_max_u32(on ? patch_chunks<G>(pts, use_hi) : 0u);
-        const float T = stage_threshold(kind, pl.d, P.th_dist, thr_seed);  // the pass's test in float (lane_stage_accum)
-        // (early termination and the membership plane: see k_fit_w64 -- every R-GPF round from the second on, and the last one,
-        // leaves its set in the plane; a round whose totals repeat the round before's ends the patch)
-        const bool wbits = kind == ST_ITER && (last || it >= 1);
         MomentsT<WIDE> m;
         m.clear();
         bool clamped = false;
@@ -1118,9 +1191,9 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
             ChunkPts nx;  // the next chunk is in flight while this one is accumulated
             load_chunk<G>(nx, pts, chunk_sel<G>(pts, c + 1u, use_hi, on));
             bool hit = false;
-            const unsigned gmask = lane_stage_accum<G>(cp, kind, T, pl.nx, pl.ny, pl.nz, scale, org, m, hit);
+            const unsigned gmask = lane_stage_accum<G>(cp, kind, t.T, pl.nx, pl.ny, pl.nz, fc.scale, org, m, hit);
             clamped = clamped || (wbits && hit);
-            if (__any(wbits)) store_member<G>(frame_member, chunk_sel<G>(pts, c, use_hi, on), gmask, wbits);
+            if (__any(wbits)) store_member<G>(fc.member, chunk_sel<G>(pts, c, use_hi, on), gmask, wbits);
             cp = nx;
         }
         const long long cnt = Row<G>::sum_i64(m.n);
@@ -1146,7 +1219,7 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
                 for (int k = 0; k < 3; ++k) same = same && prev[1 + k] == s1[k];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) same = same && prev[4 + k] == (long long)(unsigned long long)s2[k] && prev[10 + k] == (long long)(s2[k] >> 64);
-                conv = kind == ST_ITER && !last && it >= 1 && cnt > 3 && same;  // (1-3 points: the tiny-fit path, never compared)
+                conv = round_converged(t.comparable, cnt, same);
                 wave_lds_sync();
                 if (kind == ST_ITER && j == 0) {
                     prev[0] = cnt;
@@ -1161,10 +1234,10 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
                 wave_lds_sync();
             }
             if (__any(clamped && (last || conv)) && lane_id() == 0) flag_clamped(Bt, f);
-            const bool fit = kind != ST_DONE && cnt > 0 && !conv;  // empty: ref :49; converged: the solve would return the plane in force
+            const bool fit = kind != ST_DONE && stage_solves(cnt, conv);
             const bool tiny = fit && cnt <= 3;            // contract v3: the reference's float arithmetic (row-uniform)
             float mt[3], ct[6];
-            if (__any(tiny)) tiny_fit_row<G>(pts, tiny, kind, T, pl.nx, pl.ny, pl.nz, mt, ct);
+            if (__any(tiny)) tiny_fit_row<G>(pts, tiny, kind, t.T, pl.nx, pl.ny, pl.nz, mt, ct);
             if (fit) {
                 float mean[3], c6[6];
                 if (tiny) {
@@ -1184,7 +1257,7 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
             kind = ST_DONE;
         }
         // (the rows of a wave may be at different stages: everything wave-wide -- wave_max_u32 -- stays outside the per-stage branches)
-        const bool vertical = kind == ST_VPF && (double)pl.nz < P.uprightness_thr;  // ref :489
+        const bool vertical = plane_is_vertical(P, kind, pl.nz);
         if (__any(vertical)) {
             bool any = false;
             const unsigned nstrip_max = wave_max_u32(vertical ? patch_chunks<G>(pts, true) : 0u);
@@ -1204,24 +1277,8 @@ __device__ __forceinline__ void fit_srows_body(const PwppBatch &Bt, int b_lo, in
             }
             if (Row<G>::ballot(any) != 0ull) lpr_valid = false;  // the working set changed
         }
-        if (kind == ST_VPF) {
-            ++it;
-            if (!vertical || it >= P.num_iter) {
-                kind = ST_SEED;
-                it = 0;
-            }
-        } else if (kind == ST_SEED) {
-            kind = (cnt == 0 && P.enable_RVPF != 0 && zone != 0) ? ST_LAZY : ST_ITER;
-        } else if (kind == ST_LAZY) {
-            kind = ST_ITER;
-        } else if (kind == ST_ITER) {
-            if (last || conv) {
-                if (j == 0)
-                    write_record(Bt.recs + (size_t)f * P.num_bins + bin, pl, n, (unsigned)cnt, !use_hi && pc.n_hi > 0u, G == 64 ? 6 : (G == 32 ? 5 : (G == 16 ? 4 : 3)), it + 1);
-                kind = ST_DONE;
-            }
-            ++it;
-        }
+        if (next_stage(P, zone, kind, it, vertical, cnt, last, conv) && j == 0)
+            write_record(Bt.recs + (size_t)f * P.num_bins + bin, pl, n, (unsigned)cnt, !use_hi && pc.n_hi > 0u, member_lg<G>(), it);
     }
 }
 
@@ -1277,7 +1334,8 @@ struct W64Owner {
     double lpr;
     float z0;
     int kind, it;
-    int lpr_valid, z0_set, fitted, hi_skipped, stash_valid;
+    int lpr_valid, z0_set, fitted, stash_valid;
+    int hi_skipped;  // the last points phase of this patch did not read the high part
     int bin, zone;
     unsigned n, n_hi;
     float4 bb;
@@ -1293,209 +1351,143 @@ struct W64Shared {
 };
 
 
-// G = lanes per patch in the points phases (16: four patches at a time; 64: one at a time, for
-// big bins), PW = patches owned by the wave = lanes active in the solve phase.
-// Moments per patch in LDS: rows of 16 lanes only see patches below 2048 points, whose ten totals fit
-// int64; 64-lane rows leave sixteen values (second moments as 32-bit halves, Row<64>::reduce16_scatter).
-template <int G, int PW, bool WIDE>
-__global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_OCC : PWPP_W16_OCC)) void k_fit_w64(PwppBatch Bt, int b_lo, int b_hi) {
-    // ONE WAVE PER WORKGROUP: the waves never talk to each other, and a workgroup of four only starts when a CU has
-    // room for all four at once -- with waves of very different lifetimes the slots of the early finishers stood empty
-    // (27 % of the wave slots of k_fit_w64<64,2>, profiles/).
-    constexpr int MW = (G == 64 || WIDE) ? 16 : 10;  // (the wide grid: second moments beyond int64 -- sixteen values in 16-lane rows too)
-    typedef MomentsT<WIDE> Moments;
-    __shared__ W64Shared<PW, G == 64, MW> sh;
-    constexpr int R = 64 / G;      // patches per points-phase sub-batch
-    constexpr int NSB = PW / R;    // sub-batches
-    static_assert(PW % R == 0 && PW <= 64, "patches per wave");
-    const int f = blockIdx.x;  // frame = fast grid dimension, see fit_srows_body
-    const PwppDevParams &P = Bt.P;
-    const uint32_t *cs = Bt.cls_start + (size_t)f * PWPP_CLS_STRIDE;
-    const unsigned cbeg = cs[b_lo], cend = cs[b_hi];
-    const unsigned npatch = cend - cbeg;
-    const unsigned nwaves = (npatch + PW - 1u) / PW;
-    const unsigned w = blockIdx.y;
-    if (w >= nwaves) return;  // wave-uniform
-    const int ln = lane_id();
-    const int j = ln & (G - 1), row = ln / G;
-    const PwppFrameDesc fd = Bt.frames[f];
-    uint8_t *frame_member = Bt.member + fd.mbase;
-    const double sensor_height = fd.state_in >= 0 ? Bt.st_scalar[fd.state_in].sensor_height : P.sensor_height;
-    const double cutoff = P.margin * sensor_height;  // ref :90
-    const float zs = hi_split_z(P, sensor_height);
-    const double scale = (double)(1 << P.fxp_shift);
+// Phase profile (build with -DPWPP_PHASE_PROBE, option debug_flags = 4: tools/fit_phases.py): shader-clock cycles every wave spends in
+// each phase of its loop, added up over all waves in Bt.dbg[16 + 8 * (G == 64) + phase] -- 0 set-up, 1 lowest points, 2 publish,
+// 3 points phase, 4 solve (tiny fits included), 5 R-VPF strip, 6 state step; [32 + ...]: the waves counted.  PWPP_SUB: the parts of
+// the solve phase, in Bt.dbg[48 | 56 + part].
+#ifdef PWPP_PHASE_PROBE
+#define PWPP_PROBE_ADD(slot, since)                                                                                      \
+    do {                                                                                                                 \
+        const long long now_ = (long long)clock64();                                                                     \
+        if ((Bt.debug & 4) && lane_id() == 0) atomicAdd(&Bt.dbg[slot], (unsigned long long)(now_ - since));              \
+        since = now_;                                                                                                    \
+    } while (0)
+#define PWPP_PHASE(ph) PWPP_PROBE_ADD(16 + (G == 64 ? 8 : 0) + (ph), probe_t)
+#define PWPP_SUB_BEGIN() long long sub_t = (long long)clock64()
+#define PWPP_SUB(k) PWPP_PROBE_ADD((G == 64 ? 48 : 56) + (k), sub_t)
+#else
+#define PWPP_PHASE(ph) do { } while (0)
+#define PWPP_SUB_BEGIN() do { } while (0)
+#define PWPP_SUB(k) do { } while (0)
+#endif
 
-    // ---- owner lane: patch `ln` of this wave (lanes >= PW own nothing)
-    const unsigned slot = cbeg + w + (unsigned)ln * nwaves;
-    const bool alive = ln < PW && slot < cend;
-    const PatchCtx pc = patch_ctx(Bt, f, slot, alive);
-    constexpr bool OWN_LDS = G == 64;  // the owner state in LDS (W64Owner)
-    W64Owner own_regs;
-    const int oi = ln < PW ? ln : PW;
-#define O(fld) (*(OWN_LDS ? &sh.o[OWN_LDS ? oi : 0].fld : &own_regs.fld))
-    if (!OWN_LDS || ln <= PW) {
-        plane_clear(O(pl));
-        O(lpr) = 0.0;
-        O(z0) = 0.0f;
-        O(kind) = !alive ? ST_DONE : ((P.enable_RVPF != 0 && pc.zone == 0) ? ST_VPF : ST_SEED);
-        O(it) = 0;
-        O(lpr_valid) = 0;
-        O(z0_set) = 0;
-        O(fitted) = 0;      // a plane of this patch's own exists
-        O(hi_skipped) = 0;  // the last points phase of this patch did not read the high part
-        O(stash_valid) = 0;
-        O(bin) = pc.bin;
-        O(zone) = pc.zone;
-        O(n) = pc.n;
-        O(n_hi) = pc.n_hi;
-        O(bb) = Bt.bin_bbox[pc.bin];
-        O(cnt) = 0;
-    }
+struct W64Round {
+    bool dual_now;    // this round's pass also fills the stash
+    bool from_stash;  // no pass: totals come from the stash
+    int nact;         // patches in the coming points phase
+};
+
+// The shape of a k_fit_w64 instance and the phases of its loop.  Each phase takes the wave's LDS block `sh` and the state of
+// this lane's patch `o` (a W64Owner in LDS or in registers, the kernel decides); what else a phase hands to a later one is a
+// return value.  (The owner is a typed reference, not a macro: the listings of the 64-lane kernels show ds_* accesses for it
+// and no flat_* one.)
+template <int G, int PW, bool WIDE>
+struct W64 {
+    static constexpr int MW = (G == 64 || WIDE) ? 16 : 10;  // (the wide grid: second moments beyond int64 -- sixteen values in 16-lane rows too)
+    static constexpr int R = 64 / G;     // patches per points-phase sub-batch
+    static constexpr int NSB = PW / R;   // sub-batches
     // Dual seed pass (big bins, G == 64): the R-VPF round and the R-GPF seed stage of a zone-0 patch
     // select seeds from the same working set with the same lowest-point representative and two
     // thresholds (th_seeds_v / th_seeds, ref :480,:511).  The R-VPF pass therefore accumulates the
     // moments below the smaller threshold and those of the band up to the larger one; the sums are
     // exact integers, so one set is A and the other A + B.  If R-VPF removes nothing, the R-GPF seed
     // stage takes its totals from the stash instead of streaming the patch again.
-    constexpr bool DUAL = G == 64;
-    const bool v_is_hi = P.th_seeds_v >= P.th_seeds;
-    if (ln < PW) {
-        sh.p[ln].off_lo = pc.off_lo;
-        sh.p[ln].n_lo = pc.n_lo;
-        sh.p[ln].off_hi = pc.off_hi;
-        sh.p[ln].n_hi = pc.n_hi;
-        sh.p[ln].kind = ST_DONE;
-        sh.p[ln].flags = pc.zone == 0 ? 2 : 0;
-        sh.p[ln].bin = pc.bin;
-        sh.p[ln].ox = pc.ox;
-        sh.p[ln].oy = pc.oy;
-        sh.p[ln].z0 = 0.0f;
-    }
-    wave_lds_sync();
+    static constexpr bool DUAL = G == 64;
+    static constexpr bool OWN_LDS = G == 64;  // the owner state in LDS (W64Owner)
+    typedef MomentsT<WIDE> Moments;
+    typedef W64Shared<PW, DUAL, MW> Shared;
+    static_assert(PW % R == 0 && PW <= 64, "patches per wave");
 
-    // Phase profile (build with -DPWPP_PHASE_PROBE, option debug_flags = 4: tools/fit_phases.py): shader-clock cycles every wave spends in
-    // each phase of its loop, added up over all waves in Bt.dbg[16 + 8 * (G == 64) + phase] -- 0 set-up, 1 lowest points, 2 publish,
-    // 3 points phase, 4 solve (tiny fits included), 5 R-VPF strip, 6 state step; [32 + ...]: the waves counted.
-#ifdef PWPP_PHASE_PROBE
-    long long probe_t = (long long)clock64();
-#define PWPP_PHASE(ph)                                                                                                   \
-    do {                                                                                                                 \
-        const long long now_ = (long long)clock64();                                                                     \
-        if ((Bt.debug & 4) && ln == 0) atomicAdd(&Bt.dbg[16 + (G == 64 ? 8 : 0) + (ph)], (unsigned long long)(now_ - probe_t)); \
-        probe_t = now_;                                                                                                  \
-    } while (0)
-    if ((Bt.debug & 4) && ln == 0) atomicAdd(&Bt.dbg[32 + (G == 64 ? 8 : 0)], 1ull);
-    long long sub_t = 0;
-#define PWPP_SUB_BEGIN() do { sub_t = (long long)clock64(); } while (0)
-#define PWPP_SUB(k)                                                                                                       \
-    do {                                                                                                                 \
-        const long long now_ = (long long)clock64();                                                                     \
-        if ((Bt.debug & 4) && ln == 0) atomicAdd(&Bt.dbg[(G == 64 ? 48 : 56) + (k)], (unsigned long long)(now_ - sub_t)); \
-        sub_t = now_;                                                                                                    \
-    } while (0)
-#else
-#define PWPP_PHASE(ph) do { } while (0)
-#define PWPP_SUB_BEGIN() do { } while (0)
-#define PWPP_SUB(k) do { } while (0)
-#endif
-    PWPP_PHASE(0);
-    for (int guard = 0; guard < 4 * P.num_iter + 8; ++guard) {
-        if (!__any(O(kind) != ST_DONE)) break;
-
-        // ---- A. lowest-point representative (ref :84-103) for the patches whose working set is new: z only
-        const bool need_lpr = (O(kind) == ST_VPF || O(kind) == ST_SEED) && !O(lpr_valid);
+    // ---- A. lowest-point representative (ref :84-103) for the patches whose working set is new: z only
+    static __device__ __forceinline__ void lowest_points(const PwppBatch &Bt, const FrameCtx &fc, Shared &sh, W64Owner &o) {
+        const PwppDevParams &P = Bt.P;
+        const int ln = lane_id(), j = ln & (G - 1), row = ln / G;
+        const bool need_lpr = (o.kind == ST_VPF || o.kind == ST_SEED) && !o.lpr_valid;
         const unsigned long long lpr_mask = __ballot(need_lpr);
-        if (lpr_mask) {
-            // (16-lane rows: the z pass is the FIRST touch of a patch -- every sub-batch waited for its own HBM round trip, sixteen in
-            // a row.  The first chunk of the NEXT sub-batch that needs a pass is requested before this one's keys are ranked and
-            // sorted: eight registers, in a phase far from the kernel's register peak.  Round 6.)
-            constexpr bool kAhead = G == 16;
-            auto sb_needs = [&](int sb) { return sb < NSB && ((lpr_mask >> (R * sb)) & ((1ull << R) - 1ull)) != 0ull; };
-            auto request = [&](int sb, ChunkZ &cz) {
-                const int q = R * sb + row;
-                const bool need_row = (lpr_mask >> q) & 1ull;
-                const PatchRef qpts = patch_ref(Bt, fd, sh.p[q].off_lo, sh.p[q].n_lo, sh.p[q].off_hi, sh.p[q].n_hi);
-                PartSel sel;
-                sel.off = qpts.off_lo;
-                sel.n = need_row ? qpts.n_lo : 0u;
-                sel.c = 0u;
-                sel.moff = 0u;
-                load_chunk_z<G>(cz, qpts, sel);
-            };
-            ChunkZ ahead;
-            int sb = 0;
-            while (sb < NSB && !sb_needs(sb)) ++sb;
-            if (kAhead && sb < NSB) request(sb, ahead);
-            for (; sb < NSB;) {
-                int nxt = sb + 1;
-                while (nxt < NSB && !sb_needs(nxt)) ++nxt;
-                const ChunkZ cur = ahead;
-                if (kAhead && nxt < NSB) request(nxt, ahead);
-                const int q = R * sb + row;
-                const bool need_row = (lpr_mask >> q) & 1ull;
-                const bool use_cutoff = (sh.p[q].flags & 2) != 0;
-                const PatchRef qpts = patch_ref(Bt, fd, sh.p[q].off_lo, sh.p[q].n_lo, sh.p[q].off_hi, sh.p[q].n_hi);
-                const double l = srow_lpr<G>(qpts, need_row, use_cutoff, cutoff, P.num_lpr, (Bt.debug >> 14) & 3, kAhead ? &cur : nullptr);
-                if (need_row && j == 0) sh.p[q].u.lpr = l;
-                sb = nxt;
-            }
-            wave_lds_sync();
-            if (need_lpr) {
-                const double l = sh.p[ln].u.lpr;
-                O(lpr) = l;
-                O(lpr_valid) = 1;
-                if (!O(z0_set)) {  // the z origin of this patch's sums: its first lowest-point representative
-                    O(z0) = fxp_z_origin(l);
-                    O(z0_set) = 1;
-                }
+        if (!lpr_mask) return;
+        // (16-lane rows: the z pass is the FIRST touch of a patch -- every sub-batch waited for its own HBM round trip, sixteen in
+        // a row.  The first chunk of the NEXT sub-batch that needs a pass is requested before this one's keys are ranked and
+        // sorted: eight registers, in a phase far from the kernel's register peak.  Round 6.)
+        constexpr bool kAhead = G == 16;
+        auto sb_needs = [&](int sb) { return sb < NSB && ((lpr_mask >> (R * sb)) & ((1ull << R) - 1ull)) != 0ull; };
+        auto request = [&](int sb, ChunkZ &cz) {
+            const int q = R * sb + row;
+            const bool need_row = (lpr_mask >> q) & 1ull;
+            const PatchRef qpts = patch_ref(Bt, fc.fd, sh.p[q].off_lo, sh.p[q].n_lo, sh.p[q].off_hi, sh.p[q].n_hi);
+            const PartSel sel = {qpts.off_lo, need_row ? qpts.n_lo : 0u, 0u, 0u};
+            load_chunk_z<G>(cz, qpts, sel);
+        };
+        ChunkZ ahead;
+        int sb = 0;
+        while (sb < NSB && !sb_needs(sb)) ++sb;
+        if (kAhead && sb < NSB) request(sb, ahead);
+        for (; sb < NSB;) {
+            int nxt = sb + 1;
+            while (nxt < NSB && !sb_needs(nxt)) ++nxt;
+            const ChunkZ cur = ahead;
+            if (kAhead && nxt < NSB) request(nxt, ahead);
+            const int q = R * sb + row;
+            const bool need_row = (lpr_mask >> q) & 1ull;
+            const bool use_cutoff = (sh.p[q].flags & 2) != 0;
+            const PatchRef qpts = patch_ref(Bt, fc.fd, sh.p[q].off_lo, sh.p[q].n_lo, sh.p[q].off_hi, sh.p[q].n_hi);
+            const double l = srow_lpr<G>(qpts, need_row, use_cutoff, fc.cutoff, P.num_lpr, (Bt.debug >> 14) & 3, kAhead ? &cur : nullptr);
+            if (need_row && j == 0) sh.p[q].u.lpr = l;
+            sb = nxt;
+        }
+        wave_lds_sync();
+        if (need_lpr) {
+            const double l = sh.p[ln].u.lpr;
+            o.lpr = l;
+            o.lpr_valid = 1;
+            if (!o.z0_set) {  // the z origin of this patch's sums: its first lowest-point representative
+                o.z0 = fxp_z_origin(l);
+                o.z0_set = 1;
             }
         }
+    }
 
-        PWPP_PHASE(1);
-        // ---- B. publish the stage of every patch
-        const bool dual_now = DUAL && O(kind) == ST_VPF;                         // this round's pass also fills the stash
-        const bool from_stash = DUAL && O(kind) == ST_SEED && O(stash_valid) != 0;  // no pass: totals come from the stash
-        const int pub_kind = from_stash ? ST_DONE : O(kind);
+    // ---- B. publish the stage of every patch; returns how the owner's patch takes part in this round
+    static __device__ __forceinline__ W64Round publish(const PwppBatch &Bt, const FrameCtx &fc, Shared &sh, W64Owner &o) {
+        const PwppDevParams &P = Bt.P;
+        const int ln = lane_id();
+        W64Round r;
+        r.dual_now = DUAL && o.kind == ST_VPF;
+        r.from_stash = DUAL && o.kind == ST_SEED && o.stash_valid != 0;
+        const int pub_kind = r.from_stash ? ST_DONE : o.kind;
         if (ln < PW) {
-            const int kind = O(kind);
-            const PlaneFit pl = O(pl);
-            const double lpr = O(lpr);
-            const bool last = kind == ST_ITER && O(it) == P.num_iter - 1;
-            // EARLY TERMINATION (exact): the plane is a function of the ten integer totals.  If an R-GPF round's totals equal
-            // those of the round before -- which gave the plane this round tested with -- the next plane is this plane bit for
-            // bit, hence every later round selects this round's set again and the final plane (ref :537-542) is the one in
-            // force: the patch is finished, its split is what this round left in the membership plane.  Every round that can
-            // be the last one that way (from the second on) writes its bits; the totals of 1-3 points are not compared (the
-            // tiny-fit path replaces them in LDS).
-            const bool wbits = kind == ST_ITER && (last || O(it) >= 1);
-            const bool cmp = kind == ST_ITER && !last && O(it) >= 1 && O(cnt) > 3;
-            const double th = (kind == ST_VPF || kind == ST_LAZY) ? P.th_seeds_v : P.th_seeds;
-            const double thr_seed = lpr + (dual_now ? (v_is_hi ? P.th_seeds : P.th_seeds_v) : th);
-            const double thr_band = lpr + (v_is_hi ? P.th_seeds_v : P.th_seeds);
-            const unsigned n_hi = O(n_hi);
-            const bool use_hi = pub_kind != ST_DONE &&
-                                stage_needs_hi(kind, n_hi, dual_now && thr_band > thr_seed ? thr_band : thr_seed, P.th_dist, pl, O(bb), zs);
-            if (pub_kind != ST_DONE) O(hi_skipped) = !use_hi && n_hi > 0u;
+            const int kind = o.kind;
+            const PlaneFit pl = o.pl;
+            const PassTests t = pass_tests(P, kind, o.it, o.lpr, pl.d, r.dual_now);
+            // (the totals of a round of 1-3 points are not in LDS any more -- the tiny-fit path replaced them: never comparable)
+            const bool cmp = t.comparable && o.cnt > 3;
+            const unsigned n_hi = o.n_hi;
+            const bool use_hi = pub_kind != ST_DONE && stage_needs_hi(kind, n_hi, t.thr_max, P.th_dist, pl, o.bb, fc.zs);
+            if (pub_kind != ST_DONE) o.hi_skipped = !use_hi && n_hi > 0u;
             sh.p[ln].kind = pub_kind;
-            sh.p[ln].flags = (O(zone) == 0 ? 2 : 0) | (last ? 1 : 0) | (dual_now ? 4 : 0) | (use_hi ? 8 : 0) | (wbits ? 32 : 0) | (cmp ? 64 : 0);
+            sh.p[ln].flags = (o.zone == 0 ? 2 : 0) | (t.last ? 1 : 0) | (r.dual_now ? 4 : 0) | (use_hi ? 8 : 0) | (t.wbits ? 32 : 0) | (cmp ? 64 : 0);
             sh.p[ln].nx = pl.nx;
             sh.p[ln].ny = pl.ny;
             sh.p[ln].nz = pl.nz;
-            sh.p[ln].z0 = O(z0);
+            sh.p[ln].z0 = o.z0;
             if (pub_kind != ST_DONE) {  // the pass's tests as float thresholds (lane_stage_accum)
-                sh.p[ln].u.thr.t = stage_threshold(kind, pl.d, P.th_dist, thr_seed);
-                sh.p[ln].u.thr.t2 = dual_now ? plane_test_threshold(0.0, thr_band) : 0.0f;
+                sh.p[ln].u.thr.t = t.T;
+                sh.p[ln].u.thr.t2 = t.T_band;
             }
         }
         // the patches of the coming points phase, packed: patches that are finished (early termination), that take their
         // totals from the stash or that are at another point of their chain leave no idle rows in the sub-batches
         const unsigned long long act_mask = __ballot(pub_kind != ST_DONE);
         if (pub_kind != ST_DONE) sh.order[__popcll(act_mask & ((1ull << ln) - 1ull))] = (unsigned char)ln;
-        const int nact = __popcll(act_mask);
+        r.nact = __popcll(act_mask);
         wave_lds_sync();
+        return r;
+    }
 
-        PWPP_PHASE(2);
-        // ---- C. points phase: R patches at a time, G lanes each
+    // ---- C. points phase: R patches at a time, G lanes each; leaves every patch's totals in sh.mom (sh.mom2: the band of a dual pass)
+    static __device__ __forceinline__ void points(const PwppBatch &Bt, const FrameCtx &fc, int f, Shared &sh, int nact) {
+        const PwppDevParams &P = Bt.P;
+        const int ln = lane_id(), j = ln & (G - 1), row = ln / G;
+        const double scale = fc.scale;
         for (int sb = 0; R * sb < nact; ++sb) {
             const bool row_on = R * sb + row < nact;
             const int q = row_on ? (int)sh.order[R * sb + row] : (int)sh.order[0];
@@ -1505,24 +1497,19 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
             const bool wbits = on && (pp.flags & 32);
             const bool use_hi = (pp.flags & 8) != 0;
             const FxpOrg org = fxp_org(pp.ox, pp.oy, pp.z0, scale, P.fxp_zr);
-            const PatchRef pts = patch_ref(Bt, fd, pp.off_lo, pp.n_lo, pp.off_hi, pp.n_hi, pp.bin);
+            const PatchRef pts = patch_ref(Bt, fc.fd, pp.off_lo, pp.n_lo, pp.off_hi, pp.n_hi, pp.bin);
             const unsigned nchunk_max = wave_max_u32(on ? patch_chunks<G>(pts, use_hi) : 0u);
             const bool dual = DUAL && on && (pp.flags & 4);
             Moments m, m2;
             m.clear();
             m2.clear();
             bool clamped = false;  // a height of the round's set lay outside z0 +- ZR (matters if this set is the final one)
-            // The loads of chunk c + 1 are issued before chunk c is consumed: a wave is a chain load -> wait -> ~250
-            // instructions, and with 3-4 waves per SIMD the waits were not covered (k_fit_w64<64,2> moved its bytes at
-            // 4.8 TB/s where a plain read stream reaches 6.3, tools/ubench/read_bw.hip).  The solve phase sets the
-            // register allocation of these kernels, so the second chunk in flight costs the points phase nothing.
-            constexpr bool kPrefetch = PWPP_FIT_PREFETCH != 0 && G == 64;  // (the 16-lane kernels have no registers to spare: 76 spilled without it)
+            // One chunk in flight: chunk c + 1 is requested when chunk c has been consumed.  (A second chunk in flight behind the
+            // arithmetic was measured and dropped: it cost the 64-lane kernels 182 spilled registers, W64Owner above.)
             const bool any_wbits = __any(wbits);
             ChunkPts cp;
             if (nchunk_max > 0u) load_chunk<G>(cp, pts, chunk_sel<G>(pts, 0u, use_hi, on));
             for (unsigned c = 0; c < nchunk_max; ++c) {
-                ChunkPts nx;
-                if (kPrefetch && c + 1u < nchunk_max) load_chunk<G>(nx, pts, chunk_sel<G>(pts, c + 1u, use_hi, on));  // (wave-uniform)
                 bool hit = false;
                 const unsigned gmask = lane_stage_accum<G>(cp, pp.kind, pp.u.thr.t, pp.nx, pp.ny, pp.nz, scale, org, m, hit);
                 clamped = clamped || (wbits && hit);
@@ -1535,14 +1522,9 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
                     }
                 }
                 if (any_wbits) {  // the round's set -> membership plane: the split of the patch if this round turns out to be its last
-                    store_member<G>(frame_member, chunk_sel<G>(pts, c, use_hi, on), gmask, wbits);
+                    store_member<G>(fc.member, chunk_sel<G>(pts, c, use_hi, on), gmask, wbits);
                 }
-                if (c + 1u < nchunk_max) {
-                    if (kPrefetch)
-                        cp = nx;
-                    else
-                        load_chunk<G>(cp, pts, chunk_sel<G>(pts, c + 1u, use_hi, on));
-                }
+                if (c + 1u < nchunk_max) load_chunk<G>(cp, pts, chunk_sel<G>(pts, c + 1u, use_hi, on));
             }
             // the row's totals -> LDS.  64-lane rows: reduce-scatter of sixteen values, each stored by the lane it
             // ends up with; 16-lane rows: ten butterflies (four steps each; the selects of a scatter cost what its
@@ -1584,21 +1566,27 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
             if (__any(clamped && (last || conv)) && ln == 0) flag_clamped(Bt, f);  // (only a FINAL ground set counts, pwpp_get_clamped_frames)
         }
         wave_lds_sync();
-        PWPP_PHASE(3);
+    }
 
-        // ---- D. solve phase: lane p fits patch p (ref :47-75)
+    // ---- D. solve phase: lane p fits patch p (ref :47-75); the rows first gather the points of the sets of 1-3 (contract v3).
+    // Returns whether the owner's patch has converged (early termination).
+    static __device__ __forceinline__ bool solve(const PwppBatch &Bt, const FrameCtx &fc, int f, Shared &sh, W64Owner &o, const W64Round &rd) {
+        const PwppDevParams &P = Bt.P;
+        const int ln = lane_id(), j = ln & (G - 1), row = ln / G;
+        const bool dual_now = rd.dual_now, from_stash = rd.from_stash, v_is_hi = seeds_v_is_hi(P);
         PWPP_SUB_BEGIN();
         long long cnt = 0;
         bool tiny = false;  // contract v3: a fit set of 1-3 points follows the reference's float arithmetic (tiny_fit_row)
         bool conv = false;  // early termination: this round's totals repeat the last round's, the plane in force is the final one
-        if (O(kind) != ST_DONE) {
+        if (o.kind != ST_DONE) {
             const long long a0 = sh.mom[ln][0], b0 = DUAL ? sh.mom2[DUAL ? ln : 0][0] : 0;
             cnt = from_stash ? b0 : (dual_now ? (v_is_hi ? a0 + b0 : a0) : a0);
             tiny = cnt >= 1 && cnt <= 3;
-            conv = ln < PW && (sh.p[ln < PW ? ln : 0].flags & 128) != 0 && cnt > 3;
+            // (flags bit 7 is only ever set in a comparable round, bit 6)
+            conv = ln < PW && round_converged(true, cnt, (sh.p[ln < PW ? ln : 0].flags & 128) != 0);
         }
         const unsigned long long t_mask = __ballot(tiny);
-        if (t_mask) {  // the rows gather the points of those patches again (the stage of phase B is still published)
+        if (t_mask) {  // the rows gather the points of those patches again (the stage publish() left is still published)
             for (int sb = 0; sb < NSB; ++sb) {
                 if (((t_mask >> (R * sb)) & ((1ull << R) - 1ull)) == 0ull) continue;
                 const int q = R * sb + row;
@@ -1608,7 +1596,7 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
                 if constexpr (DUAL) {
                     if ((pp.flags & 4) && v_is_hi) thr = pp.u.thr.t2;  // dual pass: this round's set is the R-VPF one
                 }
-                const PatchRef pts = patch_ref(Bt, fd, pp.off_lo, pp.n_lo, pp.off_hi, pp.n_hi);
+                const PatchRef pts = patch_ref(Bt, fc.fd, pp.off_lo, pp.n_lo, pp.off_hi, pp.n_hi);
                 float mt[3], ct[6];
                 tiny_fit_row<G>(pts, trow, pp.kind, thr, pp.nx, pp.ny, pp.nz, mt, ct);
                 if (trow && j == 0) {  // mean and covariance take the place of the patch's moments 1..5 (the count stays)
@@ -1626,7 +1614,7 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
         // the phase is a chain of dependent 64-bit operations whose LENGTH is the same for one output as for nine interleaved ones, plus
         // two hand-overs through LDS.  tools/fit_phases.py, profiles/r06_fit_phases.txt.)
         PWPP_SUB(1);
-        if (O(kind) != ST_DONE) {
+        if (o.kind != ST_DONE) {
             float mean[3], c6[6];
             if (tiny) {
                 const float *src = reinterpret_cast<const float *>(&sh.mom[ln][1]);
@@ -1634,7 +1622,7 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
                 for (int k = 0; k < 3; ++k) mean[k] = src[k];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) c6[k] = src[3 + k];
-                if (dual_now) O(stash_valid) = 0;  // (its moments are gone: the R-GPF seed stage streams the patch itself)
+                if (dual_now) o.stash_valid = 0;  // (its moments are gone: the R-GPF seed stage streams the patch itself)
             } else {
                 long long tot[MW];
 #pragma unroll
@@ -1648,9 +1636,9 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
                         sh.mom2[DUAL ? ln : 0][k] = v_is_hi ? a : ab;    // stash: the R-GPF seeds (th_seeds)
                         if (k == 0) stash_cnt = v_is_hi ? a : ab;
                     }
-                    O(stash_valid) = !(stash_cnt >= 1 && stash_cnt <= 3);  // (1-3 seeds: that stage gathers the points, it needs its own pass)
+                    o.stash_valid = !(stash_cnt >= 1 && stash_cnt <= 3);  // (1-3 seeds: that stage gathers the points, it needs its own pass)
                 }
-                if (cnt > 0 && !conv) {
+                if (stage_solves(cnt, conv)) {
                     constexpr bool kRaw = MW == 16 && G == 16;  // (to_row16's values)
                     const long long s1[3] = {kRaw ? wide_first(tot[1], cnt) : tot[1], kRaw ? wide_first(tot[2], cnt) : tot[2], kRaw ? wide_first(tot[3], cnt) : tot[3]};
                     __int128 s2[6];
@@ -1658,107 +1646,164 @@ __global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_
                     for (int k = 0; k < 6; ++k)
                         s2[k] = kRaw ? wide_second(tot[4 + k], tot[MW == 16 ? 10 + k : 4 + k])
                                      : (MW == 16 ? join_halves(tot[4 + k], tot[MW == 16 ? 10 + k : 4 + k]) : (__int128)tot[4 + k]);
-                    mean_cov_from_totals(cnt, s1, s2, P.fxp_shift, sh.p[ln].ox, sh.p[ln].oy, O(z0), mean, c6);
+                    mean_cov_from_totals(cnt, s1, s2, P.fxp_shift, sh.p[ln].ox, sh.p[ln].oy, o.z0, mean, c6);
                 }
             }
             PWPP_SUB(2);
-            if (cnt > 0 && !conv) {  // empty set: the previous plane stays (ref :49); converged: the solve would return the plane in force
+            if (stage_solves(cnt, conv)) {
                 PlaneFit npl;
                 plane_from_mean_c6(mean, c6, Bt.debug, npl);
                 PWPP_SUB(3);
-                O(pl) = npl;
-                O(fitted) = 1;
+                o.pl = npl;
+                o.fitted = 1;  // a plane of this patch's own exists
             }
-            if (needs_previous_plane(P, O(kind), O(zone), O(fitted) != 0)) {
-                mark_needs_previous_plane(Bt, f, Bt.recs + (size_t)f * P.num_bins + O(bin), O(n));
-                O(kind) = ST_DONE;
+            if (needs_previous_plane(P, o.kind, o.zone, o.fitted != 0)) {
+                mark_needs_previous_plane(Bt, f, Bt.recs + (size_t)f * P.num_bins + o.bin, o.n);
+                o.kind = ST_DONE;
             }
-            O(cnt) = cnt;
+            o.cnt = cnt;
         }
         PWPP_SUB(4);
+        return conv;
+    }
 
-        PWPP_PHASE(4);
-        // ---- E. R-VPF strip (ref :489-505) for the zone-0 patches whose plane came out vertical
-        const bool vertical = O(kind) == ST_VPF && (double)O(pl).nz < P.uprightness_thr;
+    // ---- E. R-VPF strip (ref :489-505) for the zone-0 patches whose plane came out vertical; returns whether the owner's is one
+    static __device__ __forceinline__ bool strip(const PwppBatch &Bt, const FrameCtx &fc, Shared &sh, W64Owner &o) {
+        const PwppDevParams &P = Bt.P;
+        const int ln = lane_id(), j = ln & (G - 1), row = ln / G;
+        const bool vertical = plane_is_vertical(P, o.kind, o.pl.nz);
         const unsigned long long v_mask = __ballot(vertical);
-        if (v_mask) {
-            if (ln < PW) {
-                const PlaneFit pl = O(pl);
-                sh.p[ln].nx = pl.nx;
-                sh.p[ln].ny = pl.ny;
-                sh.p[ln].nz = pl.nz;
-                if (vertical) {
-                    const StripBand band = strip_band(pl.d, P.th_dist_v);
-                    sh.p[ln].u.thr.t = band.lo;
-                    sh.p[ln].u.thr.t2 = band.hi;
-                }
-                sh.p[ln].flags = (sh.p[ln].flags & 0xef) | (O(it) << 8);  // nothing removed yet; the round
+        if (!v_mask) return vertical;
+        if (ln < PW) {
+            const PlaneFit pl = o.pl;
+            sh.p[ln].nx = pl.nx;
+            sh.p[ln].ny = pl.ny;
+            sh.p[ln].nz = pl.nz;
+            if (vertical) {
+                const StripBand band = strip_band(pl.d, P.th_dist_v);
+                sh.p[ln].u.thr.t = band.lo;
+                sh.p[ln].u.thr.t2 = band.hi;
             }
-            wave_lds_sync();
-            for (int sb = 0; sb < NSB; ++sb) {
-                if (((v_mask >> (R * sb)) & ((1ull << R) - 1ull)) == 0ull) continue;
-                const int q = R * sb + row;
-                const bool vrow = (v_mask >> q) & 1ull;
-                const W64Patch pp = sh.p[q];
-                StripBand band;
-                band.lo = pp.u.thr.t;
-                band.hi = pp.u.thr.t2;
-                const PatchRef pts = patch_ref(Bt, fd, pp.off_lo, pp.n_lo, pp.off_hi, pp.n_hi);
-                const int vpf_round = (pp.flags >> 8) & 0xff;
-                const unsigned nchunk_max = wave_max_u32(vrow ? patch_chunks<G>(pts, true) : 0u);
-                bool any = false;
-                for (unsigned c = 0; c < nchunk_max; ++c) {
-                    ChunkPts cp;
-                    const PartSel sel = chunk_sel<G>(pts, c, true, vrow);
-                    load_chunk<G>(cp, pts, sel);
-                    const unsigned hit = lane_strip<G>(cp, vrow, pp.nx, pp.ny, pp.nz, band);
-#pragma unroll
-                    for (int k = 0; k < kPPT; ++k) {
-                        if (hit >> k & 1u) {
-                            strip_point(pts, chunk_slot<G>(sel, k, (unsigned)j), vpf_round);
-                        }
-                    }
-                    any = any || hit != 0;
-                }
-                if (Row<G>::ballot(any) != 0ull && j == 0) sh.p[q].flags = pp.flags | 16;
-            }
-            wave_lds_sync();
-            if (vertical && (sh.p[ln].flags & 16)) {  // the working set changed
-                O(lpr_valid) = 0;
-                O(stash_valid) = 0;
-            }
+            sh.p[ln].flags = (sh.p[ln].flags & 0xef) | (o.it << 8);  // nothing removed yet; the round
         }
+        wave_lds_sync();
+        for (int sb = 0; sb < NSB; ++sb) {
+            if (((v_mask >> (R * sb)) & ((1ull << R) - 1ull)) == 0ull) continue;
+            const int q = R * sb + row;
+            const bool vrow = (v_mask >> q) & 1ull;
+            const W64Patch pp = sh.p[q];
+            const StripBand band = {pp.u.thr.t, pp.u.thr.t2};
+            const PatchRef pts = patch_ref(Bt, fc.fd, pp.off_lo, pp.n_lo, pp.off_hi, pp.n_hi);
+            const int vpf_round = (pp.flags >> 8) & 0xff;
+            const unsigned nchunk_max = wave_max_u32(vrow ? patch_chunks<G>(pts, true) : 0u);
+            bool any = false;
+            for (unsigned c = 0; c < nchunk_max; ++c) {
+                ChunkPts cp;
+                const PartSel sel = chunk_sel<G>(pts, c, true, vrow);
+                load_chunk<G>(cp, pts, sel);
+                const unsigned hit = lane_strip<G>(cp, vrow, pp.nx, pp.ny, pp.nz, band);
+#pragma unroll
+                for (int k = 0; k < kPPT; ++k) {
+                    if (hit >> k & 1u) {
+                        strip_point(pts, chunk_slot<G>(sel, k, (unsigned)j), vpf_round);
+                    }
+                }
+                any = any || hit != 0;
+            }
+            if (Row<G>::ballot(any) != 0ull && j == 0) sh.p[q].flags = pp.flags | 16;
+        }
+        wave_lds_sync();
+        if (vertical && (sh.p[ln].flags & 16)) {  // the working set changed
+            o.lpr_valid = 0;
+            o.stash_valid = 0;
+        }
+        return vertical;
+    }
+};
 
+// G = lanes per patch in the points phases (16: four patches at a time; 64: one at a time, for
+// big bins), PW = patches owned by the wave = lanes active in the solve phase.
+// Moments per patch in LDS: rows of 16 lanes only see patches below 2048 points, whose ten totals fit
+// int64; 64-lane rows leave sixteen values (second moments as 32-bit halves, Row<64>::reduce16_scatter).
+template <int G, int PW, bool WIDE>
+__global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_OCC : PWPP_W16_OCC)) void k_fit_w64(PwppBatch Bt, int b_lo, int b_hi) {
+    // ONE WAVE PER WORKGROUP: the waves never talk to each other, and a workgroup of four only starts when a CU has
+    // room for all four at once -- with waves of very different lifetimes the slots of the early finishers stood empty
+    // (27 % of the wave slots of k_fit_w64<64,2>, profiles/).
+    typedef W64<G, PW, WIDE> K;
+    __shared__ typename K::Shared sh;
+    const int f = blockIdx.x;  // frame = fast grid dimension, see fit_srows_body
+    const PwppDevParams &P = Bt.P;
+    const uint32_t *cs = Bt.cls_start + (size_t)f * PWPP_CLS_STRIDE;
+    const unsigned cbeg = cs[b_lo], cend = cs[b_hi];
+    const unsigned npatch = cend - cbeg;
+    const unsigned nwaves = (npatch + PW - 1u) / PW;
+    const unsigned w = blockIdx.y;
+    if (w >= nwaves) return;  // wave-uniform
+    const int ln = lane_id();
+    const FrameCtx fc = frame_ctx(Bt, f);
+
+    // ---- owner lane: patch `ln` of this wave (lanes >= PW own nothing)
+    const unsigned slot = cbeg + w + (unsigned)ln * nwaves;
+    const bool alive = ln < PW && slot < cend;
+    const PatchCtx pc = patch_ctx(Bt, f, slot, alive);
+    W64Owner own_regs;
+    const int oi = ln < PW ? ln : PW;
+    W64Owner &o = K::OWN_LDS ? sh.o[K::OWN_LDS ? oi : 0] : own_regs;
+    if (!K::OWN_LDS || ln <= PW) {
+        o = W64Owner();  // (no plane, no lowest points, nothing stashed, round 0)
+        o.kind = first_stage(P, pc.zone, alive);
+        o.bin = pc.bin;
+        o.zone = pc.zone;
+        o.n = pc.n;
+        o.n_hi = pc.n_hi;
+        o.bb = Bt.bin_bbox[pc.bin];
+    }
+    if (ln < PW) {
+        sh.p[ln].off_lo = pc.off_lo;
+        sh.p[ln].n_lo = pc.n_lo;
+        sh.p[ln].off_hi = pc.off_hi;
+        sh.p[ln].n_hi = pc.n_hi;
+        sh.p[ln].kind = ST_DONE;
+        sh.p[ln].flags = pc.zone == 0 ? 2 : 0;
+        sh.p[ln].bin = pc.bin;
+        sh.p[ln].ox = pc.ox;
+        sh.p[ln].oy = pc.oy;
+        sh.p[ln].z0 = 0.0f;
+    }
+    wave_lds_sync();
+
+#ifdef PWPP_PHASE_PROBE
+    long long probe_t = (long long)clock64();
+    if ((Bt.debug & 4) && ln == 0) atomicAdd(&Bt.dbg[32 + (G == 64 ? 8 : 0)], 1ull);
+#endif
+    PWPP_PHASE(0);
+    for (int guard = 0; guard < 4 * P.num_iter + 8; ++guard) {
+        if (!__any(o.kind != ST_DONE)) break;
+        K::lowest_points(Bt, fc, sh, o);
+        PWPP_PHASE(1);
+        const W64Round rd = K::publish(Bt, fc, sh, o);
+        PWPP_PHASE(2);
+        K::points(Bt, fc, f, sh, rd.nact);
+        PWPP_PHASE(3);
+        const bool conv = K::solve(Bt, fc, f, sh, o, rd);
+        PWPP_PHASE(4);
+        const bool vertical = K::strip(Bt, fc, sh, o);
         PWPP_PHASE(5);
         // ---- what comes next for the patch of this lane
-        const int kind = O(kind);
-        if (kind == ST_VPF) {
-            const int it = O(it) + 1;
-            O(it) = it;
-            if (!vertical || it >= P.num_iter) {  // ref :506 / loop end
-                O(kind) = ST_SEED;
-                O(it) = 0;
-            }
-        } else if (kind == ST_SEED) {
-            O(kind) = (O(cnt) == 0 && P.enable_RVPF != 0 && O(zone) != 0) ? ST_LAZY : ST_ITER;
-        } else if (kind == ST_LAZY) {
-            O(kind) = ST_ITER;
-        } else if (kind == ST_ITER) {
-            const int it = O(it);
-            if (it == P.num_iter - 1 || conv) {
-                write_record(Bt.recs + (size_t)f * P.num_bins + O(bin), O(pl), O(n), (unsigned)O(cnt), O(hi_skipped) != 0, G == 64 ? 6 : (G == 32 ? 5 : (G == 16 ? 4 : 3)), it + 1);
-                O(kind) = ST_DONE;
-            }
-            O(it) = it + 1;
-        }
-        if (OWN_LDS) wave_lds_sync();  // (the owner state is LDS: ordered like every other hand-over between the phases)
+        const bool last = o.kind == ST_ITER && o.it == P.num_iter - 1;
+        if (next_stage(P, o.zone, o.kind, o.it, vertical, o.cnt, last, conv))
+            write_record(Bt.recs + (size_t)f * P.num_bins + o.bin, o.pl, o.n, (unsigned)o.cnt, o.hi_skipped != 0, member_lg<G>(), o.it);
+        if (K::OWN_LDS) wave_lds_sync();  // (the owner state is LDS: ordered like every other hand-over between the phases)
         PWPP_PHASE(6);
     }
+}
 #undef PWPP_PHASE
 #undef PWPP_SUB
 #undef PWPP_SUB_BEGIN
-#undef O
-}
+#ifdef PWPP_PHASE_PROBE
+#undef PWPP_PROBE_ADD
+#endif
 
 struct FitShared {
     long long part[kWaves][22];
@@ -2094,17 +2139,8 @@ __device__ double brow_lpr(BRowShared &sh, const PatchRef &pts, bool use_hi, boo
     if (kx > 0 && kx <= 32) {
         unsigned s0 = k0, s1 = k1, s2 = k2, s3 = k3;
         row64_lowest32(s0, s1, s2, s3);
-        const unsigned kk[4] = {s0, s1, s2, s3};
-        double part = 0.0;
-        bool ok = true;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const bool sel = ln < 8 && 4 * ln + r < kx;
-            const float zv = key_z(kk[r]);
-            const unsigned e = (__float_as_uint(zv) >> 23) & 0xffu;
-            ok = ok && (!sel || zv == 0.0f || (e >= 115u && e < 135u));
-            part += sel ? (double)zv : 0.0;
-        }
+        double part;
+        const bool ok = lowest_keys_sum_exact(s0, s1, s2, s3, ln < 8, ln, kx, part);
         quick = __ballot(!ok) == 0ull;
         if (quick) {
             const double s = row16_sum_f64(part);
@@ -2156,15 +2192,11 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
     const PatchCtx pc = patch_ctx(Bt, f, slot, true);
     const int bin = pc.bin, zone = pc.zone;
     const unsigned n = pc.n;  // (at most 2047 points per lane, see Moments; pwpp_launch_fit sends larger patches to k_fit_stream)
-    const PwppFrameDesc fd = Bt.frames[f];
-    const PatchRef pts = patch_ref(Bt, fd, pc);
-    uint8_t *frame_member = Bt.member + fd.mbase;
-    const double sensor_height = fd.state_in >= 0 ? Bt.st_scalar[fd.state_in].sensor_height : P.sensor_height;
-    const double cutoff = P.margin * sensor_height;
-    const float zs = hi_split_z(P, sensor_height);
+    const FrameCtx fc = frame_ctx(Bt, f);
+    const PatchRef pts = patch_ref(Bt, fc.fd, pc);
     const float4 bb = Bt.bin_bbox[bin];
     const bool use_cutoff = zone == 0;
-    const double scale = (double)(1 << P.fxp_shift);
+    const double scale = fc.scale;
 
     PlaneFit pl;
     plane_clear(pl);
@@ -2172,14 +2204,14 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
     bool lpr_valid = false, z0_set = false;
     float z0 = 0.0f;
     FxpOrg org = fxp_org(pc.ox, pc.oy, 0.0f, scale, P.fxp_zr);
-    int kind = (P.enable_RVPF != 0 && zone == 0) ? ST_VPF : ST_SEED;  // everything below is workgroup-uniform
+    int kind = first_stage(P, zone);  // everything below is workgroup-uniform
     int it = 0;
     // Dual seed pass as in k_fit_w64 (an R-VPF round and the R-GPF seed stage pick their seeds from the
     // same working set with two thresholds: the pass sums the points below the smaller one and the band
     // up to the larger one), and because this kernel is a latency chain with four SIMDs to itself, the two
     // planes are also SOLVED side by side: waves 0-1 fit the R-VPF seeds, waves 2-3 the R-GPF seeds.  If
     // the R-VPF round removes nothing, the R-GPF seed stage is already done: no pass, no solve.
-    const bool v_is_hi = P.th_seeds_v >= P.th_seeds;
+    const bool v_is_hi = seeds_v_is_hi(P);
     bool stash_valid = false;
     long long stash_cnt = 0;
     bool fitted = false;  // a plane of this patch's own exists
@@ -2205,7 +2237,7 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
         if ((kind == ST_VPF || kind == ST_SEED) && !lpr_valid) {
             int eligible = 0;
             for (int both = 0; both < 2; ++both) {  // the low part alone, unless it holds fewer than num_lpr eligible points (srow_lpr)
-                lpr = brow_lpr(sh, pts, both != 0, use_cutoff, cutoff, P.num_lpr, eligible, (Bt.debug >> 14) & 3);
+                lpr = brow_lpr(sh, pts, both != 0, use_cutoff, fc.cutoff, P.num_lpr, eligible, (Bt.debug >> 14) & 3);
                 if (eligible >= P.num_lpr || pc.n_hi == 0u) break;
             }
             lpr_valid = true;
@@ -2217,18 +2249,14 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
             probe(2);
         }
         const bool dual_now = kind == ST_VPF;
-        const double thr_seed = lpr + (dual_now ? (v_is_hi ? P.th_seeds : P.th_seeds_v) : (kind == ST_LAZY ? P.th_seeds_v : P.th_seeds));
-        const double thr_band = lpr + (v_is_hi ? P.th_seeds_v : P.th_seeds);
-        const bool last = kind == ST_ITER && it == P.num_iter - 1;
-        const bool use_hi = stage_needs_hi(kind, pc.n_hi, dual_now && thr_band > thr_seed ? thr_band : thr_seed, P.th_dist, pl, bb, zs);
+        const PassTests t = pass_tests(P, kind, it, lpr, pl.d, dual_now);
+        const bool last = t.last, wbits = t.wbits;
+        const float T = t.T, T_band = t.T_band;
+        const bool use_hi = stage_needs_hi(kind, pc.n_hi, t.thr_max, P.th_dist, pl, bb, fc.zs);
         const unsigned nchunk = patch_chunks<64>(pts, use_hi);
-        const float T = stage_threshold(kind, pl.d, P.th_dist, thr_seed);  // the pass's tests in float (lane_stage_accum)
-        const float T_band = dual_now ? plane_test_threshold(0.0, thr_band) : 0.0f;
         Moments m, m2;
         m.clear();
         m2.clear();
-        // (early termination and the membership plane: see k_fit_w64)
-        const bool wbits = kind == ST_ITER && (last || it >= 1);
         bool clamped = false;
         ChunkPts cp;
         load_chunk<64>(cp, pts, chunk_sel<64>(pts, (unsigned)wv, use_hi));
@@ -2245,7 +2273,7 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
                     if ((rest >> k & 1u) & (cp.z[k] < T_band) & (k_off<64>(k) < cp.rem)) m2.add(cp.x[k], cp.y[k], cp.z[k], scale, org);
             }
             if (wbits) {  // the round's set -> membership plane (every wave its own chunks)
-                store_member<64>(frame_member, chunk_sel<64>(pts, c, use_hi), gmask, true);
+                store_member<64>(fc.member, chunk_sel<64>(pts, c, use_hi), gmask, true);
             }
             cp = nx;
         }
@@ -2290,7 +2318,7 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
             for (int k = 0; k < 6; ++k) s2[k] = join_halves(t16[4 + k], t16[10 + k]);
             if (kind == ST_ITER) {  // (prev_tot is double-buffered by round: no barrier between its read and its write)
                 const bool differs = sh.prev_tot[(it & 1) ^ 1][k16] != mine;
-                conv = !last && it >= 1 && cnt > 3 && __ballot(differs) == 0ull;
+                conv = round_converged(t.comparable, cnt, __ballot(differs) == 0ull);
                 if (wv == 0 && ln < 16) sh.prev_tot[it & 1][ln] = mine;
             }
         }
@@ -2298,7 +2326,7 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
         __syncthreads();
         probe(4);
         PlaneFit fitted_pl = pl;
-        if (tot[0] > 0 && !conv) {  // empty: ref :49; converged: the solve would return the plane in force
+        if (stage_solves(tot[0], conv)) {
             float mean[3], c6[6];
             if (tot[0] <= 3) {  // contract v3 (wave-uniform): this wave gathers the 1-3 points of its set itself
                 const float thr_t = dual_now ? ((spec == v_is_hi) ? T : T_band) : T;
@@ -2325,43 +2353,28 @@ __device__ __forceinline__ void fit_brows_body(BRowShared &sh, const PwppBatch &
             continue;
         }
         probe(5);
-        if (kind == ST_VPF) {
-            const bool vertical = (double)pl.nz < P.uprightness_thr;  // ref :489
-            if (vertical) {
-                int any = 0;
-                const unsigned nstrip = patch_chunks<64>(pts, true);
-                const StripBand band = strip_band(pl.d, P.th_dist_v);
-                for (unsigned c = (unsigned)wv; c < nstrip; c += kWaves) {
-                    ChunkPts cs2;
-                    const PartSel sel = chunk_sel<64>(pts, c, true);
-                    load_chunk<64>(cs2, pts, sel);
-                    const unsigned hit = lane_strip<64>(cs2, true, pl.nx, pl.ny, pl.nz, band);
+        const bool vertical = plane_is_vertical(P, kind, pl.nz);
+        if (vertical) {
+            int any = 0;
+            const unsigned nstrip = patch_chunks<64>(pts, true);
+            const StripBand band = strip_band(pl.d, P.th_dist_v);
+            for (unsigned c = (unsigned)wv; c < nstrip; c += kWaves) {
+                ChunkPts cs2;
+                const PartSel sel = chunk_sel<64>(pts, c, true);
+                load_chunk<64>(cs2, pts, sel);
+                const unsigned hit = lane_strip<64>(cs2, true, pl.nx, pl.ny, pl.nz, band);
 #pragma unroll
-                    for (int k = 0; k < kPPT; ++k)
-                        if (hit >> k & 1u) strip_point(pts, chunk_slot<64>(sel, k, (unsigned)ln), it);
-                    any |= hit != 0u;
-                }
-                if (__syncthreads_or(any)) {  // the working set changed (and the marks are visible)
-                    lpr_valid = false;
-                    stash_valid = false;
-                }
+                for (int k = 0; k < kPPT; ++k)
+                    if (hit >> k & 1u) strip_point(pts, chunk_slot<64>(sel, k, (unsigned)ln), it);
+                any |= hit != 0u;
             }
-            ++it;
-            if (!vertical || it >= P.num_iter) {
-                kind = ST_SEED;
-                it = 0;
+            if (__syncthreads_or(any)) {  // the working set changed (and the marks are visible)
+                lpr_valid = false;
+                stash_valid = false;
             }
-        } else if (kind == ST_SEED) {
-            kind = (cnt == 0 && P.enable_RVPF != 0 && zone != 0) ? ST_LAZY : ST_ITER;
-        } else if (kind == ST_LAZY) {
-            kind = ST_ITER;
-        } else if (kind == ST_ITER) {
-            if (last || conv) {
-                if (threadIdx.x == 0) write_record(Bt.recs + (size_t)f * P.num_bins + bin, pl, n, (unsigned)cnt, !use_hi && pc.n_hi > 0u, 6, it + 1);
-                kind = ST_DONE;
-            }
-            ++it;
         }
+        if (next_stage(P, zone, kind, it, vertical, cnt, last, conv) && threadIdx.x == 0)
+            write_record(Bt.recs + (size_t)f * P.num_bins + bin, pl, n, (unsigned)cnt, !use_hi && pc.n_hi > 0u, member_lg<64>(), it);
         probe(6);
     }
     if (probing) Bt.dbg[62] = n;
@@ -2397,13 +2410,11 @@ __device__ __forceinline__ void fit_stream_patch(FitShared &sh, const PwppBatch 
     const int bin = pc.bin, zone = pc.zone;
     const unsigned n = pc.n;
     PwppPatchRec *rec = Bt.recs + (size_t)f * P.num_bins + bin;
-    const PwppFrameDesc fd = Bt.frames[f];
-    const PatchRef pts = patch_ref(Bt, fd, pc);  // (always both parts: a patch this large is rare)
-    uint8_t *frame_member = Bt.member + fd.mbase;
-    const double sensor_height = fd.state_in >= 0 ? Bt.st_scalar[fd.state_in].sensor_height : P.sensor_height;
-    const double cutoff = P.margin * sensor_height;  // ref :90
+    const FrameCtx fc = frame_ctx(Bt, f);
+    const PatchRef pts = patch_ref(Bt, fc.fd, pc);  // (always both parts: a patch this large is rare)
+    uint8_t *frame_member = fc.member;
+    const double cutoff = fc.cutoff, scale = fc.scale;
     const bool use_cutoff = zone == 0;
-    const double scale = (double)(1 << P.fxp_shift);
 
     if (threadIdx.x == 0) {
         for (int k = 0; k < 3; ++k) {
@@ -2626,10 +2637,39 @@ __global__ __launch_bounds__(kBlock) void k_fit_fixup(PwppBatch Bt) {
 
 }  // namespace
 
+// every kernel exists for both widths of the arithmetic contract (PwppDevParams.fxp_wide): launch the <..., wide> instance
+template <class... A>
+static void launch_width(bool wide, void (*narrow)(A...), void (*wider)(A...), dim3 grid, dim3 block, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(wide ? wider : narrow, grid, block, 0, stream, args...);
+}
+// The kernels a plan entry "<mode><lanes>[.<patches per wave>]" may name.  lanes = 0: the mode takes any of 8, 16, 32, 64 (its
+// kernel has one row width); "H" is not here: k_fit_hybrid is launched with its own grid and arguments.
+struct FitPlanKernel {
+    char mode;
+    int lanes, per_wave;
+    void (*narrow)(PwppBatch, int, int);
+    void (*wider)(PwppBatch, int, int);
+};
+#define PWPP_FIT_ROW(mode, lanes, per_wave, kern, ...) {mode, lanes, per_wave, kern<__VA_ARGS__, false>, kern<__VA_ARGS__, true>}
+static const FitPlanKernel kFitPlanKernels[] = {
+    PWPP_FIT_ROW('S', 8, 0, k_fit_srows, 8),
+    PWPP_FIT_ROW('S', 16, 0, k_fit_srows, 16),
+    PWPP_FIT_ROW('S', 32, 0, k_fit_srows, 32),
+    PWPP_FIT_ROW('S', 64, 0, k_fit_srows, 64),
+    {'B', 0, 0, k_fit_brows<false>, k_fit_brows<true>},
+    PWPP_FIT_ROW('W', 16, 64, k_fit_w64, 16, 64),
+    PWPP_FIT_ROW('W', 16, 32, k_fit_w64, 16, 32),
+    PWPP_FIT_ROW('W', 16, 16, k_fit_w64, 16, 16),
+    PWPP_FIT_ROW('W', 64, 16, k_fit_w64, 64, 16),
+    PWPP_FIT_ROW('W', 64, 8, k_fit_w64, 64, 8),
+    PWPP_FIT_ROW('W', 64, 4, k_fit_w64, 64, 4),
+    PWPP_FIT_ROW('W', 64, 2, k_fit_w64, 64, 2),
+};
+#undef PWPP_FIT_ROW
+
 extern "C" int pwpp_launch_fixup(const PwppBatch *batch, hipStream_t stream) {
     if (batch->num_frames <= 0) return 0;
-    if (batch->P.fxp_wide) hipLaunchKernelGGL(k_fit_fixup<true>, dim3(batch->num_frames), dim3(kBlock), 0, stream, *batch);
-    else hipLaunchKernelGGL(k_fit_fixup<false>, dim3(batch->num_frames), dim3(kBlock), 0, stream, *batch);
+    launch_width(batch->P.fxp_wide != 0, k_fit_fixup<false>, k_fit_fixup<true>, dim3(batch->num_frames), dim3(kBlock), stream, *batch);
     return (int)hipGetLastError();
 }
 
@@ -2653,6 +2693,7 @@ extern "C" const char *pwpp_big_batch_plan(int max_n, int num_bins, int wide) {
 extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev) {
     const PwppBatch &B = *batch;
     const int F = B.num_frames, nb = B.P.num_bins;
+    const bool wide = B.P.fxp_wide != 0;
     const unsigned min_pts = B.P.min_pts < 1 ? 1u : (unsigned)(B.P.min_pts > 0xffffffffull ? 0xffffffffu : B.P.min_pts);
     // a class whose patches have more than `lo` points holds at most max_n / lo of them per frame
     auto cap = [&](unsigned lo) -> unsigned {
@@ -2722,18 +2763,10 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
             if (ev) (void)hipEventRecord(ev[slot], stream);
             const unsigned patches = cap(n_lo);
             const dim3 grid(F, (patches * (unsigned)g + kBlock - 1) / kBlock);
-            // (every kernel exists for both widths of the arithmetic contract, PwppDevParams.fxp_wide)
-#define PWPP_LAUNCH2(kern, ...) do { if (B.P.fxp_wide) hipLaunchKernelGGL((kern<true>), __VA_ARGS__); else hipLaunchKernelGGL((kern<false>), __VA_ARGS__); } while (0)
-#define PWPP_LAUNCH_T(kern, a, ...) do { if (B.P.fxp_wide) hipLaunchKernelGGL((kern<a, true>), __VA_ARGS__); else hipLaunchKernelGGL((kern<a, false>), __VA_ARGS__); } while (0)
-#define PWPP_LAUNCH_W(a, b, ...) do { if (B.P.fxp_wide) hipLaunchKernelGGL((k_fit_w64<a, b, true>), __VA_ARGS__); else hipLaunchKernelGGL((k_fit_w64<a, b, false>), __VA_ARGS__); } while (0)
-            if (mode == 'S' && g == 8) PWPP_LAUNCH_T(k_fit_srows, 8, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
-            else if (mode == 'S' && g == 16) PWPP_LAUNCH_T(k_fit_srows, 16, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
-            else if (mode == 'S' && g == 32) PWPP_LAUNCH_T(k_fit_srows, 32, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
-            else if (mode == 'S' && g == 64) PWPP_LAUNCH_T(k_fit_srows, 64, grid, dim3(kBlock), 0, stream, B, k_lo, k_hi);
-            else if (mode == 'H') {  // "H64:<n>": up to n points a wave per patch, four waves above (up to 2^19 - 1 points), everything in one launch
+            if (mode == 'H') {  // "H64:<n>": up to n points a wave per patch, four waves above (up to 2^19 - 1 points), everything in one launch
                 const int k_top = pwpp_size_bucket(2023u * 256u + 1u);
                 const unsigned nb_big = cap(pwpp_bucket_floor(k_hi));
-                PWPP_LAUNCH2(k_fit_hybrid, dim3(F, nb_big + (patches + kWaves - 1) / kWaves), dim3(kBlock), 0, stream, B, k_hi, k_top, nb_big);
+                launch_width(wide, k_fit_hybrid<false>, k_fit_hybrid<true>, dim3(F, nb_big + (patches + kWaves - 1) / kWaves), dim3(kBlock), stream, B, k_hi, k_top, nb_big);
                 k_lo = k_top;
                 n_lo = pwpp_bucket_floor(k_top);
                 ++slot;
@@ -2741,20 +2774,13 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
                 if (*p == ',') ++p;
                 continue;
             }
-            else if (mode == 'B') PWPP_LAUNCH2(k_fit_brows, dim3(F, patches), dim3(kBlock), 0, stream, B, k_lo, k_hi);
-            else if (mode == 'W') {  // "W<lanes per patch>.<patches per wave>"
-                if (pw == 0) pw = 64;
-                const dim3 wgrid(F, (patches + (unsigned)pw - 1) / (unsigned)pw), wblock(64);  // one wave per workgroup
-                if (g == 16 && pw == 64) PWPP_LAUNCH_W(16, 64, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else if (g == 16 && pw == 32) PWPP_LAUNCH_W(16, 32, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else if (g == 16 && pw == 16) PWPP_LAUNCH_W(16, 16, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else if (g == 64 && pw == 16) PWPP_LAUNCH_W(64, 16, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else if (g == 64 && pw == 8) PWPP_LAUNCH_W(64, 8, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else if (g == 64 && pw == 4) PWPP_LAUNCH_W(64, 4, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else if (g == 64 && pw == 2) PWPP_LAUNCH_W(64, 2, wgrid, wblock, 0, stream, B, k_lo, k_hi);
-                else return (int)hipErrorInvalidValue;
-            }
-            else return (int)hipErrorInvalidValue;
+            if (mode == 'W' && pw == 0) pw = 64;  // "W<lanes per patch>.<patches per wave>"
+            const FitPlanKernel *fk = nullptr;
+            for (const FitPlanKernel &k : kFitPlanKernels)
+                if (k.mode == mode && (k.lanes == 0 || k.lanes == g) && (mode != 'W' || k.per_wave == pw)) fk = &k;
+            if (!fk) return (int)hipErrorInvalidValue;
+            if (mode == 'W') launch_width(wide, fk->narrow, fk->wider, dim3(F, (patches + (unsigned)pw - 1) / (unsigned)pw), dim3(64), stream, B, k_lo, k_hi);  // one wave per workgroup
+            else launch_width(wide, fk->narrow, fk->wider, mode == 'B' ? dim3(F, patches) : grid, dim3(kBlock), stream, B, k_lo, k_hi);
             ++slot;
             k_lo = k_hi;
             n_lo = pwpp_bucket_floor(k_hi);
@@ -2767,7 +2793,7 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
     if (ev) (void)hipEventRecord(ev[5], stream);
     // whatever is larger than the plan's last class: a workgroup per patch (none can exist when the largest
     // frame of the batch is smaller than that class's upper bound -- one launch less on the latency path)
-    if ((unsigned)B.max_n >= n_lo) PWPP_LAUNCH2(k_fit_stream, dim3(F, cap(n_lo)), dim3(kBlock), 0, stream, B, k_lo);
+    if ((unsigned)B.max_n >= n_lo) launch_width(wide, k_fit_stream<false>, k_fit_stream<true>, dim3(F, cap(n_lo)), dim3(kBlock), stream, B, k_lo);
     if (ev) (void)hipEventRecord(ev[6], stream);
     return (int)hipGetLastError();
 }
