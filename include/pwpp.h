@@ -347,6 +347,36 @@ PWPP_API int pwpp_get_all_point_distances(pwpp_handle *h, float *out);          
 /* device pointers (either may be NULL); frame_base as in the device view */
 PWPP_API int pwpp_get_device_point_planes(pwpp_handle *h, const int32_t **patches, const float **distances);
 
+/* ---- whole records of the ground / non-ground points (pwpp_set_point_records, pwpp_get_*_records) ------------------------
+ * getGround() / getNonground() (reference patchworkpp.h:157-158) with everything the input carried: row r of a list is the
+ * record of the point the index getter names at r, in whatever output order the handle has.  The row size is the same for
+ * every frame of a call, pwpp_get_record_bytes():
+ *   PWPP_LAYOUT_ROW_MAJOR   cols * 4       the input row
+ *   PWPP_LAYOUT_COL_MAJOR   cols * 4       {x, y, z[, w]} gathered from the planes, row-major
+ *   pwpp_estimate_ground_fields*  point_step   the point verbatim: every byte, padding and the fields the library never reads included
+ * Bytes are copied, never interpreted: NaN payloads, -0.0 and integer fields (ring, time stamps) arrive as they were.
+ * pwpp_get_ground_records / pwpp_get_nonground_records fill count x record_bytes bytes and work after every call:
+ *   - after a call launched with pwpp_set_point_records(h, 1) the rows were written on the device behind the lists (their time
+ *     counts in the k_emit slot of the kernel profile) and are only copied: the input is not touched again, so after a
+ *     PWPP_MEM_DEVICE call the caller's buffer may be overwritten or freed;
+ *   - otherwise they are gathered from the frame's input when the getter runs, as pwpp_get_ground_xyz does, under its lifetime
+ *     rule: after a PWPP_MEM_DEVICE call the caller's buffer must still hold the frame.
+ * pwpp_get_all_records (the whole batch in ONE copy) and pwpp_get_device_records (device pointer, nothing copied) need a last
+ * call that ran with the setting on and return PWPP_E_STATE otherwise.  The buffer is laid out like the index lists, in rows:
+ * frame f starts at row frame_base[f] (byte frame_base[f] * record_bytes: 4-byte aligned, 16-byte aligned when record_bytes is a
+ * multiple of 16), holds its n_ground ground rows, then its n_nonground non-ground rows; the frame's remaining n_dropped rows are
+ * unspecified.  frame_base (frames + 1 entries) and counts (frames x 8 int32) as in pwpp_get_all_indices; either may be NULL.
+ * `out` must hold total points x record_bytes bytes.  The device buffer stays valid until the handle's next estimate call,
+ * pwpp_trim_workspace or pwpp_destroy.  The setting applies to the batches launched after the call; with it off nothing is
+ * allocated or launched for it.  A pipe's handles take it through pwpp_pipe_handle. */
+#define PWPP_HAS_POINT_RECORDS 1
+PWPP_API int pwpp_set_point_records(pwpp_handle *h, int on);
+PWPP_API int pwpp_get_record_bytes(pwpp_handle *h);   /* bytes per row of the last call; PWPP_E_STATE before any call */
+PWPP_API int pwpp_get_ground_records(pwpp_handle *h, int frame, void *out);
+PWPP_API int pwpp_get_nonground_records(pwpp_handle *h, int frame, void *out);
+PWPP_API int pwpp_get_all_records(pwpp_handle *h, void *out, int64_t *frame_base, int32_t *counts);
+PWPP_API int pwpp_get_device_records(pwpp_handle *h, const void **out, int32_t *record_bytes);   /* either may be NULL */
+
 /* Overlap mode (ON by default): batches of 128 frames or more are processed as two frame ranges -- binning
  * and index lists of both on the handle's main stream, each range's plane fits on a stream of its own -- so
  * that the stages of one range fill the wave slots the other leaves empty (binning and index lists are bound
@@ -421,6 +451,9 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         (default 0.6; 1e30 = no high parts): the fit passes skip a high part whenever they can
  *                         prove that none of its points can enter the pass
  *   "hi_split_zones"      how many zones' bins are stored in two parts (0..4, default 1: the near zone)
+ *   "records_path"        how the point records are gathered (pwpp_set_point_records): "0" (default) the kernel chooses by row size and
+ *                         alignment; "1": one lane per row at every size (the yardstick of tools/point_records_cost.py); "2": never
+ *                         the 16-byte pieces (tests)
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

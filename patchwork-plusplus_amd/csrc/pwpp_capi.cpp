@@ -29,6 +29,7 @@ extern "C" int pwpp_launch_clear(const PwppBatch *batch, hipStream_t stream);
 extern "C" int pwpp_launch_k5_tail(const PwppBatch *batch, hipStream_t aux, hipEvent_t aux_fork, hipEvent_t aux_join);
 extern "C" int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream);
 extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, int count, float *out, hipStream_t stream);
+extern "C" int pwpp_launch_gather_records(const PwppFrameDesc *fd, const int *idx, int count, void *out, int path, hipStream_t stream);
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
 
@@ -190,6 +191,11 @@ struct pwpp_handle {
     DevBuf<int32_t> d_pt_patch;     // [total points] the row of every point's patch (-1: none), laid out like d_out
     DevBuf<float> d_pt_dist;        // [total points] its signed distance to that patch's plane (NaN: none)
     DevBuf<int32_t> d_pt_rows;      // [frames][B] K9's bin -> row table (PwppBatch.pt_rows)
+    bool point_records = false;     // pwpp_set_point_records
+    bool point_records_last = false; // the last call ran with them
+    int record_bytes = 0;           // bytes per row of the last call's records (0: no call yet)
+    int records_path = 0;           // option "records_path"
+    DevBuf<uint8_t> d_records;      // [total points][record_bytes] + 64: the records of the listed points, rows laid out like d_out
     DevBuf<uint32_t> d_bins;   // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
     DevBuf<uint32_t> d_parts;  // TWO copies of 3 slabs of frames*(2B+2): part_count, part_off, part_cursor (pwpp_dev.h: a bin is stored in two
                                // parts); a call works on one copy while its K5 zeroes the other for the next call (PwppBatch.next_part_count)
@@ -614,6 +620,11 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt) {
         bt.pt_patch = h->d_pt_patch.p;
         bt.pt_dist = h->d_pt_dist.p;
         bt.pt_rows = h->d_pt_rows.p;
+    }
+    if (h->point_records) {
+        bt.records = h->d_records.p;
+        bt.record_bytes = h->record_bytes;
+        bt.records_path = h->records_path;
     }
     if (labels_on(h)) {
         bt.labels = h->d_labels.p;
@@ -1270,6 +1281,7 @@ int pwpp_destroy(pwpp_handle *h) {
     h->d_results.release();
     h->h_results.release();
     h->d_xyz.release();
+    h->d_records.release();
     h->d_dbg.release();
     h->d_st_stream.release();
     h->d_st_fresh.release();
@@ -1397,6 +1409,9 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
         if ((rc = h->d_pt_rows.ensure((size_t)frames * B))) return rc;
     }
     h->point_planes_last = h->point_planes;
+    h->record_bytes = fs ? fs->step : 4 * cols;
+    if (h->point_records && (rc = h->d_records.ensure(tp * (size_t)h->record_bytes + 64))) return rc;  // (64 bytes of slack behind the last row)
+    h->point_records_last = h->point_records;
     if ((rc = h->d_bins.ensure((size_t)frames * NB * 4))) return rc;
     if ((rc = h->d_parts.ensure(2 * counters_copy_words((size_t)frames * NP)))) return rc;  // two copies
     if ((rc = h->d_recs.ensure((size_t)frames * B))) return rc;
@@ -1956,6 +1971,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         HIPCHK(hipMemsetAsync(h->d_bin_max.p, 0, (size_t)PWPP_NUM_PARTS(h->dp.num_bins) * sizeof(uint32_t), h->stream));
         h->have_observation = false;
         h->table_stale = true;
+    } else if (k == "records_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "records_path=%s: 0, 1 or 2 expected", value);
+        h->records_path = v;
     } else if (k == "debug_flags") {
         const int v = std::atoi(value);
         //  the fit-chain probes (4) and the binning / scan / GLE probes (8) write the same 64-entry array
@@ -1980,7 +1999,8 @@ int64_t pwpp_get_workspace_bytes(pwpp_handle *h) {
            b(h->d_xyz.cap, 4) + b(h->d_dbg.cap, 8) + b(h->d_st_stream.cap, sizeof(PwppStateScalar)) + b(h->d_st_fresh.cap, sizeof(PwppStateScalar)) +
            b(h->d_st_snap.cap, sizeof(PwppStateScalar)) + b(h->d_hist_stream.cap, 8) + b(h->d_hist_fresh.cap, 8) + b(h->d_hist_snap.cap, 8) +
            b(h->d_pl_stream.cap, sizeof(PwppPlaneState)) + b(h->d_pl_fresh.cap, sizeof(PwppPlaneState)) + b(h->d_pl_snap.cap, sizeof(PwppPlaneState)) +
-           b(h->d_labels.cap, 1) + b(h->d_label_tiles.cap, 4) + b(h->d_pt_patch.cap, 4) + b(h->d_pt_dist.cap, 4) + b(h->d_pt_rows.cap, 4);
+           b(h->d_labels.cap, 1) + b(h->d_label_tiles.cap, 4) + b(h->d_pt_patch.cap, 4) + b(h->d_pt_dist.cap, 4) + b(h->d_pt_rows.cap, 4) +
+           b(h->d_records.cap, 1);
 }
 
 int pwpp_trim_workspace(pwpp_handle *h) {
@@ -2007,6 +2027,7 @@ int pwpp_trim_workspace(pwpp_handle *h) {
     h->d_pt_patch.release();
     h->d_pt_dist.release();
     h->d_pt_rows.release();
+    h->d_records.release();
     h->d_xyz.release();
     h->d_frames.release();
     h->d_frames_probe.release();
@@ -2133,6 +2154,76 @@ int pwpp_get_device_point_planes(pwpp_handle *h, const int32_t **patches, const 
     if (rc || (rc = check_point_planes(h))) return rc;
     if (patches) *patches = h->d_pt_patch.p;
     if (distances) *distances = h->d_pt_dist.p;
+    return PWPP_OK;
+}
+
+int pwpp_set_point_records(pwpp_handle *h, int on) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    int rc = use_device(h);
+    if (rc) return rc;
+    if ((rc = finish_pending(h))) return rc;
+    h->point_records = on != 0;
+    return PWPP_OK;
+}
+
+int pwpp_get_record_bytes(pwpp_handle *h) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (h->record_bytes <= 0) return fail(PWPP_E_STATE, "no frame has been processed yet");
+    return h->record_bytes;
+}
+
+// the record buffer of the last call: its results, and point records among them
+static int check_point_records(pwpp_handle *h) {
+    if (!h->point_records_last) return fail(PWPP_E_STATE, "the last call ran without point records (pwpp_set_point_records)");
+    return PWPP_OK;
+}
+
+// The rows of one list of one frame.  A call that ran with point records left them in d_records: a copy.  Otherwise they are
+// gathered now from the frame's input, like copy_xyz (after a PWPP_MEM_DEVICE call: the caller's buffer, which must still hold it).
+static int copy_records(pwpp_handle *h, int frame, void *out, bool ground) {
+    int rc = check_frame(h, frame);
+    if (rc) return rc;
+    const PwppFrameResult &r = h->h_results.p[frame];
+    const int64_t first = h->h_base.p[frame] + (ground ? 0 : r.n_ground);
+    const int count = ground ? r.n_ground : r.n_nonground;
+    if (count <= 0) return PWPP_OK;
+    if (!out) return fail(PWPP_E_ARG, "null output");
+    const size_t rb = (size_t)h->record_bytes, bytes = (size_t)count * rb;
+    const uint8_t *src = h->d_records.p + (size_t)first * rb;
+    if (!h->point_records_last) {
+        // (d_xyz is the getters' gather scratch: whole floats, and 16-byte aligned for the wide pieces)
+        if ((rc = h->d_xyz.ensure((bytes + 3) / 4))) return rc;
+        const int lrc = pwpp_launch_gather_records(&h->descs[(size_t)frame], h->d_out.p + first, count, h->d_xyz.p, h->records_path, h->stream);
+        if (lrc != 0) return fail(PWPP_E_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)lrc));
+        src = reinterpret_cast<const uint8_t *>(h->d_xyz.p);
+    }
+    HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PWPP_OK;
+}
+int pwpp_get_ground_records(pwpp_handle *h, int frame, void *out) { return copy_records(h, frame, out, true); }
+int pwpp_get_nonground_records(pwpp_handle *h, int frame, void *out) { return copy_records(h, frame, out, false); }
+
+int pwpp_get_all_records(pwpp_handle *h, void *out, int64_t *frame_base, int32_t *counts) {
+    int rc = check_frame(h, 0);
+    if (rc || (rc = check_point_records(h))) return rc;
+    const int64_t total = h->h_base.p[h->frames];
+    if (total > 0) {
+        if (!out) return fail(PWPP_E_ARG, "null output");
+        HIPCHK(hipMemcpyAsync(out, h->d_records.p, (size_t)total * (size_t)h->record_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if (frame_base) std::memcpy(frame_base, h->h_base.p, ((size_t)h->frames + 1) * sizeof(int64_t));
+    if (counts) std::memcpy(counts, h->h_results.p, (size_t)h->frames * sizeof(PwppFrameResult));
+    return PWPP_OK;
+}
+
+int pwpp_get_device_records(pwpp_handle *h, const void **out, int32_t *record_bytes) {
+    if (!h || (!out && !record_bytes)) return fail(PWPP_E_ARG, "null argument");
+    int rc = check_frame(h, 0);
+    if (rc || (rc = check_point_records(h))) return rc;
+    if (out) *out = h->d_records.p;
+    if (record_bytes) *record_bytes = h->record_bytes;
     return PWPP_OK;
 }
 

@@ -91,6 +91,10 @@ struct PwppFrameDesc {
                        // path, frame * slots_per_frame on the one-pass path (see cap_off)
 };
 
+// Bytes of one row of pwpp_get_*_records: a matrix row is its `cols` floats (gathered from the planes of a column-major
+// matrix), a PWPP_LAYOUT_FIELDS point its whole record of `step` bytes.  2 = PWPP_LAYOUT_FIELDS (include/pwpp.h).
+__host__ __device__ inline int32_t pwpp_record_bytes(const PwppFrameDesc &fd) { return fd.layout == 2 ? fd.step : 4 * fd.cols; }
+
 struct PwppStateScalar {  // = pwpp_state
     double sensor_height;
     double elevation_thr[4];
@@ -209,6 +213,10 @@ struct PwppBatch {
     int32_t *pt_patch;           // [total points] laid out like out_idx: the row of the point's patch in the frame's patch records, -1 = none
     float *pt_dist;              // same slots: the signed distance of the point to that patch's reported plane, NaN = none
     int32_t *pt_rows;            // [frames][B] scratch: the row of every bin that is a patch, -1 for the others
+    // Whole point records of the listed points (pwpp_set_point_records), written behind the lists of this launch's frames; null = off
+    uint8_t *records;            // [total points][record_bytes] laid out like out_idx: row fd.base + r = the record of the point out_idx[fd.base + r]
+    int32_t record_bytes;        // bytes per row, the same for every frame of a call (pwpp_record_bytes)
+    int32_t records_path;        // option "records_path": 0 = the path the kernel chooses, 1 / 2 = measurement and test variants (k_point_records)
     // host side only (the kernels never read these)
     int64_t point_first, point_count;  // the per-point slots of this launch's frames (contiguous: the fills of labels and point planes)
     const char *fit_plan;        // option "fit_plan": overrides the plan pwpp_launch_fit would choose; null or empty = automatic

@@ -18,6 +18,7 @@
 //   K7  k_order_sublists   optional: the reference's order inside every part of the lists
 //   K8  k_label_*          optional: per-point labels from the final lists; cloud-order lists from the labels
 //   K9  k_pp_*             optional: per-point patch row and signed distance to the patch's plane  (ref :551-554)
+//   K10 k_point_records    optional: the whole input records of the listed points, row for row behind the lists  (ref :8-16)
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -2797,7 +2798,133 @@ __global__ __launch_bounds__(kPpWave, 8) void k_pp_patch(PwppBatch Bt) {
     }
 }
 
+
+// ------------------------------------------------------------------------------------------
+// K10 (optional)  whole records of the listed points (pwpp_set_point_records, pwpp_get_*_records)
+// ------------------------------------------------------------------------------------------
+// Row r of a list = the record of point idx[r], as bytes: the `cols` floats of a matrix row (gathered from the planes of a
+// column-major matrix), the whole point_step bytes of a PointCloud2 point -- padding and the fields nobody reads included.  Moved
+// as dwords, never as floats: NaN payloads, -0.0 and integer fields survive.  A wave takes 64 consecutive list entries (one
+// coalesced load of their indices) and writes their 64 W dwords (W = record_bytes / 4, wave-uniform) as one contiguous stream:
+//   W = 3, W = 4 (16-byte aligned input) and column-major planes: one lane per row -- three dwords / one 16-byte piece per lane
+//     is that stream already;
+//   otherwise lane l writes piece l + 64 t, t = 0 .. W - 1, fetches the index of the entry that owns the piece with a shuffle and
+//     reads piece (l + 64 t) % W of that record: a record is read by a run of adjacent lanes, every store instruction covers 256
+//     contiguous bytes -- 1 KiB with 16-byte pieces, when W is a multiple of 4 and both sides are 16-byte aligned.  The owner and
+//     the piece follow l + 64 t by additions (64 = dq W + dr), not by a division per piece.
+// Dword stores need the 4-byte alignment every row has (a frame's rows start at frame_base * record_bytes: with 12-byte rows no
+// more than that).  An entry whose index is not a point of the frame (a frame whose lists are not written yet: k_label_scatter
+// above) writes nothing; such a frame is gathered again behind its lists.
+constexpr int kRecBlock = 256;      // four waves of 64 list entries
+constexpr int kRecPlain = 1;        // option "records_path": one lane per row at every width (the yardstick of tools/point_records_cost.py)
+constexpr int kRecDwords = 2;       // ... never the 16-byte pieces (tests, measurements); 0 = as described above
+
+// the streaming path: V = one piece (a dword or 16 bytes), W = pieces per record, i = the lane's own index (entry e0 + lane)
+template <class V>
+__device__ __forceinline__ void stream_rows64(const V *src, V *orow, unsigned W, int i, unsigned n) {
+    const unsigned l = (unsigned)lane_id();
+    const unsigned dq = 64u / W, dr = 64u % W;
+    unsigned q = W > 63u ? 0u : l / W, r = l - q * W;  // piece l + 64 t = piece r of entry q
+    // four pieces in flight per lane, in named registers (an array indexed under a predicate ends up in LDS)
+    auto fetch = [&](bool live, V &v) -> bool {
+        if (!live) return false;  // (wave-uniform: every lane takes part in the shuffle; q <= 63 for every piece below 64 W)
+        const int iq = __shfl(i, (int)q, 64);
+        const bool has = (unsigned)iq < n;
+        if (has) v = src[(size_t)iq * W + r];
+        q += dq;
+        r += dr;
+        if (r >= W) {
+            r -= W;
+            ++q;
+        }
+        return has;
+    };
+#pragma unroll 1
+    for (unsigned t = 0; t < W; t += 4) {
+        V v0 = V(), v1 = V(), v2 = V(), v3 = V();
+        const bool h0 = fetch(true, v0), h1 = fetch(t + 1 < W, v1), h2 = fetch(t + 2 < W, v2), h3 = fetch(t + 3 < W, v3);
+        V *o = orow + l + 64u * t;
+        if (h0) o[0] = v0;
+        if (h1) o[64] = v1;
+        if (h2) o[128] = v2;
+        if (h3) o[192] = v3;
+    }
+}
+
+// the rows e0 .. e0 + 63 (below `count`) of the list `idx` of frame fd -> out, row 0 of the list at out[0]; one wave
+__device__ __forceinline__ void gather_rows64(const PwppFrameDesc &fd, const int *idx, int64_t e0, int64_t count, uint32_t *out, int path) {
+    const unsigned l = (unsigned)lane_id(), n = (unsigned)fd.n;
+    const unsigned W = (unsigned)pwpp_record_bytes(fd) >> 2;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(fd.pts);
+    const int i = e0 + l < count ? idx[e0 + l] : -1;
+    const bool ok = (unsigned)i < n;
+    uint32_t *orow = out + (size_t)e0 * W;  // the wave's 64 W dwords
+    const bool both16 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0u;
+    if (fd.layout == PWPP_LAYOUT_COL_MAJOR) {  // W = 3 or 4 planes of n dwords
+        if (!ok) return;
+        uint32_t v[4];
+#pragma unroll
+        for (unsigned k = 0; k < 4; ++k) v[k] = k < W ? src[(size_t)k * n + (unsigned)i] : 0u;
+        if (W == 4u && both16) {
+            reinterpret_cast<uint4 *>(orow)[l] = make_uint4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (unsigned k = 0; k < 4; ++k)
+                if (k < W) orow[(size_t)l * W + k] = v[k];
+        }
+    } else if (path == kRecPlain) {
+        if (!ok) return;
+        for (unsigned k = 0; k < W; ++k) orow[(size_t)l * W + k] = src[(size_t)(unsigned)i * W + k];
+    } else if (W == 3u) {
+        if (!ok) return;
+        const uint32_t *p = src + (size_t)3 * (unsigned)i;
+        const uint32_t a = p[0], b = p[1], c = p[2];
+        orow[3u * l] = a;
+        orow[3u * l + 1u] = b;
+        orow[3u * l + 2u] = c;
+    } else if (W == 4u && both16) {
+        if (ok) reinterpret_cast<uint4 *>(orow)[l] = reinterpret_cast<const uint4 *>(src)[i];
+    } else if ((W & 3u) == 0u && both16 && path != kRecDwords) {
+        stream_rows64(reinterpret_cast<const uint4 *>(src), reinterpret_cast<uint4 *>(orow), W >> 2, i, n);
+    } else {
+        stream_rows64(src, orow, W, i, n);
+    }
+}
+
+// batch form: grid (tiles of kRecBlock entries over the largest frame, frames); frame f's two lists are one run of
+// n_ground + n_nonground entries at out_idx + fd.base, its rows start at records + fd.base * record_bytes
+__global__ __launch_bounds__(kRecBlock) void k_point_records(PwppBatch Bt) {
+    const int f = blockIdx.y;
+    const PwppFrameDesc fd = Bt.frames[f];
+    int64_t ng, nn;
+    label_counts(Bt, f, fd.n, ng, nn);
+    const int64_t e0 = ((int64_t)blockIdx.x * (kRecBlock / 64) + wave_id()) * 64;
+    if (e0 >= ng + nn) return;
+    gather_rows64(fd, Bt.out_idx + fd.base, e0, ng + nn, reinterpret_cast<uint32_t *>(Bt.records + (size_t)fd.base * (size_t)Bt.record_bytes),
+                  Bt.records_path);
+}
+
+// on-demand form: one list of one frame (the getters after a call that ran without point records)
+__global__ __launch_bounds__(kRecBlock) void k_gather_records(PwppFrameDesc fd, const int *idx, int count, uint32_t *out, int path) {
+    const int64_t e0 = ((int64_t)blockIdx.x * (kRecBlock / 64) + wave_id()) * 64;
+    if (e0 >= count) return;
+    gather_rows64(fd, idx, e0, count, out, path);
+}
+
 }  // namespace
+
+// the records of the launch's frames, behind their final lists
+static void launch_point_records(const PwppBatch &B, hipStream_t stream) {
+    const unsigned gx = (unsigned)(((int64_t)B.max_n + kRecBlock - 1) / kRecBlock);
+    if (gx > 0) hipLaunchKernelGGL(k_point_records, dim3(gx, B.num_frames), dim3(kRecBlock), 0, stream, B);
+}
+
+extern "C" int pwpp_launch_gather_records(const PwppFrameDesc *fd, const int *idx, int count, void *out, int path, hipStream_t stream) {
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL(k_gather_records, dim3((count + kRecBlock - 1) / kRecBlock), dim3(kRecBlock), 0, stream, *fd, idx, count,
+                       static_cast<uint32_t *>(out), path);
+    return (int)hipGetLastError();
+}
 
 // the per-point patch rows and plane distances of the launch's frames, behind their final lists
 static void launch_point_planes(const PwppBatch &B, hipStream_t stream) {
@@ -2891,7 +3018,7 @@ extern "C" int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream)
     return (int)hipGetLastError();
 }
 
-// stages: bit 0 = binning (K0-K3), bit 1 = plane fits + K5, bit 2 = index lists (K6, K7, K8, K9); the overlap schedule of
+// stages: bit 0 = binning (K0-K3), bit 1 = plane fits + K5, bit 2 = index lists (K6 - K10); the overlap schedule of
 // pwpp_capi.cpp launches the stages of a frame range on different streams.  Bit 3 (with bit 1): k_fit_fixup instead of the
 // fit kernels -- the host finishing a frame whose patches needed the plane fitted before them (batch->fixup_run set).
 extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev /* PWPP_NUM_KERNELS + 1 events or null */,
@@ -2962,7 +3089,7 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
             if (order_a) hipLaunchKernelGGL((k_emit<false, true>), lgrid, dim3(kEmitBlock), 0, stream, L, order_a);
             else hipLaunchKernelGGL((k_emit<false, false>), lgrid, dim3(kEmitBlock), 0, stream, L, order_a);
         }
-        if (ev && !B.labels && !B.pt_patch) (void)hipEventRecord(ev[11], stream);
+        if (ev && !B.labels && !B.pt_patch && !B.records) (void)hipEventRecord(ev[11], stream);
         if (order_a) {
             hipLaunchKernelGGL((k_order_sublists<64, 256, 0>), dim3(NB, F), dim3(64), 0, stream, B, order_a, order_b);
             // the lists above 256 entries: a work list per frame, then one workgroup per item (at most points / 257 + the two a bin can add)
@@ -2970,9 +3097,10 @@ extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, 
             hipLaunchKernelGGL(k_order_worklist, dim3(F), dim3(kBlock), 0, stream, B, 256);
             hipLaunchKernelGGL((k_order_sublists<PWPP_ORDER_BLOCK, 4096, 256>), dim3(max_items, F), dim3(PWPP_ORDER_BLOCK), 0, stream, B, order_a, order_b);
         }
-        if (B.labels || B.pt_patch) {  // behind the final lists (K7's, in reference order); profiled in k_emit's slot
+        if (B.labels || B.pt_patch || B.records) {  // behind the final lists (K7's, in reference order); profiled in k_emit's slot
             if (B.labels) launch_labels(B, stream);
             if (B.pt_patch) launch_point_planes(B, stream);
+            if (B.records) launch_point_records(B, stream);  // (behind the labels: cloud order rewrites the lists from them)
             if (ev) (void)hipEventRecord(ev[11], stream);
         }
     }

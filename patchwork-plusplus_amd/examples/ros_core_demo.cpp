@@ -3,7 +3,8 @@
 // offsets 4, 12, 20 between other fields, as a driver might publish them -- and goes through ONE long-lived node core with
 // the parameter set of the launch file (ros/launch/patchworkpp.launch.py), message after message.  Prints, per message,
 // the sizes and checksums of the three payloads the node would publish (FNV-1a of the cloud, the sum of the points' FNV-1a for the two lists); tests/test_gpu_parity.py::test_ros_node_core
-// compares them with what the C-ABI gives for the same sequence.
+// compares them with what the C-ABI gives for the same sequence.  --keep-fields (first argument): the core's keep_fields
+// parameter -- ring and time are filled in too, the two lists are checksummed as whole 32-byte records and their field lists printed.
 //
 //   g++ -std=c++17 -O2 -I ../ros/include -I ../include -I ../../include ros_core_demo.cpp -L ../lib -lpwpp_hip -o ros_core_demo
 #include <cstdio>
@@ -34,9 +35,15 @@ static unsigned long long fnv1a(const uint8_t *d, size_t n) {
 static unsigned long long fnv1a(const std::vector<uint8_t> &d) { return fnv1a(d.data(), d.size()); }
 // the order inside a patch's part of a list is the scatter order (atomics: it differs from run to run): the lists are compared
 // as multisets of 16-byte points -- the sum of the points' checksums
-static unsigned long long point_sum(const std::vector<uint8_t> &d) {
+static unsigned long long point_sum(const std::vector<uint8_t> &d, size_t step = 16) {
     unsigned long long s = 0;
-    for (size_t i = 0; i + 16 <= d.size(); i += 16) s += fnv1a(d.data() + i, 16);
+    for (size_t i = 0; i + step <= d.size(); i += step) s += fnv1a(d.data() + i, step);
+    return s;
+}
+static std::string field_list(const std::vector<patchworkpp_ros::Field> &f) {  // "name:offset:datatype:count", ...
+    std::string s;
+    for (const auto &x : f)
+        s += (s.empty() ? "\"" : ", \"") + x.name + ":" + std::to_string(x.offset) + ":" + std::to_string((int)x.datatype) + ":" + std::to_string(x.count) + "\"";
     return s;
 }
 
@@ -50,7 +57,8 @@ int main(int argc, char **argv) {
             [&](const std::string &n, double d) { return dbl.count(n) ? dbl.at(n) : d; },
             [&](const std::string &n, int d) { return ints.count(n) ? ints.at(n) : d; },
             [&](const std::string &, bool) { return false; });
-        patchworkpp_ros::SegmentationCore core(params);
+        const bool keep_fields = argc > 1 && std::string(argv[1]) == "--keep-fields";
+        patchworkpp_ros::SegmentationCore core(params, 0, keep_fields);
         const std::vector<patchworkpp_ros::Field> fields = {{"intensity", 0, patchworkpp_ros::kFloat32, 1}, {"x", 4, patchworkpp_ros::kFloat32, 1},
                                                             {"ring", 8, 4 /* UINT16 */, 1},              {"y", 12, patchworkpp_ros::kFloat32, 1},
                                                             {"z", 20, patchworkpp_ros::kFloat32, 1},     {"time", 24, 8 /* FLOAT64 */, 1}};
@@ -58,7 +66,7 @@ int main(int argc, char **argv) {
         // reaches beyond point_step (the core must refuse it before anything reads past a point)
         std::vector<patchworkpp_ros::Field> alt = fields;
         uint32_t step = 32;
-        int first = 1;
+        int first = keep_fields ? 2 : 1;
         if (argc > 1 && std::string(argv[1]) == "--layout=odd") {
             alt = {{"x", 1, patchworkpp_ros::kFloat32, 1}, {"y", 9, patchworkpp_ros::kFloat32, 1}, {"z", 17, patchworkpp_ros::kFloat32, 1}};
             step = 29;
@@ -73,6 +81,12 @@ int main(int argc, char **argv) {
             std::vector<uint8_t> blob(n * step + 8, 0xA5);  // (whatever lies between the fields must not matter)
             for (size_t i = 0; i < n; ++i) {
                 if (alt.size() == fields.size()) std::memcpy(&blob[i * step + 0], &pts[i * 4 + 3], 4);
+                if (keep_fields) {  // the fields the library never reads: they must come back with their points
+                    const uint16_t ring = (uint16_t)(i % 64);
+                    const double time = 1e-6 * (double)i;
+                    std::memcpy(&blob[i * step + 8], &ring, 2);
+                    std::memcpy(&blob[i * step + 24], &time, 8);
+                }
                 for (const auto &f : alt) {
                     const int c = f.name == "x" ? 0 : (f.name == "y" ? 1 : (f.name == "z" ? 2 : -1));
                     if (c >= 0 && f.offset + 4 <= step) std::memcpy(&blob[i * step + f.offset], &pts[i * 4 + c], 4);
@@ -87,6 +101,15 @@ int main(int argc, char **argv) {
             msg.data = blob.data();
             msg.data_size = n * step;
             const patchworkpp_ros::SegmentationCore::Output out = core.estimate(msg);
+            if (keep_fields) {
+                std::printf("{\"file\": \"%s\", \"points\": %zu, \"cloud\": [%u, %u, \"%016llx\"], \"ground\": [%u, %u, \"%016llx\"], "
+                            "\"nonground\": [%u, %u, \"%016llx\"], \"ground_fields\": [%s], \"nonground_fields\": [%s]}\n",
+                            argv[a], n, out.cloud.width, out.cloud.point_step, fnv1a(out.cloud.data), out.ground.width, out.ground.point_step,
+                            point_sum(out.ground.data, out.ground.point_step), out.nonground.width, out.nonground.point_step,
+                            point_sum(out.nonground.data, out.nonground.point_step), field_list(out.ground.fields).c_str(),
+                            field_list(out.nonground.fields).c_str());
+                continue;
+            }
             std::printf("{\"file\": \"%s\", \"points\": %zu, \"cloud\": [%u, %u, \"%016llx\"], \"ground\": [%u, %u, \"%016llx\"], "
                         "\"nonground\": [%u, %u, \"%016llx\"], \"time_us\": %.1f}\n",
                         argv[a], n, out.cloud.width, out.cloud.point_step, fnv1a(out.cloud.data), out.ground.width, out.ground.point_step,

@@ -179,6 +179,21 @@ private:
     std::vector<float> v_;
 };
 
+// Row-major (rows, cols) floats: whole input rows, intensity included (getGroundPoints without Eigen)
+class Points {
+public:
+    Points() : rows_(0), cols_(0) {}
+    Points(int rows, int cols) : rows_(rows), cols_(cols), v_((size_t)rows * (size_t)cols) {}
+    int rows() const { return rows_; }
+    int cols() const { return cols_; }
+    float operator()(int i, int j) const { return v_[(size_t)i * (size_t)cols_ + (size_t)j]; }
+    float *data() { return v_.data(); }
+    const float *data() const { return v_.data(); }
+private:
+    int rows_, cols_;
+    std::vector<float> v_;
+};
+
 // reference patchworkpp.h:114-163
 class PatchWorkpp {
 public:
@@ -278,6 +293,19 @@ public:
 #endif
     Indices pointPatchList() { return pointPatches(); }
     Distances pointDistanceList() { return pointDistances(); }
+    // extension: the frames estimated afterwards also leave the whole rows of their ground / non-ground points on the device
+    // (pwpp.h, pwpp_set_point_records); getGroundPoints / getNongroundPoints work either way, and gather on demand without it
+    void setPointRecords(bool on) { check(pwpp_set_point_records(h_, on ? 1 : 0)); }
+    // getGround() / getNonground() with every column of the input: (count, cols) floats, rows aligned with the index getters
+#ifdef PWPP_HAVE_EIGEN
+    Eigen::MatrixXf getGroundPoints() { return to_eigen(points(true)); }
+    Eigen::MatrixXf getNongroundPoints() { return to_eigen(points(false)); }
+#else
+    Points getGroundPoints() { return points(true); }
+    Points getNongroundPoints() { return points(false); }
+#endif
+    Points groundPointRows() { return points(true); }
+    Points nongroundPointRows() { return points(false); }
 
 #ifdef PWPP_HAVE_EIGEN
     // the reference's return types (fresh objects on every call, as the reference's toEigenCloud / toIndices, :8-26)
@@ -312,6 +340,12 @@ private:
         Eigen::MatrixX3f m(c.rows(), 3);
         for (int i = 0; i < c.rows(); ++i)
             for (int j = 0; j < 3; ++j) m(i, j) = c(i, j);
+        return m;
+    }
+    static Eigen::MatrixXf to_eigen(const Points &c) {
+        Eigen::MatrixXf m(c.rows(), c.cols());
+        for (int i = 0; i < c.rows(); ++i)
+            for (int j = 0; j < c.cols(); ++j) m(i, j) = c(i, j);
         return m;
     }
     static Eigen::VectorXi to_eigen(const Indices &v) {
@@ -371,6 +405,15 @@ private:
         Distances v(frame_points());
         check(pwpp_get_point_distances(h_, 0, v.data()));
         return v;
+    }
+    Points points(bool ground) {  // (the class only takes matrices: a record is a row of `cols` floats)
+        int32_t g, n, p;
+        counts(g, n, p);
+        const int rb = pwpp_get_record_bytes(h_);
+        check(rb);
+        Points c(ground ? g : n, rb / (int)sizeof(float));
+        check(ground ? pwpp_get_ground_records(h_, 0, c.data()) : pwpp_get_nonground_records(h_, 0, c.data()));
+        return c;
     }
     Cloud rows(bool centers) {
         int32_t g, n, p;

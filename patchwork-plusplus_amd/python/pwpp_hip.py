@@ -138,6 +138,13 @@ def load():
         for name in ("pwpp_get_all_point_patches", "pwpp_get_all_point_distances"):
             getattr(L, name).argtypes = [vp, vp]
         L.pwpp_get_device_point_planes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+        if hasattr(L, "pwpp_set_point_records"):  # (an older build named by PWPP_LIB_PATH has no point records: A/B runs against it)
+            L.pwpp_set_point_records.argtypes = [vp, ci]
+            L.pwpp_get_record_bytes.argtypes = [vp]
+            for name in ("pwpp_get_ground_records", "pwpp_get_nonground_records"):
+                getattr(L, name).argtypes = [vp, ci, vp]
+            L.pwpp_get_all_records.argtypes = [vp, vp, vp, vp]
+            L.pwpp_get_device_records.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int32)]
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
@@ -445,7 +452,7 @@ class Handle:
 
     def set_option(self, name, value):
         """Tuning / test switches (pwpp_set_option): fit_plan, one_pass, exact_moments, split_k5, redo_whole_batch,
-        one_pass_min_frames, one_pass_scale, fit_streams, overlap_ranges, hi_split, hi_split_zones, debug_flags.
+        one_pass_min_frames, one_pass_scale, fit_streams, overlap_ranges, hi_split, hi_split_zones, records_path, debug_flags.
         None of them changes a result except exact_moments (include/pwpp.h)."""
         self._check(self._L.pwpp_set_option(self._h, name.encode(), str(value).encode()))
 
@@ -534,6 +541,55 @@ class Handle:
         p, d = ctypes.c_void_p(), ctypes.c_void_p()
         self._check(self._L.pwpp_get_device_point_planes(self._h, ctypes.byref(p), ctypes.byref(d)))
         return int(p.value or 0), int(d.value or 0)
+
+    def set_point_records(self, on):
+        """True: the batches launched afterwards also write the whole records of their ground / non-ground points on the
+        device, row for row behind the index lists (include/pwpp.h)."""
+        self._check(self._L.pwpp_set_point_records(self._h, 1 if on else 0))
+
+    @property
+    def record_bytes(self):
+        """Bytes per row of the last call's records: cols * 4 for a matrix, point_step for a fields layout."""
+        return self._check(self._L.pwpp_get_record_bytes(self._h))
+
+    def _records(self, fn, frame, which):
+        rb = self.record_bytes
+        cnt = ctypes.c_int32(0)
+        args = [None, None, None]
+        args[which] = ctypes.byref(cnt)
+        self._check(self._L.pwpp_get_counts(self._h, frame, *args))
+        out = np.empty((max(cnt.value, 1), rb), np.uint8)
+        self._check(fn(self._h, frame, _vp(out)))
+        return out[:cnt.value]
+
+    def ground_records(self, frame=0):
+        """(n_ground, record_bytes) uint8: the records of the frame's ground points, rows aligned with ground_indices."""
+        return self._records(self._L.pwpp_get_ground_records, frame, 0)
+
+    def nonground_records(self, frame=0):
+        """(n_nonground, record_bytes) uint8: the records of the frame's non-ground points, rows aligned with nonground_indices."""
+        return self._records(self._L.pwpp_get_nonground_records, frame, 1)
+
+    def all_records(self, out=None):
+        """Every frame's records in one device-to-host copy: (records (total, record_bytes) uint8, frame_base, counts).  Frame
+        f's ground rows start at frame_base[f], its non-ground rows follow; needs a call that ran with set_point_records(True)."""
+        rb = self.record_bytes
+        v = self.device_view()
+        base = np.zeros(v.frames + 1, np.int64)
+        counts = np.zeros((v.frames, 8), np.int32)
+        total = int(np.ctypeslib.as_array(v.frame_base, shape=(v.frames + 1,))[-1])
+        if out is None:
+            out = np.empty((max(total, 1), rb), np.uint8)
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < total * rb:
+            raise ValueError("out: a contiguous uint8 array of at least %d bytes expected" % (total * rb))
+        self._check(self._L.pwpp_get_all_records(self._h, _vp(out), _vp(base), _vp(counts)))
+        return out.reshape(-1)[:total * rb].reshape(total, rb), base, counts
+
+    def device_records(self):
+        """(device address, record_bytes) of the last call's records (frame f at row frame_base[f])."""
+        p, rb = ctypes.c_void_p(), ctypes.c_int32(0)
+        self._check(self._L.pwpp_get_device_records(self._h, ctypes.byref(p), ctypes.byref(rb)))
+        return int(p.value or 0), int(rb.value)
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

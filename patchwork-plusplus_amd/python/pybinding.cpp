@@ -34,6 +34,11 @@ py::array_t<float> to_numpy(const patchwork::Distances &v) {
     if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows() * sizeof(float));
     return out;
 }
+py::array_t<float> to_numpy(const patchwork::Points &v) {
+    py::array_t<float> out({(py::ssize_t)v.rows(), (py::ssize_t)v.cols()});
+    if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows() * (size_t)v.cols() * sizeof(float));
+    return out;
+}
 py::array_t<int32_t> to_numpy(const patchwork::Indices &v) {
     py::array_t<int32_t> out((py::ssize_t)v.rows());
     if (v.rows() > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)v.rows() * sizeof(int32_t));
@@ -112,6 +117,9 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def("setPointPlanes", &PatchWorkpp::setPointPlanes, py::arg("on"))
         .def("getPointPatches", [](PatchWorkpp &s) { return to_numpy(s.pointPatchList()); })
         .def("getPointDistances", [](PatchWorkpp &s) { return to_numpy(s.pointDistanceList()); })
+        .def("setPointRecords", &PatchWorkpp::setPointRecords, py::arg("on"))
+        .def("getGroundPoints", [](PatchWorkpp &s) { return to_numpy(s.groundPointRows()); })
+        .def("getNongroundPoints", [](PatchWorkpp &s) { return to_numpy(s.nongroundPointRows()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
         .def("getNonground", [](PatchWorkpp &s) { return to_numpy(s.getNonground()); })
         .def("getCenters", [](PatchWorkpp &s) { return to_numpy(s.getCenters()); })

@@ -8,7 +8,8 @@
 //   ros/src/Utils.hpp:158-172                    PointCloud2ToEigenMat: the float32 fields "x", "y", "z" of height * width points
 //   ros/src/Utils.hpp:80-104                     CreatePointCloud2Msg: fields x, y, z (FLOAT32 at 0, 4, 8), point_step 16
 // Different on purpose: the input message is never converted to a matrix -- the binning kernels read the fields in place
-// (pwpp_estimate_ground_fields, include/pwpp.h).
+// (pwpp_estimate_ground_fields, include/pwpp.h).  And, only when asked for (keep_fields): the ground / non-ground clouds keep
+// every field of the incoming points -- intensity, ring, time -- instead of x, y, z alone (pwpp_get_*_records).
 #ifndef PATCHWORKPP_ROS_SEGMENTATION_CORE_HPP
 #define PATCHWORKPP_ROS_SEGMENTATION_CORE_HPP
 
@@ -42,7 +43,8 @@ struct CloudView {
     size_t data_size = 0;
 };
 
-// what it fills of an outgoing one: the layout of the reference's CreatePointCloud2Msg (Utils.hpp:80-104)
+// what it fills of an outgoing one: the layout of the reference's CreatePointCloud2Msg (Utils.hpp:80-104) -- or, for the two
+// lists of a core that keeps the fields, the incoming message's own fields and point_step
 struct XyzCloud {
     uint32_t height = 1, width = 0, point_step = 16, row_step = 0;
     std::vector<Field> fields;
@@ -52,6 +54,15 @@ struct XyzCloud {
         c.width = (uint32_t)n;
         c.row_step = c.width * c.point_step;
         c.fields = {{"x", 0, kFloat32, 1}, {"y", 4, kFloat32, 1}, {"z", 8, kFloat32, 1}};
+        c.data.assign(n * c.point_step, 0);
+        return c;
+    }
+    static XyzCloud like(const CloudView &msg, size_t n) {  // n points laid out as the message's own
+        XyzCloud c;
+        c.width = (uint32_t)n;
+        c.point_step = msg.point_step;
+        c.row_step = c.width * c.point_step;
+        c.fields.assign(msg.fields, msg.fields + msg.num_fields);
         c.data.assign(n * c.point_step, 0);
         return c;
     }
@@ -86,7 +97,12 @@ public:
         double time_taken_us = 0.0;
     };
 
-    explicit SegmentationCore(const patchwork::Params &params, int device = 0) : pw_(new patchwork::PatchWorkpp(params, device)) {}
+    // keep_fields (node parameter, default false = the reference's payloads): "ground" and "nonground" carry the incoming
+    // message's fields and point_step and the whole records of their points; "cloud" stays x, y, z either way
+    explicit SegmentationCore(const patchwork::Params &params, int device = 0, bool keep_fields = false)
+        : pw_(new patchwork::PatchWorkpp(params, device)), keep_fields_(keep_fields) {
+        if (keep_fields_) pw_->setPointRecords(true);  // (the records are gathered on the device behind the lists: the getters only copy)
+    }
 
     // one message: GroundSegmentationServer::EstimateGround (:76-86).  The object is long-lived, so the adaptive state carries
     // over from message to message exactly as in the reference node.
@@ -126,8 +142,13 @@ public:
             std::memcpy(dst + 4, src + oy, 4);
             std::memcpy(dst + 8, src + oz, 4);
         }
-        out.ground = pack(pw_->groundCloud());
-        out.nonground = pack(pw_->nongroundCloud());
+        if (keep_fields_) {
+            out.ground = records(msg, true, !repacked.empty());
+            out.nonground = records(msg, false, !repacked.empty());
+        } else {
+            out.ground = pack(pw_->groundCloud());
+            out.nonground = pack(pw_->nongroundCloud());
+        }
         out.time_taken_us = pw_->getTimeTaken();
         return out;
     }
@@ -136,6 +157,28 @@ public:
 
 private:
     std::unique_ptr<patchwork::PatchWorkpp> pw_;
+    bool keep_fields_;
+
+    // one list with the message's own records.  The library saw the blob itself: its rows are the records.  A repacked message
+    // (see estimate) left only x, y, z with the library: the original records are gathered here, by the index list.
+    XyzCloud records(const CloudView &msg, bool ground, bool was_repacked) {
+        if (was_repacked) {
+            const patchwork::Indices idx = ground ? pw_->groundIndexList() : pw_->nongroundIndexList();
+            XyzCloud out = XyzCloud::like(msg, (size_t)idx.rows());
+            for (int r = 0; r < idx.rows(); ++r)
+                std::memcpy(out.data.data() + (size_t)r * msg.point_step, msg.data + (size_t)idx(r) * msg.point_step, msg.point_step);
+            return out;
+        }
+        int32_t g = 0, ng = 0;
+        check(pwpp_get_counts(pw_->handle(), 0, &g, &ng, nullptr));
+        if (pwpp_get_record_bytes(pw_->handle()) != (int)msg.point_step) throw std::runtime_error("patchworkpp (HIP): record size differs from point_step");
+        XyzCloud out = XyzCloud::like(msg, (size_t)(ground ? g : ng));
+        check(ground ? pwpp_get_ground_records(pw_->handle(), 0, out.data.data()) : pwpp_get_nonground_records(pw_->handle(), 0, out.data.data()));
+        return out;
+    }
+    static void check(int rc) {
+        if (rc < 0) throw std::runtime_error(std::string("patchworkpp (HIP): ") + pwpp_last_error());
+    }
 
     static int offset_of(const CloudView &msg, const char *name) {
         for (size_t k = 0; k < msg.num_fields; ++k)

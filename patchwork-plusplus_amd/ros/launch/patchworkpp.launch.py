@@ -16,9 +16,12 @@ def generate_launch_description():
     topic = LaunchConfiguration("cloud_topic", default="/pointcloud")
     base_frame = LaunchConfiguration("base_frame", default="base_link")
     use_sim_time = LaunchConfiguration("use_sim_time", default="true")
+    # true: the ground / non-ground clouds keep every field of the incoming points (intensity, ring, time ...), not x, y, z alone
+    keep_fields = LaunchConfiguration("keep_fields", default="false")
     node = Node(
         package="patchworkpp", executable="patchworkpp_node", name="patchworkpp_node", output="screen",
         remappings=[("pointcloud_topic", topic)],
-        parameters=[dict(PATCHWORKPP, base_frame=base_frame, use_sim_time=use_sim_time)],
+        parameters=[dict(PATCHWORKPP, base_frame=base_frame, use_sim_time=use_sim_time, keep_fields=keep_fields)],
     )
-    return LaunchDescription([DeclareLaunchArgument("cloud_topic", default_value="/pointcloud"), node])
+    return LaunchDescription([DeclareLaunchArgument("cloud_topic", default_value="/pointcloud"),
+                              DeclareLaunchArgument("keep_fields", default_value="false"), node])

@@ -28,7 +28,10 @@ public:
             [this](const std::string &name, double def) { return declare_parameter<double>(name, def); },
             [this](const std::string &name, int def) { return (int)declare_parameter<int>(name, def); },
             [this](const std::string &name, bool def) { return declare_parameter<bool>(name, def); });
-        core_ = std::make_unique<SegmentationCore>(params, (int)declare_parameter<int>("device", 0));
+        const int device = (int)declare_parameter<int>("device", 0);
+        // keep_fields: /patchworkpp/ground and /patchworkpp/nonground carry the incoming cloud's own fields (intensity, ring, time ...)
+        // and point_step instead of the reference's x, y, z; false = the reference's payloads
+        core_ = std::make_unique<SegmentationCore>(params, device, declare_parameter<bool>("keep_fields", false));
 
         sub_ = create_subscription<sensor_msgs::msg::PointCloud2>(
             "pointcloud_topic", rclcpp::SensorDataQoS(), std::bind(&GroundSegmentationServer::on_cloud, this, std::placeholders::_1));
