@@ -15,6 +15,7 @@
 #include <atomic>
 #include <string>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -53,10 +54,35 @@ int fail(int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail(PWPP_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// The handle's workspace: every buffer is declared ONCE, with its lifetime, and enrols itself in the list it is given
+// (pwpp_handle::bufs).  pwpp_destroy, pwpp_trim_workspace and pwpp_get_workspace_bytes are loops over that list.
+enum Lifetime {
+    kPerBatch,   // its size follows the batch: pwpp_trim_workspace frees it
+    kPerHandle,  // stays until pwpp_destroy
+};
+
+struct BufBase {
+    const bool on_device, per_batch;
+    virtual size_t bytes() const = 0;
+    virtual void release() = 0;
+    BufBase(const BufBase &) = delete;
+    BufBase &operator=(const BufBase &) = delete;
+
+  protected:
+    BufBase(std::vector<BufBase *> &list, bool on_device_, Lifetime life) : on_device(on_device_), per_batch(life == kPerBatch) { list.push_back(this); }
+    ~BufBase() = default;
+};
+
 template <class T>
-struct DevBuf {
+struct DevBuf final : BufBase {
     T *p = nullptr;
     size_t cap = 0;  // elements
+    DevBuf(std::vector<BufBase *> &list, Lifetime life) : BufBase(list, true, life) {}
+    size_t bytes() const override { return cap * sizeof(T); }
+    void swap(DevBuf &o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
     int ensure(size_t n) {
         if (n <= cap) return PWPP_OK;
         if (p) (void)hipFree(p);
@@ -70,7 +96,7 @@ struct DevBuf {
         cap = want;
         return PWPP_OK;
     }
-    void release() {
+    void release() override {
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
@@ -78,9 +104,11 @@ struct DevBuf {
 };
 
 template <class T>
-struct PinnedBuf {
+struct PinnedBuf final : BufBase {
     T *p = nullptr;
     size_t cap = 0;
+    PinnedBuf(std::vector<BufBase *> &list, Lifetime life) : BufBase(list, false, life) {}
+    size_t bytes() const override { return cap * sizeof(T); }
     int ensure(size_t n) {
         if (n <= cap) return PWPP_OK;
         if (p) (void)hipHostFree(p);
@@ -92,11 +120,27 @@ struct PinnedBuf {
         cap = want;
         return PWPP_OK;
     }
-    void release() {
+    void release() override {
         if (p) (void)hipHostFree(p);
         p = nullptr;
         cap = 0;
     }
+};
+
+// the per-point outputs a call may write next to its index lists
+enum Output { kLabels, kPointPlanes, kPointRecords };
+const char *const kOutputMissing[] = {"the last call ran without labels (pwpp_set_labels, PWPP_ORDER_CLOUD)",
+                                      "the last call ran without point planes (pwpp_set_point_planes)",
+                                      "the last call ran without point records (pwpp_set_point_records)"};
+
+// "The OTHER copy of the counters (d_parts / d_results) is clean": what the last call's K5 zeroed, and in which allocations.
+struct CleanCopy {
+    bool valid = false;
+    int frames = 0, slabs = 0;  // for a call of this many frames and slabs (1: one-pass, 3: two-pass)
+    const void *parts = nullptr, *results = nullptr;
+    size_t parts_cap = 0, results_cap = 0;
+    void capture(const pwpp_handle *h, int frames_, int slabs_);
+    bool matches(const pwpp_handle *h, int frames_, int slabs_) const;
 };
 
 const char *kKernelNames[PWPP_NUM_KERNELS] = {"k_czm_bin", "k_czm_scan", "k_czm_scatter", "k_fit_w64<16,64>", "k_fit_w64<64,p>",
@@ -107,6 +151,7 @@ std::atomic<bool> g_slot0_one_pass{false};  // diagnostic only (pwpp_kernel_name
 }  // namespace
 
 struct pwpp_handle {
+    std::vector<BufBase *> bufs;  // every DevBuf / PinnedBuf below, in declaration order (declared first: the buffers enrol as they are built)
     pwpp_params params;
     PwppDevParams dp;
     int device = 0;
@@ -152,7 +197,7 @@ struct pwpp_handle {
     int one_pass_holdoff = 0;        // batches to run on the two-pass path after an overflow
     int64_t slots_per_frame = 0;     // of the current capacity table: the parts' segments + the frame's overflow arena
     uint32_t arena_base = 0, arena_slots = 0, arena_spill = 0;  // the arena of the current table (pwpp_dev.h): first slot, slots (0: none), room for spilled records
-    DevBuf<uint2> d_arena_tag;       // [frames][arena_spill]
+    DevBuf<uint2> d_arena_tag{bufs, kPerBatch};  // [frames][arena_spill]
     int cap_max_n = -1;              // largest frame the capacity table on the device was built for
     bool cap_few = false;            // ... and whether it was built with the head-room of calls of a few frames
     int max_n = 0;
@@ -167,72 +212,65 @@ struct pwpp_handle {
     long long clamped_frames = 0;    // frames with a patch whose final ground set spanned more than z0 +- ZR (PwppFrameResult.overflow bit 2)
 
     // workspace
-    DevBuf<PwppFrameDesc> d_frames;
-    PinnedBuf<PwppFrameDesc> h_frames;
-    PinnedBuf<int64_t> h_base;
-    DevBuf<float> d_in;  // staging for host inputs
-    DevBuf<uint16_t> d_codes;
-    DevBuf<float> d_sorted_z;     // the bin-ordered planes (pwpp_dev.h): z, {x, y}, cloud index
-    DevBuf<float2> d_sorted_xy;
-    DevBuf<int> d_sorted_idx;
-    DevBuf<float2> d_bin_origin;  // [B] origins of the fixed-point plane-fit sums
-    DevBuf<float4> d_bin_bbox;    // [B] {xmin, xmax, ymin, ymax} of every bin (the fit kernels' skip test of the high parts)
-    DevBuf<uint8_t> d_member;     // membership plane (pwpp_dev.h, PWPP_SLOT_ALIGN): one bit per slot + PWPP_MEMBER_PAD bytes per part
-    DevBuf<int32_t> d_out;
-    DevBuf<unsigned long long> d_ord_a, d_ord_b;  // scratch of the reference-order mode (long sub-lists)
-    DevBuf<uint32_t> d_ord_work;                  // ... and its work lists: the sub-lists above 256 entries of every frame
+    DevBuf<PwppFrameDesc> d_frames{bufs, kPerBatch};
+    PinnedBuf<PwppFrameDesc> h_frames{bufs, kPerHandle};
+    PinnedBuf<int64_t> h_base{bufs, kPerHandle};
+    DevBuf<float> d_in{bufs, kPerBatch};  // staging for host inputs
+    DevBuf<uint16_t> d_codes{bufs, kPerBatch};
+    DevBuf<float> d_sorted_z{bufs, kPerBatch};  // the bin-ordered planes (pwpp_dev.h): z, {x, y}, cloud index
+    DevBuf<float2> d_sorted_xy{bufs, kPerBatch};
+    DevBuf<int> d_sorted_idx{bufs, kPerBatch};
+    DevBuf<float2> d_bin_origin{bufs, kPerHandle};  // [B] origins of the fixed-point plane-fit sums
+    DevBuf<float4> d_bin_bbox{bufs, kPerHandle};  // [B] {xmin, xmax, ymin, ymax} of every bin (the fit kernels' skip test of the high parts)
+    DevBuf<uint8_t> d_member{bufs, kPerBatch};  // membership plane (pwpp_dev.h, PWPP_SLOT_ALIGN): one bit per slot + PWPP_MEMBER_PAD bytes per part
+    DevBuf<int32_t> d_out{bufs, kPerBatch};
+    DevBuf<unsigned long long> d_ord_a{bufs, kPerBatch}, d_ord_b{bufs, kPerBatch};  // scratch of the reference-order mode (long sub-lists)
+    DevBuf<uint32_t> d_ord_work{bufs, kPerBatch};  // ... and its work lists: the sub-lists above 256 entries of every frame
     int output_order = PWPP_ORDER_SCATTER;
-    bool labels = false;            // pwpp_set_labels (PWPP_ORDER_CLOUD implies them)
-    bool labels_last = false;       // the last call ran with labels
-    DevBuf<uint8_t> d_labels;       // [total points + 16] one PWPP_LABEL_* per point, laid out like d_out
-    DevBuf<uint32_t> d_label_tiles; // PWPP_ORDER_CLOUD: [frames][tiles per frame] counts of the compaction (PwppBatch.label_tiles)
-    bool point_planes = false;      // pwpp_set_point_planes
-    bool point_planes_last = false; // the last call ran with them
-    DevBuf<int32_t> d_pt_patch;     // [total points] the row of every point's patch (-1: none), laid out like d_out
-    DevBuf<float> d_pt_dist;        // [total points] its signed distance to that patch's plane (NaN: none)
-    DevBuf<int32_t> d_pt_rows;      // [frames][B] K9's bin -> row table (PwppBatch.pt_rows)
-    bool point_records = false;     // pwpp_set_point_records
-    bool point_records_last = false; // the last call ran with them
+    unsigned outputs = 0;           // bits 1 << Output: what the next call writes (pwpp_set_labels, pwpp_set_point_planes, pwpp_set_point_records)
+    unsigned outputs_last = 0;      // ... and what the last call wrote (PWPP_ORDER_CLOUD implies the labels)
+    DevBuf<uint8_t> d_labels{bufs, kPerBatch};  // [total points + 16] one PWPP_LABEL_* per point, laid out like d_out
+    DevBuf<uint32_t> d_label_tiles{bufs, kPerBatch};  // PWPP_ORDER_CLOUD: [frames][tiles per frame] counts of the compaction (PwppBatch.label_tiles)
+    DevBuf<int32_t> d_pt_patch{bufs, kPerBatch};  // [total points] the row of every point's patch (-1: none), laid out like d_out
+    DevBuf<float> d_pt_dist{bufs, kPerBatch};  // [total points] its signed distance to that patch's plane (NaN: none)
+    DevBuf<int32_t> d_pt_rows{bufs, kPerBatch};  // [frames][B] K9's bin -> row table (PwppBatch.pt_rows)
     int record_bytes = 0;           // bytes per row of the last call's records (0: no call yet)
     int records_path = 0;           // option "records_path"
-    DevBuf<uint8_t> d_records;      // [total points][record_bytes] + 64: the records of the listed points, rows laid out like d_out
-    DevBuf<uint32_t> d_bins;   // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
-    DevBuf<uint32_t> d_parts;  // TWO copies of 3 slabs of frames*(2B+2): part_count, part_off, part_cursor (pwpp_dev.h: a bin is stored in two
+    DevBuf<uint8_t> d_records{bufs, kPerBatch};  // [total points][record_bytes] + 64: the records of the listed points, rows laid out like d_out
+    DevBuf<uint32_t> d_bins{bufs, kPerBatch};  // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
+    DevBuf<uint32_t> d_parts{bufs, kPerBatch};  // TWO copies of 3 slabs of frames*(2B+2): part_count, part_off, part_cursor (pwpp_dev.h: a bin is stored in two
                                // parts); a call works on one copy while its K5 zeroes the other for the next call (PwppBatch.next_part_count)
-    DevBuf<uint32_t> d_cls_start;  // frames * 8
-    DevBuf<uint32_t> d_cap_off;    // 2B + 3 segment starts of the one-pass path (one segment per part)
-    DevBuf<uint32_t> d_bin_max;    // 2B + 2: largest count of every part so far (k_czm_scan)
-    DevBuf<uint8_t> d_emit_long;   // k_emit's table of long bins: B + 2 flags, then (4-byte aligned) the list of those bins as uint16
+    DevBuf<uint32_t> d_cls_start{bufs, kPerBatch};  // frames * 8
+    DevBuf<uint32_t> d_cap_off{bufs, kPerHandle};  // 2B + 3 segment starts of the one-pass path (one segment per part)
+    DevBuf<uint32_t> d_bin_max{bufs, kPerHandle};  // 2B + 2: largest count of every part so far (k_czm_scan)
+    DevBuf<uint8_t> d_emit_long{bufs, kPerHandle};  // k_emit's table of long bins: B + 2 flags, then (4-byte aligned) the list of those bins as uint16
     std::vector<uint8_t> emit_long_flags;
     int emit_long_n = 0, emit_long_parts = 1;
     std::vector<uint32_t> observed, cap_table, cap_seen;  // host copies: d_bin_max as last read; capacities of the table on the device and the counts it was built from
     bool have_observation = false, table_stale = true;
-    DevBuf<PwppFrameDesc> d_frames_probe;
-    PinnedBuf<uint32_t> h_bin_max;
-    DevBuf<uint16_t> d_cls_list;   // frames * B
-    DevBuf<PwppPatchRec> d_recs;
-    DevBuf<float> d_centers, d_normals;
-    DevBuf<PwppFrameResult> d_results;  // two copies (see d_parts)
+    DevBuf<PwppFrameDesc> d_frames_probe{bufs, kPerBatch};
+    PinnedBuf<uint32_t> h_bin_max{bufs, kPerHandle};
+    DevBuf<uint16_t> d_cls_list{bufs, kPerBatch};  // frames * B
+    DevBuf<PwppPatchRec> d_recs{bufs, kPerBatch};
+    DevBuf<float> d_centers{bufs, kPerBatch}, d_normals{bufs, kPerBatch};
+    DevBuf<PwppFrameResult> d_results{bufs, kPerBatch};  // two copies (see d_parts)
     int counters_copy = 0;           // which copy of d_parts / d_results the call in flight (or the last one) works on
-    bool next_clean = false;         // the OTHER copy was zeroed by the last call's K5 ...
-    int next_clean_frames = 0, next_clean_slabs = 0;   // ... for a call of this many frames and slabs (1: one-pass, 3: two-pass)
-    const void *next_clean_parts = nullptr, *next_clean_results = nullptr;  // ... in these allocations
-    size_t next_clean_parts_cap = 0, next_clean_results_cap = 0;
-    PinnedBuf<PwppFrameResult> h_results;
-    DevBuf<float> d_xyz;  // gather scratch
-    DevBuf<unsigned long long> d_dbg;  // timing probes (PWPP_DEBUG_FLAGS & 4)
+    CleanCopy next_clean;            // the OTHER copy, if the last call's K5 zeroed it
+    PinnedBuf<PwppFrameResult> h_results{bufs, kPerHandle};
+    DevBuf<float> d_xyz{bufs, kPerBatch};  // gather scratch
+    DevBuf<unsigned long long> d_dbg{bufs, kPerHandle};  // timing probes (PWPP_DEBUG_FLAGS & 4)
 
     // adaptive state: streams (long history slabs) and per-frame fresh outputs (short slabs)
     int num_streams = 0;
     int stream_hist_cap = 0, fresh_hist_cap = 0;
     int max_pushes_per_frame = 0;  // bins of the widest ring of interest: what one frame can add to a history
-    DevBuf<PwppStateScalar> d_st_stream, d_st_fresh;
-    DevBuf<double> d_hist_stream, d_hist_fresh;
-    DevBuf<PwppPlaneState> d_pl_stream, d_pl_fresh, d_pl_snap;  // the reference object's plane members after a frame (pwpp_dev.h)
+    DevBuf<PwppStateScalar> d_st_stream{bufs, kPerHandle}, d_st_fresh{bufs, kPerBatch};
+    DevBuf<double> d_hist_stream{bufs, kPerHandle}, d_hist_fresh{bufs, kPerBatch};
+    DevBuf<PwppPlaneState> d_pl_stream{bufs, kPerHandle}, d_pl_fresh{bufs, kPerBatch}, d_pl_snap{bufs, kPerBatch};  // the reference object's plane members after a frame (pwpp_dev.h)
     // one-pass batches of stateful streams: the state of the streams before the batch, so that a redo after an
     // overflow starts from it (the first attempt has already advanced sensor height, thresholds, histories)
-    DevBuf<PwppStateScalar> d_st_snap;
-    DevBuf<double> d_hist_snap;
+    DevBuf<PwppStateScalar> d_st_snap{bufs, kPerBatch};
+    DevBuf<double> d_hist_snap{bufs, kPerBatch};
 };
 
 namespace {
@@ -411,13 +449,14 @@ void sync_all_streams(pwpp_handle *h) {
 int grow_stream_histories(pwpp_handle *h, int new_cap) {
     new_cap = (new_cap + 1) & ~1;  // (even: k_gle_tgr fetches two entries per load)
     const size_t rows = (size_t)h->num_streams * 8;
-    DevBuf<double> bigger;
+    std::vector<BufBase *> own;  // (a buffer of this function's, not yet the handle's)
+    DevBuf<double> bigger{own, kPerHandle};
     int rc = bigger.ensure(rows * (size_t)new_cap);
     if (rc) return rc;
     HIPCHK(hipMemcpy2D(bigger.p, (size_t)new_cap * sizeof(double), h->d_hist_stream.p, (size_t)h->stream_hist_cap * sizeof(double),
                        (size_t)h->stream_hist_cap * sizeof(double), rows, hipMemcpyDeviceToDevice));
-    h->d_hist_stream.release();
-    h->d_hist_stream = bigger;
+    bigger.swap(h->d_hist_stream);
+    bigger.release();
     h->stream_hist_cap = new_cap;
     return PWPP_OK;
 }
@@ -484,7 +523,10 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt);
 // on a 16-byte boundary too (3 x frames x parts + 4 is 8 mod 16 bytes for a single frame of the default CZM).
 inline size_t counters_copy_words(size_t slab_words) { return (3 * slab_words + 4 + 3) & ~(size_t)3; }
 
-bool labels_on(const pwpp_handle *h) { return h->labels || h->output_order == PWPP_ORDER_CLOUD; }
+constexpr unsigned bit(Output o) { return 1u << o; }
+// what the next call writes: the settings, and the labels that PWPP_ORDER_CLOUD implies
+unsigned outputs_on(const pwpp_handle *h) { return h->outputs | (h->output_order == PWPP_ORDER_CLOUD ? bit(kLabels) : 0u); }
+bool labels_on(const pwpp_handle *h) { return outputs_on(h) & bit(kLabels); }
 int64_t label_tile_stride(int max_n) { return ((int64_t)max_n + 15 + PWPP_LABEL_TILE - 1) / PWPP_LABEL_TILE; }
 
 int read_observed(pwpp_handle *h) {
@@ -519,7 +561,7 @@ int probe_histogram(pwpp_handle *h) {
     bt.num_frames = S;
     bt.max_n = max_n;
     bt.cap_off = nullptr;
-    h->next_clean = false;  // (the probe's own K0-K2 run on sample frames with their own frame count)
+    h->next_clean.valid = false;  // (the probe's own K0-K2 run on sample frames with their own frame count)
     bt.next_part_count = nullptr;
     const int lrc = pwpp_launch_histogram(&bt, h->stream);
     if (lrc != 0) return fail(PWPP_E_HIP, "histogram probe failed: %s", hipGetErrorString((hipError_t)lrc));
@@ -612,21 +654,22 @@ void fill_batch(pwpp_handle *h, PwppBatch &bt) {
     bt.results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
     bt.results_host = h->h_results.p;  // hipHostMalloc'ed: the same address on the device
     bt.dbg = h->d_dbg.p;
-    if (labels_on(h) || h->point_planes) {
+    const unsigned outputs = outputs_on(h);
+    if (outputs & (bit(kLabels) | bit(kPointPlanes))) {
         bt.point_first = 0;
         bt.point_count = h->h_base.p[h->frames];
     }
-    if (h->point_planes) {
+    if (outputs & bit(kPointPlanes)) {
         bt.pt_patch = h->d_pt_patch.p;
         bt.pt_dist = h->d_pt_dist.p;
         bt.pt_rows = h->d_pt_rows.p;
     }
-    if (h->point_records) {
+    if (outputs & bit(kPointRecords)) {
         bt.records = h->d_records.p;
         bt.record_bytes = h->record_bytes;
         bt.records_path = h->records_path;
     }
-    if (labels_on(h)) {
+    if (outputs & bit(kLabels)) {
         bt.labels = h->d_labels.p;
         if (h->output_order == PWPP_ORDER_CLOUD) {
             bt.label_tiles = h->d_label_tiles.p;
@@ -700,6 +743,44 @@ PwppBatch frame_range(const pwpp_handle *h, const PwppBatch &bt, int f0, int nf)
     return v;
 }
 
+void CleanCopy::capture(const pwpp_handle *h, int frames_, int slabs_) {
+    valid = true;
+    frames = frames_;
+    slabs = slabs_;
+    parts = h->d_parts.p;
+    results = h->d_results.p;
+    parts_cap = h->d_parts.cap;
+    results_cap = h->d_results.cap;
+}
+bool CleanCopy::matches(const pwpp_handle *h, int frames_, int slabs_) const {
+    return valid && frames == frames_ && slabs >= slabs_ && parts == h->d_parts.p && results == h->d_results.p &&
+           parts_cap == h->d_parts.cap && results_cap == h->d_results.cap;
+}
+
+// the overflow arena of the current capacity table (one-pass layout), for a view that starts at frame f0
+void set_arena(const pwpp_handle *h, PwppBatch &v, int f0) {
+    v.arena_base = h->arena_base;
+    v.arena_slots = h->arena_slots;
+    v.arena_spill = h->arena_spill;
+    v.arena_tag = h->arena_slots ? h->d_arena_tag.p + (size_t)f0 * h->arena_spill : nullptr;
+}
+
+// nothing of a half-launched schedule may still be running when the caller sees the error
+int launch_failed(pwpp_handle *h, int lrc) {
+    sync_all_streams(h);
+    return fail(PWPP_E_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+}
+
+// the stages of one pipeline on the main stream.  whole_call: a call's own launch, with the profiling events and the second
+// stream of the latency plan; a redo or a fix-up runs without them.
+int launch_pipeline(pwpp_handle *h, const PwppBatch &v, int stages, bool whole_call = false) {
+    const bool ordered = h->output_order == PWPP_ORDER_REFERENCE;
+    const int lrc = pwpp_launch_pipeline(&v, h->stream, whole_call && h->profiling ? h->ev_k : nullptr, whole_call ? h->aux_stream : nullptr,
+                                         whole_call ? h->aux_fork : nullptr, whole_call ? h->aux_join : nullptr,
+                                         ordered ? h->d_ord_a.p : nullptr, ordered ? h->d_ord_b.p : nullptr, stages);
+    return lrc != 0 ? launch_failed(h, lrc) : PWPP_OK;
+}
+
 // Launches the pipeline over the batch described by h->descs (buffers sized, inputs on the device).
 // one_pass: fixed bin segments (k_czm_bin_scatter); otherwise the exact two-pass binning.
 int launch_prepared(pwpp_handle *h, bool one_pass) {
@@ -733,10 +814,8 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
     // clearing kernel runs in front of the binning
     h->counters_copy ^= 1;
     const int slabs = one_pass ? 1 : 3;
-    const bool pre_cleared = h->next_clean && h->next_clean_frames == frames && h->next_clean_slabs >= slabs &&
-                             h->next_clean_parts == h->d_parts.p && h->next_clean_results == h->d_results.p &&
-                             h->next_clean_parts_cap == h->d_parts.cap && h->next_clean_results_cap == h->d_results.cap;
-    h->next_clean = false;  // (set again below, once this call's K5 is on its way for every frame)
+    const bool pre_cleared = h->next_clean.matches(h, frames, slabs);
+    h->next_clean.valid = false;  // (set again below, once this call's K5 is on its way for every frame)
     PwppBatch bt;
     fill_batch(h, bt);
     bt.next_slabs = slabs;
@@ -748,12 +827,7 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
                           h->output_order != PWPP_ORDER_REFERENCE && h->dp.min_pts != 0;
     bt.k5_split = split_k5 ? h->split_k5 : 0;
     bt.cap_off = one_pass ? h->d_cap_off.p : nullptr;
-    if (one_pass) {
-        bt.arena_base = h->arena_base;
-        bt.arena_slots = h->arena_slots;
-        bt.arena_spill = h->arena_spill;
-        bt.arena_tag = h->arena_slots ? h->d_arena_tag.p : nullptr;
-    }
+    if (one_pass) set_arena(h, bt, 0);
     if (one_pass && h->mode == PWPP_MODE_STREAMS) {  // what a redo after a segment overflow starts from: copied by the binning kernel
         bt.snap_scalar = h->d_st_snap.p;
         bt.snap_hist = h->d_hist_snap.p;
@@ -781,13 +855,12 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
         HIPCHK(hipMemsetAsync(bt.dbg, 0, 64 * sizeof(unsigned long long), h->stream));
         HIPCHK(hipMemsetAsync(bt.dbg + 60, 0xFF, sizeof(unsigned long long), h->stream));  // slot 60 is a minimum
     }
-    const bool ordered = h->output_order == PWPP_ORDER_REFERENCE;
-    int lrc;
     // Overlap mode: the pipeline alternates memory-bound stages (binning, emit) and VALU-bound ones (the
     // fits).  Two halves of the batch, each with its own launches on its own stream, put one kind under the
     // other (tools/two_handles.py: +7.5 % on 1024 KITTI frames).  Every per-frame array is indexed by the
     // frame, so the halves are two views of the same workspaces with shifted base pointers.
-    if (h->overlap && !h->profiling && !ordered && frames >= 128 && bt.debug == 0) {
+    const bool overlapped = h->overlap && !h->profiling && h->output_order != PWPP_ORDER_REFERENCE && frames >= 128 && bt.debug == 0;
+    if (overlapped) {
         auto range = [&](int f0, int nf) { return frame_range(h, bt, f0, nf); };
         // R frame ranges of whole groups of eight frames (K1' deals frames to the 8 XCDs).  Every range is launched
         // with the fit plan of the WHOLE batch (the machine is shared, not split).
@@ -801,7 +874,7 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
             int f1 = r == R ? frames : (int)(((int64_t)frames * r / R + 7) / 8 * 8);
             first[(size_t)r] = f1 > frames ? frames : f1;
         }
-        lrc = pre_cleared ? 0 : pwpp_launch_clear(&bt, h->stream);
+        int lrc = pre_cleared ? 0 : pwpp_launch_clear(&bt, h->stream);
         // A software pipeline over the two streams: the MEMORY stream bins range r + 2 and then writes the lists of
         // range r, the FIT stream runs the plane fits (and K5) of range r + 1 meanwhile -- the streams never run the
         // same kind of stage at the same time (two whole-range pipelines side by side start in lock step: both
@@ -849,33 +922,20 @@ int launch_prepared(pwpp_handle *h, bool one_pass) {
             if (r + 2 < R) bin(r + 2);
         }
         // (the memory stream ends with the lists of the last range, which wait for its fits: h->stream is the join)
-    } else {
-        lrc = pwpp_launch_pipeline(&bt, h->stream, h->profiling ? h->ev_k : nullptr, h->aux_stream, h->aux_fork, h->aux_join,
-                                   ordered ? h->d_ord_a.p : nullptr, ordered ? h->d_ord_b.p : nullptr, 7);
-    }
-    if (lrc != 0) {  // nothing of a half-launched schedule may still be running when the caller sees the error
-        sync_all_streams(h);
-        return fail(PWPP_E_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+        if (lrc != 0) return launch_failed(h, lrc);
+    } else if (const int rc = launch_pipeline(h, bt, 7, true)) {
+        return rc;
     }
     HIPCHK(hipEventRecord(h->ev_end, h->stream));
-    if (bt.k5_split && !(h->overlap && !h->profiling && !ordered && frames >= 128 && bt.debug == 0)) {
+    if (bt.k5_split && !overlapped) {
         if (bt.k5_split == 2) {  // the second part behind the lists
             HIPCHK(hipEventRecord(h->aux_fork, h->stream));
             const int trc = pwpp_launch_k5_tail(&bt, h->aux_stream, h->aux_fork, h->aux_join);
-            if (trc != 0) {
-                sync_all_streams(h);
-                return fail(PWPP_E_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)trc));
-            }
+            if (trc != 0) return launch_failed(h, trc);
         }
         h->k5_tail_unjoined = h->k5_tail_unsynced = true;
     }
-    h->next_clean = true;  // every frame's K5 is enqueued: the other copy will be zero for a call of this shape
-    h->next_clean_frames = frames;
-    h->next_clean_slabs = slabs;
-    h->next_clean_parts = h->d_parts.p;
-    h->next_clean_results = h->d_results.p;
-    h->next_clean_parts_cap = h->d_parts.cap;
-    h->next_clean_results_cap = h->d_results.cap;
+    h->next_clean.capture(h, frames, slabs);  // every frame's K5 is enqueued: the other copy will be zero for a call of this shape
     if (one_pass)  // the bins' largest counts, for the segment sizes of the next batches (finish_pending)
         HIPCHK(hipMemcpyAsync(h->h_bin_max.p, h->d_bin_max.p, (size_t)NP * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     h->profile_pending = h->profiling;
@@ -996,7 +1056,6 @@ int finish_pending(pwpp_handle *h, bool lists_only) {
             fill_batch(h, bt);
             bt.cap_off = nullptr;  // compact layout, exact two-pass binning (K1, K2, K3)
             bt.next_slabs = 1;     // (the other copy of the counters was zeroed for a one-pass call by the first attempt's K5 already)
-            const bool ordered = h->output_order == PWPP_ORDER_REFERENCE;
             for (size_t i = 0; i < redo.size();) {  // runs of neighbouring frames go through the pipeline together
                 size_t j = i + 1;
                 while (j < redo.size() && redo[j] == redo[j - 1] + 1) ++j;
@@ -1013,9 +1072,7 @@ int finish_pending(pwpp_handle *h, bool lists_only) {
                 HIPCHK(hipMemsetAsync(v.part_off, 0, words, h->stream));
                 HIPCHK(hipMemsetAsync(v.part_cursor, 0, words, h->stream));
                 HIPCHK(hipMemsetAsync(v.results, 0, (size_t)nf * sizeof(PwppFrameResult), h->stream));
-                const int lrc = pwpp_launch_pipeline(&v, h->stream, nullptr, nullptr, nullptr, nullptr, ordered ? h->d_ord_a.p : nullptr,
-                                                     ordered ? h->d_ord_b.p : nullptr, 7);
-                if (lrc != 0) return fail(PWPP_E_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+                if (const int rc = launch_pipeline(h, v, 7)) return rc;
                 i = j;
             }
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -1032,20 +1089,12 @@ int finish_pending(pwpp_handle *h, bool lists_only) {
             PwppBatch bt;
             fill_batch(h, bt);
             bt.fixup_run = 1;
-            const bool ordered = h->output_order == PWPP_ORDER_REFERENCE;
             for (int f = 0; f < h->frames; ++f) {
                 if (!(h->h_results.p[f].overflow & 2)) continue;
                 PwppBatch v = frame_range(h, bt, f, 1);
                 v.cap_off = was_one_pass && !h->frame_two_pass[(size_t)f] ? h->d_cap_off.p : nullptr;  // (a frame redone in place is in the compact layout)
-                if (v.cap_off) {  // (where its moved parts' bits live: pwpp_member_offset)
-                    v.arena_base = h->arena_base;
-                    v.arena_slots = h->arena_slots;
-                    v.arena_spill = h->arena_spill;
-                    v.arena_tag = h->arena_slots ? h->d_arena_tag.p + (size_t)f * h->arena_spill : nullptr;
-                }
-                const int lrc = pwpp_launch_pipeline(&v, h->stream, nullptr, nullptr, nullptr, nullptr, ordered ? h->d_ord_a.p : nullptr,
-                                                     ordered ? h->d_ord_b.p : nullptr, 2 | 4 | 8);
-                if (lrc != 0) return fail(PWPP_E_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+                if (v.cap_off) set_arena(h, v, f);  // (where its moved parts' bits live: pwpp_member_offset)
+                if (const int rc = launch_pipeline(h, v, 2 | 4 | 8)) return rc;
                 ++h->fixed_up_frames;
             }
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -1070,14 +1119,47 @@ int finish_pending(pwpp_handle *h, bool lists_only) {
     return defer_tail ? PWPP_OK : settle_k5_tail(h);
 }
 
-int check_frame(pwpp_handle *h, int frame) {
+// What every entry point that works on a handle starts with: the handle, its device, and the call in flight landed
+// (lists_only: see finish_pending).
+int enter(pwpp_handle *h, bool lists_only = false) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
-    if (rc) return rc;
-    rc = finish_pending(h, true);  // (a call's results: counts, lists, patch rows)
+    const int rc = use_device(h);
+    return rc ? rc : finish_pending(h, lists_only);
+}
+
+int check_frame(pwpp_handle *h, int frame) {
+    const int rc = enter(h, true);  // (a call's results: counts, lists, patch rows)
     if (rc) return rc;
     if (!h->have_results) return fail(PWPP_E_STATE, "no frame has been processed yet");
     if (frame < 0 || frame >= h->frames) return fail(PWPP_E_ARG, "frame %d out of range [0,%d)", frame, h->frames);
+    return PWPP_OK;
+}
+
+// a frame of the last call's results, and the per-point output `which` among them
+int need_output(pwpp_handle *h, int frame, Output which) {
+    const int rc = check_frame(h, frame);
+    if (rc) return rc;
+    if (!(h->outputs_last & bit(which))) return fail(PWPP_E_STATE, "%s", kOutputMissing[which]);
+    return PWPP_OK;
+}
+
+// One frame's span of a per-point array of the output `which` (`elem` bytes per point, laid out like d_out), or the whole batch.
+int copy_output(pwpp_handle *h, Output which, int frame, bool whole_batch, void *out, const void *src_all, size_t elem) {
+    const int rc = need_output(h, frame, which);
+    if (rc) return rc;
+    const int64_t first = whole_batch ? 0 : h->h_base.p[frame], end = h->h_base.p[whole_batch ? h->frames : frame + 1];
+    if (end > first) {
+        if (!out) return fail(PWPP_E_ARG, "null output");
+        HIPCHK(hipMemcpyAsync(out, static_cast<const char *>(src_all) + (size_t)first * elem, (size_t)(end - first) * elem, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return PWPP_OK;
+}
+
+int set_output(pwpp_handle *h, Output which, int on) {
+    const int rc = enter(h);
+    if (rc) return rc;
+    h->outputs = on ? h->outputs | bit(which) : h->outputs & ~bit(which);
     return PWPP_OK;
 }
 
@@ -1135,9 +1217,7 @@ int pwpp_params_default(pwpp_params *p) {  // reference patchworkpp.h:79-111
 int pwpp_set_num_streams(pwpp_handle *h, int streams) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (streams < 1) return fail(PWPP_E_ARG, "streams must be >= 1");
-    int rc = use_device(h);
-    if (rc) return rc;
-    rc = finish_pending(h);
+    int rc = enter(h);
     if (rc) return rc;
     if ((rc = h->d_st_stream.ensure((size_t)streams))) return rc;
     if ((rc = h->d_hist_stream.ensure((size_t)streams * 8 * (size_t)h->stream_hist_cap))) return rc;
@@ -1250,48 +1330,7 @@ int pwpp_destroy(pwpp_handle *h) {
     if (!h) return PWPP_OK;
     (void)hipSetDevice(h->device);
     sync_all_streams(h);
-    h->d_frames.release();
-    h->h_frames.release();
-    h->h_base.release();
-    h->d_in.release();
-    h->d_codes.release();
-    h->d_sorted_z.release();
-    h->d_sorted_xy.release();
-    h->d_sorted_idx.release();
-    h->d_bin_origin.release();
-    h->d_bin_bbox.release();
-    h->d_parts.release();
-    h->d_bin_max.release();
-    h->h_bin_max.release();
-    h->d_frames_probe.release();
-    h->d_member.release();
-    h->d_arena_tag.release();
-    h->d_out.release();
-    h->d_ord_a.release();
-    h->d_ord_b.release();
-    h->d_ord_work.release();
-    h->d_bins.release();
-    h->d_recs.release();
-    h->d_cls_start.release();
-    h->d_cap_off.release();
-    h->d_emit_long.release();
-    h->d_cls_list.release();
-    h->d_centers.release();
-    h->d_normals.release();
-    h->d_results.release();
-    h->h_results.release();
-    h->d_xyz.release();
-    h->d_records.release();
-    h->d_dbg.release();
-    h->d_st_stream.release();
-    h->d_st_fresh.release();
-    h->d_hist_stream.release();
-    h->d_hist_fresh.release();
-    h->d_st_snap.release();
-    h->d_hist_snap.release();
-    h->d_pl_stream.release();
-    h->d_pl_fresh.release();
-    h->d_pl_snap.release();
+    for (BufBase *b : h->bufs) b->release();
     if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
     if (h->ev_end) (void)hipEventDestroy(h->ev_end);
     for (int k = 0; k <= PWPP_NUM_KERNELS; ++k)
@@ -1365,9 +1404,8 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
     if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE && mem != PWPP_MEM_HOST_PINNED) return fail(PWPP_E_ARG, "bad mem %d", mem);
     const bool from_host = mem != PWPP_MEM_DEVICE;
     if (mode != PWPP_MODE_FRESH && mode != PWPP_MODE_STREAMS) return fail(PWPP_E_ARG, "bad mode %d", mode);
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (mode == PWPP_MODE_STREAMS && frames > h->num_streams)
         return fail(PWPP_E_ARG, "%d frames but only %d streams (pwpp_set_num_streams)", frames, h->num_streams);
 
@@ -1402,16 +1440,14 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
         if ((rc = h->d_labels.ensure(tp + 16))) return rc;
         if (h->output_order == PWPP_ORDER_CLOUD && (rc = h->d_label_tiles.ensure((size_t)frames * (size_t)label_tile_stride(max_n)))) return rc;
     }
-    h->labels_last = labels_on(h);
-    if (h->point_planes) {
+    if (h->outputs & bit(kPointPlanes)) {
         if ((rc = h->d_pt_patch.ensure(tp))) return rc;
         if ((rc = h->d_pt_dist.ensure(tp))) return rc;
         if ((rc = h->d_pt_rows.ensure((size_t)frames * B))) return rc;
     }
-    h->point_planes_last = h->point_planes;
     h->record_bytes = fs ? fs->step : 4 * cols;
-    if (h->point_records && (rc = h->d_records.ensure(tp * (size_t)h->record_bytes + 64))) return rc;  // (64 bytes of slack behind the last row)
-    h->point_records_last = h->point_records;
+    if ((h->outputs & bit(kPointRecords)) && (rc = h->d_records.ensure(tp * (size_t)h->record_bytes + 64))) return rc;  // (64 bytes of slack behind the last row)
+    h->outputs_last = outputs_on(h);
     if ((rc = h->d_bins.ensure((size_t)frames * NB * 4))) return rc;
     if ((rc = h->d_parts.ensure(2 * counters_copy_words((size_t)frames * NP)))) return rc;  // two copies
     if ((rc = h->d_recs.ensure((size_t)frames * B))) return rc;
@@ -1568,10 +1604,7 @@ int pwpp_estimate_ground(pwpp_handle *h, const float *points, int n, int cols, i
 }
 
 int pwpp_synchronize(pwpp_handle *h) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
-    if (rc) return rc;
-    return finish_pending(h, true);  // (the call's results; a stream's state is settled by whoever touches it: settle_k5_tail)
+    return enter(h, true);  // (the call's results; a stream's state is settled by whoever touches it: settle_k5_tail)
 }
 
 int pwpp_get_counts(pwpp_handle *h, int frame, int32_t *n_ground, int32_t *n_nonground, int32_t *n_patches) {
@@ -1682,9 +1715,8 @@ double pwpp_get_time_us(pwpp_handle *h) {
 
 int pwpp_get_state(pwpp_handle *h, int index, pwpp_state *out) {
     if (!h || !out) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     const bool fresh = h->have_results && h->mode == PWPP_MODE_FRESH;
     const int limit = fresh ? h->frames : h->num_streams;
     if (index < 0 || index >= limit) return fail(PWPP_E_ARG, "state index %d out of range [0,%d)", index, limit);
@@ -1712,9 +1744,8 @@ int pwpp_get_history(pwpp_handle *h, int index, int which, int ring, double *out
 
 int pwpp_set_state(pwpp_handle *h, int stream, const pwpp_state *in) {
     if (!h || !in) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (stream < 0 || stream >= h->num_streams) return fail(PWPP_E_ARG, "stream %d out of range", stream);
     PwppStateScalar s;
     std::memcpy(&s, in, sizeof(s));
@@ -1774,9 +1805,8 @@ int64_t pwpp_get_fixed_up_frames(pwpp_handle *h) {
 
 int pwpp_get_plane_state(pwpp_handle *h, int index, float out[10]) {
     if (!h || !out) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     const bool fresh = h->have_results && h->mode == PWPP_MODE_FRESH;
     const int limit = fresh ? h->frames : h->num_streams;
     if (index < 0 || index >= limit) return fail(PWPP_E_ARG, "state index %d out of range [0,%d)", index, limit);
@@ -1793,9 +1823,8 @@ int pwpp_get_plane_state(pwpp_handle *h, int index, float out[10]) {
 
 int pwpp_set_plane_state(pwpp_handle *h, int stream, const float in[10]) {
     if (!h || !in) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (stream < 0 || stream >= h->num_streams) return fail(PWPP_E_ARG, "stream %d out of range", stream);
     PwppPlaneState ps;
     for (int i = 0; i < 3; ++i) {
@@ -1811,9 +1840,8 @@ int pwpp_set_plane_state(pwpp_handle *h, int stream, const float in[10]) {
 
 int pwpp_set_history(pwpp_handle *h, int stream, int which, int ring, const double *values, int count) {
     if (!h || (count > 0 && !values)) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (stream < 0 || stream >= h->num_streams) return fail(PWPP_E_ARG, "stream %d out of range", stream);
     if (which < 0 || which > 1 || ring < 0 || ring > 3) return fail(PWPP_E_ARG, "bad history selector");
     if (count < 0 || count > (1 << 24)) return fail(PWPP_E_ARG, "count %d out of range", count);
@@ -1835,9 +1863,8 @@ int pwpp_set_history(pwpp_handle *h, int stream, int which, int ring, const doub
 
 int pwpp_get_device_view(pwpp_handle *h, pwpp_device_view *out) {
     if (!h || !out) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (!h->have_results) return fail(PWPP_E_STATE, "no frame has been processed yet");
     out->indices = h->d_out.p;
     out->frame_base = h->h_base.p;
@@ -1874,18 +1901,14 @@ int pwpp_get_all_indices(pwpp_handle *h, int32_t *out, int64_t *frame_base, int3
 }
 
 int pwpp_set_profiling(pwpp_handle *h, int enable) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     h->profiling = enable != 0;
     return PWPP_OK;
 }
 int pwpp_get_kernel_profile(pwpp_handle *h, double *sum_ms, int64_t *launches) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     for (int k = 0; k < PWPP_NUM_KERNELS; ++k) {
         if (sum_ms) sum_ms[k] = h->prof_ms[k];
         if (launches) launches[k] = h->prof_launches[k];
@@ -1915,9 +1938,8 @@ int pwpp_get_fxp_origins(pwpp_handle *h, float *out_xy, int capacity_bins) {
 
 int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
     if (!h || !name || !value) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     const std::string k = name;
     if (k == "fit_plan") {
         for (const char *c = value; *c; ++c)
@@ -1990,63 +2012,22 @@ int64_t pwpp_get_workspace_bytes(pwpp_handle *h) {
     if (!h) return PWPP_E_ARG;
     // EVERY device allocation of the handle (the sum used to leave out the descriptors, the stream state and
     // the tables, and reported the per-frame buffers pwpp_trim_workspace did not free)
-    auto b = [](size_t cap, size_t elt) { return (int64_t)(cap * elt); };
-    return b(h->d_frames.cap, sizeof(PwppFrameDesc)) + b(h->d_frames_probe.cap, sizeof(PwppFrameDesc)) + b(h->d_in.cap, 4) + b(h->d_codes.cap, 2) +
-           b(h->d_sorted_z.cap, 4) + b(h->d_sorted_xy.cap, 8) + b(h->d_sorted_idx.cap, 4) + b(h->d_bin_origin.cap, 8) + b(h->d_bin_bbox.cap, 16) +
-           b(h->d_member.cap, 1) + b(h->d_arena_tag.cap, 8) + b(h->d_out.cap, 4) + b(h->d_ord_a.cap, 8) + b(h->d_ord_b.cap, 8) + b(h->d_ord_work.cap, 4) + b(h->d_bins.cap, 4) + b(h->d_parts.cap, 4) +
-           b(h->d_cls_start.cap, 4) + b(h->d_cap_off.cap, 4) + b(h->d_emit_long.cap, 1) + b(h->d_bin_max.cap, 4) + b(h->d_cls_list.cap, 2) +
-           b(h->d_recs.cap, sizeof(PwppPatchRec)) + b(h->d_centers.cap, 4) + b(h->d_normals.cap, 4) + b(h->d_results.cap, sizeof(PwppFrameResult)) +
-           b(h->d_xyz.cap, 4) + b(h->d_dbg.cap, 8) + b(h->d_st_stream.cap, sizeof(PwppStateScalar)) + b(h->d_st_fresh.cap, sizeof(PwppStateScalar)) +
-           b(h->d_st_snap.cap, sizeof(PwppStateScalar)) + b(h->d_hist_stream.cap, 8) + b(h->d_hist_fresh.cap, 8) + b(h->d_hist_snap.cap, 8) +
-           b(h->d_pl_stream.cap, sizeof(PwppPlaneState)) + b(h->d_pl_fresh.cap, sizeof(PwppPlaneState)) + b(h->d_pl_snap.cap, sizeof(PwppPlaneState)) +
-           b(h->d_labels.cap, 1) + b(h->d_label_tiles.cap, 4) + b(h->d_pt_patch.cap, 4) + b(h->d_pt_dist.cap, 4) + b(h->d_pt_rows.cap, 4) +
-           b(h->d_records.cap, 1);
+    int64_t sum = 0;
+    for (const BufBase *b : h->bufs)
+        if (b->on_device) sum += (int64_t)b->bytes();
+    return sum;
 }
 
 int pwpp_trim_workspace(pwpp_handle *h) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     // everything whose size follows the batch: inputs, bin-ordered planes, lists, per-frame tables and records, the state of
     // FRESH frames and the snapshots of a one-pass batch.  What stays: the streams' state (thresholds, histories, plane
     // members), the per-handle tables (origins, boxes, segment table, largest counts) and 512 bytes of timing probes.
-    h->d_in.release();
-    h->d_codes.release();
-    h->d_sorted_z.release();
-    h->d_sorted_xy.release();
-    h->d_sorted_idx.release();
-    h->d_member.release();
-    h->d_arena_tag.release();
-    h->d_out.release();
-    h->d_ord_a.release();
-    h->d_ord_b.release();
-    h->d_ord_work.release();
-    h->d_labels.release();
-    h->d_label_tiles.release();
-    h->d_pt_patch.release();
-    h->d_pt_dist.release();
-    h->d_pt_rows.release();
-    h->d_records.release();
-    h->d_xyz.release();
-    h->d_frames.release();
-    h->d_frames_probe.release();
-    h->d_bins.release();
-    h->d_parts.release();
-    h->d_recs.release();
-    h->d_cls_start.release();
-    h->d_cls_list.release();
-    h->d_centers.release();
-    h->d_normals.release();
-    h->d_results.release();
-    h->d_st_fresh.release();
-    h->d_hist_fresh.release();
-    h->d_pl_fresh.release();
-    h->d_st_snap.release();
-    h->d_hist_snap.release();
-    h->d_pl_snap.release();
+    for (BufBase *b : h->bufs)
+        if (b->per_batch) b->release();
     h->have_results = false;  // the index lists lived in d_out, the records in d_recs
-    h->next_clean = false;    // (the counters' copies are gone with d_parts / d_results)
+    h->next_clean.valid = false;  // (the counters' copies are gone with d_parts / d_results)
     h->descs_on_device.clear();
     return PWPP_OK;
 }
@@ -2054,115 +2035,49 @@ int pwpp_trim_workspace(pwpp_handle *h) {
 int pwpp_set_output_order(pwpp_handle *h, int order) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (order != PWPP_ORDER_SCATTER && order != PWPP_ORDER_REFERENCE && order != PWPP_ORDER_CLOUD) return fail(PWPP_E_ARG, "bad order %d", order);
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     h->output_order = order;
     return PWPP_OK;
 }
 
-int pwpp_set_labels(pwpp_handle *h, int on) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
-    if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
-    h->labels = on != 0;
-    return PWPP_OK;
-}
-
-// the labels of the last call: its results, and labels among them
-static int check_labels(pwpp_handle *h) {
-    if (!h->labels_last) return fail(PWPP_E_STATE, "the last call ran without labels (pwpp_set_labels, PWPP_ORDER_CLOUD)");
-    return PWPP_OK;
-}
+int pwpp_set_labels(pwpp_handle *h, int on) { return set_output(h, kLabels, on); }
+int pwpp_set_point_planes(pwpp_handle *h, int on) { return set_output(h, kPointPlanes, on); }
+int pwpp_set_point_records(pwpp_handle *h, int on) { return set_output(h, kPointRecords, on); }
 
 int pwpp_get_labels(pwpp_handle *h, int frame, uint8_t *out) {
-    int rc = check_frame(h, frame);
-    if (rc || (rc = check_labels(h))) return rc;
-    const int64_t base = h->h_base.p[frame], n = h->h_base.p[frame + 1] - base;
-    if (n > 0) {
-        if (!out) return fail(PWPP_E_ARG, "null output");
-        HIPCHK(hipMemcpy(out, h->d_labels.p + base, (size_t)n, hipMemcpyDeviceToHost));
-    }
-    return PWPP_OK;
+    return copy_output(h, kLabels, frame, false, out, h ? h->d_labels.p : nullptr, 1);
 }
-
 int pwpp_get_all_labels(pwpp_handle *h, uint8_t *out) {
-    int rc = check_frame(h, 0);
-    if (rc || (rc = check_labels(h))) return rc;
-    const int64_t total = h->h_base.p[h->frames];
-    if (total > 0) {
-        if (!out) return fail(PWPP_E_ARG, "null output");
-        HIPCHK(hipMemcpyAsync(out, h->d_labels.p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return PWPP_OK;
+    return copy_output(h, kLabels, 0, true, out, h ? h->d_labels.p : nullptr, 1);
+}
+int pwpp_get_point_patches(pwpp_handle *h, int frame, int32_t *out) {
+    return copy_output(h, kPointPlanes, frame, false, out, h ? h->d_pt_patch.p : nullptr, sizeof(int32_t));
+}
+int pwpp_get_point_distances(pwpp_handle *h, int frame, float *out) {
+    return copy_output(h, kPointPlanes, frame, false, out, h ? h->d_pt_dist.p : nullptr, sizeof(float));
+}
+int pwpp_get_all_point_patches(pwpp_handle *h, int32_t *out) {
+    return copy_output(h, kPointPlanes, 0, true, out, h ? h->d_pt_patch.p : nullptr, sizeof(int32_t));
+}
+int pwpp_get_all_point_distances(pwpp_handle *h, float *out) {
+    return copy_output(h, kPointPlanes, 0, true, out, h ? h->d_pt_dist.p : nullptr, sizeof(float));
 }
 
 int pwpp_get_device_labels(pwpp_handle *h, const uint8_t **out) {
     if (!h || !out) return fail(PWPP_E_ARG, "null argument");
-    int rc = check_frame(h, 0);
-    if (rc || (rc = check_labels(h))) return rc;
+    const int rc = need_output(h, 0, kLabels);
+    if (rc) return rc;
     *out = h->d_labels.p;
     return PWPP_OK;
 }
 
-int pwpp_set_point_planes(pwpp_handle *h, int on) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
-    if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
-    h->point_planes = on != 0;
-    return PWPP_OK;
-}
-
-// the point planes of the last call: its results, and point planes among them
-static int check_point_planes(pwpp_handle *h) {
-    if (!h->point_planes_last) return fail(PWPP_E_STATE, "the last call ran without point planes (pwpp_set_point_planes)");
-    return PWPP_OK;
-}
-
-// one frame of one of the two arrays (`elem` bytes per point), or the whole batch in one copy
-static int copy_point_planes(pwpp_handle *h, int frame, bool whole_batch, void *out, const void *src_all, size_t elem) {
-    int rc = check_frame(h, frame);
-    if (rc || (rc = check_point_planes(h))) return rc;
-    const int64_t first = whole_batch ? 0 : h->h_base.p[frame], end = h->h_base.p[whole_batch ? h->frames : frame + 1];
-    if (end > first) {
-        if (!out) return fail(PWPP_E_ARG, "null output");
-        HIPCHK(hipMemcpyAsync(out, static_cast<const char *>(src_all) + (size_t)first * elem, (size_t)(end - first) * elem, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return PWPP_OK;
-}
-
-int pwpp_get_point_patches(pwpp_handle *h, int frame, int32_t *out) {
-    return copy_point_planes(h, frame, false, out, h ? h->d_pt_patch.p : nullptr, sizeof(int32_t));
-}
-int pwpp_get_point_distances(pwpp_handle *h, int frame, float *out) {
-    return copy_point_planes(h, frame, false, out, h ? h->d_pt_dist.p : nullptr, sizeof(float));
-}
-int pwpp_get_all_point_patches(pwpp_handle *h, int32_t *out) {
-    return copy_point_planes(h, 0, true, out, h ? h->d_pt_patch.p : nullptr, sizeof(int32_t));
-}
-int pwpp_get_all_point_distances(pwpp_handle *h, float *out) {
-    return copy_point_planes(h, 0, true, out, h ? h->d_pt_dist.p : nullptr, sizeof(float));
-}
-
 int pwpp_get_device_point_planes(pwpp_handle *h, const int32_t **patches, const float **distances) {
     if (!h || (!patches && !distances)) return fail(PWPP_E_ARG, "null argument");
-    int rc = check_frame(h, 0);
-    if (rc || (rc = check_point_planes(h))) return rc;
+    const int rc = need_output(h, 0, kPointPlanes);
+    if (rc) return rc;
     if (patches) *patches = h->d_pt_patch.p;
     if (distances) *distances = h->d_pt_dist.p;
-    return PWPP_OK;
-}
-
-int pwpp_set_point_records(pwpp_handle *h, int on) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
-    if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
-    h->point_records = on != 0;
     return PWPP_OK;
 }
 
@@ -2170,12 +2085,6 @@ int pwpp_get_record_bytes(pwpp_handle *h) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (h->record_bytes <= 0) return fail(PWPP_E_STATE, "no frame has been processed yet");
     return h->record_bytes;
-}
-
-// the record buffer of the last call: its results, and point records among them
-static int check_point_records(pwpp_handle *h) {
-    if (!h->point_records_last) return fail(PWPP_E_STATE, "the last call ran without point records (pwpp_set_point_records)");
-    return PWPP_OK;
 }
 
 // The rows of one list of one frame.  A call that ran with point records left them in d_records: a copy.  Otherwise they are
@@ -2190,7 +2099,7 @@ static int copy_records(pwpp_handle *h, int frame, void *out, bool ground) {
     if (!out) return fail(PWPP_E_ARG, "null output");
     const size_t rb = (size_t)h->record_bytes, bytes = (size_t)count * rb;
     const uint8_t *src = h->d_records.p + (size_t)first * rb;
-    if (!h->point_records_last) {
+    if (!(h->outputs_last & bit(kPointRecords))) {
         // (d_xyz is the getters' gather scratch: whole floats, and 16-byte aligned for the wide pieces)
         if ((rc = h->d_xyz.ensure((bytes + 3) / 4))) return rc;
         const int lrc = pwpp_launch_gather_records(&h->descs[(size_t)frame], h->d_out.p + first, count, h->d_xyz.p, h->records_path, h->stream);
@@ -2205,14 +2114,8 @@ int pwpp_get_ground_records(pwpp_handle *h, int frame, void *out) { return copy_
 int pwpp_get_nonground_records(pwpp_handle *h, int frame, void *out) { return copy_records(h, frame, out, false); }
 
 int pwpp_get_all_records(pwpp_handle *h, void *out, int64_t *frame_base, int32_t *counts) {
-    int rc = check_frame(h, 0);
-    if (rc || (rc = check_point_records(h))) return rc;
-    const int64_t total = h->h_base.p[h->frames];
-    if (total > 0) {
-        if (!out) return fail(PWPP_E_ARG, "null output");
-        HIPCHK(hipMemcpyAsync(out, h->d_records.p, (size_t)total * (size_t)h->record_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
+    const int rc = copy_output(h, kPointRecords, 0, true, out, h ? h->d_records.p : nullptr, h ? (size_t)h->record_bytes : 0);
+    if (rc) return rc;
     if (frame_base) std::memcpy(frame_base, h->h_base.p, ((size_t)h->frames + 1) * sizeof(int64_t));
     if (counts) std::memcpy(counts, h->h_results.p, (size_t)h->frames * sizeof(PwppFrameResult));
     return PWPP_OK;
@@ -2220,37 +2123,31 @@ int pwpp_get_all_records(pwpp_handle *h, void *out, int64_t *frame_base, int32_t
 
 int pwpp_get_device_records(pwpp_handle *h, const void **out, int32_t *record_bytes) {
     if (!h || (!out && !record_bytes)) return fail(PWPP_E_ARG, "null argument");
-    int rc = check_frame(h, 0);
-    if (rc || (rc = check_point_records(h))) return rc;
+    const int rc = need_output(h, 0, kPointRecords);
+    if (rc) return rc;
     if (out) *out = h->d_records.p;
     if (record_bytes) *record_bytes = h->record_bytes;
     return PWPP_OK;
 }
 
 int pwpp_set_overlap(pwpp_handle *h, int on) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     h->overlap = on != 0;
     return PWPP_OK;
 }
 
 int pwpp_get_one_pass_stats(pwpp_handle *h, int64_t *batches, int64_t *redone) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (batches) *batches = h->one_pass_batches;
     if (redone) *redone = h->one_pass_redone;
     return PWPP_OK;
 }
 
 int pwpp_get_arena_stats(pwpp_handle *h, int64_t *frames_with_moved_parts, int64_t *slots_per_frame, int64_t *arena_slots) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (frames_with_moved_parts) *frames_with_moved_parts = h->arena_frames;
     if (slots_per_frame) *slots_per_frame = h->slots_per_frame;
     if (arena_slots) *arena_slots = h->arena_slots;
@@ -2258,10 +2155,8 @@ int pwpp_get_arena_stats(pwpp_handle *h, int64_t *frames_with_moved_parts, int64
 }
 
 int pwpp_get_redo_stats(pwpp_handle *h, int64_t *frames_one_pass, int64_t *frames_redone) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (frames_one_pass) *frames_one_pass = h->one_pass_frames;
     if (frames_redone) *frames_redone = h->one_pass_redone_frames;
     return PWPP_OK;
@@ -2270,9 +2165,8 @@ int pwpp_get_redo_stats(pwpp_handle *h, int64_t *frames_one_pass, int64_t *frame
 /* timing probes of the last call (PWPP_DEBUG_FLAGS & 4) */
 int pwpp_debug_read(pwpp_handle *h, unsigned long long *out64) {
     if (!h || !out64) return fail(PWPP_E_ARG, "null argument");
-    int rc = use_device(h);
+    int rc = enter(h);
     if (rc) return rc;
-    if ((rc = finish_pending(h))) return rc;
     if (!h->d_dbg.p) return fail(PWPP_E_STATE, "no probes");
     HIPCHK(hipMemcpy(out64, h->d_dbg.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PWPP_OK;

@@ -445,6 +445,81 @@ def test_labels_point_planes_and_records_together(oracle, order):
     alone.close()
 
 
+def tiny_frames():
+    """Three synthetic frames: a few hundred points, an empty one and a single point."""
+    c = pwpp_synth.make_cloud(31, beams=8, azimuth_steps=60)
+    assert 200 < c.shape[0] < 1000
+    return [np.ascontiguousarray(c), np.zeros((0, 4), np.float32), np.ascontiguousarray(c[17:18])]
+
+
+def all_outputs(h):
+    """Everything the last call wrote, as bytes: lists, labels, point planes and records of the whole batch."""
+    idx, base, counts = h.all_indices()
+    lists = b"".join(idx[base[k]:base[k] + counts[k, 0] + counts[k, 1]].tobytes() for k in range(len(base) - 1))
+    return (lists, counts[:, :3].tobytes(), h.all_labels()[0].tobytes(), h.all_point_patches()[0].tobytes(),
+            h.all_point_distances()[0].tobytes(), written_rows(h))
+
+
+def test_trim_leaves_the_same_bytes_with_and_without_outputs():
+    clouds = tiny_frames()
+    points = sum(c.shape[0] for c in clouds)
+    on, off = pwpp_hip.Handle(), pwpp_hip.Handle()
+    on.set_labels(True)
+    on.set_point_planes(True)
+    on.set_point_records(True)
+    for h, last_order in ((on, pwpp_hip.ORDER_CLOUD), (off, pwpp_hip.ORDER_SCATTER)):
+        h.set_num_streams(3)
+        h.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_FRESH)
+        h.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_STREAMS)
+        h.set_order(pwpp_hip.ORDER_REFERENCE)
+        h.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_FRESH)
+        h.set_order(last_order)  # (cloud order implies labels; the handle without outputs runs a plain call instead)
+        h.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_FRESH)
+    assert on.record_bytes == 16
+    assert on.workspace_bytes() >= off.workspace_bytes() + (1 + 4 + 4 + on.record_bytes) * points
+    before = all_outputs(on)
+    on.trim_workspace()
+    off.trim_workspace()
+    assert on.workspace_bytes() == off.workspace_bytes()
+    on.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_FRESH)
+    assert all_outputs(on) == before
+    on.close()
+    off.close()
+
+
+def test_frame_getters_equal_the_batch_getters():
+    clouds = tiny_frames()
+    h = pwpp_hip.Handle()
+    h.set_labels(True)
+    h.set_point_planes(True)
+    h.set_point_records(True)
+    h.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_FRESH)
+    base = h.frame_base()
+    assert list(np.diff(base)) == [c.shape[0] for c in clouds]
+    labels, patches, dists = h.all_labels()[0], h.all_point_patches()[0], h.all_point_distances()[0]
+    rec, rbase, counts = h.all_records()
+    assert np.array_equal(rbase, base)
+    for k in range(len(clouds)):
+        span = slice(int(base[k]), int(base[k + 1]))
+        assert np.array_equal(h.labels(k), labels[span])
+        assert np.array_equal(h.point_patches(k), patches[span])
+        assert np.array_equal(h.point_distances(k).view(np.uint32), dists[span].view(np.uint32))
+        rows = np.concatenate([h.ground_records(k), h.nonground_records(k)])
+        assert np.array_equal(rows, rec[base[k]:base[k] + counts[k, 0] + counts[k, 1]])
+    # a call with an output off: its getters, per frame and for the batch, say which one is missing
+    for off, text, getters in (
+            (h.set_labels, "without labels", (lambda: h.labels(0), lambda: h.labels(1), h.all_labels, h.device_labels)),
+            (h.set_point_planes, "without point planes", (lambda: h.point_patches(0), lambda: h.point_distances(1), h.all_point_patches,
+                                                          h.all_point_distances, h.device_point_planes)),
+            (h.set_point_records, "without point records", (h.all_records, h.device_records))):
+        off(False)
+        h.estimate_ground_batch(clouds, mode=pwpp_hip.MODE_FRESH)
+        for get in getters:
+            with pytest.raises(pwpp_hip.PwppError, match=text):
+                get()
+    h.close()
+
+
 # ---- 7. class and ROS core ---------------------------------------------------------------------------------------------------
 def test_pybind_ground_points_keep_the_intensity(kitti):
     import pypatchworkpp
