@@ -377,6 +377,56 @@ PWPP_API int pwpp_get_nonground_records(pwpp_handle *h, int frame, void *out);
 PWPP_API int pwpp_get_all_records(pwpp_handle *h, void *out, int64_t *frame_base, int32_t *counts);
 PWPP_API int pwpp_get_device_records(pwpp_handle *h, const void **out, int32_t *record_bytes);   /* either may be NULL */
 
+/* ---- the fitted ground model at arbitrary positions and as a grid (pwpp_query_ground, pwpp_rasterize_ground) ---------------
+ * What pwpp_set_point_planes gives for the cloud's own points, for ANY position: the ground height under a detection box, the
+ * height above ground of a return that was not part of the fit (radar, a second LiDAR), a bird's-eye elevation image.
+ *   When      Both calls answer from the results of the handle's LAST estimate call and work after every kind of call (fresh or
+ *             streams, any layout, memory kind and schedule, a pipe's handles); no setter is needed.  They enter like the getters:
+ *             the call in flight lands first, a frame that awaits the serial fix-up or a redo is finished first.  PWPP_E_STATE
+ *             before any call and after pwpp_trim_workspace.  Pure reads: no result, state or timing of the estimate path changes.
+ *   mem       PWPP_MEM_HOST: input and output are host memory, staged through buffers of the handle; synchronous.
+ *             PWPP_MEM_DEVICE: input and output are device memory, the work is enqueued on the handle's stream and is complete
+ *             after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   bin       The bin the reference's pc2czm (patchworkpp.cpp:593-615) puts a point with these x, y into, all in double.  The
+ *             query's z plays no part in it.  RNR and the skip marker z == FLT_MIN are tests on the points of a cloud and do NOT
+ *             apply to positions -- consequence: a cloud point that RNR removed has patch -1 in pwpp_get_point_patches, but its
+ *             position queries into its bin's patch.  The no-patch sample {-1, 0, NaN, NaN} answers: a position outside
+ *             (min_range, max_range] or with a NaN / inf x or y; a position in a bin with fewer than num_min_pts points; an entry
+ *             whose frame[i] is outside [0, frames of the last call) -- the kernel checks that, the host does not scan the list,
+ *             so both memory kinds behave the same.
+ *   patch     The row of the bin's patch in pwpp_get_patch_records / pwpp_get_centers / pwpp_get_normals: patch bins ranked in
+ *             ascending bin order.  With num_min_pts <= 0 empty bins are rows too and answer with their inherited plane, as their
+ *             record does.
+ *   distance  The point-planes formula, unchanged, against the record's normal and d (the patch's REPORTED plane):
+ *                 s = fl32(fl32(fl32(n0 * x) + fl32(n1 * y)) + fl32(n2 * z));   distance = (float)((double)s + d)
+ *             A NaN or inf z gives what IEEE arithmetic gives.
+ *   ground_z  The height of that plane at (x, y), in double on the record's floats, rounded once:
+ *                 ground_z = (float)( -(((double)n0 * (double)x + (double)n1 * (double)y) + d) / (double)n2 )
+ *             (the products are exact in double; one rounding per add, one IEEE division, one rounding to float).  n2 == 0 gives
+ *             what IEEE gives; in a patch decided NOT_UPRIGHT it is the height of a wall's plane, not of ground: see `decision`.
+ *   edge      m == 0 is PWPP_OK and launches nothing; a null xyz or out with m > 0 is PWPP_E_ARG.  Caller pointers need the natural
+ *             alignment of their element types (4 bytes) and no more.
+ * Nothing is allocated for this until the first query; pwpp_trim_workspace frees it and pwpp_get_workspace_bytes counts it. */
+#define PWPP_HAS_GROUND_QUERY 1
+typedef struct pwpp_ground_sample {   /* 16 bytes */
+    int32_t patch;      /* row in pwpp_get_patch_records / centers / normals of the patch whose bin holds (x, y); -1: none */
+    int32_t decision;   /* that record's pwpp_decision; 0 where patch is -1 */
+    float   ground_z;   /* height of the patch's REPORTED plane at (x, y); NaN where patch is -1 */
+    float   distance;   /* signed distance of (x, y, z) to that plane; NaN where patch is -1 */
+} pwpp_ground_sample;
+PWPP_API int pwpp_query_ground(pwpp_handle *h, const float *xyz /* (m,3) row-major */, const int32_t *frame /* m entries, or NULL: frame 0 */,
+                               int64_t m, int mem, pwpp_ground_sample *out);
+/* The same as an image: cell (ix, iy) of a frame is the query of its centre,
+ *     cx = (float)(x0 + (ix + 0.5) * cell),   cy = (float)(y0 + (iy + 0.5) * cell)     evaluated in double,
+ * height[f][iy][ix] that query's ground_z and patch[f][iy][ix] its row (patch may be NULL), for the frames frame_first ..
+ * frame_first + frames - 1 of the last call.  With PWPP_GRID_GROUND_ONLY the cells whose patch was decided NOT_UPRIGHT, HEADING or
+ * TGR_REJECT get a NaN height; their row is still reported.  PWPP_E_ARG: a null grid or height, nx or ny < 1, a cell that is not
+ * finite and positive, a frame range outside the last call, nx * ny * frames beyond 2^31. */
+typedef struct pwpp_ground_grid { double x0, y0, cell; int32_t nx, ny; int32_t flags; int32_t pad_; } pwpp_ground_grid;
+enum { PWPP_GRID_GROUND_ONLY = 1 };
+PWPP_API int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem,
+                                   float *height /* [frames][ny][nx] */, int32_t *patch /* same shape, may be NULL */);
+
 /* Overlap mode (ON by default): batches of 128 frames or more are processed as two frame ranges -- binning
  * and index lists of both on the handle's main stream, each range's plane fits on a stream of its own -- so
  * that the stages of one range fill the wave slots the other leaves empty (binning and index lists are bound

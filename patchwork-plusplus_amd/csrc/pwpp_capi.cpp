@@ -31,8 +31,14 @@ extern "C" int pwpp_launch_k5_tail(const PwppBatch *batch, hipStream_t aux, hipE
 extern "C" int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream);
 extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, int count, float *out, hipStream_t stream);
 extern "C" int pwpp_launch_gather_records(const PwppFrameDesc *fd, const int *idx, int count, void *out, int path, hipStream_t stream);
+extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, int rows_valid, const float *xyz, const int32_t *frame, int64_t m, void *out,
+                                        hipStream_t stream);
+extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_valid, const PwppGroundGrid *grid, int frame_first, int frames,
+                                         float *height, int32_t *patch, hipStream_t stream);
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
+static_assert(sizeof(pwpp_ground_sample) == sizeof(PwppGroundSample) && sizeof(pwpp_ground_sample) == 16, "pwpp_ground_sample must mirror PwppGroundSample");
+static_assert(sizeof(pwpp_ground_grid) == sizeof(PwppGroundGrid) && sizeof(pwpp_ground_grid) == 40, "pwpp_ground_grid must mirror PwppGroundGrid");
 
 namespace {
 
@@ -237,6 +243,11 @@ struct pwpp_handle {
     int record_bytes = 0;           // bytes per row of the last call's records (0: no call yet)
     int records_path = 0;           // option "records_path"
     DevBuf<uint8_t> d_records{bufs, kPerBatch};  // [total points][record_bytes] + 64: the records of the listed points, rows laid out like d_out
+    // ground queries of the last call's results (pwpp_query_ground, pwpp_rasterize_ground): nothing is allocated before the first one
+    DevBuf<int32_t> d_ground_rows{bufs, kPerBatch};   // [frames][B] bin -> row of the last call (PwppGroundView.rows)
+    DevBuf<uint32_t> d_ground_stage{bufs, kPerBatch};  // PWPP_MEM_HOST queries: the output, then the input, in 4-byte words
+    bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
+    bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
     DevBuf<uint32_t> d_bins{bufs, kPerBatch};  // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
     DevBuf<uint32_t> d_parts{bufs, kPerBatch};  // TWO copies of 3 slabs of frames*(2B+2): part_count, part_off, part_cursor (pwpp_dev.h: a bin is stored in two
                                // parts); a call works on one copy while its K5 zeroes the other for the next call (PwppBatch.next_part_count)
@@ -1587,6 +1598,7 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
         // (the copies themselves are made by the binning kernel: PwppBatch.snap_*, set in launch_prepared)
     }
     if (frames > 64 && (rc = refresh_emit_long(h))) return rc;
+    h->ground_rows_valid = false;  // (the ground queries rank this call's bins anew)
     if ((rc = launch_prepared(h, one_pass))) return rc;
     h->pending = true;
     h->have_results = false;
@@ -1604,7 +1616,13 @@ int pwpp_estimate_ground(pwpp_handle *h, const float *points, int n, int cols, i
 }
 
 int pwpp_synchronize(pwpp_handle *h) {
-    return enter(h, true);  // (the call's results; a stream's state is settled by whoever touches it: settle_k5_tail)
+    const int rc = enter(h, true);  // (the call's results; a stream's state is settled by whoever touches it: settle_k5_tail)
+    if (rc) return rc;
+    if (h->ground_query_queued) {  // (a PWPP_MEM_DEVICE ground query behind a call that had landed already)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->ground_query_queued = false;
+    }
+    return PWPP_OK;
 }
 
 int pwpp_get_counts(pwpp_handle *h, int frame, int32_t *n_ground, int32_t *n_nonground, int32_t *n_patches) {
@@ -2027,6 +2045,7 @@ int pwpp_trim_workspace(pwpp_handle *h) {
     for (BufBase *b : h->bufs)
         if (b->per_batch) b->release();
     h->have_results = false;  // the index lists lived in d_out, the records in d_recs
+    h->ground_rows_valid = false;
     h->next_clean.valid = false;  // (the counters' copies are gone with d_parts / d_results)
     h->descs_on_device.clear();
     return PWPP_OK;
@@ -2127,6 +2146,104 @@ int pwpp_get_device_records(pwpp_handle *h, const void **out, int32_t *record_by
     if (rc) return rc;
     if (out) *out = h->d_records.p;
     if (record_bytes) *record_bytes = h->record_bytes;
+    return PWPP_OK;
+}
+
+// ---- ground queries: the last call's planes at arbitrary positions -------------------------------------------------------
+namespace {
+// the last call's results as the ground-query kernels see them; the bin -> row table is allocated here, on the first query
+int ground_view(pwpp_handle *h, PwppGroundView &v) {
+    const int32_t *const held = h->d_ground_rows.p;
+    const int rc = h->d_ground_rows.ensure((size_t)h->frames * (size_t)h->dp.num_bins);
+    if (h->d_ground_rows.p != held) h->ground_rows_valid = false;
+    if (rc) return rc;
+    std::memset(&v, 0, sizeof(v));
+    v.P = h->dp;
+    v.bin_count = h->d_bins.p;  // (the first slab: fill_batch)
+    v.recs = h->d_recs.p;
+    v.rows = h->d_ground_rows.p;
+    v.num_frames = h->frames;
+    v.debug = h->debug_flags;
+    return PWPP_OK;
+}
+int ground_mem(int mem) {
+    if (mem == PWPP_MEM_HOST || mem == PWPP_MEM_DEVICE) return PWPP_OK;
+    return fail(PWPP_E_ARG, "mem %d: the ground queries take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
+}
+}  // namespace
+
+int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, int64_t m, int mem, pwpp_ground_sample *out) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (m < 0 || m > ((int64_t)1 << 31)) return fail(PWPP_E_ARG, "%lld positions (0..2^31 supported)", (long long)m);
+    if (m > 0 && (!xyz || !out)) return fail(PWPP_E_ARG, "null %s", xyz ? "output" : "positions");
+    int rc = ground_mem(mem);
+    if (rc) return rc;
+    if ((rc = check_frame(h, 0))) return rc;
+    if (m == 0) return PWPP_OK;
+    PwppGroundView v;
+    const float *d_xyz = xyz;
+    const int32_t *d_frame = frame;
+    void *d_out = out;
+    const size_t um = (size_t)m;
+    if (mem == PWPP_MEM_HOST) {  // the output first: 16-byte aligned for the kernel's wide stores
+        if ((rc = h->d_ground_stage.ensure(um * 8))) return rc;
+        uint32_t *w = h->d_ground_stage.p;
+        d_out = w;
+        d_xyz = reinterpret_cast<const float *>(w + um * 4);
+        HIPCHK(hipMemcpyAsync(w + um * 4, xyz, um * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if (frame) {
+            d_frame = reinterpret_cast<const int32_t *>(w + um * 7);
+            HIPCHK(hipMemcpyAsync(w + um * 7, frame, um * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        }
+    }
+    if ((rc = ground_view(h, v))) return rc;
+    const int lrc = pwpp_launch_ground_query(&v, h->ground_rows_valid, d_xyz, d_frame, m, d_out, h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    h->ground_rows_valid = true;
+    if (mem == PWPP_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(out, d_out, um * sizeof(pwpp_ground_sample), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        h->ground_query_queued = true;
+    }
+    return PWPP_OK;
+}
+
+int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, float *height, int32_t *patch) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !height) return fail(PWPP_E_ARG, "null %s", g ? "height image" : "grid");
+    if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
+        return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
+    int rc = ground_mem(mem);
+    if (rc) return rc;
+    if ((rc = check_frame(h, 0))) return rc;
+    if (frame_first < 0 || frames < 1 || frames > h->frames - frame_first)
+        return fail(PWPP_E_ARG, "frames [%d, %d + %d) outside the last call's [0, %d)", frame_first, frame_first, frames, h->frames);
+    const int64_t per_frame = (int64_t)g->nx * (int64_t)g->ny;  // (< 2^62)
+    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", g->nx, g->ny, frames);
+    const size_t cells = (size_t)per_frame * (size_t)frames;
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    float *d_height = height;
+    int32_t *d_patch = patch;
+    if (mem == PWPP_MEM_HOST) {
+        if ((rc = h->d_ground_stage.ensure(cells * (patch ? 2 : 1)))) return rc;
+        d_height = reinterpret_cast<float *>(h->d_ground_stage.p);
+        d_patch = patch ? reinterpret_cast<int32_t *>(h->d_ground_stage.p + cells) : nullptr;
+    }
+    if ((rc = ground_view(h, v))) return rc;
+    const int lrc = pwpp_launch_ground_raster(&v, h->ground_rows_valid, &grid, frame_first, frames, d_height, d_patch, h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    h->ground_rows_valid = true;
+    if (mem == PWPP_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(height, d_height, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (patch) HIPCHK(hipMemcpyAsync(patch, d_patch, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        h->ground_query_queued = true;
+    }
     return PWPP_OK;
 }
 

@@ -239,4 +239,25 @@ struct PwppBatch {
     int32_t next_slabs;          // 1 (one-pass binning: counts only) or 3
 };
 
+// What the ground-query kernels read of the LAST call (pwpp_query_ground / pwpp_rasterize_ground): a post-call view, by value
+// in the kernarg segment like PwppBatch.  Nothing of the estimate pipeline is written.
+struct PwppGroundView {
+    PwppDevParams P;
+    const uint32_t *bin_count;   // [frames][B+2] PwppBatch.bin_count of the last call
+    const PwppPatchRec *recs;    // [frames][B]   PwppBatch.recs of the last call
+    int32_t *rows;               // [frames][B]   the row of every bin that is a patch, -1 for the others (k_ground_rows)
+    int32_t num_frames;          // frames of the last call
+    int32_t debug;               // option "debug_flags": 16 = exact binning only
+};
+
+struct PwppGroundSample {  // = pwpp_ground_sample
+    int32_t patch, decision;
+    float ground_z, distance;
+};
+
+struct PwppGroundGrid {  // = pwpp_ground_grid
+    double x0, y0, cell;
+    int32_t nx, ny, flags, pad_;
+};
+
 #endif

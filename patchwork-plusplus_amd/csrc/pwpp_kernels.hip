@@ -19,6 +19,8 @@
 //   K8  k_label_*          optional: per-point labels from the final lists; cloud-order lists from the labels
 //   K9  k_pp_*             optional: per-point patch row and signed distance to the patch's plane  (ref :551-554)
 //   K10 k_point_records    optional: the whole input records of the listed points, row for row behind the lists  (ref :8-16)
+// After a call, on demand: k_ground_rows / k_ground_query / k_ground_raster read the fitted planes at positions that are not
+// cloud points (pwpp_query_ground, pwpp_rasterize_ground); they write nothing the pipeline reads.
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -2699,6 +2701,27 @@ __global__ __launch_bounds__(kLabelBlock) void k_label_compact(PwppBatch Bt) {
 constexpr int kPpBlock = 256;
 constexpr int kPpWave = 64;
 
+// The rows of pwpp_get_patch_records of one frame: its bins with at least num_min_pts points, ranked in ascending bin order.
+// One workgroup of kPpBlock lanes, every lane a run of neighbouring bins; rows[b] = the row of bin b, -1 where b is no patch.
+// `cnt`: the frame's bin_count, `s_tot`: kPpBlock / 64 words of LDS.  Shared by k_pp_prep and k_ground_rows.
+__device__ __forceinline__ void rank_patch_bins(const PwppDevParams &P, const uint32_t *cnt, int32_t *rows, unsigned *s_tot) {
+    const int B = P.num_bins;
+    constexpr int kPer = (PWPP_MAX_BINS + kPpBlock - 1) / kPpBlock;
+    const int per = (B + kPpBlock - 1) / kPpBlock, b0 = (int)threadIdx.x * per;
+    unsigned is_patch = 0u;  // bit j: bin b0 + j is a patch
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+        if (j < per && b0 + j < B && (uint64_t)cnt[b0 + j] >= P.min_pts) is_patch |= 1u << j;
+    const unsigned c = (unsigned)__popc(is_patch), incl = wave_incl_scan(c);
+    if (lane_id() == 63) s_tot[wave_id()] = incl;
+    __syncthreads();
+    unsigned row = incl - c;
+    for (int w = 0; w < wave_id(); ++w) row += s_tot[w];
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+        if (j < per && b0 + j < B) rows[b0 + j] = (is_patch >> j & 1u) ? (int32_t)(row++) : -1;
+}
+
 // blocks [0, fill_blocks): the slots [first, first + count) = -1 / NaN, 16 bytes per lane and array; then one block per frame: the
 // bin -> row table (pt_rows)
 __global__ __launch_bounds__(kPpBlock) void k_pp_prep(PwppBatch Bt, int64_t first, int64_t count, unsigned fill_blocks) {
@@ -2720,24 +2743,8 @@ __global__ __launch_bounds__(kPpBlock) void k_pp_prep(PwppBatch Bt, int64_t firs
     }
     __shared__ unsigned s_tot[kPpBlock / 64];
     const int f = (int)(blockIdx.x - fill_blocks);
-    const PwppDevParams &P = Bt.P;
-    const int B = P.num_bins, NB = B + 2;
-    constexpr int kPer = (PWPP_MAX_BINS + kPpBlock - 1) / kPpBlock;
-    const int per = (B + kPpBlock - 1) / kPpBlock, b0 = (int)threadIdx.x * per;
-    const uint32_t *cnt = Bt.bin_count + (size_t)f * NB;
-    unsigned is_patch = 0u;  // bit j: bin b0 + j is a patch
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-        if (j < per && b0 + j < B && (uint64_t)cnt[b0 + j] >= P.min_pts) is_patch |= 1u << j;
-    const unsigned c = (unsigned)__popc(is_patch), incl = wave_incl_scan(c);
-    if (lane_id() == 63) s_tot[wave_id()] = incl;
-    __syncthreads();
-    unsigned row = incl - c;
-    for (int w = 0; w < wave_id(); ++w) row += s_tot[w];
-    int32_t *rows = Bt.pt_rows + (size_t)f * B;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-        if (j < per && b0 + j < B) rows[b0 + j] = (is_patch >> j & 1u) ? (int32_t)(row++) : -1;
+    const int B = Bt.P.num_bins;
+    rank_patch_bins(Bt.P, Bt.bin_count + (size_t)f * (B + 2), Bt.pt_rows + (size_t)f * B, s_tot);
 }
 
 // one wave per (patch bin, frame), gridDim.z waves per bin share its slots in steps of 256 (four per lane: 16-byte loads)
@@ -2911,6 +2918,86 @@ __global__ __launch_bounds__(kRecBlock) void k_gather_records(PwppFrameDesc fd, 
     gather_rows64(fd, idx, e0, count, out, path);
 }
 
+// ------------------------------------------------------------------------------------------
+// Ground queries (pwpp_query_ground, pwpp_rasterize_ground): the fitted ground model of the LAST call at arbitrary positions
+// ------------------------------------------------------------------------------------------
+// Post-call reads of bin_count and the patch records: nothing of the estimate pipeline is launched again or written.  The bin of
+// a position is pc2czm's (:593-615) for its x, y -- RNR and the z == FLT_MIN marker are tests on cloud points, not on positions
+// -- the row is its rank among the frame's patch bins (k_ground_rows, the ranking of k_pp_prep), the plane the record's:
+//   distance = calc_point_to_plane_d (:551-554) as k_pp_patch evaluates it: float products and sums left to right, + d in double
+//   ground_z = the z at which that plane passes (x, y): -((n0 x + n1 y) + d) / n2 in double -- the products of two floats are
+//              exact there, so: one rounding per add, one division, one rounding to float.  n2 == 0: what IEEE gives.
+// Frame, bin and row are checked before every load that depends on them: no input of a caller can form an address outside the
+// view's arrays.
+constexpr int kGqBlock = 256;
+
+__global__ __launch_bounds__(kPpBlock) void k_ground_rows(PwppGroundView Q) {
+    __shared__ unsigned s_tot[kPpBlock / 64];
+    const int f = blockIdx.x, B = Q.P.num_bins;
+    rank_patch_bins(Q.P, Q.bin_count + (size_t)f * (B + 2), Q.rows + (size_t)f * B, s_tot);
+}
+
+__device__ __forceinline__ PwppGroundSample ground_sample(const PwppGroundView &Q, int f, unsigned code, float x, float y, float z) {
+    const float qnan = __uint_as_float(0x7fc00000u);
+    PwppGroundSample s = {-1, 0, qnan, qnan};
+    const unsigned B = (unsigned)Q.P.num_bins;
+    if ((unsigned)f >= (unsigned)Q.num_frames || code >= B) return s;  // (code >= B: outside (min_range, max_range], NaN, inf)
+    const int row = Q.rows[(size_t)f * B + code];
+    if ((unsigned)row >= B) return s;  // (-1: fewer than num_min_pts points)
+    const PwppPatchRec *rec = Q.recs + (size_t)f * B + code;
+    const float n0 = rec->normal[0], n1 = rec->normal[1], n2 = rec->normal[2];
+    const double d = rec->d;
+    s.patch = row;
+    s.decision = rec->decision;
+    const float t = n0 * x + n1 * y + n2 * z;  // ref :553 (-ffp-contract=off: no FMA)
+    s.distance = (float)((double)t + d);
+    s.ground_z = (float)(-(((double)n0 * (double)x + (double)n1 * (double)y) + d) / (double)n2);
+    return s;
+}
+
+// one lane per query, one 16-byte store per lane where `out` is 16-byte aligned (a caller's array of 4-byte fields need not be)
+__global__ __launch_bounds__(kGqBlock) void k_ground_query(PwppGroundView Q, const float *xyz, const int32_t *frame, int64_t m, PwppGroundSample *out) {
+    const int64_t i = (int64_t)blockIdx.x * kGqBlock + threadIdx.x;
+    if (i >= m) return;
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    const int f = frame ? frame[i] : 0;
+    const PwppGroundSample s = ground_sample(Q, f, bin_code_exact(Q.P, x, y), x, y, z);
+    if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0u) {
+        *reinterpret_cast<int4 *>(out + i) = make_int4(s.patch, s.decision, __float_as_int(s.ground_z), __float_as_int(s.distance));
+    } else {
+        out[i].patch = s.patch;
+        out[i].decision = s.decision;
+        out[i].ground_z = s.ground_z;
+        out[i].distance = s.distance;
+    }
+}
+
+// grid (tiles of kGqBlock cells along x, rows, frames): lanes run along ix, so a wave's stores are 256 contiguous bytes of a row.
+// Cell (ix, iy) is the query of its centre; the bin comes from bin_code_fast where that is sure, from bin_code_exact otherwise
+// (czm_code's rule; debug bit 16: always exact).  Neighbouring cells mostly share a bin: their lanes read the same 64-byte
+// record, which the vector memory path serves as one request per distinct line -- a plain per-lane load, no wave-level broadcast.
+__global__ __launch_bounds__(kGqBlock) void k_ground_raster(PwppGroundView Q, PwppGroundGrid G, int frame_first, float *height, int32_t *patch) {
+    __shared__ float4 s_zt[8];
+    fill_zone_table(Q.P, s_zt);
+    __syncthreads();
+    const int ix = (int)(blockIdx.x * kGqBlock + threadIdx.x);
+    if (ix >= G.nx) return;
+    const int fr = blockIdx.z;  // (relative to frame_first)
+    const float cx = (float)(G.x0 + ((double)ix + 0.5) * G.cell);
+    const bool exact_only = (Q.debug & 16) != 0;
+    for (int iy = blockIdx.y; iy < G.ny; iy += (int)gridDim.y) {
+        const float cy = (float)(G.y0 + ((double)iy + 0.5) * G.cell);
+        unsigned code = 0;
+        if (exact_only || !bin_code_fast(Q.P, s_zt, cx, cy, code)) code = bin_code_exact(Q.P, cx, cy);
+        const PwppGroundSample s = ground_sample(Q, frame_first + fr, code, cx, cy, 0.0f);
+        const bool hidden = (G.flags & PWPP_GRID_GROUND_ONLY) &&
+                            (s.decision == PWPP_DEC_NOT_UPRIGHT || s.decision == PWPP_DEC_HEADING || s.decision == PWPP_DEC_TGR_REJECT);
+        const size_t o = ((size_t)fr * (size_t)G.ny + (size_t)iy) * (size_t)G.nx + (size_t)ix;
+        height[o] = hidden ? __uint_as_float(0x7fc00000u) : s.ground_z;
+        if (patch) patch[o] = s.patch;
+    }
+}
+
 }  // namespace
 
 // the records of the launch's frames, behind their final lists
@@ -2955,6 +3042,25 @@ static void launch_labels(const PwppBatch &B, hipStream_t stream) {
 extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, int count, float *out, hipStream_t stream) {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(k_gather_xyz, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, *fd, idx, count, out);
+    return (int)hipGetLastError();
+}
+
+// The ground queries of pwpp_capi.cpp.  rows_valid == 0: the bin -> row table of every frame of the view is computed first
+// (once per estimate call).
+extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, int rows_valid, const float *xyz, const int32_t *frame, int64_t m, void *out,
+                                        hipStream_t stream) {
+    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+    if (m > 0)
+        hipLaunchKernelGGL(k_ground_query, dim3((unsigned)((m + kGqBlock - 1) / kGqBlock)), dim3(kGqBlock), 0, stream, *view, xyz, frame, m,
+                           static_cast<PwppGroundSample *>(out));
+    return (int)hipGetLastError();
+}
+
+extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_valid, const PwppGroundGrid *grid, int frame_first, int frames,
+                                         float *height, int32_t *patch, hipStream_t stream) {
+    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+    const dim3 g((unsigned)((grid->nx + kGqBlock - 1) / kGqBlock), (unsigned)(grid->ny < 65535 ? grid->ny : 65535), (unsigned)frames);
+    hipLaunchKernelGGL(k_ground_raster, g, dim3(kGqBlock), 0, stream, *view, *grid, frame_first, height, patch);
     return (int)hipGetLastError();
 }
 

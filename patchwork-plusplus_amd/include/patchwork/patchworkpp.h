@@ -306,6 +306,39 @@ public:
 #endif
     Points groundPointRows() { return points(true); }
     Points nongroundPointRows() { return points(false); }
+    // extension: the fitted ground model of the last frame at positions that are not cloud points (pwpp.h, pwpp_query_ground):
+    // per position the row of its bin's patch in getCenters() / getNormals() (-1: none), that patch's decision, the height of
+    // its plane at (x, y) and the signed distance of (x, y, z) to it.  `xyz`: m row-major (x, y, z) triples.
+    std::vector<pwpp_ground_sample> queryGround(const float *xyz, int m) {
+        std::vector<pwpp_ground_sample> out((size_t)(m > 0 ? m : 0));
+        check(pwpp_query_ground(h_, xyz, nullptr, m, PWPP_MEM_HOST, out.data()));
+        return out;
+    }
+    // ... and as a bird's-eye elevation image (pwpp_rasterize_ground): row iy, column ix = the plane height at the cell centre
+    // (x0 + (ix + 0.5) cell, y0 + (iy + 0.5) cell), NaN where no patch answers; ground_only: NaN too where the patch was decided
+    // not upright, heading or rejected by TGR
+    Points elevationMapRows(double x0, double y0, double cell, int nx, int ny, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        Points img(ny > 0 ? ny : 0, nx > 0 ? nx : 0);
+        float none = 0.0f;
+        check(pwpp_rasterize_ground(h_, &g, 0, 1, PWPP_MEM_HOST, img.rows() > 0 && img.cols() > 0 ? img.data() : &none, nullptr));
+        return img;
+    }
+#ifdef PWPP_HAVE_EIGEN
+    std::vector<pwpp_ground_sample> queryGround(const Eigen::MatrixX3f &positions) {
+        std::vector<float> xyz((size_t)positions.rows() * 3);
+        for (int i = 0; i < (int)positions.rows(); ++i)
+            for (int j = 0; j < 3; ++j) xyz[(size_t)i * 3 + (size_t)j] = positions(i, j);
+        return queryGround(xyz.data(), (int)positions.rows());
+    }
+    Eigen::MatrixXf getElevationMap(double x0, double y0, double cell, int nx, int ny, bool ground_only = false) {
+        return to_eigen(elevationMapRows(x0, y0, cell, nx, ny, ground_only));
+    }
+#else
+    Points getElevationMap(double x0, double y0, double cell, int nx, int ny, bool ground_only = false) {
+        return elevationMapRows(x0, y0, cell, nx, ny, ground_only);
+    }
+#endif
 
 #ifdef PWPP_HAVE_EIGEN
     // the reference's return types (fresh objects on every call, as the reference's toEigenCloud / toIndices, :8-26)

@@ -56,6 +56,20 @@ class DeviceView(ctypes.Structure):
                 ("counts", ctypes.POINTER(ctypes.c_int32)), ("frames", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+class GroundSample(ctypes.Structure):  # pwpp_ground_sample
+    _fields_ = [("patch", ctypes.c_int32), ("decision", ctypes.c_int32), ("ground_z", ctypes.c_float),
+                ("distance", ctypes.c_float)]
+
+
+class GroundGrid(ctypes.Structure):  # pwpp_ground_grid
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("cell", ctypes.c_double), ("nx", ctypes.c_int32),
+                ("ny", ctypes.c_int32), ("flags", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+GROUND_SAMPLE_DTYPE = np.dtype([("patch", "<i4"), ("decision", "<i4"), ("ground_z", "<f4"), ("distance", "<f4")])
+GRID_GROUND_ONLY = 1
+
+
 class PwppError(RuntimeError):
     pass
 
@@ -145,6 +159,9 @@ def load():
                 getattr(L, name).argtypes = [vp, ci, vp]
             L.pwpp_get_all_records.argtypes = [vp, vp, vp, vp]
             L.pwpp_get_device_records.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "pwpp_query_ground"):  # (as above: an older build has no ground queries)
+            L.pwpp_query_ground.argtypes = [vp, vp, vp, ctypes.c_int64, ci, vp]
+            L.pwpp_rasterize_ground.argtypes = [vp, ctypes.POINTER(GroundGrid), ci, ci, ci, vp, vp]
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
@@ -590,6 +607,50 @@ class Handle:
         p, rb = ctypes.c_void_p(), ctypes.c_int32(0)
         self._check(self._L.pwpp_get_device_records(self._h, ctypes.byref(p), ctypes.byref(rb)))
         return int(p.value or 0), int(rb.value)
+
+    def query_ground(self, xyz, frames=None):
+        """The last call's ground model at arbitrary positions: xyz (m, 3) float32, frames None (frame 0), an int or (m,) int32.
+        Returns a structured (m,) array with the fields patch, decision, ground_z, distance (include/pwpp.h)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        m = xyz.shape[0]
+        fr = None
+        if frames is not None:
+            fr = np.ascontiguousarray(np.broadcast_to(np.asarray(frames, np.int32), (m,)))
+        out = np.empty(max(m, 1), GROUND_SAMPLE_DTYPE)
+        self._check(self._L.pwpp_query_ground(self._h, _vp(xyz), _vp(fr) if fr is not None else None, m, MEM_HOST, _vp(out)))
+        return out[:m]
+
+    def query_ground_device(self, xyz_ptr, frames_ptr, m, out_ptr):
+        """query_ground on device memory: addresses of (m, 3) float32 positions, m int32 frames (0 / None: frame 0) and m
+        16-byte samples.  Enqueued on the handle's stream; complete after synchronize()."""
+        self._check(self._L.pwpp_query_ground(self._h, ctypes.c_void_p(xyz_ptr), ctypes.c_void_p(frames_ptr or None), int(m), MEM_DEVICE,
+                                              ctypes.c_void_p(out_ptr)))
+
+    def _grid(self, x0, y0, cell, nx, ny, frame_first, frames, ground_only):
+        if frames is None:
+            frames = self.device_view().frames - frame_first
+        return GroundGrid(float(x0), float(y0), float(cell), int(nx), int(ny), GRID_GROUND_ONLY if ground_only else 0, 0), int(frames)
+
+    def rasterize_ground(self, x0, y0, cell, nx, ny, frame_first=0, frames=None, ground_only=False, with_patches=False):
+        """The last call's ground model as an elevation image: (frames, ny, nx) float32 heights of the cell centres
+        (x0 + (ix + 0.5) cell, y0 + (iy + 0.5) cell), NaN where no patch answers; with_patches: also the int32 patch rows.
+        ground_only: NaN too where the patch was decided not_upright, heading or tgr_reject."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        height = np.empty(shape, np.float32)
+        patch = np.empty(shape, np.int32) if with_patches else None
+        # (an empty image still goes to the library: it is the one that names the bad argument)
+        hp = _vp(height) if height.size else _vp(np.empty(1, np.float32))
+        self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, hp,
+                                                  _vp(patch) if with_patches and patch.size else None))
+        return (height, patch) if with_patches else height
+
+    def rasterize_ground_device(self, x0, y0, cell, nx, ny, height_ptr, patch_ptr=0, frame_first=0, frames=None, ground_only=False):
+        """rasterize_ground into device memory: addresses of the (frames, ny, nx) float32 image and (0: none) the int32 one.
+        Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE,
+                                                  ctypes.c_void_p(height_ptr), ctypes.c_void_p(patch_ptr or None)))
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

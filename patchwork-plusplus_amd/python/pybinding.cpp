@@ -45,6 +45,27 @@ py::array_t<int32_t> to_numpy(const patchwork::Indices &v) {
     return out;
 }
 
+// queryGround: (m, 3) positions -> a structured array with the fields of pwpp_ground_sample
+py::array query_ground(PatchWorkpp &self, py::array positions) {
+    py::array_t<float, py::array::c_style | py::array::forcecast> a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(positions);
+    if (!a || a.ndim() != 2 || a.shape(1) != 3) throw py::value_error("queryGround expects an (m, 3) array");
+    const int m = (int)a.shape(0);
+    std::vector<pwpp_ground_sample> v;
+    {
+        const float *data = a.data();
+        py::gil_scoped_release release;
+        v = self.queryGround(data, m);
+    }
+    py::list fields;
+    fields.append(py::make_tuple("patch", "<i4"));
+    fields.append(py::make_tuple("decision", "<i4"));
+    fields.append(py::make_tuple("ground_z", "<f4"));
+    fields.append(py::make_tuple("distance", "<f4"));
+    py::array out(py::dtype::from_args(fields), std::vector<py::ssize_t>{(py::ssize_t)m});
+    if (m > 0) std::memcpy(out.mutable_data(), v.data(), (size_t)m * sizeof(pwpp_ground_sample));
+    return out;
+}
+
 void estimate_ground(PatchWorkpp &self, py::array cloud) {
     if (cloud.ndim() != 2) throw py::value_error("estimateGround expects a 2-D array (N, 3|4)");
     // F-contiguous float32 is consumed as column-major (the layout Eigen::MatrixXf would have),
@@ -118,6 +139,12 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def("getPointPatches", [](PatchWorkpp &s) { return to_numpy(s.pointPatchList()); })
         .def("getPointDistances", [](PatchWorkpp &s) { return to_numpy(s.pointDistanceList()); })
         .def("setPointRecords", &PatchWorkpp::setPointRecords, py::arg("on"))
+        .def("queryGround", &query_ground, py::arg("positions"))
+        .def("getElevationMap",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, bool ground_only) {
+                 return to_numpy(s.elevationMapRows(x0, y0, cell, nx, ny, ground_only));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("ground_only") = false)
         .def("getGroundPoints", [](PatchWorkpp &s) { return to_numpy(s.groundPointRows()); })
         .def("getNongroundPoints", [](PatchWorkpp &s) { return to_numpy(s.nongroundPointRows()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
