@@ -203,7 +203,8 @@ PWPP_API int pwpp_get_nonground_indices(pwpp_handle *h, int frame, int32_t *out)
 /* getGround()/getNonground(), reference patchworkpp.h:157-158: row-major (count,3) float32,
  * rows aligned with the index getters above.  The rows are gathered from the frame's input when these getters are
  * called: after a PWPP_MEM_DEVICE call that input is the caller's device buffer, which must therefore still hold the
- * frame (unchanged, not freed) when they run.  The index getters have no such need. */
+ * frame (unchanged, not freed) when they run.  The index getters have no such need.  With input transforms set
+ * (pwpp_set_input_transforms) the rows are the TRANSFORMED coordinates, those the call ran on. */
 PWPP_API int pwpp_get_ground_xyz(pwpp_handle *h, int frame, float *out);
 PWPP_API int pwpp_get_nonground_xyz(pwpp_handle *h, int frame, float *out);
 /* getCenters()/getNormals(), reference patchworkpp.h:162-163: row-major (n_patches,3), bin traversal order */
@@ -426,6 +427,44 @@ typedef struct pwpp_ground_grid { double x0, y0, cell; int32_t nx, ny; int32_t f
 enum { PWPP_GRID_GROUND_ONLY = 1 };
 PWPP_API int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem,
                                    float *height /* [frames][ny][nx] */, int32_t *patch /* same shape, may be NULL */);
+
+/* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
+ * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
+ * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
+ * every frame: instead of writing a transformed copy of each cloud first (one more read and one more write of the whole batch, and
+ * the end of the in-place input paths), hand over T_f = [R | t], a 3 x 4 row-major float matrix per frame.
+ *   Rule      With transforms set, every result of an estimate call is what the same call returns for the cloud whose points are
+ *             T_f(p) -- bit for bit, in every layout, memory kind, mode, schedule and output option.  The kernels apply T_f where
+ *             they read an input coordinate (no extra kernel, no extra bytes: nine multiplies and nine adds per point).
+ *   T_f       Any affine map: rotation, scale, mirror.  Nothing checks orthonormality.  The arithmetic is part of the contract
+ *             (no FMA is formed anywhere):
+ *                 x' = fl32(fl32(fl32(fl32(r00 * x) + fl32(r01 * y)) + fl32(r02 * z)) + t0)     y', z' alike with rows 1 and 2
+ *             so the identity matrix is NOT "off": it turns -0.0 into +0.0 (-0.0 + 0.0 is +0.0) and leaves every other value alone.
+ *             The fourth column of the input (intensity) passes through untouched.  Non-finite coordinates give what IEEE gives:
+ *             0 * inf is NaN, so ONE infinite coordinate of a point poisons all three: an output is NaN where the matrix has a zero
+ *             in that coordinate's column and +-inf or NaN elsewhere -- also under the identity, which returns {inf, NaN, NaN}
+ *             for {inf, y, z}.  A NaN coordinate makes NaN of all three.
+ *   Tests     All tests of the reference act on the transformed values: RNR's vertical angle and z guard, the range test, and the
+ *             skip marker z == FLT_MIN.  An input z of FLT_MIN is not special unless it maps to FLT_MIN; a point that maps onto
+ *             FLT_MIN exactly is skipped.
+ *   Setting   `T` is count x 12 floats in HOST memory, copied at the call; sticky; applies to the estimate calls launched
+ *             afterwards.  count == 1: that transform for every frame of every later call.  count > 1: entry i is for frame i (in
+ *             PWPP_MODE_STREAMS: stream i) and count must equal `frames` of each later call -- an estimate call with another
+ *             number of frames returns PWPP_E_ARG and launches nothing (the results of the call before stay readable).
+ *             T == NULL or count == 0 turns it off: nothing is allocated or launched for it, results are byte-identical to a
+ *             handle that never had transforms.  PWPP_E_ARG: a negative count, more than 65535 entries, an entry that is not
+ *             finite.  A pipe's handles take the setting through pwpp_pipe_handle, like the other settings.
+ *   Getters   pwpp_get_ground_xyz / pwpp_get_nonground_xyz (getGround() / getNonground()) return TRANSFORMED coordinates: the rows
+ *             of the cloud the rule speaks of.  pwpp_get_*_records, pwpp_get_all_records and the device records stay verbatim
+ *             copies of the input bytes, in the SENSOR's frame ("bytes are copied, never interpreted" keeps holding).  Point
+ *             distances, centers, normals, patch records, the adaptive state, pwpp_query_ground and pwpp_rasterize_ground live
+ *             in the transformed frame: carry query positions there with pwpp_transform_points.
+ * pwpp_transform_points: host only, no device needed.  out[i] = T(xyz[i]) for m rows of {x, y, z}, by the formula above, compiled
+ * from the same function the kernels use -- for query positions, detection boxes or a second sensor's returns that must land in
+ * the model's frame with exactly this library's rounding.  out may be xyz itself.  m == 0 is PWPP_OK. */
+#define PWPP_HAS_INPUT_TRANSFORM 1
+PWPP_API int pwpp_set_input_transforms(pwpp_handle *h, const float *T /* count x 12, host memory */, int count);
+PWPP_API int pwpp_transform_points(const float T[12], const float *xyz /* (m,3) row-major */, int64_t m, float *out /* (m,3) */);
 
 /* Overlap mode (ON by default): batches of 128 frames or more are processed as two frame ranges -- binning
  * and index lists of both on the handle's main stream, each range's plane fits on a stream of its own -- so

@@ -240,6 +240,11 @@ struct pwpp_handle {
     DevBuf<int32_t> d_pt_patch{bufs, kPerBatch};  // [total points] the row of every point's patch (-1: none), laid out like d_out
     DevBuf<float> d_pt_dist{bufs, kPerBatch};  // [total points] its signed distance to that patch's plane (NaN: none)
     DevBuf<int32_t> d_pt_rows{bufs, kPerBatch};  // [frames][B] K9's bin -> row table (PwppBatch.pt_rows)
+    std::vector<float> input_xf;    // pwpp_set_input_transforms: 12 floats per entry, copied at that call; empty = off.  One entry applies to
+                                    // every frame, several to frame i each (estimate_batch points the frame descriptors at them)
+    DevBuf<float> d_xf{bufs, kPerHandle};    // the transforms of the last call on the device (PwppFrameDesc.xf points into it); nothing before the first call with transforms
+    PinnedBuf<float> h_xf{bufs, kPerHandle}; // ... and what it holds
+    size_t xf_on_device = 0;                 // floats of h_xf that d_xf mirrors
     int record_bytes = 0;           // bytes per row of the last call's records (0: no call yet)
     int records_path = 0;           // option "records_path"
     DevBuf<uint8_t> d_records{bufs, kPerBatch};  // [total points][record_bytes] + 64: the records of the listed points, rows laid out like d_out
@@ -1419,6 +1424,9 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
     if (rc) return rc;
     if (mode == PWPP_MODE_STREAMS && frames > h->num_streams)
         return fail(PWPP_E_ARG, "%d frames but only %d streams (pwpp_set_num_streams)", frames, h->num_streams);
+    const size_t xf_count = h->input_xf.size() / 12;
+    if (xf_count > 1 && xf_count != (size_t)frames)  // (before anything of the last call is touched: its results stay readable)
+        return fail(PWPP_E_ARG, "%d frames but %zu input transforms (pwpp_set_input_transforms: one, or one per frame)", frames, xf_count);
 
     const int B = h->dp.num_bins, NB = B + 2, NP = PWPP_NUM_PARTS(B);
     int64_t total = 0, total_in = 0;
@@ -1475,6 +1483,17 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
         if ((rc = h->d_pl_fresh.ensure((size_t)frames))) return rc;
     }
     if (from_host && (rc = h->d_in.ensure((size_t)(total_in > 0 ? total_in : 4)))) return rc;
+    if (xf_count) {  // the transforms this call runs with, on the device before its first kernel; copied only when they changed
+        const size_t floats = h->input_xf.size();
+        if (h->d_xf.cap < floats) h->xf_on_device = 0;
+        if ((rc = h->d_xf.ensure(floats))) return rc;
+        if ((rc = h->h_xf.ensure(floats))) return rc;
+        if (h->xf_on_device != floats || std::memcmp(h->h_xf.p, h->input_xf.data(), floats * sizeof(float)) != 0) {
+            std::memcpy(h->h_xf.p, h->input_xf.data(), floats * sizeof(float));
+            HIPCHK(hipMemcpyAsync(h->d_xf.p, h->h_xf.p, floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            h->xf_on_device = floats;
+        }
+    }
 
     // ---- 2. frame descriptors; host inputs start their way to the device
     h->descs.resize((size_t)frames);
@@ -1492,6 +1511,7 @@ int estimate_batch(pwpp_handle *h, const float *const *points, const int32_t *n,
             d.step = fs->step;
             for (int k = 0; k < 4; ++k) d.off[k] = fs->off[k];
         }
+        if (xf_count) d.xf = h->d_xf.p + 12 * (xf_count == 1 ? 0 : (size_t)f);
         d.base = base;
         if (mode == PWPP_MODE_FRESH) {
             d.state_in = -1;
@@ -2063,6 +2083,30 @@ int pwpp_set_output_order(pwpp_handle *h, int order) {
 int pwpp_set_labels(pwpp_handle *h, int on) { return set_output(h, kLabels, on); }
 int pwpp_set_point_planes(pwpp_handle *h, int on) { return set_output(h, kPointPlanes, on); }
 int pwpp_set_point_records(pwpp_handle *h, int on) { return set_output(h, kPointRecords, on); }
+
+int pwpp_set_input_transforms(pwpp_handle *h, const float *T, int count) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (count < 0 || count > 65535) return fail(PWPP_E_ARG, "count=%d: 0 ... 65535 transforms expected", count);
+    const size_t floats = T ? 12 * (size_t)count : 0;
+    for (size_t k = 0; k < floats; ++k)
+        if (!std::isfinite(T[k])) return fail(PWPP_E_ARG, "transform %zu, entry %zu is not finite", k / 12, k % 12);
+    const int rc = enter(h);
+    if (rc) return rc;
+    h->input_xf.assign(T, T + floats);  // (d_xf keeps what the last call ran with until the next estimate call: its lazy gathers use that)
+    return PWPP_OK;
+}
+
+int pwpp_transform_points(const float T[12], const float *xyz, int64_t m, float *out) {
+    if (m < 0 || !T || (m > 0 && (!xyz || !out))) return fail(PWPP_E_ARG, "null argument or negative count");
+    for (int64_t i = 0; i < m; ++i) {
+        float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+        pwpp_transform_point(T, x, y, z);
+        out[3 * i] = x;
+        out[3 * i + 1] = y;
+        out[3 * i + 2] = z;
+    }
+    return PWPP_OK;
+}
 
 int pwpp_get_labels(pwpp_handle *h, int frame, uint8_t *out) {
     return copy_output(h, kLabels, frame, false, out, h ? h->d_labels.p : nullptr, 1);

@@ -34,7 +34,8 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
     return v;
 }
 
-__device__ __forceinline__ void load_point(const PwppFrameDesc &fd, int i, float &x, float &y, float &z, float &w) {
+// the floats of point i as they lie in the input (the sensor's frame)
+__device__ __forceinline__ void load_point_raw(const PwppFrameDesc &fd, int i, float &x, float &y, float &z, float &w) {
     if (fd.layout == PWPP_LAYOUT_ROW_MAJOR) {
         if (fd.cols == 4) {
             const float4 v = reinterpret_cast<const float4 *>(fd.pts)[i];  // 16 B/lane, 1 KiB per wave instruction
@@ -64,6 +65,35 @@ __device__ __forceinline__ void load_point(const PwppFrameDesc &fd, int i, float
         z = fd.pts[2 * n + i];
         w = fd.cols == 4 ? fd.pts[3 * n + i] : 0.0f;
     }
+}
+// The frame's input transform (pwpp_set_input_transforms) on a point just loaded: a wave-uniform branch, and behind it the
+// twelve operands.  UNIFORM (the binning kernels, whose frame is a function of the workgroup): read through the constant address
+// space -- scalar loads into SGPRs whatever the kernel has stored before (the matrix was written before the launch, nothing on the
+// device writes it).  Otherwise (the rare re-fetch of a stripped point's height in k_emit / k_pp_patch, the getters' gather): plain
+// loads of the rows that are used, so the kernels keep their registers.
+template <bool UNIFORM = false>
+__device__ __forceinline__ void transform_point(const PwppFrameDesc &fd, float &x, float &y, float &z) {
+    if (fd.xf) {
+        float T[12];
+        if (UNIFORM) {
+            typedef const float __attribute__((address_space(4))) *const_f32;
+            const const_f32 m = (const_f32)fd.xf;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = m[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = fd.xf[k];
+        }
+        pwpp_transform_point(T, x, y, z);
+    }
+}
+// Point i of the frame as the pipeline sees it: EVERY kernel that looks at an input coordinate comes through here (or through the
+// two halves above, k_czm_bin_scatter: all its loads first, then the arithmetic), so the binning, the reference-order keys, the
+// point planes and the xyz getters agree on the transformed coordinates bit for bit.  The intensity passes through untouched.
+template <bool UNIFORM = false>
+__device__ __forceinline__ void load_point(const PwppFrameDesc &fd, int i, float &x, float &y, float &z, float &w) {
+    load_point_raw(fd, i, x, y, z, w);
+    transform_point<UNIFORM>(fd, x, y, z);
 }
 
 __device__ __forceinline__ double i128_to_double(__int128 v) {  // one rounding, to nearest even

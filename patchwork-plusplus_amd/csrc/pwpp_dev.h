@@ -89,7 +89,22 @@ struct PwppFrameDesc {
     int64_t mbase;     // first byte of this frame in the membership plane (= sbase / 8 + 2 * PWPP_MEMBER_PAD * parts * frame index)
     int64_t sbase;     // first slot of this frame in the part-ordered buffers (sorted_*): compact on the two-pass
                        // path, frame * slots_per_frame on the one-pass path (see cap_off)
+    const float *xf;   // the frame's input transform [R | t], 3 x 4 row-major, in device memory (pwpp_set_input_transforms); null = none.
+                       // The POINTER travels with the descriptor, so whatever receives one -- the binning kernels, a redo, the fix-up,
+                       // the lazy gathers -- sees the same frame; the twelve floats are fetched behind the branch that needs them
+                       // (inside the descriptor they cost k_czm_bin a wave of occupancy and the ordered k_emit 16 bytes of scratch:
+                       // profiles/input_transform_resources.txt)
 };
+
+// The input transform, in the operations include/pwpp.h promises (-ffp-contract=off: no FMA is formed, on either side):
+//   x' = fl32(fl32(fl32(fl32(r00 * x) + fl32(r01 * y)) + fl32(r02 * z)) + t0),   y', z' alike with rows 1 and 2
+// One function for the kernels (load_point, pwpp_common.hpp) and for the host's pwpp_transform_points.
+__host__ __device__ inline void pwpp_transform_point(const float *T, float &x, float &y, float &z) {
+    const float a = x, b = y, c = z;
+    x = T[0] * a + T[1] * b + T[2] * c + T[3];
+    y = T[4] * a + T[5] * b + T[6] * c + T[7];
+    z = T[8] * a + T[9] * b + T[10] * c + T[11];
+}
 
 // Bytes of one row of pwpp_get_*_records: a matrix row is its `cols` floats (gathered from the planes of a column-major
 // matrix), a PWPP_LAYOUT_FIELDS point its whole record of `step` bytes.  2 = PWPP_LAYOUT_FIELDS (include/pwpp.h).

@@ -249,7 +249,7 @@ __device__ __forceinline__ unsigned part_of(const PwppDevParams &P, unsigned cod
     return code < B ? 2u * code : code + B;
 }
 
-__global__ __launch_bounds__(kBlock) void k_czm_bin(PwppBatch Bt) {
+__global__ __launch_bounds__(kBlock, 8) void k_czm_bin(PwppBatch Bt) {  // (eight workgroups per CU as before the input transform: its two SGPRs more would otherwise cost a wave per SIMD)
     extern __shared__ unsigned s_dyn[];  // [parts of this model] -- sized at launch (binning_lds_bytes): 4 KB for the default
     unsigned *s_hist = s_dyn;            // model instead of the 16 KB of the largest one
     __shared__ float4 s_zt[8];
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_czm_bin_scatter(PwppBatch Bt, int
     for (int j = 0; j < kPer; ++j) {
         const int i = first + j * kBlock + threadIdx.x;
         px[j] = py[j] = pz[j] = pw[j] = 0.0f;
-        if (i < fd.n) load_point(fd, i, px[j], py[j], pz[j], pw[j]);
+        if (i < fd.n) load_point_raw(fd, i, px[j], py[j], pz[j], pw[j]);  // (transformed below, once all four loads are on their way)
     }
     for (int b = threadIdx.x; b < NB; b += kBlock) s_cnt[b] = 0;
     for (int b0 = 0; b0 <= NB; b0 += 4 * kBlock) {  // (four table entries per thread in flight: not one L2 round trip per iteration)
@@ -661,6 +661,10 @@ __global__ __launch_bounds__(kBlock, 8) void k_czm_bin_scatter(PwppBatch Bt, int
     const float rnr_z_guard = (float)(-sensor_height - 0.8) + 1e-3f;
     const float zs = hi_split_z(P, sensor_height);
     unsigned dropped = 0;
+    if (fd.xf) {  // the second half of load_point (lanes beyond the frame transform zeros that nobody reads)
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) transform_point<true>(fd, px[j], py[j], pz[j]);
+    }
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
         const int i = first + j * kBlock + threadIdx.x;

@@ -1,5 +1,6 @@
 /* capi_demo.c -- the C-ABI from plain C99 (what a cgo / JNI / ctypes-style binding sees): one KITTI-layout
- * .bin frame through pwpp_estimate_ground(), counts and the first indices printed.
+ * .bin frame through pwpp_estimate_ground(), counts and the first indices printed; then the frame as a tilted sensor delivers it
+ * (pwpp_set_input_transforms), and batches in flight.
  *   gcc -std=c99 -Wall -Werror -I ../../include capi_demo.c -o capi_demo -L ../lib -lpwpp_hip -Wl,-rpath,'$ORIGIN/../lib'
  *   ./capi_demo <frame.bin>
  * Mirrors the read loop of the reference demo (cpp/patchworkpp/examples/demo_visualize.cpp:18-34) and its
@@ -60,6 +61,42 @@ int main(int argc, char **argv) {
            (int)n_patches, pwpp_get_height(h), pwpp_get_time_us(h));
     free(ground);
     pwpp_destroy(h);
+
+    /* A tilted sensor (pwpp_set_input_transforms, no reference counterpart): the same frame as a LiDAR pitched by 5 degrees and
+     * mounted 0.2 m higher would deliver it, and the matrix [R | t] that levels it again handed to the library, which applies it
+     * while it bins the points -- no transformed copy of the cloud.  pwpp_transform_points (host only) is the same arithmetic: here
+     * it builds the tilted cloud with the inverse map; a caller uses it to carry positions into the levelled frame. */
+    {
+        const float c5 = 0.9961947f, s5 = 0.08715574f;  /* cos, sin of 5 degrees */
+        const float level[12] = {c5, 0.0f, s5, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, -s5, 0.0f, c5, 0.2f};     /* Ry(5 deg), then up 0.2 m */
+        const float tilt[12] = {c5, 0.0f, -s5, 0.2f * s5, 0.0f, 1.0f, 0.0f, 0.0f, s5, 0.0f, c5, -0.2f * c5}; /* its inverse */
+        float *xyz = (float *)malloc((size_t)n * 3 * sizeof(float)), *tilted = (float *)malloc((size_t)n * 4 * sizeof(float));
+        pwpp_handle *h2 = NULL;
+        int32_t g2 = 0, ng2 = 0, np2 = 0;
+        int i;
+        if (!xyz || !tilted) return 1;
+        for (i = 0; i < n; ++i) {
+            xyz[3 * i] = pts[4 * i];
+            xyz[3 * i + 1] = pts[4 * i + 1];
+            xyz[3 * i + 2] = pts[4 * i + 2];
+        }
+        if (pwpp_transform_points(tilt, xyz, n, xyz) != PWPP_OK) return fail("pwpp_transform_points");
+        for (i = 0; i < n; ++i) {
+            tilted[4 * i] = xyz[3 * i];
+            tilted[4 * i + 1] = xyz[3 * i + 1];
+            tilted[4 * i + 2] = xyz[3 * i + 2];
+            tilted[4 * i + 3] = pts[4 * i + 3];
+        }
+        if (pwpp_create(&params, 0, &h2) != PWPP_OK) return fail("pwpp_create");
+        if (pwpp_set_input_transforms(h2, level, 1) != PWPP_OK) return fail("pwpp_set_input_transforms");
+        if (pwpp_estimate_ground(h2, tilted, n, 4, PWPP_LAYOUT_ROW_MAJOR) != PWPP_OK) return fail("pwpp_estimate_ground (tilted)");
+        if (pwpp_get_counts(h2, 0, &g2, &ng2, &np2) != PWPP_OK) return fail("pwpp_get_counts");
+        printf("tilted sensor, levelled while binning: ground %d nonground %d patches %d (level frame: %d / %d / %d)\n", (int)g2, (int)ng2,
+               (int)np2, (int)n_ground, (int)n_nonground, (int)n_patches);
+        pwpp_destroy(h2);
+        free(xyz);
+        free(tilted);
+    }
 
     /* Batches in flight (pwpp_pipe_*, no reference counterpart): four batches of three independent frames through a pipe of depth 2.
      * From pageable host memory a submit returns with the batch done (PWPP_MEM_HOST); device or pinned buffers make it asynchronous

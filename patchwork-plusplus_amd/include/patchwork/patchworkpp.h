@@ -296,6 +296,11 @@ public:
     // extension: the frames estimated afterwards also leave the whole rows of their ground / non-ground points on the device
     // (pwpp.h, pwpp_set_point_records); getGroundPoints / getNongroundPoints work either way, and gather on demand without it
     void setPointRecords(bool on) { check(pwpp_set_point_records(h_, on ? 1 : 0)); }
+    // extension: an affine transform [R | t] (3 x 4 row-major) applied to every point of the frames estimated afterwards, while
+    // they are binned (pwpp.h, pwpp_set_input_transforms): a tilted mount, millimetres, an IMU's levelling.  getGround() /
+    // getNonground(), centers, normals and queryGround() then live in the transformed frame; getGroundPoints() /
+    // getNongroundPoints() stay the input rows.  nullptr turns it off.
+    void setInputTransform(const float T[12]) { check(pwpp_set_input_transforms(h_, T, T ? 1 : 0)); }
     // getGround() / getNonground() with every column of the input: (count, cols) floats, rows aligned with the index getters
 #ifdef PWPP_HAVE_EIGEN
     Eigen::MatrixXf getGroundPoints() { return to_eigen(points(true)); }

@@ -162,6 +162,9 @@ def load():
         if hasattr(L, "pwpp_query_ground"):  # (as above: an older build has no ground queries)
             L.pwpp_query_ground.argtypes = [vp, vp, vp, ctypes.c_int64, ci, vp]
             L.pwpp_rasterize_ground.argtypes = [vp, ctypes.POINTER(GroundGrid), ci, ci, ci, vp, vp]
+        if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
+            L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
+            L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
@@ -197,6 +200,34 @@ def default_params():
 
 def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _transforms(T):
+    """(k, 12) float32 from (12,), (3, 4), (k, 12) or (k, 3, 4)."""
+    T = np.asarray(T, dtype=np.float32)
+    if T.shape in ((12,), (3, 4)):
+        T = T.reshape(1, 12)
+    elif (T.ndim == 2 and T.shape[1] == 12) or (T.ndim == 3 and T.shape[1:] == (3, 4)):
+        T = T.reshape(T.shape[0], 12)
+    else:
+        raise ValueError("transforms of shape (12,), (3, 4), (k, 12) or (k, 3, 4) expected, got %s" % (T.shape,))
+    return np.ascontiguousarray(T)
+
+
+def transform_points(T, xyz):
+    """pwpp_transform_points: xyz (m, 3) float32 through T = [R | t] ((12,) or (3, 4)) with the library's own rounding --
+    fl(fl(fl(fl(r0 x) + fl(r1 y)) + fl(r2 z)) + t) per row.  Host only; no GPU needed."""
+    T = _transforms(T)
+    if T.shape[0] != 1:
+        raise ValueError("one transform expected")
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("xyz: an (m, 3) array expected")
+    out = np.empty_like(xyz)
+    L = load()
+    if L.pwpp_transform_points(_vp(T), _vp(xyz) if xyz.size else None, xyz.shape[0], _vp(out) if out.size else None) < 0:
+        raise PwppError(L.pwpp_last_error().decode())
+    return out
 
 
 class Handle:
@@ -564,6 +595,16 @@ class Handle:
         device, row for row behind the index lists (include/pwpp.h)."""
         self._check(self._L.pwpp_set_point_records(self._h, 1 if on else 0))
 
+    def set_input_transforms(self, T):
+        """An affine transform [R | t] per frame, applied to the input while it is binned (include/pwpp.h): T of shape (12,) or
+        (3, 4) applies to every frame of every later call, (k, 12) or (k, 3, 4) gives frame (stream) i its own and needs calls
+        of exactly k frames.  None turns it off.  Copied here; sticky."""
+        if T is None:
+            self._check(self._L.pwpp_set_input_transforms(self._h, None, 0))
+            return
+        T = _transforms(T)
+        self._check(self._L.pwpp_set_input_transforms(self._h, _vp(T) if T.size else None, T.shape[0]))
+
     @property
     def record_bytes(self):
         """Bytes per row of the last call's records: cols * 4 for a matrix, point_step for a fields layout."""
@@ -724,6 +765,11 @@ class Pipe:
         if rc < 0:
             raise PwppError("pwpp error %d: %s" % (rc, self._L.pwpp_last_error().decode()))
         return self._view(holder)
+
+    def set_input_transforms(self, T):
+        """Handle.set_input_transforms on every handle of the pipe (each batch submitted afterwards runs with it)."""
+        for i in range(self.depth):
+            self.handle(i).set_input_transforms(T)
 
     def drain(self):
         rc = self._L.pwpp_pipe_drain(self._p)

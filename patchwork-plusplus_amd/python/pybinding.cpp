@@ -66,6 +66,18 @@ py::array query_ground(PatchWorkpp &self, py::array positions) {
     return out;
 }
 
+// setInputTransform: (3, 4) = [R | t], or (4, 4) homogeneous with the last row 0 0 0 1; None turns the transform off
+void set_input_transform(PatchWorkpp &self, py::object T) {
+    if (T.is_none()) return self.setInputTransform(nullptr);
+    py::array_t<float, py::array::c_style | py::array::forcecast> a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(T);
+    if (!a || a.ndim() != 2 || a.shape(1) != 4 || (a.shape(0) != 3 && a.shape(0) != 4))
+        throw py::value_error("setInputTransform expects a (3, 4) or (4, 4) array");
+    const float *v = a.data();
+    if (a.shape(0) == 4 && !(v[12] == 0.0f && v[13] == 0.0f && v[14] == 0.0f && v[15] == 1.0f))
+        throw py::value_error("setInputTransform: the last row of a (4, 4) transform must be 0 0 0 1");
+    self.setInputTransform(v);  // (the first twelve floats of either shape)
+}
+
 void estimate_ground(PatchWorkpp &self, py::array cloud) {
     if (cloud.ndim() != 2) throw py::value_error("estimateGround expects a 2-D array (N, 3|4)");
     // F-contiguous float32 is consumed as column-major (the layout Eigen::MatrixXf would have),
@@ -139,6 +151,7 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def("getPointPatches", [](PatchWorkpp &s) { return to_numpy(s.pointPatchList()); })
         .def("getPointDistances", [](PatchWorkpp &s) { return to_numpy(s.pointDistanceList()); })
         .def("setPointRecords", &PatchWorkpp::setPointRecords, py::arg("on"))
+        .def("setInputTransform", &set_input_transform, py::arg("T").none(true))
         .def("queryGround", &query_ground, py::arg("positions"))
         .def("getElevationMap",
              [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, bool ground_only) {

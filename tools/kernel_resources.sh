@@ -15,5 +15,5 @@ for l in sys.stdin:
 for r in rows:
     n=subprocess.run(["c++filt",r["name"]],capture_output=True,text=True).stdout.strip()
     n=re.sub(r"\(anonymous namespace\)::","",n).split("(")[0].replace("void ","")
-    print("%-28s VGPR %3s AGPR %3s spillV %3s spillS %3s scratch %4s occ %s LDS %s"%(n,r.get("VGPRs"),r.get("AGPRs"),r.get("VGPRs Spill"),r.get("SGPRs Spill"),r.get("ScratchSize [bytes/lane]"),r.get("Occupancy [waves/SIMD]"),r.get("LDS Size [bytes/block]")))
+    print("%-28s VGPR %3s AGPR %3s SGPR %3s spillV %3s spillS %3s scratch %4s occ %s LDS %s"%(n,r.get("VGPRs"),r.get("AGPRs"),r.get("TotalSGPRs"),r.get("VGPRs Spill"),r.get("SGPRs Spill"),r.get("ScratchSize [bytes/lane]"),r.get("Occupancy [waves/SIMD]"),r.get("LDS Size [bytes/block]")))
 '
