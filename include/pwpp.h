@@ -428,6 +428,49 @@ enum { PWPP_GRID_GROUND_ONLY = 1 };
 PWPP_API int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem,
                                    float *height /* [frames][ny][nx] */, int32_t *patch /* same shape, may be NULL */);
 
+/* ---- the non-ground points as an obstacle grid (pwpp_rasterize_obstacles) --------------------------------------------------------
+ * The other half of a 2.5-D map on the grid of pwpp_rasterize_ground: per cell how many non-ground returns, how tall the tallest,
+ * and how many nobody can vouch for -- what a costmap, an occupancy grid or a BEV detector builds next, without the lists or the
+ * coordinates of a batch leaving the device.
+ *   When, mem Exactly as pwpp_rasterize_ground: answers from the handle's LAST estimate call of any kind (a pipe's handles
+ *             included), enters like the getters (the call in flight lands first, a frame that awaits the fix-up or a redo is
+ *             finished first), PWPP_E_STATE before any call and after pwpp_trim_workspace.  PWPP_MEM_HOST: the images are host
+ *             memory, staged through the ground queries' buffer; synchronous.  PWPP_MEM_DEVICE: device memory (4-byte aligned, no
+ *             more), enqueued on the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.  A pure
+ *             read: no result, state or timing of the estimate path changes, and nothing is allocated beyond what the ground
+ *             queries hold.
+ *   points    The points the frame's non-ground index list names (n_nonground entries, in whatever output order the handle has),
+ *             read from the frame's INPUT as the pipeline reads it: with input transforms set, the transformed coordinates.  The
+ *             lifetime rule of pwpp_get_nonground_xyz applies: after a PWPP_MEM_DEVICE estimate call the caller's buffer must still
+ *             hold the frame when this call runs.
+ *   reference The sample pwpp_query_ground gives for the point's own (x, y, z): position-query semantics, unchanged.  Consequence:
+ *             an RNR point is in the non-ground list and queries into its bin's patch with a large negative distance (RNR only
+ *             takes points more than 0.8 m below the sensor's ground level): a band with h_min above about -0.8 m leaves it out.
+ *             A point has NO reference where that sample has patch == -1 -- outside (min_range, max_range], a bin with fewer than
+ *             num_min_pts points, a non-finite x or y -- and, with PWPP_GRID_GROUND_ONLY in g->flags, also where its patch was
+ *             decided NOT_UPRIGHT, HEADING or TGR_REJECT: the three decisions the ground raster blanks.
+ *   height    hgt = that sample's distance: the point-planes formula against the patch's REPORTED plane, the number
+ *             pwpp_get_point_distances has for a point that owns its patch.  A point is COUNTED iff it has a reference and
+ *             h_min <= hgt && hgt <= h_max as float comparisons (a NaN height is not counted).  Infinite bounds are legal.
+ *   cell      In double on the float coordinates, one subtraction and one IEEE division each, no reciprocal, no FMA:
+ *                 u = ((double)x - x0) / cell,   ix = (int)floor(u),   kept iff 0 <= u && u < nx;     v, iy alike with y, y0, ny
+ *             A point outside the grid, or whose u or v is a NaN, touches no image.
+ *   images    count[f][iy][ix]  the counted points of the cell;
+ *             unref[f][iy][ix]  the points of the cell without a reference (may be NULL);
+ *             top[f][iy][ix]    the largest hgt among the counted points, in the total order in which -0.0 < +0.0; the quiet NaN
+ *                               where count is 0 (may be NULL);
+ *             for the frames frame_first .. frame_first + frames - 1 of the last call.  Integer adds and an integer-keyed maximum
+ *             only: all three are functions of the input alone -- bit-reproducible from call to call, independent of the output
+ *             order, the schedule and the memory kind of the estimate call.
+ *   errors    PWPP_E_ARG: everything pwpp_rasterize_ground rejects of a grid and a frame range (nx * ny * frames beyond 2^31
+ *             included), a null count, flags other than 0 or PWPP_GRID_GROUND_ONLY, a NaN h_min or h_max, h_min > h_max. */
+#define PWPP_HAS_OBSTACLE_GRID 1
+PWPP_API int pwpp_rasterize_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                      int frame_first, int frames, int mem,
+                                      int32_t *count /* [frames][ny][nx] */,
+                                      float   *top   /* same shape, may be NULL */,
+                                      int32_t *unref /* same shape, may be NULL */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU

@@ -35,6 +35,9 @@ extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, int rows_val
                                         hipStream_t stream);
 extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_valid, const PwppGroundGrid *grid, int frame_first, int frames,
                                          float *height, int32_t *patch, hipStream_t stream);
+extern "C" int pwpp_launch_obstacle_raster(const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
+                                           const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground,
+                                           float h_min, float h_max, int32_t *count, float *top, int32_t *unref, hipStream_t stream);
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
 static_assert(sizeof(pwpp_ground_sample) == sizeof(PwppGroundSample) && sizeof(pwpp_ground_sample) == 16, "pwpp_ground_sample must mirror PwppGroundSample");
@@ -2253,9 +2256,10 @@ int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, in
     return PWPP_OK;
 }
 
-int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, float *height, int32_t *patch) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    if (!g || !height) return fail(PWPP_E_ARG, "null %s", g ? "height image" : "grid");
+namespace {
+// What both rasters check of their grid and frame range, in this order, after the null checks of their own; lands the call in
+// flight.  `cells`: nx * ny * frames.
+int ground_grid_args(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, size_t &cells) {
     if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);
     if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
         return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
@@ -2266,7 +2270,17 @@ int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_f
         return fail(PWPP_E_ARG, "frames [%d, %d + %d) outside the last call's [0, %d)", frame_first, frame_first, frames, h->frames);
     const int64_t per_frame = (int64_t)g->nx * (int64_t)g->ny;  // (< 2^62)
     if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", g->nx, g->ny, frames);
-    const size_t cells = (size_t)per_frame * (size_t)frames;
+    cells = (size_t)per_frame * (size_t)frames;
+    return PWPP_OK;
+}
+}  // namespace
+
+int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, float *height, int32_t *patch) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !height) return fail(PWPP_E_ARG, "null %s", g ? "height image" : "grid");
+    size_t cells = 0;
+    int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
+    if (rc) return rc;
     PwppGroundView v;
     PwppGroundGrid grid;
     std::memcpy(&grid, g, sizeof(grid));
@@ -2284,6 +2298,52 @@ int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_f
     if (mem == PWPP_MEM_HOST) {
         HIPCHK(hipMemcpyAsync(height, d_height, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         if (patch) HIPCHK(hipMemcpyAsync(patch, d_patch, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        h->ground_query_queued = true;
+    }
+    return PWPP_OK;
+}
+
+// The non-ground points of the last call per cell of the grid.  Everything the kernel reads is on the device since the call: the
+// frame descriptors (d_frames), this call's copy of the frame counters (d_results), the lists (d_out) -- and the INPUT, which after
+// a PWPP_MEM_DEVICE call is the caller's buffer (the lifetime rule of pwpp_get_nonground_xyz).
+int pwpp_rasterize_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem,
+                             int32_t *count, float *top, int32_t *unref) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !count) return fail(PWPP_E_ARG, "null %s", g ? "count image" : "grid");
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
+    size_t cells = 0;
+    int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
+    if (rc) return rc;
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    int32_t *d_count = count, *d_unref = unref;
+    float *d_top = top;
+    if (mem == PWPP_MEM_HOST) {  // count, then top, then unref (16-byte aligned when cells is a multiple of 4; the kernels do not need it)
+        if ((rc = h->d_ground_stage.ensure(cells * (size_t)(1 + (top ? 1 : 0) + (unref ? 1 : 0))))) return rc;
+        uint32_t *w = h->d_ground_stage.p;
+        d_count = reinterpret_cast<int32_t *>(w);
+        d_top = top ? reinterpret_cast<float *>(w + cells) : nullptr;
+        d_unref = unref ? reinterpret_cast<int32_t *>(w + cells * (size_t)(top ? 2 : 1)) : nullptr;
+    }
+    if ((rc = ground_view(h, v))) return rc;
+    int max_nonground = 0;
+    for (int f = frame_first; f < frame_first + frames; ++f) {
+        const int nn = h->h_results.p[f].n_nonground;
+        max_nonground = nn > max_nonground ? nn : max_nonground;
+    }
+    const PwppFrameResult *results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
+    const int lrc = pwpp_launch_obstacle_raster(&v, h->ground_rows_valid, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground,
+                                                h_min, h_max, d_count, d_top, d_unref, h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    h->ground_rows_valid = true;
+    if (mem == PWPP_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(count, d_count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (top) HIPCHK(hipMemcpyAsync(top, d_top, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (unref) HIPCHK(hipMemcpyAsync(unref, d_unref, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     } else {
         h->ground_query_queued = true;

@@ -20,7 +20,8 @@
 //   K9  k_pp_*             optional: per-point patch row and signed distance to the patch's plane  (ref :551-554)
 //   K10 k_point_records    optional: the whole input records of the listed points, row for row behind the lists  (ref :8-16)
 // After a call, on demand: k_ground_rows / k_ground_query / k_ground_raster read the fitted planes at positions that are not
-// cloud points (pwpp_query_ground, pwpp_rasterize_ground); they write nothing the pipeline reads.
+// cloud points (pwpp_query_ground, pwpp_rasterize_ground); k_obstacle_fill / k_obstacle_raster / k_obstacle_top count the non-ground
+// points per cell of the same grid (pwpp_rasterize_obstacles).  They write nothing the pipeline reads.
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -3002,6 +3003,117 @@ __global__ __launch_bounds__(kGqBlock) void k_ground_raster(PwppGroundView Q, Pw
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Obstacle grid (pwpp_rasterize_obstacles): the non-ground points of the LAST call, counted per cell of a pwpp_ground_grid
+// ------------------------------------------------------------------------------------------
+// The other half of a 2.5-D map, and a post-call read like the ground queries: a frame's non-ground list, the input behind
+// load_point, and for every point the sample pwpp_query_ground gives for its own (x, y, z).  Three images per frame:
+//   count  points with a reference whose height sample.distance lies in [h_min, h_max]
+//   top    the largest such height -- an integer atomicMax on a monotone key of the float, so that the result is a function of
+//          the SET of points (an order in which -0.0 < +0.0, no float atomics): key = bits ^ (sign ? 0xffffffff : 0x80000000),
+//          0 = empty (it would be the key of the NaN 0xffffffff, and a NaN height is never counted)
+//   unref  points without a reference: sample.patch == -1, or (PWPP_GRID_GROUND_ONLY) a patch the ground raster blanks
+// k_obstacle_fill zeroes the images, k_obstacle_raster adds the points, k_obstacle_top turns the keys into floats in place.
+constexpr int kObBlock = 256;
+
+// Word t of a quad walk over `words` 4-byte words at `p` (4-byte aligned, no more): quad t starts at p0 = 4 t - (words of p past
+// a 16-byte boundary), so p + p0 is 16-byte aligned.  True: the whole quad lies inside the array.
+__device__ __forceinline__ bool quad_inside(const void *p, int64_t t, int64_t words, int64_t &p0) {
+    p0 = 4 * t - (int64_t)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u);
+    return p0 >= 0 && p0 + 4 <= words;
+}
+
+__device__ __forceinline__ void zero_quad(uint32_t *p, int64_t t, int64_t words) {
+    int64_t p0;
+    if (quad_inside(p, t, words, p0)) {
+        *reinterpret_cast<uint4 *>(p + p0) = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (int k = 0; k < 4; ++k)
+            if (p0 + k >= 0 && p0 + k < words) p[p0 + k] = 0u;
+    }
+}
+
+// count = unref = 0, top = empty: 16 bytes per lane and image, the words before the first and behind the last whole quad one by
+// one (a caller's device pointers are 4-byte aligned only).  Lanes 0 .. cells / 4 + 1: a misaligned image spans one quad more.
+__global__ __launch_bounds__(kObBlock) void k_obstacle_fill(int64_t cells, uint32_t *count, uint32_t *top, uint32_t *unref) {
+    const int64_t t = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    if (4 * t >= cells + 3) return;
+    zero_quad(count, t, cells);
+    if (top) zero_quad(top, t, cells);
+    if (unref) zero_quad(unref, t, cells);
+}
+
+__device__ __forceinline__ uint32_t height_key(float h) {
+    const uint32_t b = __float_as_uint(h);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float height_of_key(uint32_t k) {
+    return k == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
+// the cell of a coordinate: u = (c - c0) / cell in double (one subtraction, one IEEE division), kept iff 0 <= u < n (NaN: not)
+__device__ __forceinline__ bool grid_cell(float c, double c0, double cell, int n, int &i) {
+    const double u = ((double)c - c0) / cell;
+    if (!(u >= 0.0 && u < (double)n)) return false;
+    i = (int)floor(u);
+    return true;
+}
+
+// grid (tiles of kObBlock entries over the longest non-ground list of the range, frames): one lane per list entry, one coalesced
+// load of the indices.  Consecutive entries mostly belong to one patch, so a wave's atomics hit few cells: plain global atomics
+// (DESIGN.md section K has what a combine of equal cells would have to beat).  An index that is not a point of the frame (a frame
+// whose lists are unwritten: k_label_scatter) is dropped; frame, bin, row and cell are checked before an address is formed.
+__global__ __launch_bounds__(kObBlock) void k_obstacle_raster(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
+                                                              const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
+                                                              int32_t *count, uint32_t *top, int32_t *unref) {
+    __shared__ float4 s_zt[8];
+    fill_zone_table(Q.P, s_zt);
+    __syncthreads();
+    const int fr = blockIdx.y, f = frame_first + fr;  // (fr: relative to frame_first, the image's frame)
+    if ((unsigned)f >= (unsigned)Q.num_frames) return;
+    const PwppFrameDesc fd = frames[f];
+    const PwppFrameResult r = results[f];
+    const int64_t n = fd.n;  // (the two counts clamped to the frame: label_counts)
+    const int64_t ng = r.n_ground < 0 ? 0 : (r.n_ground > n ? n : (int64_t)r.n_ground);
+    const int64_t nn = r.n_nonground < 0 ? 0 : (r.n_nonground > n - ng ? n - ng : (int64_t)r.n_nonground);
+    const int64_t e = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    if (e >= nn) return;
+    const int i = out_idx[fd.base + ng + e];
+    if ((unsigned)i >= (unsigned)fd.n) return;
+    float x, y, z, w;
+    load_point<true>(fd, i, x, y, z, w);
+    int ix, iy;
+    if (!grid_cell(x, G.x0, G.cell, G.nx, ix) || !grid_cell(y, G.y0, G.cell, G.ny, iy)) return;
+    unsigned code = 0;
+    if ((Q.debug & 16) || !bin_code_fast(Q.P, s_zt, x, y, code)) code = bin_code_exact(Q.P, x, y);
+    const PwppGroundSample s = ground_sample(Q, f, code, x, y, z);
+    const size_t o = ((size_t)fr * (size_t)G.ny + (size_t)iy) * (size_t)G.nx + (size_t)ix;
+    const bool hidden = (G.flags & PWPP_GRID_GROUND_ONLY) &&
+                        (s.decision == PWPP_DEC_NOT_UPRIGHT || s.decision == PWPP_DEC_HEADING || s.decision == PWPP_DEC_TGR_REJECT);
+    if (s.patch < 0 || hidden) {
+        if (unref) atomicAdd(unref + o, 1);
+        return;
+    }
+    const float hgt = s.distance;
+    if (!(h_min <= hgt && hgt <= h_max)) return;  // (a NaN height fails)
+    atomicAdd(count + o, 1);
+    if (top) atomicMax(top + o, height_key(hgt));
+}
+
+// the keys of `top` as floats, in place: empty = the quiet NaN.  Quads as in k_obstacle_fill.
+__global__ __launch_bounds__(kObBlock) void k_obstacle_top(int64_t cells, uint32_t *top) {
+    const int64_t t = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    if (4 * t >= cells + 3) return;
+    int64_t p0;
+    if (quad_inside(top, t, cells, p0)) {
+        const uint4 k = *reinterpret_cast<const uint4 *>(top + p0);
+        *reinterpret_cast<float4 *>(top + p0) = make_float4(height_of_key(k.x), height_of_key(k.y), height_of_key(k.z), height_of_key(k.w));
+    } else {
+        for (int j = 0; j < 4; ++j)
+            if (p0 + j >= 0 && p0 + j < cells) top[p0 + j] = __float_as_uint(height_of_key(top[p0 + j]));
+    }
+}
+
 }  // namespace
 
 // the records of the launch's frames, behind their final lists
@@ -3065,6 +3177,24 @@ extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_va
     if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
     const dim3 g((unsigned)((grid->nx + kGqBlock - 1) / kGqBlock), (unsigned)(grid->ny < 65535 ? grid->ny : 65535), (unsigned)frames);
     hipLaunchKernelGGL(k_ground_raster, g, dim3(kGqBlock), 0, stream, *view, *grid, frame_first, height, patch);
+    return (int)hipGetLastError();
+}
+
+// pwpp_rasterize_obstacles: fill, points, keys -> floats.  `descs`, `results`, `out_idx`: the last call's frame descriptors, frame
+// counters and index lists on the device; max_nonground: the longest non-ground list of the frame range (0: only the fill runs).
+extern "C" int pwpp_launch_obstacle_raster(const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
+                                           const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground,
+                                           float h_min, float h_max, int32_t *count, float *top, int32_t *unref, hipStream_t stream) {
+    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+    const int64_t cells = (int64_t)grid->nx * (int64_t)grid->ny * (int64_t)frames;  // (<= 2^31: checked by the caller)
+    const unsigned quads = (unsigned)(((cells + 2) / 4 + 1 + kObBlock - 1) / kObBlock);
+    uint32_t *keys = reinterpret_cast<uint32_t *>(top);
+    hipLaunchKernelGGL(k_obstacle_fill, dim3(quads), dim3(kObBlock), 0, stream, cells, reinterpret_cast<uint32_t *>(count), keys,
+                       reinterpret_cast<uint32_t *>(unref));
+    if (max_nonground > 0)
+        hipLaunchKernelGGL(k_obstacle_raster, dim3((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames), dim3(kObBlock), 0, stream,
+                           *view, descs, results, out_idx, *grid, frame_first, h_min, h_max, count, keys, unref);
+    if (top) hipLaunchKernelGGL(k_obstacle_top, dim3(quads), dim3(kObBlock), 0, stream, cells, keys);
     return (int)hipGetLastError();
 }
 

@@ -329,6 +329,26 @@ public:
         check(pwpp_rasterize_ground(h_, &g, 0, 1, PWPP_MEM_HOST, img.rows() > 0 && img.cols() > 0 ? img.data() : &none, nullptr));
         return img;
     }
+    // ... and the other half of a 2.5-D map on the same grid (pwpp_rasterize_obstacles): per cell the number of non-ground points
+    // whose height over their patch's plane lies in [h_min, h_max], and that largest height (NaN where the count is 0)
+    struct ObstacleMap {
+        std::vector<int32_t> count;  // ny x nx, row-major: row iy, column ix
+        Points top;                  // (ny, nx)
+    };
+    ObstacleMap obstacleMapRows(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        ObstacleMap m;
+        m.top = Points(ny > 0 ? ny : 0, nx > 0 ? nx : 0);
+        m.count.assign((size_t)m.top.rows() * (size_t)m.top.cols(), 0);
+        int32_t none_c = 0;
+        float none_t = 0.0f;
+        const bool any = !m.count.empty();
+        check(pwpp_rasterize_obstacles(h_, &g, h_min, h_max, 0, 1, PWPP_MEM_HOST, any ? m.count.data() : &none_c, any ? m.top.data() : &none_t, nullptr));
+        return m;
+    }
+    ObstacleMap getObstacleMap(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, bool ground_only = false) {
+        return obstacleMapRows(x0, y0, cell, nx, ny, h_min, h_max, ground_only);
+    }
 #ifdef PWPP_HAVE_EIGEN
     std::vector<pwpp_ground_sample> queryGround(const Eigen::MatrixX3f &positions) {
         std::vector<float> xyz((size_t)positions.rows() * 3);

@@ -162,6 +162,8 @@ def load():
         if hasattr(L, "pwpp_query_ground"):  # (as above: an older build has no ground queries)
             L.pwpp_query_ground.argtypes = [vp, vp, vp, ctypes.c_int64, ci, vp]
             L.pwpp_rasterize_ground.argtypes = [vp, ctypes.POINTER(GroundGrid), ci, ci, ci, vp, vp]
+        if hasattr(L, "pwpp_rasterize_obstacles"):  # (as above: an older build has no obstacle grid)
+            L.pwpp_rasterize_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -692,6 +694,33 @@ class Handle:
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE,
                                                   ctypes.c_void_p(height_ptr), ctypes.c_void_p(patch_ptr or None)))
+
+    def rasterize_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, frame_first=0, frames=None, ground_only=False, want_top=True,
+                            want_unref=False):
+        """The last call's non-ground points on the grid of rasterize_ground: (frames, ny, nx) int32 counts of the points whose
+        height over their patch's plane lies in [h_min, h_max]; want_top: also the float32 largest such height (NaN where the
+        count is 0); want_unref: also the int32 counts of the points without a ground reference (include/pwpp.h;
+        ground_only: patches decided not_upright, heading or tgr_reject give no reference either).
+        Returns count, or the tuple (count[, top][, unref])."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        count = np.empty(shape, np.int32)
+        top = np.empty(shape, np.float32) if want_top else None
+        unref = np.empty(shape, np.int32) if want_unref else None
+        # (an empty image still goes to the library: it is the one that names the bad argument)
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_rasterize_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_HOST,
+                                                     ptr(count), ptr(top), ptr(unref)))
+        out = tuple(a for a in (count, top, unref) if a is not None)
+        return out if len(out) > 1 else count
+
+    def rasterize_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, count_ptr, top_ptr=0, unref_ptr=0, frame_first=0, frames=None,
+                                   ground_only=False):
+        """rasterize_obstacles into device memory: addresses of the (frames, ny, nx) int32 count image and (0: none) the float32
+        top and int32 unref images.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_rasterize_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
+                                                     ctypes.c_void_p(count_ptr), ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(unref_ptr or None)))
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

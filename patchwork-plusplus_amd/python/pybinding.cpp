@@ -158,6 +158,15 @@ PYBIND11_MODULE(pypatchworkpp, m) {
                  return to_numpy(s.elevationMapRows(x0, y0, cell, nx, ny, ground_only));
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("ground_only") = false)
+        .def("getObstacleMap",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, bool ground_only) {
+                 const PatchWorkpp::ObstacleMap m = s.obstacleMapRows(x0, y0, cell, nx, ny, h_min, h_max, ground_only);
+                 py::array_t<int32_t> count({(py::ssize_t)m.top.rows(), (py::ssize_t)m.top.cols()});
+                 if (!m.count.empty()) std::memcpy(count.mutable_data(), m.count.data(), m.count.size() * sizeof(int32_t));
+                 return py::make_tuple(count, to_numpy(m.top));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("ground_only") = false)
         .def("getGroundPoints", [](PatchWorkpp &s) { return to_numpy(s.groundPointRows()); })
         .def("getNongroundPoints", [](PatchWorkpp &s) { return to_numpy(s.nongroundPointRows()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
