@@ -471,6 +471,66 @@ PWPP_API int pwpp_rasterize_obstacles(pwpp_handle *h, const pwpp_ground_grid *g,
                                       float   *top   /* same shape, may be NULL */,
                                       int32_t *unref /* same shape, may be NULL */);
 
+/* ---- the occupied cells of an obstacle grid as connected clusters (pwpp_label_grid, pwpp_label_obstacles) ------------------------
+ * The last piece of the 2.5-D map: which cells of the obstacle grid belong together.  Connected-component labelling of the count
+ * image on the device -- the step before tracking, boxes or a per-object costmap -- without an image per frame leaving the
+ * device, and for pwpp_label_obstacles without the caller restating the cell arithmetic to map points to cells.
+ *   occupied  A cell is occupied iff count >= min_count; min_count >= 1.
+ *   cluster   A maximal set of occupied cells of ONE frame that are connected through edge neighbours (connectivity 4) or edge
+ *             and corner neighbours (connectivity 8).  Frames never connect.
+ *   label     label[f][iy][ix] is -1 for an unoccupied cell, else the RANK of the cell's cluster among the frame's clusters in
+ *             ascending first_cell: 0, 1, 2, ...  That rank is the cluster's row in the frame's part of `clusters`.  The ranks
+ *             are complete also when the frame has more clusters than max_clusters.
+ *   clusters  Row r of frame f (clusters[f * max_clusters + r]) is the cluster of rank r, for the first min(n, max_clusters)
+ *             ranks; rows beyond the frame's n are unspecified.  n_clusters[f] is the frame's TRUE number of clusters, also when
+ *             it exceeds max_clusters.  Every sum is an integer sum and the maximum is taken on the integer key of
+ *             pwpp_rasterize_obstacles: label image, table and counts are functions of the count and top images alone --
+ *             bit-reproducible from call to call, and in pwpp_label_obstacles independent of the output order, the schedule and
+ *             the memory kind of the estimate call.
+ *   label_obstacles   count and top are exactly the images pwpp_rasterize_obstacles(g, h_min, h_max, ...) gives for the frame
+ *             range, written for the caller where asked for and kept in the handle's cluster buffer otherwise; label, clusters and
+ *             n_clusters are exactly what pwpp_label_grid gives for those two images.  When, mem, the grid's flags, the lifetime
+ *             rule of the INPUT and the errors are those of pwpp_rasterize_obstacles.
+ *   point_cluster     One int32 per point of the frame range, in cloud order: frame f starts at frame_base[f] -
+ *             frame_base[frame_first], frame_base as in pwpp_get_device_view.  A point's value is the label of its cell iff it is
+ *             a COUNTED point of the obstacle grid (named by the non-ground list, inside the grid, has a reference, height in the
+ *             band: pwpp_rasterize_obstacles' rules, evaluated by the same device function).  Every other point gets -1: ground,
+ *             unclassified, without a reference, out of the band, out of the grid, or in a cell below min_count.
+ *   mem       PWPP_MEM_HOST: every array is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory, 4-byte aligned and no more -- except `clusters`, which must be 8-byte aligned --
+ *             enqueued on the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG: a null handle, label or (pwpp_label_grid) count; nx, ny or frames < 1; nx * ny beyond 2^31 - 1 or
+ *             nx * ny * frames beyond 2^31; min_count < 1; a connectivity other than 4 or 8; max_clusters < 0; max_clusters > 0
+ *             with a null clusters; for pwpp_label_obstacles everything pwpp_rasterize_obstacles rejects.  Null arguments are
+ *             named before the device is touched.  pwpp_label_obstacles before any estimate call: PWPP_E_STATE.
+ *   buffers   One cluster buffer per handle holds the working image (a root's rank inside its counting unit), the per-unit root
+ *             counts, and the images, table and ids a call stages or keeps.  It is allocated on first use, counted by
+ *             pwpp_get_workspace_bytes and freed by pwpp_trim_workspace.  pwpp_label_grid needs a handle for its stream and this
+ *             buffer only: it enters like a getter (the call in flight lands first) and works before any estimate call.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of the estimate path changes. */
+#define PWPP_HAS_OBSTACLE_CLUSTERS 1
+typedef struct pwpp_obstacle_cluster {   /* 48 bytes */
+    int32_t first_cell;                  /* iy * nx + ix of the cluster's smallest cell in row-major order: its canonical name */
+    int32_t cells;                       /* occupied cells */
+    int32_t points;                      /* sum of count over them */
+    int32_t ix_min, ix_max, iy_min, iy_max;
+    float   top;                         /* largest top over them, in the order of pwpp_rasterize_obstacles (-0.0 < +0.0); NaN when no top image */
+    int64_t sum_ix, sum_iy;              /* sum of count * ix, count * iy: the point-weighted centroid is x0 + (sum_ix / points + 0.5) * cell */
+} pwpp_obstacle_cluster;
+/* any occupancy image: needs a handle (stream, buffers), no estimate call */
+PWPP_API int pwpp_label_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
+                             const int32_t *count, const float *top /* may be NULL */,
+                             int min_count, int connectivity /* 4 or 8 */,
+                             int32_t *label /* [frames][ny][nx] */,
+                             pwpp_obstacle_cluster *clusters /* [frames][max_clusters], may be NULL */,
+                             int32_t *n_clusters /* [frames], may be NULL */, int max_clusters);
+/* rasterize + label for frames of the LAST estimate call, one call */
+PWPP_API int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                  int min_count, int connectivity, int frame_first, int frames, int mem,
+                                  int32_t *label, int32_t *count /* may be NULL */, float *top /* may be NULL */,
+                                  pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters,
+                                  int32_t *point_cluster /* may be NULL */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -586,6 +646,9 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *   "records_path"        how the point records are gathered (pwpp_set_point_records): "0" (default) the kernel chooses by row size and
  *                         alignment; "1": one lane per row at every size (the yardstick of tools/point_records_cost.py); "2": never
  *                         the 16-byte pieces (tests)
+ *   "clusters_path"       how the obstacle clusters are labelled (pwpp_label_grid, pwpp_label_obstacles): "0" (default) tiles of
+ *                         64 x 16 cells in LDS, then the tiles' borders; "1": one global union-find without LDS (the yardstick of
+ *                         tools/obstacle_clusters_cost.py).  The results are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

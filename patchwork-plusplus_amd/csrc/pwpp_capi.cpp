@@ -35,6 +35,13 @@ extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, int rows_val
                                         hipStream_t stream);
 extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_valid, const PwppGroundGrid *grid, int frame_first, int frames,
                                          float *height, int32_t *patch, hipStream_t stream);
+extern "C" int pwpp_launch_point_cluster(const PwppGroundView *view, const PwppFrameDesc *descs, const PwppFrameResult *results, const int32_t *out_idx,
+                                         const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min, float h_max,
+                                         const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
+// pwpp_clusters.hip
+extern "C" size_t pwpp_cluster_work_words(int nx, int ny, int frames);
+extern "C" int pwpp_launch_label_grid(int nx, int ny, int frames, const int32_t *count, const float *top, int min_count, int connectivity, int path,
+                                      int32_t *label, void *clusters, int32_t *n_clusters, int max_clusters, uint32_t *work, hipStream_t stream);
 extern "C" int pwpp_launch_obstacle_raster(const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
                                            const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground,
                                            float h_min, float h_max, int32_t *count, float *top, int32_t *unref, hipStream_t stream);
@@ -254,6 +261,10 @@ struct pwpp_handle {
     // ground queries of the last call's results (pwpp_query_ground, pwpp_rasterize_ground): nothing is allocated before the first one
     DevBuf<int32_t> d_ground_rows{bufs, kPerBatch};   // [frames][B] bin -> row of the last call (PwppGroundView.rows)
     DevBuf<uint32_t> d_ground_stage{bufs, kPerBatch};  // PWPP_MEM_HOST queries: the output, then the input, in 4-byte words
+    // obstacle clusters (pwpp_label_grid, pwpp_label_obstacles): nothing is allocated before the first of them
+    DevBuf<uint32_t> d_clusters{bufs, kPerBatch};  // the cluster buffer, in 4-byte words: the kernels' working image and chunk counts, then whatever
+                                                   // images, table, counts and point ids the call stages or keeps (cluster_plan)
+    int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
     bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
     DevBuf<uint32_t> d_bins{bufs, kPerBatch};  // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
@@ -2038,6 +2049,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "records_path=%s: 0, 1 or 2 expected", value);
         h->records_path = v;
+    } else if (k == "clusters_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "clusters_path=%s: 0 or 1 expected", value);
+        h->clusters_path = v;
     } else if (k == "debug_flags") {
         const int v = std::atoi(value);
         //  the fit-chain probes (4) and the binning / scan / GLE probes (8) write the same 64-entry array
@@ -2344,6 +2359,152 @@ int pwpp_rasterize_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_
         HIPCHK(hipMemcpyAsync(count, d_count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         if (top) HIPCHK(hipMemcpyAsync(top, d_top, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         if (unref) HIPCHK(hipMemcpyAsync(unref, d_unref, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        h->ground_query_queued = true;
+    }
+    return PWPP_OK;
+}
+
+// ---- obstacle clusters: connected occupied cells of an obstacle grid ------------------------------------------------------------
+namespace {
+// what both entry points check of an image and a table, before the device is touched
+int cluster_args(int nx, int ny, int frames, int mem, int min_count, int connectivity, const void *clusters, int max_clusters, size_t &cells) {
+    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
+    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
+    if (per_frame > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", nx, ny);
+    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
+    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (connectivity != 4 && connectivity != 8) return fail(PWPP_E_ARG, "connectivity %d: 4 or 8 expected", connectivity);
+    if (max_clusters < 0) return fail(PWPP_E_ARG, "max_clusters %d", max_clusters);
+    if (max_clusters > 0 && !clusters) return fail(PWPP_E_ARG, "null cluster table with max_clusters %d", max_clusters);
+    if (mem == PWPP_MEM_DEVICE && (reinterpret_cast<uintptr_t>(clusters) & 7u)) return fail(PWPP_E_ARG, "the cluster table must be 8-byte aligned");
+    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle clusters take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
+    cells = (size_t)per_frame * (size_t)frames;
+    return PWPP_OK;
+}
+
+// The cluster buffer of one call: the kernels' working words first, then the sections the call asks for, each starting at a
+// multiple of four words (16 bytes: the table's 64-bit sums need 8).
+struct ClusterPlan {
+    size_t words = 0;
+    size_t take(size_t n) {
+        const size_t at = words;
+        words += (n + 3) & ~(size_t)3;
+        return at;
+    }
+};
+constexpr size_t kClusterRowWords = sizeof(pwpp_obstacle_cluster) / 4;
+static_assert(sizeof(pwpp_obstacle_cluster) == 48, "pwpp_obstacle_cluster is 48 bytes");
+}  // namespace
+
+int pwpp_label_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, const float *top, int min_count, int connectivity,
+                    int32_t *label, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!label || !count) return fail(PWPP_E_ARG, "null %s image", count ? "label" : "count");
+    size_t cells = 0;
+    int rc = cluster_args(nx, ny, frames, mem, min_count, connectivity, clusters, max_clusters, cells);
+    if (rc) return rc;
+    if ((rc = enter(h, true))) return rc;  // (like a getter: the call in flight lands first; no results are needed)
+    const size_t rows = (size_t)frames * (size_t)max_clusters;
+    ClusterPlan plan;
+    const size_t o_work = plan.take(pwpp_cluster_work_words(nx, ny, frames));
+    const bool host = mem == PWPP_MEM_HOST;
+    const size_t o_count = host ? plan.take(cells) : 0, o_top = host && top ? plan.take(cells) : 0, o_label = host ? plan.take(cells) : 0;
+    const size_t o_table = host ? plan.take(rows * kClusterRowWords) : 0, o_n = host ? plan.take((size_t)frames) : 0;
+    if ((rc = h->d_clusters.ensure(plan.words))) return rc;
+    uint32_t *w = h->d_clusters.p;
+    const int32_t *d_count = count;
+    const float *d_top = top;
+    int32_t *d_label = label, *d_n = n_clusters;
+    void *d_table = clusters;
+    if (host) {
+        d_count = reinterpret_cast<const int32_t *>(w + o_count);
+        d_top = top ? reinterpret_cast<const float *>(w + o_top) : nullptr;
+        d_label = reinterpret_cast<int32_t *>(w + o_label);
+        d_table = w + o_table;
+        d_n = reinterpret_cast<int32_t *>(w + o_n);
+        HIPCHK(hipMemcpyAsync(w + o_count, count, cells * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        if (top) HIPCHK(hipMemcpyAsync(w + o_top, top, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    const int lrc = pwpp_launch_label_grid(nx, ny, frames, d_count, d_top, min_count, connectivity, h->clusters_path, d_label, d_table, d_n, max_clusters,
+                                           w + o_work, h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    if (host) {
+        HIPCHK(hipMemcpyAsync(label, d_label, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (rows > 0) HIPCHK(hipMemcpyAsync(clusters, d_table, rows * sizeof(pwpp_obstacle_cluster), hipMemcpyDeviceToHost, h->stream));
+        if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_n, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        h->ground_query_queued = true;
+    }
+    return PWPP_OK;
+}
+
+// pwpp_rasterize_obstacles, pwpp_label_grid on its two images and the per-point scatter, enqueued as one sequence.  An image the
+// caller does not ask for stays in the cluster buffer.
+int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int connectivity, int frame_first, int frames,
+                         int mem, int32_t *label, int32_t *count, float *top, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters,
+                         int32_t *point_cluster) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label) return fail(PWPP_E_ARG, "null %s", g ? "label image" : "grid");
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
+    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (connectivity != 4 && connectivity != 8) return fail(PWPP_E_ARG, "connectivity %d: 4 or 8 expected", connectivity);
+    if (max_clusters < 0) return fail(PWPP_E_ARG, "max_clusters %d", max_clusters);
+    if (max_clusters > 0 && !clusters) return fail(PWPP_E_ARG, "null cluster table with max_clusters %d", max_clusters);
+    if (mem == PWPP_MEM_DEVICE && (reinterpret_cast<uintptr_t>(clusters) & 7u)) return fail(PWPP_E_ARG, "the cluster table must be 8-byte aligned");
+    size_t cells = 0;
+    int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
+    if (rc) return rc;
+    if ((int64_t)g->nx * (int64_t)g->ny > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", g->nx, g->ny);
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    const int64_t base_first = h->h_base.p[frame_first];
+    const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
+    const size_t rows = (size_t)frames * (size_t)max_clusters;
+    const bool host = mem == PWPP_MEM_HOST;
+    ClusterPlan plan;
+    const size_t o_work = plan.take(pwpp_cluster_work_words(g->nx, g->ny, frames));
+    const size_t o_count = host || !count ? plan.take(cells) : 0, o_top = host || !top ? plan.take(cells) : 0, o_label = host ? plan.take(cells) : 0;
+    const size_t o_table = host ? plan.take(rows * kClusterRowWords) : 0, o_n = host ? plan.take((size_t)frames) : 0, o_pc = host ? plan.take(points) : 0;
+    if ((rc = h->d_clusters.ensure(plan.words))) return rc;
+    uint32_t *w = h->d_clusters.p;
+    int32_t *d_count = host || !count ? reinterpret_cast<int32_t *>(w + o_count) : count;
+    float *d_top = host || !top ? reinterpret_cast<float *>(w + o_top) : top;
+    int32_t *d_label = host ? reinterpret_cast<int32_t *>(w + o_label) : label;
+    void *d_table = host ? static_cast<void *>(w + o_table) : static_cast<void *>(clusters);
+    int32_t *d_n = host ? reinterpret_cast<int32_t *>(w + o_n) : n_clusters;
+    int32_t *d_pc = host ? reinterpret_cast<int32_t *>(w + o_pc) : point_cluster;
+    if ((rc = ground_view(h, v))) return rc;
+    int max_nonground = 0;
+    for (int f = frame_first; f < frame_first + frames; ++f) {
+        const int nn = h->h_results.p[f].n_nonground;
+        max_nonground = nn > max_nonground ? nn : max_nonground;
+    }
+    const PwppFrameResult *results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
+    int lrc = pwpp_launch_obstacle_raster(&v, h->ground_rows_valid, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground, h_min,
+                                          h_max, d_count, d_top, nullptr, h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    h->ground_rows_valid = true;
+    lrc = pwpp_launch_label_grid(g->nx, g->ny, frames, d_count, d_top, min_count, connectivity, h->clusters_path, d_label, d_table, d_n, max_clusters,
+                                 w + o_work, h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    if (points > 0) {
+        HIPCHK(hipMemsetAsync(d_pc, 0xff, points * sizeof(int32_t), h->stream));  // (-1: every point that is not a counted one)
+        lrc = pwpp_launch_point_cluster(&v, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground, h_min, h_max, d_label, d_pc,
+                                        base_first, h->stream);
+        if (lrc != 0) return launch_failed(h, lrc);
+    }
+    if (host) {
+        HIPCHK(hipMemcpyAsync(label, d_label, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (count) HIPCHK(hipMemcpyAsync(count, d_count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (top) HIPCHK(hipMemcpyAsync(top, d_top, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (rows > 0) HIPCHK(hipMemcpyAsync(clusters, d_table, rows * sizeof(pwpp_obstacle_cluster), hipMemcpyDeviceToHost, h->stream));
+        if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_n, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (points > 0) HIPCHK(hipMemcpyAsync(point_cluster, d_pc, points * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     } else {
         h->ground_query_queued = true;

@@ -21,7 +21,8 @@
 //   K10 k_point_records    optional: the whole input records of the listed points, row for row behind the lists  (ref :8-16)
 // After a call, on demand: k_ground_rows / k_ground_query / k_ground_raster read the fitted planes at positions that are not
 // cloud points (pwpp_query_ground, pwpp_rasterize_ground); k_obstacle_fill / k_obstacle_raster / k_obstacle_top count the non-ground
-// points per cell of the same grid (pwpp_rasterize_obstacles).  They write nothing the pipeline reads.
+// points per cell of the same grid (pwpp_rasterize_obstacles), k_point_cluster gives every counted point the cluster of its cell
+// (pwpp_label_obstacles; the image kernels of the clusters are pwpp_clusters.hip).  They write nothing the pipeline reads.
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -41,6 +42,7 @@
 #include <type_traits>
 
 #include "pwpp_common.hpp"
+#include "pwpp_unionfind.h"
 
 namespace {
 
@@ -3043,13 +3045,9 @@ __global__ __launch_bounds__(kObBlock) void k_obstacle_fill(int64_t cells, uint3
     if (unref) zero_quad(unref, t, cells);
 }
 
-__device__ __forceinline__ uint32_t height_key(float h) {
-    const uint32_t b = __float_as_uint(h);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float height_of_key(uint32_t k) {
-    return k == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
+// (the key and its inverse: pwpp_unionfind.h -- the cluster table takes the same maximum over the cells of a cluster)
+__device__ __forceinline__ uint32_t height_key(float h) { return pwpp_height_key(h); }
+__device__ __forceinline__ float height_of_key(uint32_t k) { return pwpp_height_of_key(k); }
 
 // the cell of a coordinate: u = (c - c0) / cell in double (one subtraction, one IEEE division), kept iff 0 <= u < n (NaN: not)
 __device__ __forceinline__ bool grid_cell(float c, double c0, double cell, int n, int &i) {
@@ -3059,10 +3057,38 @@ __device__ __forceinline__ bool grid_cell(float c, double c0, double cell, int n
     return true;
 }
 
+// What entry e of frame f's non-ground list is to the obstacle grid: ONE function for k_obstacle_raster and k_point_cluster, so
+// that "the points of a cell" are the same points in both.  An index that is not a point of the frame (a frame whose lists are
+// unwritten: k_label_scatter) is dropped; frame, bin, row and cell are checked before an address is formed.
+enum ObstaclePoint { kObNone, kObUnref, kObCounted };  // outside the list, the frame or the grid | no reference | counted: `hgt` in the band
+__device__ __forceinline__ ObstaclePoint obstacle_point(const PwppGroundView &Q, const float4 *s_zt, const PwppFrameDesc &fd, const PwppFrameResult &r,
+                                                        const int32_t *out_idx, int f, int64_t e, const PwppGroundGrid &G, float h_min, float h_max,
+                                                        int &i, size_t &cell, float &hgt) {
+    const int64_t n = fd.n;  // (the two counts clamped to the frame: label_counts)
+    const int64_t ng = r.n_ground < 0 ? 0 : (r.n_ground > n ? n : (int64_t)r.n_ground);
+    const int64_t nn = r.n_nonground < 0 ? 0 : (r.n_nonground > n - ng ? n - ng : (int64_t)r.n_nonground);
+    if (e >= nn) return kObNone;
+    i = out_idx[fd.base + ng + e];
+    if ((unsigned)i >= (unsigned)fd.n) return kObNone;
+    float x, y, z, w;
+    load_point<true>(fd, i, x, y, z, w);
+    int ix, iy;
+    if (!grid_cell(x, G.x0, G.cell, G.nx, ix) || !grid_cell(y, G.y0, G.cell, G.ny, iy)) return kObNone;
+    unsigned code = 0;
+    if ((Q.debug & 16) || !bin_code_fast(Q.P, s_zt, x, y, code)) code = bin_code_exact(Q.P, x, y);
+    const PwppGroundSample s = ground_sample(Q, f, code, x, y, z);
+    cell = (size_t)iy * (size_t)G.nx + (size_t)ix;  // (inside the frame's image)
+    const bool hidden = (G.flags & PWPP_GRID_GROUND_ONLY) &&
+                        (s.decision == PWPP_DEC_NOT_UPRIGHT || s.decision == PWPP_DEC_HEADING || s.decision == PWPP_DEC_TGR_REJECT);
+    if (s.patch < 0 || hidden) return kObUnref;
+    hgt = s.distance;
+    if (!(h_min <= hgt && hgt <= h_max)) return kObNone;  // (a NaN height fails)
+    return kObCounted;
+}
+
 // grid (tiles of kObBlock entries over the longest non-ground list of the range, frames): one lane per list entry, one coalesced
 // load of the indices.  Consecutive entries mostly belong to one patch, so a wave's atomics hit few cells: plain global atomics
-// (DESIGN.md section K has what a combine of equal cells would have to beat).  An index that is not a point of the frame (a frame
-// whose lists are unwritten: k_label_scatter) is dropped; frame, bin, row and cell are checked before an address is formed.
+// (DESIGN.md section K has what a combine of equal cells would have to beat).
 __global__ __launch_bounds__(kObBlock) void k_obstacle_raster(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
                                                               const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
                                                               int32_t *count, uint32_t *top, int32_t *unref) {
@@ -3073,31 +3099,38 @@ __global__ __launch_bounds__(kObBlock) void k_obstacle_raster(PwppGroundView Q, 
     if ((unsigned)f >= (unsigned)Q.num_frames) return;
     const PwppFrameDesc fd = frames[f];
     const PwppFrameResult r = results[f];
-    const int64_t n = fd.n;  // (the two counts clamped to the frame: label_counts)
-    const int64_t ng = r.n_ground < 0 ? 0 : (r.n_ground > n ? n : (int64_t)r.n_ground);
-    const int64_t nn = r.n_nonground < 0 ? 0 : (r.n_nonground > n - ng ? n - ng : (int64_t)r.n_nonground);
-    const int64_t e = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
-    if (e >= nn) return;
-    const int i = out_idx[fd.base + ng + e];
-    if ((unsigned)i >= (unsigned)fd.n) return;
-    float x, y, z, w;
-    load_point<true>(fd, i, x, y, z, w);
-    int ix, iy;
-    if (!grid_cell(x, G.x0, G.cell, G.nx, ix) || !grid_cell(y, G.y0, G.cell, G.ny, iy)) return;
-    unsigned code = 0;
-    if ((Q.debug & 16) || !bin_code_fast(Q.P, s_zt, x, y, code)) code = bin_code_exact(Q.P, x, y);
-    const PwppGroundSample s = ground_sample(Q, f, code, x, y, z);
-    const size_t o = ((size_t)fr * (size_t)G.ny + (size_t)iy) * (size_t)G.nx + (size_t)ix;
-    const bool hidden = (G.flags & PWPP_GRID_GROUND_ONLY) &&
-                        (s.decision == PWPP_DEC_NOT_UPRIGHT || s.decision == PWPP_DEC_HEADING || s.decision == PWPP_DEC_TGR_REJECT);
-    if (s.patch < 0 || hidden) {
+    int i;
+    size_t cell;
+    float hgt;
+    const ObstaclePoint k = obstacle_point(Q, s_zt, fd, r, out_idx, f, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, i, cell, hgt);
+    if (k == kObNone) return;
+    const size_t o = (size_t)fr * (size_t)G.ny * (size_t)G.nx + cell;
+    if (k == kObUnref) {
         if (unref) atomicAdd(unref + o, 1);
         return;
     }
-    const float hgt = s.distance;
-    if (!(h_min <= hgt && hgt <= h_max)) return;  // (a NaN height fails)
     atomicAdd(count + o, 1);
     if (top) atomicMax(top + o, height_key(hgt));
+}
+
+// pwpp_label_obstacles' per-point cluster id: the launch of k_obstacle_raster again, and every COUNTED point takes the label of its
+// cell (-1 where the cell stayed below min_count).  point_cluster was filled with -1 and starts at the first point of frame_first
+// (`base_first`: that frame's fd.base); a point is named by at most one list entry, so every word has one writer.
+__global__ __launch_bounds__(kObBlock) void k_point_cluster(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
+                                                            const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
+                                                            const int32_t *label, int32_t *point_cluster, int64_t base_first) {
+    __shared__ float4 s_zt[8];
+    fill_zone_table(Q.P, s_zt);
+    __syncthreads();
+    const int fr = blockIdx.y, f = frame_first + fr;
+    if ((unsigned)f >= (unsigned)Q.num_frames) return;
+    const PwppFrameDesc fd = frames[f];
+    const PwppFrameResult r = results[f];
+    int i;
+    size_t cell;
+    float hgt;
+    if (obstacle_point(Q, s_zt, fd, r, out_idx, f, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, i, cell, hgt) != kObCounted) return;
+    point_cluster[fd.base - base_first + i] = label[(size_t)fr * (size_t)G.ny * (size_t)G.nx + cell];
 }
 
 // the keys of `top` as floats, in place: empty = the quiet NaN.  Quads as in k_obstacle_fill.
@@ -3195,6 +3228,17 @@ extern "C" int pwpp_launch_obstacle_raster(const PwppGroundView *view, int rows_
         hipLaunchKernelGGL(k_obstacle_raster, dim3((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames), dim3(kObBlock), 0, stream,
                            *view, descs, results, out_idx, *grid, frame_first, h_min, h_max, count, keys, unref);
     if (top) hipLaunchKernelGGL(k_obstacle_top, dim3(quads), dim3(kObBlock), 0, stream, cells, keys);
+    return (int)hipGetLastError();
+}
+
+// the per-point cluster ids of pwpp_label_obstacles: `label` is the finished label image of the frame range, point_cluster has been
+// filled with -1 (arguments as above; base_first: the first per-point slot of frame_first)
+extern "C" int pwpp_launch_point_cluster(const PwppGroundView *view, const PwppFrameDesc *descs, const PwppFrameResult *results, const int32_t *out_idx,
+                                         const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min, float h_max,
+                                         const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream) {
+    if (max_nonground > 0)
+        hipLaunchKernelGGL(k_point_cluster, dim3((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames), dim3(kObBlock), 0, stream,
+                           *view, descs, results, out_idx, *grid, frame_first, h_min, h_max, label, point_cluster, base_first);
     return (int)hipGetLastError();
 }
 

@@ -349,6 +349,31 @@ public:
     ObstacleMap getObstacleMap(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, bool ground_only = false) {
         return obstacleMapRows(x0, y0, cell, nx, ny, h_min, h_max, ground_only);
     }
+    // ... and its occupied cells (count >= min_count) as connected clusters (pwpp_label_obstacles): per cell the rank of its
+    // cluster in ascending first cell (-1: unoccupied), and per cluster the row of that rank -- cells, points, bounding box, top,
+    // the sums of the point-weighted centroid.  connectivity: 4 (edges) or 8 (edges and corners).
+    struct ObstacleClusters {
+        std::vector<int32_t> label;                   // ny x nx, row-major: row iy, column ix
+        std::vector<pwpp_obstacle_cluster> clusters;  // one row per cluster
+        int count = 0;                                // clusters.size()
+    };
+    ObstacleClusters getObstacleClusters(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count = 1,
+                                         int connectivity = 8, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        ObstacleClusters c;
+        c.label.assign((size_t)(ny > 0 ? ny : 0) * (size_t)(nx > 0 ? nx : 0), -1);
+        int32_t none = -1, n = 0;
+        int32_t *label = c.label.empty() ? &none : c.label.data();
+        // (the number of clusters first, then a table of exactly that many rows: the labels are the same both times)
+        check(pwpp_label_obstacles(h_, &g, h_min, h_max, min_count, connectivity, 0, 1, PWPP_MEM_HOST, label, nullptr, nullptr, nullptr, &n, 0, nullptr));
+        if (n > 0) {
+            c.clusters.resize((size_t)n);
+            check(pwpp_label_obstacles(h_, &g, h_min, h_max, min_count, connectivity, 0, 1, PWPP_MEM_HOST, label, nullptr, nullptr, c.clusters.data(), &n, n,
+                                       nullptr));
+        }
+        c.count = n;
+        return c;
+    }
 #ifdef PWPP_HAVE_EIGEN
     std::vector<pwpp_ground_sample> queryGround(const Eigen::MatrixX3f &positions) {
         std::vector<float> xyz((size_t)positions.rows() * 3);

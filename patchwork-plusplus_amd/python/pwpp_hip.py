@@ -66,6 +66,14 @@ class GroundGrid(ctypes.Structure):  # pwpp_ground_grid
                 ("ny", ctypes.c_int32), ("flags", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+class ObstacleCluster(ctypes.Structure):  # pwpp_obstacle_cluster (48 bytes)
+    _fields_ = [("first_cell", ctypes.c_int32), ("cells", ctypes.c_int32), ("points", ctypes.c_int32), ("ix_min", ctypes.c_int32),
+                ("ix_max", ctypes.c_int32), ("iy_min", ctypes.c_int32), ("iy_max", ctypes.c_int32), ("top", ctypes.c_float),
+                ("sum_ix", ctypes.c_int64), ("sum_iy", ctypes.c_int64)]
+
+
+OBSTACLE_CLUSTER_DTYPE = np.dtype([("first_cell", "<i4"), ("cells", "<i4"), ("points", "<i4"), ("ix_min", "<i4"), ("ix_max", "<i4"),
+                                   ("iy_min", "<i4"), ("iy_max", "<i4"), ("top", "<f4"), ("sum_ix", "<i8"), ("sum_iy", "<i8")])
 GROUND_SAMPLE_DTYPE = np.dtype([("patch", "<i4"), ("decision", "<i4"), ("ground_z", "<f4"), ("distance", "<f4")])
 GRID_GROUND_ONLY = 1
 
@@ -164,6 +172,9 @@ def load():
             L.pwpp_rasterize_ground.argtypes = [vp, ctypes.POINTER(GroundGrid), ci, ci, ci, vp, vp]
         if hasattr(L, "pwpp_rasterize_obstacles"):  # (as above: an older build has no obstacle grid)
             L.pwpp_rasterize_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, vp]
+        if hasattr(L, "pwpp_label_grid"):  # (as above: an older build has no obstacle clusters)
+            L.pwpp_label_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, ci]
+            L.pwpp_label_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -721,6 +732,80 @@ class Handle:
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_rasterize_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
                                                      ctypes.c_void_p(count_ptr), ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(unref_ptr or None)))
+
+    def label_grid(self, count, top=None, min_count=1, connectivity=8, max_clusters=0):
+        """Connected clusters of the occupied cells (count >= min_count) of a (frames, ny, nx) or (ny, nx) int32 count image, each
+        frame on its own; top: the float32 image of the same shape whose maximum the table reports, or None.  Works before any
+        estimate call.  Returns (label, clusters, n_clusters): int32 labels of count's shape (-1: unoccupied, else the cluster's
+        rank in ascending first_cell), the (frames, max_clusters) structured table (OBSTACLE_CLUSTER_DTYPE; rows beyond
+        min(n, max_clusters) unspecified) and the (frames,) int32 true numbers of clusters (include/pwpp.h)."""
+        count = np.ascontiguousarray(count, np.int32)
+        shape = count.shape
+        c3 = count.reshape((1,) + shape) if count.ndim == 2 else count
+        if c3.ndim != 3:
+            raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+        if top is not None:
+            top = np.ascontiguousarray(top, np.float32)
+            if top.shape != shape:
+                raise ValueError("top: the shape of count expected")
+        frames, ny, nx = c3.shape
+        label = np.empty(c3.shape, np.int32)
+        table = np.zeros((max(frames, 0), max(int(max_clusters), 0)), OBSTACLE_CLUSTER_DTYPE)
+        n = np.zeros(max(frames, 1), np.int32)
+        # (an empty image still goes to the library: it is the one that names the bad argument)
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_label_grid(self._h, nx, ny, frames, MEM_HOST, ptr(c3), ptr(top), int(min_count), int(connectivity), ptr(label),
+                                            _vp(table) if table.size else None, _vp(n), int(max_clusters)))
+        return label.reshape(shape), table, n[:frames]
+
+    def label_grid_device(self, nx, ny, frames, count_ptr, top_ptr, min_count, connectivity, label_ptr, clusters_ptr=0, n_clusters_ptr=0,
+                          max_clusters=0):
+        """label_grid on device memory: addresses of the (frames, ny, nx) int32 count, float32 top (0: none) and int32 label
+        images, the (frames, max_clusters) table of 48-byte rows (8-byte aligned; 0: none) and the (frames,) int32 counts
+        (0: none).  Enqueued on the handle's stream; complete after synchronize()."""
+        self._check(self._L.pwpp_label_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, ctypes.c_void_p(count_ptr), ctypes.c_void_p(top_ptr or None),
+                                            int(min_count), int(connectivity), ctypes.c_void_p(label_ptr), ctypes.c_void_p(clusters_ptr or None),
+                                            ctypes.c_void_p(n_clusters_ptr or None), int(max_clusters)))
+
+    def label_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, min_count=1, connectivity=8, max_clusters=0, frame_first=0, frames=None,
+                        ground_only=False, want_images=False, want_point_cluster=False):
+        """rasterize_obstacles and label_grid in one call, for frames of the last estimate call.  Returns (label, clusters,
+        n_clusters) as label_grid does for the (frames, ny, nx) images; want_images: then the int32 count and float32 top images
+        of rasterize_obstacles; want_point_cluster: then one int32 per point of the frame range in cloud order (frame f at
+        frame_base()[f] - frame_base()[frame_first]): the label of the point's cell if the obstacle grid counted the point, else -1."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        label = np.empty(shape, np.int32)
+        count = np.empty(shape, np.int32) if want_images else None
+        top = np.empty(shape, np.float32) if want_images else None
+        table = np.zeros((shape[0], max(int(max_clusters), 0)), OBSTACLE_CLUSTER_DTYPE)
+        n = np.zeros(max(frames, 1), np.int32)
+        pc = None
+        if want_point_cluster:
+            base = self.frame_base()
+            last = min(max(int(frame_first) + frames, 0), len(base) - 1)
+            first = min(max(int(frame_first), 0), last)
+            pc = np.empty(int(base[last] - base[first]), np.int32)
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_label_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity),
+                                                 int(frame_first), frames, MEM_HOST, ptr(label), ptr(count), ptr(top),
+                                                 _vp(table) if table.size else None, _vp(n), int(max_clusters), ptr(pc)))
+        out = (label, table, n[:max(frames, 0)])
+        if want_images:
+            out += (count, top)
+        if want_point_cluster:
+            out += (pc,)
+        return out
+
+    def label_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, min_count, connectivity, label_ptr, count_ptr=0, top_ptr=0,
+                               clusters_ptr=0, n_clusters_ptr=0, max_clusters=0, point_cluster_ptr=0, frame_first=0, frames=None, ground_only=False):
+        """label_obstacles into device memory: addresses as in label_grid_device and rasterize_obstacles_device (0: not wanted),
+        point_cluster_ptr: one int32 per point of the frame range.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_label_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity),
+                                                 int(frame_first), frames, MEM_DEVICE, ctypes.c_void_p(label_ptr), ctypes.c_void_p(count_ptr or None),
+                                                 ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(clusters_ptr or None),
+                                                 ctypes.c_void_p(n_clusters_ptr or None), int(max_clusters), ctypes.c_void_p(point_cluster_ptr or None)))
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

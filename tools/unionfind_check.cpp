@@ -1,0 +1,264 @@
+// unionfind_check.cpp -- the obstacle clusters' sequence of passes on the host, against a flood fill.
+//
+// The kernels of patchwork-plusplus_amd/csrc/pwpp_clusters.hip are built from the primitives of pwpp_unionfind.h (find, union,
+// compress, the neighbour rule, the height key).  This program runs the same sequence with the same primitives over plain memory
+// -- tile pass tile by tile on tile-local words, border pass over the edge cells, compress, rank by chunks of the row-major
+// order, table -- on a set of patterns, with the cells of every pass visited in a shuffled order (the order the GPU leaves open),
+// and compares label image, table and cluster count with a breadth-first flood fill.  Exit status 0: all equal.
+//
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -I patchwork-plusplus_amd/csrc tools/unionfind_check.cpp -o unionfind_check
+// (tests/test_obstacle_clusters_cpu.py builds and runs it; it needs no GPU and no HIP.)
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "pwpp_unionfind.h"
+
+namespace {
+
+struct Row {  // = pwpp_obstacle_cluster with the top as its key
+    int32_t first_cell, cells, points, ix_min, ix_max, iy_min, iy_max;
+    uint32_t top_key;
+    int64_t sum_ix, sum_iy;
+    bool operator==(const Row &o) const {
+        return first_cell == o.first_cell && cells == o.cells && points == o.points && ix_min == o.ix_min && ix_max == o.ix_max && iy_min == o.iy_min &&
+               iy_max == o.iy_max && top_key == o.top_key && sum_ix == o.sum_ix && sum_iy == o.sum_iy;
+    }
+};
+
+struct Words {  // plain memory: the host's policy
+    int32_t *w;
+    int32_t load(int32_t i) { return w[i]; }
+    int32_t fetch_min(int32_t i, int32_t v) {
+        const int32_t old = w[i];
+        w[i] = std::min(old, v);
+        return old;
+    }
+};
+
+struct Image {
+    int nx, ny;
+    std::vector<int32_t> count;
+    std::vector<float> top;
+};
+
+void add_to_row(Row &r, int c, int x, int y, int32_t n, float top) {
+    r.first_cell = std::min(r.first_cell, c);
+    r.cells += 1;
+    r.points += n;
+    r.ix_min = std::min(r.ix_min, x), r.ix_max = std::max(r.ix_max, x);
+    r.iy_min = std::min(r.iy_min, y), r.iy_max = std::max(r.iy_max, y);
+    r.top_key = std::max(r.top_key, pwpp_height_key(top));
+    r.sum_ix += (int64_t)n * x, r.sum_iy += (int64_t)n * y;
+}
+const Row kEmptyRow = {INT_MAX, 0, 0, INT_MAX, -1, INT_MAX, -1, 0u, 0, 0};
+
+// the reference: seeds in row-major order, so clusters come out in ascending first_cell
+void flood_fill(const Image &im, int min_count, int conn, std::vector<int32_t> &label, std::vector<Row> &rows) {
+    const int N = im.nx * im.ny;
+    label.assign((size_t)N, -1);
+    rows.clear();
+    std::vector<int> queue;
+    for (int s = 0; s < N; ++s) {
+        if (im.count[s] < min_count || label[s] >= 0) continue;
+        const int id = (int)rows.size();
+        rows.push_back(kEmptyRow);
+        queue.assign(1, s);
+        label[s] = id;
+        for (size_t q = 0; q < queue.size(); ++q) {
+            const int c = queue[q], x = c % im.nx, y = c / im.nx;
+            add_to_row(rows[id], c, x, y, im.count[c], im.top[c]);
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    if ((dx == 0 && dy == 0) || (conn == 4 && dx != 0 && dy != 0)) continue;
+                    const int qx = x + dx, qy = y + dy;
+                    if (qx < 0 || qx >= im.nx || qy < 0 || qy >= im.ny) continue;
+                    const int q2 = qy * im.nx + qx;
+                    if (im.count[q2] >= min_count && label[q2] < 0) {
+                        label[q2] = id;
+                        queue.push_back(q2);
+                    }
+                }
+        }
+    }
+}
+
+std::vector<int> shuffled(int n, std::mt19937 &rng) {
+    std::vector<int> v((size_t)n);
+    for (int i = 0; i < n; ++i) v[i] = i;
+    std::shuffle(v.begin(), v.end(), rng);
+    return v;
+}
+
+// the passes of pwpp_clusters.hip; tiled = false: the yardstick path (init, merge)
+void passes(const Image &im, int min_count, int conn, bool tiled, std::mt19937 &rng, std::vector<int32_t> &label, std::vector<Row> &rows) {
+    const int nx = im.nx, ny = im.ny, N = nx * ny;
+    label.assign((size_t)N, -1);
+    Words g{label.data()};
+    if (tiled) {
+        const int TX = PWPP_CL_TILE_X, TY = PWPP_CL_TILE_Y;
+        for (int ty0 = 0; ty0 < ny; ty0 += TY)
+            for (int tx0 = 0; tx0 < nx; tx0 += TX) {  // 1: a tile on its own words
+                int32_t par[PWPP_CL_TILE_X * PWPP_CL_TILE_Y];
+                Words t{par};
+                for (int c = 0; c < TX * TY; ++c) {
+                    const int x = tx0 + c % TX, y = ty0 + c / TX;
+                    par[c] = x < nx && y < ny && im.count[y * nx + x] >= min_count ? c : -1;
+                }
+                for (int c : shuffled(TX * TY, rng)) {
+                    if (par[c] < 0) continue;
+                    for (int k = 0; k < 4; ++k) {
+                        int qx, qy;
+                        if (!uf_neighbour(k, conn, c % TX, c / TX, TX, qx, qy)) continue;
+                        if (par[qy * TX + qx] >= 0) uf_union(t, c, qy * TX + qx, TX * TY);
+                    }
+                }
+                for (int c = 0; c < TX * TY; ++c) {
+                    const int x = tx0 + c % TX, y = ty0 + c / TX;
+                    if (x >= nx || y >= ny) continue;
+                    const int root = par[c] < 0 ? -1 : uf_find(t, c, TX * TY);
+                    label[y * nx + x] = root < 0 ? -1 : (ty0 + root / TX) * nx + tx0 + root % TX;
+                }
+            }
+        for (int c : shuffled(N, rng)) {  // 2: the pairs whose cells lie in different tiles
+            const int x = c % nx, y = c / nx;
+            if (label[c] < 0) continue;
+            for (int k = 0; k < 4; ++k) {
+                int qx, qy;
+                if (!uf_neighbour(k, conn, x, y, nx, qx, qy)) continue;
+                if (qx / TX == x / TX && qy / TY == y / TY) continue;
+                if (label[qy * nx + qx] >= 0) uf_union(g, c, qy * nx + qx, N);
+            }
+        }
+    } else {
+        for (int c = 0; c < N; ++c) label[c] = im.count[c] >= min_count ? c : -1;
+        for (int c : shuffled(N, rng)) {
+            if (label[c] < 0) continue;
+            for (int k = 0; k < 4; ++k) {
+                int qx, qy;
+                if (!uf_neighbour(k, conn, c % nx, c / nx, nx, qx, qy)) continue;
+                if (label[qy * nx + qx] >= 0) uf_union(g, c, qy * nx + qx, N);
+            }
+        }
+    }
+    // 3: compress; roots per chunk of the row-major order, a root's rank inside its chunk; scan
+    const int chunks = (N + PWPP_CL_CHUNK - 1) / PWPP_CL_CHUNK;
+    std::vector<int32_t> rank_in((size_t)N, -1), chunk((size_t)chunks, 0);
+    for (int c : shuffled(N, rng))
+        if (label[c] >= 0) (void)uf_compress(g, c, N);
+    for (int c = 0; c < N; ++c)
+        if (label[c] == c) rank_in[c] = chunk[c / PWPP_CL_CHUNK]++;
+    int total = 0;
+    for (int k = 0; k < chunks; ++k) {
+        const int v = chunk[k];
+        chunk[k] = total;
+        total += v;
+    }
+    // 4: relabel and table
+    rows.assign((size_t)total, kEmptyRow);
+    for (int c = 0; c < N; ++c) {
+        const int r = label[c];
+        if (r < 0) continue;
+        const int rank = chunk[r / PWPP_CL_CHUNK] + rank_in[r];
+        label[c] = rank;
+        add_to_row(rows[rank], c, c % nx, c / nx, im.count[c], im.top[c]);
+    }
+}
+
+// counts from 0..3: the pattern's cells min_count..3, the others 0..min_count - 1
+Image pattern(const std::string &name, int nx, int ny, int min_count, std::mt19937 &rng) {
+    Image im{nx, ny, std::vector<int32_t>((size_t)nx * ny, 0), std::vector<float>((size_t)nx * ny, 0.0f)};
+    std::vector<char> occ((size_t)nx * ny, 0);
+    auto at = [&](int x, int y) -> char & { return occ[(size_t)y * nx + x]; };
+    std::uniform_real_distribution<float> uni(0.0f, 1.0f);
+    if (name == "full") {
+        std::fill(occ.begin(), occ.end(), 1);
+    } else if (name == "checker") {
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) at(x, y) = (x + y) % 2 == 0;
+    } else if (name == "diagonals") {
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) at(x, y) = (x % std::max(ny, 2) == y) || ((nx - 1 - x) % std::max(ny, 2) == y);
+    } else if (name == "comb") {  // teeth in the even columns, joined only by the last row
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) at(x, y) = x % 2 == 0 || y == ny - 1;
+    } else if (name == "spiral") {  // one cell wide, from the rim to the centre, a free ring between the turns
+        int x0 = 0, y0 = 0, x1 = nx - 1, y1 = ny - 1;
+        bool first = true;
+        while (x0 <= x1 && y0 <= y1) {
+            for (int x = first ? x0 : x0 - 1; x <= x1; ++x) at(std::max(x, 0), y0) = 1;
+            for (int y = y0; y <= y1; ++y) at(x1, y) = 1;
+            if (y1 > y0)
+                for (int x = x0; x <= x1; ++x) at(x, y1) = 1;
+            if (x1 > x0 && y1 - y0 >= 2)
+                for (int y = y0 + 2; y <= y1; ++y) at(x0, y) = 1;
+            if (x1 - x0 >= 2 && y1 - y0 >= 2) at(x0 + 1, y0 + 2) = 1;
+            first = false;
+            x0 += 2, y0 += 2, x1 -= 2, y1 -= 2;
+        }
+    } else if (name == "serpentine") {  // every other row full, joined at alternating ends
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) at(x, y) = y % 2 == 0 || x == ((y / 2) % 2 == 0 ? nx - 1 : 0);
+    } else if (name == "corner") {  // two blocks that touch only at the corner of the first tile
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x)
+                at(x, y) = (x < PWPP_CL_TILE_X && y < PWPP_CL_TILE_Y && x >= PWPP_CL_TILE_X - 3 && y >= PWPP_CL_TILE_Y - 3) ||
+                           (x >= PWPP_CL_TILE_X && y >= PWPP_CL_TILE_Y && x < PWPP_CL_TILE_X + 3 && y < PWPP_CL_TILE_Y + 3);
+    } else if (name.rfind("random", 0) == 0) {
+        const float p = std::stof(name.substr(6));
+        for (auto &o : occ) o = uni(rng) < p;
+    }  // "empty": nothing
+    for (size_t i = 0; i < occ.size(); ++i) {
+        im.count[i] = occ[i] ? min_count + (int)(rng() % (unsigned)(4 - min_count)) : (int)(rng() % (unsigned)min_count);
+        im.top[i] = im.count[i] > 0 ? uni(rng) * 4.0f - 1.0f : __builtin_nanf("");
+    }
+    return im;
+}
+
+}  // namespace
+
+int main() {
+    const int shapes[][2] = {{1, 1}, {7, 5}, {64, 16}, {65, 17}, {129, 33}, {257, 3}, {3, 257}, {200, 70}};
+    const char *names[] = {"empty", "full", "checker", "diagonals", "comb", "spiral", "serpentine", "random0.1", "random0.3", "random0.59", "corner"};
+    std::mt19937 rng(20240607u);
+    int cases = 0, bad = 0;
+    for (const auto &sh : shapes)
+        for (const char *name : names) {
+            for (int min_count = 1; min_count <= 2; ++min_count)
+                for (int conn = 4; conn <= 8; conn += 4) {
+                    const Image im = pattern(name, sh[0], sh[1], min_count, rng);
+                    std::vector<int32_t> want, got;
+                    std::vector<Row> want_rows, got_rows;
+                    flood_fill(im, min_count, conn, want, want_rows);
+                    for (int tiled = 0; tiled < 2; ++tiled) {
+                        passes(im, min_count, conn, tiled != 0, rng, got, got_rows);
+                        ++cases;
+                        if (got != want || !(got_rows == want_rows)) {
+                            ++bad;
+                            std::fprintf(stderr, "MISMATCH %s %dx%d connectivity %d min_count %d %s: %zu clusters, flood fill %zu\n", name, sh[0], sh[1], conn,
+                                         min_count, tiled ? "tiled" : "global", got_rows.size(), want_rows.size());
+                        }
+                    }
+                }
+        }
+    // the checkerboard's two faces: all singletons with edge neighbours, one cluster with corners too
+    {
+        Image im = pattern("checker", 65, 17, 1, rng);
+        for (size_t i = 0; i < im.count.size(); ++i) im.count[i] = ((i % 65) + (i / 65)) % 2 == 0 ? 1 : 0;
+        std::vector<int32_t> l;
+        std::vector<Row> r4, r8;
+        passes(im, 1, 4, true, rng, l, r4);
+        passes(im, 1, 8, true, rng, l, r8);
+        if (r4.size() != (65 * 17 + 1) / 2 || r8.size() != 1) {
+            ++bad;
+            std::fprintf(stderr, "MISMATCH checkerboard: %zu singletons, %zu cluster(s)\n", r4.size(), r8.size());
+        }
+    }
+    std::printf("unionfind_check: %d cases, %d mismatches\n", cases, bad);
+    return bad ? 1 : 0;
+}
