@@ -531,6 +531,67 @@ PWPP_API int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, flo
                                   pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters,
                                   int32_t *point_cluster /* may be NULL */);
 
+/* ---- every cluster of the obstacle grid as an oriented box (pwpp_box_obstacles, pwpp_box_points) ----------------------------------
+ * The step from cells to objects: the COUNTED points of every label of a label image reduced to a centre and a heading in metres,
+ * a length and a width, the spread along and across, and the vertical extent -- what a tracker, a box publisher or a costmap
+ * inflater takes -- without point_cluster and the coordinates of a batch leaving the device.
+ *   counted   The points pwpp_rasterize_obstacles(g, h_min, h_max, ...) counts (one device function decides it for all of them).
+ *   row       A counted point of frame f in cell c belongs to row label[f][c]; it contributes to boxes[f * max_boxes + row] iff
+ *             0 <= row < max_boxes, every other value (-1, a rank beyond the table) is skipped.  The label image is the
+ *             caller's: what pwpp_label_obstacles wrote for the same grid and band, or an edited one -- clusters merged, dropped,
+ *             renumbered.  No min_count and no connectivity enters here.  It is not written.
+ *   arithmetic   Part of the contract; only + - * / sqrt, no FMA.  With dx = (double)x - x0, dy = (double)y - y0 (the doubles the
+ *             cell arithmetic starts from):
+ *             1  qx = llrint(dx * 1024), qy alike (ties to even); per row the 64-bit integer sums N, Sx, Sy, Sxx, Sxy, Syy.
+ *             2  A = N Sxx - Sx Sx, B = N Sxy - Sx Sy, C = N Syy - Sy Sy in 128-bit integers; each rounded ONCE to a double a, b, c.
+ *             3  d = (a - c) * 0.5; r = sqrt(d*d + b*b); (vx, vy) = d >= 0 ? (d + r, b) : (b, r - d); n = sqrt(vx*vx + vy*vy);
+ *                the axis is (vx / n, vy / n), negated when ux < 0 or (ux == 0 and uy < 0) -- or (1, 0) when n is not finite and
+ *                positive (one point, coincident points, an isotropic set).  ax = (float)ux, ay = (float)uy.
+ *             4  m = (a + c) * 0.5; sigma_long = (float)(sqrt(m + r) / ((double)N * 1024)), sigma_short alike from max(m - r, 0);
+ *                mean_x = (float)(x0 + ((double)Sx / (double)N) / 1024), mean_y alike.
+ *             5  per point p = (float)(dx * (double)ax + dy * (double)ay), q = (float)(dy * (double)ax - dx * (double)ay): against
+ *                the FLOAT axis, so the box is a rectangle in the reported frame.  Minima and maxima of p, q, the height over
+ *                ground and z on the integer key of pwpp_rasterize_obstacles (-0.0 < +0.0).  length = (float)((double)pmax -
+ *                (double)pmin), width alike from q; pc = ((double)pmin + (double)pmax) * 0.5, qc alike;
+ *                cx = (float)(x0 + (pc * (double)ax - qc * (double)ay)), cy = (float)(y0 + (pc * (double)ay + qc * (double)ax)).
+ *             Integer sums, minima and maxima commute: every field is a function of the input, the grid, the band and the label
+ *             image alone -- the same bytes for every output order, schedule, memory kind and value of the option "boxes_path".
+ *   extent    nx * cell <= 1024 and ny * cell <= 1024 (in double): then q <= 2^20 + 1 and the sums of a frame's 2^22 points stay
+ *             below 2^63.  frames * max_boxes <= 2^24.
+ *   rows      A row no counted point named: points 0, every float the quiet NaN (0x7fc00000).  For the rows of a
+ *             pwpp_label_obstacles table `points` equals the cluster row's points and h_max has the bits of its top.
+ *   when, mem, errors   Those of pwpp_label_obstacles: frames of the LAST estimate call, the lifetime rule of the input, PWPP_E_STATE
+ *             before any estimate call.  PWPP_MEM_HOST: label and boxes are host memory, staged through the handle's cluster
+ *             buffer; synchronous.  PWPP_MEM_DEVICE: device memory, 4-byte aligned and no more, enqueued on the handle's stream,
+ *             complete after pwpp_synchronize; boxes is also the kernels' scratch between the passes.  PWPP_MEM_HOST_PINNED,
+ *             a null handle, grid, label or boxes, max_boxes < 1, an extent beyond 1024 m: PWPP_E_ARG, named before the device
+ *             is touched.  The accumulators (80 bytes per row) live in the cluster buffer: allocated on first use, counted by
+ *             pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *   box_points   Host only, no handle, no device: the same rows for a caller's own points, compiled from the same functions as
+ *             the kernels.  Row and height over ground of every point are the caller's, z is xyz[:, 2].  Skipped: a row outside
+ *             [0, max_boxes), a NaN hgt, a point outside the grid (the cell rule of pwpp_rasterize_ground).  m <= 2^22.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of the estimate path changes. */
+#define PWPP_HAS_OBSTACLE_BOXES 1
+typedef struct pwpp_obstacle_box {      /* 64 bytes, 4-byte aligned fields only */
+    int32_t points;                     /* counted points that named this row; 0: every float below is the quiet NaN */
+    int32_t pad_;                       /* 0 */
+    float mean_x, mean_y;               /* point mean, from the 1/1024 m moments */
+    float cx, cy;                       /* centre of the box */
+    float ax, ay;                       /* unit vector of the principal axis; ax > 0, or ax == 0 and ay > 0 */
+    float length, width;                /* extent along the axis / across it (length is NOT forced >= width) */
+    float sigma_long, sigma_short;      /* standard deviations along / across, metres */
+    float h_min, h_max;                 /* lowest / largest height over ground (the obstacle grid's height) */
+    float z_min, z_max;                 /* lowest / largest z as the pipeline read it (transformed, if transforms are set) */
+} pwpp_obstacle_box;
+/* rows for frames of the LAST estimate call, from a label image on the obstacle grid g */
+PWPP_API int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                int frame_first, int frames, int mem,
+                                const int32_t *label /* [frames][ny][nx] */,
+                                pwpp_obstacle_box *boxes /* [frames][max_boxes] */, int max_boxes);
+/* host only, no device: the same arithmetic for a caller's own points */
+PWPP_API int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz /* (m,3) */, const float *hgt /* m */,
+                             const int32_t *row /* m */, int64_t m, pwpp_obstacle_box *boxes, int max_boxes);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -649,6 +710,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *   "clusters_path"       how the obstacle clusters are labelled (pwpp_label_grid, pwpp_label_obstacles): "0" (default) tiles of
  *                         64 x 16 cells in LDS, then the tiles' borders; "1": one global union-find without LDS (the yardstick of
  *                         tools/obstacle_clusters_cost.py).  The results are identical bytes.
+ *   "boxes_path"          how the points reach the rows of the obstacle boxes (pwpp_box_obstacles): "0" (default) the faster of the
+ *                         two by tools/obstacle_boxes_cost.py; "1": every counted lane issues its atomics on its row (the yardstick);
+ *                         "2": the lanes of a wave that name the same row are summed first, one set of atomics per distinct row.
+ *                         The results are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <new>
@@ -21,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pwpp.h"
+#include "pwpp_boxes.h"
 #include "pwpp_dev.h"
 
 extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev, hipStream_t aux,
@@ -38,7 +40,12 @@ extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_va
 extern "C" int pwpp_launch_point_cluster(const PwppGroundView *view, const PwppFrameDesc *descs, const PwppFrameResult *results, const int32_t *out_idx,
                                          const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min, float h_max,
                                          const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
+extern "C" int pwpp_launch_box_pass(int pass, int combine, const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs,
+                                    const PwppFrameResult *results, const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames,
+                                    int max_nonground, float h_min, float h_max, const int32_t *label, int max_boxes, uint32_t *acc, const void *boxes,
+                                    hipStream_t stream);
 // pwpp_clusters.hip
+extern "C" int pwpp_launch_box_rows(int step, int64_t rows, uint32_t *acc, double x0, double y0, void *boxes, hipStream_t stream);
 extern "C" size_t pwpp_cluster_work_words(int nx, int ny, int frames);
 extern "C" int pwpp_launch_label_grid(int nx, int ny, int frames, const int32_t *count, const float *top, int min_count, int connectivity, int path,
                                       int32_t *label, void *clusters, int32_t *n_clusters, int max_clusters, uint32_t *work, hipStream_t stream);
@@ -265,6 +272,7 @@ struct pwpp_handle {
     DevBuf<uint32_t> d_clusters{bufs, kPerBatch};  // the cluster buffer, in 4-byte words: the kernels' working image and chunk counts, then whatever
                                                    // images, table, counts and point ids the call stages or keeps (cluster_plan)
     int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
+    int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
     bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
     DevBuf<uint32_t> d_bins{bufs, kPerBatch};  // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
@@ -2053,6 +2061,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 1) return fail(PWPP_E_ARG, "clusters_path=%s: 0 or 1 expected", value);
         h->clusters_path = v;
+    } else if (k == "boxes_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
+        h->boxes_path = v;
     } else if (k == "debug_flags") {
         const int v = std::atoi(value);
         //  the fit-chain probes (4) and the binning / scan / GLE probes (8) write the same 64-entry array
@@ -2508,6 +2520,136 @@ int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
         HIPCHK(hipStreamSynchronize(h->stream));
     } else {
         h->ground_query_queued = true;
+    }
+    return PWPP_OK;
+}
+
+// ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------
+namespace {
+static_assert(sizeof(pwpp_obstacle_box) == 64 && alignof(pwpp_obstacle_box) == 4, "pwpp_obstacle_box is 64 bytes of 4-byte fields");
+constexpr size_t kBoxRowWords = sizeof(pwpp_obstacle_box) / 4;
+// What option "boxes_path" = 0 means: whether the lanes of a wave that name one row are combined before the atomics.  Decided by
+// tools/obstacle_boxes_cost.py (profiles/obstacle_boxes_cost.txt), not in advance.
+constexpr bool kBoxesDefaultCombine = false;
+
+int box_extent_args(const pwpp_ground_grid *g) {
+    if (!((double)g->nx * g->cell <= PWPP_BOX_MAX_EXTENT) || !((double)g->ny * g->cell <= PWPP_BOX_MAX_EXTENT))
+        return fail(PWPP_E_ARG, "grid of %d x %d cells of %g m: the obstacle boxes take an extent of at most 1024 m", g->nx, g->ny, g->cell);
+    return PWPP_OK;
+}
+}  // namespace
+
+// Init, first pass, solve, second pass, finish: five launches on the handle's stream.  The accumulators, and for PWPP_MEM_HOST the
+// label image and the rows, live in the cluster buffer.
+int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem, const int32_t *label,
+                       pwpp_obstacle_box *boxes, int max_boxes) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label || !boxes) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!label ? "label image" : "box table"));
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
+    if (max_boxes < 1) return fail(PWPP_E_ARG, "max_boxes %d: at least 1 expected", max_boxes);
+    if (frames > 0 && (int64_t)frames * (int64_t)max_boxes > ((int64_t)1 << 24))
+        return fail(PWPP_E_ARG, "%d frames x %d boxes exceed 2^24 rows", frames, max_boxes);
+    int rc = box_extent_args(g);
+    if (rc) return rc;
+    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle boxes take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((int64_t)g->nx * (int64_t)g->ny > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", g->nx, g->ny);
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    const size_t rows = (size_t)frames * (size_t)max_boxes;
+    const bool host = mem == PWPP_MEM_HOST;
+    ClusterPlan plan;
+    const size_t o_acc = plan.take(rows * PWPP_BOX_ACC_WORDS);
+    const size_t o_label = host ? plan.take(cells) : 0, o_rows = host ? plan.take(rows * kBoxRowWords) : 0;
+    if ((rc = h->d_clusters.ensure(plan.words))) return rc;
+    uint32_t *w = h->d_clusters.p;
+    const int32_t *d_label = host ? reinterpret_cast<const int32_t *>(w + o_label) : label;
+    void *d_rows = host ? static_cast<void *>(w + o_rows) : static_cast<void *>(boxes);
+    if (host) HIPCHK(hipMemcpyAsync(w + o_label, label, cells * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = ground_view(h, v))) return rc;
+    int max_nonground = 0;
+    for (int f = frame_first; f < frame_first + frames; ++f) {
+        const int nn = h->h_results.p[f].n_nonground;
+        max_nonground = nn > max_nonground ? nn : max_nonground;
+    }
+    const PwppFrameResult *results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
+    const int combine = h->boxes_path == 0 ? (kBoxesDefaultCombine ? 1 : 0) : (h->boxes_path == 2 ? 1 : 0);
+    int lrc = pwpp_launch_box_rows(0, (int64_t)rows, w + o_acc, g->x0, g->y0, d_rows, h->stream);
+    for (int pass = 0; pass < 2 && lrc == 0; ++pass) {
+        lrc = pwpp_launch_box_pass(pass, combine, &v, h->ground_rows_valid, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground,
+                                   h_min, h_max, d_label, max_boxes, w + o_acc, d_rows, h->stream);
+        if (lrc != 0) break;
+        h->ground_rows_valid = true;
+        lrc = pwpp_launch_box_rows(1 + pass, (int64_t)rows, w + o_acc, g->x0, g->y0, d_rows, h->stream);
+    }
+    if (lrc != 0) return launch_failed(h, lrc);
+    if (host) {
+        HIPCHK(hipMemcpyAsync(boxes, d_rows, rows * sizeof(pwpp_obstacle_box), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        h->ground_query_queued = true;
+    }
+    return PWPP_OK;
+}
+
+// The same rows on the host, from the functions the kernels compile (pwpp_boxes.h); row and height of every point are the caller's.
+int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz, const float *hgt, const int32_t *row, int64_t m, pwpp_obstacle_box *boxes, int max_boxes) {
+    if (!g || !boxes) return fail(PWPP_E_ARG, "null %s", g ? "box table" : "grid");
+    if (max_boxes < 1 || max_boxes > (1 << 24)) return fail(PWPP_E_ARG, "max_boxes %d: 1 .. 2^24 expected", max_boxes);
+    if (m < 0 || m > ((int64_t)1 << 22)) return fail(PWPP_E_ARG, "%lld points (0..2^22 supported)", (long long)m);
+    if (m > 0 && (!xyz || !hgt || !row)) return fail(PWPP_E_ARG, "null %s", !xyz ? "positions" : (!hgt ? "heights" : "rows"));
+    if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
+        return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
+    const int rc = box_extent_args(g);
+    if (rc) return rc;
+    struct Acc {
+        long long s[PWPP_BOX_SUMS];
+        uint32_t k[PWPP_BOX_KEYS];
+    };
+    Acc empty;
+    for (int j = 0; j < PWPP_BOX_SUMS; ++j) empty.s[j] = 0;
+    for (int j = 0; j < PWPP_BOX_KEYS; ++j) empty.k[j] = (j & 1) ? PWPP_BOX_KEY_NO_MAX : PWPP_BOX_KEY_NO_MIN;
+    std::vector<Acc> acc((size_t)max_boxes, empty);
+    std::vector<PwppBoxAxis> axis((size_t)max_boxes, PwppBoxAxis{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f});
+    // the grid_cell rule of the kernels: u = (c - c0) / cell in double, kept iff 0 <= u < n (a NaN: not)
+    const auto inside = [](double d, double cell, int n) {
+        const double u = d / cell;
+        return u >= 0.0 && u < (double)n;
+    };
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int64_t i = 0; i < m; ++i) {
+            const int32_t r = row[i];
+            if (r < 0 || r >= max_boxes || hgt[i] != hgt[i]) continue;
+            const double dx = (double)xyz[3 * i] - g->x0, dy = (double)xyz[3 * i + 1] - g->y0;
+            if (!inside(dx, g->cell, g->nx) || !inside(dy, g->cell, g->ny)) continue;
+            Acc &a = acc[(size_t)r];
+            if (pass == 0) {
+                const long long qx = pwpp_box_quantise(dx), qy = pwpp_box_quantise(dy);
+                a.s[0] += 1, a.s[1] += qx, a.s[2] += qy, a.s[3] += qx * qx, a.s[4] += qx * qy, a.s[5] += qy * qy;
+            } else {
+                float p, q;
+                pwpp_box_project(dx, dy, axis[(size_t)r].ax, axis[(size_t)r].ay, p, q);
+                const uint32_t k[4] = {pwpp_height_key(p), pwpp_height_key(q), pwpp_height_key(hgt[i]), pwpp_height_key(xyz[3 * i + 2])};
+                for (int j = 0; j < 4; ++j) {
+                    a.k[2 * j] = std::min(a.k[2 * j], k[j]);
+                    a.k[2 * j + 1] = std::max(a.k[2 * j + 1], k[j]);
+                }
+            }
+        }
+        for (int r = 0; r < max_boxes; ++r) {
+            const Acc &a = acc[(size_t)r];
+            if (pass == 0) {
+                if (a.s[0] > 0) axis[(size_t)r] = pwpp_box_solve(a.s[0], a.s[1], a.s[2], a.s[3], a.s[4], a.s[5], g->x0, g->y0);
+            } else {
+                uint32_t out[16];
+                pwpp_box_row(a.s[0], axis[(size_t)r], a.k, g->x0, g->y0, out);
+                std::memcpy(&boxes[r], out, sizeof(out));
+            }
+        }
     }
     return PWPP_OK;
 }

@@ -29,10 +29,14 @@
 // retry, never a wrong merge; and the root of a finished component is its smallest cell.  Plain stores (steps 1, 4) and plain
 // loads (step 4) touch label words only in launches where no other workgroup touches the same word, and the launch boundary on
 // the stream orders them against the atomic steps.
+//
+// The ROW kernels of the obstacle boxes (pwpp_box_obstacles) live here too, at the end: k_box_init / k_box_solve / k_box_finish, one
+// lane per accumulator word or per row, around the two point passes of pwpp_kernels.hip.  pwpp_boxes.h has their arithmetic.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "pwpp_boxes.h"
 #include "pwpp_unionfind.h"
 
 namespace {
@@ -273,7 +277,59 @@ __global__ __launch_bounds__(kClBlock) void k_cl_tops(int64_t rows, int32_t *tab
     *p = __builtin_bit_cast(uint32_t, pwpp_height_of_key(*p));
 }
 
+// ---- the row kernels of the obstacle boxes (pwpp_box_obstacles; pwpp_boxes.h has the arithmetic and the accumulators) -----------------
+// One lane per accumulator word: the sums 0, the keys empty.
+__global__ __launch_bounds__(kClBlock) void k_box_init(int64_t rows, uint32_t *acc) {
+    const int64_t i = (int64_t)blockIdx.x * kClBlock + threadIdx.x;
+    if (i >= rows * PWPP_BOX_ACC_WORDS) return;
+    const int k = (int)(i % PWPP_BOX_ACC_WORDS) - 2 * PWPP_BOX_SUMS;
+    acc[i] = k < 0 ? 0u : ((k & 1) ? PWPP_BOX_KEY_NO_MAX : PWPP_BOX_KEY_NO_MIN);
+}
+
+// Between the passes, one lane per row: covariance, axis, spread and mean of a row with points into its place in `boxes` (words,
+// 4-byte aligned and no more).  A row without points is never read by the second pass.
+__global__ __launch_bounds__(kClBlock) void k_box_solve(int64_t rows, const uint32_t *acc, double x0, double y0, uint32_t *boxes) {
+    const int64_t i = (int64_t)blockIdx.x * kClBlock + threadIdx.x;
+    if (i >= rows) return;
+    const long long *s = reinterpret_cast<const long long *>(acc + i * PWPP_BOX_ACC_WORDS);
+    if (s[0] <= 0) return;
+    const PwppBoxAxis a = pwpp_box_solve(s[0], s[1], s[2], s[3], s[4], s[5], x0, y0);
+    float *row = reinterpret_cast<float *>(boxes + i * 16);
+    row[2] = a.mean_x, row[3] = a.mean_y, row[6] = a.ax, row[7] = a.ay, row[10] = a.sigma_long, row[11] = a.sigma_short;
+}
+
+// Behind the second pass, one lane per row: the sixteen words of the finished row; a row without points: 0, 0 and the quiet NaN.
+__global__ __launch_bounds__(kClBlock) void k_box_finish(int64_t rows, const uint32_t *acc, double x0, double y0, uint32_t *boxes) {
+    const int64_t i = (int64_t)blockIdx.x * kClBlock + threadIdx.x;
+    if (i >= rows) return;
+    const uint32_t *w = acc + i * PWPP_BOX_ACC_WORDS;
+    const long long n = *reinterpret_cast<const long long *>(w);
+    uint32_t *row = boxes + i * 16;
+    PwppBoxAxis a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (n > 0) {
+        const float *f = reinterpret_cast<const float *>(row);
+        a.mean_x = f[2], a.mean_y = f[3], a.ax = f[6], a.ay = f[7], a.sigma_long = f[10], a.sigma_short = f[11];
+    }
+    uint32_t out[16];
+    pwpp_box_row(n, a, w + 2 * PWPP_BOX_SUMS, x0, y0, out);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) row[k] = out[k];
+}
+
 }  // namespace
+
+// The row steps of pwpp_box_obstacles on `rows` rows.  step 0: the accumulators' initial values; 1: steps 2 to 4 of every row
+// between the passes; 2: the finished rows.  acc: PWPP_BOX_ACC_WORDS words per row, 8-byte aligned; boxes: 16 words per row.
+extern "C" int pwpp_launch_box_rows(int step, int64_t rows, uint32_t *acc, double x0, double y0, void *boxes, hipStream_t stream) {
+    const dim3 per_row((unsigned)((rows + kClBlock - 1) / kClBlock)), per_word((unsigned)((rows * PWPP_BOX_ACC_WORDS + kClBlock - 1) / kClBlock));
+    if (step == 0)
+        hipLaunchKernelGGL(k_box_init, per_word, dim3(kClBlock), 0, stream, rows, acc);
+    else if (step == 1)
+        hipLaunchKernelGGL(k_box_solve, per_row, dim3(kClBlock), 0, stream, rows, acc, x0, y0, static_cast<uint32_t *>(boxes));
+    else
+        hipLaunchKernelGGL(k_box_finish, per_row, dim3(kClBlock), 0, stream, rows, acc, x0, y0, static_cast<uint32_t *>(boxes));
+    return (int)hipGetLastError();
+}
 
 // Words of the handle's cluster buffer the kernels need for an image of nx * ny * frames cells: the roots' ranks inside their
 // chunks (one per cell), then the chunk counts.

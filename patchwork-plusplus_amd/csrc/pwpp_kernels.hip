@@ -22,7 +22,8 @@
 // After a call, on demand: k_ground_rows / k_ground_query / k_ground_raster read the fitted planes at positions that are not
 // cloud points (pwpp_query_ground, pwpp_rasterize_ground); k_obstacle_fill / k_obstacle_raster / k_obstacle_top count the non-ground
 // points per cell of the same grid (pwpp_rasterize_obstacles), k_point_cluster gives every counted point the cluster of its cell
-// (pwpp_label_obstacles; the image kernels of the clusters are pwpp_clusters.hip).  They write nothing the pipeline reads.
+// (pwpp_label_obstacles; the image kernels of the clusters are pwpp_clusters.hip), k_box_moments / k_box_extents reduce the counted
+// points of every label to an oriented box (pwpp_box_obstacles; pwpp_boxes.h has the arithmetic).  They write nothing the pipeline reads.
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -42,6 +43,7 @@
 #include <type_traits>
 
 #include "pwpp_common.hpp"
+#include "pwpp_boxes.h"
 #include "pwpp_unionfind.h"
 
 namespace {
@@ -3133,6 +3135,164 @@ __global__ __launch_bounds__(kObBlock) void k_point_cluster(PwppGroundView Q, co
     point_cluster[fd.base - base_first + i] = label[(size_t)fr * (size_t)G.ny * (size_t)G.nx + cell];
 }
 
+// ---- obstacle boxes (pwpp_box_obstacles): two passes over the launch of k_obstacle_raster ------------------------------------------
+// A list entry belongs to row label[fr][cell] of its frame iff it is a COUNTED point (obstacle_point) and 0 <= row < max_boxes.
+// The coordinates are those obstacle_point looked at: the same load_point of the same index.
+__device__ __forceinline__ bool box_point(const PwppGroundView &Q, const float4 *s_zt, const PwppFrameDesc &fd, const PwppFrameResult &r,
+                                          const int32_t *out_idx, int f, int fr, int64_t e, const PwppGroundGrid &G, float h_min, float h_max,
+                                          const int32_t *label, int max_boxes, int &row, double &dx, double &dy, float &hgt, float &z) {
+    int i;
+    size_t cell;
+    if (obstacle_point(Q, s_zt, fd, r, out_idx, f, e, G, h_min, h_max, i, cell, hgt) != kObCounted) return false;
+    row = label[(size_t)fr * (size_t)G.ny * (size_t)G.nx + cell];
+    if ((unsigned)row >= (unsigned)max_boxes) return false;  // (-1, or a rank beyond the table)
+    float x, y, w;
+    load_point<true>(fd, i, x, y, z, w);
+    dx = (double)x - G.x0;  // (the doubles grid_cell starts from: both >= 0 inside the grid)
+    dy = (double)y - G.y0;
+    return true;
+}
+
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// The lanes of a wave that still hold a contribution (`todo`, wave-uniform) and name the row of the first of them: `mine` for the
+// caller's lane, the lanes taken off `todo`.  Every lane of the wave calls this together.  Returns that first lane.
+__device__ __forceinline__ int box_next_row(unsigned long long &todo, bool counted, int row, bool &mine) {
+    const int leader = __ffsll((long long)todo) - 1;
+    mine = counted && row == __shfl(row, leader, 64);
+    todo &= ~__ballot(mine);
+    return leader;
+}
+
+// First pass: the six integer sums of every row (pwpp_boxes.h), 64-bit adds.  COMBINE false: every counted lane adds to its row.
+// COMBINE true: consecutive entries mostly name one row, so the lanes of a wave that name the same row are summed first and one
+// lane adds for them -- at most 64 rounds, one per distinct row of the wave; integer sums, so the same bytes.
+template <bool COMBINE>
+__global__ __launch_bounds__(kObBlock) void k_box_moments(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
+                                                          const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
+                                                          const int32_t *label, int max_boxes, uint32_t *acc) {
+    __shared__ float4 s_zt[8];
+    fill_zone_table(Q.P, s_zt);
+    __syncthreads();
+    const int fr = blockIdx.y, f = frame_first + fr;
+    if ((unsigned)f >= (unsigned)Q.num_frames) return;
+    const PwppFrameDesc fd = frames[f];
+    const PwppFrameResult r = results[f];
+    int row = -1;
+    double dx = 0.0, dy = 0.0;
+    float hgt, z;
+    const bool counted = box_point(Q, s_zt, fd, r, out_idx, f, fr, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, label, max_boxes,
+                                   row, dx, dy, hgt, z);
+    const unsigned long long qx = counted ? (unsigned long long)pwpp_box_quantise(dx) : 0ull;  // (<= 2^20 + 1)
+    const unsigned long long qy = counted ? (unsigned long long)pwpp_box_quantise(dy) : 0ull;
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(acc + ((size_t)fr * (size_t)max_boxes + (size_t)(counted ? row : 0)) * PWPP_BOX_ACC_WORDS);
+    if (!COMBINE) {
+        if (!counted) return;
+        atomicAdd(sums + 0, 1ull);
+        atomicAdd(sums + 1, qx);
+        atomicAdd(sums + 2, qy);
+        atomicAdd(sums + 3, qx * qx);
+        atomicAdd(sums + 4, qx * qy);
+        atomicAdd(sums + 5, qy * qy);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(counted);
+    for (int round = 0; round < 64 && todo; ++round) {
+        bool mine;
+        const int leader = box_next_row(todo, counted, row, mine);
+        const uint32_t n = wave_sum<uint32_t>(mine ? 1u : 0u);  // (64 lanes of at most 2^20 + 1: below 2^27)
+        const uint32_t sx = wave_sum<uint32_t>(mine ? (uint32_t)qx : 0u), sy = wave_sum<uint32_t>(mine ? (uint32_t)qy : 0u);
+        const unsigned long long sxx = wave_sum<unsigned long long>(mine ? qx * qx : 0ull);
+        const unsigned long long sxy = wave_sum<unsigned long long>(mine ? qx * qy : 0ull);
+        const unsigned long long syy = wave_sum<unsigned long long>(mine ? qy * qy : 0ull);
+        if (lane == leader) {  // (a counted lane: `sums` is its row)
+            atomicAdd(sums + 0, (unsigned long long)n);
+            atomicAdd(sums + 1, (unsigned long long)sx);
+            atomicAdd(sums + 2, (unsigned long long)sy);
+            atomicAdd(sums + 3, sxx);
+            atomicAdd(sums + 4, sxy);
+            atomicAdd(sums + 5, syy);
+        }
+    }
+}
+
+// Second pass: the rows' axes stand in `boxes` (k_box_solve); minima and maxima of the keys of p, q, hgt and z.  COMBINE as above.
+template <bool COMBINE>
+__global__ __launch_bounds__(kObBlock) void k_box_extents(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
+                                                          const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
+                                                          const int32_t *label, int max_boxes, uint32_t *acc, const float *boxes) {
+    __shared__ float4 s_zt[8];
+    fill_zone_table(Q.P, s_zt);
+    __syncthreads();
+    const int fr = blockIdx.y, f = frame_first + fr;
+    if ((unsigned)f >= (unsigned)Q.num_frames) return;
+    const PwppFrameDesc fd = frames[f];
+    const PwppFrameResult r = results[f];
+    int row = -1;
+    double dx = 0.0, dy = 0.0;
+    float hgt = 0.0f, z = 0.0f;
+    const bool counted = box_point(Q, s_zt, fd, r, out_idx, f, fr, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, label, max_boxes,
+                                   row, dx, dy, hgt, z);
+    const size_t at = (size_t)fr * (size_t)max_boxes + (size_t)(counted ? row : 0);
+    uint32_t *keys = acc + at * PWPP_BOX_ACC_WORDS + 2 * PWPP_BOX_SUMS;
+    uint32_t k[4] = {0u, 0u, 0u, 0u};
+    if (counted) {
+        float p, q;
+        pwpp_box_project(dx, dy, boxes[at * 16 + 6], boxes[at * 16 + 7], p, q);  // (words 6, 7 of a row: ax, ay)
+        k[0] = pwpp_height_key(p), k[1] = pwpp_height_key(q), k[2] = pwpp_height_key(hgt), k[3] = pwpp_height_key(z);
+    }
+    if (!COMBINE) {
+        if (!counted) return;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            atomicMin(keys + 2 * j, k[j]);
+            atomicMax(keys + 2 * j + 1, k[j]);
+        }
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(counted);
+    for (int round = 0; round < 64 && todo; ++round) {
+        bool mine;
+        const int leader = box_next_row(todo, counted, row, mine);
+        uint32_t lo[4], hi[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            lo[j] = wave_min(mine ? k[j] : PWPP_BOX_KEY_NO_MIN);
+            hi[j] = wave_max(mine ? k[j] : PWPP_BOX_KEY_NO_MAX);
+        }
+        if (lane == leader) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                atomicMin(keys + 2 * j, lo[j]);
+                atomicMax(keys + 2 * j + 1, hi[j]);
+            }
+        }
+    }
+}
+
 // the keys of `top` as floats, in place: empty = the quiet NaN.  Quads as in k_obstacle_fill.
 __global__ __launch_bounds__(kObBlock) void k_obstacle_top(int64_t cells, uint32_t *top) {
     const int64_t t = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
@@ -3239,6 +3399,24 @@ extern "C" int pwpp_launch_point_cluster(const PwppGroundView *view, const PwppF
     if (max_nonground > 0)
         hipLaunchKernelGGL(k_point_cluster, dim3((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames), dim3(kObBlock), 0, stream,
                            *view, descs, results, out_idx, *grid, frame_first, h_min, h_max, label, point_cluster, base_first);
+    return (int)hipGetLastError();
+}
+
+// The two point passes of pwpp_box_obstacles (arguments as above).  pass 0: the sums of every row into `acc` (PWPP_BOX_ACC_WORDS words
+// per row, initialised by pwpp_launch_box_rows); pass 1: the keys, against the axes that stand in `boxes`.  combine: sum equal rows
+// inside a wave first.
+extern "C" int pwpp_launch_box_pass(int pass, int combine, const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
+                                    const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min,
+                                    float h_max, const int32_t *label, int max_boxes, uint32_t *acc, const void *boxes, hipStream_t stream) {
+    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+    if (max_nonground <= 0) return (int)hipGetLastError();
+    const dim3 g((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames);
+    if (pass == 0)
+        hipLaunchKernelGGL(combine ? k_box_moments<true> : k_box_moments<false>, g, dim3(kObBlock), 0, stream, *view, descs, results, out_idx, *grid,
+                           frame_first, h_min, h_max, label, max_boxes, acc);
+    else
+        hipLaunchKernelGGL(combine ? k_box_extents<true> : k_box_extents<false>, g, dim3(kObBlock), 0, stream, *view, descs, results, out_idx, *grid,
+                           frame_first, h_min, h_max, label, max_boxes, acc, static_cast<const float *>(boxes));
     return (int)hipGetLastError();
 }
 

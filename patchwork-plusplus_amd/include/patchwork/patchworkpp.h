@@ -26,6 +26,7 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pwpp.h"
@@ -373,6 +374,28 @@ public:
         }
         c.count = n;
         return c;
+    }
+    // ... and every cluster as an oriented box (pwpp_box_obstacles on the labels above): centre, heading, length and width in
+    // metres, the spread along and across, the extent in height over ground and in z.  boxes[r] belongs to clusters[r].
+    struct ObstacleBoxes {
+        std::vector<int32_t> label;                   // ny x nx, row-major
+        std::vector<pwpp_obstacle_cluster> clusters;  // one row per cluster
+        std::vector<pwpp_obstacle_box> boxes;         // one box per cluster
+        int count = 0;                                // clusters.size() == boxes.size()
+    };
+    ObstacleBoxes getObstacleBoxes(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count = 1, int connectivity = 8,
+                                   bool ground_only = false) {
+        ObstacleClusters c = getObstacleClusters(x0, y0, cell, nx, ny, h_min, h_max, min_count, connectivity, ground_only);
+        ObstacleBoxes b;
+        b.count = c.count;
+        if (c.count > 0) {
+            const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+            b.boxes.resize((size_t)c.count);
+            check(pwpp_box_obstacles(h_, &g, h_min, h_max, 0, 1, PWPP_MEM_HOST, c.label.data(), b.boxes.data(), c.count));
+        }
+        b.label = std::move(c.label);
+        b.clusters = std::move(c.clusters);
+        return b;
     }
 #ifdef PWPP_HAVE_EIGEN
     std::vector<pwpp_ground_sample> queryGround(const Eigen::MatrixX3f &positions) {

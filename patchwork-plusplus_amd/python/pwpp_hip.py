@@ -74,6 +74,14 @@ class ObstacleCluster(ctypes.Structure):  # pwpp_obstacle_cluster (48 bytes)
 
 OBSTACLE_CLUSTER_DTYPE = np.dtype([("first_cell", "<i4"), ("cells", "<i4"), ("points", "<i4"), ("ix_min", "<i4"), ("ix_max", "<i4"),
                                    ("iy_min", "<i4"), ("iy_max", "<i4"), ("top", "<f4"), ("sum_ix", "<i8"), ("sum_iy", "<i8")])
+_BOX_FLOATS = ("mean_x", "mean_y", "cx", "cy", "ax", "ay", "length", "width", "sigma_long", "sigma_short", "h_min", "h_max", "z_min", "z_max")
+
+
+class ObstacleBox(ctypes.Structure):  # pwpp_obstacle_box (64 bytes)
+    _fields_ = [("points", ctypes.c_int32), ("pad_", ctypes.c_int32)] + [(n, ctypes.c_float) for n in _BOX_FLOATS]
+
+
+OBSTACLE_BOX_DTYPE = np.dtype([("points", "<i4"), ("pad_", "<i4")] + [(n, "<f4") for n in _BOX_FLOATS])
 GROUND_SAMPLE_DTYPE = np.dtype([("patch", "<i4"), ("decision", "<i4"), ("ground_z", "<f4"), ("distance", "<f4")])
 GRID_GROUND_ONLY = 1
 
@@ -175,6 +183,9 @@ def load():
         if hasattr(L, "pwpp_label_grid"):  # (as above: an older build has no obstacle clusters)
             L.pwpp_label_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, ci]
             L.pwpp_label_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp]
+        if hasattr(L, "pwpp_box_obstacles"):  # (as above: an older build has no obstacle boxes)
+            L.pwpp_box_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, ci]
+            L.pwpp_box_points.argtypes = [ctypes.POINTER(GroundGrid), vp, vp, vp, ctypes.c_int64, vp, ci]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -241,6 +252,25 @@ def transform_points(T, xyz):
     if L.pwpp_transform_points(_vp(T), _vp(xyz) if xyz.size else None, xyz.shape[0], _vp(out) if out.size else None) < 0:
         raise PwppError(L.pwpp_last_error().decode())
     return out
+
+
+def box_points(x0, y0, cell, nx, ny, xyz, hgt, row, max_boxes):
+    """pwpp_box_points: the (max_boxes,) rows (OBSTACLE_BOX_DTYPE) of pwpp_box_obstacles' arithmetic for a caller's own points --
+    xyz (m, 3) float32, hgt (m,) float32 heights over ground, row (m,) int32.  Skipped: a row outside [0, max_boxes), a NaN hgt,
+    a point outside the grid.  Host only; no GPU needed."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("xyz: an (m, 3) array expected")
+    hgt, row = np.ascontiguousarray(hgt, np.float32).reshape(-1), np.ascontiguousarray(row, np.int32).reshape(-1)
+    if len(hgt) != len(xyz) or len(row) != len(xyz):
+        raise ValueError("hgt and row: one value per point expected")
+    g = GroundGrid(float(x0), float(y0), float(cell), int(nx), int(ny), 0, 0)
+    boxes = np.zeros(max(int(max_boxes), 0), OBSTACLE_BOX_DTYPE)
+    L = load()
+    ptr = lambda a: _vp(a) if a.size else None
+    if L.pwpp_box_points(ctypes.byref(g), ptr(xyz), ptr(hgt), ptr(row), len(xyz), ptr(boxes), int(max_boxes)) < 0:
+        raise PwppError(L.pwpp_last_error().decode())
+    return boxes
 
 
 class Handle:
@@ -806,6 +836,27 @@ class Handle:
                                                  int(frame_first), frames, MEM_DEVICE, ctypes.c_void_p(label_ptr), ctypes.c_void_p(count_ptr or None),
                                                  ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(clusters_ptr or None),
                                                  ctypes.c_void_p(n_clusters_ptr or None), int(max_clusters), ctypes.c_void_p(point_cluster_ptr or None)))
+
+    def box_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_boxes, frame_first=0, frames=None, ground_only=False):
+        """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as oriented
+        boxes, for frames of the last estimate call: the (frames, max_boxes) structured table (OBSTACLE_BOX_DTYPE).  Row r of a
+        frame takes the counted points whose cell is labelled r; other labels (-1, >= max_boxes) are skipped; a row nobody names
+        has points 0 and NaN floats (include/pwpp.h has the arithmetic)."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        label = np.ascontiguousarray(label, np.int32)
+        if label.shape not in ((max(frames, 0), g.ny, g.nx), (g.ny, g.nx)) or (label.ndim == 2 and frames != 1):
+            raise ValueError("label: a (frames, ny, nx) image expected")
+        boxes = np.zeros((max(frames, 0), max(int(max_boxes), 0)), OBSTACLE_BOX_DTYPE)
+        self._check(self._L.pwpp_box_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_HOST,
+                                               _vp(label) if label.size else None, _vp(boxes) if boxes.size else None, int(max_boxes)))
+        return boxes
+
+    def box_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, label_ptr, boxes_ptr, max_boxes, frame_first=0, frames=None, ground_only=False):
+        """box_obstacles on device memory: addresses of the (frames, ny, nx) int32 label image and of the (frames, max_boxes) table
+        of 64-byte rows, both 4-byte aligned.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_box_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
+                                               ctypes.c_void_p(label_ptr or None), ctypes.c_void_p(boxes_ptr or None), int(max_boxes)))
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

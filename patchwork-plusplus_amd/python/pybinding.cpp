@@ -139,6 +139,9 @@ PYBIND11_MODULE(pypatchworkpp, m) {
 
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_cluster, first_cell, cells, points, ix_min, ix_max, iy_min, iy_max, top, sum_ix, sum_iy);
 
+    PYBIND11_NUMPY_DTYPE(pwpp_obstacle_box, points, pad_, mean_x, mean_y, cx, cy, ax, ay, length, width, sigma_long, sigma_short, h_min, h_max, z_min,
+                         z_max);
+
     py::class_<PatchWorkpp>(m, "patchworkpp")
         .def(py::init<Params>())
         .def(py::init<Params, int>(), py::arg("params"), py::arg("device"))
@@ -178,6 +181,20 @@ PYBIND11_MODULE(pypatchworkpp, m) {
                  py::array_t<pwpp_obstacle_cluster> table((py::ssize_t)c.clusters.size());  // a structured array: one field per member
                  if (!c.clusters.empty()) std::memcpy(table.mutable_data(), c.clusters.data(), c.clusters.size() * sizeof(pwpp_obstacle_cluster));
                  return py::make_tuple(label, table, c.count);
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("min_count") = 1, py::arg("connectivity") = 8, py::arg("ground_only") = false)
+        .def("getObstacleBoxes",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int connectivity,
+                bool ground_only) {
+                 const PatchWorkpp::ObstacleBoxes b = s.getObstacleBoxes(x0, y0, cell, nx, ny, h_min, h_max, min_count, connectivity, ground_only);
+                 py::array_t<int32_t> label({(py::ssize_t)(ny > 0 ? ny : 0), (py::ssize_t)(nx > 0 ? nx : 0)});
+                 if (!b.label.empty()) std::memcpy(label.mutable_data(), b.label.data(), b.label.size() * sizeof(int32_t));
+                 py::array_t<pwpp_obstacle_cluster> table((py::ssize_t)b.clusters.size());
+                 if (!b.clusters.empty()) std::memcpy(table.mutable_data(), b.clusters.data(), b.clusters.size() * sizeof(pwpp_obstacle_cluster));
+                 py::array_t<pwpp_obstacle_box> boxes((py::ssize_t)b.boxes.size());
+                 if (!b.boxes.empty()) std::memcpy(boxes.mutable_data(), b.boxes.data(), b.boxes.size() * sizeof(pwpp_obstacle_box));
+                 return py::make_tuple(label, table, boxes, b.count);
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("connectivity") = 8, py::arg("ground_only") = false)
