@@ -25,34 +25,6 @@
 #include "pwpp_boxes.h"
 #include "pwpp_dev.h"
 
-extern "C" int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev, hipStream_t aux,
-                                    hipEvent_t aux_fork, hipEvent_t aux_join, unsigned long long *order_a, unsigned long long *order_b,
-                                    int stages);
-extern "C" int pwpp_launch_clear(const PwppBatch *batch, hipStream_t stream);
-extern "C" int pwpp_launch_k5_tail(const PwppBatch *batch, hipStream_t aux, hipEvent_t aux_fork, hipEvent_t aux_join);
-extern "C" int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream);
-extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, int count, float *out, hipStream_t stream);
-extern "C" int pwpp_launch_gather_records(const PwppFrameDesc *fd, const int *idx, int count, void *out, int path, hipStream_t stream);
-extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, int rows_valid, const float *xyz, const int32_t *frame, int64_t m, void *out,
-                                        hipStream_t stream);
-extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_valid, const PwppGroundGrid *grid, int frame_first, int frames,
-                                         float *height, int32_t *patch, hipStream_t stream);
-extern "C" int pwpp_launch_point_cluster(const PwppGroundView *view, const PwppFrameDesc *descs, const PwppFrameResult *results, const int32_t *out_idx,
-                                         const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min, float h_max,
-                                         const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
-extern "C" int pwpp_launch_box_pass(int pass, int combine, const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs,
-                                    const PwppFrameResult *results, const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames,
-                                    int max_nonground, float h_min, float h_max, const int32_t *label, int max_boxes, uint32_t *acc, const void *boxes,
-                                    hipStream_t stream);
-// pwpp_clusters.hip
-extern "C" int pwpp_launch_box_rows(int step, int64_t rows, uint32_t *acc, double x0, double y0, void *boxes, hipStream_t stream);
-extern "C" size_t pwpp_cluster_work_words(int nx, int ny, int frames);
-extern "C" int pwpp_launch_label_grid(int nx, int ny, int frames, const int32_t *count, const float *top, int min_count, int connectivity, int path,
-                                      int32_t *label, void *clusters, int32_t *n_clusters, int max_clusters, uint32_t *work, hipStream_t stream);
-extern "C" int pwpp_launch_obstacle_raster(const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
-                                           const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground,
-                                           float h_min, float h_max, int32_t *count, float *top, int32_t *unref, hipStream_t stream);
-
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
 static_assert(sizeof(pwpp_ground_sample) == sizeof(PwppGroundSample) && sizeof(pwpp_ground_sample) == 16, "pwpp_ground_sample must mirror PwppGroundSample");
 static_assert(sizeof(pwpp_ground_grid) == sizeof(PwppGroundGrid) && sizeof(pwpp_ground_grid) == 40, "pwpp_ground_grid must mirror PwppGroundGrid");
@@ -267,10 +239,10 @@ struct pwpp_handle {
     DevBuf<uint8_t> d_records{bufs, kPerBatch};  // [total points][record_bytes] + 64: the records of the listed points, rows laid out like d_out
     // ground queries of the last call's results (pwpp_query_ground, pwpp_rasterize_ground): nothing is allocated before the first one
     DevBuf<int32_t> d_ground_rows{bufs, kPerBatch};   // [frames][B] bin -> row of the last call (PwppGroundView.rows)
-    DevBuf<uint32_t> d_ground_stage{bufs, kPerBatch};  // PWPP_MEM_HOST queries: the output, then the input, in 4-byte words
+    DevBuf<uint32_t> d_ground_stage{bufs, kPerBatch};  // PWPP_MEM_HOST queries: the sections of the call, in 4-byte words (Staging)
     // obstacle clusters (pwpp_label_grid, pwpp_label_obstacles): nothing is allocated before the first of them
     DevBuf<uint32_t> d_clusters{bufs, kPerBatch};  // the cluster buffer, in 4-byte words: the kernels' working image and chunk counts, then whatever
-                                                   // images, table, counts and point ids the call stages or keeps (cluster_plan)
+                                                   // images, table, counts and point ids the call stages or keeps (Staging)
     int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
@@ -473,7 +445,6 @@ void fill_default_state(const pwpp_handle *h, PwppStateScalar &s) {
 }
 
 int finish_pending(pwpp_handle *h, bool lists_only = false);
-extern "C" const char *pwpp_big_batch_plan(int max_n, int num_bins, int wide);  // pwpp_fit.hip
 
 // every stream a schedule may have put work on (error paths, pwpp_destroy): the main stream alone is not the join of a
 // schedule that stopped half way
@@ -1193,6 +1164,64 @@ int copy_output(pwpp_handle *h, Output which, int frame, bool whole_batch, void 
     }
     return PWPP_OK;
 }
+
+// One call's arrays in a staging buffer of the handle, for both memory kinds.  The call declares its sections in buffer order:
+// 4-byte words, the caller's pointer (null: an optional array that is absent -- a null device pointer, no copy; it keeps the room
+// of its words, so a call declares it with 0 words where none is wanted) and what becomes of it.  PWPP_MEM_DEVICE: the kernels work
+// on the caller's pointers, only the kKept sections lie in the buffer, end() notes the enqueued work.  PWPP_MEM_HOST: every section
+// lies in the buffer, begin() uploads the kIn ones, end() downloads the kOut ones and waits.  `align`: every section starts at a
+// multiple of so many words.
+class Staging {
+  public:
+    enum Dir { kIn, kOut, kKept };  // read by the kernels | written by them | theirs alone: in the buffer whatever the memory kind
+    Staging(pwpp_handle *h, DevBuf<uint32_t> &buf, int mem, size_t align = 1) : h_(h), buf_(buf), host_(mem == PWPP_MEM_HOST), align_(align) {}
+    int add(size_t words, const void *user, Dir dir) {  // (at most kMaxSections per call)
+        sec_[n_] = Section{words_, words, user, dir};
+        if (dir == kKept || host_) words_ += (words + align_ - 1) / align_ * align_;
+        return n_++;
+    }
+    int begin() {
+        const int rc = buf_.ensure(words_);
+        if (rc) return rc;
+        for (int k = 0; k < n_ && host_; ++k)
+            if (sec_[k].dir == kIn && sec_[k].user && sec_[k].words > 0)
+                HIPCHK(hipMemcpyAsync(buf_.p + sec_[k].at, sec_[k].user, sec_[k].words * 4, hipMemcpyHostToDevice, h_->stream));
+        return PWPP_OK;
+    }
+    template <class T>
+    T *dev(int k) const {  // (after begin(): the buffer may have moved)
+        const Section &c = sec_[k];
+        if (c.dir != kKept && (!host_ || !c.user)) return static_cast<T *>(const_cast<void *>(c.user));
+        return reinterpret_cast<T *>(buf_.p + c.at);
+    }
+    int end() {
+        if (!host_) {
+            h_->ground_query_queued = true;
+            return PWPP_OK;
+        }
+        for (int k = 0; k < n_; ++k)
+            if (sec_[k].dir == kOut && sec_[k].user && sec_[k].words > 0)
+                HIPCHK(hipMemcpyAsync(const_cast<void *>(sec_[k].user), buf_.p + sec_[k].at, sec_[k].words * 4, hipMemcpyDeviceToHost, h_->stream));
+        HIPCHK(hipStreamSynchronize(h_->stream));
+        return PWPP_OK;
+    }
+
+  private:
+    static constexpr int kMaxSections = 8;
+    struct Section {
+        size_t at, words;
+        const void *user;
+        Dir dir;
+    };
+    pwpp_handle *h_;
+    DevBuf<uint32_t> &buf_;
+    const bool host_;
+    const size_t align_;
+    size_t words_ = 0;
+    int n_ = 0;
+    Section sec_[kMaxSections];
+};
+constexpr size_t kClusterAlign = 4;  // the cluster buffer's sections start at multiples of 16 bytes (the table's 64-bit sums need 8)
 
 int set_output(pwpp_handle *h, Output which, int on) {
     const int rc = enter(h);
@@ -2225,7 +2254,8 @@ int pwpp_get_device_records(pwpp_handle *h, const void **out, int32_t *record_by
 
 // ---- ground queries: the last call's planes at arbitrary positions -------------------------------------------------------
 namespace {
-// the last call's results as the ground-query kernels see them; the bin -> row table is allocated here, on the first query
+// The last call's results as the ground-query kernels see them.  The bin -> row table is allocated here, on the first query, and
+// computed here: once per estimate call, before the first kernel that reads the rows.
 int ground_view(pwpp_handle *h, PwppGroundView &v) {
     const int32_t *const held = h->d_ground_rows.p;
     const int rc = h->d_ground_rows.ensure((size_t)h->frames * (size_t)h->dp.num_bins);
@@ -2238,12 +2268,18 @@ int ground_view(pwpp_handle *h, PwppGroundView &v) {
     v.rows = h->d_ground_rows.p;
     v.num_frames = h->frames;
     v.debug = h->debug_flags;
+    if (!h->ground_rows_valid) {
+        const int lrc = pwpp_launch_ground_rows(&v, h->stream);
+        if (lrc != 0) return launch_failed(h, lrc);
+        h->ground_rows_valid = true;
+    }
     return PWPP_OK;
 }
 int ground_mem(int mem) {
     if (mem == PWPP_MEM_HOST || mem == PWPP_MEM_DEVICE) return PWPP_OK;
     return fail(PWPP_E_ARG, "mem %d: the ground queries take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
 }
+
 }  // namespace
 
 int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, int64_t m, int mem, pwpp_ground_sample *out) {
@@ -2254,33 +2290,14 @@ int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, in
     if (rc) return rc;
     if ((rc = check_frame(h, 0))) return rc;
     if (m == 0) return PWPP_OK;
-    PwppGroundView v;
-    const float *d_xyz = xyz;
-    const int32_t *d_frame = frame;
-    void *d_out = out;
     const size_t um = (size_t)m;
-    if (mem == PWPP_MEM_HOST) {  // the output first: 16-byte aligned for the kernel's wide stores
-        if ((rc = h->d_ground_stage.ensure(um * 8))) return rc;
-        uint32_t *w = h->d_ground_stage.p;
-        d_out = w;
-        d_xyz = reinterpret_cast<const float *>(w + um * 4);
-        HIPCHK(hipMemcpyAsync(w + um * 4, xyz, um * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if (frame) {
-            d_frame = reinterpret_cast<const int32_t *>(w + um * 7);
-            HIPCHK(hipMemcpyAsync(w + um * 7, frame, um * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        }
-    }
+    Staging st(h, h->d_ground_stage, mem);  // the output first: 16-byte aligned for the kernel's wide stores
+    const int s_out = st.add(um * 4, out, Staging::kOut), s_xyz = st.add(um * 3, xyz, Staging::kIn), s_frame = st.add(um, frame, Staging::kIn);
+    if ((rc = st.begin())) return rc;
+    PwppGroundView v;
     if ((rc = ground_view(h, v))) return rc;
-    const int lrc = pwpp_launch_ground_query(&v, h->ground_rows_valid, d_xyz, d_frame, m, d_out, h->stream);
-    if (lrc != 0) return launch_failed(h, lrc);
-    h->ground_rows_valid = true;
-    if (mem == PWPP_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(out, d_out, um * sizeof(pwpp_ground_sample), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        h->ground_query_queued = true;
-    }
-    return PWPP_OK;
+    const int lrc = pwpp_launch_ground_query(&v, st.dev<const float>(s_xyz), st.dev<const int32_t>(s_frame), m, st.dev<void>(s_out), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
 namespace {
@@ -2300,6 +2317,37 @@ int ground_grid_args(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first,
     cells = (size_t)per_frame * (size_t)frames;
     return PWPP_OK;
 }
+
+// ... of the grid's flags and the height band of a counted point (the three entry points over the non-ground lists) ...
+int obstacle_band_args(const pwpp_ground_grid *g, float h_min, float h_max) {
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
+    return PWPP_OK;
+}
+
+// ... and of one frame's cells where a cell index is an int32 (labels, the cluster table's first_cell)
+int frame_cells_args(int nx, int ny) {
+    if ((int64_t)nx * (int64_t)ny > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", nx, ny);
+    return PWPP_OK;
+}
+
+// "The non-ground lists of frames [frame_first, frame_first + frames) of the last call over the grid g", as the kernels take it
+// (PwppObstacleScan); the arguments are checked.  Everything those kernels read is on the device since the call: the frame
+// descriptors (d_frames), this call's copy of the frame counters (d_results), the lists (d_out) -- and the INPUT, which after a
+// PWPP_MEM_DEVICE call is the caller's buffer (the lifetime rule of pwpp_get_nonground_xyz).
+int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, PwppObstacleScan &s) {
+    std::memset(&s, 0, sizeof(s));
+    const int rc = ground_view(h, s.Q);
+    if (rc) return rc;
+    s.descs = h->d_frames.p;
+    s.results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
+    s.out_idx = h->d_out.p;
+    std::memcpy(&s.G, g, sizeof(s.G));
+    s.frame_first = frame_first, s.frames = frames;
+    for (int f = frame_first; f < frame_first + frames; ++f) s.max_nonground = std::max(s.max_nonground, h->h_results.p[f].n_nonground);
+    s.h_min = h_min, s.h_max = h_max;
+    return PWPP_OK;
+}
 }  // namespace
 
 int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, float *height, int32_t *patch) {
@@ -2308,108 +2356,66 @@ int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_f
     size_t cells = 0;
     int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
     if (rc) return rc;
+    Staging st(h, h->d_ground_stage, mem);
+    const int s_height = st.add(cells, height, Staging::kOut), s_patch = st.add(patch ? cells : 0, patch, Staging::kOut);
+    if ((rc = st.begin())) return rc;
     PwppGroundView v;
     PwppGroundGrid grid;
     std::memcpy(&grid, g, sizeof(grid));
-    float *d_height = height;
-    int32_t *d_patch = patch;
-    if (mem == PWPP_MEM_HOST) {
-        if ((rc = h->d_ground_stage.ensure(cells * (patch ? 2 : 1)))) return rc;
-        d_height = reinterpret_cast<float *>(h->d_ground_stage.p);
-        d_patch = patch ? reinterpret_cast<int32_t *>(h->d_ground_stage.p + cells) : nullptr;
-    }
     if ((rc = ground_view(h, v))) return rc;
-    const int lrc = pwpp_launch_ground_raster(&v, h->ground_rows_valid, &grid, frame_first, frames, d_height, d_patch, h->stream);
-    if (lrc != 0) return launch_failed(h, lrc);
-    h->ground_rows_valid = true;
-    if (mem == PWPP_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(height, d_height, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (patch) HIPCHK(hipMemcpyAsync(patch, d_patch, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        h->ground_query_queued = true;
-    }
-    return PWPP_OK;
+    const int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), st.dev<int32_t>(s_patch), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
-// The non-ground points of the last call per cell of the grid.  Everything the kernel reads is on the device since the call: the
-// frame descriptors (d_frames), this call's copy of the frame counters (d_results), the lists (d_out) -- and the INPUT, which after
-// a PWPP_MEM_DEVICE call is the caller's buffer (the lifetime rule of pwpp_get_nonground_xyz).
+// The non-ground points of the last call per cell of the grid: count, then top, then unref.
 int pwpp_rasterize_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem,
                              int32_t *count, float *top, int32_t *unref) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !count) return fail(PWPP_E_ARG, "null %s", g ? "count image" : "grid");
-    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
-    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
-    size_t cells = 0;
-    int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
+    int rc = obstacle_band_args(g, h_min, h_max);
     if (rc) return rc;
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
-    int32_t *d_count = count, *d_unref = unref;
-    float *d_top = top;
-    if (mem == PWPP_MEM_HOST) {  // count, then top, then unref (16-byte aligned when cells is a multiple of 4; the kernels do not need it)
-        if ((rc = h->d_ground_stage.ensure(cells * (size_t)(1 + (top ? 1 : 0) + (unref ? 1 : 0))))) return rc;
-        uint32_t *w = h->d_ground_stage.p;
-        d_count = reinterpret_cast<int32_t *>(w);
-        d_top = top ? reinterpret_cast<float *>(w + cells) : nullptr;
-        d_unref = unref ? reinterpret_cast<int32_t *>(w + cells * (size_t)(top ? 2 : 1)) : nullptr;
-    }
-    if ((rc = ground_view(h, v))) return rc;
-    int max_nonground = 0;
-    for (int f = frame_first; f < frame_first + frames; ++f) {
-        const int nn = h->h_results.p[f].n_nonground;
-        max_nonground = nn > max_nonground ? nn : max_nonground;
-    }
-    const PwppFrameResult *results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
-    const int lrc = pwpp_launch_obstacle_raster(&v, h->ground_rows_valid, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground,
-                                                h_min, h_max, d_count, d_top, d_unref, h->stream);
-    if (lrc != 0) return launch_failed(h, lrc);
-    h->ground_rows_valid = true;
-    if (mem == PWPP_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(count, d_count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (top) HIPCHK(hipMemcpyAsync(top, d_top, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (unref) HIPCHK(hipMemcpyAsync(unref, d_unref, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        h->ground_query_queued = true;
-    }
-    return PWPP_OK;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    Staging st(h, h->d_ground_stage, mem);
+    const int s_count = st.add(cells, count, Staging::kOut), s_top = st.add(top ? cells : 0, top, Staging::kOut);
+    const int s_unref = st.add(unref ? cells : 0, unref, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    const int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), st.dev<float>(s_top), st.dev<int32_t>(s_unref), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
 // ---- obstacle clusters: connected occupied cells of an obstacle grid ------------------------------------------------------------
 namespace {
-// what both entry points check of an image and a table, before the device is touched
-int cluster_args(int nx, int ny, int frames, int mem, int min_count, int connectivity, const void *clusters, int max_clusters, size_t &cells) {
-    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
-    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
-    if (per_frame > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", nx, ny);
-    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
+// what both entry points check of min_count, connectivity and the table ...
+int cluster_param_args(int mem, int min_count, int connectivity, const void *clusters, int max_clusters) {
     if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
     if (connectivity != 4 && connectivity != 8) return fail(PWPP_E_ARG, "connectivity %d: 4 or 8 expected", connectivity);
     if (max_clusters < 0) return fail(PWPP_E_ARG, "max_clusters %d", max_clusters);
     if (max_clusters > 0 && !clusters) return fail(PWPP_E_ARG, "null cluster table with max_clusters %d", max_clusters);
     if (mem == PWPP_MEM_DEVICE && (reinterpret_cast<uintptr_t>(clusters) & 7u)) return fail(PWPP_E_ARG, "the cluster table must be 8-byte aligned");
+    return PWPP_OK;
+}
+
+// ... and pwpp_label_grid of its images, before the device is touched
+int cluster_args(int nx, int ny, int frames, int mem, int min_count, int connectivity, const void *clusters, int max_clusters, size_t &cells) {
+    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
+    int rc = frame_cells_args(nx, ny);
+    if (rc) return rc;
+    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
+    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
+    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
     if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle clusters take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
     cells = (size_t)per_frame * (size_t)frames;
     return PWPP_OK;
 }
 
-// The cluster buffer of one call: the kernels' working words first, then the sections the call asks for, each starting at a
-// multiple of four words (16 bytes: the table's 64-bit sums need 8).
-struct ClusterPlan {
-    size_t words = 0;
-    size_t take(size_t n) {
-        const size_t at = words;
-        words += (n + 3) & ~(size_t)3;
-        return at;
-    }
-};
 constexpr size_t kClusterRowWords = sizeof(pwpp_obstacle_cluster) / 4;
 static_assert(sizeof(pwpp_obstacle_cluster) == 48, "pwpp_obstacle_cluster is 48 bytes");
 }  // namespace
 
+// The cluster buffer of a call: the kernels' working words first, then the sections the call stages.
 int pwpp_label_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, const float *top, int min_count, int connectivity,
                     int32_t *label, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
@@ -2418,39 +2424,16 @@ int pwpp_label_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const i
     int rc = cluster_args(nx, ny, frames, mem, min_count, connectivity, clusters, max_clusters, cells);
     if (rc) return rc;
     if ((rc = enter(h, true))) return rc;  // (like a getter: the call in flight lands first; no results are needed)
-    const size_t rows = (size_t)frames * (size_t)max_clusters;
-    ClusterPlan plan;
-    const size_t o_work = plan.take(pwpp_cluster_work_words(nx, ny, frames));
-    const bool host = mem == PWPP_MEM_HOST;
-    const size_t o_count = host ? plan.take(cells) : 0, o_top = host && top ? plan.take(cells) : 0, o_label = host ? plan.take(cells) : 0;
-    const size_t o_table = host ? plan.take(rows * kClusterRowWords) : 0, o_n = host ? plan.take((size_t)frames) : 0;
-    if ((rc = h->d_clusters.ensure(plan.words))) return rc;
-    uint32_t *w = h->d_clusters.p;
-    const int32_t *d_count = count;
-    const float *d_top = top;
-    int32_t *d_label = label, *d_n = n_clusters;
-    void *d_table = clusters;
-    if (host) {
-        d_count = reinterpret_cast<const int32_t *>(w + o_count);
-        d_top = top ? reinterpret_cast<const float *>(w + o_top) : nullptr;
-        d_label = reinterpret_cast<int32_t *>(w + o_label);
-        d_table = w + o_table;
-        d_n = reinterpret_cast<int32_t *>(w + o_n);
-        HIPCHK(hipMemcpyAsync(w + o_count, count, cells * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        if (top) HIPCHK(hipMemcpyAsync(w + o_top, top, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
-    const int lrc = pwpp_launch_label_grid(nx, ny, frames, d_count, d_top, min_count, connectivity, h->clusters_path, d_label, d_table, d_n, max_clusters,
-                                           w + o_work, h->stream);
-    if (lrc != 0) return launch_failed(h, lrc);
-    if (host) {
-        HIPCHK(hipMemcpyAsync(label, d_label, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (rows > 0) HIPCHK(hipMemcpyAsync(clusters, d_table, rows * sizeof(pwpp_obstacle_cluster), hipMemcpyDeviceToHost, h->stream));
-        if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_n, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        h->ground_query_queued = true;
-    }
-    return PWPP_OK;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(pwpp_cluster_work_words(nx, ny, frames), nullptr, Staging::kKept);
+    const int s_count = st.add(cells, count, Staging::kIn), s_top = st.add(top ? cells : 0, top, Staging::kIn), s_label = st.add(cells, label, Staging::kOut);
+    const int s_table = st.add((size_t)frames * (size_t)max_clusters * kClusterRowWords, clusters, Staging::kOut);
+    const int s_n = st.add((size_t)frames, n_clusters, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    const int lrc = pwpp_launch_label_grid(nx, ny, frames, st.dev<const int32_t>(s_count), st.dev<const float>(s_top), min_count, connectivity,
+                                           h->clusters_path, st.dev<int32_t>(s_label), st.dev<void>(s_table), st.dev<int32_t>(s_n), max_clusters,
+                                           st.dev<uint32_t>(s_work), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
 // pwpp_rasterize_obstacles, pwpp_label_grid on its two images and the per-point scatter, enqueued as one sequence.  An image the
@@ -2460,68 +2443,35 @@ int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
                          int32_t *point_cluster) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !label) return fail(PWPP_E_ARG, "null %s", g ? "label image" : "grid");
-    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
-    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
-    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
-    if (connectivity != 4 && connectivity != 8) return fail(PWPP_E_ARG, "connectivity %d: 4 or 8 expected", connectivity);
-    if (max_clusters < 0) return fail(PWPP_E_ARG, "max_clusters %d", max_clusters);
-    if (max_clusters > 0 && !clusters) return fail(PWPP_E_ARG, "null cluster table with max_clusters %d", max_clusters);
-    if (mem == PWPP_MEM_DEVICE && (reinterpret_cast<uintptr_t>(clusters) & 7u)) return fail(PWPP_E_ARG, "the cluster table must be 8-byte aligned");
-    size_t cells = 0;
-    int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
+    int rc = obstacle_band_args(g, h_min, h_max);
     if (rc) return rc;
-    if ((int64_t)g->nx * (int64_t)g->ny > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", g->nx, g->ny);
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
+    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
     const int64_t base_first = h->h_base.p[frame_first];
     const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
-    const size_t rows = (size_t)frames * (size_t)max_clusters;
-    const bool host = mem == PWPP_MEM_HOST;
-    ClusterPlan plan;
-    const size_t o_work = plan.take(pwpp_cluster_work_words(g->nx, g->ny, frames));
-    const size_t o_count = host || !count ? plan.take(cells) : 0, o_top = host || !top ? plan.take(cells) : 0, o_label = host ? plan.take(cells) : 0;
-    const size_t o_table = host ? plan.take(rows * kClusterRowWords) : 0, o_n = host ? plan.take((size_t)frames) : 0, o_pc = host ? plan.take(points) : 0;
-    if ((rc = h->d_clusters.ensure(plan.words))) return rc;
-    uint32_t *w = h->d_clusters.p;
-    int32_t *d_count = host || !count ? reinterpret_cast<int32_t *>(w + o_count) : count;
-    float *d_top = host || !top ? reinterpret_cast<float *>(w + o_top) : top;
-    int32_t *d_label = host ? reinterpret_cast<int32_t *>(w + o_label) : label;
-    void *d_table = host ? static_cast<void *>(w + o_table) : static_cast<void *>(clusters);
-    int32_t *d_n = host ? reinterpret_cast<int32_t *>(w + o_n) : n_clusters;
-    int32_t *d_pc = host ? reinterpret_cast<int32_t *>(w + o_pc) : point_cluster;
-    if ((rc = ground_view(h, v))) return rc;
-    int max_nonground = 0;
-    for (int f = frame_first; f < frame_first + frames; ++f) {
-        const int nn = h->h_results.p[f].n_nonground;
-        max_nonground = nn > max_nonground ? nn : max_nonground;
-    }
-    const PwppFrameResult *results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
-    int lrc = pwpp_launch_obstacle_raster(&v, h->ground_rows_valid, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground, h_min,
-                                          h_max, d_count, d_top, nullptr, h->stream);
-    if (lrc != 0) return launch_failed(h, lrc);
-    h->ground_rows_valid = true;
-    lrc = pwpp_launch_label_grid(g->nx, g->ny, frames, d_count, d_top, min_count, connectivity, h->clusters_path, d_label, d_table, d_n, max_clusters,
-                                 w + o_work, h->stream);
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(pwpp_cluster_work_words(g->nx, g->ny, frames), nullptr, Staging::kKept);
+    const int s_count = st.add(cells, count, count ? Staging::kOut : Staging::kKept), s_top = st.add(cells, top, top ? Staging::kOut : Staging::kKept);
+    const int s_label = st.add(cells, label, Staging::kOut);
+    const int s_table = st.add((size_t)frames * (size_t)max_clusters * kClusterRowWords, clusters, Staging::kOut);
+    const int s_n = st.add((size_t)frames, n_clusters, Staging::kOut), s_pc = st.add(points, point_cluster, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), st.dev<float>(s_top), nullptr, h->stream);
+    if (lrc == 0)
+        lrc = pwpp_launch_label_grid(g->nx, g->ny, frames, st.dev<int32_t>(s_count), st.dev<float>(s_top), min_count, connectivity, h->clusters_path,
+                                     st.dev<int32_t>(s_label), st.dev<void>(s_table), st.dev<int32_t>(s_n), max_clusters, st.dev<uint32_t>(s_work),
+                                     h->stream);
     if (lrc != 0) return launch_failed(h, lrc);
     if (points > 0) {
-        HIPCHK(hipMemsetAsync(d_pc, 0xff, points * sizeof(int32_t), h->stream));  // (-1: every point that is not a counted one)
-        lrc = pwpp_launch_point_cluster(&v, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground, h_min, h_max, d_label, d_pc,
-                                        base_first, h->stream);
+        HIPCHK(hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream));  // (-1: every point that is not a counted one)
+        lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s_label), st.dev<int32_t>(s_pc), base_first, h->stream);
         if (lrc != 0) return launch_failed(h, lrc);
     }
-    if (host) {
-        HIPCHK(hipMemcpyAsync(label, d_label, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (count) HIPCHK(hipMemcpyAsync(count, d_count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (top) HIPCHK(hipMemcpyAsync(top, d_top, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (rows > 0) HIPCHK(hipMemcpyAsync(clusters, d_table, rows * sizeof(pwpp_obstacle_cluster), hipMemcpyDeviceToHost, h->stream));
-        if (n_clusters) HIPCHK(hipMemcpyAsync(n_clusters, d_n, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (points > 0) HIPCHK(hipMemcpyAsync(point_cluster, d_pc, points * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        h->ground_query_queued = true;
-    }
-    return PWPP_OK;
+    return st.end();
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------
@@ -2545,54 +2495,31 @@ int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, f
                        pwpp_obstacle_box *boxes, int max_boxes) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !label || !boxes) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!label ? "label image" : "box table"));
-    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
-    if (!(h_min <= h_max)) return fail(PWPP_E_ARG, "height band [%g, %g]: h_min <= h_max expected, neither a NaN", (double)h_min, (double)h_max);
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
     if (max_boxes < 1) return fail(PWPP_E_ARG, "max_boxes %d: at least 1 expected", max_boxes);
     if (frames > 0 && (int64_t)frames * (int64_t)max_boxes > ((int64_t)1 << 24))
         return fail(PWPP_E_ARG, "%d frames x %d boxes exceed 2^24 rows", frames, max_boxes);
-    int rc = box_extent_args(g);
-    if (rc) return rc;
+    if ((rc = box_extent_args(g))) return rc;
     if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle boxes take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    if ((int64_t)g->nx * (int64_t)g->ny > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", g->nx, g->ny);
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
+    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
     const size_t rows = (size_t)frames * (size_t)max_boxes;
-    const bool host = mem == PWPP_MEM_HOST;
-    ClusterPlan plan;
-    const size_t o_acc = plan.take(rows * PWPP_BOX_ACC_WORDS);
-    const size_t o_label = host ? plan.take(cells) : 0, o_rows = host ? plan.take(rows * kBoxRowWords) : 0;
-    if ((rc = h->d_clusters.ensure(plan.words))) return rc;
-    uint32_t *w = h->d_clusters.p;
-    const int32_t *d_label = host ? reinterpret_cast<const int32_t *>(w + o_label) : label;
-    void *d_rows = host ? static_cast<void *>(w + o_rows) : static_cast<void *>(boxes);
-    if (host) HIPCHK(hipMemcpyAsync(w + o_label, label, cells * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = ground_view(h, v))) return rc;
-    int max_nonground = 0;
-    for (int f = frame_first; f < frame_first + frames; ++f) {
-        const int nn = h->h_results.p[f].n_nonground;
-        max_nonground = nn > max_nonground ? nn : max_nonground;
-    }
-    const PwppFrameResult *results = h->d_results.p + (size_t)h->counters_copy * (size_t)h->frames;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_acc = st.add(rows * PWPP_BOX_ACC_WORDS, nullptr, Staging::kKept);
+    const int s_label = st.add(cells, label, Staging::kIn), s_rows = st.add(rows * kBoxRowWords, boxes, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    const PwppBoxRows table = {st.dev<const int32_t>(s_label), max_boxes, st.dev<uint32_t>(s_acc), st.dev<const float>(s_rows)};
     const int combine = h->boxes_path == 0 ? (kBoxesDefaultCombine ? 1 : 0) : (h->boxes_path == 2 ? 1 : 0);
-    int lrc = pwpp_launch_box_rows(0, (int64_t)rows, w + o_acc, g->x0, g->y0, d_rows, h->stream);
+    int lrc = pwpp_launch_box_rows(0, (int64_t)rows, table.acc, g->x0, g->y0, st.dev<void>(s_rows), h->stream);
     for (int pass = 0; pass < 2 && lrc == 0; ++pass) {
-        lrc = pwpp_launch_box_pass(pass, combine, &v, h->ground_rows_valid, h->d_frames.p, results, h->d_out.p, &grid, frame_first, frames, max_nonground,
-                                   h_min, h_max, d_label, max_boxes, w + o_acc, d_rows, h->stream);
-        if (lrc != 0) break;
-        h->ground_rows_valid = true;
-        lrc = pwpp_launch_box_rows(1 + pass, (int64_t)rows, w + o_acc, g->x0, g->y0, d_rows, h->stream);
+        lrc = pwpp_launch_box_pass(pass, combine, &scan, &table, h->stream);
+        if (lrc == 0) lrc = pwpp_launch_box_rows(1 + pass, (int64_t)rows, table.acc, g->x0, g->y0, st.dev<void>(s_rows), h->stream);
     }
-    if (lrc != 0) return launch_failed(h, lrc);
-    if (host) {
-        HIPCHK(hipMemcpyAsync(boxes, d_rows, rows * sizeof(pwpp_obstacle_box), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        h->ground_query_queued = true;
-    }
-    return PWPP_OK;
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
 // The same rows on the host, from the functions the kernels compile (pwpp_boxes.h); row and height of every point are the caller's.

@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "pwpp_boxes.h"
+#include "pwpp_dev.h"  // the launchers' prototypes
 #include "pwpp_unionfind.h"
 
 namespace {

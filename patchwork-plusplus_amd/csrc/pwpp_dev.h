@@ -1,5 +1,6 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip).  Internal; the public boundary is include/pwpp.h.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip), and the prototypes of the launchers they call across files.
+// Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
 
@@ -274,5 +275,56 @@ struct PwppGroundGrid {  // = pwpp_ground_grid
     double x0, y0, cell;
     int32_t nx, ny, flags, pad_;
 };
+
+// "The non-ground lists of frames [frame_first, frame_first + frames) of the LAST call over a grid": what every kernel that walks
+// those lists reads (k_obstacle_raster, k_point_cluster, k_box_moments, k_box_extents), by value in the kernarg segment.  Filled in
+// one place on the host (obstacle_scan, pwpp_capi.cpp).
+struct PwppObstacleScan {
+    PwppGroundView Q;
+    const PwppFrameDesc *descs;      // [Q.num_frames] the last call's frame descriptors ...
+    const PwppFrameResult *results;  // ... the copy of the frame counters it worked on ...
+    const int32_t *out_idx;          // ... and its index lists (PwppBatch.out_idx)
+    PwppGroundGrid G;
+    int32_t frame_first, frames;     // the frame range: image fr of an output belongs to frame frame_first + fr
+    int32_t max_nonground;           // the longest non-ground list of the range (0: no list kernel is launched)
+    float h_min, h_max;              // the height band of a counted point
+};
+
+// The rows of pwpp_box_obstacles as the two point passes see them.
+struct PwppBoxRows {
+    const int32_t *label;  // [frames][ny][nx] the row of every cell (-1: none)
+    int32_t max_boxes;     // rows per frame
+    uint32_t *acc;         // [frames][max_boxes][PWPP_BOX_ACC_WORDS] the accumulators (pwpp_boxes.h), 8-byte aligned
+    const float *boxes;    // [frames][max_boxes][16] the rows themselves: the second pass reads the axes k_box_solve left in them
+};
+
+// ---- the launchers: every extern "C" function one translation unit of the library calls in another, declared ONCE ----------------
+// (C linkage: a second, diverging declaration would link without complaint.)  All return hipGetLastError() as an int.
+extern "C" {
+// pwpp_kernels.hip
+int pwpp_launch_pipeline(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev, hipStream_t aux, hipEvent_t aux_fork, hipEvent_t aux_join,
+                         unsigned long long *order_a, unsigned long long *order_b, int stages);
+int pwpp_launch_clear(const PwppBatch *batch, hipStream_t stream);
+int pwpp_launch_k5_tail(const PwppBatch *batch, hipStream_t aux, hipEvent_t aux_fork, hipEvent_t aux_join);
+int pwpp_launch_histogram(const PwppBatch *batch, hipStream_t stream);
+int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, int count, float *out, hipStream_t stream);
+int pwpp_launch_gather_records(const PwppFrameDesc *fd, const int *idx, int count, void *out, int path, hipStream_t stream);
+int pwpp_launch_ground_rows(const PwppGroundView *view, hipStream_t stream);
+int pwpp_launch_ground_query(const PwppGroundView *view, const float *xyz, const int32_t *frame, int64_t m, void *out, hipStream_t stream);
+int pwpp_launch_ground_raster(const PwppGroundView *view, const PwppGroundGrid *grid, int frame_first, int frames, float *height, int32_t *patch,
+                              hipStream_t stream);
+int pwpp_launch_obstacle_raster(const PwppObstacleScan *scan, int32_t *count, float *top, int32_t *unref, hipStream_t stream);
+int pwpp_launch_point_cluster(const PwppObstacleScan *scan, const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
+int pwpp_launch_box_pass(int pass, int combine, const PwppObstacleScan *scan, const PwppBoxRows *rows, hipStream_t stream);
+// pwpp_fit.hip
+int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev);
+int pwpp_launch_fixup(const PwppBatch *batch, hipStream_t stream);
+const char *pwpp_big_batch_plan(int max_n, int num_bins, int wide);
+// pwpp_clusters.hip
+int pwpp_launch_box_rows(int step, int64_t rows, uint32_t *acc, double x0, double y0, void *boxes, hipStream_t stream);
+size_t pwpp_cluster_work_words(int nx, int ny, int frames);
+int pwpp_launch_label_grid(int nx, int ny, int frames, const int32_t *count, const float *top, int min_count, int connectivity, int path,
+                           int32_t *label, void *clusters, int32_t *n_clusters, int max_clusters, uint32_t *work, hipStream_t stream);
+}
 
 #endif

@@ -23,7 +23,8 @@
 // cloud points (pwpp_query_ground, pwpp_rasterize_ground); k_obstacle_fill / k_obstacle_raster / k_obstacle_top count the non-ground
 // points per cell of the same grid (pwpp_rasterize_obstacles), k_point_cluster gives every counted point the cluster of its cell
 // (pwpp_label_obstacles; the image kernels of the clusters are pwpp_clusters.hip), k_box_moments / k_box_extents reduce the counted
-// points of every label to an oriented box (pwpp_box_obstacles; pwpp_boxes.h has the arithmetic).  They write nothing the pipeline reads.
+// points of every label to an oriented box (pwpp_box_obstacles; pwpp_boxes.h has the arithmetic).  The four kernels that walk the
+// non-ground lists take one PwppObstacleScan (pwpp_dev.h).  They write nothing the pipeline reads.
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -3059,97 +3060,104 @@ __device__ __forceinline__ bool grid_cell(float c, double c0, double cell, int n
     return true;
 }
 
-// What entry e of frame f's non-ground list is to the obstacle grid: ONE function for k_obstacle_raster and k_point_cluster, so
-// that "the points of a cell" are the same points in both.  An index that is not a point of the frame (a frame whose lists are
-// unwritten: k_label_scatter) is dropped; frame, bin, row and cell are checked before an address is formed.
+// What one lane of a kernel over a PwppObstacleScan works on: entry e of the non-ground list of frame f = S.frame_first + fr.
+struct ScanEntry {
+    int fr, f;  // (fr: relative to S.frame_first, the image's frame)
+    int64_t e;
+    PwppFrameDesc fd;
+    PwppFrameResult r;
+};
+
+// The prologue of those kernels, launched over scan_grid (below): the zone table of bin_code_fast, then the block's frame and the
+// lane's entry.  False: the frame is not one of the view's (every lane of the block returns).
+__device__ __forceinline__ bool scan_entry(const PwppObstacleScan &S, float4 *s_zt, ScanEntry &t) {
+    fill_zone_table(S.Q.P, s_zt);
+    __syncthreads();
+    t.fr = blockIdx.y, t.f = S.frame_first + t.fr;
+    if ((unsigned)t.f >= (unsigned)S.Q.num_frames) return false;
+    t.fd = S.descs[t.f];
+    t.r = S.results[t.f];
+    t.e = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    return true;
+}
+
+// What that entry is to the obstacle grid: ONE function for every kernel over a scan, so that "the points of a cell" are the same
+// points in all of them.  An index that is not a point of the frame (a frame whose lists are unwritten: k_label_scatter) is
+// dropped; frame, bin, row and cell are checked before an address is formed.  `p`: the point's index in its frame, its word in
+// the range's images and the coordinates that decided -- all set when the point is counted, i and o as soon as it is kObUnref.
 enum ObstaclePoint { kObNone, kObUnref, kObCounted };  // outside the list, the frame or the grid | no reference | counted: `hgt` in the band
-__device__ __forceinline__ ObstaclePoint obstacle_point(const PwppGroundView &Q, const float4 *s_zt, const PwppFrameDesc &fd, const PwppFrameResult &r,
-                                                        const int32_t *out_idx, int f, int64_t e, const PwppGroundGrid &G, float h_min, float h_max,
-                                                        int &i, size_t &cell, float &hgt) {
-    const int64_t n = fd.n;  // (the two counts clamped to the frame: label_counts)
-    const int64_t ng = r.n_ground < 0 ? 0 : (r.n_ground > n ? n : (int64_t)r.n_ground);
-    const int64_t nn = r.n_nonground < 0 ? 0 : (r.n_nonground > n - ng ? n - ng : (int64_t)r.n_nonground);
-    if (e >= nn) return kObNone;
-    i = out_idx[fd.base + ng + e];
-    if ((unsigned)i >= (unsigned)fd.n) return kObNone;
-    float x, y, z, w;
-    load_point<true>(fd, i, x, y, z, w);
+struct ObstacleHit {
+    int i;
+    size_t o;
+    float x, y, z, hgt;
+};
+__device__ __forceinline__ ObstaclePoint obstacle_point(const PwppObstacleScan &S, const float4 *s_zt, const ScanEntry &t, ObstacleHit &p) {
+    const PwppGroundView &Q = S.Q;
+    const PwppGroundGrid &G = S.G;
+    const int64_t n = t.fd.n;  // (the two counts clamped to the frame: label_counts)
+    const int64_t ng = t.r.n_ground < 0 ? 0 : (t.r.n_ground > n ? n : (int64_t)t.r.n_ground);
+    const int64_t nn = t.r.n_nonground < 0 ? 0 : (t.r.n_nonground > n - ng ? n - ng : (int64_t)t.r.n_nonground);
+    if (t.e >= nn) return kObNone;
+    p.i = S.out_idx[t.fd.base + ng + t.e];
+    if ((unsigned)p.i >= (unsigned)t.fd.n) return kObNone;
+    float w;
+    load_point<true>(t.fd, p.i, p.x, p.y, p.z, w);
     int ix, iy;
-    if (!grid_cell(x, G.x0, G.cell, G.nx, ix) || !grid_cell(y, G.y0, G.cell, G.ny, iy)) return kObNone;
+    if (!grid_cell(p.x, G.x0, G.cell, G.nx, ix) || !grid_cell(p.y, G.y0, G.cell, G.ny, iy)) return kObNone;
     unsigned code = 0;
-    if ((Q.debug & 16) || !bin_code_fast(Q.P, s_zt, x, y, code)) code = bin_code_exact(Q.P, x, y);
-    const PwppGroundSample s = ground_sample(Q, f, code, x, y, z);
-    cell = (size_t)iy * (size_t)G.nx + (size_t)ix;  // (inside the frame's image)
+    if ((Q.debug & 16) || !bin_code_fast(Q.P, s_zt, p.x, p.y, code)) code = bin_code_exact(Q.P, p.x, p.y);
+    const PwppGroundSample s = ground_sample(Q, t.f, code, p.x, p.y, p.z);
+    p.o = ((size_t)t.fr * (size_t)G.ny + (size_t)iy) * (size_t)G.nx + (size_t)ix;  // (inside the range's images)
     const bool hidden = (G.flags & PWPP_GRID_GROUND_ONLY) &&
                         (s.decision == PWPP_DEC_NOT_UPRIGHT || s.decision == PWPP_DEC_HEADING || s.decision == PWPP_DEC_TGR_REJECT);
     if (s.patch < 0 || hidden) return kObUnref;
-    hgt = s.distance;
-    if (!(h_min <= hgt && hgt <= h_max)) return kObNone;  // (a NaN height fails)
+    p.hgt = s.distance;
+    if (!(S.h_min <= p.hgt && p.hgt <= S.h_max)) return kObNone;  // (a NaN height fails)
     return kObCounted;
 }
 
 // grid (tiles of kObBlock entries over the longest non-ground list of the range, frames): one lane per list entry, one coalesced
 // load of the indices.  Consecutive entries mostly belong to one patch, so a wave's atomics hit few cells: plain global atomics
 // (DESIGN.md section K has what a combine of equal cells would have to beat).
-__global__ __launch_bounds__(kObBlock) void k_obstacle_raster(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
-                                                              const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
-                                                              int32_t *count, uint32_t *top, int32_t *unref) {
+__global__ __launch_bounds__(kObBlock) void k_obstacle_raster(PwppObstacleScan S, int32_t *count, uint32_t *top, int32_t *unref) {
     __shared__ float4 s_zt[8];
-    fill_zone_table(Q.P, s_zt);
-    __syncthreads();
-    const int fr = blockIdx.y, f = frame_first + fr;  // (fr: relative to frame_first, the image's frame)
-    if ((unsigned)f >= (unsigned)Q.num_frames) return;
-    const PwppFrameDesc fd = frames[f];
-    const PwppFrameResult r = results[f];
-    int i;
-    size_t cell;
-    float hgt;
-    const ObstaclePoint k = obstacle_point(Q, s_zt, fd, r, out_idx, f, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, i, cell, hgt);
+    ScanEntry t;
+    if (!scan_entry(S, s_zt, t)) return;
+    ObstacleHit p;
+    const ObstaclePoint k = obstacle_point(S, s_zt, t, p);
     if (k == kObNone) return;
-    const size_t o = (size_t)fr * (size_t)G.ny * (size_t)G.nx + cell;
     if (k == kObUnref) {
-        if (unref) atomicAdd(unref + o, 1);
+        if (unref) atomicAdd(unref + p.o, 1);
         return;
     }
-    atomicAdd(count + o, 1);
-    if (top) atomicMax(top + o, height_key(hgt));
+    atomicAdd(count + p.o, 1);
+    if (top) atomicMax(top + p.o, height_key(p.hgt));
 }
 
-// pwpp_label_obstacles' per-point cluster id: the launch of k_obstacle_raster again, and every COUNTED point takes the label of its
-// cell (-1 where the cell stayed below min_count).  point_cluster was filled with -1 and starts at the first point of frame_first
+// pwpp_label_obstacles' per-point cluster id: the scan of k_obstacle_raster again, and every COUNTED point takes the label of its
+// cell (-1 where the cell stayed below min_count).  point_cluster was filled with -1 and starts at the first point of S.frame_first
 // (`base_first`: that frame's fd.base); a point is named by at most one list entry, so every word has one writer.
-__global__ __launch_bounds__(kObBlock) void k_point_cluster(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
-                                                            const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
-                                                            const int32_t *label, int32_t *point_cluster, int64_t base_first) {
+__global__ __launch_bounds__(kObBlock) void k_point_cluster(PwppObstacleScan S, const int32_t *label, int32_t *point_cluster, int64_t base_first) {
     __shared__ float4 s_zt[8];
-    fill_zone_table(Q.P, s_zt);
-    __syncthreads();
-    const int fr = blockIdx.y, f = frame_first + fr;
-    if ((unsigned)f >= (unsigned)Q.num_frames) return;
-    const PwppFrameDesc fd = frames[f];
-    const PwppFrameResult r = results[f];
-    int i;
-    size_t cell;
-    float hgt;
-    if (obstacle_point(Q, s_zt, fd, r, out_idx, f, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, i, cell, hgt) != kObCounted) return;
-    point_cluster[fd.base - base_first + i] = label[(size_t)fr * (size_t)G.ny * (size_t)G.nx + cell];
+    ScanEntry t;
+    if (!scan_entry(S, s_zt, t)) return;
+    ObstacleHit p;
+    if (obstacle_point(S, s_zt, t, p) != kObCounted) return;
+    point_cluster[t.fd.base - base_first + p.i] = label[p.o];
 }
 
-// ---- obstacle boxes (pwpp_box_obstacles): two passes over the launch of k_obstacle_raster ------------------------------------------
+// ---- obstacle boxes (pwpp_box_obstacles): two passes over the scan of k_obstacle_raster -----------------------------------------------
 // A list entry belongs to row label[fr][cell] of its frame iff it is a COUNTED point (obstacle_point) and 0 <= row < max_boxes.
-// The coordinates are those obstacle_point looked at: the same load_point of the same index.
-__device__ __forceinline__ bool box_point(const PwppGroundView &Q, const float4 *s_zt, const PwppFrameDesc &fd, const PwppFrameResult &r,
-                                          const int32_t *out_idx, int f, int fr, int64_t e, const PwppGroundGrid &G, float h_min, float h_max,
-                                          const int32_t *label, int max_boxes, int &row, double &dx, double &dy, float &hgt, float &z) {
-    int i;
-    size_t cell;
-    if (obstacle_point(Q, s_zt, fd, r, out_idx, f, e, G, h_min, h_max, i, cell, hgt) != kObCounted) return false;
-    row = label[(size_t)fr * (size_t)G.ny * (size_t)G.nx + cell];
-    if ((unsigned)row >= (unsigned)max_boxes) return false;  // (-1, or a rank beyond the table)
-    float x, y, w;
-    load_point<true>(fd, i, x, y, z, w);
-    dx = (double)x - G.x0;  // (the doubles grid_cell starts from: both >= 0 inside the grid)
-    dy = (double)y - G.y0;
+// The coordinates are those obstacle_point looked at and hands back.
+__device__ __forceinline__ bool box_point(const PwppObstacleScan &S, const float4 *s_zt, const ScanEntry &t, const PwppBoxRows &R, int &row, double &dx,
+                                          double &dy, float &hgt, float &z) {
+    ObstacleHit p;
+    if (obstacle_point(S, s_zt, t, p) != kObCounted) return false;
+    row = R.label[p.o];
+    if ((unsigned)row >= (unsigned)R.max_boxes) return false;  // (-1, or a rank beyond the table)
+    hgt = p.hgt, z = p.z;
+    dx = (double)p.x - S.G.x0;  // (the doubles grid_cell starts from: both >= 0 inside the grid)
+    dy = (double)p.y - S.G.y0;
     return true;
 }
 
@@ -3189,24 +3197,17 @@ __device__ __forceinline__ int box_next_row(unsigned long long &todo, bool count
 // COMBINE true: consecutive entries mostly name one row, so the lanes of a wave that name the same row are summed first and one
 // lane adds for them -- at most 64 rounds, one per distinct row of the wave; integer sums, so the same bytes.
 template <bool COMBINE>
-__global__ __launch_bounds__(kObBlock) void k_box_moments(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
-                                                          const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
-                                                          const int32_t *label, int max_boxes, uint32_t *acc) {
+__global__ __launch_bounds__(kObBlock) void k_box_moments(PwppObstacleScan S, PwppBoxRows R) {
     __shared__ float4 s_zt[8];
-    fill_zone_table(Q.P, s_zt);
-    __syncthreads();
-    const int fr = blockIdx.y, f = frame_first + fr;
-    if ((unsigned)f >= (unsigned)Q.num_frames) return;
-    const PwppFrameDesc fd = frames[f];
-    const PwppFrameResult r = results[f];
+    ScanEntry t;
+    if (!scan_entry(S, s_zt, t)) return;
     int row = -1;
     double dx = 0.0, dy = 0.0;
     float hgt, z;
-    const bool counted = box_point(Q, s_zt, fd, r, out_idx, f, fr, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, label, max_boxes,
-                                   row, dx, dy, hgt, z);
+    const bool counted = box_point(S, s_zt, t, R, row, dx, dy, hgt, z);
     const unsigned long long qx = counted ? (unsigned long long)pwpp_box_quantise(dx) : 0ull;  // (<= 2^20 + 1)
     const unsigned long long qy = counted ? (unsigned long long)pwpp_box_quantise(dy) : 0ull;
-    unsigned long long *sums = reinterpret_cast<unsigned long long *>(acc + ((size_t)fr * (size_t)max_boxes + (size_t)(counted ? row : 0)) * PWPP_BOX_ACC_WORDS);
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(R.acc + ((size_t)t.fr * (size_t)R.max_boxes + (size_t)(counted ? row : 0)) * PWPP_BOX_ACC_WORDS);
     if (!COMBINE) {
         if (!counted) return;
         atomicAdd(sums + 0, 1ull);
@@ -3238,29 +3239,22 @@ __global__ __launch_bounds__(kObBlock) void k_box_moments(PwppGroundView Q, cons
     }
 }
 
-// Second pass: the rows' axes stand in `boxes` (k_box_solve); minima and maxima of the keys of p, q, hgt and z.  COMBINE as above.
+// Second pass: the rows' axes stand in R.boxes (k_box_solve); minima and maxima of the keys of p, q, hgt and z.  COMBINE as above.
 template <bool COMBINE>
-__global__ __launch_bounds__(kObBlock) void k_box_extents(PwppGroundView Q, const PwppFrameDesc *frames, const PwppFrameResult *results,
-                                                          const int32_t *out_idx, PwppGroundGrid G, int frame_first, float h_min, float h_max,
-                                                          const int32_t *label, int max_boxes, uint32_t *acc, const float *boxes) {
+__global__ __launch_bounds__(kObBlock) void k_box_extents(PwppObstacleScan S, PwppBoxRows R) {
     __shared__ float4 s_zt[8];
-    fill_zone_table(Q.P, s_zt);
-    __syncthreads();
-    const int fr = blockIdx.y, f = frame_first + fr;
-    if ((unsigned)f >= (unsigned)Q.num_frames) return;
-    const PwppFrameDesc fd = frames[f];
-    const PwppFrameResult r = results[f];
+    ScanEntry t;
+    if (!scan_entry(S, s_zt, t)) return;
     int row = -1;
     double dx = 0.0, dy = 0.0;
     float hgt = 0.0f, z = 0.0f;
-    const bool counted = box_point(Q, s_zt, fd, r, out_idx, f, fr, (int64_t)blockIdx.x * kObBlock + threadIdx.x, G, h_min, h_max, label, max_boxes,
-                                   row, dx, dy, hgt, z);
-    const size_t at = (size_t)fr * (size_t)max_boxes + (size_t)(counted ? row : 0);
-    uint32_t *keys = acc + at * PWPP_BOX_ACC_WORDS + 2 * PWPP_BOX_SUMS;
+    const bool counted = box_point(S, s_zt, t, R, row, dx, dy, hgt, z);
+    const size_t at = (size_t)t.fr * (size_t)R.max_boxes + (size_t)(counted ? row : 0);
+    uint32_t *keys = R.acc + at * PWPP_BOX_ACC_WORDS + 2 * PWPP_BOX_SUMS;
     uint32_t k[4] = {0u, 0u, 0u, 0u};
     if (counted) {
         float p, q;
-        pwpp_box_project(dx, dy, boxes[at * 16 + 6], boxes[at * 16 + 7], p, q);  // (words 6, 7 of a row: ax, ay)
+        pwpp_box_project(dx, dy, R.boxes[at * 16 + 6], R.boxes[at * 16 + 7], p, q);  // (words 6, 7 of a row: ax, ay)
         k[0] = pwpp_height_key(p), k[1] = pwpp_height_key(q), k[2] = pwpp_height_key(hgt), k[3] = pwpp_height_key(z);
     }
     if (!COMBINE) {
@@ -3354,78 +3348,71 @@ extern "C" int pwpp_launch_gather_xyz(const PwppFrameDesc *fd, const int *idx, i
     return (int)hipGetLastError();
 }
 
-// The ground queries of pwpp_capi.cpp.  rows_valid == 0: the bin -> row table of every frame of the view is computed first
-// (once per estimate call).
-extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, int rows_valid, const float *xyz, const int32_t *frame, int64_t m, void *out,
-                                        hipStream_t stream) {
-    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+// The ground queries of pwpp_capi.cpp.  The bin -> row table of every frame of the view: computed once per estimate call, before
+// the first kernel that reads the rows (the host keeps track: ground_view).
+extern "C" int pwpp_launch_ground_rows(const PwppGroundView *view, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pwpp_launch_ground_query(const PwppGroundView *view, const float *xyz, const int32_t *frame, int64_t m, void *out, hipStream_t stream) {
     if (m > 0)
         hipLaunchKernelGGL(k_ground_query, dim3((unsigned)((m + kGqBlock - 1) / kGqBlock)), dim3(kGqBlock), 0, stream, *view, xyz, frame, m,
                            static_cast<PwppGroundSample *>(out));
     return (int)hipGetLastError();
 }
 
-extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, int rows_valid, const PwppGroundGrid *grid, int frame_first, int frames,
-                                         float *height, int32_t *patch, hipStream_t stream) {
-    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
+extern "C" int pwpp_launch_ground_raster(const PwppGroundView *view, const PwppGroundGrid *grid, int frame_first, int frames, float *height,
+                                         int32_t *patch, hipStream_t stream) {
     const dim3 g((unsigned)((grid->nx + kGqBlock - 1) / kGqBlock), (unsigned)(grid->ny < 65535 ? grid->ny : 65535), (unsigned)frames);
     hipLaunchKernelGGL(k_ground_raster, g, dim3(kGqBlock), 0, stream, *view, *grid, frame_first, height, patch);
     return (int)hipGetLastError();
 }
 
-// pwpp_rasterize_obstacles: fill, points, keys -> floats.  `descs`, `results`, `out_idx`: the last call's frame descriptors, frame
-// counters and index lists on the device; max_nonground: the longest non-ground list of the frame range (0: only the fill runs).
-extern "C" int pwpp_launch_obstacle_raster(const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
-                                           const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground,
-                                           float h_min, float h_max, int32_t *count, float *top, int32_t *unref, hipStream_t stream) {
-    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
-    const int64_t cells = (int64_t)grid->nx * (int64_t)grid->ny * (int64_t)frames;  // (<= 2^31: checked by the caller)
+// The launch of every kernel over a scan: tiles of kObBlock entries over the longest non-ground list of the range, by frames.
+// False: all lists are empty, nothing is launched.
+static bool scan_grid(const PwppObstacleScan &S, dim3 &g) {
+    g = dim3((unsigned)(((int64_t)S.max_nonground + kObBlock - 1) / kObBlock), (unsigned)S.frames);
+    return S.max_nonground > 0;
+}
+
+// pwpp_rasterize_obstacles: fill, points, keys -> floats (without a list only the fill runs).
+extern "C" int pwpp_launch_obstacle_raster(const PwppObstacleScan *scan, int32_t *count, float *top, int32_t *unref, hipStream_t stream) {
+    const int64_t cells = (int64_t)scan->G.nx * (int64_t)scan->G.ny * (int64_t)scan->frames;  // (<= 2^31: checked by the caller)
     const unsigned quads = (unsigned)(((cells + 2) / 4 + 1 + kObBlock - 1) / kObBlock);
     uint32_t *keys = reinterpret_cast<uint32_t *>(top);
     hipLaunchKernelGGL(k_obstacle_fill, dim3(quads), dim3(kObBlock), 0, stream, cells, reinterpret_cast<uint32_t *>(count), keys,
                        reinterpret_cast<uint32_t *>(unref));
-    if (max_nonground > 0)
-        hipLaunchKernelGGL(k_obstacle_raster, dim3((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames), dim3(kObBlock), 0, stream,
-                           *view, descs, results, out_idx, *grid, frame_first, h_min, h_max, count, keys, unref);
+    dim3 g;
+    if (scan_grid(*scan, g)) hipLaunchKernelGGL(k_obstacle_raster, g, dim3(kObBlock), 0, stream, *scan, count, keys, unref);
     if (top) hipLaunchKernelGGL(k_obstacle_top, dim3(quads), dim3(kObBlock), 0, stream, cells, keys);
     return (int)hipGetLastError();
 }
 
 // the per-point cluster ids of pwpp_label_obstacles: `label` is the finished label image of the frame range, point_cluster has been
-// filled with -1 (arguments as above; base_first: the first per-point slot of frame_first)
-extern "C" int pwpp_launch_point_cluster(const PwppGroundView *view, const PwppFrameDesc *descs, const PwppFrameResult *results, const int32_t *out_idx,
-                                         const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min, float h_max,
-                                         const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream) {
-    if (max_nonground > 0)
-        hipLaunchKernelGGL(k_point_cluster, dim3((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames), dim3(kObBlock), 0, stream,
-                           *view, descs, results, out_idx, *grid, frame_first, h_min, h_max, label, point_cluster, base_first);
+// filled with -1 (base_first: the first per-point slot of scan->frame_first)
+extern "C" int pwpp_launch_point_cluster(const PwppObstacleScan *scan, const int32_t *label, int32_t *point_cluster, int64_t base_first,
+                                         hipStream_t stream) {
+    dim3 g;
+    if (scan_grid(*scan, g)) hipLaunchKernelGGL(k_point_cluster, g, dim3(kObBlock), 0, stream, *scan, label, point_cluster, base_first);
     return (int)hipGetLastError();
 }
 
-// The two point passes of pwpp_box_obstacles (arguments as above).  pass 0: the sums of every row into `acc` (PWPP_BOX_ACC_WORDS words
-// per row, initialised by pwpp_launch_box_rows); pass 1: the keys, against the axes that stand in `boxes`.  combine: sum equal rows
-// inside a wave first.
-extern "C" int pwpp_launch_box_pass(int pass, int combine, const PwppGroundView *view, int rows_valid, const PwppFrameDesc *descs, const PwppFrameResult *results,
-                                    const int32_t *out_idx, const PwppGroundGrid *grid, int frame_first, int frames, int max_nonground, float h_min,
-                                    float h_max, const int32_t *label, int max_boxes, uint32_t *acc, const void *boxes, hipStream_t stream) {
-    if (!rows_valid) hipLaunchKernelGGL(k_ground_rows, dim3(view->num_frames), dim3(kPpBlock), 0, stream, *view);
-    if (max_nonground <= 0) return (int)hipGetLastError();
-    const dim3 g((unsigned)(((int64_t)max_nonground + kObBlock - 1) / kObBlock), (unsigned)frames);
+// The two point passes of pwpp_box_obstacles.  pass 0: the sums of every row into rows->acc (initialised by pwpp_launch_box_rows);
+// pass 1: the keys, against the axes that stand in rows->boxes.  combine: sum equal rows inside a wave first.
+extern "C" int pwpp_launch_box_pass(int pass, int combine, const PwppObstacleScan *scan, const PwppBoxRows *rows, hipStream_t stream) {
+    dim3 g;
+    if (!scan_grid(*scan, g)) return (int)hipGetLastError();
     if (pass == 0)
-        hipLaunchKernelGGL(combine ? k_box_moments<true> : k_box_moments<false>, g, dim3(kObBlock), 0, stream, *view, descs, results, out_idx, *grid,
-                           frame_first, h_min, h_max, label, max_boxes, acc);
+        hipLaunchKernelGGL(combine ? k_box_moments<true> : k_box_moments<false>, g, dim3(kObBlock), 0, stream, *scan, *rows);
     else
-        hipLaunchKernelGGL(combine ? k_box_extents<true> : k_box_extents<false>, g, dim3(kObBlock), 0, stream, *view, descs, results, out_idx, *grid,
-                           frame_first, h_min, h_max, label, max_boxes, acc, static_cast<const float *>(boxes));
+        hipLaunchKernelGGL(combine ? k_box_extents<true> : k_box_extents<false>, g, dim3(kObBlock), 0, stream, *scan, *rows);
     return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
 // host-side launcher used by pwpp_capi.cpp
 // ------------------------------------------------------------------------------------------
-extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev);
-extern "C" int pwpp_launch_fixup(const PwppBatch *batch, hipStream_t stream);
-
 // K0: the per-launch zeroing (histogram / cursor slabs and the frame counters) in ONE dispatch; two
 // hipMemsetAsync calls were three fill kernels of the runtime, ~6 us apart on the queue
 namespace {

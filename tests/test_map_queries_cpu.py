@@ -1,0 +1,87 @@
+"""No-GPU checks of what the post-call map queries share (pwpp_rasterize_obstacles, pwpp_label_obstacles, pwpp_box_obstacles): the
+argument checks they have in common, fed to all three through one loop -- the same code and the same message fragment from each
+-- and, with the restatements, that the batch of tests/test_gpu_map_query_ranges.py has clusters and boxes in the frames its
+comparison is about."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import ground_query_ref as gq
+import obstacle_boxes_ref as ob
+import obstacle_clusters_ref as oc
+import obstacle_grid_ref as og
+import oracle_lib as ol
+import pwpp_hip
+from test_gpu_map_query_ranges import BAND, CONN, FIRST, GRID, MAX_ROWS, MIN_COUNT, batch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "patchwork-plusplus_amd")
+F32 = np.float32
+E_ARG = -1
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(pwpp_hip.LIB_PATH):
+        subprocess.run(["make", "-C", PKG, "lib/libpwpp_hip.so"], check=True, stdout=subprocess.DEVNULL)
+    return pwpp_hip.load()
+
+
+# (grid fields x0, y0, cell, nx, ny, flags), band, mem, a fragment of the message.  A NaN cell is the one input the three do not
+# name alike: pwpp_box_obstacles' extent check comes first ("... cells of nan m: ... at most 1024 m"), the others say "cell size".
+SHARED_BAD_INPUTS = [
+    ("grid flags 2", dict(flags=2), (0.2, 2.5), pwpp_hip.MEM_HOST, b"grid flags 2: 0 or PWPP_GRID_GROUND_ONLY"),
+    ("band (2.5, 0.2)", {}, (2.5, 0.2), pwpp_hip.MEM_HOST, b"height band [2.5, 0.2]: h_min <= h_max expected"),
+    ("band (NaN, 1)", {}, (np.nan, 1.0), pwpp_hip.MEM_HOST, b"h_min <= h_max expected, neither a NaN"),
+    ("nx 0", dict(nx=0), (0.2, 2.5), pwpp_hip.MEM_HOST, b"grid of 0 x 4 cells"),
+    ("cell 0", dict(cell=0.0), (0.2, 2.5), pwpp_hip.MEM_HOST, b"cell size must be finite, the cell size positive"),
+    ("cell NaN", dict(cell=np.nan), (0.2, 2.5), pwpp_hip.MEM_HOST, b"cell"),
+    ("mem PWPP_MEM_HOST_PINNED", {}, (0.2, 2.5), pwpp_hip.MEM_HOST_PINNED, b"mem 2: the "),
+]
+
+
+def test_shared_bad_inputs_are_named_alike_by_all_three_entry_points(lib):
+    img = np.zeros(16, np.int32)
+    box = np.zeros(4, ob.BOX_DTYPE)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # (never dereferenced: these checks come first)
+    entry_points = {
+        "pwpp_rasterize_obstacles": lambda g, band, mem: lib.pwpp_rasterize_obstacles(fake, g, band[0], band[1], 0, 1, mem, vp(img), None, None),
+        "pwpp_label_obstacles": lambda g, band, mem: lib.pwpp_label_obstacles(fake, g, band[0], band[1], 1, 8, 0, 1, mem, vp(img), None, None, None, None, 0, None),
+        "pwpp_box_obstacles": lambda g, band, mem: lib.pwpp_box_obstacles(fake, g, band[0], band[1], 0, 1, mem, vp(img), vp(box), 4),
+    }
+    for what, fields, band, mem, fragment in SHARED_BAD_INPUTS:
+        g = pwpp_hip.GroundGrid(**dict(dict(x0=0.0, y0=0.0, cell=1.0, nx=4, ny=4, flags=0, pad_=0), **fields))
+        for name, call in entry_points.items():
+            assert call(ctypes.byref(g), band, mem) == E_ARG, "%s: %s" % (name, what)
+            assert fragment in lib.pwpp_last_error(), "%s, %s: %s" % (name, what, lib.pwpp_last_error())
+            if what.startswith("mem"):
+                assert b"take PWPP_MEM_HOST or PWPP_MEM_DEVICE" in lib.pwpp_last_error(), name
+
+
+def test_the_batch_has_clusters_and_boxes_in_the_sub_range(oracle_built):
+    oracle = oracle_built.restatement()
+    p = oracle.default_params()
+    x0, y0, cell, nx, ny = GRID
+    lists = []
+    for f, pts in enumerate(batch()):
+        assert 2000 <= len(pts) <= 6400
+        ref = ol.Estimator(oracle, arith=ol.ARITH_FXP).run(pts)
+        lists.append(len(ref.nonground_idx))
+        xyz = np.ascontiguousarray(pts[np.sort(ref.nonground_idx), :3], F32)
+        s, _ = gq.restate_query(xyz, ref.records, p)
+        count, top, _ = og.restate_obstacles(xyz, s, x0, y0, cell, nx, ny, *BAND)
+        label, table, n = oc.flood_fill(count, top, MIN_COUNT, CONN)
+        kx, ix = og.cells_of(xyz[:, 0], x0, cell, nx)
+        ky, iy = og.cells_of(xyz[:, 1], y0, cell, ny)
+        hgt = np.ascontiguousarray(s["distance"], F32)
+        with np.errstate(invalid="ignore"):
+            counted = kx & ky & (s["patch"] >= 0) & (F32(BAND[0]) <= hgt) & (hgt <= F32(BAND[1]))
+        rows = ob.box_rows(*GRID, xyz[counted], hgt[counted], label[iy[counted], ix[counted]].astype(np.int32), MAX_ROWS)
+        print("frame %d: %d non-ground points, %d counted, %d clusters, %d boxes with points" % (f, lists[-1], counted.sum(), n, (rows["points"] > 0).sum()))
+        if f >= FIRST:
+            assert 2 <= n <= MAX_ROWS and (rows["points"][:n] > 0).all() and rows["points"].sum() == count[label >= 0].sum() > 50
+    assert lists[2] > max(lists[:2]) and lists[0] != lists[1]
