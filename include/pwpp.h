@@ -592,6 +592,53 @@ PWPP_API int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float
 PWPP_API int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz /* (m,3) */, const float *hgt /* m */,
                              const int32_t *row /* m */, int64_t m, pwpp_obstacle_box *boxes, int max_boxes);
 
+/* ---- the distance of every cell to the nearest occupied cell (pwpp_distance_grid, pwpp_distance_obstacles) ------------------------
+ * What a costmap, a planner and a collision check start from: for every cell of an obstacle grid, occupied or free, how far the
+ * nearest occupied cell is and which one it is -- an exact Euclidean distance transform on the device, each frame on its own,
+ * without a count image per frame leaving the device for a CPU transform.
+ *   occupied  A cell is occupied iff count >= min_count; min_count >= 1 (the rule of pwpp_label_grid).
+ *   dist2     dist2[f][iy][ix] = the minimum of (ix - jx)^2 + (iy - jy)^2 over the occupied cells (jx, jy) of the same frame, an
+ *             exact integer: 0 on an occupied cell, PWPP_DIST_BEYOND when the frame has no occupied cell.
+ *   nearest   nearest[f][iy][ix] = jy * nx + jx of the cell that attains the minimum, the SMALLEST such index among several; -1
+ *             where dist2 is PWPP_DIST_BEYOND.  Consequence: label[f].flat[nearest] is the nearest cluster of every cell.
+ *   metres    metres[f][iy][ix] = (float)(sqrt((double)dist2) * cell): one correctly rounded square root, one multiply in double,
+ *             one rounding to float; +inf where dist2 is PWPP_DIST_BEYOND.  pwpp_distance_obstacles uses g->cell; `cell` is read
+ *             only when metres != NULL.
+ *   max_dist  Cells, 0 .. 46340; 0: unlimited.  With max_dist > 0 every cell whose TRUE dist2 exceeds max_dist^2 reports
+ *             PWPP_DIST_BEYOND / -1 / +inf, and every other cell exactly what the unlimited call reports: it lets the kernels
+ *             bound their search (an inflation radius is a few metres), it is not an approximation.
+ *   Frames never influence each other.  All three images are functions of the count image alone: the same bytes for every call,
+ *   mem, alignment, max_dist window strategy and value of the option "distance_path".
+ *   distance_obstacles   count is exactly the image pwpp_rasterize_obstacles(g, h_min, h_max, ...) gives for the frame range,
+ *             written for the caller where asked for and kept in the handle's cluster buffer otherwise; the other images are
+ *             exactly what pwpp_distance_grid gives for it.  When, mem, the grid's flags, the lifetime rule of the INPUT and the
+ *             errors are those of pwpp_label_obstacles.
+ *   mem       PWPP_MEM_HOST: every array is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory, 4-byte aligned and no more, enqueued on the handle's stream, complete after
+ *             pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched: a null handle, (pwpp_distance_grid) count, dist2 or grid; nx, ny or
+ *             frames < 1; nx or ny > 32768 (the largest possible dist2, 2 * 32767^2, stays below PWPP_DIST_BEYOND); nx * ny *
+ *             frames beyond 2^31; min_count < 1; max_dist outside 0 .. 46340; a non-null metres with a cell that is not finite
+ *             and positive; for pwpp_distance_obstacles everything pwpp_rasterize_obstacles rejects.  pwpp_distance_obstacles
+ *             before any estimate call: PWPP_E_STATE.
+ *   buffers   The kernels' working image lives in the cluster buffer: one int32 per cell, the nearest occupied column of the
+ *             cell's own row.  Allocated on first use, counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *             pwpp_distance_grid needs a handle for its stream and this buffer only, like pwpp_label_grid.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of the estimate path changes. */
+#define PWPP_HAS_OBSTACLE_DISTANCE 1
+#define PWPP_DIST_BEYOND 0x7fffffff
+/* any occupancy image: needs a handle (stream, buffer), no estimate call -- like pwpp_label_grid */
+PWPP_API int pwpp_distance_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
+                                const int32_t *count /* [frames][ny][nx] */, int min_count,
+                                int max_dist /* cells; 0: unlimited */, double cell /* metres per cell; read only when metres != NULL */,
+                                int32_t *dist2 /* [frames][ny][nx] */, int32_t *nearest /* same shape, may be NULL */,
+                                float *metres /* same shape, may be NULL */);
+/* rasterize + distance for frames of the LAST estimate call, one call -- like pwpp_label_obstacles */
+PWPP_API int pwpp_distance_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                     int min_count, int max_dist, int frame_first, int frames, int mem,
+                                     int32_t *dist2, int32_t *nearest /* may be NULL */, float *metres /* may be NULL */,
+                                     int32_t *count /* may be NULL: kept in the handle's buffer */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -714,6 +761,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         two by tools/obstacle_boxes_cost.py; "1": every counted lane issues its atomics on its row (the yardstick);
  *                         "2": the lanes of a wave that name the same row are summed first, one set of atomics per distinct row.
  *                         The results are identical bytes.
+ *   "distance_path"       how the column pass of the obstacle distances runs (pwpp_distance_grid, pwpp_distance_obstacles): "0"
+ *                         (default) the strip's rows in LDS where they fit, outward from the cell's own row with the exact early
+ *                         exit; "1": every row from global memory, no LDS, no early exit (the yardstick of
+ *                         tools/obstacle_distance_cost.py).  The results are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

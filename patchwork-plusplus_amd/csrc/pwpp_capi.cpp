@@ -24,6 +24,7 @@
 #include "../../include/pwpp.h"
 #include "pwpp_boxes.h"
 #include "pwpp_dev.h"
+#include "pwpp_distance.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
 static_assert(sizeof(pwpp_ground_sample) == sizeof(PwppGroundSample) && sizeof(pwpp_ground_sample) == 16, "pwpp_ground_sample must mirror PwppGroundSample");
@@ -244,6 +245,7 @@ struct pwpp_handle {
     DevBuf<uint32_t> d_clusters{bufs, kPerBatch};  // the cluster buffer, in 4-byte words: the kernels' working image and chunk counts, then whatever
                                                    // images, table, counts and point ids the call stages or keeps (Staging)
     int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
+    int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
     bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
@@ -2090,6 +2092,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 1) return fail(PWPP_E_ARG, "clusters_path=%s: 0 or 1 expected", value);
         h->clusters_path = v;
+    } else if (k == "distance_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "distance_path=%s: 0 or 1 expected", value);
+        h->distance_path = v;
     } else if (k == "boxes_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
@@ -2472,6 +2478,82 @@ int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
         if (lrc != 0) return launch_failed(h, lrc);
     }
     return st.end();
+}
+
+// ---- obstacle distances: every cell's distance to the nearest occupied cell, and that cell ----------------------------------------
+namespace {
+static_assert(PWPP_DIST_BEYOND == PWPP_DIST_NONE, "PWPP_DIST_BEYOND is the kernels' PWPP_DIST_NONE");
+// what both entry points check of an image's sides (the largest dist2, 2 * 32767^2, stays below PWPP_DIST_BEYOND) ...
+int distance_side_args(int nx, int ny) {
+    if (nx > PWPP_DIST_MAX_SIDE || ny > PWPP_DIST_MAX_SIDE) return fail(PWPP_E_ARG, "%d x %d cells: the obstacle distances take at most 32768 a side", nx, ny);
+    return PWPP_OK;
+}
+
+// ... of min_count and max_dist ...
+int distance_param_args(int min_count, int max_dist) {
+    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (max_dist < 0 || max_dist > PWPP_DIST_MAX_CAP) return fail(PWPP_E_ARG, "max_dist %d: 0 (unlimited) .. 46340 cells expected", max_dist);
+    return PWPP_OK;
+}
+
+// ... and pwpp_distance_grid of its images, before the device is touched
+int distance_args(int nx, int ny, int frames, int mem, int min_count, int max_dist, double cell, const float *metres, size_t &cells) {
+    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
+    int rc = distance_side_args(nx, ny);
+    if (rc) return rc;
+    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
+    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
+    if ((rc = distance_param_args(min_count, max_dist))) return rc;
+    if (metres && (!(cell > 0.0) || !std::isfinite(cell))) return fail(PWPP_E_ARG, "cell size %g: finite and positive expected with a metres image", cell);
+    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle distances take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
+    cells = (size_t)per_frame * (size_t)frames;
+    return PWPP_OK;
+}
+}  // namespace
+
+// The cluster buffer of a call: the kernels' working image first, then the sections the call stages.
+int pwpp_distance_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, int min_count, int max_dist, double cell, int32_t *dist2,
+                       int32_t *nearest, float *metres) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!count || !dist2) return fail(PWPP_E_ARG, "null %s image", count ? "dist2" : "count");
+    size_t cells = 0;
+    int rc = distance_args(nx, ny, frames, mem, min_count, max_dist, cell, metres, cells);
+    if (rc) return rc;
+    if ((rc = enter(h, true))) return rc;  // (like pwpp_label_grid: the call in flight lands first; no results are needed)
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(pwpp_distance_work_words(nx, ny, frames), nullptr, Staging::kKept);
+    const int s_count = st.add(cells, count, Staging::kIn), s_dist2 = st.add(cells, dist2, Staging::kOut);
+    const int s_near = st.add(nearest ? cells : 0, nearest, Staging::kOut), s_metres = st.add(metres ? cells : 0, metres, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    const int lrc = pwpp_launch_distance_grid(nx, ny, frames, st.dev<const int32_t>(s_count), min_count, max_dist, cell, h->distance_path,
+                                              st.dev<int32_t>(s_dist2), st.dev<int32_t>(s_near), st.dev<float>(s_metres), st.dev<uint32_t>(s_work), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// pwpp_rasterize_obstacles (the count image alone) and pwpp_distance_grid on it, enqueued as one sequence.  A count image the
+// caller does not ask for stays in the cluster buffer.
+int pwpp_distance_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int max_dist, int frame_first, int frames,
+                            int mem, int32_t *dist2, int32_t *nearest, float *metres, int32_t *count) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !dist2) return fail(PWPP_E_ARG, "null %s", g ? "dist2 image" : "grid");
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    if ((rc = distance_side_args(g->nx, g->ny))) return rc;
+    if ((rc = distance_param_args(min_count, max_dist))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;  // (the cell size of metres is the grid's: finite and positive)
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(pwpp_distance_work_words(g->nx, g->ny, frames), nullptr, Staging::kKept);
+    const int s_count = st.add(cells, count, count ? Staging::kOut : Staging::kKept), s_dist2 = st.add(cells, dist2, Staging::kOut);
+    const int s_near = st.add(nearest ? cells : 0, nearest, Staging::kOut), s_metres = st.add(metres ? cells : 0, metres, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), nullptr, nullptr, h->stream);
+    if (lrc == 0)
+        lrc = pwpp_launch_distance_grid(g->nx, g->ny, frames, st.dev<int32_t>(s_count), min_count, max_dist, g->cell, h->distance_path, st.dev<int32_t>(s_dist2),
+                                        st.dev<int32_t>(s_near), st.dev<float>(s_metres), st.dev<uint32_t>(s_work), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -325,6 +325,10 @@ int pwpp_launch_box_rows(int step, int64_t rows, uint32_t *acc, double x0, doubl
 size_t pwpp_cluster_work_words(int nx, int ny, int frames);
 int pwpp_launch_label_grid(int nx, int ny, int frames, const int32_t *count, const float *top, int min_count, int connectivity, int path,
                            int32_t *label, void *clusters, int32_t *n_clusters, int max_clusters, uint32_t *work, hipStream_t stream);
+// pwpp_distance.hip
+size_t pwpp_distance_work_words(int nx, int ny, int frames);
+int pwpp_launch_distance_grid(int nx, int ny, int frames, const int32_t *count, int min_count, int max_dist, double cell, int path, int32_t *dist2,
+                              int32_t *nearest, float *metres, uint32_t *work, hipStream_t stream);
 }
 
 #endif

@@ -375,6 +375,29 @@ public:
         c.count = n;
         return c;
     }
+    // ... and every cell's distance to the nearest occupied cell (pwpp_distance_obstacles): the squared distance in cells
+    // (PWPP_DIST_BEYOND: none in reach), the index iy * nx + ix of that cell (-1: none; the smallest among several) and the
+    // distance in metres (+inf: none) -- an exact Euclidean distance transform, what a costmap inflater starts from.  max_dist > 0:
+    // cells further than max_dist cells from every occupied cell report none.  clusters.label[nearest] is the nearest cluster.
+    struct ObstacleDistances {
+        std::vector<int32_t> dist2;    // ny x nx, row-major: row iy, column ix
+        std::vector<int32_t> nearest;  // same shape
+        Points metres;                 // (ny, nx)
+    };
+    ObstacleDistances getObstacleDistances(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count = 1, int max_dist = 0,
+                                           bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        ObstacleDistances d;
+        d.metres = Points(ny > 0 ? ny : 0, nx > 0 ? nx : 0);
+        d.dist2.assign((size_t)d.metres.rows() * (size_t)d.metres.cols(), PWPP_DIST_BEYOND);
+        d.nearest.assign(d.dist2.size(), -1);
+        int32_t none_d = 0, none_n = 0;
+        float none_m = 0.0f;
+        const bool any = !d.dist2.empty();
+        check(pwpp_distance_obstacles(h_, &g, h_min, h_max, min_count, max_dist, 0, 1, PWPP_MEM_HOST, any ? d.dist2.data() : &none_d,
+                                      any ? d.nearest.data() : &none_n, any ? d.metres.data() : &none_m, nullptr));
+        return d;
+    }
     // ... and every cluster as an oriented box (pwpp_box_obstacles on the labels above): centre, heading, length and width in
     // metres, the spread along and across, the extent in height over ground and in z.  boxes[r] belongs to clusters[r].
     struct ObstacleBoxes {

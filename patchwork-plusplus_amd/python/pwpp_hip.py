@@ -84,6 +84,7 @@ class ObstacleBox(ctypes.Structure):  # pwpp_obstacle_box (64 bytes)
 OBSTACLE_BOX_DTYPE = np.dtype([("points", "<i4"), ("pad_", "<i4")] + [(n, "<f4") for n in _BOX_FLOATS])
 GROUND_SAMPLE_DTYPE = np.dtype([("patch", "<i4"), ("decision", "<i4"), ("ground_z", "<f4"), ("distance", "<f4")])
 GRID_GROUND_ONLY = 1
+DIST_BEYOND = 0x7fffffff  # PWPP_DIST_BEYOND: dist2 where no occupied cell is in reach (nearest -1, metres +inf)
 
 
 class PwppError(RuntimeError):
@@ -186,6 +187,9 @@ def load():
         if hasattr(L, "pwpp_box_obstacles"):  # (as above: an older build has no obstacle boxes)
             L.pwpp_box_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, ci]
             L.pwpp_box_points.argtypes = [ctypes.POINTER(GroundGrid), vp, vp, vp, ctypes.c_int64, vp, ci]
+        if hasattr(L, "pwpp_distance_grid"):  # (as above: an older build has no obstacle distances)
+            L.pwpp_distance_grid.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ctypes.c_double, vp, vp, vp]
+            L.pwpp_distance_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -836,6 +840,58 @@ class Handle:
                                                  int(frame_first), frames, MEM_DEVICE, ctypes.c_void_p(label_ptr), ctypes.c_void_p(count_ptr or None),
                                                  ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(clusters_ptr or None),
                                                  ctypes.c_void_p(n_clusters_ptr or None), int(max_clusters), ctypes.c_void_p(point_cluster_ptr or None)))
+
+    def distance_grid(self, count, min_count=1, max_dist=0, cell=1.0, want_nearest=True, want_metres=True):
+        """The exact Euclidean distance of every cell of a (frames, ny, nx) or (ny, nx) int32 count image to the nearest occupied
+        cell (count >= min_count) of its frame.  Works before any estimate call.  Returns (dist2, nearest, metres) of count's
+        shape: the int32 squared distance in cells (DIST_BEYOND: none in reach), the int32 index iy * nx + ix of the nearest
+        occupied cell (the smallest among several; -1: none) and float32 sqrt(dist2) * cell (+inf: none); None for an image that
+        is not wanted.  max_dist > 0: cells further than max_dist cells from every occupied cell report none (include/pwpp.h)."""
+        count = np.ascontiguousarray(count, np.int32)
+        shape = count.shape
+        c3 = count.reshape((1,) + shape) if count.ndim == 2 else count
+        if c3.ndim != 3:
+            raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+        frames, ny, nx = c3.shape
+        dist2 = np.empty(c3.shape, np.int32)
+        nearest = np.empty(c3.shape, np.int32) if want_nearest else None
+        metres = np.empty(c3.shape, np.float32) if want_metres else None
+        # (an empty image still goes to the library: it is the one that names the bad argument)
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_distance_grid(self._h, nx, ny, frames, MEM_HOST, ptr(c3), int(min_count), int(max_dist), float(cell), ptr(dist2),
+                                               ptr(nearest), ptr(metres)))
+        return tuple(None if a is None else a.reshape(shape) for a in (dist2, nearest, metres))
+
+    def distance_grid_device(self, nx, ny, frames, count_ptr, min_count, max_dist, cell, dist2_ptr, nearest_ptr=0, metres_ptr=0):
+        """distance_grid on device memory: addresses of the (frames, ny, nx) int32 count and dist2 images and (0: not wanted) the
+        int32 nearest and float32 metres images, 4-byte aligned.  Enqueued on the handle's stream; complete after synchronize()."""
+        self._check(self._L.pwpp_distance_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, ctypes.c_void_p(count_ptr), int(min_count), int(max_dist),
+                                               float(cell), ctypes.c_void_p(dist2_ptr), ctypes.c_void_p(nearest_ptr or None), ctypes.c_void_p(metres_ptr or None)))
+
+    def distance_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, min_count=1, max_dist=0, frame_first=0, frames=None, ground_only=False,
+                           want_nearest=True, want_metres=True, want_count=False):
+        """rasterize_obstacles and distance_grid in one call, for frames of the last estimate call.  Returns (dist2, nearest,
+        metres) as distance_grid does for the (frames, ny, nx) count image, metres with the grid's cell; want_count: then that
+        int32 count image too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        dist2 = np.empty(shape, np.int32)
+        nearest = np.empty(shape, np.int32) if want_nearest else None
+        metres = np.empty(shape, np.float32) if want_metres else None
+        count = np.empty(shape, np.int32) if want_count else None
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_distance_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(max_dist), int(frame_first),
+                                                    frames, MEM_HOST, ptr(dist2), ptr(nearest), ptr(metres), ptr(count)))
+        return (dist2, nearest, metres) + ((count,) if want_count else ())
+
+    def distance_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, min_count, max_dist, dist2_ptr, nearest_ptr=0, metres_ptr=0, count_ptr=0,
+                                  frame_first=0, frames=None, ground_only=False):
+        """distance_obstacles into device memory: addresses as in distance_grid_device, count_ptr the int32 count image (0: not
+        wanted).  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_distance_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(max_dist), int(frame_first),
+                                                    frames, MEM_DEVICE, ctypes.c_void_p(dist2_ptr), ctypes.c_void_p(nearest_ptr or None),
+                                                    ctypes.c_void_p(metres_ptr or None), ctypes.c_void_p(count_ptr or None)))
 
     def box_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_boxes, frame_first=0, frames=None, ground_only=False):
         """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as oriented

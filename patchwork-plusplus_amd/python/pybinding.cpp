@@ -184,6 +184,17 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("connectivity") = 8, py::arg("ground_only") = false)
+        .def("getObstacleDistances",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_dist, bool ground_only) {
+                 const PatchWorkpp::ObstacleDistances d = s.getObstacleDistances(x0, y0, cell, nx, ny, h_min, h_max, min_count, max_dist, ground_only);
+                 py::array_t<int32_t> dist2({(py::ssize_t)d.metres.rows(), (py::ssize_t)d.metres.cols()});
+                 py::array_t<int32_t> nearest({(py::ssize_t)d.metres.rows(), (py::ssize_t)d.metres.cols()});
+                 if (!d.dist2.empty()) std::memcpy(dist2.mutable_data(), d.dist2.data(), d.dist2.size() * sizeof(int32_t));
+                 if (!d.nearest.empty()) std::memcpy(nearest.mutable_data(), d.nearest.data(), d.nearest.size() * sizeof(int32_t));
+                 return py::make_tuple(dist2, nearest, to_numpy(d.metres));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("min_count") = 1, py::arg("max_dist") = 0, py::arg("ground_only") = false)
         .def("getObstacleBoxes",
              [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int connectivity,
                 bool ground_only) {
