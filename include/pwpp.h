@@ -639,6 +639,68 @@ PWPP_API int pwpp_distance_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, 
                                      int32_t *dist2, int32_t *nearest /* may be NULL */, float *metres /* may be NULL */,
                                      int32_t *count /* may be NULL: kept in the handle's buffer */);
 
+/* ---- line-of-sight free space on the obstacle grid (pwpp_visibility_grid, pwpp_visibility_obstacles) ------------------------------
+ * What separates a cell that holds no obstacle because it was SEEN to be empty from one that holds none because something hides
+ * it from the sensor: for every cell of an occupancy image the first occupied cell on the digital line from the sensor's cell,
+ * and from it the tri-state byte of a nav_msgs/OccupancyGrid -- on the device, each frame on its own, all integer arithmetic.
+ * THIS IS 2-D LINE OF SIGHT ON A 2.5-D MAP: a free cell behind a low obstacle that the sensor saw OVER is reported unknown.
+ *   occupied  A cell is occupied iff count >= min_count; min_count >= 1 (the rule of pwpp_label_grid).
+ *   origin    One sensor cell o = (ox, oy) per frame, inside the image.  n_origins == 1: that origin for every frame; n_origins ==
+ *             frames: entry i for frame frame_first + i; any other number: PWPP_E_ARG.  The array is HOST memory in both mem kinds
+ *             and is copied at the call (as pwpp_set_input_transforms copies T): the caller may free it on return.
+ *             pwpp_visibility_obstacles takes positions in metres in the model's frame -- normally {0, 0}; with input transforms
+ *             set, the t of the transform -- and turns them into cells by the cell rule of pwpp_rasterize_obstacles, in double:
+ *             u = (x - x0) / cell, ox = (int)floor(u).  A position that is not finite or falls outside the grid: PWPP_E_ARG, naming
+ *             the entry.
+ *   line      For the cell c = (cx, cy): dx = cx - ox, dy = cy - oy, n = max(|dx|, |dy|); P_0 = o and for k = 1 .. n
+ *             P_k = (ox + sgn(dx) * ((2k|dx| + n) / (2n)), oy + sgn(dy) * ((2k|dy| + n) / (2n))), the divisions rounding down.
+ *             P_n = c; consecutive points differ by at most 1 in each coordinate.
+ *   first     Walk k = 1 .. n; at each step, in this order: (a) if both coordinates changed from P_{k-1} to P_k, take
+ *             A = (x_{k-1}, y_k) and B = (x_k, y_{k-1}); both occupied: the line is blocked, first = the smaller of their indices
+ *             (jy * nx + jx), stop -- a line does not squeeze diagonally between two occupied cells, so a wall that is only
+ *             8-connected is opaque; (b) if P_k is occupied: first = its index, stop.  Nothing found: PWPP_VIS_NONE.  n == 0: the
+ *             cell's own index if it is occupied, else PWPP_VIS_NONE.  The origin's cell never blocks another cell (k starts at
+ *             1): it holds the vehicle's own returns.  So first == own index: a seen surface; first == PWPP_VIS_NONE: seen and
+ *             free; anything else: hidden, and label[f].flat[first] is the cluster that hides it.
+ *   max_range Cells, Chebyshev, 0 .. 32768; 0: unlimited.  A cell with n > max_range reports PWPP_VIS_BEYOND, every other cell
+ *             exactly what the unlimited call reports (its walk only passes cells with a smaller n): it bounds the work, it is
+ *             not an approximation.
+ *   occupancy PWPP_OCC_OCCUPIED where the cell is occupied, hidden or not (it holds returns: it was seen in 3-D); otherwise
+ *             PWPP_OCC_FREE where first == PWPP_VIS_NONE; PWPP_OCC_UNKNOWN in all other cases, hidden or beyond range.
+ *   Frames never influence each other.  Both images are functions of the count image, the origins, min_count and max_range alone:
+ *   the same bytes for every call, mem, alignment and value of the option "visibility_path".
+ *   visibility_obstacles   count is exactly the image pwpp_rasterize_obstacles(g, h_min, h_max, ...) gives for the frame range,
+ *             written for the caller where asked for and kept in the handle's cluster buffer otherwise; the other images are
+ *             exactly what pwpp_visibility_grid gives for it.  When, mem, the grid's flags, the lifetime rule of the INPUT and the
+ *             errors are those of pwpp_distance_obstacles.
+ *   mem       PWPP_MEM_HOST: every image is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- first and count 4-byte aligned and no more, occupancy byte aligned -- enqueued on
+ *             the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, count, first, origin or grid; nx, ny
+ *             or frames < 1; nx or ny > 32768; nx * ny * frames beyond 2^31; min_count < 1; max_range outside 0 .. 32768; the
+ *             number of origins; an origin outside the image; mem.  For pwpp_visibility_obstacles everything
+ *             pwpp_rasterize_obstacles rejects; before any estimate call: PWPP_E_STATE.
+ *   buffers   The kernels' working image lives in the cluster buffer: one BIT per cell, rows padded to 32 (8 KiB for 256 x 256
+ *             cells), and the origins where there is one per frame.  Allocated on first use, counted by pwpp_get_workspace_bytes,
+ *             freed by pwpp_trim_workspace.  pwpp_visibility_grid needs a handle for its stream and this buffer only.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of the estimate path changes. */
+#define PWPP_HAS_OBSTACLE_VISIBILITY 1
+#define PWPP_VIS_NONE   (-1)   /* nothing on the line: the cell is seen */
+#define PWPP_VIS_BEYOND (-2)   /* further than max_range: not examined */
+enum { PWPP_OCC_FREE = 0, PWPP_OCC_OCCUPIED = 100, PWPP_OCC_UNKNOWN = -1 };   /* nav_msgs/OccupancyGrid values */
+
+/* any occupancy image: needs a handle (stream, buffer), no estimate call -- like pwpp_distance_grid */
+PWPP_API int pwpp_visibility_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
+                                  const int32_t *count /* [frames][ny][nx] */, int min_count,
+                                  const int32_t *origin /* HOST memory, n_origins x {ox, oy} cells */, int n_origins,
+                                  int max_range /* cells, Chebyshev; 0: unlimited */,
+                                  int32_t *first /* [frames][ny][nx] */, int8_t *occupancy /* same shape, may be NULL */);
+/* rasterize + visibility for frames of the LAST estimate call, one call -- like pwpp_distance_obstacles */
+PWPP_API int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                       int min_count, const double *origin_xy /* HOST, n_origins x {x, y} metres */, int n_origins,
+                                       int max_range, int frame_first, int frames, int mem,
+                                       int32_t *first, int8_t *occupancy /* may be NULL */, int32_t *count /* may be NULL: kept */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -765,6 +827,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         (default) the strip's rows in LDS where they fit, outward from the cell's own row with the exact early
  *                         exit; "1": every row from global memory, no LDS, no early exit (the yardstick of
  *                         tools/obstacle_distance_cost.py).  The results are identical bytes.
+ *   "visibility_path"     how the line-of-sight free space tests a cell (pwpp_visibility_grid, pwpp_visibility_obstacles): "0"
+ *                         (default) a bit image of the frame, one ballot per 64 cells, kept in LDS where it fits; "1": no bit
+ *                         image, no LDS, every test reads count in global memory (the yardstick of
+ *                         tools/obstacle_visibility_cost.py).  The results are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

@@ -25,6 +25,7 @@
 #include "pwpp_boxes.h"
 #include "pwpp_dev.h"
 #include "pwpp_distance.h"
+#include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
 static_assert(sizeof(pwpp_ground_sample) == sizeof(PwppGroundSample) && sizeof(pwpp_ground_sample) == 16, "pwpp_ground_sample must mirror PwppGroundSample");
@@ -246,6 +247,8 @@ struct pwpp_handle {
                                                    // images, table, counts and point ids the call stages or keeps (Staging)
     int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
     int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
+    int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
+    std::vector<int32_t> vis_origins;  // the origin cells of the last visibility call with one origin per frame: the source of its upload
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
     bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
@@ -1177,8 +1180,9 @@ class Staging {
   public:
     enum Dir { kIn, kOut, kKept };  // read by the kernels | written by them | theirs alone: in the buffer whatever the memory kind
     Staging(pwpp_handle *h, DevBuf<uint32_t> &buf, int mem, size_t align = 1) : h_(h), buf_(buf), host_(mem == PWPP_MEM_HOST), align_(align) {}
-    int add(size_t words, const void *user, Dir dir) {  // (at most kMaxSections per call)
-        sec_[n_] = Section{words_, words, user, dir};
+    // (at most kMaxSections per call; `bytes`: of the caller's array where it is no whole number of words -- a byte image)
+    int add(size_t words, const void *user, Dir dir, size_t bytes = 0) {
+        sec_[n_] = Section{words_, words, bytes ? bytes : words * 4, user, dir};
         if (dir == kKept || host_) words_ += (words + align_ - 1) / align_ * align_;
         return n_++;
     }
@@ -1187,7 +1191,7 @@ class Staging {
         if (rc) return rc;
         for (int k = 0; k < n_ && host_; ++k)
             if (sec_[k].dir == kIn && sec_[k].user && sec_[k].words > 0)
-                HIPCHK(hipMemcpyAsync(buf_.p + sec_[k].at, sec_[k].user, sec_[k].words * 4, hipMemcpyHostToDevice, h_->stream));
+                HIPCHK(hipMemcpyAsync(buf_.p + sec_[k].at, sec_[k].user, sec_[k].bytes, hipMemcpyHostToDevice, h_->stream));
         return PWPP_OK;
     }
     template <class T>
@@ -1203,7 +1207,7 @@ class Staging {
         }
         for (int k = 0; k < n_; ++k)
             if (sec_[k].dir == kOut && sec_[k].user && sec_[k].words > 0)
-                HIPCHK(hipMemcpyAsync(const_cast<void *>(sec_[k].user), buf_.p + sec_[k].at, sec_[k].words * 4, hipMemcpyDeviceToHost, h_->stream));
+                HIPCHK(hipMemcpyAsync(const_cast<void *>(sec_[k].user), buf_.p + sec_[k].at, sec_[k].bytes, hipMemcpyDeviceToHost, h_->stream));
         HIPCHK(hipStreamSynchronize(h_->stream));
         return PWPP_OK;
     }
@@ -1211,7 +1215,7 @@ class Staging {
   private:
     static constexpr int kMaxSections = 8;
     struct Section {
-        size_t at, words;
+        size_t at, words, bytes;
         const void *user;
         Dir dir;
     };
@@ -2096,6 +2100,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 1) return fail(PWPP_E_ARG, "distance_path=%s: 0 or 1 expected", value);
         h->distance_path = v;
+    } else if (k == "visibility_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "visibility_path=%s: 0 or 1 expected", value);
+        h->visibility_path = v;
     } else if (k == "boxes_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
@@ -2553,6 +2561,114 @@ int pwpp_distance_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_m
     if (lrc == 0)
         lrc = pwpp_launch_distance_grid(g->nx, g->ny, frames, st.dev<int32_t>(s_count), min_count, max_dist, g->cell, h->distance_path, st.dev<int32_t>(s_dist2),
                                         st.dev<int32_t>(s_near), st.dev<float>(s_metres), st.dev<uint32_t>(s_work), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// ---- line-of-sight free space: the first occupied cell between the sensor's cell and every cell, and the tri-state byte ----------
+namespace {
+static_assert(PWPP_VIS_NONE == PWPP_VIS_FIRST_NONE && PWPP_VIS_BEYOND == PWPP_VIS_FIRST_BEYOND, "the kernels' values of first");
+static_assert(PWPP_OCC_FREE == PWPP_VIS_FREE && PWPP_OCC_OCCUPIED == PWPP_VIS_OCCUPIED && PWPP_OCC_UNKNOWN == PWPP_VIS_UNKNOWN, "the kernels' occupancy bytes");
+// what both entry points check of an image's sides ...
+int visibility_side_args(int nx, int ny) {
+    if (nx > PWPP_VIS_MAX_SIDE || ny > PWPP_VIS_MAX_SIDE) return fail(PWPP_E_ARG, "%d x %d cells: the visibility takes at most 32768 a side", nx, ny);
+    return PWPP_OK;
+}
+
+// ... of min_count and max_range ...
+int visibility_param_args(int min_count, int max_range) {
+    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (max_range < 0 || max_range > PWPP_VIS_MAX_SIDE) return fail(PWPP_E_ARG, "max_range %d: 0 (unlimited) .. 32768 cells expected", max_range);
+    return PWPP_OK;
+}
+
+// ... and of the number of origins
+int visibility_origin_count(int n_origins, int frames) {
+    if (n_origins < 1 || (n_origins != 1 && n_origins != frames)) return fail(PWPP_E_ARG, "%d origins for %d frames: 1 or one per frame expected", n_origins, frames);
+    return PWPP_OK;
+}
+
+// The kernels over the sections of a call; `cells`: the origin cells, n_origins x {ox, oy}, checked.  One origin travels as an
+// argument; one per frame is copied into its section from the handle's own copy (the caller's array may go on return).  The
+// result is a HIP error code, like a launcher's.
+int visibility_launch(pwpp_handle *h, Staging &st, int nx, int ny, int frames, int min_count, const std::vector<int32_t> &cells, int max_range, int s_count,
+                      int s_first, int s_occ, int s_org, int s_work) {
+    const int32_t *d_org = nullptr;
+    if (cells.size() > 2) {
+        h->vis_origins = cells;
+        int32_t *dst = st.dev<int32_t>(s_org);
+        const hipError_t e = hipMemcpyAsync(dst, h->vis_origins.data(), h->vis_origins.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) return (int)e;
+        d_org = dst;
+    }
+    return pwpp_launch_visibility_grid(nx, ny, frames, st.dev<const int32_t>(s_count), min_count, cells[0], cells[1], d_org, max_range, h->visibility_path,
+                                       st.dev<int32_t>(s_first), st.dev<int8_t>(s_occ), st.dev<uint32_t>(s_work), h->stream);
+}
+}  // namespace
+
+// The cluster buffer of a call: the kernels' bit image and the origins first, then the sections the call stages.
+int pwpp_visibility_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, int min_count, const int32_t *origin, int n_origins,
+                         int max_range, int32_t *first, int8_t *occupancy) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!count || !first || !origin) return fail(PWPP_E_ARG, "null %s", !count ? "count image" : (!first ? "first image" : "origin"));
+    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
+    int rc = visibility_side_args(nx, ny);
+    if (rc) return rc;
+    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
+    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
+    if ((rc = visibility_param_args(min_count, max_range))) return rc;
+    if ((rc = visibility_origin_count(n_origins, frames))) return rc;
+    for (int i = 0; i < n_origins; ++i)
+        if (origin[2 * i] < 0 || origin[2 * i] >= nx || origin[2 * i + 1] < 0 || origin[2 * i + 1] >= ny)
+            return fail(PWPP_E_ARG, "origin %d, cell (%d, %d), lies outside the %d x %d cells", i, origin[2 * i], origin[2 * i + 1], nx, ny);
+    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the visibility takes PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
+    const size_t cells = (size_t)per_frame * (size_t)frames;
+    const std::vector<int32_t> org(origin, origin + 2 * (size_t)n_origins);
+    if ((rc = enter(h, true))) return rc;  // (like pwpp_distance_grid: the call in flight lands first; no results are needed)
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
+    const int s_org = st.add(n_origins > 1 ? org.size() : 0, nullptr, Staging::kKept);
+    const int s_count = st.add(cells, count, Staging::kIn), s_first = st.add(cells, first, Staging::kOut);
+    const int s_occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
+    if ((rc = st.begin())) return rc;
+    const int lrc = visibility_launch(h, st, nx, ny, frames, min_count, org, max_range, s_count, s_first, s_occ, s_org, s_work);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// pwpp_rasterize_obstacles (the count image alone) and pwpp_visibility_grid on it, enqueued as one sequence.  A count image the
+// caller does not ask for stays in the cluster buffer.
+int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
+                              int max_range, int frame_first, int frames, int mem, int32_t *first, int8_t *occupancy, int32_t *count) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !first || !origin_xy) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!first ? "first image" : "origin"));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);  // (ground_grid_args' own two checks: the origins need the grid)
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
+        return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
+    if ((rc = visibility_side_args(g->nx, g->ny))) return rc;
+    if ((rc = visibility_param_args(min_count, max_range))) return rc;
+    if ((rc = visibility_origin_count(n_origins, frames))) return rc;
+    std::vector<int32_t> org(2 * (size_t)n_origins);
+    for (int i = 0; i < n_origins; ++i) {
+        const double x = origin_xy[2 * i], y = origin_xy[2 * i + 1];
+        int ox = 0, oy = 0;
+        if (!std::isfinite(x) || !std::isfinite(y)) return fail(PWPP_E_ARG, "origin %d, (%g, %g), is not finite", i, x, y);
+        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
+            return fail(PWPP_E_ARG, "origin %d, (%g, %g) m, lies outside the grid", i, x, y);
+        org[2 * i] = ox, org[2 * i + 1] = oy;
+    }
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(pwpp_visibility_work_words(g->nx, g->ny, frames, h->visibility_path), nullptr, Staging::kKept);
+    const int s_org = st.add(n_origins > 1 ? org.size() : 0, nullptr, Staging::kKept);
+    const int s_count = st.add(cells, count, count ? Staging::kOut : Staging::kKept), s_first = st.add(cells, first, Staging::kOut);
+    const int s_occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), nullptr, nullptr, h->stream);
+    if (lrc == 0) lrc = visibility_launch(h, st, g->nx, g->ny, frames, min_count, org, max_range, s_count, s_first, s_occ, s_org, s_work);
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 

@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -329,6 +329,10 @@ int pwpp_launch_label_grid(int nx, int ny, int frames, const int32_t *count, con
 size_t pwpp_distance_work_words(int nx, int ny, int frames);
 int pwpp_launch_distance_grid(int nx, int ny, int frames, const int32_t *count, int min_count, int max_dist, double cell, int path, int32_t *dist2,
                               int32_t *nearest, float *metres, uint32_t *work, hipStream_t stream);
+// pwpp_visibility.hip
+size_t pwpp_visibility_work_words(int nx, int ny, int frames, int path);
+int pwpp_launch_visibility_grid(int nx, int ny, int frames, const int32_t *count, int min_count, int ox, int oy, const int32_t *origins, int max_range,
+                                int path, int32_t *first, int8_t *occupancy, uint32_t *work, hipStream_t stream);
 }
 
 #endif

@@ -398,6 +398,31 @@ public:
                                       any ? d.nearest.data() : &none_n, any ? d.metres.data() : &none_m, nullptr));
         return d;
     }
+    // ... and the line-of-sight free space (pwpp_visibility_obstacles): for every cell the index iy * nx + ix of the first occupied
+    // cell on the digital line from the sensor's cell (PWPP_VIS_NONE: the line is clear; PWPP_VIS_BEYOND: further than max_range >
+    // 0 cells) and the tri-state byte of a nav_msgs/OccupancyGrid (PWPP_OCC_FREE, PWPP_OCC_OCCUPIED, PWPP_OCC_UNKNOWN).  The
+    // sensor stands at (origin_x, origin_y) metres in the model's frame.  2-D line of sight on a 2.5-D map: a free cell behind a
+    // low obstacle the sensor saw over is reported unknown.
+    struct ObstacleVisibility {
+        int nx = 0, ny = 0;
+        std::vector<int32_t> first;     // ny x nx, row-major: row iy, column ix
+        std::vector<int8_t> occupancy;  // same shape
+    };
+    ObstacleVisibility getObstacleVisibility(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count = 1,
+                                             int max_range = 0, double origin_x = 0.0, double origin_y = 0.0, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        ObstacleVisibility v;
+        v.nx = nx > 0 ? nx : 0, v.ny = ny > 0 ? ny : 0;
+        v.first.assign((size_t)v.nx * (size_t)v.ny, PWPP_VIS_NONE);
+        v.occupancy.assign(v.first.size(), (int8_t)PWPP_OCC_UNKNOWN);
+        int32_t none_f = 0;
+        int8_t none_o = 0;
+        const double origin[2] = {origin_x, origin_y};
+        const bool any = !v.first.empty();
+        check(pwpp_visibility_obstacles(h_, &g, h_min, h_max, min_count, origin, 1, max_range, 0, 1, PWPP_MEM_HOST, any ? v.first.data() : &none_f,
+                                        any ? v.occupancy.data() : &none_o, nullptr));
+        return v;
+    }
     // ... and every cluster as an oriented box (pwpp_box_obstacles on the labels above): centre, heading, length and width in
     // metres, the spread along and across, the extent in height over ground and in z.  boxes[r] belongs to clusters[r].
     struct ObstacleBoxes {

@@ -85,6 +85,8 @@ OBSTACLE_BOX_DTYPE = np.dtype([("points", "<i4"), ("pad_", "<i4")] + [(n, "<f4")
 GROUND_SAMPLE_DTYPE = np.dtype([("patch", "<i4"), ("decision", "<i4"), ("ground_z", "<f4"), ("distance", "<f4")])
 GRID_GROUND_ONLY = 1
 DIST_BEYOND = 0x7fffffff  # PWPP_DIST_BEYOND: dist2 where no occupied cell is in reach (nearest -1, metres +inf)
+VIS_NONE, VIS_BEYOND = -1, -2  # PWPP_VIS_NONE, PWPP_VIS_BEYOND: first where nothing lies on the line / the cell is beyond max_range
+OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 100, -1  # PWPP_OCC_*: the occupancy bytes, nav_msgs/OccupancyGrid values
 
 
 class PwppError(RuntimeError):
@@ -190,6 +192,9 @@ def load():
         if hasattr(L, "pwpp_distance_grid"):  # (as above: an older build has no obstacle distances)
             L.pwpp_distance_grid.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ctypes.c_double, vp, vp, vp]
             L.pwpp_distance_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+        if hasattr(L, "pwpp_visibility_grid"):  # (as above: an older build has no line-of-sight free space)
+            L.pwpp_visibility_grid.argtypes = [vp, ci, ci, ci, ci, vp, ci, vp, ci, ci, vp, vp]
+            L.pwpp_visibility_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -892,6 +897,62 @@ class Handle:
         self._check(self._L.pwpp_distance_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(max_dist), int(frame_first),
                                                     frames, MEM_DEVICE, ctypes.c_void_p(dist2_ptr), ctypes.c_void_p(nearest_ptr or None),
                                                     ctypes.c_void_p(metres_ptr or None), ctypes.c_void_p(count_ptr or None)))
+
+    def visibility_grid(self, count, origin, min_count=1, max_range=0, want_occupancy=True):
+        """The line-of-sight free space of a (frames, ny, nx) or (ny, nx) int32 count image: for every cell the first occupied cell
+        (count >= min_count) on the digital line from the sensor's cell.  origin: (ox, oy) for every frame, or (frames, 2) cells.
+        Works before any estimate call.  Returns (first, occupancy) of count's shape: the int32 index iy * nx + ix of that cell
+        (VIS_NONE: the line is clear; VIS_BEYOND: the cell is further than max_range > 0 cells, Chebyshev) and the int8 byte
+        OCC_OCCUPIED / OCC_FREE / OCC_UNKNOWN (None when not wanted).  The rules: include/pwpp.h."""
+        count = np.ascontiguousarray(count, np.int32)
+        shape = count.shape
+        c3 = count.reshape((1,) + shape) if count.ndim == 2 else count
+        if c3.ndim != 3:
+            raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+        frames, ny, nx = c3.shape
+        org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 2))
+        first = np.empty(c3.shape, np.int32)
+        occupancy = np.empty(c3.shape, np.int8) if want_occupancy else None
+        # (an empty image still goes to the library: it is the one that names the bad argument)
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_visibility_grid(self._h, nx, ny, frames, MEM_HOST, ptr(c3), int(min_count), ptr(org), len(org), int(max_range),
+                                                 ptr(first), ptr(occupancy)))
+        return first.reshape(shape), None if occupancy is None else occupancy.reshape(shape)
+
+    def visibility_grid_device(self, nx, ny, frames, count_ptr, origin, min_count, max_range, first_ptr, occupancy_ptr=0):
+        """visibility_grid on device memory: addresses of the (frames, ny, nx) int32 count and first images, 4-byte aligned, and
+        (0: not wanted) the int8 occupancy image; origin stays a host array, (ox, oy) or (frames, 2).  Enqueued on the handle's
+        stream; complete after synchronize()."""
+        org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 2))
+        self._check(self._L.pwpp_visibility_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, ctypes.c_void_p(count_ptr), int(min_count),
+                                                 _vp(org) if org.size else None, len(org), int(max_range), ctypes.c_void_p(first_ptr),
+                                                 ctypes.c_void_p(occupancy_ptr or None)))
+
+    def visibility_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, origin_xy=(0.0, 0.0), min_count=1, max_range=0, frame_first=0, frames=None,
+                             ground_only=False, want_occupancy=True, want_count=False):
+        """rasterize_obstacles and visibility_grid in one call, for frames of the last estimate call.  origin_xy: the sensor's
+        position in metres in the model's frame, (x, y) for every frame or (frames, 2).  Returns (first, occupancy) as
+        visibility_grid does for the (frames, ny, nx) count image; want_count: then that int32 count image too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        first = np.empty(shape, np.int32)
+        occupancy = np.empty(shape, np.int8) if want_occupancy else None
+        count = np.empty(shape, np.int32) if want_count else None
+        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
+        self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), ptr(org), len(org),
+                                                      int(max_range), int(frame_first), frames, MEM_HOST, ptr(first), ptr(occupancy), ptr(count)))
+        return (first, occupancy) + ((count,) if want_count else ())
+
+    def visibility_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, origin_xy, min_count, max_range, first_ptr, occupancy_ptr=0, count_ptr=0,
+                                    frame_first=0, frames=None, ground_only=False):
+        """visibility_obstacles into device memory: addresses as in visibility_grid_device, count_ptr the int32 count image (0: not
+        wanted); origin_xy stays a host array.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count),
+                                                      _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
+                                                      ctypes.c_void_p(first_ptr), ctypes.c_void_p(occupancy_ptr or None), ctypes.c_void_p(count_ptr or None)))
 
     def box_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_boxes, frame_first=0, frames=None, ground_only=False):
         """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as oriented

@@ -195,6 +195,19 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("max_dist") = 0, py::arg("ground_only") = false)
+        .def("getObstacleVisibility",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_range, double origin_x,
+                double origin_y, bool ground_only) {
+                 const PatchWorkpp::ObstacleVisibility v =
+                     s.getObstacleVisibility(x0, y0, cell, nx, ny, h_min, h_max, min_count, max_range, origin_x, origin_y, ground_only);
+                 py::array_t<int32_t> first({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 py::array_t<int8_t> occupancy({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 if (!v.first.empty()) std::memcpy(first.mutable_data(), v.first.data(), v.first.size() * sizeof(int32_t));
+                 if (!v.occupancy.empty()) std::memcpy(occupancy.mutable_data(), v.occupancy.data(), v.occupancy.size());
+                 return py::make_tuple(first, occupancy);
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0, py::arg("ground_only") = false)
         .def("getObstacleBoxes",
              [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int connectivity,
                 bool ground_only) {
