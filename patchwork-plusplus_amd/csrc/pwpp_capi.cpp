@@ -2289,18 +2289,19 @@ int ground_view(pwpp_handle *h, PwppGroundView &v) {
     }
     return PWPP_OK;
 }
-int ground_mem(int mem) {
-    if (mem == PWPP_MEM_HOST || mem == PWPP_MEM_DEVICE) return PWPP_OK;
-    return fail(PWPP_E_ARG, "mem %d: the ground queries take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
-}
 
+// The memory kinds of the calls that stage their arrays; `who`: the subject and its verb, "the ground queries take".
+int mem_args(int mem, const char *who) {
+    if (mem == PWPP_MEM_HOST || mem == PWPP_MEM_DEVICE) return PWPP_OK;
+    return fail(PWPP_E_ARG, "mem %d: %s PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem, who);
+}
 }  // namespace
 
 int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, int64_t m, int mem, pwpp_ground_sample *out) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (m < 0 || m > ((int64_t)1 << 31)) return fail(PWPP_E_ARG, "%lld positions (0..2^31 supported)", (long long)m);
     if (m > 0 && (!xyz || !out)) return fail(PWPP_E_ARG, "null %s", xyz ? "output" : "positions");
-    int rc = ground_mem(mem);
+    int rc = mem_args(mem, "the ground queries take");
     if (rc) return rc;
     if ((rc = check_frame(h, 0))) return rc;
     if (m == 0) return PWPP_OK;
@@ -2314,15 +2315,23 @@ int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, in
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
+}  // extern "C"
+
 namespace {
-// What both rasters check of their grid and frame range, in this order, after the null checks of their own; lands the call in
-// flight.  `cells`: nx * ny * frames.
-int ground_grid_args(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, size_t &cells) {
+// What every entry point that takes a grid checks of it; reads the grid alone.
+int grid_geometry_args(const pwpp_ground_grid *g) {
     if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);
     if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
         return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
-    int rc = ground_mem(mem);
+    return PWPP_OK;
+}
+
+// What the entry points over the last call's results check of their grid and frame range, in this order, after the null checks
+// of their own; lands the call in flight.  `cells`: nx * ny * frames.
+int ground_grid_args(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, size_t &cells) {
+    int rc = grid_geometry_args(g);
     if (rc) return rc;
+    if ((rc = mem_args(mem, "the ground queries take"))) return rc;
     if ((rc = check_frame(h, 0))) return rc;
     if (frame_first < 0 || frames < 1 || frames > h->frames - frame_first)
         return fail(PWPP_E_ARG, "frames [%d, %d + %d) outside the last call's [0, %d)", frame_first, frame_first, frames, h->frames);
@@ -2339,9 +2348,34 @@ int obstacle_band_args(const pwpp_ground_grid *g, float h_min, float h_max) {
     return PWPP_OK;
 }
 
-// ... and of one frame's cells where a cell index is an int32 (labels, the cluster table's first_cell)
+// ... of one frame's cells where a cell index is an int32 (labels, the cluster table's first_cell) ...
 int frame_cells_args(int nx, int ny) {
     if ((int64_t)nx * (int64_t)ny > (int64_t)INT32_MAX) return fail(PWPP_E_ARG, "%d x %d cells exceed 2^31 - 1", nx, ny);
+    return PWPP_OK;
+}
+
+// ... of an image's sides where a coordinate has 15 bits (distances: the largest dist2, 2 * 32767^2, stays below
+// PWPP_DIST_BEYOND; visibility); `who` as in mem_args ...
+static_assert(PWPP_DIST_MAX_SIDE == 32768 && PWPP_VIS_MAX_SIDE == 32768, "the side limit of the message");
+int side_args(int nx, int ny, const char *who) {
+    if (nx > 32768 || ny > 32768) return fail(PWPP_E_ARG, "%d x %d cells: %s at most 32768 a side", nx, ny, who);
+    return PWPP_OK;
+}
+
+// ... and of the occupancy threshold (every operator on an occupancy image)
+int min_count_args(int min_count) {
+    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    return PWPP_OK;
+}
+
+// What the pwpp_*_grid entry points check of the shape of the caller's images.  `side_who`: the operator takes at most 32768 cells
+// a side (side_args); null: it indexes one frame's cells with an int32 (frame_cells_args).  `cells`: nx * ny * frames.
+int image_args(int nx, int ny, int frames, const char *side_who, size_t &cells) {
+    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
+    if (const int rc = side_who ? side_args(nx, ny, side_who) : frame_cells_args(nx, ny)) return rc;
+    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
+    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
+    cells = (size_t)per_frame * (size_t)frames;
     return PWPP_OK;
 }
 
@@ -2362,7 +2396,45 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
     s.h_min = h_min, s.h_max = h_max;
     return PWPP_OK;
 }
+
+// ---- operators on an occupancy image: clusters, distances, visibility ----------------------------------------------------------
+// Each has two entry points: pwpp_*_grid works on the caller's count image, pwpp_*_obstacles on the one it first rasterises from
+// the last call's non-ground lists.  An operator states its sections once (*_sections: the kernels' working words first, then
+// what the call stages) and its launch once (*_launch: a HIP error code, like a launcher's); an entry point checks its arguments,
+// declares the sections and runs one of the two tails below.
+
+// The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
+// From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
+int add_image(Staging &st, size_t cells, const void *user, bool from_raster) {
+    if (from_raster) return st.add(cells, user, user ? Staging::kOut : Staging::kKept);
+    return st.add(user ? cells : 0, user, Staging::kIn);
+}
+
+// On a caller's image.  Like a getter, the call in flight lands first; no results are needed.
+template <class Op>
+int run_on_image(pwpp_handle *h, Staging &st, Op op) {
+    int rc = enter(h, true);
+    if (rc || (rc = st.begin())) return rc;
+    const int lrc = op();
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// On the obstacle grid: pwpp_rasterize_obstacles into the sections s_count and (-1: none) s_top, then the operator and whatever
+// the entry point appends (`op`: it sees the scan and returns a HIP error code), enqueued as one sequence.
+template <class Op>
+int run_on_obstacles(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int s_count, int s_top,
+                     Op op) {
+    int rc = st.begin();
+    if (rc) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), s_top < 0 ? nullptr : st.dev<float>(s_top), nullptr, h->stream);
+    if (lrc == 0) lrc = op(scan);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
 }  // namespace
+
+extern "C" {
 
 int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, float *height, int32_t *patch) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
@@ -2402,9 +2474,9 @@ int pwpp_rasterize_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_
 
 // ---- obstacle clusters: connected occupied cells of an obstacle grid ------------------------------------------------------------
 namespace {
-// what both entry points check of min_count, connectivity and the table ...
+// what both entry points check of min_count, connectivity and the table
 int cluster_param_args(int mem, int min_count, int connectivity, const void *clusters, int max_clusters) {
-    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (const int rc = min_count_args(min_count)) return rc;
     if (connectivity != 4 && connectivity != 8) return fail(PWPP_E_ARG, "connectivity %d: 4 or 8 expected", connectivity);
     if (max_clusters < 0) return fail(PWPP_E_ARG, "max_clusters %d", max_clusters);
     if (max_clusters > 0 && !clusters) return fail(PWPP_E_ARG, "null cluster table with max_clusters %d", max_clusters);
@@ -2412,46 +2484,43 @@ int cluster_param_args(int mem, int min_count, int connectivity, const void *clu
     return PWPP_OK;
 }
 
-// ... and pwpp_label_grid of its images, before the device is touched
-int cluster_args(int nx, int ny, int frames, int mem, int min_count, int connectivity, const void *clusters, int max_clusters, size_t &cells) {
-    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
-    int rc = frame_cells_args(nx, ny);
-    if (rc) return rc;
-    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
-    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
-    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
-    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle clusters take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
-    cells = (size_t)per_frame * (size_t)frames;
-    return PWPP_OK;
-}
-
 constexpr size_t kClusterRowWords = sizeof(pwpp_obstacle_cluster) / 4;
 static_assert(sizeof(pwpp_obstacle_cluster) == 48, "pwpp_obstacle_cluster is 48 bytes");
+
+struct ClusterSections {
+    int work, count, top, label, table, n;
+};
+ClusterSections cluster_sections(Staging &st, int nx, int ny, int frames, size_t cells, bool from_raster, const int32_t *count, const float *top,
+                                 int32_t *label, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters) {
+    ClusterSections s;
+    s.work = st.add(pwpp_cluster_work_words(nx, ny, frames), nullptr, Staging::kKept);
+    s.count = add_image(st, cells, count, from_raster), s.top = add_image(st, cells, top, from_raster);
+    s.label = st.add(cells, label, Staging::kOut);
+    s.table = st.add((size_t)frames * (size_t)max_clusters * kClusterRowWords, clusters, Staging::kOut);
+    s.n = st.add((size_t)frames, n_clusters, Staging::kOut);
+    return s;
+}
+int cluster_launch(pwpp_handle *h, const Staging &st, const ClusterSections &s, int nx, int ny, int frames, int min_count, int connectivity, int max_clusters) {
+    return pwpp_launch_label_grid(nx, ny, frames, st.dev<const int32_t>(s.count), st.dev<const float>(s.top), min_count, connectivity, h->clusters_path,
+                                  st.dev<int32_t>(s.label), st.dev<void>(s.table), st.dev<int32_t>(s.n), max_clusters, st.dev<uint32_t>(s.work), h->stream);
+}
 }  // namespace
 
-// The cluster buffer of a call: the kernels' working words first, then the sections the call stages.
 int pwpp_label_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, const float *top, int min_count, int connectivity,
                     int32_t *label, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!label || !count) return fail(PWPP_E_ARG, "null %s image", count ? "label" : "count");
     size_t cells = 0;
-    int rc = cluster_args(nx, ny, frames, mem, min_count, connectivity, clusters, max_clusters, cells);
+    int rc = image_args(nx, ny, frames, nullptr, cells);
     if (rc) return rc;
-    if ((rc = enter(h, true))) return rc;  // (like a getter: the call in flight lands first; no results are needed)
+    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    if ((rc = mem_args(mem, "the obstacle clusters take"))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_work = st.add(pwpp_cluster_work_words(nx, ny, frames), nullptr, Staging::kKept);
-    const int s_count = st.add(cells, count, Staging::kIn), s_top = st.add(top ? cells : 0, top, Staging::kIn), s_label = st.add(cells, label, Staging::kOut);
-    const int s_table = st.add((size_t)frames * (size_t)max_clusters * kClusterRowWords, clusters, Staging::kOut);
-    const int s_n = st.add((size_t)frames, n_clusters, Staging::kOut);
-    if ((rc = st.begin())) return rc;
-    const int lrc = pwpp_launch_label_grid(nx, ny, frames, st.dev<const int32_t>(s_count), st.dev<const float>(s_top), min_count, connectivity,
-                                           h->clusters_path, st.dev<int32_t>(s_label), st.dev<void>(s_table), st.dev<int32_t>(s_n), max_clusters,
-                                           st.dev<uint32_t>(s_work), h->stream);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    const ClusterSections s = cluster_sections(st, nx, ny, frames, cells, false, count, top, label, clusters, n_clusters, max_clusters);
+    return run_on_image(h, st, [&] { return cluster_launch(h, st, s, nx, ny, frames, min_count, connectivity, max_clusters); });
 }
 
-// pwpp_rasterize_obstacles, pwpp_label_grid on its two images and the per-point scatter, enqueued as one sequence.  An image the
-// caller does not ask for stays in the cluster buffer.
+// (then the per-point scatter)
 int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int connectivity, int frame_first, int frames,
                          int mem, int32_t *label, int32_t *count, float *top, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters,
                          int32_t *point_cluster) {
@@ -2466,117 +2535,84 @@ int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
     const int64_t base_first = h->h_base.p[frame_first];
     const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_work = st.add(pwpp_cluster_work_words(g->nx, g->ny, frames), nullptr, Staging::kKept);
-    const int s_count = st.add(cells, count, count ? Staging::kOut : Staging::kKept), s_top = st.add(cells, top, top ? Staging::kOut : Staging::kKept);
-    const int s_label = st.add(cells, label, Staging::kOut);
-    const int s_table = st.add((size_t)frames * (size_t)max_clusters * kClusterRowWords, clusters, Staging::kOut);
-    const int s_n = st.add((size_t)frames, n_clusters, Staging::kOut), s_pc = st.add(points, point_cluster, Staging::kOut);
-    if ((rc = st.begin())) return rc;
-    PwppObstacleScan scan;
-    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
-    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), st.dev<float>(s_top), nullptr, h->stream);
-    if (lrc == 0)
-        lrc = pwpp_launch_label_grid(g->nx, g->ny, frames, st.dev<int32_t>(s_count), st.dev<float>(s_top), min_count, connectivity, h->clusters_path,
-                                     st.dev<int32_t>(s_label), st.dev<void>(s_table), st.dev<int32_t>(s_n), max_clusters, st.dev<uint32_t>(s_work),
-                                     h->stream);
-    if (lrc != 0) return launch_failed(h, lrc);
-    if (points > 0) {
-        HIPCHK(hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream));  // (-1: every point that is not a counted one)
-        lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s_label), st.dev<int32_t>(s_pc), base_first, h->stream);
-        if (lrc != 0) return launch_failed(h, lrc);
-    }
-    return st.end();
+    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, count, top, label, clusters, n_clusters, max_clusters);
+    const int s_pc = st.add(points, point_cluster, Staging::kOut);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
+        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, max_clusters);
+        if (lrc != 0 || points == 0) return lrc;
+        lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (-1: every point that is not a counted one)
+        return lrc != 0 ? lrc : pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
+    });
 }
 
 // ---- obstacle distances: every cell's distance to the nearest occupied cell, and that cell ----------------------------------------
 namespace {
 static_assert(PWPP_DIST_BEYOND == PWPP_DIST_NONE, "PWPP_DIST_BEYOND is the kernels' PWPP_DIST_NONE");
-// what both entry points check of an image's sides (the largest dist2, 2 * 32767^2, stays below PWPP_DIST_BEYOND) ...
-int distance_side_args(int nx, int ny) {
-    if (nx > PWPP_DIST_MAX_SIDE || ny > PWPP_DIST_MAX_SIDE) return fail(PWPP_E_ARG, "%d x %d cells: the obstacle distances take at most 32768 a side", nx, ny);
-    return PWPP_OK;
-}
-
-// ... of min_count and max_dist ...
+constexpr const char *kDistanceWho = "the obstacle distances take";
+// what both entry points check of min_count and max_dist
 int distance_param_args(int min_count, int max_dist) {
-    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (const int rc = min_count_args(min_count)) return rc;
     if (max_dist < 0 || max_dist > PWPP_DIST_MAX_CAP) return fail(PWPP_E_ARG, "max_dist %d: 0 (unlimited) .. 46340 cells expected", max_dist);
     return PWPP_OK;
 }
 
-// ... and pwpp_distance_grid of its images, before the device is touched
-int distance_args(int nx, int ny, int frames, int mem, int min_count, int max_dist, double cell, const float *metres, size_t &cells) {
-    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
-    int rc = distance_side_args(nx, ny);
-    if (rc) return rc;
-    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
-    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
-    if ((rc = distance_param_args(min_count, max_dist))) return rc;
-    if (metres && (!(cell > 0.0) || !std::isfinite(cell))) return fail(PWPP_E_ARG, "cell size %g: finite and positive expected with a metres image", cell);
-    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle distances take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
-    cells = (size_t)per_frame * (size_t)frames;
-    return PWPP_OK;
+struct DistanceSections {
+    int work, count, dist2, nearest, metres;
+};
+DistanceSections distance_sections(Staging &st, int nx, int ny, int frames, size_t cells, bool from_raster, const int32_t *count, int32_t *dist2,
+                                   int32_t *nearest, float *metres) {
+    DistanceSections s;
+    s.work = st.add(pwpp_distance_work_words(nx, ny, frames), nullptr, Staging::kKept);
+    s.count = add_image(st, cells, count, from_raster), s.dist2 = st.add(cells, dist2, Staging::kOut);
+    s.nearest = st.add(nearest ? cells : 0, nearest, Staging::kOut), s.metres = st.add(metres ? cells : 0, metres, Staging::kOut);
+    return s;
+}
+int distance_launch(pwpp_handle *h, const Staging &st, const DistanceSections &s, int nx, int ny, int frames, int min_count, int max_dist, double cell) {
+    return pwpp_launch_distance_grid(nx, ny, frames, st.dev<const int32_t>(s.count), min_count, max_dist, cell, h->distance_path, st.dev<int32_t>(s.dist2),
+                                     st.dev<int32_t>(s.nearest), st.dev<float>(s.metres), st.dev<uint32_t>(s.work), h->stream);
 }
 }  // namespace
 
-// The cluster buffer of a call: the kernels' working image first, then the sections the call stages.
 int pwpp_distance_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, int min_count, int max_dist, double cell, int32_t *dist2,
                        int32_t *nearest, float *metres) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!count || !dist2) return fail(PWPP_E_ARG, "null %s image", count ? "dist2" : "count");
     size_t cells = 0;
-    int rc = distance_args(nx, ny, frames, mem, min_count, max_dist, cell, metres, cells);
+    int rc = image_args(nx, ny, frames, kDistanceWho, cells);
     if (rc) return rc;
-    if ((rc = enter(h, true))) return rc;  // (like pwpp_label_grid: the call in flight lands first; no results are needed)
+    if ((rc = distance_param_args(min_count, max_dist))) return rc;
+    if (metres && (!(cell > 0.0) || !std::isfinite(cell))) return fail(PWPP_E_ARG, "cell size %g: finite and positive expected with a metres image", cell);
+    if ((rc = mem_args(mem, kDistanceWho))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_work = st.add(pwpp_distance_work_words(nx, ny, frames), nullptr, Staging::kKept);
-    const int s_count = st.add(cells, count, Staging::kIn), s_dist2 = st.add(cells, dist2, Staging::kOut);
-    const int s_near = st.add(nearest ? cells : 0, nearest, Staging::kOut), s_metres = st.add(metres ? cells : 0, metres, Staging::kOut);
-    if ((rc = st.begin())) return rc;
-    const int lrc = pwpp_launch_distance_grid(nx, ny, frames, st.dev<const int32_t>(s_count), min_count, max_dist, cell, h->distance_path,
-                                              st.dev<int32_t>(s_dist2), st.dev<int32_t>(s_near), st.dev<float>(s_metres), st.dev<uint32_t>(s_work), h->stream);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    const DistanceSections s = distance_sections(st, nx, ny, frames, cells, false, count, dist2, nearest, metres);
+    return run_on_image(h, st, [&] { return distance_launch(h, st, s, nx, ny, frames, min_count, max_dist, cell); });
 }
 
-// pwpp_rasterize_obstacles (the count image alone) and pwpp_distance_grid on it, enqueued as one sequence.  A count image the
-// caller does not ask for stays in the cluster buffer.
 int pwpp_distance_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int max_dist, int frame_first, int frames,
                             int mem, int32_t *dist2, int32_t *nearest, float *metres, int32_t *count) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !dist2) return fail(PWPP_E_ARG, "null %s", g ? "dist2 image" : "grid");
     int rc = obstacle_band_args(g, h_min, h_max);
     if (rc) return rc;
-    if ((rc = distance_side_args(g->nx, g->ny))) return rc;
+    if ((rc = side_args(g->nx, g->ny, kDistanceWho))) return rc;
     if ((rc = distance_param_args(min_count, max_dist))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;  // (the cell size of metres is the grid's: finite and positive)
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_work = st.add(pwpp_distance_work_words(g->nx, g->ny, frames), nullptr, Staging::kKept);
-    const int s_count = st.add(cells, count, count ? Staging::kOut : Staging::kKept), s_dist2 = st.add(cells, dist2, Staging::kOut);
-    const int s_near = st.add(nearest ? cells : 0, nearest, Staging::kOut), s_metres = st.add(metres ? cells : 0, metres, Staging::kOut);
-    if ((rc = st.begin())) return rc;
-    PwppObstacleScan scan;
-    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
-    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), nullptr, nullptr, h->stream);
-    if (lrc == 0)
-        lrc = pwpp_launch_distance_grid(g->nx, g->ny, frames, st.dev<int32_t>(s_count), min_count, max_dist, g->cell, h->distance_path, st.dev<int32_t>(s_dist2),
-                                        st.dev<int32_t>(s_near), st.dev<float>(s_metres), st.dev<uint32_t>(s_work), h->stream);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    const DistanceSections s = distance_sections(st, g->nx, g->ny, frames, cells, true, count, dist2, nearest, metres);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, -1, [&](const PwppObstacleScan &) {
+        return distance_launch(h, st, s, g->nx, g->ny, frames, min_count, max_dist, g->cell);
+    });
 }
 
 // ---- line-of-sight free space: the first occupied cell between the sensor's cell and every cell, and the tri-state byte ----------
 namespace {
 static_assert(PWPP_VIS_NONE == PWPP_VIS_FIRST_NONE && PWPP_VIS_BEYOND == PWPP_VIS_FIRST_BEYOND, "the kernels' values of first");
 static_assert(PWPP_OCC_FREE == PWPP_VIS_FREE && PWPP_OCC_OCCUPIED == PWPP_VIS_OCCUPIED && PWPP_OCC_UNKNOWN == PWPP_VIS_UNKNOWN, "the kernels' occupancy bytes");
-// what both entry points check of an image's sides ...
-int visibility_side_args(int nx, int ny) {
-    if (nx > PWPP_VIS_MAX_SIDE || ny > PWPP_VIS_MAX_SIDE) return fail(PWPP_E_ARG, "%d x %d cells: the visibility takes at most 32768 a side", nx, ny);
-    return PWPP_OK;
-}
-
-// ... of min_count and max_range ...
+constexpr const char *kVisibilityWho = "the visibility takes";
+// what both entry points check of min_count and max_range ...
 int visibility_param_args(int min_count, int max_range) {
-    if (min_count < 1) return fail(PWPP_E_ARG, "min_count %d: at least 1 expected", min_count);
+    if (const int rc = min_count_args(min_count)) return rc;
     if (max_range < 0 || max_range > PWPP_VIS_MAX_SIDE) return fail(PWPP_E_ARG, "max_range %d: 0 (unlimited) .. 32768 cells expected", max_range);
     return PWPP_OK;
 }
@@ -2587,65 +2623,63 @@ int visibility_origin_count(int n_origins, int frames) {
     return PWPP_OK;
 }
 
-// The kernels over the sections of a call; `cells`: the origin cells, n_origins x {ox, oy}, checked.  One origin travels as an
-// argument; one per frame is copied into its section from the handle's own copy (the caller's array may go on return).  The
-// result is a HIP error code, like a launcher's.
-int visibility_launch(pwpp_handle *h, Staging &st, int nx, int ny, int frames, int min_count, const std::vector<int32_t> &cells, int max_range, int s_count,
-                      int s_first, int s_occ, int s_org, int s_work) {
+// (the kernels' bit image and the origins first; `org`: the origin cells, n_origins x {ox, oy}, checked)
+struct VisibilitySections {
+    int work, org, count, first, occ;
+};
+VisibilitySections visibility_sections(pwpp_handle *h, Staging &st, int nx, int ny, int frames, size_t cells, bool from_raster, const int32_t *count,
+                                       const std::vector<int32_t> &org, int32_t *first, int8_t *occupancy) {
+    VisibilitySections s;
+    s.work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
+    s.org = st.add(org.size() > 2 ? org.size() : 0, nullptr, Staging::kKept);
+    s.count = add_image(st, cells, count, from_raster), s.first = st.add(cells, first, Staging::kOut);
+    s.occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
+    return s;
+}
+// One origin travels as an argument; one per frame is copied into its section from the handle's own copy (the caller's array may
+// go on return).
+int visibility_launch(pwpp_handle *h, const Staging &st, const VisibilitySections &s, int nx, int ny, int frames, int min_count,
+                      const std::vector<int32_t> &org, int max_range) {
     const int32_t *d_org = nullptr;
-    if (cells.size() > 2) {
-        h->vis_origins = cells;
-        int32_t *dst = st.dev<int32_t>(s_org);
+    if (org.size() > 2) {
+        h->vis_origins = org;
+        int32_t *dst = st.dev<int32_t>(s.org);
         const hipError_t e = hipMemcpyAsync(dst, h->vis_origins.data(), h->vis_origins.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
         if (e != hipSuccess) return (int)e;
         d_org = dst;
     }
-    return pwpp_launch_visibility_grid(nx, ny, frames, st.dev<const int32_t>(s_count), min_count, cells[0], cells[1], d_org, max_range, h->visibility_path,
-                                       st.dev<int32_t>(s_first), st.dev<int8_t>(s_occ), st.dev<uint32_t>(s_work), h->stream);
+    return pwpp_launch_visibility_grid(nx, ny, frames, st.dev<const int32_t>(s.count), min_count, org[0], org[1], d_org, max_range, h->visibility_path,
+                                       st.dev<int32_t>(s.first), st.dev<int8_t>(s.occ), st.dev<uint32_t>(s.work), h->stream);
 }
 }  // namespace
 
-// The cluster buffer of a call: the kernels' bit image and the origins first, then the sections the call stages.
 int pwpp_visibility_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, int min_count, const int32_t *origin, int n_origins,
                          int max_range, int32_t *first, int8_t *occupancy) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!count || !first || !origin) return fail(PWPP_E_ARG, "null %s", !count ? "count image" : (!first ? "first image" : "origin"));
-    if (nx < 1 || ny < 1 || frames < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, nx, ny);
-    int rc = visibility_side_args(nx, ny);
+    size_t cells = 0;
+    int rc = image_args(nx, ny, frames, kVisibilityWho, cells);
     if (rc) return rc;
-    const int64_t per_frame = (int64_t)nx * (int64_t)ny;
-    if (per_frame > ((int64_t)1 << 31) / frames) return fail(PWPP_E_ARG, "%d x %d cells x %d frames exceed 2^31", nx, ny, frames);
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
     if ((rc = visibility_origin_count(n_origins, frames))) return rc;
     for (int i = 0; i < n_origins; ++i)
         if (origin[2 * i] < 0 || origin[2 * i] >= nx || origin[2 * i + 1] < 0 || origin[2 * i + 1] >= ny)
             return fail(PWPP_E_ARG, "origin %d, cell (%d, %d), lies outside the %d x %d cells", i, origin[2 * i], origin[2 * i + 1], nx, ny);
-    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the visibility takes PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
-    const size_t cells = (size_t)per_frame * (size_t)frames;
+    if ((rc = mem_args(mem, kVisibilityWho))) return rc;
     const std::vector<int32_t> org(origin, origin + 2 * (size_t)n_origins);
-    if ((rc = enter(h, true))) return rc;  // (like pwpp_distance_grid: the call in flight lands first; no results are needed)
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
-    const int s_org = st.add(n_origins > 1 ? org.size() : 0, nullptr, Staging::kKept);
-    const int s_count = st.add(cells, count, Staging::kIn), s_first = st.add(cells, first, Staging::kOut);
-    const int s_occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
-    if ((rc = st.begin())) return rc;
-    const int lrc = visibility_launch(h, st, nx, ny, frames, min_count, org, max_range, s_count, s_first, s_occ, s_org, s_work);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    const VisibilitySections s = visibility_sections(h, st, nx, ny, frames, cells, false, count, org, first, occupancy);
+    return run_on_image(h, st, [&] { return visibility_launch(h, st, s, nx, ny, frames, min_count, org, max_range); });
 }
 
-// pwpp_rasterize_obstacles (the count image alone) and pwpp_visibility_grid on it, enqueued as one sequence.  A count image the
-// caller does not ask for stays in the cluster buffer.
 int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
                               int max_range, int frame_first, int frames, int mem, int32_t *first, int8_t *occupancy, int32_t *count) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !first || !origin_xy) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!first ? "first image" : "origin"));
     int rc = obstacle_band_args(g, h_min, h_max);
     if (rc) return rc;
-    if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);  // (ground_grid_args' own two checks: the origins need the grid)
-    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
-        return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
-    if ((rc = visibility_side_args(g->nx, g->ny))) return rc;
+    if ((rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
+    if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
     if ((rc = visibility_origin_count(n_origins, frames))) return rc;
     std::vector<int32_t> org(2 * (size_t)n_origins);
@@ -2660,16 +2694,10 @@ int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_work = st.add(pwpp_visibility_work_words(g->nx, g->ny, frames, h->visibility_path), nullptr, Staging::kKept);
-    const int s_org = st.add(n_origins > 1 ? org.size() : 0, nullptr, Staging::kKept);
-    const int s_count = st.add(cells, count, count ? Staging::kOut : Staging::kKept), s_first = st.add(cells, first, Staging::kOut);
-    const int s_occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
-    if ((rc = st.begin())) return rc;
-    PwppObstacleScan scan;
-    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
-    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), nullptr, nullptr, h->stream);
-    if (lrc == 0) lrc = visibility_launch(h, st, g->nx, g->ny, frames, min_count, org, max_range, s_count, s_first, s_occ, s_org, s_work);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    const VisibilitySections s = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, count, org, first, occupancy);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, -1, [&](const PwppObstacleScan &) {
+        return visibility_launch(h, st, s, g->nx, g->ny, frames, min_count, org, max_range);
+    });
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------
@@ -2699,7 +2727,7 @@ int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, f
     if (frames > 0 && (int64_t)frames * (int64_t)max_boxes > ((int64_t)1 << 24))
         return fail(PWPP_E_ARG, "%d frames x %d boxes exceed 2^24 rows", frames, max_boxes);
     if ((rc = box_extent_args(g))) return rc;
-    if (mem != PWPP_MEM_HOST && mem != PWPP_MEM_DEVICE) return fail(PWPP_E_ARG, "mem %d: the obstacle boxes take PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem);
+    if ((rc = mem_args(mem, "the obstacle boxes take"))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
@@ -2726,11 +2754,8 @@ int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz, const float *hg
     if (max_boxes < 1 || max_boxes > (1 << 24)) return fail(PWPP_E_ARG, "max_boxes %d: 1 .. 2^24 expected", max_boxes);
     if (m < 0 || m > ((int64_t)1 << 22)) return fail(PWPP_E_ARG, "%lld points (0..2^22 supported)", (long long)m);
     if (m > 0 && (!xyz || !hgt || !row)) return fail(PWPP_E_ARG, "null %s", !xyz ? "positions" : (!hgt ? "heights" : "rows"));
-    if (g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "grid of %d x %d cells", g->nx, g->ny);
-    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !std::isfinite(g->x0) || !std::isfinite(g->y0))
-        return fail(PWPP_E_ARG, "grid origin and cell size must be finite, the cell size positive");
-    const int rc = box_extent_args(g);
-    if (rc) return rc;
+    int rc = grid_geometry_args(g);
+    if (rc || (rc = box_extent_args(g))) return rc;
     struct Acc {
         long long s[PWPP_BOX_SUMS];
         uint32_t k[PWPP_BOX_KEYS];

@@ -235,6 +235,28 @@ def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _hp(a):
+    """A host array, or None, as the library's pointer.  An empty array goes as a one-element dummy: the library is the one that
+    names the bad argument."""
+    if a is None:
+        return None
+    return _vp(a) if a.size else _vp(np.empty(1, a.dtype))
+
+
+def _dp(address):
+    """A device address as the library's pointer; 0: none."""
+    return ctypes.c_void_p(address or None)
+
+
+def _count_image(count):
+    """(the (frames, ny, nx) int32 view, the shape as given) of a (frames, ny, nx) or (ny, nx) count image."""
+    count = np.ascontiguousarray(count, np.int32)
+    c3 = count.reshape((1,) + count.shape) if count.ndim == 2 else count
+    if c3.ndim != 3:
+        raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+    return c3, count.shape
+
+
 def _transforms(T):
     """(k, 12) float32 from (12,), (3, 4), (k, 12) or (k, 3, 4)."""
     T = np.asarray(T, dtype=np.float32)
@@ -716,25 +738,27 @@ class Handle:
     def query_ground_device(self, xyz_ptr, frames_ptr, m, out_ptr):
         """query_ground on device memory: addresses of (m, 3) float32 positions, m int32 frames (0 / None: frame 0) and m
         16-byte samples.  Enqueued on the handle's stream; complete after synchronize()."""
-        self._check(self._L.pwpp_query_ground(self._h, ctypes.c_void_p(xyz_ptr), ctypes.c_void_p(frames_ptr or None), int(m), MEM_DEVICE,
-                                              ctypes.c_void_p(out_ptr)))
+        self._check(self._L.pwpp_query_ground(self._h, _dp(xyz_ptr), _dp(frames_ptr), int(m), MEM_DEVICE, _dp(out_ptr)))
 
     def _grid(self, x0, y0, cell, nx, ny, frame_first, frames, ground_only):
         if frames is None:
             frames = self.device_view().frames - frame_first
         return GroundGrid(float(x0), float(y0), float(cell), int(nx), int(ny), GRID_GROUND_ONLY if ground_only else 0, 0), int(frames)
 
+    @staticmethod
+    def _grid_shape(g, frames):
+        """The shape of the images of a call over frames of the grid g; a bad argument, left to the library to name, counts as 0."""
+        return (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+
     def rasterize_ground(self, x0, y0, cell, nx, ny, frame_first=0, frames=None, ground_only=False, with_patches=False):
         """The last call's ground model as an elevation image: (frames, ny, nx) float32 heights of the cell centres
         (x0 + (ix + 0.5) cell, y0 + (iy + 0.5) cell), NaN where no patch answers; with_patches: also the int32 patch rows.
         ground_only: NaN too where the patch was decided not_upright, heading or tgr_reject."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        shape = self._grid_shape(g, frames)
         height = np.empty(shape, np.float32)
         patch = np.empty(shape, np.int32) if with_patches else None
-        # (an empty image still goes to the library: it is the one that names the bad argument)
-        hp = _vp(height) if height.size else _vp(np.empty(1, np.float32))
-        self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, hp,
+        self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, _hp(height),
                                                   _vp(patch) if with_patches and patch.size else None))
         return (height, patch) if with_patches else height
 
@@ -742,8 +766,7 @@ class Handle:
         """rasterize_ground into device memory: addresses of the (frames, ny, nx) float32 image and (0: none) the int32 one.
         Enqueued on the handle's stream; complete after synchronize()."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE,
-                                                  ctypes.c_void_p(height_ptr), ctypes.c_void_p(patch_ptr or None)))
+        self._check(self._L.pwpp_rasterize_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, _dp(height_ptr), _dp(patch_ptr)))
 
     def rasterize_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, frame_first=0, frames=None, ground_only=False, want_top=True,
                             want_unref=False):
@@ -753,14 +776,12 @@ class Handle:
         ground_only: patches decided not_upright, heading or tgr_reject give no reference either).
         Returns count, or the tuple (count[, top][, unref])."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        shape = self._grid_shape(g, frames)
         count = np.empty(shape, np.int32)
         top = np.empty(shape, np.float32) if want_top else None
         unref = np.empty(shape, np.int32) if want_unref else None
-        # (an empty image still goes to the library: it is the one that names the bad argument)
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
         self._check(self._L.pwpp_rasterize_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_HOST,
-                                                     ptr(count), ptr(top), ptr(unref)))
+                                                     _hp(count), _hp(top), _hp(unref)))
         out = tuple(a for a in (count, top, unref) if a is not None)
         return out if len(out) > 1 else count
 
@@ -770,7 +791,7 @@ class Handle:
         top and int32 unref images.  Enqueued on the handle's stream; complete after synchronize()."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_rasterize_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
-                                                     ctypes.c_void_p(count_ptr), ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(unref_ptr or None)))
+                                                     _dp(count_ptr), _dp(top_ptr), _dp(unref_ptr)))
 
     def label_grid(self, count, top=None, min_count=1, connectivity=8, max_clusters=0):
         """Connected clusters of the occupied cells (count >= min_count) of a (frames, ny, nx) or (ny, nx) int32 count image, each
@@ -778,11 +799,7 @@ class Handle:
         estimate call.  Returns (label, clusters, n_clusters): int32 labels of count's shape (-1: unoccupied, else the cluster's
         rank in ascending first_cell), the (frames, max_clusters) structured table (OBSTACLE_CLUSTER_DTYPE; rows beyond
         min(n, max_clusters) unspecified) and the (frames,) int32 true numbers of clusters (include/pwpp.h)."""
-        count = np.ascontiguousarray(count, np.int32)
-        shape = count.shape
-        c3 = count.reshape((1,) + shape) if count.ndim == 2 else count
-        if c3.ndim != 3:
-            raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+        c3, shape = _count_image(count)
         if top is not None:
             top = np.ascontiguousarray(top, np.float32)
             if top.shape != shape:
@@ -791,9 +808,7 @@ class Handle:
         label = np.empty(c3.shape, np.int32)
         table = np.zeros((max(frames, 0), max(int(max_clusters), 0)), OBSTACLE_CLUSTER_DTYPE)
         n = np.zeros(max(frames, 1), np.int32)
-        # (an empty image still goes to the library: it is the one that names the bad argument)
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
-        self._check(self._L.pwpp_label_grid(self._h, nx, ny, frames, MEM_HOST, ptr(c3), ptr(top), int(min_count), int(connectivity), ptr(label),
+        self._check(self._L.pwpp_label_grid(self._h, nx, ny, frames, MEM_HOST, _hp(c3), _hp(top), int(min_count), int(connectivity), _hp(label),
                                             _vp(table) if table.size else None, _vp(n), int(max_clusters)))
         return label.reshape(shape), table, n[:frames]
 
@@ -802,9 +817,8 @@ class Handle:
         """label_grid on device memory: addresses of the (frames, ny, nx) int32 count, float32 top (0: none) and int32 label
         images, the (frames, max_clusters) table of 48-byte rows (8-byte aligned; 0: none) and the (frames,) int32 counts
         (0: none).  Enqueued on the handle's stream; complete after synchronize()."""
-        self._check(self._L.pwpp_label_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, ctypes.c_void_p(count_ptr), ctypes.c_void_p(top_ptr or None),
-                                            int(min_count), int(connectivity), ctypes.c_void_p(label_ptr), ctypes.c_void_p(clusters_ptr or None),
-                                            ctypes.c_void_p(n_clusters_ptr or None), int(max_clusters)))
+        self._check(self._L.pwpp_label_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(count_ptr), _dp(top_ptr), int(min_count),
+                                            int(connectivity), _dp(label_ptr), _dp(clusters_ptr), _dp(n_clusters_ptr), int(max_clusters)))
 
     def label_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, min_count=1, connectivity=8, max_clusters=0, frame_first=0, frames=None,
                         ground_only=False, want_images=False, want_point_cluster=False):
@@ -813,7 +827,7 @@ class Handle:
         of rasterize_obstacles; want_point_cluster: then one int32 per point of the frame range in cloud order (frame f at
         frame_base()[f] - frame_base()[frame_first]): the label of the point's cell if the obstacle grid counted the point, else -1."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        shape = self._grid_shape(g, frames)
         label = np.empty(shape, np.int32)
         count = np.empty(shape, np.int32) if want_images else None
         top = np.empty(shape, np.float32) if want_images else None
@@ -825,10 +839,9 @@ class Handle:
             last = min(max(int(frame_first) + frames, 0), len(base) - 1)
             first = min(max(int(frame_first), 0), last)
             pc = np.empty(int(base[last] - base[first]), np.int32)
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
         self._check(self._L.pwpp_label_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity),
-                                                 int(frame_first), frames, MEM_HOST, ptr(label), ptr(count), ptr(top),
-                                                 _vp(table) if table.size else None, _vp(n), int(max_clusters), ptr(pc)))
+                                                 int(frame_first), frames, MEM_HOST, _hp(label), _hp(count), _hp(top),
+                                                 _vp(table) if table.size else None, _vp(n), int(max_clusters), _hp(pc)))
         out = (label, table, n[:max(frames, 0)])
         if want_images:
             out += (count, top)
@@ -842,9 +855,8 @@ class Handle:
         point_cluster_ptr: one int32 per point of the frame range.  Enqueued on the handle's stream; complete after synchronize()."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_label_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity),
-                                                 int(frame_first), frames, MEM_DEVICE, ctypes.c_void_p(label_ptr), ctypes.c_void_p(count_ptr or None),
-                                                 ctypes.c_void_p(top_ptr or None), ctypes.c_void_p(clusters_ptr or None),
-                                                 ctypes.c_void_p(n_clusters_ptr or None), int(max_clusters), ctypes.c_void_p(point_cluster_ptr or None)))
+                                                 int(frame_first), frames, MEM_DEVICE, _dp(label_ptr), _dp(count_ptr), _dp(top_ptr),
+                                                 _dp(clusters_ptr), _dp(n_clusters_ptr), int(max_clusters), _dp(point_cluster_ptr)))
 
     def distance_grid(self, count, min_count=1, max_dist=0, cell=1.0, want_nearest=True, want_metres=True):
         """The exact Euclidean distance of every cell of a (frames, ny, nx) or (ny, nx) int32 count image to the nearest occupied
@@ -852,26 +864,20 @@ class Handle:
         shape: the int32 squared distance in cells (DIST_BEYOND: none in reach), the int32 index iy * nx + ix of the nearest
         occupied cell (the smallest among several; -1: none) and float32 sqrt(dist2) * cell (+inf: none); None for an image that
         is not wanted.  max_dist > 0: cells further than max_dist cells from every occupied cell report none (include/pwpp.h)."""
-        count = np.ascontiguousarray(count, np.int32)
-        shape = count.shape
-        c3 = count.reshape((1,) + shape) if count.ndim == 2 else count
-        if c3.ndim != 3:
-            raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+        c3, shape = _count_image(count)
         frames, ny, nx = c3.shape
         dist2 = np.empty(c3.shape, np.int32)
         nearest = np.empty(c3.shape, np.int32) if want_nearest else None
         metres = np.empty(c3.shape, np.float32) if want_metres else None
-        # (an empty image still goes to the library: it is the one that names the bad argument)
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
-        self._check(self._L.pwpp_distance_grid(self._h, nx, ny, frames, MEM_HOST, ptr(c3), int(min_count), int(max_dist), float(cell), ptr(dist2),
-                                               ptr(nearest), ptr(metres)))
+        self._check(self._L.pwpp_distance_grid(self._h, nx, ny, frames, MEM_HOST, _hp(c3), int(min_count), int(max_dist), float(cell), _hp(dist2),
+                                               _hp(nearest), _hp(metres)))
         return tuple(None if a is None else a.reshape(shape) for a in (dist2, nearest, metres))
 
     def distance_grid_device(self, nx, ny, frames, count_ptr, min_count, max_dist, cell, dist2_ptr, nearest_ptr=0, metres_ptr=0):
         """distance_grid on device memory: addresses of the (frames, ny, nx) int32 count and dist2 images and (0: not wanted) the
         int32 nearest and float32 metres images, 4-byte aligned.  Enqueued on the handle's stream; complete after synchronize()."""
-        self._check(self._L.pwpp_distance_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, ctypes.c_void_p(count_ptr), int(min_count), int(max_dist),
-                                               float(cell), ctypes.c_void_p(dist2_ptr), ctypes.c_void_p(nearest_ptr or None), ctypes.c_void_p(metres_ptr or None)))
+        self._check(self._L.pwpp_distance_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(count_ptr), int(min_count), int(max_dist),
+                                               float(cell), _dp(dist2_ptr), _dp(nearest_ptr), _dp(metres_ptr)))
 
     def distance_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, min_count=1, max_dist=0, frame_first=0, frames=None, ground_only=False,
                            want_nearest=True, want_metres=True, want_count=False):
@@ -879,14 +885,13 @@ class Handle:
         metres) as distance_grid does for the (frames, ny, nx) count image, metres with the grid's cell; want_count: then that
         int32 count image too."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        shape = self._grid_shape(g, frames)
         dist2 = np.empty(shape, np.int32)
         nearest = np.empty(shape, np.int32) if want_nearest else None
         metres = np.empty(shape, np.float32) if want_metres else None
         count = np.empty(shape, np.int32) if want_count else None
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
         self._check(self._L.pwpp_distance_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(max_dist), int(frame_first),
-                                                    frames, MEM_HOST, ptr(dist2), ptr(nearest), ptr(metres), ptr(count)))
+                                                    frames, MEM_HOST, _hp(dist2), _hp(nearest), _hp(metres), _hp(count)))
         return (dist2, nearest, metres) + ((count,) if want_count else ())
 
     def distance_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, min_count, max_dist, dist2_ptr, nearest_ptr=0, metres_ptr=0, count_ptr=0,
@@ -895,8 +900,7 @@ class Handle:
         wanted).  Enqueued on the handle's stream; complete after synchronize()."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_distance_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(max_dist), int(frame_first),
-                                                    frames, MEM_DEVICE, ctypes.c_void_p(dist2_ptr), ctypes.c_void_p(nearest_ptr or None),
-                                                    ctypes.c_void_p(metres_ptr or None), ctypes.c_void_p(count_ptr or None)))
+                                                    frames, MEM_DEVICE, _dp(dist2_ptr), _dp(nearest_ptr), _dp(metres_ptr), _dp(count_ptr)))
 
     def visibility_grid(self, count, origin, min_count=1, max_range=0, want_occupancy=True):
         """The line-of-sight free space of a (frames, ny, nx) or (ny, nx) int32 count image: for every cell the first occupied cell
@@ -904,19 +908,13 @@ class Handle:
         Works before any estimate call.  Returns (first, occupancy) of count's shape: the int32 index iy * nx + ix of that cell
         (VIS_NONE: the line is clear; VIS_BEYOND: the cell is further than max_range > 0 cells, Chebyshev) and the int8 byte
         OCC_OCCUPIED / OCC_FREE / OCC_UNKNOWN (None when not wanted).  The rules: include/pwpp.h."""
-        count = np.ascontiguousarray(count, np.int32)
-        shape = count.shape
-        c3 = count.reshape((1,) + shape) if count.ndim == 2 else count
-        if c3.ndim != 3:
-            raise ValueError("count: a (frames, ny, nx) or (ny, nx) image expected")
+        c3, shape = _count_image(count)
         frames, ny, nx = c3.shape
         org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 2))
         first = np.empty(c3.shape, np.int32)
         occupancy = np.empty(c3.shape, np.int8) if want_occupancy else None
-        # (an empty image still goes to the library: it is the one that names the bad argument)
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
-        self._check(self._L.pwpp_visibility_grid(self._h, nx, ny, frames, MEM_HOST, ptr(c3), int(min_count), ptr(org), len(org), int(max_range),
-                                                 ptr(first), ptr(occupancy)))
+        self._check(self._L.pwpp_visibility_grid(self._h, nx, ny, frames, MEM_HOST, _hp(c3), int(min_count), _hp(org), len(org), int(max_range),
+                                                 _hp(first), _hp(occupancy)))
         return first.reshape(shape), None if occupancy is None else occupancy.reshape(shape)
 
     def visibility_grid_device(self, nx, ny, frames, count_ptr, origin, min_count, max_range, first_ptr, occupancy_ptr=0):
@@ -924,9 +922,8 @@ class Handle:
         (0: not wanted) the int8 occupancy image; origin stays a host array, (ox, oy) or (frames, 2).  Enqueued on the handle's
         stream; complete after synchronize()."""
         org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 2))
-        self._check(self._L.pwpp_visibility_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, ctypes.c_void_p(count_ptr), int(min_count),
-                                                 _vp(org) if org.size else None, len(org), int(max_range), ctypes.c_void_p(first_ptr),
-                                                 ctypes.c_void_p(occupancy_ptr or None)))
+        self._check(self._L.pwpp_visibility_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(count_ptr), int(min_count),
+                                                 _vp(org) if org.size else None, len(org), int(max_range), _dp(first_ptr), _dp(occupancy_ptr)))
 
     def visibility_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, origin_xy=(0.0, 0.0), min_count=1, max_range=0, frame_first=0, frames=None,
                              ground_only=False, want_occupancy=True, want_count=False):
@@ -934,14 +931,13 @@ class Handle:
         position in metres in the model's frame, (x, y) for every frame or (frames, 2).  Returns (first, occupancy) as
         visibility_grid does for the (frames, ny, nx) count image; want_count: then that int32 count image too."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        shape = (max(frames, 0), max(g.ny, 0), max(g.nx, 0))
+        shape = self._grid_shape(g, frames)
         org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
         first = np.empty(shape, np.int32)
         occupancy = np.empty(shape, np.int8) if want_occupancy else None
         count = np.empty(shape, np.int32) if want_count else None
-        ptr = lambda a: None if a is None else (_vp(a) if a.size else _vp(np.empty(1, a.dtype)))
-        self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), ptr(org), len(org),
-                                                      int(max_range), int(frame_first), frames, MEM_HOST, ptr(first), ptr(occupancy), ptr(count)))
+        self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org),
+                                                      int(max_range), int(frame_first), frames, MEM_HOST, _hp(first), _hp(occupancy), _hp(count)))
         return (first, occupancy) + ((count,) if want_count else ())
 
     def visibility_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, origin_xy, min_count, max_range, first_ptr, occupancy_ptr=0, count_ptr=0,
@@ -952,7 +948,7 @@ class Handle:
         org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
         self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count),
                                                       _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
-                                                      ctypes.c_void_p(first_ptr), ctypes.c_void_p(occupancy_ptr or None), ctypes.c_void_p(count_ptr or None)))
+                                                      _dp(first_ptr), _dp(occupancy_ptr), _dp(count_ptr)))
 
     def box_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_boxes, frame_first=0, frames=None, ground_only=False):
         """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as oriented
@@ -973,7 +969,7 @@ class Handle:
         of 64-byte rows, both 4-byte aligned.  Enqueued on the handle's stream; complete after synchronize()."""
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_box_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
-                                               ctypes.c_void_p(label_ptr or None), ctypes.c_void_p(boxes_ptr or None), int(max_boxes)))
+                                               _dp(label_ptr), _dp(boxes_ptr), int(max_boxes)))
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

@@ -235,6 +235,71 @@ def test_distance_obstacles_after_streams_and_device_memory_calls():
     del tens
 
 
+def test_the_optional_images_of_the_obstacles_entry_points_change_nothing_else():
+    """pwpp_label_obstacles, pwpp_distance_obstacles and pwpp_visibility_obstacles, each on host and on device memory, with and
+    without the images of the raster (count; top for the labels): kept in the handle's buffer or handed to the caller, the
+    operator's own outputs are the same bytes, and a count image that is returned is pwpp_rasterize_obstacles'."""
+    import torch
+    x0, y0, cell, nx, ny = grid = GRIDS[1]  # 65 x 17: no multiple of 64 across, cuts the cloud
+    rows, origin = 64, (3.0, 0.0)
+    h = pwpp_hip.Handle()
+    h.estimate_ground_batch(three_frames(), mode=pwpp_hip.MODE_FRESH)
+    rc, rtop = h.rasterize_obstacles(*grid, *BAND)
+    assert (rc[0] > 0).sum() >= 3
+    cells = 3 * nx * ny
+    words = lambda n=cells: torch.full((n,), -7, dtype=torch.int32, device="cuda")
+
+    def fetch(*tensors):
+        h.synchronize()
+        return [t.cpu().numpy() for t in tensors]
+
+    def label_bytes(label, table, n):
+        n = np.asarray(n).reshape(-1)
+        assert n[0] >= 1
+        table = np.asarray(table).view(np.uint8).reshape(3, rows * 48)
+        return label.tobytes(), b"".join(table[f, :48 * min(n[f], rows)].tobytes() for f in range(3)), n.tobytes()  # (the rows below n)
+
+    def labels(on_device, images):
+        if not on_device:
+            out = h.label_obstacles(*grid, *BAND, 1, 8, rows, want_images=images)
+            return label_bytes(*out[:3]), (out[3], out[4]) if images else None
+        d_label, d_table, d_n, d_count, d_top = words(), words(3 * rows * 12), words(3), words(), words()
+        h.label_obstacles_device(*grid, *BAND, 1, 8, d_label.data_ptr(), d_count.data_ptr() if images else 0, d_top.data_ptr() if images else 0,
+                                 d_table.data_ptr(), d_n.data_ptr(), rows)
+        label, table, n, count, top = fetch(d_label, d_table, d_n, d_count, d_top)
+        return label_bytes(label, table, n), (count, top.view(np.float32)) if images else None
+
+    def distances(on_device, images):
+        if not on_device:
+            out = h.distance_obstacles(*grid, *BAND, 1, 0, want_count=images)
+            return tuple(a.tobytes() for a in out[:3]), (out[3],) if images else None
+        d_dist2, d_nearest, d_metres, d_count = words(), words(), words(), words()
+        h.distance_obstacles_device(*grid, *BAND, 1, 0, d_dist2.data_ptr(), d_nearest.data_ptr(), d_metres.data_ptr(), d_count.data_ptr() if images else 0)
+        dist2, nearest, metres, count = fetch(d_dist2, d_nearest, d_metres, d_count)
+        return (dist2.tobytes(), nearest.tobytes(), metres.tobytes()), (count,) if images else None
+
+    def visibility(on_device, images):
+        if not on_device:
+            out = h.visibility_obstacles(*grid, *BAND, origin, 1, 0, want_count=images)
+            return (out[0].tobytes(), out[1].tobytes()), (out[2],) if images else None
+        d_first, d_occ, d_count = words(), torch.full((cells,), -7, dtype=torch.int8, device="cuda"), words()
+        h.visibility_obstacles_device(*grid, *BAND, origin, 1, 0, d_first.data_ptr(), d_occ.data_ptr(), d_count.data_ptr() if images else 0)
+        first, occ, count = fetch(d_first, d_occ, d_count)
+        return (first.tobytes(), occ.tobytes()), (count,) if images else None
+
+    for operator in (labels, distances, visibility):
+        want = None
+        for on_device in (False, True):
+            for images in (True, False):
+                what = "%s, %s memory, %s the images" % (operator.__name__, "device" if on_device else "host", "with" if images else "without")
+                got, raster = operator(on_device, images)
+                want = got if want is None else want
+                assert got == want, what
+                if images:
+                    assert raster[0].tobytes() == rc.tobytes(), what + ": the count image differs from pwpp_rasterize_obstacles"
+                    assert len(raster) == 1 or raster[1].tobytes() == rtop.tobytes(), what + ": the top image differs from pwpp_rasterize_obstacles"
+
+
 def test_state_workspace_and_arguments():
     L = pwpp_hip.load()
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None

@@ -1,6 +1,7 @@
-"""No-GPU checks of what the post-call map queries share (pwpp_rasterize_obstacles, pwpp_label_obstacles, pwpp_box_obstacles): the
-argument checks they have in common, fed to all three through one loop -- the same code and the same message fragment from each
--- and, with the restatements, that the batch of tests/test_gpu_map_query_ranges.py has clusters and boxes in the frames its
+"""No-GPU checks of what the post-call map queries share (pwpp_rasterize_obstacles, pwpp_label_obstacles, pwpp_box_obstacles,
+pwpp_distance_obstacles, pwpp_visibility_obstacles; and pwpp_label_grid, pwpp_distance_grid, pwpp_visibility_grid on a caller's
+image): the argument checks they have in common, fed to all of a kind through one loop -- the same code and the same message
+fragment from each -- and, with the restatements, that the batch of tests/test_gpu_map_query_ranges.py has clusters and boxes in the frames its
 comparison is about."""
 import ctypes
 import os
@@ -30,7 +31,7 @@ def lib():
     return pwpp_hip.load()
 
 
-# (grid fields x0, y0, cell, nx, ny, flags), band, mem, a fragment of the message.  A NaN cell is the one input the three do not
+# (grid fields x0, y0, cell, nx, ny, flags), band, mem, a fragment of the message.  A NaN cell is the one input they do not
 # name alike: pwpp_box_obstacles' extent check comes first ("... cells of nan m: ... at most 1024 m"), the others say "cell size".
 SHARED_BAD_INPUTS = [
     ("grid flags 2", dict(flags=2), (0.2, 2.5), pwpp_hip.MEM_HOST, b"grid flags 2: 0 or PWPP_GRID_GROUND_ONLY"),
@@ -43,15 +44,18 @@ SHARED_BAD_INPUTS = [
 ]
 
 
-def test_shared_bad_inputs_are_named_alike_by_all_three_entry_points(lib):
+def test_shared_bad_inputs_are_named_alike_by_all_five_entry_points(lib):
     img = np.zeros(16, np.int32)
     box = np.zeros(4, ob.BOX_DTYPE)
+    xy = np.array([0.5, 0.5], np.float64)  # (the sensor of pwpp_visibility_obstacles: inside every grid of the table that has cells)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # (never dereferenced: these checks come first)
     entry_points = {
         "pwpp_rasterize_obstacles": lambda g, band, mem: lib.pwpp_rasterize_obstacles(fake, g, band[0], band[1], 0, 1, mem, vp(img), None, None),
         "pwpp_label_obstacles": lambda g, band, mem: lib.pwpp_label_obstacles(fake, g, band[0], band[1], 1, 8, 0, 1, mem, vp(img), None, None, None, None, 0, None),
         "pwpp_box_obstacles": lambda g, band, mem: lib.pwpp_box_obstacles(fake, g, band[0], band[1], 0, 1, mem, vp(img), vp(box), 4),
+        "pwpp_distance_obstacles": lambda g, band, mem: lib.pwpp_distance_obstacles(fake, g, band[0], band[1], 1, 0, 0, 1, mem, vp(img), None, None, None),
+        "pwpp_visibility_obstacles": lambda g, band, mem: lib.pwpp_visibility_obstacles(fake, g, band[0], band[1], 1, vp(xy), 1, 0, 0, 1, mem, vp(img), None, None),
     }
     for what, fields, band, mem, fragment in SHARED_BAD_INPUTS:
         g = pwpp_hip.GroundGrid(**dict(dict(x0=0.0, y0=0.0, cell=1.0, nx=4, ny=4, flags=0, pad_=0), **fields))
@@ -60,6 +64,44 @@ def test_shared_bad_inputs_are_named_alike_by_all_three_entry_points(lib):
             assert fragment in lib.pwpp_last_error(), "%s, %s: %s" % (name, what, lib.pwpp_last_error())
             if what.startswith("mem"):
                 assert b"take PWPP_MEM_HOST or PWPP_MEM_DEVICE" in lib.pwpp_last_error(), name
+
+
+# What the three operators on a caller's count image (pwpp_label_grid, pwpp_distance_grid, pwpp_visibility_grid) check alike:
+# (nx, ny, frames, min_count, mem), a fragment of the message.
+SHARED_BAD_IMAGES = [
+    ("nx 0", dict(nx=0), b"frames of"),
+    ("frames 0", dict(frames=0), b"frames of"),
+    ("32768 x 32768 x 3 cells", dict(nx=32768, ny=32768, frames=3), b"exceed 2^31"),
+    ("min_count 0", dict(min_count=0), b"min_count 0: at least 1 expected"),
+    ("mem PWPP_MEM_HOST_PINNED", dict(mem=pwpp_hip.MEM_HOST_PINNED), b"take PWPP_MEM_HOST or PWPP_MEM_DEVICE"),
+]
+# The one message of the table that is not worded alike: "the visibility" is a singular, so its verb is "takes" -- and the fragment
+# above is not in it.  The sentence is pinned whole instead, for all three.
+MEM_SENTENCES = {
+    "pwpp_label_grid": b"mem 2: the obstacle clusters take PWPP_MEM_HOST or PWPP_MEM_DEVICE",
+    "pwpp_distance_grid": b"mem 2: the obstacle distances take PWPP_MEM_HOST or PWPP_MEM_DEVICE",
+    "pwpp_visibility_grid": b"mem 2: the visibility takes PWPP_MEM_HOST or PWPP_MEM_DEVICE",
+}
+
+
+def test_shared_bad_images_are_named_alike_by_the_three_grid_entry_points(lib):
+    img = np.zeros(16, np.int32)
+    org = np.zeros(2, np.int32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # (never dereferenced: these checks come first)
+    entry_points = {
+        "pwpp_label_grid": lambda nx, ny, frames, min_count, mem: lib.pwpp_label_grid(fake, nx, ny, frames, mem, vp(img), None, min_count, 8, vp(img), None, None, 0),
+        "pwpp_distance_grid": lambda nx, ny, frames, min_count, mem: lib.pwpp_distance_grid(fake, nx, ny, frames, mem, vp(img), min_count, 0, 1.0, vp(img), None, None),
+        "pwpp_visibility_grid": lambda nx, ny, frames, min_count, mem: lib.pwpp_visibility_grid(fake, nx, ny, frames, mem, vp(img), min_count, vp(org), 1, 0, vp(img), None),
+    }
+    for what, fields, fragment in SHARED_BAD_IMAGES:
+        args = dict(dict(nx=4, ny=4, frames=1, min_count=1, mem=pwpp_hip.MEM_HOST), **fields)
+        for name, call in entry_points.items():
+            assert call(**args) == E_ARG, "%s: %s" % (name, what)
+            if what.startswith("mem"):
+                assert lib.pwpp_last_error() == MEM_SENTENCES[name], "%s, %s: %s" % (name, what, lib.pwpp_last_error())
+            if not (what.startswith("mem") and name == "pwpp_visibility_grid"):
+                assert fragment in lib.pwpp_last_error(), "%s, %s: %s" % (name, what, lib.pwpp_last_error())
 
 
 def test_the_batch_has_clusters_and_boxes_in_the_sub_range(oracle_built):
