@@ -701,6 +701,99 @@ PWPP_API int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g
                                        int max_range, int frame_first, int frames, int mem,
                                        int32_t *first, int8_t *occupancy /* may be NULL */, int32_t *count /* may be NULL: kept */);
 
+/* ---- persistent log-odds maps: per-frame occupancy fused over time (pwpp_fuse_grid, pwpp_fuse_obstacles) -------------------------
+ * One scan sees little: the occupancy byte of the visibility says "unknown" for most cells of a frame.  A map a planner can drive
+ * on accumulates the scans in a FIXED frame, given the vehicle's pose: the log-odds update of every occupancy-grid mapper -- here
+ * on the device, with integer state and a fixed arithmetic, so that the fused map is a function of its inputs alone and bit-
+ * reproducible.  The maps are the caller's arrays, like every other image; a handle holds nothing of them between calls.
+ * All n_maps maps share the geometry and parameters of *m.  Below (X0, Y0, CELL, NX, NY) are m's fields, (x0, y0, cell, nx, ny) g's.
+ *   pose      Map-from-frame, six doubles {a, b, tx, c, d, ty}: a frame position (x, y) lies at (a x + b y + tx, c x + d y + ty)
+ *             in the map's frame.  A matrix, not an angle: no sin or cos enters the contract.  HOST memory in both mem kinds,
+ *             copied at the call (like the origins of the visibility).  n_poses == 1: that pose for every frame; n_poses ==
+ *             frames: entry i for frame i; any other number: PWPP_E_ARG.  Nothing checks orthonormality: the inverse used is the
+ *             TRANSPOSE (below), exact for a rotation; for anything else -- a mirror, a scale -- the formula is the definition.  A
+ *             pose that is not finite is no error: its samples are outside, the frame observes nothing.
+ *   samples   The operator is a gather: a map cell asks the frames, a frame cell never writes.  The map cell (jx, jy) is sampled at
+ *             the centres of its four quadrants, q = (qx, qy) in {0, 1}^2, all in double, every product, sum and quotient rounded
+ *             on its own (no FMA):
+ *                 mx = X0 + ((double)jx + (0.25 + 0.5 * qx)) * CELL          my alike with jy, qy, Y0
+ *                 dx = mx - tx;  dy = my - ty
+ *                 fx = a * dx + c * dy;   fy = b * dx + d * dy
+ *                 u = (fx - x0) / cell;  ix = (int)floor(u), inside iff 0 <= u && u < nx      v, iy alike with fy, y0, ny
+ *             (the cell rule of pwpp_rasterize_obstacles).  A sample outside the frame image, or whose u or v is a NaN, reads
+ *             PWPP_OCC_UNKNOWN; every other sample reads occupancy[f][iy][ix].
+ *             Why four samples and not the centre: with equal cell sizes and a yaw of 45 degrees, 17.7 % of the frame's cells lie
+ *             under no map cell's centre (13 % at 30 degrees) -- a thin obstacle would vanish from a frame.  The quadrant centres
+ *             form a lattice of spacing CELL / 2 with covering radius 0.354 CELL, less than the inscribed radius 0.5 cell of a
+ *             frame cell whenever CELL <= cell.  THE GUARANTEE: under a rigid pose with CELL <= cell, every occupied frame cell
+ *             whose circumscribed disc lies inside the map marks at least one map cell.  The price is a dilation of at most half
+ *             a map cell.  A translation by whole cells or a quarter turn with equal cell sizes puts all four samples into one
+ *             frame cell: lossless.
+ *   observation  of a map cell in a frame: OCCUPIED if any of the four samples reads exactly PWPP_OCC_OCCUPIED; otherwise FREE if
+ *             all four read exactly PWPP_OCC_FREE; otherwise none.  Any other byte (a caller may have edited the image) counts as
+ *             unknown.
+ *   update    L is an int16_t per map cell, computed in int32.  OCCUPIED: L = min(L + hit, l_max).  FREE: L = max(L - miss,
+ *             l_min).  None: unchanged.  The formulas apply as they stand to an input outside [l_min, l_max].
+ *   order     map_of_frame[i] in [-1, n_maps) names frame i's map; -1: the frame is skipped; anything else: PWPP_E_ARG, naming
+ *             the entry.  NULL with n_maps == 1: every frame updates map 0 -- a batch is a sequence.  NULL with n_maps == frames:
+ *             frame i updates map i -- the lock-step streams.  NULL otherwise: PWPP_E_ARG.  A map's frames act in ASCENDING frame
+ *             index; clamping makes the order matter: from L = 340 with hit 40, miss 20, l_max 350, a hit followed by a miss
+ *             gives 330, a miss followed by a hit 350.
+ *   shift     map_out[k][jy][jx] starts from map_in[k][jy + sy_k][jx + sx_k], or from 0 where that lies outside the map or map_in
+ *             is NULL; the call's frames act on that start.  m describes the OUT map: a caller whose vehicle moved two cells east
+ *             passes x0 + 2 * cell and sx = 2.  |sx| and |sy| may exceed the map.  A map no frame names comes out as its shifted
+ *             input.  map_out == map_in is allowed iff every shift is {0, 0} (each cell is then read and written by one lane); any
+ *             other overlap of the byte ranges of map_in, map_out and map_occupancy: PWPP_E_ARG.
+ *   byte      map_occupancy = PWPP_OCC_OCCUPIED where L >= occupied_at; otherwise PWPP_OCC_FREE where L <= free_at; otherwise
+ *             PWPP_OCC_UNKNOWN.
+ *   composition  Two calls, the second reading the first's map_out with no shift, give exactly one call over the concatenated
+ *             frames.  The same bytes for every call, mem, alignment and value of the option "fusion_path".
+ *   fuse_obstacles   the per-frame bytes are exactly the occupancy image pwpp_visibility_obstacles(g, h_min, h_max, min_count,
+ *             origin_xy, n_origins, max_range, frame_first, frames) gives, written for the caller where asked for and kept in the
+ *             handle's cluster buffer otherwise (with its count and first images); the maps are exactly what pwpp_fuse_grid gives
+ *             for them.  Entry i of pose and map_of_frame belongs to frame frame_first + i.  When, the grid's flags, the lifetime
+ *             rule of the INPUT and the errors are those of pwpp_visibility_obstacles.
+ *   mem       PWPP_MEM_HOST: every image and map is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- maps 2-byte aligned, bytes byte aligned, no more -- enqueued on the handle's
+ *             stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.  pose, map_of_frame and shift are HOST
+ *             memory always.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, grid, occupancy (pwpp_fuse_grid),
+ *             pose, map description or map_out; frames or a side of the frame image < 1, a side > 32768, nx * ny * frames beyond
+ *             2^31; g->flags != 0 (pwpp_fuse_grid); the same three of n_maps and the map; a cell or CELL that is not finite and
+ *             positive; hit, miss, the clamps and the thresholds outside the ranges at the struct; the number of poses;
+ *             map_of_frame; the overlaps; mem.  pwpp_fuse_obstacles rejects first everything pwpp_visibility_obstacles rejects of
+ *             its grid, band, min_count, max_range and origins, then the above of the map, and last the frame range and mem;
+ *             before any estimate call: PWPP_E_STATE.
+ *   buffers   No working image.  The poses, the frame lists (begin[n_maps + 1], frames[]) and the shifts are uploaded into the
+ *             cluster buffer: allocated on first use, counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *             pwpp_fuse_grid needs a handle for its stream and this buffer only.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of the estimate path changes. */
+#define PWPP_HAS_OCCUPANCY_FUSION 1
+typedef struct pwpp_fusion_map {     /* 56 bytes */
+    double  x0, y0, cell;            /* the MAP's grid, in the fixed frame: cell (jx, jy) covers x0 + [jx, jx+1) * cell, ... */
+    int32_t nx, ny;
+    int32_t hit, miss;               /* added for an OCCUPIED / subtracted for a FREE observation; 0 .. 32767 */
+    int32_t l_min, l_max;            /* clamps: -32768 <= l_min <= 0 <= l_max <= 32767 */
+    int32_t occupied_at, free_at;    /* thresholds of the derived byte; -32768 <= free_at < occupied_at <= 32767 */
+} pwpp_fusion_map;
+
+/* any occupancy images: needs a handle (stream, buffer), no estimate call -- like pwpp_visibility_grid */
+PWPP_API int pwpp_fuse_grid(pwpp_handle *h, const pwpp_ground_grid *g /* the FRAME images' grid; flags must be 0 */, int frames, int mem,
+                            const int8_t *occupancy /* [frames][g->ny][g->nx] */,
+                            const double *pose /* HOST, n_poses x 6 */, int n_poses,
+                            const int32_t *map_of_frame /* HOST, frames entries, or NULL */,
+                            const pwpp_fusion_map *m, int n_maps,
+                            const int32_t *shift /* HOST, n_maps x {sx, sy} cells, or NULL: none */,
+                            const int16_t *map_in /* [n_maps][m->ny][m->nx], or NULL: all zero */,
+                            int16_t *map_out /* same shape */, int8_t *map_occupancy /* same shape, may be NULL */);
+/* rasterize + visibility + fuse for frames of the LAST estimate call, one call -- like pwpp_visibility_obstacles */
+PWPP_API int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count,
+                                 const double *origin_xy, int n_origins, int max_range, int frame_first, int frames, int mem,
+                                 const double *pose, int n_poses, const int32_t *map_of_frame,
+                                 const pwpp_fusion_map *m, int n_maps, const int32_t *shift,
+                                 const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy /* may be NULL */,
+                                 int8_t *occupancy /* the per-frame bytes, may be NULL: kept in the handle's buffer */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -831,6 +924,11 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         (default) a bit image of the frame, one ballot per 64 cells, kept in LDS where it fits; "1": no bit
  *                         image, no LDS, every test reads count in global memory (the yardstick of
  *                         tools/obstacle_visibility_cost.py).  The results are identical bytes.
+ *   "fusion_path"         how the occupancy fusion forms a sample's cell (pwpp_fuse_grid, pwpp_fuse_obstacles): "0" (default)
+ *                         u = (fx - x0) * (1 / cell) where the frame images' cell size is a power of two -- the reciprocal is
+ *                         exact and the product the same bits as the quotient -- and the division otherwise; "1": always the
+ *                         double division as the contract writes it (the yardstick of tools/occupancy_fusion_cost.py).  The
+ *                         results are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

@@ -25,6 +25,7 @@
 #include "pwpp_boxes.h"
 #include "pwpp_dev.h"
 #include "pwpp_distance.h"
+#include "pwpp_fusion.h"
 #include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
@@ -248,6 +249,8 @@ struct pwpp_handle {
     int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
     int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
+    int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
+    std::vector<uint32_t> fuse_upload;  // the poses, frame lists and shifts of the last fusion call: the source of its upload
     std::vector<int32_t> vis_origins;  // the origin cells of the last visibility call with one origin per frame: the source of its upload
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
@@ -1213,7 +1216,7 @@ class Staging {
     }
 
   private:
-    static constexpr int kMaxSections = 8;
+    static constexpr int kMaxSections = 12;
     struct Section {
         size_t at, words, bytes;
         const void *user;
@@ -2104,6 +2107,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 1) return fail(PWPP_E_ARG, "visibility_path=%s: 0 or 1 expected", value);
         h->visibility_path = v;
+    } else if (k == "fusion_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "fusion_path=%s: 0 or 1 expected", value);
+        h->fusion_path = v;
     } else if (k == "boxes_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
@@ -2397,7 +2404,7 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
     return PWPP_OK;
 }
 
-// ---- operators on an occupancy image: clusters, distances, visibility ----------------------------------------------------------
+// ---- operators on an occupancy image: clusters, distances, visibility, fusion --------------------------------------------------
 // Each has two entry points: pwpp_*_grid works on the caller's count image, pwpp_*_obstacles on the one it first rasterises from
 // the last call's non-ground lists.  An operator states its sections once (*_sections: the kernels' working words first, then
 // what the call stages) and its launch once (*_launch: a HIP error code, like a launcher's); an entry point checks its arguments,
@@ -2623,17 +2630,40 @@ int visibility_origin_count(int n_origins, int frames) {
     return PWPP_OK;
 }
 
-// (the kernels' bit image and the origins first; `org`: the origin cells, n_origins x {ox, oy}, checked)
+// What the entry points that rasterise first check of the grid, min_count, max_range and the origins in metres, which they turn
+// into cells (`org`: n_origins x {ox, oy}).
+int visibility_origin_args(const pwpp_ground_grid *g, int min_count, const double *origin_xy, int n_origins, int max_range, int frames,
+                           std::vector<int32_t> &org) {
+    int rc = grid_geometry_args(g);  // (the origins need the grid)
+    if (rc) return rc;
+    if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
+    if ((rc = visibility_param_args(min_count, max_range))) return rc;
+    if ((rc = visibility_origin_count(n_origins, frames))) return rc;
+    org.assign(2 * (size_t)n_origins, 0);
+    for (int i = 0; i < n_origins; ++i) {
+        const double x = origin_xy[2 * i], y = origin_xy[2 * i + 1];
+        int ox = 0, oy = 0;
+        if (!std::isfinite(x) || !std::isfinite(y)) return fail(PWPP_E_ARG, "origin %d, (%g, %g), is not finite", i, x, y);
+        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
+            return fail(PWPP_E_ARG, "origin %d, (%g, %g) m, lies outside the grid", i, x, y);
+        org[2 * i] = ox, org[2 * i + 1] = oy;
+    }
+    return PWPP_OK;
+}
+
+// (the kernels' bit image and the origins first; `org`: the origin cells, n_origins x {ox, oy}, checked; `keep`: an image the
+// caller gives no pointer for still lies in the buffer -- the fusion reads it there)
 struct VisibilitySections {
     int work, org, count, first, occ;
 };
 VisibilitySections visibility_sections(pwpp_handle *h, Staging &st, int nx, int ny, int frames, size_t cells, bool from_raster, const int32_t *count,
-                                       const std::vector<int32_t> &org, int32_t *first, int8_t *occupancy) {
+                                       const std::vector<int32_t> &org, int32_t *first, int8_t *occupancy, bool keep = false) {
     VisibilitySections s;
     s.work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
     s.org = st.add(org.size() > 2 ? org.size() : 0, nullptr, Staging::kKept);
-    s.count = add_image(st, cells, count, from_raster), s.first = st.add(cells, first, Staging::kOut);
-    s.occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
+    s.count = add_image(st, cells, count, from_raster), s.first = st.add(cells, first, keep && !first ? Staging::kKept : Staging::kOut);
+    if (keep && !occupancy) s.occ = st.add((cells + 3) / 4, nullptr, Staging::kKept);
+    else s.occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
     return s;
 }
 // One origin travels as an argument; one per frame is copied into its section from the handle's own copy (the caller's array may
@@ -2678,25 +2708,162 @@ int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h
     if (!g || !first || !origin_xy) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!first ? "first image" : "origin"));
     int rc = obstacle_band_args(g, h_min, h_max);
     if (rc) return rc;
-    if ((rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
-    if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
-    if ((rc = visibility_param_args(min_count, max_range))) return rc;
-    if ((rc = visibility_origin_count(n_origins, frames))) return rc;
-    std::vector<int32_t> org(2 * (size_t)n_origins);
-    for (int i = 0; i < n_origins; ++i) {
-        const double x = origin_xy[2 * i], y = origin_xy[2 * i + 1];
-        int ox = 0, oy = 0;
-        if (!std::isfinite(x) || !std::isfinite(y)) return fail(PWPP_E_ARG, "origin %d, (%g, %g), is not finite", i, x, y);
-        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
-            return fail(PWPP_E_ARG, "origin %d, (%g, %g) m, lies outside the grid", i, x, y);
-        org[2 * i] = ox, org[2 * i + 1] = oy;
-    }
+    std::vector<int32_t> org;
+    if ((rc = visibility_origin_args(g, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const VisibilitySections s = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, count, org, first, occupancy);
     return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, -1, [&](const PwppObstacleScan &) {
         return visibility_launch(h, st, s, g->nx, g->ny, frames, min_count, org, max_range);
+    });
+}
+
+// ---- occupancy fusion: per-frame occupancy bytes, under a pose per frame, into persistent int16 log-odds maps --------------------
+namespace {
+static_assert(PWPP_OCC_FREE == PWPP_FUSE_FREE && PWPP_OCC_OCCUPIED == PWPP_FUSE_OCCUPIED && PWPP_OCC_UNKNOWN == PWPP_FUSE_UNKNOWN, "the kernel's occupancy bytes");
+static_assert(sizeof(pwpp_fusion_map) == 56, "pwpp_fusion_map is 56 bytes");
+constexpr const char *kFusionWho = "the fusion takes";
+
+// What a checked call hands to the kernel besides its images: the geometry, the parameters and the words to upload -- the poses
+// first (8-byte aligned at the section's start), then begin[n_maps + 1], the frame list and the shifts (none: no words).
+struct FusionPlan {
+    PwppFusionGeometry G;
+    PwppFusionParams P;
+    int n_poses = 0, n_maps = 0, listed = 0;
+    bool shifted = false;  // a shift array was given
+    size_t map_cells = 0;  // NX * NY * n_maps
+    std::vector<uint32_t> words;
+    size_t at_begin() const { return (size_t)n_poses * 12; }
+    size_t at_list() const { return at_begin() + (size_t)n_maps + 1; }
+    size_t at_shift() const { return at_list() + (size_t)listed; }
+};
+
+// What both entry points check of the map, the poses, the frame lists, the shifts and the overlaps, in the header's order, after
+// the frame images' own checks (frames >= 1); fills the plan.  Touches no handle.
+int fusion_args(const pwpp_ground_grid *g, int frames, const double *pose, int n_poses, const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps,
+                const int32_t *shift, const int16_t *map_in, const int16_t *map_out, const int8_t *map_occupancy, FusionPlan &plan) {
+    if (const int rc = image_args(m->nx, m->ny, n_maps, kFusionWho, plan.map_cells)) return rc;
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !(m->cell > 0.0) || !std::isfinite(m->cell))
+        return fail(PWPP_E_ARG, "cell sizes %g (frames) and %g (map): finite and positive expected", g->cell, m->cell);
+    if (m->hit < 0 || m->hit > 32767 || m->miss < 0 || m->miss > 32767) return fail(PWPP_E_ARG, "hit %d, miss %d: 0 .. 32767 expected", m->hit, m->miss);
+    if (m->l_min < -32768 || m->l_min > 0 || m->l_max < 0 || m->l_max > 32767)
+        return fail(PWPP_E_ARG, "clamps l_min %d, l_max %d: -32768 <= l_min <= 0 <= l_max <= 32767 expected", m->l_min, m->l_max);
+    if (m->free_at < -32768 || m->free_at >= m->occupied_at || m->occupied_at > 32767)
+        return fail(PWPP_E_ARG, "thresholds free_at %d, occupied_at %d: -32768 <= free_at < occupied_at <= 32767 expected", m->free_at, m->occupied_at);
+    if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
+    if (!map_of_frame && n_maps != 1 && n_maps != frames)
+        return fail(PWPP_E_ARG, "null map_of_frame with %d maps for %d frames: 1 map or one per frame expected", n_maps, frames);
+    for (int i = 0; map_of_frame && i < frames; ++i)
+        if (map_of_frame[i] < -1 || map_of_frame[i] >= n_maps)
+            return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
+    bool moved = false;
+    for (int k = 0; shift && k < n_maps; ++k) moved = moved || shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0;
+    const auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
+        const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+        return a && b && pa < pb + nb && pb < pa + na;
+    };
+    const size_t map_bytes = plan.map_cells * sizeof(int16_t);
+    if (map_in == map_out && moved) return fail(PWPP_E_ARG, "map_out == map_in with a shift that is not {0, 0}: a shifted update needs a second array");
+    if (map_in != map_out && overlap(map_in, map_bytes, map_out, map_bytes)) return fail(PWPP_E_ARG, "map_in and map_out overlap without being equal");
+    if (overlap(map_occupancy, plan.map_cells, map_out, map_bytes) || overlap(map_occupancy, plan.map_cells, map_in, map_bytes))
+        return fail(PWPP_E_ARG, "map_occupancy overlaps %s", overlap(map_occupancy, plan.map_cells, map_out, map_bytes) ? "map_out" : "map_in");
+
+    plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
+    pwpp_fuse_reciprocal(g->cell, plan.G.inv_cell);
+    plan.P = PwppFusionParams{m->hit, m->miss, m->l_min, m->l_max, m->occupied_at, m->free_at};
+    plan.n_poses = n_poses, plan.n_maps = n_maps, plan.shifted = shift != nullptr;
+    // the CSR: a counting sort of the frames by their map keeps each map's frames in ascending order
+    const auto map_of = [&](int i) { return map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i); };
+    try {
+    std::vector<int32_t> begin((size_t)n_maps + 1, 0);
+    for (int i = 0; i < frames; ++i)
+        if (map_of(i) >= 0) ++begin[(size_t)map_of(i) + 1], ++plan.listed;
+    for (int k = 0; k < n_maps; ++k) begin[(size_t)k + 1] += begin[k];
+    std::vector<int32_t> list((size_t)plan.listed), next(begin.begin(), begin.end() - 1);
+    for (int i = 0; i < frames; ++i)
+        if (map_of(i) >= 0) list[(size_t)next[(size_t)map_of(i)]++] = i;
+    plan.words.assign(plan.at_shift() + (shift ? 2 * (size_t)n_maps : 0), 0u);
+    std::memcpy(plan.words.data(), pose, (size_t)n_poses * 6 * sizeof(double));
+    std::memcpy(plan.words.data() + plan.at_begin(), begin.data(), begin.size() * sizeof(int32_t));
+    if (plan.listed) std::memcpy(plan.words.data() + plan.at_list(), list.data(), list.size() * sizeof(int32_t));
+    if (shift) std::memcpy(plan.words.data() + plan.at_shift(), shift, 2 * (size_t)n_maps * sizeof(int32_t));
+    } catch (const std::bad_alloc &) {
+        return fail(PWPP_E_NOMEM, "no host memory for the lists of %d maps and %d frames", n_maps, frames);
+    }
+    return PWPP_OK;
+}
+
+// (the uploaded words first; `occ` is the frame bytes' section: the caller's, or the visibility's)
+struct FusionSections {
+    int up, occ, map_in, map_out, map_occ;
+};
+FusionSections fusion_sections(Staging &st, const FusionPlan &plan, int s_occ, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
+    FusionSections s;
+    const size_t map_words = (plan.map_cells + 1) / 2, map_bytes = plan.map_cells * sizeof(int16_t);
+    s.up = st.add(plan.words.size(), nullptr, Staging::kKept);
+    s.occ = s_occ;
+    s.map_in = st.add(map_in ? map_words : 0, map_in, Staging::kIn, map_in ? map_bytes : 0);
+    s.map_out = st.add(map_words, map_out, Staging::kOut, map_bytes);
+    s.map_occ = st.add(map_occupancy ? (plan.map_cells + 3) / 4 : 0, map_occupancy, Staging::kOut, map_occupancy ? plan.map_cells : 0);
+    return s;
+}
+// The words are copied into their section from the handle's own copy (the caller's arrays may go on return), then the kernel.
+int fusion_launch(pwpp_handle *h, const Staging &st, const FusionSections &s, const FusionPlan &plan, int frames) {
+    h->fuse_upload = plan.words;
+    uint32_t *up = st.dev<uint32_t>(s.up);
+    const hipError_t e = hipMemcpyAsync(up, h->fuse_upload.data(), h->fuse_upload.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) return (int)e;
+    const int32_t *words = reinterpret_cast<const int32_t *>(up);
+    return pwpp_launch_fuse_grid(&plan.G, &plan.P, frames, st.dev<const int8_t>(s.occ), reinterpret_cast<const double *>(up), plan.n_poses, plan.n_maps,
+                                 words + plan.at_begin(), words + plan.at_list(), plan.listed, plan.shifted ? words + plan.at_shift() : nullptr,
+                                 st.dev<const int16_t>(s.map_in), st.dev<int16_t>(s.map_out), st.dev<int8_t>(s.map_occ), h->fusion_path, h->stream);
+}
+}  // namespace
+
+int pwpp_fuse_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int mem, const int8_t *occupancy, const double *pose, int n_poses,
+                   const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps, const int32_t *shift, const int16_t *map_in, int16_t *map_out,
+                   int8_t *map_occupancy) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !occupancy || !pose || !m || !map_out)
+        return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!occupancy ? "occupancy image" : (!pose ? "pose" : (!m ? "map description" : "map_out"))));
+    size_t cells = 0;
+    int rc = image_args(g->nx, g->ny, frames, kFusionWho, cells);
+    if (rc) return rc;
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the fusion's frame grid takes 0", g->flags);
+    FusionPlan plan;
+    if ((rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan))) return rc;
+    if ((rc = mem_args(mem, kFusionWho))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_occ = st.add((cells + 3) / 4, occupancy, Staging::kIn, cells);
+    const FusionSections s = fusion_sections(st, plan, s_occ, map_in, map_out, map_occupancy);
+    return run_on_image(h, st, [&] { return fusion_launch(h, st, s, plan, frames); });
+}
+
+// pwpp_visibility_obstacles and pwpp_fuse_grid on its bytes, enqueued as one sequence.  The count and first images, and the bytes the
+// caller does not ask for, stay in the cluster buffer.
+int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
+                        int max_range, int frame_first, int frames, int mem, const double *pose, int n_poses, const int32_t *map_of_frame,
+                        const pwpp_fusion_map *m, int n_maps, const int32_t *shift, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy,
+                        int8_t *occupancy) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !origin_xy || !pose || !m || !map_out)
+        return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!origin_xy ? "origin" : (!pose ? "pose" : (!m ? "map description" : "map_out"))));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    std::vector<int32_t> org;
+    if ((rc = visibility_origin_args(g, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
+    if (frames < 1) return fail(PWPP_E_ARG, "%d frames", frames);
+    FusionPlan plan;
+    if ((rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const VisibilitySections v = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
+    const FusionSections s = fusion_sections(st, plan, v.occ, map_in, map_out, map_occupancy);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, v.count, -1, [&](const PwppObstacleScan &) {
+        const int lrc = visibility_launch(h, st, v, g->nx, g->ny, frames, min_count, org, max_range);
+        return lrc != 0 ? lrc : fusion_launch(h, st, s, plan, frames);
     });
 }
 

@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -333,6 +333,10 @@ int pwpp_launch_distance_grid(int nx, int ny, int frames, const int32_t *count, 
 size_t pwpp_visibility_work_words(int nx, int ny, int frames, int path);
 int pwpp_launch_visibility_grid(int nx, int ny, int frames, const int32_t *count, int min_count, int ox, int oy, const int32_t *origins, int max_range,
                                 int path, int32_t *first, int8_t *occupancy, uint32_t *work, hipStream_t stream);
+// pwpp_fusion.hip
+int pwpp_launch_fuse_grid(const struct PwppFusionGeometry *G, const struct PwppFusionParams *P, int frames, const int8_t *occupancy, const double *poses,
+                          int n_poses, int n_maps, const int32_t *begin, const int32_t *list, int listed, const int32_t *shift, const int16_t *map_in,
+                          int16_t *map_out, int8_t *map_occupancy, int path, hipStream_t stream);
 }
 
 #endif

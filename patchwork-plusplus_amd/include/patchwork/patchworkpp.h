@@ -423,6 +423,36 @@ public:
                                         any ? v.occupancy.data() : &none_o, nullptr));
         return v;
     }
+    // ... and the scans accumulated over time (pwpp_fuse_obstacles): a persistent map in a FIXED frame, the caller's own.  log_odds
+    // holds an int16 per cell, occupancy the byte derived from it (PWPP_OCC_OCCUPIED where log_odds >= occupied_at, PWPP_OCC_FREE
+    // where <= free_at, else PWPP_OCC_UNKNOWN).  updateObstacleMap resamples the last frame's visibility bytes on the grid (x0, y0,
+    // cell, nx, ny) under the map-from-frame pose {a, b, tx, c, d, ty} and adds hit / subtracts miss with the clamps; (shift_x,
+    // shift_y) cells roll the map first: the new cell (jx, jy) starts from the old (jx + shift_x, jy + shift_y), the map's x0 and
+    // y0 advance by shift * cell.
+    struct FusedObstacleMap {
+        double x0 = 0.0, y0 = 0.0, cell = 0.0;  // the map's grid: cell (jx, jy) covers x0 + [jx, jx + 1) * cell, ...
+        int nx = 0, ny = 0;
+        int hit = 40, miss = 20, l_min = -200, l_max = 350, occupied_at = 60, free_at = -40;
+        std::vector<int16_t> log_odds;  // ny x nx, row-major; sized and zeroed by the first update
+        std::vector<int8_t> occupancy;  // same shape
+    };
+    void updateObstacleMap(FusedObstacleMap &map, const double pose[6], double x0, double y0, double cell, int nx, int ny, float h_min, float h_max,
+                           int min_count = 1, int max_range = 0, double origin_x = 0.0, double origin_y = 0.0, int shift_x = 0, int shift_y = 0) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, 0, 0};
+        const double mx0 = map.x0 + (double)shift_x * map.cell, my0 = map.y0 + (double)shift_y * map.cell;
+        const pwpp_fusion_map m = {mx0, my0, map.cell, map.nx, map.ny, map.hit, map.miss, map.l_min, map.l_max, map.occupied_at, map.free_at};
+        const size_t cells = (size_t)(map.nx > 0 ? map.nx : 0) * (size_t)(map.ny > 0 ? map.ny : 0);
+        if (map.log_odds.size() != cells) map.log_odds.assign(cells, 0);
+        std::vector<int16_t> out(cells ? cells : 1);
+        map.occupancy.assign(cells ? cells : 1, (int8_t)PWPP_OCC_UNKNOWN);
+        const double origin[2] = {origin_x, origin_y};
+        const int32_t shift[2] = {shift_x, shift_y};
+        check(pwpp_fuse_obstacles(h_, &g, h_min, h_max, min_count, origin, 1, max_range, 0, 1, PWPP_MEM_HOST, pose, 1, nullptr, &m, 1, shift,
+                                  cells ? map.log_odds.data() : nullptr, out.data(), map.occupancy.data(), nullptr));
+        out.resize(cells), map.occupancy.resize(cells);
+        map.log_odds.swap(out);
+        map.x0 = mx0, map.y0 = my0;
+    }
     // ... and every cluster as an oriented box (pwpp_box_obstacles on the labels above): centre, heading, length and width in
     // metres, the spread along and across, the extent in height over ground and in z.  boxes[r] belongs to clusters[r].
     struct ObstacleBoxes {

@@ -89,6 +89,12 @@ VIS_NONE, VIS_BEYOND = -1, -2  # PWPP_VIS_NONE, PWPP_VIS_BEYOND: first where not
 OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 100, -1  # PWPP_OCC_*: the occupancy bytes, nav_msgs/OccupancyGrid values
 
 
+class FusionMap(ctypes.Structure):  # pwpp_fusion_map: the grid of the fused maps in the fixed frame, the update's parameters, the byte's thresholds
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("cell", ctypes.c_double), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32),
+                ("hit", ctypes.c_int32), ("miss", ctypes.c_int32), ("l_min", ctypes.c_int32), ("l_max", ctypes.c_int32),
+                ("occupied_at", ctypes.c_int32), ("free_at", ctypes.c_int32)]
+
+
 class PwppError(RuntimeError):
     pass
 
@@ -195,6 +201,10 @@ def load():
         if hasattr(L, "pwpp_visibility_grid"):  # (as above: an older build has no line-of-sight free space)
             L.pwpp_visibility_grid.argtypes = [vp, ci, ci, ci, ci, vp, ci, vp, ci, ci, vp, vp]
             L.pwpp_visibility_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+        if hasattr(L, "pwpp_fuse_grid"):  # (as above: an older build has no occupancy fusion)
+            gp, mp = ctypes.POINTER(GroundGrid), ctypes.POINTER(FusionMap)
+            L.pwpp_fuse_grid.argtypes = [vp, gp, ci, ci, vp, vp, ci, vp, mp, ci, vp, vp, vp, vp]
+            L.pwpp_fuse_obstacles.argtypes = [vp, gp, ctypes.c_float, ctypes.c_float, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, mp, ci, vp, vp, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -949,6 +959,78 @@ class Handle:
         self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count),
                                                       _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
                                                       _dp(first_ptr), _dp(occupancy_ptr), _dp(count_ptr)))
+
+    @staticmethod
+    def _fusion_host(pose, map_of_frame, shift):
+        """The host arrays every fusion call takes: (n_poses, 6) float64, (frames,) int32 or None, (n_maps, 2) int32 or None."""
+        pose = np.ascontiguousarray(np.asarray(pose, np.float64).reshape(-1, 6))
+        mof = None if map_of_frame is None else np.ascontiguousarray(map_of_frame, np.int32).reshape(-1)
+        shift = None if shift is None else np.ascontiguousarray(np.asarray(shift, np.int32).reshape(-1, 2))
+        return pose, mof, shift
+
+    def fuse_grid(self, occupancy, grid, pose, fmap, n_maps=1, map_in=None, map_of_frame=None, shift=None, want_occupancy=True, map_out=None):
+        """Fuses the (frames, ny, nx) or (ny, nx) int8 occupancy images on the grid `grid` = (x0, y0, cell) into n_maps int16 log-odds
+        maps described by the FusionMap `fmap`.  pose: the map-from-frame {a, b, tx, c, d, ty}, one for every frame or (frames, 6);
+        map_of_frame: None (one map: a sequence; n_maps == frames: frame i into map i) or a map index per frame, -1: skipped;
+        shift: None or (n_maps, 2) cells {sx, sy}; map_in: the (n_maps, NY, NX) int16 maps to start from, None: zero; map_out: the
+        array to write (map_in itself is allowed without a shift), None: a new one.  Works before any estimate call.  Returns
+        (map_out, map_occupancy) of shape (n_maps, NY, NX), the int8 bytes None when not wanted.  The rules: include/pwpp.h."""
+        occ = np.ascontiguousarray(occupancy, np.int8)
+        o3 = occ.reshape((1,) + occ.shape) if occ.ndim == 2 else occ
+        if o3.ndim != 3:
+            raise ValueError("occupancy: a (frames, ny, nx) or (ny, nx) image expected")
+        frames, ny, nx = o3.shape
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), nx, ny, 0, 0)
+        pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
+        shape = self._grid_shape(fmap, n_maps)
+        if map_in is not None:
+            map_in = np.ascontiguousarray(map_in, np.int16).reshape(shape)
+        out = np.empty(shape, np.int16) if map_out is None else map_out
+        byte = np.empty(shape, np.int8) if want_occupancy else None
+        self._check(self._L.pwpp_fuse_grid(self._h, ctypes.byref(g), frames, MEM_HOST, _hp(o3), _hp(pose), len(pose), _hp(mof), ctypes.byref(fmap),
+                                           int(n_maps), _hp(shift), _hp(map_in), _hp(out), _hp(byte)))
+        return out, byte
+
+    def fuse_grid_device(self, grid, nx, ny, frames, occupancy_ptr, pose, fmap, n_maps, map_in_ptr, map_out_ptr, map_occupancy_ptr=0, map_of_frame=None,
+                         shift=None):
+        """fuse_grid on device memory: addresses of the (frames, ny, nx) int8 occupancy images, the (n_maps, NY, NX) int16 maps
+        (map_in_ptr 0: zero; 2-byte aligned) and (0: not wanted) the int8 map bytes; pose, map_of_frame and shift stay host arrays.
+        Enqueued on the handle's stream; complete after synchronize()."""
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), int(nx), int(ny), 0, 0)
+        pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
+        self._check(self._L.pwpp_fuse_grid(self._h, ctypes.byref(g), int(frames), MEM_DEVICE, _dp(occupancy_ptr), _hp(pose), len(pose), _hp(mof),
+                                           ctypes.byref(fmap), int(n_maps), _hp(shift), _dp(map_in_ptr), _dp(map_out_ptr), _dp(map_occupancy_ptr)))
+
+    def fuse_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, pose, fmap, n_maps=1, map_in=None, origin_xy=(0.0, 0.0), min_count=1, max_range=0,
+                       frame_first=0, frames=None, map_of_frame=None, shift=None, ground_only=False, want_occupancy=True, want_frames=False):
+        """rasterize_obstacles, visibility_grid and fuse_grid in one call, for frames of the last estimate call: (map_out,
+        map_occupancy) as fuse_grid gives them for the occupancy bytes of visibility_obstacles; want_frames: then those
+        (frames, ny, nx) int8 bytes too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
+        shape = self._grid_shape(fmap, n_maps)
+        if map_in is not None:
+            map_in = np.ascontiguousarray(map_in, np.int16).reshape(shape)
+        out = np.empty(shape, np.int16)
+        byte = np.empty(shape, np.int8) if want_occupancy else None
+        occ = np.empty(self._grid_shape(g, frames), np.int8) if want_frames else None
+        self._check(self._L.pwpp_fuse_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
+                                                int(frame_first), frames, MEM_HOST, _hp(pose), len(pose), _hp(mof), ctypes.byref(fmap), int(n_maps),
+                                                _hp(shift), _hp(map_in), _hp(out), _hp(byte), _hp(occ)))
+        return (out, byte) + ((occ,) if want_frames else ())
+
+    def fuse_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, pose, fmap, n_maps, map_in_ptr, map_out_ptr, map_occupancy_ptr=0, occupancy_ptr=0,
+                              origin_xy=(0.0, 0.0), min_count=1, max_range=0, frame_first=0, frames=None, map_of_frame=None, shift=None,
+                              ground_only=False):
+        """fuse_obstacles into device memory: addresses as in fuse_grid_device, occupancy_ptr the (frames, ny, nx) int8 bytes of the
+        frames (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
+        self._check(self._L.pwpp_fuse_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
+                                                int(frame_first), frames, MEM_DEVICE, _hp(pose), len(pose), _hp(mof), ctypes.byref(fmap), int(n_maps),
+                                                _hp(shift), _dp(map_in_ptr), _dp(map_out_ptr), _dp(map_occupancy_ptr), _dp(occupancy_ptr)))
 
     def box_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_boxes, frame_first=0, frames=None, ground_only=False):
         """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as oriented

@@ -7,6 +7,8 @@
 // to float32 (C- or F-contiguous is used in place, anything else is copied), the getters
 // return fresh C-contiguous numpy arrays: (n, 3) float32 and (n,) int32.  The GIL is
 // released while the GPU works.
+#include <array>
+
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -142,6 +144,20 @@ PYBIND11_MODULE(pypatchworkpp, m) {
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_box, points, pad_, mean_x, mean_y, cx, cy, ax, ay, length, width, sigma_long, sigma_short, h_min, h_max, z_min,
                          z_max);
 
+    py::class_<PatchWorkpp::FusedObstacleMap>(m, "FusedObstacleMap")  // the caller's persistent map of updateObstacleMap
+        .def(py::init<>())
+        .def_readwrite("x0", &PatchWorkpp::FusedObstacleMap::x0)
+        .def_readwrite("y0", &PatchWorkpp::FusedObstacleMap::y0)
+        .def_readwrite("cell", &PatchWorkpp::FusedObstacleMap::cell)
+        .def_readwrite("nx", &PatchWorkpp::FusedObstacleMap::nx)
+        .def_readwrite("ny", &PatchWorkpp::FusedObstacleMap::ny)
+        .def_readwrite("hit", &PatchWorkpp::FusedObstacleMap::hit)
+        .def_readwrite("miss", &PatchWorkpp::FusedObstacleMap::miss)
+        .def_readwrite("l_min", &PatchWorkpp::FusedObstacleMap::l_min)
+        .def_readwrite("l_max", &PatchWorkpp::FusedObstacleMap::l_max)
+        .def_readwrite("occupied_at", &PatchWorkpp::FusedObstacleMap::occupied_at)
+        .def_readwrite("free_at", &PatchWorkpp::FusedObstacleMap::free_at);
+
     py::class_<PatchWorkpp>(m, "patchworkpp")
         .def(py::init<Params>())
         .def(py::init<Params, int>(), py::arg("params"), py::arg("device"))
@@ -208,6 +224,19 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0, py::arg("ground_only") = false)
+        .def("updateObstacleMap",
+             [](PatchWorkpp &s, PatchWorkpp::FusedObstacleMap &map, const std::array<double, 6> &pose, double x0, double y0, double cell, int nx, int ny,
+                float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y, int shift_x, int shift_y) {
+                 s.updateObstacleMap(map, pose.data(), x0, y0, cell, nx, ny, h_min, h_max, min_count, max_range, origin_x, origin_y, shift_x, shift_y);
+                 py::array_t<int16_t> log_odds({(py::ssize_t)map.ny, (py::ssize_t)map.nx});
+                 py::array_t<int8_t> occupancy({(py::ssize_t)map.ny, (py::ssize_t)map.nx});
+                 if (!map.log_odds.empty()) std::memcpy(log_odds.mutable_data(), map.log_odds.data(), map.log_odds.size() * sizeof(int16_t));
+                 if (!map.occupancy.empty()) std::memcpy(occupancy.mutable_data(), map.occupancy.data(), map.occupancy.size());
+                 return py::make_tuple(log_odds, occupancy);
+             },
+             py::arg("map"), py::arg("pose"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"),
+             py::arg("h_max"), py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0,
+             py::arg("shift_x") = 0, py::arg("shift_y") = 0)
         .def("getObstacleBoxes",
              [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int connectivity,
                 bool ground_only) {
