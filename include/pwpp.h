@@ -794,6 +794,79 @@ PWPP_API int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, floa
                                  const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy /* may be NULL */,
                                  int8_t *occupancy /* the per-frame bytes, may be NULL: kept in the handle's buffer */);
 
+/* ---- correlative scan match: where a frame's occupancy fits the fused map (pwpp_match_grid, pwpp_match_obstacles) ------------------
+ * The fusion takes a pose per frame and trusts it; a map fused under a pose one cell or one degree off smears every wall.  The
+ * match closes the chain: for a set of candidate poses and a window of whole-cell shifts it adds up the map's log-odds under the
+ * frame's occupied cells and names the best (Olson 2009) -- integer sums, a total order for the maximum, so bit-reproducible.
+ * estimate -> occupancy -> match -> fuse under the matched pose.  Below (X0, Y0, CELL, NX, NY) are m's fields (its update parameters
+ * and thresholds are not read), (x0, y0, cell, nx, ny) g's.
+ *   candidate A map-from-frame matrix {a, b, tx, c, d, ty}, exactly the fusion's pose; no angle enters the contract (the caller, or a
+ *             binding's helper, builds the rotations).  HOST memory in both mem kinds, copied at the call: [n_sets][n_candidates][6],
+ *             n_sets == 1: the same candidates for every frame; n_sets == frames: set i for frame i.  A candidate that is not
+ *             finite is no error: its cells land nowhere.
+ *   landing   For every cell (ix, iy) of frame f whose byte is exactly PWPP_OCC_OCCUPIED and every candidate r, all in double, every
+ *             product, sum and quotient rounded on its own (no FMA, as in the fusion):
+ *                 x = x0 + ((double)ix + 0.5) * cell          y alike
+ *                 X = (a * x + b * y) + tx                    Y = (c * x + d * y) + ty
+ *                 U = (X - X0) / CELL                         V alike
+ *             The cell lands iff -1048576 <= U < 1048576 and the same for V (a NaN does not land); then Jx = (int)floor(U),
+ *             Jy = (int)floor(V).
+ *   score     For sx in [-wx, wx] and sy in [-wy, wy], scores[f][r][sy + wy][sx + wx] is the int64 sum of map[k][Jy + sy][Jx + sx]
+ *             over the landed cells of (f, r); only cells with 0 <= Jx + sx < NX and 0 <= Jy + sy < NY contribute.  k is the frame's
+ *             map by the fusion's map_of_frame rule: NULL with one map, NULL with one map per frame, or explicit.  A frame with
+ *             map_of_frame == -1 is skipped: candidate -1, score 0, shift 0, cells still counted, its scores all 0.
+ *   best      The maximum of the scores of a frame under this total order: the larger score; then the smaller sx * sx + sy * sy;
+ *             then the smaller candidate index; then the smaller sy; then the smaller sx.  Callers put the prior first.  A frame
+ *             with no occupied cell returns {0, 0, 0, 0, 0}.
+ *   match_pose  Host only, no device needed: out is the candidate with tx + (double)sx * CELL and ty + (double)sy * CELL, one product
+ *             and one sum each: what the caller hands to pwpp_fuse_* next.
+ *   match_obstacles   the per-frame bytes are exactly the occupancy image pwpp_visibility_obstacles gives for the same arguments,
+ *             written for the caller where asked for and kept in the handle's cluster buffer otherwise; best and scores are exactly
+ *             what pwpp_match_grid gives for them.  Entry i of the candidate sets and of map_of_frame belongs to frame frame_first
+ *             + i.  When, the lifetime rule of the INPUT and PWPP_E_STATE are those of pwpp_fuse_obstacles.
+ *   mem       PWPP_MEM_HOST: images, map, best and scores are host memory, staged through the cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- the map 2-byte aligned, the bytes byte aligned, no more; best and scores 8-byte
+ *             aligned -- enqueued on the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *             candidates and map_of_frame are HOST memory always.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, grid, occupancy (pwpp_match_grid),
+ *             candidates, map description, map or best; frames or a side of the frame image < 1, a side > 32768, nx * ny * frames
+ *             beyond 2^31; g->flags != 0 (pwpp_match_grid); the same three of n_maps and the map; a cell or CELL that is not finite
+ *             and positive; n_candidates outside 1 .. 256; n_sets neither 1 nor frames; wx or wy outside 0 .. 64; frames *
+ *             n_candidates beyond 2^24; with scores, their element count beyond 2^31; map_of_frame; mem; in PWPP_MEM_DEVICE a best
+ *             or scores that is not 8-byte aligned.  pwpp_match_obstacles rejects first everything pwpp_visibility_obstacles
+ *             rejects of its grid, band, min_count, max_range and origins, then the above of the map, and last the frame range and
+ *             mem; before any estimate call: PWPP_E_STATE.
+ *   buffers   The candidates and the frames' maps are uploaded into the cluster buffer; the frames' occupied cells (one packed word
+ *             each, at most nx * ny per frame) and the workgroups' bests are working words there: allocated on first use, counted by
+ *             pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *   outputs   The same bytes for every call, mem, alignment and value of the option "match_path".
+ * With none of the three called nothing is allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_SCAN_MATCH 1
+typedef struct pwpp_match_best {   /* 24 bytes, 8-byte aligned */
+    int64_t score;                 /* the winning sum */
+    int32_t candidate;             /* index into the frame's candidates; -1: the frame was skipped */
+    int32_t sx, sy;                /* the winning shift, whole MAP cells */
+    int32_t cells;                 /* occupied cells of the frame (bytes == PWPP_OCC_OCCUPIED) */
+} pwpp_match_best;
+
+/* any occupancy images and maps: needs a handle (stream, buffer), no estimate call -- like pwpp_fuse_grid */
+PWPP_API int pwpp_match_grid(pwpp_handle *h, const pwpp_ground_grid *g /* the FRAME images' grid; flags must be 0 */, int frames, int mem,
+                             const int8_t *occupancy /* [frames][g->ny][g->nx] */,
+                             const double *candidates /* HOST, [n_sets][n_candidates][6] */, int n_sets /* 1 or frames */, int n_candidates,
+                             const int32_t *map_of_frame /* HOST, frames entries, or NULL: the fusion's rule */,
+                             const pwpp_fusion_map *m /* only x0, y0, cell, nx, ny are read */, int n_maps,
+                             const int16_t *map /* [n_maps][m->ny][m->nx] */, int wx, int wy,
+                             pwpp_match_best *best /* [frames] */,
+                             int64_t *scores /* [frames][n_candidates][2 wy + 1][2 wx + 1], may be NULL */);
+/* rasterize + visibility + match for frames of the LAST estimate call, one call -- like pwpp_fuse_obstacles */
+PWPP_API int pwpp_match_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count,
+                                  const double *origin_xy, int n_origins, int max_range, int frame_first, int frames, int mem,
+                                  const double *candidates, int n_sets, int n_candidates, const int32_t *map_of_frame,
+                                  const pwpp_fusion_map *m, int n_maps, const int16_t *map, int wx, int wy,
+                                  pwpp_match_best *best, int64_t *scores /* may be NULL */,
+                                  int8_t *occupancy /* the per-frame bytes, may be NULL: kept in the handle's buffer */);
+PWPP_API int pwpp_match_pose(const double candidate[6], double CELL, int sx, int sy, double out[6]);  /* host only */
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -929,6 +1002,11 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         exact and the product the same bits as the quotient -- and the division otherwise; "1": always the
  *                         double division as the contract writes it (the yardstick of tools/occupancy_fusion_cost.py).  The
  *                         results are identical bytes.
+ *   "match_path"          how the scan match reads the map (pwpp_match_grid, pwpp_match_obstacles): "1": every map read comes from
+ *                         global memory (the yardstick of tools/scan_match_cost.py); "2": the rectangle of the map that the
+ *                         landings of a (frame, candidate) reach under the window is copied into LDS once per workgroup where it
+ *                         holds at most 65536 cells, and read from global memory where it does not; "0" (default): whichever of
+ *                         the two that tool found faster.  The results are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

@@ -26,6 +26,7 @@
 #include "pwpp_dev.h"
 #include "pwpp_distance.h"
 #include "pwpp_fusion.h"
+#include "pwpp_match.h"
 #include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
@@ -251,6 +252,8 @@ struct pwpp_handle {
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
     std::vector<uint32_t> fuse_upload;  // the poses, frame lists and shifts of the last fusion call: the source of its upload
+    int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
+    std::vector<uint32_t> match_upload;  // the candidates and the frames' maps of the last scan match: the source of its upload
     std::vector<int32_t> vis_origins;  // the origin cells of the last visibility call with one origin per frame: the source of its upload
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
@@ -2111,6 +2114,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 1) return fail(PWPP_E_ARG, "fusion_path=%s: 0 or 1 expected", value);
         h->fusion_path = v;
+    } else if (k == "match_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
+        h->match_path = v;
     } else if (k == "boxes_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
@@ -2865,6 +2872,158 @@ int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, 
         const int lrc = visibility_launch(h, st, v, g->nx, g->ny, frames, min_count, org, max_range);
         return lrc != 0 ? lrc : fusion_launch(h, st, s, plan, frames);
     });
+}
+
+// ---- scan match: the map's log-odds summed under a frame's occupied cells, for every candidate pose and whole-cell shift ----------
+namespace {
+static_assert(PWPP_OCC_OCCUPIED == PWPP_MATCH_OCCUPIED, "the kernel's occupied byte");
+static_assert(sizeof(pwpp_match_best) == 24 && sizeof(PwppMatchKey) == 24 && alignof(pwpp_match_best) == 8, "pwpp_match_best is 24 bytes, 8-byte aligned");
+static_assert(offsetof(pwpp_match_best, candidate) == offsetof(PwppMatchKey, candidate) && offsetof(pwpp_match_best, cells) == offsetof(PwppMatchKey, cells),
+              "the kernels write pwpp_match_best rows");
+constexpr const char *kMatchWho = "the scan match takes";
+
+// What a checked call hands to the kernels besides its images: the geometry, the counts and the words to upload -- the candidates
+// first (8-byte aligned at the section's start), then every frame's map, the rule of map_of_frame resolved.
+struct MatchPlan {
+    PwppMatchGeometry G;
+    int n_sets = 0, n_candidates = 0, n_maps = 0, wx = 0, wy = 0;
+    size_t map_cells = 0;    // NX * NY * n_maps
+    size_t score_count = 0;  // frames * n_candidates * (2 wy + 1) * (2 wx + 1) where the caller wants the scores, else 0
+    std::vector<uint32_t> words;
+    size_t at_maps() const { return (size_t)n_sets * (size_t)n_candidates * 12; }
+};
+
+// What both entry points check of the map, the candidates, the window and the frames' maps, in the header's order, after the frame
+// images' own checks (frames >= 1); fills the plan.  Touches no handle.
+int match_args(const pwpp_ground_grid *g, int frames, const double *candidates, int n_sets, int n_candidates, const int32_t *map_of_frame,
+               const pwpp_fusion_map *m, int n_maps, int wx, int wy, const int64_t *scores, MatchPlan &plan) {
+    if (const int rc = image_args(m->nx, m->ny, n_maps, kMatchWho, plan.map_cells)) return rc;
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !(m->cell > 0.0) || !std::isfinite(m->cell))
+        return fail(PWPP_E_ARG, "cell sizes %g (frames) and %g (map): finite and positive expected", g->cell, m->cell);
+    if (n_candidates < 1 || n_candidates > PWPP_MATCH_MAX_CANDIDATES) return fail(PWPP_E_ARG, "%d candidates: 1 .. 256 expected", n_candidates);
+    if (n_sets < 1 || (n_sets != 1 && n_sets != frames))
+        return fail(PWPP_E_ARG, "%d candidate sets for %d frames: 1 or one per frame expected", n_sets, frames);
+    if (wx < 0 || wx > PWPP_MATCH_MAX_WINDOW || wy < 0 || wy > PWPP_MATCH_MAX_WINDOW)
+        return fail(PWPP_E_ARG, "window wx %d, wy %d: 0 .. 64 cells expected", wx, wy);
+    if ((int64_t)frames * (int64_t)n_candidates > ((int64_t)1 << 24))
+        return fail(PWPP_E_ARG, "%d frames x %d candidates exceed 2^24", frames, n_candidates);
+    const int64_t per_pair = (int64_t)(2 * wx + 1) * (int64_t)(2 * wy + 1);  // (<= 129^2; frames x candidates <= 2^24)
+    if (scores && (int64_t)frames * (int64_t)n_candidates * per_pair > ((int64_t)1 << 31))
+        return fail(PWPP_E_ARG, "%d frames x %d candidates x %lld shifts: the scores exceed 2^31 elements", frames, n_candidates, (long long)per_pair);
+    if (!map_of_frame && n_maps != 1 && n_maps != frames)
+        return fail(PWPP_E_ARG, "null map_of_frame with %d maps for %d frames: 1 map or one per frame expected", n_maps, frames);
+    for (int i = 0; map_of_frame && i < frames; ++i)
+        if (map_of_frame[i] < -1 || map_of_frame[i] >= n_maps)
+            return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
+
+    plan.G = PwppMatchGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
+    pwpp_fuse_reciprocal(m->cell, plan.G.inv_CELL);
+    plan.n_sets = n_sets, plan.n_candidates = n_candidates, plan.n_maps = n_maps, plan.wx = wx, plan.wy = wy;
+    plan.score_count = scores ? (size_t)frames * (size_t)n_candidates * (size_t)per_pair : 0;
+    try {
+        plan.words.assign(plan.at_maps() + (size_t)frames, 0u);
+    } catch (const std::bad_alloc &) {
+        return fail(PWPP_E_NOMEM, "no host memory for %d candidate sets of %d and %d frames", n_sets, n_candidates, frames);
+    }
+    std::memcpy(plan.words.data(), candidates, (size_t)n_sets * (size_t)n_candidates * 6 * sizeof(double));
+    for (int i = 0; i < frames; ++i) {
+        const int32_t k = map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i);
+        std::memcpy(plan.words.data() + plan.at_maps() + (size_t)i, &k, sizeof(k));
+    }
+    return PWPP_OK;
+}
+
+// (after mem: what PWPP_MEM_DEVICE asks of the result arrays; the map is 2-byte aligned and the bytes byte aligned, no more)
+int match_alignment_args(int mem, const void *best, const void *scores) {
+    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
+    if (reinterpret_cast<uintptr_t>(best) & 7u) return fail(PWPP_E_ARG, "the best rows must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(scores) & 7u) return fail(PWPP_E_ARG, "the scores must be 8-byte aligned");
+    return PWPP_OK;
+}
+
+// (the uploaded words and the kernels' working words first -- cell list, counts and workgroup bests are kKept like every operator's
+// work words: theirs alone, in the buffer whatever the memory kind; `occ` is the frame bytes' section: the caller's, or the visibility's)
+struct MatchSections {
+    int up, work, occ, map, best, scores;
+};
+MatchSections match_sections(Staging &st, const MatchPlan &plan, int frames, int s_occ, const int16_t *map, pwpp_match_best *best, int64_t *scores) {
+    MatchSections s;
+    s.up = st.add(plan.words.size(), nullptr, Staging::kKept);
+    s.work = st.add(pwpp_match_work_words(plan.G.nx, plan.G.ny, frames, plan.n_candidates, plan.wx, plan.wy), nullptr, Staging::kKept);
+    s.occ = s_occ;
+    s.map = st.add((plan.map_cells + 1) / 2, map, Staging::kIn, plan.map_cells * sizeof(int16_t));
+    s.best = st.add((size_t)frames * (sizeof(pwpp_match_best) / 4), best, Staging::kOut);
+    s.scores = st.add(plan.score_count * 2, scores, Staging::kOut);
+    return s;
+}
+// The words are copied into their section from the handle's own copy (the caller's arrays may go on return; the plan's vector moves
+// into the handle: nothing is allocated here), then the kernels.
+int match_launch(pwpp_handle *h, const Staging &st, const MatchSections &s, MatchPlan &plan, int frames) {
+    h->match_upload.swap(plan.words);
+    uint32_t *up = st.dev<uint32_t>(s.up);
+    const hipError_t e = hipMemcpyAsync(up, h->match_upload.data(), h->match_upload.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) return (int)e;
+    return pwpp_launch_match_grid(&plan.G, frames, st.dev<const int8_t>(s.occ), reinterpret_cast<const double *>(up), plan.n_sets, plan.n_candidates,
+                                  reinterpret_cast<const int32_t *>(up) + plan.at_maps(), plan.n_maps, st.dev<const int16_t>(s.map), plan.wx, plan.wy,
+                                  st.dev<void>(s.best), st.dev<int64_t>(s.scores), st.dev<uint32_t>(s.work), h->match_path, h->stream);
+}
+}  // namespace
+
+int pwpp_match_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int mem, const int8_t *occupancy, const double *candidates, int n_sets,
+                    int n_candidates, const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps, const int16_t *map, int wx, int wy,
+                    pwpp_match_best *best, int64_t *scores) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !occupancy || !candidates || !m || !map || !best)
+        return fail(PWPP_E_ARG, "null %s",
+                    !g ? "grid" : (!occupancy ? "occupancy image" : (!candidates ? "candidates" : (!m ? "map description" : (!map ? "map" : "best rows")))));
+    size_t cells = 0;
+    int rc = image_args(g->nx, g->ny, frames, kMatchWho, cells);
+    if (rc) return rc;
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the scan match's frame grid takes 0", g->flags);
+    MatchPlan plan;
+    if ((rc = match_args(g, frames, candidates, n_sets, n_candidates, map_of_frame, m, n_maps, wx, wy, scores, plan))) return rc;
+    if ((rc = mem_args(mem, kMatchWho))) return rc;
+    if ((rc = match_alignment_args(mem, best, scores))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_occ = st.add((cells + 3) / 4, occupancy, Staging::kIn, cells);
+    const MatchSections s = match_sections(st, plan, frames, s_occ, map, best, scores);
+    return run_on_image(h, st, [&] { return match_launch(h, st, s, plan, frames); });
+}
+
+// pwpp_visibility_obstacles and pwpp_match_grid on its bytes, enqueued as one sequence.  The count and first images, and the bytes the
+// caller does not ask for, stay in the cluster buffer.
+int pwpp_match_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
+                         int max_range, int frame_first, int frames, int mem, const double *candidates, int n_sets, int n_candidates,
+                         const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps, const int16_t *map, int wx, int wy, pwpp_match_best *best,
+                         int64_t *scores, int8_t *occupancy) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !origin_xy || !candidates || !m || !map || !best)
+        return fail(PWPP_E_ARG, "null %s",
+                    !g ? "grid" : (!origin_xy ? "origin" : (!candidates ? "candidates" : (!m ? "map description" : (!map ? "map" : "best rows")))));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    std::vector<int32_t> org;
+    if ((rc = visibility_origin_args(g, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
+    if (frames < 1) return fail(PWPP_E_ARG, "%d frames", frames);
+    MatchPlan plan;
+    if ((rc = match_args(g, frames, candidates, n_sets, n_candidates, map_of_frame, m, n_maps, wx, wy, scores, plan))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = match_alignment_args(mem, best, scores))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const VisibilitySections v = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
+    const MatchSections s = match_sections(st, plan, frames, v.occ, map, best, scores);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, v.count, -1, [&](const PwppObstacleScan &) {
+        const int lrc = visibility_launch(h, st, v, g->nx, g->ny, frames, min_count, org, max_range);
+        return lrc != 0 ? lrc : match_launch(h, st, s, plan, frames);
+    });
+}
+
+// Host only: the candidate moved by the winning shift, with the rounding of pwpp_match.h.
+int pwpp_match_pose(const double candidate[6], double CELL, int sx, int sy, double out[6]) {
+    if (!candidate || !out) return fail(PWPP_E_ARG, "null %s", candidate ? "output pose" : "candidate");
+    pwpp_match_shifted_pose(candidate, CELL, sx, sy, out);
+    return PWPP_OK;
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

@@ -337,6 +337,11 @@ int pwpp_launch_visibility_grid(int nx, int ny, int frames, const int32_t *count
 int pwpp_launch_fuse_grid(const struct PwppFusionGeometry *G, const struct PwppFusionParams *P, int frames, const int8_t *occupancy, const double *poses,
                           int n_poses, int n_maps, const int32_t *begin, const int32_t *list, int listed, const int32_t *shift, const int16_t *map_in,
                           int16_t *map_out, int8_t *map_occupancy, int path, hipStream_t stream);
+// pwpp_match.hip
+size_t pwpp_match_work_words(int nx, int ny, int frames, int n_candidates, int wx, int wy);
+int pwpp_launch_match_grid(const struct PwppMatchGeometry *G, int frames, const int8_t *occupancy, const double *candidates, int n_sets, int n_candidates,
+                           const int32_t *map_of_frame, int n_maps, const int16_t *map, int wx, int wy, void *best, int64_t *scores, uint32_t *work,
+                           int path, hipStream_t stream);
 }
 
 #endif

@@ -453,6 +453,32 @@ public:
         map.log_odds.swap(out);
         map.x0 = mx0, map.y0 = my0;
     }
+    // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},
+    // the prior first) and every shift of [-wx, wx] x [-wy, wy] map cells, the sum of log_odds under the occupied cells of the
+    // frame's visibility bytes; the best by the contract's order, and `pose`, the winning candidate moved by the winning shift
+    // (pwpp_match_pose): what updateObstacleMap takes next.  The map is read, not changed; it must have been updated once.
+    struct ObstacleMatch {
+        int candidate = -1, sx = 0, sy = 0;
+        int64_t score = 0;
+        int cells = 0;  // occupied cells of the frame
+        double pose[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    };
+    ObstacleMatch matchObstacleMap(const FusedObstacleMap &map, const double *candidates, int n_candidates, int wx, int wy, double x0, double y0,
+                                   double cell, int nx, int ny, float h_min, float h_max, int min_count = 1, int max_range = 0, double origin_x = 0.0,
+                                   double origin_y = 0.0) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, 0, 0};
+        const pwpp_fusion_map m = {map.x0, map.y0, map.cell, map.nx, map.ny, map.hit, map.miss, map.l_min, map.l_max, map.occupied_at, map.free_at};
+        const size_t cells = (size_t)(map.nx > 0 ? map.nx : 0) * (size_t)(map.ny > 0 ? map.ny : 0);
+        if (map.log_odds.size() != cells || cells == 0) throw std::runtime_error("matchObstacleMap: the map has no log_odds of its nx x ny cells");
+        const double origin[2] = {origin_x, origin_y};
+        pwpp_match_best best = {0, -1, 0, 0, 0};
+        check(pwpp_match_obstacles(h_, &g, h_min, h_max, min_count, origin, 1, max_range, 0, 1, PWPP_MEM_HOST, candidates, 1, n_candidates, nullptr, &m, 1,
+                                   map.log_odds.data(), wx, wy, &best, nullptr, nullptr));
+        ObstacleMatch r;
+        r.candidate = best.candidate, r.sx = best.sx, r.sy = best.sy, r.score = best.score, r.cells = best.cells;
+        if (best.candidate >= 0 && best.candidate < n_candidates) check(pwpp_match_pose(candidates + 6 * (size_t)best.candidate, map.cell, best.sx, best.sy, r.pose));
+        return r;
+    }
     // ... and every cluster as an oriented box (pwpp_box_obstacles on the labels above): centre, heading, length and width in
     // metres, the spread along and across, the extent in height over ground and in z.  boxes[r] belongs to clusters[r].
     struct ObstacleBoxes {

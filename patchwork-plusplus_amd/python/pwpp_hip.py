@@ -95,6 +95,13 @@ class FusionMap(ctypes.Structure):  # pwpp_fusion_map: the grid of the fused map
                 ("occupied_at", ctypes.c_int32), ("free_at", ctypes.c_int32)]
 
 
+class MatchBest(ctypes.Structure):  # pwpp_match_best (24 bytes): the winning sum, its candidate (-1: skipped) and shift, the frame's occupied cells
+    _fields_ = [("score", ctypes.c_int64), ("candidate", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("cells", ctypes.c_int32)]
+
+
+MATCH_BEST_DTYPE = np.dtype([("score", "<i8"), ("candidate", "<i4"), ("sx", "<i4"), ("sy", "<i4"), ("cells", "<i4")])
+
+
 class PwppError(RuntimeError):
     pass
 
@@ -205,6 +212,11 @@ def load():
             gp, mp = ctypes.POINTER(GroundGrid), ctypes.POINTER(FusionMap)
             L.pwpp_fuse_grid.argtypes = [vp, gp, ci, ci, vp, vp, ci, vp, mp, ci, vp, vp, vp, vp]
             L.pwpp_fuse_obstacles.argtypes = [vp, gp, ctypes.c_float, ctypes.c_float, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, mp, ci, vp, vp, vp, vp, vp]
+        if hasattr(L, "pwpp_match_grid"):  # (as above: an older build has no scan match)
+            gp, mp, cf = ctypes.POINTER(GroundGrid), ctypes.POINTER(FusionMap), ctypes.c_float
+            L.pwpp_match_grid.argtypes = [vp, gp, ci, ci, vp, vp, ci, ci, vp, mp, ci, vp, ci, ci, vp, vp]
+            L.pwpp_match_obstacles.argtypes = [vp, gp, cf, cf, ci, vp, ci, ci, ci, ci, ci, vp, ci, ci, vp, mp, ci, vp, ci, ci, vp, vp, vp]
+            L.pwpp_match_pose.argtypes = [vp, ctypes.c_double, ci, ci, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -239,6 +251,30 @@ def default_params():
     p = Params()
     load().pwpp_params_default(ctypes.byref(p))
     return p
+
+
+def match_pose(candidate, cell, sx, sy):
+    """The candidate {a, b, tx, c, d, ty} moved by the winning shift of a scan match (pwpp_match_pose): tx + sx * cell and
+    ty + sy * cell with the library's rounding, `cell` the MAP's cell size -- the pose to fuse under.  Host only."""
+    cand = np.ascontiguousarray(np.asarray(candidate, np.float64).reshape(6))
+    out = np.empty(6, np.float64)
+    L = load()
+    if L.pwpp_match_pose(_vp(cand), float(cell), int(sx), int(sy), _vp(out)) < 0:
+        raise PwppError(L.pwpp_last_error().decode())
+    return out
+
+
+def yaw_candidates(pose, step, n):
+    """(n, 6) candidate poses for a scan match: the prior `pose` first, then the prior turned by +step, -step, +2 step, -2 step ...
+    radians about the frame's origin (the prior's matrix composed with the rotation; the translation stays).  Built in numpy: a
+    convenience outside the library's contract."""
+    a, b, tx, c, d, ty = (float(v) for v in np.asarray(pose, np.float64).reshape(6))
+    out = np.empty((int(n), 6), np.float64)
+    for i in range(int(n)):
+        k = (i + 1) // 2 * (1 if i % 2 else -1)
+        co, si = np.cos(k * float(step)), np.sin(k * float(step))
+        out[i] = (a * co + b * si, b * co - a * si, tx, c * co + d * si, d * co - c * si, ty) if i else (a, b, tx, c, d, ty)
+    return out
 
 
 def _vp(a):
@@ -1031,6 +1067,81 @@ class Handle:
         self._check(self._L.pwpp_fuse_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
                                                 int(frame_first), frames, MEM_DEVICE, _hp(pose), len(pose), _hp(mof), ctypes.byref(fmap), int(n_maps),
                                                 _hp(shift), _dp(map_in_ptr), _dp(map_out_ptr), _dp(map_occupancy_ptr), _dp(occupancy_ptr)))
+
+    @staticmethod
+    def _match_host(candidates, frames, map_of_frame):
+        """The host arrays every match call takes: (n_sets, n_candidates, 6) float64 and (frames,) int32 or None."""
+        cand = np.ascontiguousarray(np.asarray(candidates, np.float64))
+        cand = cand.reshape((1,) + cand.shape) if cand.ndim == 2 else cand
+        if cand.ndim != 3 or cand.shape[2] != 6:
+            raise ValueError("candidates: (n_candidates, 6) or (n_sets, n_candidates, 6) expected")
+        mof = None if map_of_frame is None else np.ascontiguousarray(map_of_frame, np.int32).reshape(-1)
+        return cand, mof
+
+    def match_grid(self, occupancy, grid, candidates, fmap, maps, wx, wy, map_of_frame=None, want_scores=False):
+        """Matches the (frames, ny, nx) or (ny, nx) int8 occupancy images on the grid `grid` = (x0, y0, cell) against the
+        (n_maps, NY, NX) or (NY, NX) int16 log-odds maps described by the FusionMap `fmap`: for every candidate pose
+        {a, b, tx, c, d, ty} -- (n_candidates, 6) for every frame, or (frames, n_candidates, 6) -- and every shift of
+        [-wx, wx] x [-wy, wy] map cells, the sum of the map under the frame's occupied cells.  map_of_frame as in fuse_grid.
+        Works before any estimate call.  Returns the (frames,) MATCH_BEST_DTYPE rows; want_scores: (rows, scores) with the int64
+        (frames, n_candidates, 2 wy + 1, 2 wx + 1) sums.  The rules: include/pwpp.h."""
+        occ = np.ascontiguousarray(occupancy, np.int8)
+        o3 = occ.reshape((1,) + occ.shape) if occ.ndim == 2 else occ
+        if o3.ndim != 3:
+            raise ValueError("occupancy: a (frames, ny, nx) or (ny, nx) image expected")
+        frames, ny, nx = o3.shape
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), nx, ny, 0, 0)
+        maps = np.ascontiguousarray(maps, np.int16)
+        m3 = maps.reshape((1,) + maps.shape) if maps.ndim == 2 else maps
+        if m3.ndim != 3 or m3.shape[1:] != (fmap.ny, fmap.nx):
+            raise ValueError("maps: (n_maps, NY, NX) of the map description expected")
+        cand, mof = self._match_host(candidates, frames, map_of_frame)
+        best = np.zeros(frames, MATCH_BEST_DTYPE)
+        scores = np.zeros((frames, cand.shape[1], 2 * int(wy) + 1, 2 * int(wx) + 1), np.int64) if want_scores else None
+        self._check(self._L.pwpp_match_grid(self._h, ctypes.byref(g), frames, MEM_HOST, _hp(o3), _hp(cand), cand.shape[0], cand.shape[1], _hp(mof),
+                                            ctypes.byref(fmap), m3.shape[0], _hp(m3), int(wx), int(wy), _hp(best), _hp(scores)))
+        return (best, scores) if want_scores else best
+
+    def match_grid_device(self, grid, nx, ny, frames, occupancy_ptr, candidates, fmap, n_maps, map_ptr, wx, wy, best_ptr, scores_ptr=0, map_of_frame=None):
+        """match_grid on device memory: addresses of the (frames, ny, nx) int8 occupancy images, the (n_maps, NY, NX) int16 maps
+        (2-byte aligned), the (frames,) rows of 24 bytes and (0: not wanted) the int64 scores, both 8-byte aligned; candidates and
+        map_of_frame stay host arrays.  Enqueued on the handle's stream; complete after synchronize()."""
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), int(nx), int(ny), 0, 0)
+        cand, mof = self._match_host(candidates, frames, map_of_frame)
+        self._check(self._L.pwpp_match_grid(self._h, ctypes.byref(g), int(frames), MEM_DEVICE, _dp(occupancy_ptr), _hp(cand), cand.shape[0], cand.shape[1],
+                                            _hp(mof), ctypes.byref(fmap), int(n_maps), _dp(map_ptr), int(wx), int(wy), _dp(best_ptr), _dp(scores_ptr)))
+
+    def match_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, candidates, fmap, maps, wx, wy, origin_xy=(0.0, 0.0), min_count=1, max_range=0,
+                        frame_first=0, frames=None, map_of_frame=None, ground_only=False, want_scores=False, want_frames=False):
+        """rasterize_obstacles, visibility_grid and match_grid in one call, for frames of the last estimate call: the rows (and
+        scores) match_grid gives for the occupancy bytes of visibility_obstacles; want_frames: then those (frames, ny, nx) int8
+        bytes too, last."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        maps = np.ascontiguousarray(maps, np.int16)
+        m3 = maps.reshape((1,) + maps.shape) if maps.ndim == 2 else maps
+        if m3.ndim != 3 or m3.shape[1:] != (fmap.ny, fmap.nx):
+            raise ValueError("maps: (n_maps, NY, NX) of the map description expected")
+        cand, mof = self._match_host(candidates, frames, map_of_frame)
+        best = np.zeros(max(frames, 0), MATCH_BEST_DTYPE)
+        scores = np.zeros((max(frames, 0), cand.shape[1], 2 * int(wy) + 1, 2 * int(wx) + 1), np.int64) if want_scores else None
+        occ = np.empty(self._grid_shape(g, frames), np.int8) if want_frames else None
+        self._check(self._L.pwpp_match_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
+                                                 int(frame_first), frames, MEM_HOST, _hp(cand), cand.shape[0], cand.shape[1], _hp(mof), ctypes.byref(fmap),
+                                                 m3.shape[0], _hp(m3), int(wx), int(wy), _hp(best), _hp(scores), _hp(occ)))
+        out = (best,) + ((scores,) if want_scores else ()) + ((occ,) if want_frames else ())
+        return out if len(out) > 1 else best
+
+    def match_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, candidates, fmap, n_maps, map_ptr, wx, wy, best_ptr, scores_ptr=0, occupancy_ptr=0,
+                               origin_xy=(0.0, 0.0), min_count=1, max_range=0, frame_first=0, frames=None, map_of_frame=None, ground_only=False):
+        """match_obstacles on device memory: addresses as in match_grid_device, occupancy_ptr the (frames, ny, nx) int8 bytes of the
+        frames (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        cand, mof = self._match_host(candidates, frames, map_of_frame)
+        self._check(self._L.pwpp_match_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
+                                                 int(frame_first), frames, MEM_DEVICE, _hp(cand), cand.shape[0], cand.shape[1], _hp(mof), ctypes.byref(fmap),
+                                                 int(n_maps), _dp(map_ptr), int(wx), int(wy), _dp(best_ptr), _dp(scores_ptr), _dp(occupancy_ptr)))
 
     def box_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_boxes, frame_first=0, frames=None, ground_only=False):
         """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as oriented

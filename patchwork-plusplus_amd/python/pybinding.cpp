@@ -237,6 +237,17 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              py::arg("map"), py::arg("pose"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"),
              py::arg("h_max"), py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0,
              py::arg("shift_x") = 0, py::arg("shift_y") = 0)
+        .def("matchObstacleMap",
+             [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, const std::vector<std::array<double, 6>> &candidates, int wx, int wy, double x0,
+                double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y) {
+                 const PatchWorkpp::ObstacleMatch r =
+                     s.matchObstacleMap(map, candidates.empty() ? nullptr : candidates.front().data(), (int)candidates.size(), wx, wy, x0, y0, cell, nx, ny,
+                                        h_min, h_max, min_count, max_range, origin_x, origin_y);
+                 return py::make_tuple(r.candidate, r.sx, r.sy, r.score, r.cells, std::array<double, 6>{r.pose[0], r.pose[1], r.pose[2], r.pose[3], r.pose[4], r.pose[5]});
+             },
+             py::arg("map"), py::arg("candidates"), py::arg("wx"), py::arg("wy"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"),
+             py::arg("ny"), py::arg("h_min"), py::arg("h_max"), py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0,
+             py::arg("origin_y") = 0.0)
         .def("getObstacleBoxes",
              [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int connectivity,
                 bool ground_only) {
