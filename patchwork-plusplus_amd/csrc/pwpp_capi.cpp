@@ -251,10 +251,8 @@ struct pwpp_handle {
     int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
-    std::vector<uint32_t> fuse_upload;  // the poses, frame lists and shifts of the last fusion call: the source of its upload
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
-    std::vector<uint32_t> match_upload;  // the candidates and the frames' maps of the last scan match: the source of its upload
-    std::vector<int32_t> vis_origins;  // the origin cells of the last visibility call with one origin per frame: the source of its upload
+    std::vector<std::vector<uint32_t>> uploads;  // the tables the last call that uploaded any built for its kernels: the sources of their copies (Staging::add_upload)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
     bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
@@ -1180,30 +1178,37 @@ int copy_output(pwpp_handle *h, Output which, int frame, bool whole_batch, void 
 // 4-byte words, the caller's pointer (null: an optional array that is absent -- a null device pointer, no copy; it keeps the room
 // of its words, so a call declares it with 0 words where none is wanted) and what becomes of it.  PWPP_MEM_DEVICE: the kernels work
 // on the caller's pointers, only the kKept sections lie in the buffer, end() notes the enqueued work.  PWPP_MEM_HOST: every section
-// lies in the buffer, begin() uploads the kIn ones, end() downloads the kOut ones and waits.  `align`: every section starts at a
-// multiple of so many words.
+// lies in the buffer, begin() uploads the kIn ones, end() downloads the kOut ones and waits.  A table the call built on the host for
+// its kernels (add_upload): begin() hands the words to the handle, which owns them until the next call that uploads (the caller's arrays
+// may go on return), and enqueues their copy -- pageable memory, nothing waits.  `align`: every section starts at a multiple of so many words.
 class Staging {
   public:
-    enum Dir { kIn, kOut, kKept };  // read by the kernels | written by them | theirs alone: in the buffer whatever the memory kind
+    enum Dir { kIn, kOut, kKept, kUpload };  // read by the kernels | written by them | theirs alone | built for them: these two in the buffer whatever the memory kind
     Staging(pwpp_handle *h, DevBuf<uint32_t> &buf, int mem, size_t align = 1) : h_(h), buf_(buf), host_(mem == PWPP_MEM_HOST), align_(align) {}
-    // (at most kMaxSections per call; `bytes`: of the caller's array where it is no whole number of words -- a byte image)
+    // (`bytes`: of the caller's array where it is no whole number of words -- a byte image; a section beyond kMaxSections is counted, not stored: begin() refuses the call)
     int add(size_t words, const void *user, Dir dir, size_t bytes = 0) {
-        sec_[n_] = Section{words_, words, bytes ? bytes : words * 4, user, dir};
-        if (dir == kKept || host_) words_ += (words + align_ - 1) / align_ * align_;
+        if (n_ < kMaxSections) sec_[n_] = Section{words_, words, bytes ? bytes : words * 4, user, dir};
+        if (dir == kKept || dir == kUpload || host_) words_ += (words + align_ - 1) / align_ * align_;
         return n_++;
     }
+    int add_upload(std::vector<uint32_t> &&words) {  // (a vector's words stay where they are when it moves)
+        up_.push_back(std::move(words));
+        return add(up_.back().size(), up_.back().data(), kUpload);
+    }
     int begin() {
+        if (n_ > kMaxSections) return fail(PWPP_E_STATE, "the call declares %d staged sections: at most %d are supported", n_, kMaxSections);
         const int rc = buf_.ensure(words_);
         if (rc) return rc;
-        for (int k = 0; k < n_ && host_; ++k)
-            if (sec_[k].dir == kIn && sec_[k].user && sec_[k].words > 0)
+        if (!up_.empty()) h_->uploads.swap(up_);  // (those of the last call that uploaded end with this object)
+        for (int k = 0; k < n_; ++k)
+            if ((sec_[k].dir == kUpload || (host_ && sec_[k].dir == kIn)) && sec_[k].user && sec_[k].words > 0)
                 HIPCHK(hipMemcpyAsync(buf_.p + sec_[k].at, sec_[k].user, sec_[k].bytes, hipMemcpyHostToDevice, h_->stream));
         return PWPP_OK;
     }
     template <class T>
     T *dev(int k) const {  // (after begin(): the buffer may have moved)
         const Section &c = sec_[k];
-        if (c.dir != kKept && (!host_ || !c.user)) return static_cast<T *>(const_cast<void *>(c.user));
+        if (c.dir != kKept && c.dir != kUpload && (!host_ || !c.user)) return static_cast<T *>(const_cast<void *>(c.user));
         return reinterpret_cast<T *>(buf_.p + c.at);
     }
     int end() {
@@ -1222,7 +1227,7 @@ class Staging {
     static constexpr int kMaxSections = 12;
     struct Section {
         size_t at, words, bytes;
-        const void *user;
+        const void *user;  // (kUpload: the words, in up_ and after begin() in the handle)
         Dir dir;
     };
     pwpp_handle *h_;
@@ -1231,6 +1236,7 @@ class Staging {
     const size_t align_;
     size_t words_ = 0;
     int n_ = 0;
+    std::vector<std::vector<uint32_t>> up_;
     Section sec_[kMaxSections];
 };
 constexpr size_t kClusterAlign = 4;  // the cluster buffer's sections start at multiples of 16 bytes (the table's 64-bit sums need 8)
@@ -2411,11 +2417,11 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
     return PWPP_OK;
 }
 
-// ---- operators on an occupancy image: clusters, distances, visibility, fusion --------------------------------------------------
-// Each has two entry points: pwpp_*_grid works on the caller's count image, pwpp_*_obstacles on the one it first rasterises from
-// the last call's non-ground lists.  An operator states its sections once (*_sections: the kernels' working words first, then
-// what the call stages) and its launch once (*_launch: a HIP error code, like a launcher's); an entry point checks its arguments,
-// declares the sections and runs one of the two tails below.
+// ---- operators on an occupancy image: clusters, distances, visibility, fusion, scan match ----------------------------------------
+// Each has two entry points: pwpp_*_grid works on the caller's image, pwpp_*_obstacles on the one it first rasterises from the last call's
+// non-ground lists.  An operator states its sections once (*_sections: the kernels' working words and the tables the call built for them
+// first -- upload sections, copied by Staging::begin() -- then what the call stages) and its launch once (*_launch: the launcher's call alone);
+// an entry point checks its arguments, declares the sections and runs one of three tails: run_on_image, run_on_obstacles, run_on_visibility.
 
 // The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
 // From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
@@ -2637,12 +2643,12 @@ int visibility_origin_count(int n_origins, int frames) {
     return PWPP_OK;
 }
 
-// What the entry points that rasterise first check of the grid, min_count, max_range and the origins in metres, which they turn
-// into cells (`org`: n_origins x {ox, oy}).
-int visibility_origin_args(const pwpp_ground_grid *g, int min_count, const double *origin_xy, int n_origins, int max_range, int frames,
-                           std::vector<int32_t> &org) {
-    int rc = grid_geometry_args(g);  // (the origins need the grid)
-    if (rc) return rc;
+// What the entry points that rasterise first check of the band, the grid, min_count, max_range and the origins in metres, which
+// they turn into cells (`org`: n_origins x {ox, oy}).
+int visibility_origin_args(const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins, int max_range,
+                           int frames, std::vector<int32_t> &org) {
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc || (rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
     if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
     if ((rc = visibility_origin_count(n_origins, frames))) return rc;
@@ -2667,26 +2673,38 @@ VisibilitySections visibility_sections(pwpp_handle *h, Staging &st, int nx, int 
                                        const std::vector<int32_t> &org, int32_t *first, int8_t *occupancy, bool keep = false) {
     VisibilitySections s;
     s.work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
-    s.org = st.add(org.size() > 2 ? org.size() : 0, nullptr, Staging::kKept);
+    s.org = org.size() > 2 ? st.add_upload(std::vector<uint32_t>(org.begin(), org.end())) : st.add(0, nullptr, Staging::kKept);  // (one origin: no words)
     s.count = add_image(st, cells, count, from_raster), s.first = st.add(cells, first, keep && !first ? Staging::kKept : Staging::kOut);
     if (keep && !occupancy) s.occ = st.add((cells + 3) / 4, nullptr, Staging::kKept);
     else s.occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
     return s;
 }
-// One origin travels as an argument; one per frame is copied into its section from the handle's own copy (the caller's array may
-// go on return).
+// (one origin travels as an argument; one per frame lies in its section)
 int visibility_launch(pwpp_handle *h, const Staging &st, const VisibilitySections &s, int nx, int ny, int frames, int min_count,
                       const std::vector<int32_t> &org, int max_range) {
-    const int32_t *d_org = nullptr;
-    if (org.size() > 2) {
-        h->vis_origins = org;
-        int32_t *dst = st.dev<int32_t>(s.org);
-        const hipError_t e = hipMemcpyAsync(dst, h->vis_origins.data(), h->vis_origins.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) return (int)e;
-        d_org = dst;
-    }
-    return pwpp_launch_visibility_grid(nx, ny, frames, st.dev<const int32_t>(s.count), min_count, org[0], org[1], d_org, max_range, h->visibility_path,
-                                       st.dev<int32_t>(s.first), st.dev<int8_t>(s.occ), st.dev<uint32_t>(s.work), h->stream);
+    return pwpp_launch_visibility_grid(nx, ny, frames, st.dev<const int32_t>(s.count), min_count, org[0], org[1], org.size() > 2 ? st.dev<const int32_t>(s.org) : nullptr,
+                                       max_range, h->visibility_path, st.dev<int32_t>(s.first), st.dev<int8_t>(s.occ), st.dev<uint32_t>(s.work), h->stream);
+}
+
+// ... and an entry point that looks before its own operator: then frames >= 1 (the operator's checks come before the handle's, which would name the frames)
+int visibility_first_args(const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins, int max_range, int frames,
+                          std::vector<int32_t> &org) {
+    const int rc = visibility_origin_args(g, h_min, h_max, min_count, origin_xy, n_origins, max_range, frames, org);
+    return rc || frames >= 1 ? rc : fail(PWPP_E_ARG, "%d frames", frames);
+}
+
+// The third tail, for the operators on the visibility's bytes of the obstacle grid: raster, visibility -- count and first kept in the cluster buffer, the
+// bytes too unless the caller asks for them -- and the operator, as one enqueued sequence.  `declare` adds its sections behind the visibility's and returns its launch.
+extern "C++" template <class Declare>  // (the entry points' extern "C" block is open around this namespace)
+int run_on_visibility(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const std::vector<int32_t> &org, int max_range,
+                      int frame_first, int frames, int mem, size_t cells, int8_t *occupancy, Declare declare) {
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const VisibilitySections v = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
+    const auto launch = declare(st, v.occ);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, v.count, -1, [&](const PwppObstacleScan &) {
+        const int lrc = visibility_launch(h, st, v, g->nx, g->ny, frames, min_count, org, max_range);
+        return lrc != 0 ? lrc : launch();
+    });
 }
 }  // namespace
 
@@ -2713,12 +2731,10 @@ int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h
                               int max_range, int frame_first, int frames, int mem, int32_t *first, int8_t *occupancy, int32_t *count) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !first || !origin_xy) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!first ? "first image" : "origin"));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
     std::vector<int32_t> org;
-    if ((rc = visibility_origin_args(g, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    int rc = visibility_origin_args(g, h_min, h_max, min_count, origin_xy, n_origins, max_range, frames, org);
+    if (rc || (rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const VisibilitySections s = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, count, org, first, occupancy);
     return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, -1, [&](const PwppObstacleScan &) {
@@ -2731,6 +2747,29 @@ namespace {
 static_assert(PWPP_OCC_FREE == PWPP_FUSE_FREE && PWPP_OCC_OCCUPIED == PWPP_FUSE_OCCUPIED && PWPP_OCC_UNKNOWN == PWPP_FUSE_UNKNOWN, "the kernel's occupancy bytes");
 static_assert(sizeof(pwpp_fusion_map) == 56, "pwpp_fusion_map is 56 bytes");
 constexpr const char *kFusionWho = "the fusion takes";
+
+// What the operators on a fused map check of the map description's grid and the two cell sizes; `who` as in mem_args, `map_cells`: NX * NY * n_maps.
+int map_grid_args(const pwpp_ground_grid *g, const pwpp_fusion_map *m, int n_maps, const char *who, size_t &map_cells) {
+    if (const int rc = image_args(m->nx, m->ny, n_maps, who, map_cells)) return rc;
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !(m->cell > 0.0) || !std::isfinite(m->cell))
+        return fail(PWPP_E_ARG, "cell sizes %g (frames) and %g (map): finite and positive expected", g->cell, m->cell);
+    return PWPP_OK;
+}
+
+// ... and of the frames' maps (args); checked, the rule answers for frame i
+struct FrameMaps {
+    const int32_t *map_of_frame;  // (null: one map for all, or frame i's is map i)
+    int n_maps;
+    int32_t operator()(int i) const { return map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i); }
+    int args(int frames) const {
+        if (!map_of_frame && n_maps != 1 && n_maps != frames)
+            return fail(PWPP_E_ARG, "null map_of_frame with %d maps for %d frames: 1 map or one per frame expected", n_maps, frames);
+        for (int i = 0; map_of_frame && i < frames; ++i)
+            if (map_of_frame[i] < -1 || map_of_frame[i] >= n_maps)
+                return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
+        return PWPP_OK;
+    }
+};
 
 // What a checked call hands to the kernel besides its images: the geometry, the parameters and the words to upload -- the poses
 // first (8-byte aligned at the section's start), then begin[n_maps + 1], the frame list and the shifts (none: no words).
@@ -2750,20 +2789,15 @@ struct FusionPlan {
 // the frame images' own checks (frames >= 1); fills the plan.  Touches no handle.
 int fusion_args(const pwpp_ground_grid *g, int frames, const double *pose, int n_poses, const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps,
                 const int32_t *shift, const int16_t *map_in, const int16_t *map_out, const int8_t *map_occupancy, FusionPlan &plan) {
-    if (const int rc = image_args(m->nx, m->ny, n_maps, kFusionWho, plan.map_cells)) return rc;
-    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !(m->cell > 0.0) || !std::isfinite(m->cell))
-        return fail(PWPP_E_ARG, "cell sizes %g (frames) and %g (map): finite and positive expected", g->cell, m->cell);
+    if (const int rc = map_grid_args(g, m, n_maps, kFusionWho, plan.map_cells)) return rc;
     if (m->hit < 0 || m->hit > 32767 || m->miss < 0 || m->miss > 32767) return fail(PWPP_E_ARG, "hit %d, miss %d: 0 .. 32767 expected", m->hit, m->miss);
     if (m->l_min < -32768 || m->l_min > 0 || m->l_max < 0 || m->l_max > 32767)
         return fail(PWPP_E_ARG, "clamps l_min %d, l_max %d: -32768 <= l_min <= 0 <= l_max <= 32767 expected", m->l_min, m->l_max);
     if (m->free_at < -32768 || m->free_at >= m->occupied_at || m->occupied_at > 32767)
         return fail(PWPP_E_ARG, "thresholds free_at %d, occupied_at %d: -32768 <= free_at < occupied_at <= 32767 expected", m->free_at, m->occupied_at);
     if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
-    if (!map_of_frame && n_maps != 1 && n_maps != frames)
-        return fail(PWPP_E_ARG, "null map_of_frame with %d maps for %d frames: 1 map or one per frame expected", n_maps, frames);
-    for (int i = 0; map_of_frame && i < frames; ++i)
-        if (map_of_frame[i] < -1 || map_of_frame[i] >= n_maps)
-            return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
+    const FrameMaps map_of{map_of_frame, n_maps};
+    if (const int rc = map_of.args(frames)) return rc;
     bool moved = false;
     for (int k = 0; shift && k < n_maps; ++k) moved = moved || shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0;
     const auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
@@ -2781,7 +2815,6 @@ int fusion_args(const pwpp_ground_grid *g, int frames, const double *pose, int n
     plan.P = PwppFusionParams{m->hit, m->miss, m->l_min, m->l_max, m->occupied_at, m->free_at};
     plan.n_poses = n_poses, plan.n_maps = n_maps, plan.shifted = shift != nullptr;
     // the CSR: a counting sort of the frames by their map keeps each map's frames in ascending order
-    const auto map_of = [&](int i) { return map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i); };
     try {
     std::vector<int32_t> begin((size_t)n_maps + 1, 0);
     for (int i = 0; i < frames; ++i)
@@ -2801,28 +2834,23 @@ int fusion_args(const pwpp_ground_grid *g, int frames, const double *pose, int n
     return PWPP_OK;
 }
 
-// (the uploaded words first; `occ` is the frame bytes' section: the caller's, or the visibility's)
+// (the plan's words first: they move into the staging; `occ` is the frame bytes' section: the caller's, or the visibility's)
 struct FusionSections {
     int up, occ, map_in, map_out, map_occ;
 };
-FusionSections fusion_sections(Staging &st, const FusionPlan &plan, int s_occ, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
+FusionSections fusion_sections(Staging &st, FusionPlan &plan, int s_occ, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
     FusionSections s;
     const size_t map_words = (plan.map_cells + 1) / 2, map_bytes = plan.map_cells * sizeof(int16_t);
-    s.up = st.add(plan.words.size(), nullptr, Staging::kKept);
+    s.up = st.add_upload(std::move(plan.words));
     s.occ = s_occ;
     s.map_in = st.add(map_in ? map_words : 0, map_in, Staging::kIn, map_in ? map_bytes : 0);
     s.map_out = st.add(map_words, map_out, Staging::kOut, map_bytes);
     s.map_occ = st.add(map_occupancy ? (plan.map_cells + 3) / 4 : 0, map_occupancy, Staging::kOut, map_occupancy ? plan.map_cells : 0);
     return s;
 }
-// The words are copied into their section from the handle's own copy (the caller's arrays may go on return), then the kernel.
 int fusion_launch(pwpp_handle *h, const Staging &st, const FusionSections &s, const FusionPlan &plan, int frames) {
-    h->fuse_upload = plan.words;
-    uint32_t *up = st.dev<uint32_t>(s.up);
-    const hipError_t e = hipMemcpyAsync(up, h->fuse_upload.data(), h->fuse_upload.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return (int)e;
-    const int32_t *words = reinterpret_cast<const int32_t *>(up);
-    return pwpp_launch_fuse_grid(&plan.G, &plan.P, frames, st.dev<const int8_t>(s.occ), reinterpret_cast<const double *>(up), plan.n_poses, plan.n_maps,
+    const int32_t *words = st.dev<const int32_t>(s.up);
+    return pwpp_launch_fuse_grid(&plan.G, &plan.P, frames, st.dev<const int8_t>(s.occ), st.dev<const double>(s.up), plan.n_poses, plan.n_maps,
                                  words + plan.at_begin(), words + plan.at_list(), plan.listed, plan.shifted ? words + plan.at_shift() : nullptr,
                                  st.dev<const int16_t>(s.map_in), st.dev<int16_t>(s.map_out), st.dev<int8_t>(s.map_occ), h->fusion_path, h->stream);
 }
@@ -2847,8 +2875,7 @@ int pwpp_fuse_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int me
     return run_on_image(h, st, [&] { return fusion_launch(h, st, s, plan, frames); });
 }
 
-// pwpp_visibility_obstacles and pwpp_fuse_grid on its bytes, enqueued as one sequence.  The count and first images, and the bytes the
-// caller does not ask for, stay in the cluster buffer.
+// pwpp_visibility_obstacles and pwpp_fuse_grid on its bytes (run_on_visibility).
 int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
                         int max_range, int frame_first, int frames, int mem, const double *pose, int n_poses, const int32_t *map_of_frame,
                         const pwpp_fusion_map *m, int n_maps, const int32_t *shift, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy,
@@ -2856,21 +2883,15 @@ int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, 
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !origin_xy || !pose || !m || !map_out)
         return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!origin_xy ? "origin" : (!pose ? "pose" : (!m ? "map description" : "map_out"))));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
     std::vector<int32_t> org;
-    if ((rc = visibility_origin_args(g, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
-    if (frames < 1) return fail(PWPP_E_ARG, "%d frames", frames);
     FusionPlan plan;
-    if ((rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan))) return rc;
+    int rc = visibility_first_args(g, h_min, h_max, min_count, origin_xy, n_origins, max_range, frames, org);
+    if (rc || (rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const VisibilitySections v = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
-    const FusionSections s = fusion_sections(st, plan, v.occ, map_in, map_out, map_occupancy);
-    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, v.count, -1, [&](const PwppObstacleScan &) {
-        const int lrc = visibility_launch(h, st, v, g->nx, g->ny, frames, min_count, org, max_range);
-        return lrc != 0 ? lrc : fusion_launch(h, st, s, plan, frames);
+    return run_on_visibility(h, g, h_min, h_max, min_count, org, max_range, frame_first, frames, mem, cells, occupancy, [&](Staging &st, int s_occ) {
+        const FusionSections s = fusion_sections(st, plan, s_occ, map_in, map_out, map_occupancy);
+        return [&, s] { return fusion_launch(h, st, s, plan, frames); };
     });
 }
 
@@ -2897,9 +2918,7 @@ struct MatchPlan {
 // images' own checks (frames >= 1); fills the plan.  Touches no handle.
 int match_args(const pwpp_ground_grid *g, int frames, const double *candidates, int n_sets, int n_candidates, const int32_t *map_of_frame,
                const pwpp_fusion_map *m, int n_maps, int wx, int wy, const int64_t *scores, MatchPlan &plan) {
-    if (const int rc = image_args(m->nx, m->ny, n_maps, kMatchWho, plan.map_cells)) return rc;
-    if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !(m->cell > 0.0) || !std::isfinite(m->cell))
-        return fail(PWPP_E_ARG, "cell sizes %g (frames) and %g (map): finite and positive expected", g->cell, m->cell);
+    if (const int rc = map_grid_args(g, m, n_maps, kMatchWho, plan.map_cells)) return rc;
     if (n_candidates < 1 || n_candidates > PWPP_MATCH_MAX_CANDIDATES) return fail(PWPP_E_ARG, "%d candidates: 1 .. 256 expected", n_candidates);
     if (n_sets < 1 || (n_sets != 1 && n_sets != frames))
         return fail(PWPP_E_ARG, "%d candidate sets for %d frames: 1 or one per frame expected", n_sets, frames);
@@ -2910,11 +2929,8 @@ int match_args(const pwpp_ground_grid *g, int frames, const double *candidates, 
     const int64_t per_pair = (int64_t)(2 * wx + 1) * (int64_t)(2 * wy + 1);  // (<= 129^2; frames x candidates <= 2^24)
     if (scores && (int64_t)frames * (int64_t)n_candidates * per_pair > ((int64_t)1 << 31))
         return fail(PWPP_E_ARG, "%d frames x %d candidates x %lld shifts: the scores exceed 2^31 elements", frames, n_candidates, (long long)per_pair);
-    if (!map_of_frame && n_maps != 1 && n_maps != frames)
-        return fail(PWPP_E_ARG, "null map_of_frame with %d maps for %d frames: 1 map or one per frame expected", n_maps, frames);
-    for (int i = 0; map_of_frame && i < frames; ++i)
-        if (map_of_frame[i] < -1 || map_of_frame[i] >= n_maps)
-            return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
+    const FrameMaps map_of{map_of_frame, n_maps};
+    if (const int rc = map_of.args(frames)) return rc;
 
     plan.G = PwppMatchGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
     pwpp_fuse_reciprocal(m->cell, plan.G.inv_CELL);
@@ -2926,10 +2942,7 @@ int match_args(const pwpp_ground_grid *g, int frames, const double *candidates, 
         return fail(PWPP_E_NOMEM, "no host memory for %d candidate sets of %d and %d frames", n_sets, n_candidates, frames);
     }
     std::memcpy(plan.words.data(), candidates, (size_t)n_sets * (size_t)n_candidates * 6 * sizeof(double));
-    for (int i = 0; i < frames; ++i) {
-        const int32_t k = map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i);
-        std::memcpy(plan.words.data() + plan.at_maps() + (size_t)i, &k, sizeof(k));
-    }
+    for (int i = 0; i < frames; ++i) plan.words[plan.at_maps() + (size_t)i] = (uint32_t)map_of(i);
     return PWPP_OK;
 }
 
@@ -2941,14 +2954,14 @@ int match_alignment_args(int mem, const void *best, const void *scores) {
     return PWPP_OK;
 }
 
-// (the uploaded words and the kernels' working words first -- cell list, counts and workgroup bests are kKept like every operator's
+// (the plan's words, which move into the staging, and the kernels' working words first -- cell list, counts and workgroup bests are kKept like every operator's
 // work words: theirs alone, in the buffer whatever the memory kind; `occ` is the frame bytes' section: the caller's, or the visibility's)
 struct MatchSections {
     int up, work, occ, map, best, scores;
 };
-MatchSections match_sections(Staging &st, const MatchPlan &plan, int frames, int s_occ, const int16_t *map, pwpp_match_best *best, int64_t *scores) {
+MatchSections match_sections(Staging &st, MatchPlan &plan, int frames, int s_occ, const int16_t *map, pwpp_match_best *best, int64_t *scores) {
     MatchSections s;
-    s.up = st.add(plan.words.size(), nullptr, Staging::kKept);
+    s.up = st.add_upload(std::move(plan.words));
     s.work = st.add(pwpp_match_work_words(plan.G.nx, plan.G.ny, frames, plan.n_candidates, plan.wx, plan.wy), nullptr, Staging::kKept);
     s.occ = s_occ;
     s.map = st.add((plan.map_cells + 1) / 2, map, Staging::kIn, plan.map_cells * sizeof(int16_t));
@@ -2956,15 +2969,9 @@ MatchSections match_sections(Staging &st, const MatchPlan &plan, int frames, int
     s.scores = st.add(plan.score_count * 2, scores, Staging::kOut);
     return s;
 }
-// The words are copied into their section from the handle's own copy (the caller's arrays may go on return; the plan's vector moves
-// into the handle: nothing is allocated here), then the kernels.
-int match_launch(pwpp_handle *h, const Staging &st, const MatchSections &s, MatchPlan &plan, int frames) {
-    h->match_upload.swap(plan.words);
-    uint32_t *up = st.dev<uint32_t>(s.up);
-    const hipError_t e = hipMemcpyAsync(up, h->match_upload.data(), h->match_upload.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return (int)e;
-    return pwpp_launch_match_grid(&plan.G, frames, st.dev<const int8_t>(s.occ), reinterpret_cast<const double *>(up), plan.n_sets, plan.n_candidates,
-                                  reinterpret_cast<const int32_t *>(up) + plan.at_maps(), plan.n_maps, st.dev<const int16_t>(s.map), plan.wx, plan.wy,
+int match_launch(pwpp_handle *h, const Staging &st, const MatchSections &s, const MatchPlan &plan, int frames) {
+    return pwpp_launch_match_grid(&plan.G, frames, st.dev<const int8_t>(s.occ), st.dev<const double>(s.up), plan.n_sets, plan.n_candidates,
+                                  st.dev<const int32_t>(s.up) + plan.at_maps(), plan.n_maps, st.dev<const int16_t>(s.map), plan.wx, plan.wy,
                                   st.dev<void>(s.best), st.dev<int64_t>(s.scores), st.dev<uint32_t>(s.work), h->match_path, h->stream);
 }
 }  // namespace
@@ -2990,8 +2997,7 @@ int pwpp_match_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int m
     return run_on_image(h, st, [&] { return match_launch(h, st, s, plan, frames); });
 }
 
-// pwpp_visibility_obstacles and pwpp_match_grid on its bytes, enqueued as one sequence.  The count and first images, and the bytes the
-// caller does not ask for, stay in the cluster buffer.
+// pwpp_visibility_obstacles and pwpp_match_grid on its bytes (run_on_visibility).
 int pwpp_match_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
                          int max_range, int frame_first, int frames, int mem, const double *candidates, int n_sets, int n_candidates,
                          const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps, const int16_t *map, int wx, int wy, pwpp_match_best *best,
@@ -3000,22 +3006,16 @@ int pwpp_match_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
     if (!g || !origin_xy || !candidates || !m || !map || !best)
         return fail(PWPP_E_ARG, "null %s",
                     !g ? "grid" : (!origin_xy ? "origin" : (!candidates ? "candidates" : (!m ? "map description" : (!map ? "map" : "best rows")))));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
     std::vector<int32_t> org;
-    if ((rc = visibility_origin_args(g, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
-    if (frames < 1) return fail(PWPP_E_ARG, "%d frames", frames);
     MatchPlan plan;
-    if ((rc = match_args(g, frames, candidates, n_sets, n_candidates, map_of_frame, m, n_maps, wx, wy, scores, plan))) return rc;
+    int rc = visibility_first_args(g, h_min, h_max, min_count, origin_xy, n_origins, max_range, frames, org);
+    if (rc || (rc = match_args(g, frames, candidates, n_sets, n_candidates, map_of_frame, m, n_maps, wx, wy, scores, plan))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     if ((rc = match_alignment_args(mem, best, scores))) return rc;
-    Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const VisibilitySections v = visibility_sections(h, st, g->nx, g->ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
-    const MatchSections s = match_sections(st, plan, frames, v.occ, map, best, scores);
-    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, v.count, -1, [&](const PwppObstacleScan &) {
-        const int lrc = visibility_launch(h, st, v, g->nx, g->ny, frames, min_count, org, max_range);
-        return lrc != 0 ? lrc : match_launch(h, st, s, plan, frames);
+    return run_on_visibility(h, g, h_min, h_max, min_count, org, max_range, frame_first, frames, mem, cells, occupancy, [&](Staging &st, int s_occ) {
+        const MatchSections s = match_sections(st, plan, frames, s_occ, map, best, scores);
+        return [&, s] { return match_launch(h, st, s, plan, frames); };
     });
 }
 

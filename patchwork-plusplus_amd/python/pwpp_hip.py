@@ -303,6 +303,28 @@ def _count_image(count):
     return c3, count.shape
 
 
+def _occupancy_image(occupancy, grid):
+    """(the (frames, ny, nx) int8 view, frames, its GroundGrid) of a (frames, ny, nx) or (ny, nx) occupancy image on the grid (x0, y0, cell)."""
+    occ = np.ascontiguousarray(occupancy, np.int8)
+    o3 = occ.reshape((1,) + occ.shape) if occ.ndim == 2 else occ
+    if o3.ndim != 3:
+        raise ValueError("occupancy: a (frames, ny, nx) or (ny, nx) image expected")
+    return o3, o3.shape[0], GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), o3.shape[2], o3.shape[1], 0, 0)
+
+
+def _maps_image(maps, fmap):
+    """The (n_maps, NY, NX) int16 view of the (n_maps, NY, NX) or (NY, NX) maps the FusionMap `fmap` describes."""
+    maps = np.ascontiguousarray(maps, np.int16)
+    m3 = maps.reshape((1,) + maps.shape) if maps.ndim == 2 else maps
+    if m3.ndim != 3 or m3.shape[1:] != (fmap.ny, fmap.nx):
+        raise ValueError("maps: (n_maps, NY, NX) of the map description expected")
+    return m3
+
+
+def _host(a, dtype, *shape):  # a small host array the library reads, None staying None
+    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype).reshape(shape))
+
+
 def _transforms(T):
     """(k, 12) float32 from (12,), (3, 4), (k, 12) or (k, 3, 4)."""
     T = np.asarray(T, dtype=np.float32)
@@ -791,6 +813,9 @@ class Handle:
             frames = self.device_view().frames - frame_first
         return GroundGrid(float(x0), float(y0), float(cell), int(nx), int(ny), GRID_GROUND_ONLY if ground_only else 0, 0), int(frames)
 
+    def _look(self, x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy):  # _grid, and the (n_origins, 2) float64 positions of the sensor
+        return self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only) + (_host(origin_xy, np.float64, -1, 2),)
+
     @staticmethod
     def _grid_shape(g, frames):
         """The shape of the images of a call over frames of the grid g; a bad argument, left to the library to name, counts as 0."""
@@ -976,9 +1001,8 @@ class Handle:
         """rasterize_obstacles and visibility_grid in one call, for frames of the last estimate call.  origin_xy: the sensor's
         position in metres in the model's frame, (x, y) for every frame or (frames, 2).  Returns (first, occupancy) as
         visibility_grid does for the (frames, ny, nx) count image; want_count: then that int32 count image too."""
-        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
         shape = self._grid_shape(g, frames)
-        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
         first = np.empty(shape, np.int32)
         occupancy = np.empty(shape, np.int8) if want_occupancy else None
         count = np.empty(shape, np.int32) if want_count else None
@@ -990,8 +1014,7 @@ class Handle:
                                     frame_first=0, frames=None, ground_only=False):
         """visibility_obstacles into device memory: addresses as in visibility_grid_device, count_ptr the int32 count image (0: not
         wanted); origin_xy stays a host array.  Enqueued on the handle's stream; complete after synchronize()."""
-        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
         self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count),
                                                       _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
                                                       _dp(first_ptr), _dp(occupancy_ptr), _dp(count_ptr)))
@@ -999,10 +1022,7 @@ class Handle:
     @staticmethod
     def _fusion_host(pose, map_of_frame, shift):
         """The host arrays every fusion call takes: (n_poses, 6) float64, (frames,) int32 or None, (n_maps, 2) int32 or None."""
-        pose = np.ascontiguousarray(np.asarray(pose, np.float64).reshape(-1, 6))
-        mof = None if map_of_frame is None else np.ascontiguousarray(map_of_frame, np.int32).reshape(-1)
-        shift = None if shift is None else np.ascontiguousarray(np.asarray(shift, np.int32).reshape(-1, 2))
-        return pose, mof, shift
+        return _host(pose, np.float64, -1, 6), _host(map_of_frame, np.int32, -1), _host(shift, np.int32, -1, 2)
 
     def fuse_grid(self, occupancy, grid, pose, fmap, n_maps=1, map_in=None, map_of_frame=None, shift=None, want_occupancy=True, map_out=None):
         """Fuses the (frames, ny, nx) or (ny, nx) int8 occupancy images on the grid `grid` = (x0, y0, cell) into n_maps int16 log-odds
@@ -1011,12 +1031,7 @@ class Handle:
         shift: None or (n_maps, 2) cells {sx, sy}; map_in: the (n_maps, NY, NX) int16 maps to start from, None: zero; map_out: the
         array to write (map_in itself is allowed without a shift), None: a new one.  Works before any estimate call.  Returns
         (map_out, map_occupancy) of shape (n_maps, NY, NX), the int8 bytes None when not wanted.  The rules: include/pwpp.h."""
-        occ = np.ascontiguousarray(occupancy, np.int8)
-        o3 = occ.reshape((1,) + occ.shape) if occ.ndim == 2 else occ
-        if o3.ndim != 3:
-            raise ValueError("occupancy: a (frames, ny, nx) or (ny, nx) image expected")
-        frames, ny, nx = o3.shape
-        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), nx, ny, 0, 0)
+        o3, frames, g = _occupancy_image(occupancy, grid)
         pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
         shape = self._grid_shape(fmap, n_maps)
         if map_in is not None:
@@ -1042,8 +1057,7 @@ class Handle:
         """rasterize_obstacles, visibility_grid and fuse_grid in one call, for frames of the last estimate call: (map_out,
         map_occupancy) as fuse_grid gives them for the occupancy bytes of visibility_obstacles; want_frames: then those
         (frames, ny, nx) int8 bytes too."""
-        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
         pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
         shape = self._grid_shape(fmap, n_maps)
         if map_in is not None:
@@ -1061,8 +1075,7 @@ class Handle:
                               ground_only=False):
         """fuse_obstacles into device memory: addresses as in fuse_grid_device, occupancy_ptr the (frames, ny, nx) int8 bytes of the
         frames (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
-        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
         pose, mof, shift = self._fusion_host(pose, map_of_frame, shift)
         self._check(self._L.pwpp_fuse_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
                                                 int(frame_first), frames, MEM_DEVICE, _hp(pose), len(pose), _hp(mof), ctypes.byref(fmap), int(n_maps),
@@ -1075,8 +1088,7 @@ class Handle:
         cand = cand.reshape((1,) + cand.shape) if cand.ndim == 2 else cand
         if cand.ndim != 3 or cand.shape[2] != 6:
             raise ValueError("candidates: (n_candidates, 6) or (n_sets, n_candidates, 6) expected")
-        mof = None if map_of_frame is None else np.ascontiguousarray(map_of_frame, np.int32).reshape(-1)
-        return cand, mof
+        return cand, _host(map_of_frame, np.int32, -1)
 
     def match_grid(self, occupancy, grid, candidates, fmap, maps, wx, wy, map_of_frame=None, want_scores=False):
         """Matches the (frames, ny, nx) or (ny, nx) int8 occupancy images on the grid `grid` = (x0, y0, cell) against the
@@ -1085,16 +1097,8 @@ class Handle:
         [-wx, wx] x [-wy, wy] map cells, the sum of the map under the frame's occupied cells.  map_of_frame as in fuse_grid.
         Works before any estimate call.  Returns the (frames,) MATCH_BEST_DTYPE rows; want_scores: (rows, scores) with the int64
         (frames, n_candidates, 2 wy + 1, 2 wx + 1) sums.  The rules: include/pwpp.h."""
-        occ = np.ascontiguousarray(occupancy, np.int8)
-        o3 = occ.reshape((1,) + occ.shape) if occ.ndim == 2 else occ
-        if o3.ndim != 3:
-            raise ValueError("occupancy: a (frames, ny, nx) or (ny, nx) image expected")
-        frames, ny, nx = o3.shape
-        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), nx, ny, 0, 0)
-        maps = np.ascontiguousarray(maps, np.int16)
-        m3 = maps.reshape((1,) + maps.shape) if maps.ndim == 2 else maps
-        if m3.ndim != 3 or m3.shape[1:] != (fmap.ny, fmap.nx):
-            raise ValueError("maps: (n_maps, NY, NX) of the map description expected")
+        o3, frames, g = _occupancy_image(occupancy, grid)
+        m3 = _maps_image(maps, fmap)
         cand, mof = self._match_host(candidates, frames, map_of_frame)
         best = np.zeros(frames, MATCH_BEST_DTYPE)
         scores = np.zeros((frames, cand.shape[1], 2 * int(wy) + 1, 2 * int(wx) + 1), np.int64) if want_scores else None
@@ -1116,12 +1120,8 @@ class Handle:
         """rasterize_obstacles, visibility_grid and match_grid in one call, for frames of the last estimate call: the rows (and
         scores) match_grid gives for the occupancy bytes of visibility_obstacles; want_frames: then those (frames, ny, nx) int8
         bytes too, last."""
-        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
-        maps = np.ascontiguousarray(maps, np.int16)
-        m3 = maps.reshape((1,) + maps.shape) if maps.ndim == 2 else maps
-        if m3.ndim != 3 or m3.shape[1:] != (fmap.ny, fmap.nx):
-            raise ValueError("maps: (n_maps, NY, NX) of the map description expected")
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
+        m3 = _maps_image(maps, fmap)
         cand, mof = self._match_host(candidates, frames, map_of_frame)
         best = np.zeros(max(frames, 0), MATCH_BEST_DTYPE)
         scores = np.zeros((max(frames, 0), cand.shape[1], 2 * int(wy) + 1, 2 * int(wx) + 1), np.int64) if want_scores else None
@@ -1136,8 +1136,7 @@ class Handle:
                                origin_xy=(0.0, 0.0), min_count=1, max_range=0, frame_first=0, frames=None, map_of_frame=None, ground_only=False):
         """match_obstacles on device memory: addresses as in match_grid_device, occupancy_ptr the (frames, ny, nx) int8 bytes of the
         frames (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
-        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
-        org = np.ascontiguousarray(np.asarray(origin_xy, np.float64).reshape(-1, 2))
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
         cand, mof = self._match_host(candidates, frames, map_of_frame)
         self._check(self._L.pwpp_match_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
                                                  int(frame_first), frames, MEM_DEVICE, _hp(cand), cand.shape[0], cand.shape[1], _hp(mof), ctypes.byref(fmap),

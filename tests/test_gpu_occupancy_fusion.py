@@ -4,8 +4,8 @@ frame images from one cell to 64 x 64 with 1, 2 and 5 frames per map, every kind
 map_of_frame, shifts of both signs and beyond the map, map_in absent and in place, the parameters at their extremes, the order
 example and the composition of two calls, host and device memory with misaligned device arrays in poisoned surroundings, both
 values of the option "fusion_path" on cell sizes that are powers of two (where path 0 multiplies) and on ones that are not,
-pwpp_fuse_obstacles against its three steps on a KITTI frame, and that asking changes nothing
-else."""
+pwpp_fuse_obstacles against its three steps on a KITTI frame, two device calls back to back with different origins and poses, and
+that asking changes nothing else."""
 import ctypes
 import functools
 
@@ -350,6 +350,30 @@ def test_three_frames_as_a_sequence_and_in_lock_step():
     assert (lock[0][0] > 0).sum() >= 3 and (lock[0][1:] <= 0).all()  # the empty and the all-unref frame hold no obstacle
     sub = h.fuse_obstacles(*grid, *BAND, poses[1:], fm, 2, None, xy[1:], frame_first=1, frames=2)  # entry i belongs to frame frame_first + i
     assert sub[0].tobytes() == lock[0][1:].tobytes() and sub[1].tobytes() == lock[1][1:].tobytes()
+
+
+def test_two_device_calls_back_to_back_each_fuse_under_their_own_tables():
+    """The origins and the poses of a call are uploaded from the handle's own copy, and the second call replaces that copy while
+    the first may still be in flight: two calls with an origin and a pose per frame, different ones, into different maps, one
+    synchronize() after both."""
+    import torch
+    h = pwpp_hip.Handle()
+    h.estimate_ground_batch(three_frames(), mode=pwpp_hip.MODE_FRESH)
+    grid = (-16.0, -16.0, 0.5, 64, 64)
+    mgrid = (-20.0, -18.0, 0.5, 80, 72)
+    fm = fmap_of(mgrid, fr.PAR)
+    calls = [(np.array([[0.0, 0.0], [3.3, -2.1], [-15.9, 15.9]]), [fr.rigid(0.1 * f, 0.5 * f, -0.25 * f) for f in range(3)]),
+             (np.array([[-4.2, 1.1], [0.0, 0.0], [2.5, 2.5]]), [fr.rigid(-0.3 - 0.2 * f, 1.5 - f, 0.75 * f) for f in range(3)])]
+    want = [fr.fuse(h.visibility_obstacles(*grid, *BAND, xy)[1], grid[:3], poses, mgrid, fr.PAR, 3) for xy, poses in calls]
+    assert want[0][0].tobytes() != want[1][0].tobytes() and (want[0][0][0] > 0).sum() >= 3
+    cells = 3 * mgrid[3] * mgrid[4]
+    out = [(torch.full((cells,), -7, dtype=torch.int16, device="cuda"), torch.full((cells,), -7, dtype=torch.int8, device="cuda")) for _ in calls]
+    torch.cuda.synchronize()
+    for (xy, poses), (dmap, dbyte) in zip(calls, out):
+        h.fuse_obstacles_device(*grid, *BAND, poses, fm, 3, 0, dmap.data_ptr(), dbyte.data_ptr(), 0, xy)
+    h.synchronize()
+    for i, (dmap, dbyte) in enumerate(out):
+        check((dmap.cpu().numpy().reshape(want[i][0].shape), dbyte.cpu().numpy().reshape(want[i][1].shape)), want[i], "call %d of two" % i)
 
 
 # ---- workspace ------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ shifts than a workgroup has lanes and (64, 64) once, 1 to 33 candidates of every
 ratios of which one divides, every form of map_of_frame, a sum beyond int32, all three values of the option "match_path" with
 rectangles of the map that fit the LDS and ones that do not, host and
 device memory with a misaligned map and bytes in poisoned surroundings, scores absent, pwpp_match_obstacles against its three steps,
-the workspace, and that asking changes nothing else."""
+two device calls back to back with different origins and candidates, the workspace, and that asking changes nothing else."""
 import ctypes
 import functools
 
@@ -367,6 +367,33 @@ def test_match_obstacles_is_rasterize_plus_visibility_plus_match_grid():
     rocc = docc.cpu().numpy()
     assert rocc[1:1 + vocc.size].tobytes() == vocc.tobytes() and rocc[0] == -7 and (rocc[1 + vocc.size:] == -7).all()
     assert _everything(h, 3) == before, "the match changed the results of the call it reads"
+
+
+def test_two_device_calls_back_to_back_each_match_their_own_tables():
+    """The origins, the candidates and the frames' maps of a call are uploaded from the handle's own copy, and the second call
+    replaces that copy while the first may still be in flight: two calls with an origin and a candidate set per frame, different
+    ones, one synchronize() after both."""
+    import torch
+    h = pwpp_hip.Handle()
+    h.estimate_ground_batch(three_frames(), mode=pwpp_hip.MODE_FRESH)
+    grid = (-16.0, -16.0, 0.5, 64, 64)
+    mgrid = (-20.0, -18.0, 0.5, 80, 72)
+    fm = fmap_of(mgrid)
+    xy = np.array([[0.0, 0.0], [3.3, -2.1], [-15.9, 15.9]])
+    maps, _ = h.fuse_obstacles(*grid, *BAND, [fr.rigid(0.1 * f, 0.5 * f, -0.25 * f) for f in range(3)], fm, 3, None, xy)
+    calls = [(xy, np.array([pwpp_hip.yaw_candidates(fr.rigid(0.1 * f + 0.04, 0.5 * f + 1.0, -0.25 * f - 0.5), 0.02, 5) for f in range(3)])),
+             (xy[::-1].copy(), np.array([pwpp_hip.yaw_candidates(fr.rigid(0.1 * f - 0.03, 0.5 * f - 1.5, -0.25 * f + 1.0), 0.03, 5) for f in range(3)]))]
+    want = [mr.match(h.visibility_obstacles(*grid, *BAND, o)[1], grid[:3], cand, mgrid, maps, 4, 3) for o, cand in calls]
+    assert want[0][1].tobytes() != want[1][1].tobytes() and want[0][0]["cells"][0] >= 3
+    n_scores = 3 * 5 * 7 * 9
+    dmap = torch.from_numpy(maps.reshape(-1).copy()).cuda()
+    out = [(torch.full((9,), -7, dtype=torch.int64, device="cuda"), torch.full((n_scores,), -7, dtype=torch.int64, device="cuda")) for _ in calls]
+    torch.cuda.synchronize()
+    for (o, cand), (dbest, dscores) in zip(calls, out):
+        h.match_obstacles_device(*grid, *BAND, cand, fm, 3, dmap.data_ptr(), 4, 3, dbest.data_ptr(), dscores.data_ptr(), 0, o)
+    h.synchronize()
+    for i, (dbest, dscores) in enumerate(out):
+        check((np.frombuffer(dbest.cpu().numpy().tobytes(), mr.BEST_DTYPE), dscores.cpu().numpy().reshape(want[i][1].shape)), want[i], "call %d of two" % i)
 
 
 # ---- workspace ------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """No-GPU checks of what the post-call map queries share (pwpp_rasterize_obstacles, pwpp_label_obstacles, pwpp_box_obstacles,
-pwpp_distance_obstacles, pwpp_visibility_obstacles; and pwpp_label_grid, pwpp_distance_grid, pwpp_visibility_grid on a caller's
-image): the argument checks they have in common, fed to all of a kind through one loop -- the same code and the same message
-fragment from each -- and, with the restatements, that the batch of tests/test_gpu_map_query_ranges.py has clusters and boxes in the frames its
+pwpp_distance_obstacles, pwpp_visibility_obstacles, pwpp_fuse_obstacles, pwpp_match_obstacles; pwpp_label_grid, pwpp_distance_grid,
+pwpp_visibility_grid on a caller's image; the map side of pwpp_fuse_* and pwpp_match_*): the argument checks they have in common, fed
+to all of a kind through one loop -- the same code and the same message fragment from each -- and, with the restatements, that the batch of tests/test_gpu_map_query_ranges.py has clusters and boxes in the frames its
 comparison is about."""
 import ctypes
 import os
@@ -44,13 +44,24 @@ SHARED_BAD_INPUTS = [
 ]
 
 
-def test_shared_bad_inputs_are_named_alike_by_all_five_entry_points(lib):
+# The fused maps of the calls below: one of 4 x 4 cells of 1 m, and its int16 cells.
+def fusion_map(**fields):
+    return pwpp_hip.FusionMap(**dict(dict(x0=0.0, y0=0.0, cell=1.0, nx=4, ny=4, hit=40, miss=20, l_min=-200, l_max=350, occupied_at=60, free_at=-40), **fields))
+
+
+def test_shared_bad_inputs_are_named_alike_by_all_seven_entry_points(lib):
     img = np.zeros(16, np.int32)
     box = np.zeros(4, ob.BOX_DTYPE)
-    xy = np.array([0.5, 0.5], np.float64)  # (the sensor of pwpp_visibility_obstacles: inside every grid of the table that has cells)
+    xy = np.array([0.5, 0.5], np.float64)  # (the sensor of the three that look first: inside every grid of the table that has cells)
+    pose = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], np.float64)  # (the one pose of the fusion, the one candidate of the match)
+    maps, best, fm = np.zeros(16, np.int16), np.zeros(1, pwpp_hip.MATCH_BEST_DTYPE), ctypes.byref(fusion_map())
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # (never dereferenced: these checks come first)
     entry_points = {
+        "pwpp_fuse_obstacles": lambda g, band, mem: lib.pwpp_fuse_obstacles(fake, g, band[0], band[1], 1, vp(xy), 1, 0, 0, 1, mem, vp(pose), 1, None, fm, 1,
+                                                                            None, None, vp(maps), None, None),
+        "pwpp_match_obstacles": lambda g, band, mem: lib.pwpp_match_obstacles(fake, g, band[0], band[1], 1, vp(xy), 1, 0, 0, 1, mem, vp(pose), 1, 1, None, fm, 1,
+                                                                              vp(maps), 1, 1, vp(best), None, None),
         "pwpp_rasterize_obstacles": lambda g, band, mem: lib.pwpp_rasterize_obstacles(fake, g, band[0], band[1], 0, 1, mem, vp(img), None, None),
         "pwpp_label_obstacles": lambda g, band, mem: lib.pwpp_label_obstacles(fake, g, band[0], band[1], 1, 8, 0, 1, mem, vp(img), None, None, None, None, 0, None),
         "pwpp_box_obstacles": lambda g, band, mem: lib.pwpp_box_obstacles(fake, g, band[0], band[1], 0, 1, mem, vp(img), vp(box), 4),
@@ -127,3 +138,43 @@ def test_the_batch_has_clusters_and_boxes_in_the_sub_range(oracle_built):
         if f >= FIRST:
             assert 2 <= n <= MAX_ROWS and (rows["points"][:n] > 0).all() and rows["points"].sum() == count[label >= 0].sum() > 50
     assert lists[2] > max(lists[:2]) and lists[0] != lists[1]
+
+
+# What the fusion and the scan match check alike of the map side of a call of 3 frames: (fields of the map description, n_maps,
+# map_of_frame), a fragment of the message.  The one message with a subject is the side limit's.
+SHARED_BAD_MAPS = [
+    ("a map of 0 cells a side", dict(nx=0), 1, None, b"1 frames of 0 x 4 cells"),
+    ("a map of 32769 cells a side", dict(nx=32769), 1, None, b"32769 x 4 cells:  at most 32768 a side"),
+    ("map cell 0", dict(cell=0.0), 1, None, b"cell sizes 1 (frames) and 0 (map): finite and positive expected"),
+    ("map cell NaN", dict(cell=np.nan), 1, None, b"(map): finite and positive expected"),
+    ("2 maps for 3 frames, null map_of_frame", {}, 2, None, b"null map_of_frame with 2 maps for 3 frames: 1 map or one per frame expected"),
+    ("map_of_frame entry n_maps", {}, 2, [0, 2, 1], b"map_of_frame 1 names map 2: -1 (skipped) .. 1 expected"),
+    ("map_of_frame entry -2", {}, 2, [0, -1, -2], b"map_of_frame 2 names map -2: -1 (skipped) .. 1 expected"),
+]
+SUBJECTS = {"pwpp_fuse_grid": b"the fusion takes", "pwpp_fuse_obstacles": b"the fusion takes", "pwpp_match_grid": b"the scan match takes",
+            "pwpp_match_obstacles": b"the scan match takes"}
+
+
+def test_shared_bad_maps_are_named_alike_by_the_fusion_and_the_scan_match(lib):
+    frames, H = 3, pwpp_hip.MEM_HOST
+    occ, xy = np.zeros(frames * 16, np.int8), np.array([0.5, 0.5], np.float64)
+    pose = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], np.float64)  # (the one pose of the fusion, the one candidate of the match)
+    maps, best = np.zeros(2 * 16, np.int16), np.zeros(frames, pwpp_hip.MATCH_BEST_DTYPE)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # (never dereferenced: these checks come first)
+    g = ctypes.byref(pwpp_hip.GroundGrid(x0=0.0, y0=0.0, cell=1.0, nx=4, ny=4, flags=0, pad_=0))
+    entry_points = {
+        "pwpp_fuse_grid": lambda m, n_maps, mof: lib.pwpp_fuse_grid(fake, g, frames, H, vp(occ), vp(pose), 1, mof, m, n_maps, None, None, vp(maps), None),
+        "pwpp_fuse_obstacles": lambda m, n_maps, mof: lib.pwpp_fuse_obstacles(fake, g, 0.2, 2.5, 1, vp(xy), 1, 0, 0, frames, H, vp(pose), 1, mof, m, n_maps,
+                                                                              None, None, vp(maps), None, None),
+        "pwpp_match_grid": lambda m, n_maps, mof: lib.pwpp_match_grid(fake, g, frames, H, vp(occ), vp(pose), 1, 1, mof, m, n_maps, vp(maps), 1, 1, vp(best), None),
+        "pwpp_match_obstacles": lambda m, n_maps, mof: lib.pwpp_match_obstacles(fake, g, 0.2, 2.5, 1, vp(xy), 1, 0, 0, frames, H, vp(pose), 1, 1, mof, m, n_maps,
+                                                                                vp(maps), 1, 1, vp(best), None, None),
+    }
+    for what, fields, n_maps, mof, sentence in SHARED_BAD_MAPS:
+        mof = None if mof is None else np.array(mof, np.int32)
+        said = set()
+        for name, call in entry_points.items():
+            assert call(ctypes.byref(fusion_map(**fields)), n_maps, None if mof is None else vp(mof)) == E_ARG, "%s: %s" % (name, what)
+            said.add(lib.pwpp_last_error().replace(SUBJECTS[name], b""))
+        assert len(said) == 1 and sentence in said.pop(), "%s: %s" % (what, lib.pwpp_last_error())
