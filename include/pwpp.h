@@ -867,6 +867,93 @@ PWPP_API int pwpp_match_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, flo
                                   int8_t *occupancy /* the per-frame bytes, may be NULL: kept in the handle's buffer */);
 PWPP_API int pwpp_match_pose(const double candidate[6], double CELL, int sx, int sy, double out[6]);  /* host only */
 
+/* ---- persistent elevation maps: per-frame ground heights fused over time (pwpp_fuse_height_grid, pwpp_fuse_ground) ----------------
+ * The elevation image of a frame (pwpp_rasterize_ground) is NaN wherever the scan supports no ground model: bins with too few
+ * points, shadowed sectors, everything beyond max_range.  A map a planner can drive on keeps the ground height under cells that
+ * were seen three frames ago: the running mean of the heights observed per cell of a FIXED frame -- the ground half of the 2.5-D
+ * map whose obstacle half pwpp_fuse_* keeps.  Integer state and a fixed arithmetic, so the fused map is a function of its inputs
+ * alone and bit-reproducible.  The maps are the caller's arrays; a handle holds nothing of them between calls.  All n_maps maps
+ * share the geometry and n_max of *m.  Below (X0, Y0, CELL, NX, NY) are m's fields, (x0, y0, cell, nx, ny) g's, M = 2^20.
+ *   reused    pose, n_poses, map_of_frame, shift, mem, the composition of two calls and "HOST memory, copied at the call" are the
+ *             occupancy fusion's (above), word for word: the pose is map-from-frame {a, b, tx, c, d, ty} and its inverse the
+ *             TRANSPOSE; map_of_frame is NULL with one map, NULL with n_maps == frames, or explicit with -1: skipped; a map's
+ *             frames act in ASCENDING frame index; a pose that is not finite observes nothing.
+ *   z_offset  tz_f, the height of frame f's origin in the map's frame: HOST memory, n_poses doubles beside the poses (entry i with
+ *             pose i), or NULL: 0.  A z_offset that is not finite is no error: its frame observes nothing.
+ *   sample    ONE sample per map cell, at its centre.  Heights are a dense field: where a frame has a height under the centre it
+ *             is the height there, so the four-quadrant argument of the occupancy fusion (a thin obstacle must not vanish) does
+ *             not apply, and four samples would only blur steps.  All in double, every operation rounded on its own, no FMA:
+ *                 mx = X0 + ((double)jx + 0.5) * CELL                          my alike with jy, Y0
+ *                 dx = mx - tx;  dy = my - ty
+ *                 fx = a * dx + c * dy;   fy = b * dx + d * dy
+ *                 u = (fx - x0) / cell;  ix = (int)floor(u), inside iff 0 <= u && u < nx      v, iy alike with fy, y0, ny
+ *             A sample outside the frame image, or whose u or v is a NaN, observes nothing.
+ *   observation  Z = (double)height[f][iy][ix] + tz_f, one add.  The sample observes iff Z is finite and |Z| <= 1024.0; then
+ *             q = llrint(Z * 1024), ties to even (the product is exact): units of 2^-10 m, |q| <= M.  A NaN height -- a cell the
+ *             frame has no ground for -- observes nothing.
+ *   state     A cell holds n, the observations it remembers (int16), and sum, the sum of their q (int32).  At the start of a call
+ *             a cell's input is normalised: n = min(max(n_in, 0), n_max), then sum = min(max(sum_in, -n * M), n * M) in 64 bits:
+ *             any caller data is legal.
+ *   update    n < n_max: sum += q; n += 1 -- the exact running sum.  Otherwise: sum = sum - sum / n + q with C's integer division,
+ *             truncating toward zero -- the mean forgets one share of itself.  |sum| <= n * M is an invariant (|s| - floor(|s| / n)
+ *             <= (n - 1) * M), so with n_max <= 1023 an int32 never overflows.
+ *   mean      mean = (float)(((double)sum / (double)n) / 1024.0): one division, one exact scaling, one rounding; the quiet NaN
+ *             0x7fc00000 where n == 0.
+ *   order     Below n_max the result does not depend on the order of a map's frames.  Once capped it does: with n_max 1, heights
+ *             1.0 then 2.0 leave the mean 2.0, heights 2.0 then 1.0 leave 1.0; with n_max 2 from {n 2, sum 3072} (mean 1.5),
+ *             q 1024 then 3072 gives 4352, q 3072 then 1024 gives 3328.
+ *   shift     sum_out[k][jy][jx] and n_out[k][jy][jx] start from sum_in and n_in at [k][jy + sy_k][jx + sx_k], which read as 0
+ *             outside the map or with both NULL (both NULL: empty maps; exactly one NULL: PWPP_E_ARG); m describes the OUT map.
+ *             In place (sum_out == sum_in, n_out == n_in, either or both) is allowed iff every shift is {0, 0}; any other overlap
+ *             of the byte ranges of sum_in, n_in, sum_out, n_out and mean: PWPP_E_ARG.
+ *   composition  Two calls, the second reading the first's sum_out and n_out with no shift, give exactly one call over the
+ *             concatenated frames.  The same bytes for every call, mem, alignment and value of the option "elevation_path".
+ *   fuse_ground  the per-frame images are exactly what pwpp_rasterize_ground(g, frame_first, frames) gives, the NaN blanking of
+ *             PWPP_GRID_GROUND_ONLY included, written for the caller where asked for and kept in the handle's cluster buffer
+ *             otherwise; the maps are exactly what pwpp_fuse_height_grid gives for them.  Works after every kind of estimate call;
+ *             before any: PWPP_E_STATE.  Entry i of pose, z_offset and map_of_frame belongs to frame frame_first + i.
+ *   mem       PWPP_MEM_HOST: every image and map is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- sum, mean and height 4-byte aligned, n 2-byte aligned, no more -- enqueued on the
+ *             handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.  pose, z_offset, map_of_frame
+ *             and shift are HOST memory always.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, grid, height (pwpp_fuse_height_grid),
+ *             pose, map description, sum_out or n_out; frames or a side of the frame image < 1, a side > 32768, nx * ny * frames
+ *             beyond 2^31 (pwpp_fuse_height_grid; pwpp_fuse_ground names the product with the frame range); g->flags != 0
+ *             (pwpp_fuse_height_grid) or other than 0 or PWPP_GRID_GROUND_ONLY (pwpp_fuse_ground); the same three of n_maps and the
+ *             map; a cell or CELL that is not finite and positive; n_max outside 1 .. 1023; pad_ != 0; the number of poses;
+ *             map_of_frame; exactly one of sum_in and n_in null; the overlaps; mem; in PWPP_MEM_DEVICE an array below its
+ *             alignment.  pwpp_fuse_ground checks last what pwpp_rasterize_ground checks: the grid's origin, mem, PWPP_E_STATE
+ *             before any estimate call, the frame range.
+ *   buffers   No working image.  The poses, the offsets, the frame lists and the shifts are uploaded as one section of the cluster
+ *             buffer: allocated on first use, counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *             pwpp_fuse_height_grid needs a handle for its stream and this buffer only.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_ELEVATION_FUSION 1
+typedef struct pwpp_height_map {   /* 40 bytes */
+    double  x0, y0, cell;          /* the MAP's grid in the fixed frame, as in pwpp_fusion_map */
+    int32_t nx, ny;
+    int32_t n_max;                 /* observations a cell's mean remembers: 1 .. 1023 */
+    int32_t pad_;                  /* 0 */
+} pwpp_height_map;
+
+/* any height images: needs a handle (stream, buffer), no estimate call -- like pwpp_fuse_grid */
+PWPP_API int pwpp_fuse_height_grid(pwpp_handle *h, const pwpp_ground_grid *g /* the FRAME images' grid; flags must be 0 */, int frames, int mem,
+                                   const float *height /* [frames][g->ny][g->nx]; NaN: no height */,
+                                   const double *pose /* HOST, n_poses x 6, the fusion's pose */,
+                                   const double *z_offset /* HOST, n_poses, or NULL: 0 */, int n_poses,
+                                   const int32_t *map_of_frame /* HOST, frames entries, or NULL */,
+                                   const pwpp_height_map *m, int n_maps,
+                                   const int32_t *shift /* HOST, n_maps x {sx, sy} cells, or NULL: none */,
+                                   const int32_t *sum_in, const int16_t *n_in /* [n_maps][m->ny][m->nx]; both NULL: empty maps */,
+                                   int32_t *sum_out, int16_t *n_out, float *mean /* same shape, may be NULL */);
+/* rasterize_ground + fuse for frames of the LAST estimate call, one call -- like pwpp_fuse_obstacles */
+PWPP_API int pwpp_fuse_ground(pwpp_handle *h, const pwpp_ground_grid *g /* flags: 0 or PWPP_GRID_GROUND_ONLY */,
+                              int frame_first, int frames, int mem,
+                              const double *pose, const double *z_offset, int n_poses, const int32_t *map_of_frame,
+                              const pwpp_height_map *m, int n_maps, const int32_t *shift,
+                              const int32_t *sum_in, const int16_t *n_in, int32_t *sum_out, int16_t *n_out, float *mean /* may be NULL */,
+                              float *height /* the per-frame images, may be NULL: kept in the handle's buffer */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1002,6 +1089,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         exact and the product the same bits as the quotient -- and the division otherwise; "1": always the
  *                         double division as the contract writes it (the yardstick of tools/occupancy_fusion_cost.py).  The
  *                         results are identical bytes.
+ *   "elevation_path"      how the elevation fusion divides (pwpp_fuse_height_grid, pwpp_fuse_ground): "1": the quotients u, v and the share
+ *                         a capped mean forgets by divisions as the contract writes them (the yardstick); "2": the product with the exact
+ *                         reciprocal where the frame images' cell size is a power of two, and an exact multiply-shift by n_max; "0"
+ *                         (default): what tools/elevation_fusion_cost.py decided.  The same bytes for every value.
  *   "match_path"          how the scan match reads the map (pwpp_match_grid, pwpp_match_obstacles): "1": every map read comes from
  *                         global memory (the yardstick of tools/scan_match_cost.py); "2": the rectangle of the map that the
  *                         landings of a (frame, candidate) reach under the window is copied into LDS once per workgroup where it

@@ -25,6 +25,7 @@
 #include "pwpp_boxes.h"
 #include "pwpp_dev.h"
 #include "pwpp_distance.h"
+#include "pwpp_elevation.h"
 #include "pwpp_fusion.h"
 #include "pwpp_match.h"
 #include "pwpp_visibility.h"
@@ -251,6 +252,7 @@ struct pwpp_handle {
     int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
+    int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
     std::vector<std::vector<uint32_t>> uploads;  // the tables the last call that uploaded any built for its kernels: the sources of their copies (Staging::add_upload)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
@@ -2120,6 +2122,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 1) return fail(PWPP_E_ARG, "fusion_path=%s: 0 or 1 expected", value);
         h->fusion_path = v;
+    } else if (k == "elevation_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "elevation_path=%s: 0, 1 or 2 expected", value);
+        h->elevation_path = v;
     } else if (k == "match_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
@@ -2749,7 +2755,9 @@ static_assert(sizeof(pwpp_fusion_map) == 56, "pwpp_fusion_map is 56 bytes");
 constexpr const char *kFusionWho = "the fusion takes";
 
 // What the operators on a fused map check of the map description's grid and the two cell sizes; `who` as in mem_args, `map_cells`: NX * NY * n_maps.
-int map_grid_args(const pwpp_ground_grid *g, const pwpp_fusion_map *m, int n_maps, const char *who, size_t &map_cells) {
+// (pwpp_fusion_map and pwpp_height_map begin with the same grid: `M` is either)
+extern "C++" template <class M>  // (the entry points' extern "C" block is open around this namespace)
+int map_grid_args(const pwpp_ground_grid *g, const M *m, int n_maps, const char *who, size_t &map_cells) {
     if (const int rc = image_args(m->nx, m->ny, n_maps, who, map_cells)) return rc;
     if (!(g->cell > 0.0) || !std::isfinite(g->cell) || !(m->cell > 0.0) || !std::isfinite(m->cell))
         return fail(PWPP_E_ARG, "cell sizes %g (frames) and %g (map): finite and positive expected", g->cell, m->cell);
@@ -2769,7 +2777,30 @@ struct FrameMaps {
                 return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
         return PWPP_OK;
     }
+    // the CSR of the checked rule: a counting sort of the frames by their map keeps each map's frames in ascending order
+    void lists(int frames, std::vector<int32_t> &begin, std::vector<int32_t> &list) const {
+        begin.assign((size_t)n_maps + 1, 0);
+        int listed = 0;
+        for (int i = 0; i < frames; ++i)
+            if ((*this)(i) >= 0) ++begin[(size_t)(*this)(i) + 1], ++listed;
+        for (int k = 0; k < n_maps; ++k) begin[(size_t)k + 1] += begin[k];
+        list.assign((size_t)listed, 0);
+        std::vector<int32_t> next(begin.begin(), begin.end() - 1);
+        for (int i = 0; i < frames; ++i)
+            if ((*this)(i) >= 0) list[(size_t)next[(size_t)(*this)(i)]++] = i;
+    }
 };
+
+// whether a shift array moves any map, and whether two of the caller's byte ranges meet (a null one meets nothing)
+bool any_shift(const int32_t *shift, int n_maps) {
+    for (int k = 0; shift && k < n_maps; ++k)
+        if (shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0) return true;
+    return false;
+}
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
 
 // What a checked call hands to the kernel besides its images: the geometry, the parameters and the words to upload -- the poses
 // first (8-byte aligned at the section's start), then begin[n_maps + 1], the frame list and the shifts (none: no words).
@@ -2798,31 +2829,21 @@ int fusion_args(const pwpp_ground_grid *g, int frames, const double *pose, int n
     if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
     const FrameMaps map_of{map_of_frame, n_maps};
     if (const int rc = map_of.args(frames)) return rc;
-    bool moved = false;
-    for (int k = 0; shift && k < n_maps; ++k) moved = moved || shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0;
-    const auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
-        const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-        return a && b && pa < pb + nb && pb < pa + na;
-    };
+    const bool moved = any_shift(shift, n_maps);
     const size_t map_bytes = plan.map_cells * sizeof(int16_t);
     if (map_in == map_out && moved) return fail(PWPP_E_ARG, "map_out == map_in with a shift that is not {0, 0}: a shifted update needs a second array");
-    if (map_in != map_out && overlap(map_in, map_bytes, map_out, map_bytes)) return fail(PWPP_E_ARG, "map_in and map_out overlap without being equal");
-    if (overlap(map_occupancy, plan.map_cells, map_out, map_bytes) || overlap(map_occupancy, plan.map_cells, map_in, map_bytes))
-        return fail(PWPP_E_ARG, "map_occupancy overlaps %s", overlap(map_occupancy, plan.map_cells, map_out, map_bytes) ? "map_out" : "map_in");
+    if (map_in != map_out && ranges_overlap(map_in, map_bytes, map_out, map_bytes)) return fail(PWPP_E_ARG, "map_in and map_out overlap without being equal");
+    if (ranges_overlap(map_occupancy, plan.map_cells, map_out, map_bytes) || ranges_overlap(map_occupancy, plan.map_cells, map_in, map_bytes))
+        return fail(PWPP_E_ARG, "map_occupancy overlaps %s", ranges_overlap(map_occupancy, plan.map_cells, map_out, map_bytes) ? "map_out" : "map_in");
 
     plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
     pwpp_fuse_reciprocal(g->cell, plan.G.inv_cell);
     plan.P = PwppFusionParams{m->hit, m->miss, m->l_min, m->l_max, m->occupied_at, m->free_at};
     plan.n_poses = n_poses, plan.n_maps = n_maps, plan.shifted = shift != nullptr;
-    // the CSR: a counting sort of the frames by their map keeps each map's frames in ascending order
     try {
-    std::vector<int32_t> begin((size_t)n_maps + 1, 0);
-    for (int i = 0; i < frames; ++i)
-        if (map_of(i) >= 0) ++begin[(size_t)map_of(i) + 1], ++plan.listed;
-    for (int k = 0; k < n_maps; ++k) begin[(size_t)k + 1] += begin[k];
-    std::vector<int32_t> list((size_t)plan.listed), next(begin.begin(), begin.end() - 1);
-    for (int i = 0; i < frames; ++i)
-        if (map_of(i) >= 0) list[(size_t)next[(size_t)map_of(i)]++] = i;
+    std::vector<int32_t> begin, list;
+    map_of.lists(frames, begin, list);
+    plan.listed = (int)list.size();
     plan.words.assign(plan.at_shift() + (shift ? 2 * (size_t)n_maps : 0), 0u);
     std::memcpy(plan.words.data(), pose, (size_t)n_poses * 6 * sizeof(double));
     std::memcpy(plan.words.data() + plan.at_begin(), begin.data(), begin.size() * sizeof(int32_t));
@@ -3024,6 +3045,164 @@ int pwpp_match_pose(const double candidate[6], double CELL, int sx, int sy, doub
     if (!candidate || !out) return fail(PWPP_E_ARG, "null %s", candidate ? "output pose" : "candidate");
     pwpp_match_shifted_pose(candidate, CELL, sx, sy, out);
     return PWPP_OK;
+}
+
+// ---- elevation fusion: per-frame ground heights, under a pose and a height offset per frame, into persistent (sum, n) maps ---------
+namespace {
+static_assert(sizeof(pwpp_height_map) == 40, "pwpp_height_map is 40 bytes");
+constexpr const char *kElevationWho = "the elevation fusion takes";
+
+// What a checked call hands to the kernel besides its images: the geometry, the update's parameters and the words to upload -- the
+// poses first, then the offsets (both 8-byte aligned at the section's start; zeros without z_offset), begin[n_maps + 1], the frame
+// list and the shifts (none: no words).
+struct HeightPlan {
+    PwppFusionGeometry G;
+    PwppElevationParams P;
+    int n_poses = 0, n_maps = 0, listed = 0;
+    bool shifted = false;  // a shift array was given
+    size_t map_cells = 0;  // NX * NY * n_maps
+    std::vector<uint32_t> words;
+    size_t at_offset() const { return (size_t)n_poses * 12; }
+    size_t at_begin() const { return at_offset() + (size_t)n_poses * 2; }
+    size_t at_list() const { return at_begin() + (size_t)n_maps + 1; }
+    size_t at_shift() const { return at_list() + (size_t)listed; }
+};
+
+// What both entry points check of the map, the poses, the frame lists, the shifts, the inputs and the overlaps, in the header's
+// order, after the frame images' own checks (frames >= 1); fills the plan.  Touches no handle.
+int height_args(const pwpp_ground_grid *g, int frames, const double *pose, const double *z_offset, int n_poses, const int32_t *map_of_frame,
+                const pwpp_height_map *m, int n_maps, const int32_t *shift, const int32_t *sum_in, const int16_t *n_in, const int32_t *sum_out,
+                const int16_t *n_out, const float *mean, HeightPlan &plan) {
+    if (const int rc = map_grid_args(g, m, n_maps, kElevationWho, plan.map_cells)) return rc;
+    if (m->n_max < 1 || m->n_max > PWPP_ELEV_MAX_N) return fail(PWPP_E_ARG, "n_max %d: 1 .. 1023 expected", m->n_max);
+    if (m->pad_ != 0) return fail(PWPP_E_ARG, "pad_ %d of the height map: 0 expected", m->pad_);
+    if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
+    const FrameMaps map_of{map_of_frame, n_maps};
+    if (const int rc = map_of.args(frames)) return rc;
+    if (!sum_in != !n_in) return fail(PWPP_E_ARG, "null %s with a %s: both or neither expected", sum_in ? "n_in" : "sum_in", sum_in ? "sum_in" : "n_in");
+    const bool moved = any_shift(shift, n_maps);
+    struct Range {
+        const void *p;
+        size_t bytes;
+        const char *name;
+    };
+    const Range r[5] = {{sum_in, plan.map_cells * 4, "sum_in"}, {n_in, plan.map_cells * 2, "n_in"}, {sum_out, plan.map_cells * 4, "sum_out"},
+                        {n_out, plan.map_cells * 2, "n_out"}, {mean, plan.map_cells * 4, "mean"}};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j) {
+            if (!ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) continue;
+            if (j == i + 2 && i < 2 && r[i].p == r[j].p) {  // sum_out == sum_in, n_out == n_in: in place
+                if (moved) return fail(PWPP_E_ARG, "%s == %s with a shift that is not {0, 0}: a shifted update needs a second array", r[j].name, r[i].name);
+                continue;
+            }
+            return fail(PWPP_E_ARG, "%s and %s overlap%s", r[i].name, r[j].name, j == i + 2 && i < 2 ? " without being equal" : "");
+        }
+
+    plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
+    pwpp_fuse_reciprocal(g->cell, plan.G.inv_cell);
+    plan.P = pwpp_elev_magic(m->n_max);
+    plan.n_poses = n_poses, plan.n_maps = n_maps, plan.shifted = shift != nullptr;
+    try {
+        std::vector<int32_t> begin, list;
+        map_of.lists(frames, begin, list);
+        plan.listed = (int)list.size();
+        plan.words.assign(plan.at_shift() + (shift ? 2 * (size_t)n_maps : 0), 0u);
+        std::memcpy(plan.words.data(), pose, (size_t)n_poses * 6 * sizeof(double));
+        if (z_offset) std::memcpy(plan.words.data() + plan.at_offset(), z_offset, (size_t)n_poses * sizeof(double));
+        std::memcpy(plan.words.data() + plan.at_begin(), begin.data(), begin.size() * sizeof(int32_t));
+        if (plan.listed) std::memcpy(plan.words.data() + plan.at_list(), list.data(), list.size() * sizeof(int32_t));
+        if (shift) std::memcpy(plan.words.data() + plan.at_shift(), shift, 2 * (size_t)n_maps * sizeof(int32_t));
+    } catch (const std::bad_alloc &) {
+        return fail(PWPP_E_NOMEM, "no host memory for the lists of %d maps and %d frames", n_maps, frames);
+    }
+    return PWPP_OK;
+}
+
+// (after mem: what PWPP_MEM_DEVICE asks of the arrays -- words 4-byte, counts 2-byte aligned, no more)
+int height_alignment_args(int mem, const void *height, const void *sum_in, const void *n_in, const void *sum_out, const void *n_out, const void *mean) {
+    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
+    const auto off = [](const void *p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (off(height, 3u) || off(sum_in, 3u) || off(sum_out, 3u) || off(mean, 3u))
+        return fail(PWPP_E_ARG, "the %s must be 4-byte aligned", off(height, 3u) ? "height images" : (off(mean, 3u) ? "mean" : "sums"));
+    if (off(n_in, 1u) || off(n_out, 1u)) return fail(PWPP_E_ARG, "the counts must be 2-byte aligned");
+    return PWPP_OK;
+}
+
+// (the plan's words first: they move into the staging; `height` is the frame images' section: the caller's, or the ground raster's)
+struct HeightSections {
+    int up, height, sum_in, n_in, sum_out, n_out, mean;
+};
+HeightSections height_sections(Staging &st, HeightPlan &plan, int s_height, const int32_t *sum_in, const int16_t *n_in, int32_t *sum_out, int16_t *n_out,
+                               float *mean) {
+    HeightSections s;
+    const size_t n_words = (plan.map_cells + 1) / 2, n_bytes = plan.map_cells * sizeof(int16_t);
+    s.up = st.add_upload(std::move(plan.words));
+    s.height = s_height;
+    s.sum_in = st.add(sum_in ? plan.map_cells : 0, sum_in, Staging::kIn);
+    s.n_in = st.add(n_in ? n_words : 0, n_in, Staging::kIn, n_in ? n_bytes : 0);
+    s.sum_out = st.add(plan.map_cells, sum_out, Staging::kOut);
+    s.n_out = st.add(n_words, n_out, Staging::kOut, n_bytes);
+    s.mean = st.add(mean ? plan.map_cells : 0, mean, Staging::kOut);
+    return s;
+}
+int height_launch(pwpp_handle *h, const Staging &st, const HeightSections &s, const HeightPlan &plan, int frames) {
+    const int32_t *words = st.dev<const int32_t>(s.up);
+    return pwpp_launch_fuse_height(&plan.G, &plan.P, frames, st.dev<const float>(s.height), st.dev<const double>(s.up),
+                                   reinterpret_cast<const double *>(words + plan.at_offset()), plan.n_poses, plan.n_maps, words + plan.at_begin(),
+                                   words + plan.at_list(), plan.listed, plan.shifted ? words + plan.at_shift() : nullptr, st.dev<const int32_t>(s.sum_in),
+                                   st.dev<const int16_t>(s.n_in), st.dev<int32_t>(s.sum_out), st.dev<int16_t>(s.n_out), st.dev<float>(s.mean),
+                                   h->elevation_path, h->stream);
+}
+const char *height_null(const void *g, const void *first, const char *first_name, const void *pose, const void *m, const void *sum_out, const void *n_out) {
+    return !g ? "grid" : (!first ? first_name : (!pose ? "pose" : (!m ? "map description" : (!sum_out ? "sum_out" : (!n_out ? "n_out" : nullptr)))));
+}
+}  // namespace
+
+int pwpp_fuse_height_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int mem, const float *height, const double *pose, const double *z_offset,
+                          int n_poses, const int32_t *map_of_frame, const pwpp_height_map *m, int n_maps, const int32_t *shift, const int32_t *sum_in,
+                          const int16_t *n_in, int32_t *sum_out, int16_t *n_out, float *mean) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (const char *what = height_null(g, height, "height images", pose, m, sum_out, n_out)) return fail(PWPP_E_ARG, "null %s", what);
+    size_t cells = 0;
+    int rc = image_args(g->nx, g->ny, frames, kElevationWho, cells);
+    if (rc) return rc;
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the elevation fusion's frame grid takes 0", g->flags);
+    HeightPlan plan;
+    if ((rc = height_args(g, frames, pose, z_offset, n_poses, map_of_frame, m, n_maps, shift, sum_in, n_in, sum_out, n_out, mean, plan))) return rc;
+    if ((rc = mem_args(mem, kElevationWho))) return rc;
+    if ((rc = height_alignment_args(mem, height, sum_in, n_in, sum_out, n_out, mean))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_height = st.add(cells, height, Staging::kIn);
+    const HeightSections s = height_sections(st, plan, s_height, sum_in, n_in, sum_out, n_out, mean);
+    return run_on_image(h, st, [&] { return height_launch(h, st, s, plan, frames); });
+}
+
+// pwpp_rasterize_ground into a section of the cluster buffer (or the caller's images) and pwpp_fuse_height_grid on it, one enqueued sequence.
+int pwpp_fuse_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, const double *pose, const double *z_offset, int n_poses,
+                     const int32_t *map_of_frame, const pwpp_height_map *m, int n_maps, const int32_t *shift, const int32_t *sum_in, const int16_t *n_in,
+                     int32_t *sum_out, int16_t *n_out, float *mean, float *height) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (const char *what = height_null(g, g, "", pose, m, sum_out, n_out)) return fail(PWPP_E_ARG, "null %s", what);
+    if (frames < 1 || g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, g->nx, g->ny);
+    int rc = side_args(g->nx, g->ny, kElevationWho);
+    if (rc) return rc;
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    HeightPlan plan;
+    if ((rc = height_args(g, frames, pose, z_offset, n_poses, map_of_frame, m, n_maps, shift, sum_in, n_in, sum_out, n_out, mean, plan))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = height_alignment_args(mem, height, sum_in, n_in, sum_out, n_out, mean))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_height = add_image(st, cells, height, true);
+    const HeightSections s = height_sections(st, plan, s_height, sum_in, n_in, sum_out, n_out, mean);
+    if ((rc = st.begin())) return rc;
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    if ((rc = ground_view(h, v))) return rc;
+    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), nullptr, h->stream);
+    if (lrc == 0) lrc = height_launch(h, st, s, plan, frames);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

@@ -65,13 +65,31 @@ PWPP_HD inline int32_t pwpp_fuse_start(const int16_t *map_in /* one map, or null
 // ---- the sample positions of a cell along one axis, in the map's frame: p[0] the lower quadrants', p[1] the upper ones'
 PWPP_HD inline double pwpp_fuse_position(double X0, int j, int q, double CELL) { return X0 + ((double)j + (0.25 + 0.5 * (double)q)) * CELL; }
 
-// ---- the byte one sample reads: the position (mx, my) of the map's frame under the pose {a, b, tx, c, d, ty}
+// ---- where the position (mx, my) of the map's frame lies in a frame image, in cells: the pose {a, b, tx, c, d, ty}, transposed
 template <bool RECIP>
-PWPP_HD inline int8_t pwpp_fuse_sample(const PwppFusionGeometry &G, const double *pose, double mx, double my, const int8_t *image /* one frame */) {
+PWPP_HD inline void pwpp_fuse_uv(const PwppFusionGeometry &G, const double *pose, double mx, double my, double &u, double &v) {
     const double a = pose[0], b = pose[1], tx = pose[2], c = pose[3], d = pose[4], ty = pose[5];
     const double dx = mx - tx, dy = my - ty;
     const double fx = a * dx + c * dy, fy = b * dx + d * dy;
-    const double u = RECIP ? (fx - G.x0) * G.inv_cell : (fx - G.x0) / G.cell, v = RECIP ? (fy - G.y0) * G.inv_cell : (fy - G.y0) / G.cell;
+    u = RECIP ? (fx - G.x0) * G.inv_cell : (fx - G.x0) / G.cell, v = RECIP ? (fy - G.y0) * G.inv_cell : (fy - G.y0) / G.cell;
+}
+
+// ---- the frame cell under that position: false where it lies outside the image (a NaN: outside).  What the elevation fusion
+// (pwpp_elevation.h) asks at a cell's centre.
+template <bool RECIP>
+PWPP_HD inline bool pwpp_fuse_cell_of(const PwppFusionGeometry &G, const double *pose, double mx, double my, int &ix, int &iy) {
+    double u, v;
+    pwpp_fuse_uv<RECIP>(G, pose, mx, my, u, v);
+    if (!(u >= 0.0 && u < (double)G.nx && v >= 0.0 && v < (double)G.ny)) return false;
+    ix = (int)floor(u), iy = (int)floor(v);
+    return (unsigned)ix < (unsigned)G.nx && (unsigned)iy < (unsigned)G.ny;  // (always: 0 <= floor(u) <= u < nx)
+}
+
+// ---- the byte one sample reads
+template <bool RECIP>
+PWPP_HD inline int8_t pwpp_fuse_sample(const PwppFusionGeometry &G, const double *pose, double mx, double my, const int8_t *image /* one frame */) {
+    double u, v;
+    pwpp_fuse_uv<RECIP>(G, pose, mx, my, u, v);
     if (!(u >= 0.0 && u < (double)G.nx && v >= 0.0 && v < (double)G.ny)) return (int8_t)PWPP_FUSE_UNKNOWN;  // (a NaN: outside)
     const int ix = (int)floor(u), iy = (int)floor(v);
     if ((unsigned)ix >= (unsigned)G.nx || (unsigned)iy >= (unsigned)G.ny) return (int8_t)PWPP_FUSE_UNKNOWN;  // (cannot happen: 0 <= floor(u) <= u < nx)

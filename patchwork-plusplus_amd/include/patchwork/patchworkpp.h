@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstring>
 #include <iostream>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -453,6 +454,44 @@ public:
         map.log_odds.swap(out);
         map.x0 = mx0, map.y0 = my0;
     }
+    // ... and the ground under them accumulated the same way (pwpp_fuse_ground): a persistent elevation map in the same FIXED frame,
+    // the caller's own.  sum holds an int32 per cell, the sum of the heights the cell remembers in units of 2^-10 m, n how many it
+    // remembers (at most n_max; beyond that the mean forgets one share of itself per observation), mean their float mean, NaN where
+    // n is 0.  updateElevationMap resamples the last frame's elevation image on the grid (x0, y0, cell, nx, ny) at every map cell's
+    // centre under the map-from-frame pose {a, b, tx, c, d, ty}, adds z_offset (the height of the frame's origin in the map's frame)
+    // and updates; (shift_x, shift_y) roll the map first as in updateObstacleMap.
+    struct FusedElevationMap {
+        double x0 = 0.0, y0 = 0.0, cell = 0.0;  // the map's grid: cell (jx, jy) covers x0 + [jx, jx + 1) * cell, ...
+        int nx = 0, ny = 0;
+        int n_max = 16;            // 1 .. 1023
+        std::vector<int32_t> sum;  // ny x nx, row-major; sized and zeroed by the first update
+        std::vector<int16_t> n;    // same shape
+        std::vector<float> mean;   // same shape
+    };
+    void updateElevationMap(FusedElevationMap &map, const double pose[6], double z_offset, double x0, double y0, double cell, int nx, int ny,
+                            bool ground_only = false, int shift_x = 0, int shift_y = 0) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        const double mx0 = map.x0 + (double)shift_x * map.cell, my0 = map.y0 + (double)shift_y * map.cell;
+        const pwpp_height_map m = {mx0, my0, map.cell, map.nx, map.ny, map.n_max, 0};
+        const size_t cells = (size_t)(map.nx > 0 ? map.nx : 0) * (size_t)(map.ny > 0 ? map.ny : 0);
+        if (map.sum.size() != cells || map.n.size() != cells) map.sum.assign(cells, 0), map.n.assign(cells, 0);
+        std::vector<int32_t> sum(cells ? cells : 1);
+        std::vector<int16_t> n(cells ? cells : 1);
+        std::vector<float> mean(cells ? cells : 1);
+        const int32_t shift[2] = {shift_x, shift_y};
+        check(pwpp_fuse_ground(h_, &g, 0, 1, PWPP_MEM_HOST, pose, &z_offset, 1, nullptr, &m, 1, shift, cells ? map.sum.data() : nullptr,
+                               cells ? map.n.data() : nullptr, sum.data(), n.data(), mean.data(), nullptr));
+        sum.resize(cells), n.resize(cells), mean.resize(cells);
+        map.sum.swap(sum), map.n.swap(n), map.mean.swap(mean);
+        map.x0 = mx0, map.y0 = my0;
+    }
+    // (the mean image of such a map, ny x nx: NaN where it was never updated or a cell remembers nothing)
+    static Points fusedElevationRows(const FusedElevationMap &map) {
+        Points img(map.ny > 0 ? map.ny : 0, map.nx > 0 ? map.nx : 0);
+        const size_t cells = (size_t)img.rows() * (size_t)img.cols();
+        for (size_t i = 0; i < cells; ++i) img.data()[i] = map.mean.size() == cells ? map.mean[i] : std::numeric_limits<float>::quiet_NaN();
+        return img;
+    }
     // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},
     // the prior first) and every shift of [-wx, wx] x [-wy, wy] map cells, the sum of log_odds under the occupied cells of the
     // frame's visibility bytes; the best by the contract's order, and `pose`, the winning candidate moved by the winning shift
@@ -511,10 +550,12 @@ public:
     Eigen::MatrixXf getElevationMap(double x0, double y0, double cell, int nx, int ny, bool ground_only = false) {
         return to_eigen(elevationMapRows(x0, y0, cell, nx, ny, ground_only));
     }
+    Eigen::MatrixXf getFusedElevation(const FusedElevationMap &map) { return to_eigen(fusedElevationRows(map)); }
 #else
     Points getElevationMap(double x0, double y0, double cell, int nx, int ny, bool ground_only = false) {
         return elevationMapRows(x0, y0, cell, nx, ny, ground_only);
     }
+    Points getFusedElevation(const FusedElevationMap &map) { return fusedElevationRows(map); }
 #endif
 
 #ifdef PWPP_HAVE_EIGEN

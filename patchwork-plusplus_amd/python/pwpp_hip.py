@@ -95,6 +95,11 @@ class FusionMap(ctypes.Structure):  # pwpp_fusion_map: the grid of the fused map
                 ("occupied_at", ctypes.c_int32), ("free_at", ctypes.c_int32)]
 
 
+class HeightMap(ctypes.Structure):  # pwpp_height_map (40 bytes): the grid of the fused elevation maps in the fixed frame, the observations a mean remembers
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("cell", ctypes.c_double), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32),
+                ("n_max", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
 class MatchBest(ctypes.Structure):  # pwpp_match_best (24 bytes): the winning sum, its candidate (-1: skipped) and shift, the frame's occupied cells
     _fields_ = [("score", ctypes.c_int64), ("candidate", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("cells", ctypes.c_int32)]
 
@@ -217,6 +222,10 @@ def load():
             L.pwpp_match_grid.argtypes = [vp, gp, ci, ci, vp, vp, ci, ci, vp, mp, ci, vp, ci, ci, vp, vp]
             L.pwpp_match_obstacles.argtypes = [vp, gp, cf, cf, ci, vp, ci, ci, ci, ci, ci, vp, ci, ci, vp, mp, ci, vp, ci, ci, vp, vp, vp]
             L.pwpp_match_pose.argtypes = [vp, ctypes.c_double, ci, ci, vp]
+        if hasattr(L, "pwpp_fuse_height_grid"):  # (as above: an older build has no elevation fusion)
+            gp, hp = ctypes.POINTER(GroundGrid), ctypes.POINTER(HeightMap)
+            L.pwpp_fuse_height_grid.argtypes = [vp, gp, ci, ci, vp, vp, vp, ci, vp, hp, ci, vp, vp, vp, vp, vp, vp]
+            L.pwpp_fuse_ground.argtypes = [vp, gp, ci, ci, ci, vp, vp, ci, vp, hp, ci, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -1080,6 +1089,73 @@ class Handle:
         self._check(self._L.pwpp_fuse_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
                                                 int(frame_first), frames, MEM_DEVICE, _hp(pose), len(pose), _hp(mof), ctypes.byref(fmap), int(n_maps),
                                                 _hp(shift), _dp(map_in_ptr), _dp(map_out_ptr), _dp(map_occupancy_ptr), _dp(occupancy_ptr)))
+
+    @staticmethod
+    def _height_host(pose, z_offset, map_of_frame, shift):
+        """The host arrays every elevation fusion call takes: (n_poses, 6) and (n_poses,) float64 or None, (frames,) and (n_maps, 2) int32 or None."""
+        return _host(pose, np.float64, -1, 6), _host(z_offset, np.float64, -1), _host(map_of_frame, np.int32, -1), _host(shift, np.int32, -1, 2)
+
+    def _height_maps(self, hmap, n_maps, sum_in, n_in, want_mean, sum_out=None, n_out=None):
+        shape = self._grid_shape(hmap, n_maps)
+        if sum_in is not None:
+            sum_in = np.ascontiguousarray(sum_in, np.int32).reshape(shape)
+        if n_in is not None:
+            n_in = np.ascontiguousarray(n_in, np.int16).reshape(shape)
+        return (sum_in, n_in, np.empty(shape, np.int32) if sum_out is None else sum_out, np.empty(shape, np.int16) if n_out is None else n_out,
+                np.empty(shape, np.float32) if want_mean else None)
+
+    def fuse_height_grid(self, height, grid, pose, hmap, n_maps=1, sum_in=None, n_in=None, z_offset=None, map_of_frame=None, shift=None, want_mean=True,
+                         sum_out=None, n_out=None):
+        """Fuses the (frames, ny, nx) or (ny, nx) float32 height images (NaN: no height) on the grid `grid` = (x0, y0, cell) into
+        n_maps elevation maps described by the HeightMap `hmap`: an int32 sum (units of 2^-10 m) and an int16 count per cell, and
+        their float32 mean.  pose, map_of_frame and shift as in fuse_grid; z_offset: the height of each frame's origin in the map's
+        frame, one per pose, None: 0; sum_in, n_in: the (n_maps, NY, NX) maps to start from, both None: empty; sum_out, n_out: the
+        arrays to write (the inputs themselves are allowed without a shift), None: new ones.  Works before any estimate call.
+        Returns (sum_out, n_out, mean), the mean None when not wanted.  The rules: include/pwpp.h."""
+        hgt = np.ascontiguousarray(height, np.float32)
+        h3 = hgt.reshape((1,) + hgt.shape) if hgt.ndim == 2 else hgt
+        if h3.ndim != 3:
+            raise ValueError("height: a (frames, ny, nx) or (ny, nx) image expected")
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), h3.shape[2], h3.shape[1], 0, 0)
+        pose, zo, mof, shift = self._height_host(pose, z_offset, map_of_frame, shift)
+        sum_in, n_in, s_out, c_out, mean = self._height_maps(hmap, n_maps, sum_in, n_in, want_mean, sum_out, n_out)
+        self._check(self._L.pwpp_fuse_height_grid(self._h, ctypes.byref(g), h3.shape[0], MEM_HOST, _hp(h3), _hp(pose), _hp(zo), len(pose), _hp(mof),
+                                                  ctypes.byref(hmap), int(n_maps), _hp(shift), _hp(sum_in), _hp(n_in), _hp(s_out), _hp(c_out), _hp(mean)))
+        return s_out, c_out, mean
+
+    def fuse_height_grid_device(self, grid, nx, ny, frames, height_ptr, pose, hmap, n_maps, sum_in_ptr, n_in_ptr, sum_out_ptr, n_out_ptr, mean_ptr=0,
+                                z_offset=None, map_of_frame=None, shift=None):
+        """fuse_height_grid on device memory: addresses of the (frames, ny, nx) float32 height images, the (n_maps, NY, NX) int32 sums
+        and int16 counts (inputs 0: empty maps) and (0: not wanted) the float32 means; 4-, 4- and 2-byte aligned.  pose, z_offset,
+        map_of_frame and shift stay host arrays.  Enqueued on the handle's stream; complete after synchronize()."""
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), int(nx), int(ny), 0, 0)
+        pose, zo, mof, shift = self._height_host(pose, z_offset, map_of_frame, shift)
+        self._check(self._L.pwpp_fuse_height_grid(self._h, ctypes.byref(g), int(frames), MEM_DEVICE, _dp(height_ptr), _hp(pose), _hp(zo), len(pose), _hp(mof),
+                                                  ctypes.byref(hmap), int(n_maps), _hp(shift), _dp(sum_in_ptr), _dp(n_in_ptr), _dp(sum_out_ptr),
+                                                  _dp(n_out_ptr), _dp(mean_ptr)))
+
+    def fuse_ground(self, x0, y0, cell, nx, ny, pose, hmap, n_maps=1, sum_in=None, n_in=None, z_offset=None, frame_first=0, frames=None,
+                    map_of_frame=None, shift=None, ground_only=False, want_mean=True, want_frames=False):
+        """rasterize_ground and fuse_height_grid in one call, for frames of the last estimate call: (sum_out, n_out, mean) as
+        fuse_height_grid gives them for the elevation images of rasterize_ground; want_frames: then those (frames, ny, nx) float32
+        images too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        pose, zo, mof, shift = self._height_host(pose, z_offset, map_of_frame, shift)
+        sum_in, n_in, s_out, c_out, mean = self._height_maps(hmap, n_maps, sum_in, n_in, want_mean)
+        hgt = np.empty(self._grid_shape(g, frames), np.float32) if want_frames else None
+        self._check(self._L.pwpp_fuse_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, _hp(pose), _hp(zo), len(pose), _hp(mof),
+                                             ctypes.byref(hmap), int(n_maps), _hp(shift), _hp(sum_in), _hp(n_in), _hp(s_out), _hp(c_out), _hp(mean), _hp(hgt)))
+        return (s_out, c_out, mean) + ((hgt,) if want_frames else ())
+
+    def fuse_ground_device(self, x0, y0, cell, nx, ny, pose, hmap, n_maps, sum_in_ptr, n_in_ptr, sum_out_ptr, n_out_ptr, mean_ptr=0, height_ptr=0,
+                           z_offset=None, frame_first=0, frames=None, map_of_frame=None, shift=None, ground_only=False):
+        """fuse_ground into device memory: addresses as in fuse_height_grid_device, height_ptr the (frames, ny, nx) float32 images of
+        the frames (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        pose, zo, mof, shift = self._height_host(pose, z_offset, map_of_frame, shift)
+        self._check(self._L.pwpp_fuse_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, _hp(pose), _hp(zo), len(pose), _hp(mof),
+                                             ctypes.byref(hmap), int(n_maps), _hp(shift), _dp(sum_in_ptr), _dp(n_in_ptr), _dp(sum_out_ptr), _dp(n_out_ptr),
+                                             _dp(mean_ptr), _dp(height_ptr)))
 
     @staticmethod
     def _match_host(candidates, frames, map_of_frame):

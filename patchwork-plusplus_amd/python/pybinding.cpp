@@ -158,6 +158,15 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def_readwrite("occupied_at", &PatchWorkpp::FusedObstacleMap::occupied_at)
         .def_readwrite("free_at", &PatchWorkpp::FusedObstacleMap::free_at);
 
+    py::class_<PatchWorkpp::FusedElevationMap>(m, "FusedElevationMap")  // the caller's persistent map of updateElevationMap
+        .def(py::init<>())
+        .def_readwrite("x0", &PatchWorkpp::FusedElevationMap::x0)
+        .def_readwrite("y0", &PatchWorkpp::FusedElevationMap::y0)
+        .def_readwrite("cell", &PatchWorkpp::FusedElevationMap::cell)
+        .def_readwrite("nx", &PatchWorkpp::FusedElevationMap::nx)
+        .def_readwrite("ny", &PatchWorkpp::FusedElevationMap::ny)
+        .def_readwrite("n_max", &PatchWorkpp::FusedElevationMap::n_max);
+
     py::class_<PatchWorkpp>(m, "patchworkpp")
         .def(py::init<Params>())
         .def(py::init<Params, int>(), py::arg("params"), py::arg("device"))
@@ -237,6 +246,20 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              py::arg("map"), py::arg("pose"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"),
              py::arg("h_max"), py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0,
              py::arg("shift_x") = 0, py::arg("shift_y") = 0)
+        .def("updateElevationMap",
+             [](PatchWorkpp &s, PatchWorkpp::FusedElevationMap &map, const std::array<double, 6> &pose, double z_offset, double x0, double y0, double cell,
+                int nx, int ny, bool ground_only, int shift_x, int shift_y) {
+                 s.updateElevationMap(map, pose.data(), z_offset, x0, y0, cell, nx, ny, ground_only, shift_x, shift_y);
+                 py::array_t<int32_t> sum({(py::ssize_t)map.ny, (py::ssize_t)map.nx});
+                 py::array_t<int16_t> n({(py::ssize_t)map.ny, (py::ssize_t)map.nx});
+                 if (!map.sum.empty()) std::memcpy(sum.mutable_data(), map.sum.data(), map.sum.size() * sizeof(int32_t));
+                 if (!map.n.empty()) std::memcpy(n.mutable_data(), map.n.data(), map.n.size() * sizeof(int16_t));
+                 return py::make_tuple(sum, n, to_numpy(PatchWorkpp::fusedElevationRows(map)));
+             },
+             py::arg("map"), py::arg("pose"), py::arg("z_offset"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"),
+             py::arg("ground_only") = false, py::arg("shift_x") = 0, py::arg("shift_y") = 0)
+        .def("getFusedElevation", [](PatchWorkpp &, const PatchWorkpp::FusedElevationMap &map) { return to_numpy(PatchWorkpp::fusedElevationRows(map)); },
+             py::arg("map"))
         .def("matchObstacleMap",
              [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, const std::vector<std::array<double, 6>> &candidates, int wx, int wy, double x0,
                 double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y) {

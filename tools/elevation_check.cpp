@@ -1,0 +1,257 @@
+// elevation_check.cpp -- the elevation fusion's arithmetic on the host, against a brute force, and the two proofs its contract cites.
+//
+// The kernel of patchwork-plusplus_amd/csrc/pwpp_elevation.hip is built from the functions of pwpp_elevation.h (the shifted and
+// normalised start, the centre of a cell, the frame cell under it by pwpp_fusion.h's pwpp_fuse_cell_of, the observation, the
+// update, the bits of the mean).  This program
+//   1  runs the same sequence with the same functions over plain memory, dealt as the kernel deals it -- a map, a run of 256 cells, a
+//      lane per cell, the map's frames from a CSR in ascending order -- with every array allocated at EXACTLY its size (an index
+//      outside one is a sanitizer error), on many small random cases, for every pair of template arguments the kernel is built
+//      with, and compares sum, n and the mean's bits with a brute force written separately below: frame by frame over whole maps,
+//      its own formulas, 64-bit integers;
+//   2  proves the invariant |sum| <= n M of the update by brute force over EVERY state and observation for small M and n_max;
+//   3  proves the multiply-shift of pwpp_elev_magic equal to the truncating division on the whole range |sum| <= n_max M for every
+//      n_max in 1 .. 1023: the hypothesis of the header's argument (m d = 2^sh + e, 0 <= e < d, and x_max e < 2^sh) for every d;
+//      and, since floor(x / d) is constant on [k d, k d + d) while the multiply-shift is monotone in x, both ends of EVERY such
+//      segment for a spread of divisors -- equality at both ends of a segment is equality inside it.
+// Exit status 0: all equal.
+//
+//   c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -I patchwork-plusplus_amd/csrc tools/elevation_check.cpp -o elevation_check
+// (tests/test_elevation_fusion_cpu.py builds and runs it; it needs no GPU and no HIP.)
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "pwpp_elevation.h"
+
+namespace {
+
+struct Case {
+    PwppFusionGeometry G;
+    int n_max, frames, n_maps, n_poses;
+    std::vector<float> height;          // frames * ny * nx
+    std::vector<double> poses;          // n_poses * 6
+    std::vector<double> z_offset;       // n_poses
+    std::vector<int32_t> map_of_frame;  // frames
+    std::vector<int32_t> shift;         // n_maps * 2
+    std::vector<int32_t> sum_in;        // n_maps * NY * NX, or both empty: null
+    std::vector<int16_t> n_in;
+};
+
+struct Maps {
+    std::vector<int32_t> sum;
+    std::vector<int16_t> n;
+    std::vector<uint32_t> mean;
+    bool operator==(const Maps &o) const { return sum == o.sum && n == o.n && mean == o.mean; }
+};
+
+// the definition, frame by frame over whole maps
+Maps brute_force(const Case &c) {
+    const int NX = c.G.NX, NY = c.G.NY, nx = c.G.nx, ny = c.G.ny;
+    const long long M = 1 << 20;
+    const size_t all = (size_t)c.n_maps * NY * NX;
+    std::vector<long long> S(all, 0), N(all, 0);
+    for (int k = 0; k < c.n_maps; ++k)
+        for (int jy = 0; jy < NY; ++jy)
+            for (int jx = 0; jx < NX; ++jx) {
+                const long long qx = (long long)jx + c.shift[2 * k], qy = (long long)jy + c.shift[2 * k + 1];
+                if (c.sum_in.empty() || qx < 0 || qx >= NX || qy < 0 || qy >= NY) continue;
+                const size_t to = ((size_t)k * NY + jy) * NX + jx, from = ((size_t)k * NY + qy) * NX + qx;
+                N[to] = std::min<long long>(std::max<long long>(c.n_in[from], 0), c.n_max);
+                S[to] = std::min(std::max<long long>(c.sum_in[from], -N[to] * M), N[to] * M);
+            }
+    for (int f = 0; f < c.frames; ++f) {
+        const int k = c.map_of_frame[f];
+        if (k < 0) continue;
+        const size_t pi = c.n_poses == 1 ? 0 : (size_t)f;
+        const double *p = &c.poses[pi * 6];
+        for (int jy = 0; jy < NY; ++jy)
+            for (int jx = 0; jx < NX; ++jx) {
+                const double cx = (double)jx + 0.5, cy = (double)jy + 0.5;
+                const double sx = cx * c.G.CELL, sy = cy * c.G.CELL;
+                const double mx = c.G.X0 + sx, my = c.G.Y0 + sy;
+                const double dx = mx - p[2], dy = my - p[5];
+                const double t0 = p[0] * dx, t1 = p[3] * dy, t2 = p[1] * dx, t3 = p[4] * dy;
+                const double fx = t0 + t1, fy = t2 + t3;
+                const double u = (fx - c.G.x0) / c.G.cell, v = (fy - c.G.y0) / c.G.cell;
+                if (!(u >= 0.0 && u < nx && v >= 0.0 && v < ny)) continue;
+                const double Z = (double)c.height[((size_t)f * ny + (size_t)std::floor(v)) * nx + (size_t)std::floor(u)] + c.z_offset[pi];
+                if (!std::isfinite(Z) || std::fabs(Z) > 1024.0) continue;
+                const long long q = std::llrint(Z * 1024.0);
+                long long &s = S[((size_t)k * NY + jy) * NX + jx], &n = N[((size_t)k * NY + jy) * NX + jx];
+                if (n < c.n_max) s += q, n += 1;
+                else s = s - s / n + q;
+                if (std::llabs(s) > n * M) std::abort();  // (the invariant)
+            }
+    }
+    Maps m{std::vector<int32_t>(all), std::vector<int16_t>(all), std::vector<uint32_t>(all)};
+    for (size_t i = 0; i < all; ++i) {
+        m.sum[i] = (int32_t)S[i], m.n[i] = (int16_t)N[i];
+        const float mean = N[i] ? (float)(((double)S[i] / (double)N[i]) / 1024.0) : 0.0f;
+        std::memcpy(&m.mean[i], &mean, 4);
+        if (!N[i]) m.mean[i] = 0x7fc00000u;
+    }
+    return m;
+}
+
+// the kernel's sequence with the header's functions
+template <bool RECIP, bool FAST>
+Maps as_the_kernel(const Case &c, bool in_place) {
+    const int per_map = c.G.NX * c.G.NY, runs = (per_map + PWPP_FUSE_RUN - 1) / PWPP_FUSE_RUN;
+    const PwppElevationParams P = pwpp_elev_magic(c.n_max);
+    std::vector<int32_t> begin((size_t)c.n_maps + 1, 0);
+    int listed = 0;
+    for (int f = 0; f < c.frames; ++f)
+        if (c.map_of_frame[f] >= 0) ++begin[(size_t)c.map_of_frame[f] + 1], ++listed;
+    for (int k = 0; k < c.n_maps; ++k) begin[(size_t)k + 1] += begin[k];
+    std::vector<int32_t> list((size_t)listed), next(begin.begin(), begin.end() - 1);
+    for (int f = 0; f < c.frames; ++f)
+        if (c.map_of_frame[f] >= 0) list[(size_t)next[(size_t)c.map_of_frame[f]]++] = f;
+    const size_t all = (size_t)c.n_maps * per_map;
+    Maps m{std::vector<int32_t>(all), std::vector<int16_t>(all), std::vector<uint32_t>(all)};
+    if (in_place) m.sum = c.sum_in, m.n = c.n_in;  // (outputs == inputs: every cell read and written by its own lane)
+    const int32_t *s_in = c.sum_in.empty() ? nullptr : (in_place ? m.sum.data() : c.sum_in.data());
+    const int16_t *n_in = c.n_in.empty() ? nullptr : (in_place ? m.n.data() : c.n_in.data());
+    for (int b = 0; b < c.n_maps * runs; ++b)
+        for (int lane = 0; lane < PWPP_FUSE_RUN; ++lane) {
+            const int run = b % runs, k = b / runs, cell = run * PWPP_FUSE_RUN + lane;
+            if (cell >= per_map) continue;
+            const int jy = cell / c.G.NX, jx = cell - jy * c.G.NX;
+            const size_t base = (size_t)k * per_map;
+            int32_t sum = 0, n = 0;
+            pwpp_elev_start(s_in ? s_in + base : nullptr, n_in ? n_in + base : nullptr, jx, jy, c.shift[2 * k], c.shift[2 * k + 1], c.G.NX, c.G.NY, c.n_max, sum, n);
+            pwpp_elev_cell<RECIP, FAST>(c.G, P, sum, n, jx, jy, c.height.data(), c.frames, c.poses.data(), c.z_offset.data(), c.n_poses, list.data(), begin[k],
+                                        begin[(size_t)k + 1]);
+            m.sum[base + cell] = sum, m.n[base + cell] = (int16_t)n, m.mean[base + cell] = pwpp_elev_mean_bits(sum, n);
+        }
+    return m;
+}
+
+// 2: every state (n, sum) with |sum| <= n M and every |q| <= M, for small M and n_max: the update keeps |sum| <= n M and n <= n_max
+long long invariant_failures(long long &cases) {
+    long long bad = 0;
+    for (long long M = 1; M <= 6; ++M)
+        for (long long n_max = 1; n_max <= 9; ++n_max)
+            for (long long n = 0; n <= n_max; ++n)
+                for (long long s = -n * M; s <= n * M; ++s)
+                    for (long long q = -M; q <= M; ++q) {
+                        long long s2 = s, n2 = n;
+                        if (n2 < n_max) s2 += q, n2 += 1;
+                        else s2 = s2 - s2 / n2 + q;
+                        ++cases, bad += n2 > n_max || std::llabs(s2) > n2 * M;
+                    }
+    return bad;
+}
+
+// 3: the multiply-shift against the division
+long long share_failures(long long &cases) {
+    long long bad = 0;
+    const uint64_t M = PWPP_ELEV_M;
+    for (int d = 1; d <= PWPP_ELEV_MAX_N; ++d) {
+        const PwppElevationParams P = pwpp_elev_magic(d);
+        const uint64_t x_max = (uint64_t)d * M, two = (uint64_t)1 << P.shift, e = P.magic * (uint64_t)d - two;
+        // the hypothesis: the shift covers d, the product stays in 64 bits, e < d and x_max e < 2^sh
+        ++cases, bad += P.n_max != d || P.shift < 30 || P.shift > 40 || (two >> 30) < (uint64_t)d || P.magic > ((uint64_t)1 << 31) || P.magic * (uint64_t)d < two ||
+                        e >= (uint64_t)d || x_max * e >= two || x_max >= ((uint64_t)1 << 30);
+        // both signs at the ends of the range and around zero
+        for (int64_t s : {(int64_t)0, (int64_t)1, (int64_t)-1, (int64_t)d, (int64_t)-d, (int64_t)d - 1, (int64_t)1 - d, (int64_t)x_max, -(int64_t)x_max, (int64_t)x_max - 1, 1 - (int64_t)x_max})
+            ++cases, bad += pwpp_elev_share<true>((int32_t)s, P) != (int32_t)s / d || pwpp_elev_share<false>((int32_t)s, P) != (int32_t)s / d;
+    }
+    for (int d : {1, 2, 3, 5, 7, 255, 256, 257, 511, 512, 513, 1000, 1021, 1022, 1023}) {
+        const PwppElevationParams P = pwpp_elev_magic(d);
+        for (uint64_t k = 0; k <= M; ++k) {  // the segment [k d, k d + d): its first and (inside the range) its last element
+            const int32_t lo = (int32_t)(k * (uint64_t)d), hi = k < M ? lo + d - 1 : lo;
+            cases += 2;
+            bad += pwpp_elev_share<true>(lo, P) != (int32_t)k || pwpp_elev_share<true>(hi, P) != (int32_t)k;
+            bad += pwpp_elev_share<true>(-lo, P) != -(int32_t)k || pwpp_elev_share<true>(-hi, P) != -(int32_t)k;
+        }
+    }
+    return bad;
+}
+
+}  // namespace
+
+int main() {
+    std::mt19937_64 rng(20261019);
+    const auto uni = [&](int lo, int hi) { return (int)(lo + (long long)(rng() % (unsigned long long)(hi - lo + 1))); };
+    const auto real = [&](double lo, double hi) { return lo + (hi - lo) * (double)(rng() >> 11) / 9007199254740992.0; };
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    const float beyond = std::nextafter(1024.0f, 2048.0f);
+    long long cases = 0, mismatches = 0;
+    for (int t = 0; t < 2500; ++t) {
+        Case c;
+        const double cells[3] = {0.5, 0.25, 1.0}, frame_cells[4] = {0.5, 0.5, 0.3, 2.0};
+        c.G.cell = frame_cells[uni(0, 3)], c.G.CELL = cells[uni(0, 2)];
+        const bool recip = pwpp_fuse_reciprocal(c.G.cell, c.G.inv_cell);  // (0.3: the division alone)
+        c.G.nx = uni(1, 20), c.G.ny = uni(1, 20), c.G.NX = t % 7 == 0 ? uni(250, 300) : uni(1, 24), c.G.NY = t % 7 == 0 ? uni(1, 3) : uni(1, 24);
+        c.G.x0 = -0.5 * c.G.cell * c.G.nx, c.G.y0 = -0.5 * c.G.cell * c.G.ny;
+        c.G.X0 = -0.5 * c.G.CELL * c.G.NX + uni(-2, 2) * c.G.CELL, c.G.Y0 = -0.5 * c.G.CELL * c.G.NY;
+        const int n_maxes[6] = {1, 2, 3, 7, 100, 1023};
+        c.n_max = n_maxes[uni(0, 5)];
+        c.frames = uni(1, 12), c.n_maps = uni(1, 3);
+        c.n_poses = uni(0, 1) ? 1 : c.frames;
+        c.height.resize((size_t)c.frames * c.G.nx * c.G.ny);
+        const float special[] = {(float)inf, (float)-inf, 0.5f / 1024, 1.5f / 1024, -2.5f / 1024, -0.0f, 1024.0f, -1024.0f, beyond, -beyond, 1000.25f, -999.75f};
+        const bool wild = uni(0, 3) == 0;  // heights at the limits: the sums reach n M
+        for (float &z : c.height) {
+            const int r = uni(0, 99);
+            z = r < 25 ? (float)nan : (r < 35 ? special[uni(0, 11)] : (wild ? (uni(0, 1) ? 1024.0f : -1024.0f) * (float)real(0.9, 1.0) : (float)real(-3.0, 1.0)));
+        }
+        for (int i = 0; i < c.n_poses; ++i) {
+            double p[6] = {1, 0, 0, 0, 1, 0};
+            const int kind = uni(0, 7);
+            if (kind == 1) p[2] = uni(-6, 6) * c.G.cell, p[5] = uni(-6, 6) * c.G.cell;
+            if (kind == 2) p[0] = 0, p[1] = -1, p[3] = 1, p[4] = 0;
+            if (kind == 3) p[0] = -1;  // a mirror
+            if (kind == 4 || kind == 5) {
+                const double th = real(-3.2, 3.2);
+                p[0] = std::cos(th), p[1] = -std::sin(th), p[3] = std::sin(th), p[4] = std::cos(th), p[2] = real(-4, 4), p[5] = real(-4, 4);
+            }
+            if (kind == 6) p[2] = 1e6;                              // wholly outside
+            if (kind == 7) p[uni(0, 5)] = uni(0, 1) ? nan : inf;    // not finite: observes nothing
+            c.poses.insert(c.poses.end(), p, p + 6);
+            const int zk = uni(0, 9);
+            c.z_offset.push_back(zk == 0 ? nan : (zk == 1 ? inf : (zk == 2 ? 2000.0 : (zk < 6 ? 0.0 : real(-2.0, 2.0)))));
+        }
+        for (int f = 0; f < c.frames; ++f) c.map_of_frame.push_back(uni(-1, c.n_maps - 1));
+        for (int k = 0; k < c.n_maps; ++k) {
+            const int kind = uni(0, 3);
+            c.shift.push_back(kind == 0 ? 0 : (kind == 3 ? (uni(0, 1) ? INT32_MAX : INT32_MIN) : uni(-4, 4)));
+            c.shift.push_back(kind == 0 ? 0 : uni(-30, 30));
+        }
+        if (uni(0, 3)) {
+            c.sum_in.resize((size_t)c.n_maps * c.G.NX * c.G.NY), c.n_in.resize(c.sum_in.size());
+            for (size_t i = 0; i < c.sum_in.size(); ++i) {  // (outside what the normalisation keeps too)
+                const int kind = uni(0, 9);
+                c.n_in[i] = (int16_t)(kind == 0 ? (uni(0, 1) ? 32767 : -32768) : uni(-1, c.n_max + 1));
+                c.sum_in[i] = kind == 1 ? (uni(0, 1) ? INT32_MAX : INT32_MIN) : (int32_t)(real(-1.1, 1.1) * (double)std::min(std::max<int>(c.n_in[i], 1), c.n_max + 1) * 1048576.0 * (wild ? 1.0 : 0.002));
+            }
+        }
+        const Maps want = brute_force(c);
+        ++cases, mismatches += !(as_the_kernel<false, false>(c, false) == want);
+        ++cases, mismatches += !(as_the_kernel<false, true>(c, false) == want);
+        if (recip) ++cases, mismatches += !(as_the_kernel<true, true>(c, false) == want);
+        bool still = !c.sum_in.empty();
+        for (int32_t s : c.shift) still = still && s == 0;
+        if (still) ++cases, mismatches += !(as_the_kernel<false, false>(c, true) == want);
+    }
+    // the order examples of the contract: once capped, the order matters
+    {
+        Case c;
+        c.G = PwppFusionGeometry{0, 0, 1, 0, 0, 1, 1, 1, 1, 1, 1.0};
+        c.n_max = 2, c.frames = 2, c.n_maps = 1, c.n_poses = 1;
+        c.poses = {1, 0, 0, 0, 1, 0}, c.z_offset = {0.0}, c.map_of_frame = {0, 0}, c.shift = {0, 0}, c.sum_in = {3072}, c.n_in = {2};
+        c.height = {1.0f, 3.0f};
+        ++cases, mismatches += as_the_kernel<true, true>(c, false).sum[0] != 4352 || brute_force(c).sum[0] != 4352;
+        c.height = {3.0f, 1.0f};
+        ++cases, mismatches += as_the_kernel<true, true>(c, false).sum[0] != 3328 || brute_force(c).sum[0] != 3328;
+    }
+    const long long proofs = invariant_failures(cases) + share_failures(cases);
+    std::printf("elevation_check: %lld cases, %lld mismatches, %lld failed proof steps\n", cases, mismatches, proofs);
+    return mismatches == 0 && proofs == 0 ? 0 : 1;
+}
