@@ -954,6 +954,75 @@ PWPP_API int pwpp_fuse_ground(pwpp_handle *h, const pwpp_ground_grid *g /* flags
                               const int32_t *sum_in, const int16_t *n_in, int32_t *sum_out, int16_t *n_out, float *mean /* may be NULL */,
                               float *height /* the per-frame images, may be NULL: kept in the handle's buffer */);
 
+/* ---- terrain analysis of height images: step, slope, roughness, traversability cost (pwpp_terrain_grid, pwpp_terrain_ground) ------
+ * A height image says where the ground is, not whether a vehicle can stand or drive there.  For every cell these calls look at the
+ * (2r+1) x (2r+1) window around it and give the height step inside it, the slope of the least-squares plane through it, the
+ * roughness left after that plane is taken out, how many cells of the window are known, and a cost byte folded from the three.
+ * `height` is any height image: a frame's elevation image (pwpp_rasterize_ground) or the fused `mean` of n_maps elevation maps
+ * (pwpp_fuse_height_grid; then frames = n_maps).  The window sums are exact integers and the floating-point tail is written out
+ * operation by operation, so every output is a function of the heights alone and bit-reproducible.  Below r = p->radius.
+ *   known     A cell is known iff its height is finite and |height| <= 1024.0; then z = rint((double)height * 1024), ties to even
+ *             (the product is exact): the elevation fusion's observation with tz = 0, units of 2^-10 m, |z| <= 2^20.  -0.0 is 0.
+ *   window    of cell (ix, iy): the KNOWN cells (ix + dx, iy + dy), |dx|, |dy| <= r, that lie inside the frame's image; a cell
+ *             outside the image is unknown (the window is clipped, never clamped or wrapped, and never reaches another frame).
+ *             count = k, their number (<= 81), written for EVERY cell whether its centre is known or not.
+ *   centre unknown   step, slope and rough are the quiet NaN 0x7fc00000, cost is -1.
+ *   step      (float)((double)(zmax - zmin) / 1024.0) over the window: exact; 0 for k == 1.
+ *   moments   As mathematical integers over the window with x = dx, y = dy: the sums Sx, Sy, Sz, Sxx, Sxy, Syy, Sxz, Syz, Szz;
+ *             Cuv = k * Suv - Su * Sv;  D = Cxx * Cyy - Cxy^2;  A = Cxz * Cyy - Cyz * Cxy;  B = Cyz * Cxx - Cxz * Cxy;
+ *             N = D * Czz - A * Cxz - B * Cyz.  The least-squares plane has the gradient (A / D, B / D) in height units per cell
+ *             and the mean squared residual N / (D * k^2).  Adding one integer to every z changes none of D, A, B, N.
+ *   degenerate  D == 0: fewer than three known cells, or all of them on one line.  Then slope and rough are the quiet NaN and cost
+ *             is -1; step and count are defined all the same.
+ *   bounds    (r <= 4; csrc/pwpp_terrain.h has the proofs) Cxx, Cyy <= 43740; 0 <= D < 2^31; Czz <= 81^2 * 2^40 < 2^53; |Cxz|,
+ *             |Cyz| <= sqrt(Cxx * Czz) < 2^35; |A|, |B| < 2^51, exact in a double: all in int64.  0 <= N < 2^85 (Cauchy-Schwarz)
+ *             needs 128 bits; Nd is its nearest double, ties to even.
+ *   slope     In double, every operation rounded on its own, no FMA; rise over run:
+ *                 slope = (float)(sqrt((double)A * (double)A + (double)B * (double)B) / ((double)D * (1024.0 * cell)))
+ *   rough     rough = (float)(sqrt(Nd / ((double)D * (double)(k * k))) / 1024.0), metres.
+ *   cost      a traversability byte in the value range of the visibility operator's nav_msgs/OccupancyGrid byte: -1 as stated
+ *             above and where k < min_known; otherwise t = max(step / step_max, slope / slope_max, rough / rough_max), the ratios
+ *             in double from the float outputs and the float limits, an infinite limit giving the ratio 0 (that test is off);
+ *             cost = t >= 1 ? 100 : (int)floor(t * 100.0).
+ *   outputs   An output that is NULL is not written; a call may ask for cost alone.  All five NULL: PWPP_E_ARG.
+ *   overlaps  If any two of the caller's arrays overlap -- height against an output included -- PWPP_E_ARG.
+ *   terrain_ground  the per-frame images are exactly what pwpp_rasterize_ground(g, frame_first, frames) gives, the NaN blanking of
+ *             PWPP_GRID_GROUND_ONLY included, written for the caller where asked for and kept in the handle's cluster buffer
+ *             otherwise; the outputs are exactly what pwpp_terrain_grid gives for them with cell = g->cell.  Works after every
+ *             kind of estimate call; before any: PWPP_E_STATE.
+ *   mem       PWPP_MEM_HOST: every image is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- height, step, slope and rough 4-byte aligned, count and cost at any address --
+ *             enqueued on the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, height (pwpp_terrain_grid) or grid
+ *             (pwpp_terrain_ground), parameters; all five outputs null; frames or a side < 1, a side > 32768, nx * ny * frames
+ *             beyond 2^31 (pwpp_terrain_grid; pwpp_terrain_ground names the product with the frame range); a cell that is not
+ *             finite and positive (pwpp_terrain_grid) or g->flags other than 0 or PWPP_GRID_GROUND_ONLY (pwpp_terrain_ground);
+ *             radius outside 1 .. 4; min_known outside 1 .. (2r+1)^2; a limit that is a NaN or not > 0; pad_ != 0; the overlaps;
+ *             mem and, in PWPP_MEM_DEVICE, a float image below its alignment (pwpp_terrain_grid).  pwpp_terrain_ground checks last
+ *             what pwpp_rasterize_ground checks -- the grid's origin and cell, mem, PWPP_E_STATE before any estimate call, the
+ *             frame range -- and then the alignment.
+ *   buffers   No working image and no upload: the parameters travel in the launch.  The cluster buffer holds the staged images
+ *             (PWPP_MEM_HOST) and the kept raster; counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *             pwpp_terrain_grid needs a handle for its stream and this buffer only.
+ * The same bytes for every mem, alignment and value of the option "terrain_path".  With neither function called nothing is
+ * allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_TERRAIN 1
+typedef struct pwpp_terrain_params {   /* 24 bytes */
+    int32_t radius;      /* r: the window is (2r+1) x (2r+1) cells; 1 .. 4 */
+    int32_t min_known;   /* fewest known cells in the window for a cost; 1 .. (2r+1)^2 */
+    float   step_max, slope_max, rough_max;  /* metres, rise over run, metres: each > 0, +inf allowed (that test is off), not NaN */
+    int32_t pad_;        /* 0 */
+} pwpp_terrain_params;
+
+/* any height images: needs a handle (stream, buffer), no estimate call -- like pwpp_fuse_height_grid */
+PWPP_API int pwpp_terrain_grid(pwpp_handle *h, int nx, int ny, int frames, double cell, int mem,
+                               const float *height /* [frames][ny][nx]; NaN: unknown */, const pwpp_terrain_params *p,
+                               float *step, float *slope, float *rough, uint8_t *count, int8_t *cost /* same shape; each may be NULL, not all */);
+/* rasterize_ground + terrain for frames of the LAST estimate call, one enqueued sequence -- like pwpp_fuse_ground */
+PWPP_API int pwpp_terrain_ground(pwpp_handle *h, const pwpp_ground_grid *g /* flags: 0 or PWPP_GRID_GROUND_ONLY */, int frame_first, int frames, int mem,
+                                 const pwpp_terrain_params *p, float *step, float *slope, float *rough, uint8_t *count, int8_t *cost,
+                                 float *height /* the per-frame images, may be NULL: kept in the handle's buffer */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1093,6 +1162,9 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         a capped mean forgets by divisions as the contract writes them (the yardstick); "2": the product with the exact
  *                         reciprocal where the frame images' cell size is a power of two, and an exact multiply-shift by n_max; "0"
  *                         (default): what tools/elevation_fusion_cost.py decided.  The same bytes for every value.
+ *   "terrain_path"        how the terrain analysis sums a window (pwpp_terrain_grid, pwpp_terrain_ground): "1": every lane walks its whole
+ *                         window in LDS (the yardstick); "2": separable, the sums of every row over dx first, then 2r+1 rows combined with
+ *                         their dy; "0" (default): per radius what tools/terrain_cost.py decided.  The same bytes for every value.
  *   "match_path"          how the scan match reads the map (pwpp_match_grid, pwpp_match_obstacles): "1": every map read comes from
  *                         global memory (the yardstick of tools/scan_match_cost.py); "2": the rectangle of the map that the
  *                         landings of a (frame, candidate) reach under the window is copied into LDS once per workgroup where it

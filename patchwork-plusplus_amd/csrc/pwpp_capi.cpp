@@ -28,6 +28,7 @@
 #include "pwpp_elevation.h"
 #include "pwpp_fusion.h"
 #include "pwpp_match.h"
+#include "pwpp_terrain.h"
 #include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
@@ -253,6 +254,7 @@ struct pwpp_handle {
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
+    int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
     std::vector<std::vector<uint32_t>> uploads;  // the tables the last call that uploaded any built for its kernels: the sources of their copies (Staging::add_upload)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
@@ -2126,6 +2128,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "elevation_path=%s: 0, 1 or 2 expected", value);
         h->elevation_path = v;
+    } else if (k == "terrain_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "terrain_path=%s: 0, 1 or 2 expected", value);
+        h->terrain_path = v;
     } else if (k == "match_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
@@ -3202,6 +3208,114 @@ int pwpp_fuse_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first,
     if ((rc = ground_view(h, v))) return rc;
     int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), nullptr, h->stream);
     if (lrc == 0) lrc = height_launch(h, st, s, plan, frames);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// ---- terrain analysis: step, slope, roughness and cost of the window around every cell of a height image --------------------------
+namespace {
+static_assert(sizeof(pwpp_terrain_params) == 24, "pwpp_terrain_params is 24 bytes");
+constexpr const char *kTerrainWho = "the terrain analysis takes";
+
+// What both entry points check of the parameters and the overlaps, in the header's order, after the image's own checks; `cells`:
+// nx * ny * frames; fills the rule.  Touches no handle.
+int terrain_args(const pwpp_terrain_params *p, double cell, size_t cells, const float *height, const float *step, const float *slope, const float *rough,
+                 const uint8_t *count, const int8_t *cost, PwppTerrainRule &rule) {
+    if (p->radius < 1 || p->radius > PWPP_TERRAIN_MAX_R) return fail(PWPP_E_ARG, "radius %d: 1 .. 4 expected", p->radius);
+    const int window = (2 * p->radius + 1) * (2 * p->radius + 1);
+    if (p->min_known < 1 || p->min_known > window) return fail(PWPP_E_ARG, "min_known %d: 1 .. %d expected with radius %d", p->min_known, window, p->radius);
+    if (!(p->step_max > 0.0f) || !(p->slope_max > 0.0f) || !(p->rough_max > 0.0f))
+        return fail(PWPP_E_ARG, "limits %g (step), %g (slope), %g (rough): each > 0 expected, +inf allowed, not a NaN", (double)p->step_max,
+                    (double)p->slope_max, (double)p->rough_max);
+    if (p->pad_ != 0) return fail(PWPP_E_ARG, "pad_ %d of the terrain parameters: 0 expected", p->pad_);
+    struct Range {
+        const void *p;
+        size_t bytes;
+        const char *name;
+    };
+    const Range r[6] = {{height, cells * 4, "height"}, {step, cells * 4, "step"}, {slope, cells * 4, "slope"},
+                        {rough, cells * 4, "rough"},   {count, cells, "count"},   {cost, cells, "cost"}};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j)
+            if (ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) return fail(PWPP_E_ARG, "%s and %s overlap", r[i].name, r[j].name);
+    rule = PwppTerrainRule{p->radius, p->min_known, p->step_max, p->slope_max, p->rough_max, 1024.0 * cell};
+    return PWPP_OK;
+}
+
+// (after mem: what PWPP_MEM_DEVICE asks of the arrays -- floats 4-byte aligned, bytes anywhere)
+int terrain_alignment_args(int mem, const void *height, const void *step, const void *slope, const void *rough) {
+    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
+    const auto off = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (off(height) || off(step) || off(slope) || off(rough))
+        return fail(PWPP_E_ARG, "the %s must be 4-byte aligned", off(height) ? "height images" : (off(step) ? "step" : (off(slope) ? "slope" : "rough")));
+    return PWPP_OK;
+}
+
+// (`height` is the height images' section: the caller's, or the ground raster's)
+struct TerrainSections {
+    int height, step, slope, rough, count, cost;
+};
+TerrainSections terrain_sections(Staging &st, size_t cells, int s_height, float *step, float *slope, float *rough, uint8_t *count, int8_t *cost) {
+    TerrainSections s;
+    const size_t byte_words = (cells + 3) / 4;
+    s.height = s_height;
+    s.step = st.add(step ? cells : 0, step, Staging::kOut);
+    s.slope = st.add(slope ? cells : 0, slope, Staging::kOut);
+    s.rough = st.add(rough ? cells : 0, rough, Staging::kOut);
+    s.count = st.add(count ? byte_words : 0, count, Staging::kOut, count ? cells : 0);
+    s.cost = st.add(cost ? byte_words : 0, cost, Staging::kOut, cost ? cells : 0);
+    return s;
+}
+int terrain_launch(pwpp_handle *h, const Staging &st, const TerrainSections &s, const PwppTerrainRule &rule, int nx, int ny, int frames) {
+    return pwpp_launch_terrain(&rule, nx, ny, frames, st.dev<const float>(s.height), st.dev<float>(s.step), st.dev<float>(s.slope), st.dev<float>(s.rough),
+                               st.dev<uint8_t>(s.count), st.dev<int8_t>(s.cost), h->terrain_path, h->stream);
+}
+}  // namespace
+
+int pwpp_terrain_grid(pwpp_handle *h, int nx, int ny, int frames, double cell, int mem, const float *height, const pwpp_terrain_params *p, float *step,
+                      float *slope, float *rough, uint8_t *count, int8_t *cost) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!height || !p) return fail(PWPP_E_ARG, "null %s", !height ? "height images" : "terrain parameters");
+    if (!step && !slope && !rough && !count && !cost) return fail(PWPP_E_ARG, "null outputs: at least one of step, slope, rough, count and cost expected");
+    size_t cells = 0;
+    int rc = image_args(nx, ny, frames, kTerrainWho, cells);
+    if (rc) return rc;
+    if (!(cell > 0.0) || !std::isfinite(cell)) return fail(PWPP_E_ARG, "cell size %g: finite and positive expected", cell);
+    PwppTerrainRule rule;
+    if ((rc = terrain_args(p, cell, cells, height, step, slope, rough, count, cost, rule))) return rc;
+    if ((rc = mem_args(mem, kTerrainWho))) return rc;
+    if ((rc = terrain_alignment_args(mem, height, step, slope, rough))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_height = st.add(cells, height, Staging::kIn);
+    const TerrainSections s = terrain_sections(st, cells, s_height, step, slope, rough, count, cost);
+    return run_on_image(h, st, [&] { return terrain_launch(h, st, s, rule, nx, ny, frames); });
+}
+
+// pwpp_rasterize_ground into a section of the cluster buffer (or the caller's images) and pwpp_terrain_grid on it, one enqueued sequence.
+int pwpp_terrain_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, const pwpp_terrain_params *p, float *step,
+                        float *slope, float *rough, uint8_t *count, int8_t *cost, float *height) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !p) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : "terrain parameters");
+    if (!step && !slope && !rough && !count && !cost) return fail(PWPP_E_ARG, "null outputs: at least one of step, slope, rough, count and cost expected");
+    if (frames < 1 || g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, g->nx, g->ny);
+    int rc = side_args(g->nx, g->ny, kTerrainWho);
+    if (rc) return rc;
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    PwppTerrainRule rule;
+    // (the byte ranges of the overlap check: sides <= 2^15 and frames < 2^31, the product fits 64 bits; ground_grid_args names one beyond 2^31)
+    size_t cells = (size_t)g->nx * (size_t)g->ny * (size_t)frames;
+    if ((rc = terrain_args(p, g->cell, cells, height, step, slope, rough, count, cost, rule))) return rc;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = terrain_alignment_args(mem, height, step, slope, rough))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_height = add_image(st, cells, height, true);
+    const TerrainSections s = terrain_sections(st, cells, s_height, step, slope, rough, count, cost);
+    if ((rc = st.begin())) return rc;
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    if ((rc = ground_view(h, v))) return rc;
+    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), nullptr, h->stream);
+    if (lrc == 0) lrc = terrain_launch(h, st, s, rule, g->nx, g->ny, frames);
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 

@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -341,6 +341,9 @@ int pwpp_launch_fuse_grid(const struct PwppFusionGeometry *G, const struct PwppF
 int pwpp_launch_fuse_height(const struct PwppFusionGeometry *G, const struct PwppElevationParams *P, int frames, const float *height, const double *poses,
                             const double *z_offset, int n_poses, int n_maps, const int32_t *begin, const int32_t *list, int listed, const int32_t *shift,
                             const int32_t *sum_in, const int16_t *n_in, int32_t *sum_out, int16_t *n_out, float *mean, int path, hipStream_t stream);
+// pwpp_terrain.hip
+int pwpp_launch_terrain(const struct PwppTerrainRule *R, int nx, int ny, int frames, const float *height, float *step, float *slope, float *rough,
+                        uint8_t *count, int8_t *cost, int path, hipStream_t stream);
 // pwpp_match.hip
 size_t pwpp_match_work_words(int nx, int ny, int frames, int n_candidates, int wx, int wy);
 int pwpp_launch_match_grid(const struct PwppMatchGeometry *G, int frames, const int8_t *occupancy, const double *candidates, int n_sets, int n_candidates,

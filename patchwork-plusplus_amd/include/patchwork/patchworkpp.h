@@ -492,6 +492,40 @@ public:
         for (size_t i = 0; i < cells; ++i) img.data()[i] = map.mean.size() == cells ? map.mean[i] : std::numeric_limits<float>::quiet_NaN();
         return img;
     }
+    // ... and whether a vehicle can stand or drive on that ground (pwpp_terrain_ground, pwpp_terrain_grid): per cell the height step,
+    // the slope (rise over run) and the roughness (metres) of the (2 radius + 1)^2 window around it, NaN where undefined, the number
+    // of known cells in the window, and a traversability cost: -1 (none: the cell or its plane is unknown, or fewer than min_known
+    // cells), else 0 .. 100, the largest of step / step_max, slope / slope_max and rough / rough_max in per cent, capped.
+    struct TerrainParams {
+        int radius, min_known;                 // 1 .. 4; 1 .. (2 radius + 1)^2
+        float step_max, slope_max, rough_max;  // an infinite limit: that test is off
+        TerrainParams()  // (a constructor, not member initialisers: the class is a default argument of its enclosing class's members)
+            : radius(1), min_known(3), step_max(std::numeric_limits<float>::infinity()), slope_max(std::numeric_limits<float>::infinity()),
+              rough_max(std::numeric_limits<float>::infinity()) {}
+    };
+    struct Terrain {
+        int nx = 0, ny = 0;
+        std::vector<float> step, slope, rough;  // ny x nx, row-major: row iy, column ix
+        std::vector<uint8_t> count;             // same shape
+        std::vector<int8_t> cost;               // same shape
+    };
+    // (on the last frame's elevation image over the grid (x0, y0, cell, nx, ny))
+    Terrain getTerrain(double x0, double y0, double cell, int nx, int ny, const TerrainParams &params = TerrainParams(), bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        const pwpp_terrain_params p = {params.radius, params.min_known, params.step_max, params.slope_max, params.rough_max, 0};
+        Terrain t = terrain_images(nx, ny);
+        check(pwpp_terrain_ground(h_, &g, 0, 1, PWPP_MEM_HOST, &p, t.step.data(), t.slope.data(), t.rough.data(), t.count.data(), t.cost.data(), nullptr));
+        return terrain_sized(t);
+    }
+    // (on the mean of a fused elevation map)
+    Terrain fusedTerrain(const FusedElevationMap &map, const TerrainParams &params = TerrainParams()) {
+        const pwpp_terrain_params p = {params.radius, params.min_known, params.step_max, params.slope_max, params.rough_max, 0};
+        Terrain t = terrain_images(map.nx, map.ny);
+        if (map.mean.size() != (size_t)t.nx * (size_t)t.ny || map.mean.empty()) throw std::invalid_argument("fusedTerrain: the map has no mean image of ny x nx cells");
+        check(pwpp_terrain_grid(h_, map.nx, map.ny, 1, map.cell, PWPP_MEM_HOST, map.mean.data(), &p, t.step.data(), t.slope.data(), t.rough.data(),
+                                t.count.data(), t.cost.data()));
+        return terrain_sized(t);
+    }
     // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},
     // the prior first) and every shift of [-wx, wx] x [-wy, wy] map cells, the sum of log_odds under the occupied cells of the
     // frame's visibility bytes; the best by the contract's order, and `pose`, the winning candidate moved by the winning shift
@@ -586,6 +620,19 @@ private:
     patchwork::Params params_;
     pwpp_handle *h_;
 
+    // (the five images of a terrain call, with room for one cell where the grid has none: the library names the bad argument)
+    static Terrain terrain_images(int nx, int ny) {
+        Terrain t;
+        t.nx = nx > 0 ? nx : 0, t.ny = ny > 0 ? ny : 0;
+        const size_t cells = (size_t)t.nx * (size_t)t.ny, room = cells ? cells : 1;
+        t.step.assign(room, 0.0f), t.slope.assign(room, 0.0f), t.rough.assign(room, 0.0f), t.count.assign(room, 0), t.cost.assign(room, -1);
+        return t;
+    }
+    static Terrain &terrain_sized(Terrain &t) {
+        const size_t cells = (size_t)t.nx * (size_t)t.ny;
+        t.step.resize(cells), t.slope.resize(cells), t.rough.resize(cells), t.count.resize(cells), t.cost.resize(cells);
+        return t;
+    }
 #ifdef PWPP_HAVE_EIGEN
     static Eigen::MatrixX3f to_eigen(const Cloud &c) {
         Eigen::MatrixX3f m(c.rows(), 3);

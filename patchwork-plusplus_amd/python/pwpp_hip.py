@@ -100,6 +100,11 @@ class HeightMap(ctypes.Structure):  # pwpp_height_map (40 bytes): the grid of th
                 ("n_max", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+class TerrainParams(ctypes.Structure):  # pwpp_terrain_params (24 bytes): the window's radius, the fewest known cells for a cost, the three limits of the cost
+    _fields_ = [("radius", ctypes.c_int32), ("min_known", ctypes.c_int32), ("step_max", ctypes.c_float), ("slope_max", ctypes.c_float),
+                ("rough_max", ctypes.c_float), ("pad_", ctypes.c_int32)]
+
+
 class MatchBest(ctypes.Structure):  # pwpp_match_best (24 bytes): the winning sum, its candidate (-1: skipped) and shift, the frame's occupied cells
     _fields_ = [("score", ctypes.c_int64), ("candidate", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("cells", ctypes.c_int32)]
 
@@ -226,6 +231,10 @@ def load():
             gp, hp = ctypes.POINTER(GroundGrid), ctypes.POINTER(HeightMap)
             L.pwpp_fuse_height_grid.argtypes = [vp, gp, ci, ci, vp, vp, vp, ci, vp, hp, ci, vp, vp, vp, vp, vp, vp]
             L.pwpp_fuse_ground.argtypes = [vp, gp, ci, ci, ci, vp, vp, ci, vp, hp, ci, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pwpp_terrain_grid"):  # (as above: an older build has no terrain analysis)
+            gp, tp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams)
+            L.pwpp_terrain_grid.argtypes = [vp, ci, ci, ci, ctypes.c_double, ci, vp, tp, vp, vp, vp, vp, vp]
+            L.pwpp_terrain_ground.argtypes = [vp, gp, ci, ci, ci, tp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -1156,6 +1165,55 @@ class Handle:
         self._check(self._L.pwpp_fuse_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, _hp(pose), _hp(zo), len(pose), _hp(mof),
                                              ctypes.byref(hmap), int(n_maps), _hp(shift), _dp(sum_in_ptr), _dp(n_in_ptr), _dp(sum_out_ptr), _dp(n_out_ptr),
                                              _dp(mean_ptr), _dp(height_ptr)))
+
+    _TERRAIN_OUTPUTS = (("step", np.float32), ("slope", np.float32), ("rough", np.float32), ("count", np.uint8), ("cost", np.int8))
+
+    @classmethod
+    def _terrain_outputs(cls, shape, wants):
+        """The output arrays of a terrain call, None where not wanted, in the order step, slope, rough, count, cost."""
+        return tuple(np.empty(shape, dtype) if want else None for (_, dtype), want in zip(cls._TERRAIN_OUTPUTS, wants))
+
+    def terrain_grid(self, height, cell, params, want_step=True, want_slope=True, want_rough=True, want_count=True, want_cost=True):
+        """The terrain analysis of the (frames, ny, nx) or (ny, nx) float32 height images (NaN: unknown) with cells of `cell` metres
+        under the TerrainParams `params`: per cell the height step, the slope (rise over run) and the roughness of the
+        (2r+1) x (2r+1) window around it (float32, NaN where undefined), the uint8 count of known cells in the window and the int8
+        traversability cost (-1: none, 0 .. 100).  Works before any estimate call.  Returns (step, slope, rough, count, cost) in
+        the shape of `height`, None for an output that is not wanted.  The rules: include/pwpp.h."""
+        hgt = np.ascontiguousarray(height, np.float32)
+        h3 = hgt.reshape((1,) + hgt.shape) if hgt.ndim == 2 else hgt
+        if h3.ndim != 3:
+            raise ValueError("height: a (frames, ny, nx) or (ny, nx) image expected")
+        out = self._terrain_outputs(hgt.shape, (want_step, want_slope, want_rough, want_count, want_cost))
+        self._check(self._L.pwpp_terrain_grid(self._h, h3.shape[2], h3.shape[1], h3.shape[0], float(cell), MEM_HOST, _hp(h3), ctypes.byref(params),
+                                              *[_hp(a) for a in out]))
+        return out
+
+    def terrain_grid_device(self, nx, ny, frames, cell, height_ptr, params, step_ptr=0, slope_ptr=0, rough_ptr=0, count_ptr=0, cost_ptr=0):
+        """terrain_grid on device memory: addresses of the (frames, ny, nx) float32 height images and of the float32 step, slope and
+        rough, the uint8 count and the int8 cost images (0: not wanted); the floats 4-byte aligned.  Enqueued on the handle's
+        stream; complete after synchronize()."""
+        self._check(self._L.pwpp_terrain_grid(self._h, int(nx), int(ny), int(frames), float(cell), MEM_DEVICE, _dp(height_ptr), ctypes.byref(params),
+                                              _dp(step_ptr), _dp(slope_ptr), _dp(rough_ptr), _dp(count_ptr), _dp(cost_ptr)))
+
+    def terrain_ground(self, x0, y0, cell, nx, ny, params, frame_first=0, frames=None, ground_only=False, want_step=True, want_slope=True,
+                       want_rough=True, want_count=True, want_cost=True, want_frames=False):
+        """rasterize_ground and terrain_grid in one call, for frames of the last estimate call: (step, slope, rough, count, cost) as
+        terrain_grid gives them for the (frames, ny, nx) elevation images of rasterize_ground; want_frames: then those images too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        shape = self._grid_shape(g, frames)
+        out = self._terrain_outputs(shape, (want_step, want_slope, want_rough, want_count, want_cost))
+        hgt = np.empty(shape, np.float32) if want_frames else None
+        self._check(self._L.pwpp_terrain_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, ctypes.byref(params),
+                                                *([_hp(a) for a in out] + [_hp(hgt)])))
+        return out + ((hgt,) if want_frames else ())
+
+    def terrain_ground_device(self, x0, y0, cell, nx, ny, params, step_ptr=0, slope_ptr=0, rough_ptr=0, count_ptr=0, cost_ptr=0, height_ptr=0,
+                              frame_first=0, frames=None, ground_only=False):
+        """terrain_ground into device memory: addresses as in terrain_grid_device, height_ptr the (frames, ny, nx) float32 images of
+        the frames (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_terrain_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, ctypes.byref(params), _dp(step_ptr),
+                                                _dp(slope_ptr), _dp(rough_ptr), _dp(count_ptr), _dp(cost_ptr), _dp(height_ptr)))
 
     @staticmethod
     def _match_host(candidates, frames, map_of_frame):

@@ -102,6 +102,19 @@ void estimate_ground(PatchWorkpp &self, py::array cloud) {
 
 #define PWPP_FIELD(name) cls.def_readwrite(#name, &Params::name)
 
+// (step, slope, rough, count, cost) of a terrain call as (ny, nx) arrays
+template <class T>
+py::array_t<T> terrain_image(const std::vector<T> &v, int nx, int ny) {
+    py::array_t<T> a({(py::ssize_t)ny, (py::ssize_t)nx});
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+    return a;
+}
+template <class Terrain>
+py::tuple terrain_tuple(const Terrain &t) {
+    return py::make_tuple(terrain_image(t.step, t.nx, t.ny), terrain_image(t.slope, t.nx, t.ny), terrain_image(t.rough, t.nx, t.ny),
+                          terrain_image(t.count, t.nx, t.ny), terrain_image(t.cost, t.nx, t.ny));
+}
+
 PYBIND11_MODULE(pypatchworkpp, m) {
     m.doc() = "Python Patchwork++ (MI355X / HIP backend)";
     m.attr("__version__") = "0.0.1";
@@ -166,6 +179,14 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def_readwrite("nx", &PatchWorkpp::FusedElevationMap::nx)
         .def_readwrite("ny", &PatchWorkpp::FusedElevationMap::ny)
         .def_readwrite("n_max", &PatchWorkpp::FusedElevationMap::n_max);
+
+    py::class_<PatchWorkpp::TerrainParams>(m, "TerrainParams")  // the window and the limits of getTerrain and fusedTerrain
+        .def(py::init<>())
+        .def_readwrite("radius", &PatchWorkpp::TerrainParams::radius)
+        .def_readwrite("min_known", &PatchWorkpp::TerrainParams::min_known)
+        .def_readwrite("step_max", &PatchWorkpp::TerrainParams::step_max)
+        .def_readwrite("slope_max", &PatchWorkpp::TerrainParams::slope_max)
+        .def_readwrite("rough_max", &PatchWorkpp::TerrainParams::rough_max);
 
     py::class_<PatchWorkpp>(m, "patchworkpp")
         .def(py::init<Params>())
@@ -260,6 +281,17 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              py::arg("ground_only") = false, py::arg("shift_x") = 0, py::arg("shift_y") = 0)
         .def("getFusedElevation", [](PatchWorkpp &, const PatchWorkpp::FusedElevationMap &map) { return to_numpy(PatchWorkpp::fusedElevationRows(map)); },
              py::arg("map"))
+        .def("getTerrain",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, const PatchWorkpp::TerrainParams &params, bool ground_only) {
+                 return terrain_tuple(s.getTerrain(x0, y0, cell, nx, ny, params, ground_only));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("params") = PatchWorkpp::TerrainParams(),
+             py::arg("ground_only") = false)
+        .def("fusedTerrain",
+             [](PatchWorkpp &s, const PatchWorkpp::FusedElevationMap &map, const PatchWorkpp::TerrainParams &params) {
+                 return terrain_tuple(s.fusedTerrain(map, params));
+             },
+             py::arg("map"), py::arg("params") = PatchWorkpp::TerrainParams())
         .def("matchObstacleMap",
              [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, const std::vector<std::array<double, 6>> &candidates, int wx, int wy, double x0,
                 double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y) {
