@@ -2755,6 +2755,9 @@ extern "C" int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEv
         // A lane adds up at most 2047 points (Moments).  A patch is dealt out in chunks of 8 points per lane, its two
         // parts separately, the chunks of the four-waves kernel four at a time: a lane sees up to n / G + 16 (n / 256 + 24)
         // points.  Rows of 16 lanes in k_fit_w64 keep their ten totals in int64, which ends at 2047 points per PATCH.
+        // (A class ends where a size bucket begins, so the largest patches an entry really takes are 2047 for W16, 14 335 / 28 671 /
+        // 57 343 for S8 / S16 / S32, 65 535 for S64 / W64 and 458 751 for B / H: a lane sees 1793 points at most there, 129 in a row of 16 --
+        // tests/fit_limits_ref.py restates the dealing, tests/test_gpu_fit_limits.py runs those sizes on saturated coordinates.)
         const unsigned lane_cap = mode == 'B' || mode == 'H' ? 2023u * 256u : (mode == 'W' && g == 16 ? 2047u : 2031u * (unsigned)g);
         if (upper > lane_cap) upper = lane_cap;
         if (upper > 65535u && mode != 'B' && mode != 'H') upper = 65535u;  // one wave per patch: keep the classes short
