@@ -1,7 +1,8 @@
 """The obstacle clusters (pwpp_label_grid) restated by the rules of include/pwpp.h: a plain flood fill over the occupied cells of
 a count image -- label image, cluster table, number of clusters -- a second, independent restatement (iterated minimum
-propagation) to check the first against, and the pattern set both test files run.  Shared by
-tests/test_obstacle_clusters_cpu.py and tests/test_gpu_obstacle_clusters.py."""
+propagation) to check the first against, and the pattern set the test files run: the small shapes, and the large ones at which a
+frame has more chunks than one round of the rank scan takes.  Shared by tests/test_obstacle_clusters_cpu.py,
+tests/test_gpu_obstacle_clusters.py and tests/test_gpu_obstacle_clusters_large.py."""
 from collections import deque
 
 import numpy as np
@@ -15,6 +16,44 @@ assert CLUSTER_DTYPE.itemsize == 48
 TILE_X, TILE_Y = 64, 16  # the tile of the library's tile pass: the patterns aim at its edges
 SHAPES = [(1, 1), (7, 5), (64, 16), (65, 17), (129, 33), (257, 3), (3, 257)]  # (nx, ny)
 PATTERNS = ["empty", "full", "checker", "diagonals", "comb", "spiral", "serpentine", "random0.1", "random0.3", "random0.59", "corner"]
+
+# The large shapes, kept apart from SHAPES (the distance tests import SHAPES).  The ranks come from roots counted per CHUNK of
+# PWPP_CL_CHUNK consecutive cells, and one workgroup scans a frame's chunk counts SCAN_BLOCK (kClBlock) at a time with the total
+# carried between rounds: a second round needs more than CHUNK * SCAN_BLOCK = 65 536 cells in a frame.
+CHUNK = 256       # PWPP_CL_CHUNK of csrc/pwpp_unionfind.h
+SCAN_BLOCK = 256  # kClBlock of csrc/pwpp_clusters.hip: chunk counts per round of k_cl_scan
+LARGE_SHAPES = [(256, 256), (257, 256), (1030, 132)]
+# (nx, ny): cells, chunks, chunks of every scan round, tiles (x, y)
+LARGE_PLAN = {(256, 256): (65536, 256, [256], (4, 16)),          # the cost tool's shape: one round, full
+              (257, 256): (65792, 257, [256, 1], (5, 16)),         # the last tile column is one cell wide
+              (1030, 132): (135960, 532, [256, 256, 20], (17, 9))}  # the last chunk has 24 cells; nx % 64 != 0, ny % 16 != 0
+LARGE_PATTERNS = ["random0.1", "random0.3", "random0.59", "checker", "diagonals", "comb", "spiral", "serpentine", "full"]
+LARGE_CASES = [(name, 1, c) for name in LARGE_PATTERNS for c in (4, 8)] + [("random0.3", 2, 4), ("random0.3", 2, 8)]  # (name, min_count, connectivity)
+
+
+def chunk_plan(nx, ny):
+    """(cells, chunks, chunks of every scan round, tiles (x, y)) of an nx x ny frame, from CHUNK, SCAN_BLOCK and the tile."""
+    cells = nx * ny
+    chunks = -(-cells // CHUNK)
+    rounds = [min(SCAN_BLOCK, chunks - b) for b in range(0, chunks, SCAN_BLOCK)]
+    return cells, chunks, rounds, (-(-nx // TILE_X), -(-ny // TILE_Y))
+
+
+def roots_beyond(table, chunk):
+    """The number of clusters whose first cell lies in chunk `chunk` or a later one: their ranks need the scan that far."""
+    return int((table["first_cell"] // CHUNK >= chunk).sum())
+
+
+def by_construction(name, conn, count, min_count=1):
+    """(label, n) of a structured pattern, stated without any search: one cluster on the occupied cells, or, for the checkerboard
+    with edge neighbours, every occupied cell a cluster of its own, numbered in row-major order.  None: no such statement."""
+    occ = np.asarray(count) >= min_count
+    if name in ("full", "comb", "spiral", "serpentine") or (name == "checker" and conn == 8):
+        return np.where(occ, 0, -1).astype(np.int32), 1
+    if name == "checker" and conn == 4:
+        rank = (np.cumsum(occ.reshape(-1)) - 1).reshape(occ.shape)
+        return np.where(occ, rank, -1).astype(np.int32), int(occ.sum())
+    return None
 
 
 def neighbours(connectivity):
@@ -140,10 +179,12 @@ def occupancy(name, nx, ny, rng):
         occ = np.zeros((ny, nx), bool)
         cx, cy, d, stuck = 0, 0, 0, 0
         occ[0, 0] = True
-        while stuck < 2:  # walk on while the next cell is inside and the one behind it is free; turn right otherwise
+        while stuck < 2:  # walk on while the next cell is inside and free and the one behind it is free; turn right otherwise
             dx, dy = ((1, 0), (0, 1), (-1, 0), (0, -1))[d]
             qx, qy, ax, ay = cx + dx, cy + dy, cx + 2 * dx, cy + 2 * dy
-            if 0 <= qx < nx and 0 <= qy < ny and not (0 <= ax < nx and 0 <= ay < ny and occ[ay, ax]):
+            # (never back onto the path: on a square of even side the walk would otherwise circle in the centre for ever; the
+            # pattern of every shape at which it ended without this is unchanged)
+            if 0 <= qx < nx and 0 <= qy < ny and not occ[qy, qx] and not (0 <= ax < nx and 0 <= ay < ny and occ[ay, ax]):
                 cx, cy, stuck = qx, qy, 0
                 occ[cy, cx] = True
             else:

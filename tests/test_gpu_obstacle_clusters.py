@@ -3,8 +3,10 @@ tests/obstacle_clusters_ref.py through pwpp_label_grid from host and from device
 label image, table, number of clusters -- at both connectivities and min_count 1 and 2; several frames in one call, misaligned
 device images, truncated tables, repeated calls, both values of the option "clusters_path"; and pwpp_label_obstacles against
 pwpp_rasterize_obstacles + pwpp_label_grid, its per-point cluster ids against a recomputation from the library's own rows and
-queries, in every kind of call -- and that asking changes nothing else.  Shapes are small on purpose: the largest image has
-4257 cells, the clouds ~3 k points."""
+queries, in every kind of call -- and that asking changes nothing else.  Shapes are small here: the largest image has 4257 cells
+(17 chunks: one partial round of k_cl_scan, 3 x 3 tiles), the clouds ~3 k points.  Frames of more than 65 536 cells -- a second and
+third scan round, components across dozens of tiles, tables of tens of thousands of rows -- are
+tests/test_gpu_obstacle_clusters_large.py's."""
 import ctypes
 import functools
 

@@ -1,6 +1,7 @@
 """No-GPU checks of the obstacle clusters (pwpp_label_grid, pwpp_label_obstacles): the exports, the feature macro, the ctypes
 prototypes and the bindings' methods, the argument checks that need no device, the C++ mirror in both flavours -- the flood fill
-the GPU tests compare against (tests/obstacle_clusters_ref.py) against a second restatement over the whole pattern set -- and the
+the GPU tests compare against (tests/obstacle_clusters_ref.py) against a second restatement over the whole pattern set, and at the
+large shapes (more chunks than one round of the rank scan) also against the structured patterns' construction -- and the
 stand-alone program that runs the kernels' union-find primitives and pass sequence on the host against a flood fill of its own
 (tools/unionfind_check.cpp), built with the address and undefined-behaviour sanitizers where the toolchain has them."""
 import ctypes
@@ -154,6 +155,67 @@ def test_flood_fill_against_minimum_propagation(shape):
     assert seen > 0
 
 
+# ---- the large shapes: more chunks than one round of the rank scan takes ------------------------------------------------------------
+def test_large_shapes_need_the_scan_rounds_the_table_says():
+    """The table of oc.LARGE_PLAN from the constants as the kernels have them: a retuned chunk or block fails here instead of
+    quietly taking the point out of the large shapes."""
+    unionfind = open(os.path.join(PKG, "csrc", "pwpp_unionfind.h")).read()
+    kernels = open(os.path.join(PKG, "csrc", "pwpp_clusters.hip")).read()
+    assert "#define PWPP_CL_CHUNK %d " % oc.CHUNK in unionfind
+    assert "#define PWPP_CL_TILE_X %d " % oc.TILE_X in unionfind and "#define PWPP_CL_TILE_Y %d\n" % oc.TILE_Y in unionfind
+    assert "constexpr int kClBlock = %d;" % oc.SCAN_BLOCK in kernels and "base += kClBlock" in kernels
+    assert sorted(oc.LARGE_PLAN) == sorted(oc.LARGE_SHAPES) and not set(oc.LARGE_SHAPES) & set(oc.SHAPES)
+    for shape in oc.LARGE_SHAPES:
+        assert oc.chunk_plan(*shape) == oc.LARGE_PLAN[shape], shape
+    assert max(oc.chunk_plan(*s)[1] for s in oc.SHAPES) == 17  # the small shapes: one round, never full
+    assert oc.chunk_plan(256, 256)[2] == [oc.SCAN_BLOCK]       # one round, full
+    assert oc.chunk_plan(257, 256)[2] == [oc.SCAN_BLOCK, 1] and 257 % oc.TILE_X == 1
+    assert oc.chunk_plan(1030, 132)[2] == [oc.SCAN_BLOCK, oc.SCAN_BLOCK, 20] and 1030 * 132 % oc.CHUNK == 24
+    assert 1030 % oc.TILE_X and 132 % oc.TILE_Y
+    assert all(name in oc.PATTERNS for name in oc.LARGE_PATTERNS) and len(oc.LARGE_CASES) == 20
+
+
+@pytest.mark.parametrize("connectivity", [4, 8])
+@pytest.mark.parametrize("shape", oc.LARGE_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_flood_fill_at_the_large_shapes_against_anchors_that_share_nothing_with_it(shape, connectivity):
+    """Minimum propagation where paths are short (the random patterns, checker, diagonals, comb: a spiral or serpentine needs an
+    iteration per cell of its path), and the structured patterns by construction.  Then the two conditions that make the scan's
+    carry visible in the labels: enough clusters whose first cell lies beyond chunk 255, and beyond chunk 511."""
+    nx, ny = shape
+    cells, chunks, rounds, _ = oc.chunk_plan(nx, ny)
+    for name, min_count, conn in oc.LARGE_CASES:
+        if conn != connectivity:
+            continue
+        count, top = oc.pattern(name, nx, ny, min_count)
+        label, table, n = oc.flood_fill(count, top, min_count, conn)
+        what = "%s %dx%d min_count %d connectivity %d" % (name, nx, ny, min_count, conn)
+        occ = count >= min_count
+        assert np.array_equal(label >= 0, occ) and len(table) == n and (np.diff(table["first_cell"]) > 0).all(), what
+        assert table["cells"].sum() == occ.sum() and table["points"].sum() == count[occ].sum(), what
+        anchors = 0
+        if name.startswith("random") or name in ("checker", "diagonals", "comb"):
+            label2, n2 = oc.min_propagation(count, min_count, conn)
+            assert n == n2 and np.array_equal(label, label2), what
+            anchors += 1
+        built = oc.by_construction(name, conn, count, min_count)
+        if built is not None:
+            assert n == built[1] and np.array_equal(label, built[0]), what
+            anchors += 1
+        assert anchors > 0, what
+        if name == "checker":
+            assert n == ((cells + 1) // 2 if conn == 4 else 1), what
+        beyond_1, beyond_2 = oc.roots_beyond(table, oc.SCAN_BLOCK), oc.roots_beyond(table, 2 * oc.SCAN_BLOCK)
+        print("%s: n %d, roots beyond chunk 255: %d, beyond chunk 511: %d" % (what, n, beyond_1, beyond_2))
+        if conn == 4 and min_count == 1 and name in ("random0.3", "checker"):
+            if len(rounds) > 1:
+                # the cells beyond chunk 255: 257 x 256 has only 256 of them, a part of its last row, of which random0.3 occupies
+                # about 77 -- 100 roots cannot be there; at least 10 is asked of it, as of the third round below
+                few = name == "random0.3" and cells - oc.CHUNK * oc.SCAN_BLOCK <= oc.CHUNK
+                assert beyond_1 >= (10 if few else 100), what
+            if len(rounds) > 2:
+                assert beyond_2 >= 10, what
+
+
 def test_frames_never_connect_in_the_restatement():
     count = np.zeros((2, 5, 7), np.int32)
     count[0, -1, :] = 1
@@ -183,4 +245,4 @@ def test_unionfind_program_builds_and_passes(tmp_path):
                    ["-I", os.path.join(PKG, "csrc"), os.path.join(ROOT, "tools", "unionfind_check.cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)  # (a stand-alone child process with its own main)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "0 mismatches" in r.stdout and "704 cases" in r.stdout
+    assert "0 mismatches" in r.stdout and "880 cases" in r.stdout  # (10 shapes, 257 x 256 and 1030 x 132 among them)

@@ -223,7 +223,9 @@ Image pattern(const std::string &name, int nx, int ny, int min_count, std::mt199
 }  // namespace
 
 int main() {
-    const int shapes[][2] = {{1, 1}, {7, 5}, {64, 16}, {65, 17}, {129, 33}, {257, 3}, {3, 257}, {200, 70}};
+    // the last two: more than 256 chunks, so the ranks of the later roots need the scan beyond one round of the kernel's
+    // (this program's scan is a plain loop: what it checks at these sizes is the pass sequence and the index arithmetic)
+    const int shapes[][2] = {{1, 1}, {7, 5}, {64, 16}, {65, 17}, {129, 33}, {257, 3}, {3, 257}, {200, 70}, {257, 256}, {1030, 132}};
     const char *names[] = {"empty", "full", "checker", "diagonals", "comb", "spiral", "serpentine", "random0.1", "random0.3", "random0.59", "corner"};
     std::mt19937 rng(20240607u);
     int cases = 0, bad = 0;
