@@ -303,7 +303,7 @@ PWPP_API int pwpp_get_fxp_origins(pwpp_handle *h, float *out_xy, int capacity_bi
  *   PWPP_ORDER_REFERENCE the reference's order (patchworkpp.cpp:199 sorts a bin by z; :500,:532): ground
  *                        candidates ascending in z; non-ground: the points each R-VPF round removed, then
  *                        the rest, each ascending in z; small bins / RNR / out-of-range in cloud order.
- *                        Equal z: cloud order (the reference's std::sort leaves ties unspecified).
+ *                        Equal z (-0.0 and +0.0 are equal): cloud order (the reference's std::sort leaves ties unspecified).
  * Applies to the batches launched after the call. */
 enum { PWPP_ORDER_SCATTER = 0, PWPP_ORDER_REFERENCE = 1, PWPP_ORDER_CLOUD = 2 };
 PWPP_API int pwpp_set_output_order(pwpp_handle *h, int order);

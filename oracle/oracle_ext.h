@@ -41,6 +41,13 @@ long long pwo_ext_quantise(float v, double origin, int shift);
 long long pwo_ext_quantise_z(float v, double z0, int shift, double zr);
 double pwo_ext_z_origin(double lpr);
 long pwo_ext_max_sweeps(int reset); /* largest Jacobi sweep count of one fit since the last reset (this thread) */
+/* What the sort of PWPP_ORDER_REFERENCE keys on, for every entry of the ground list (which = 0) or the non-ground list (1) of the
+ * last call: the ordinal of its PART (the sub-list it was appended with -- one addCloud / insert of the reference, or all RNR
+ * hits, or all out-of-range points -- numbered in list order) and its CATEGORY: 0 for ground candidates (:262-282, :444-459) and
+ * for every entry of a part in cloud order; the R-VPF round 1, 2, ... that removed the point (:500); 255 for the rest of a patch's
+ * regionwise_nonground_ (:532).  part_in_cloud_order[p] = 1: part p is an RNR / out-of-range / small-bin part (:393, :618, :192). */
+int pwo_ext_num_list_parts(void *h, int which);
+void pwo_ext_get_list_keys(void *h, int which, int32_t *part, uint8_t *category, uint8_t *part_in_cloud_order);
 
 #ifdef __cplusplus
 }

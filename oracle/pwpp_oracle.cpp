@@ -323,6 +323,10 @@ public:
     std::vector<double> hist_elev[4], hist_flat[4];  // update_elevation_/update_flatness_, patchworkpp.h:174-175
     std::vector<Pt> cloud_ground, cloud_nonground, centers, normals;
     std::vector<pwo_patch_record> records;
+    // which part (sub-list, numbered in list order) and which category every entry of the two lists belongs to, and whether
+    // a part is in cloud order (oracle_ext.h, pwo_ext_get_list_keys): [0] ground, [1] non-ground
+    std::vector<int32_t> part_of[2];
+    std::vector<uint8_t> cat_of[2], part_in_cloud_order[2];
     long time_taken = 0;
     long fits = 0, sweeps = 0;
     void get_fxp(int *shift, double *zr, float *ox, float *oy) const {
@@ -339,6 +343,11 @@ public:
         cloud_ground.clear();
         cloud_nonground.clear();
         records.clear();
+        for (int w = 0; w < 2; ++w) {
+            part_of[w].clear();
+            cat_of[w].clear();
+            part_in_cloud_order[w].clear();
+        }
         clock_t beg = clock();
 
         zwork.resize((size_t)n);
@@ -362,6 +371,7 @@ public:
                     // :191 compares size_t with int -> the int is converted to size_t
                     if (cell.size() < (size_t)prm.num_min_pts) {
                         cloud_nonground.insert(cloud_nonground.end(), cell.begin(), cell.end());
+                        tag_part(1, true, nullptr);
                         continue;
                     }
                     std::sort(cell.begin(), cell.end(), z_less);  // :199
@@ -412,15 +422,19 @@ public:
                     // ---- decision ladder, :262-284
                     if (!is_upright) {
                         append(cloud_nonground, rg);
+                        tag_part(1, false, nullptr);
                         rec.decision = PWO_DEC_NOT_UPRIGHT;
                     } else if (!is_near) {
                         append(cloud_ground, rg);
+                        tag_part(0, false, nullptr);
                         rec.decision = PWO_DEC_FAR_GROUND;
                     } else if (!heading_outside) {
                         append(cloud_nonground, rg);
+                        tag_part(1, false, nullptr);
                         rec.decision = PWO_DEC_HEADING;
                     } else if (not_elevated || is_flat) {
                         append(cloud_ground, rg);
+                        tag_part(0, false, nullptr);
                         rec.decision = PWO_DEC_GROUND;
                     } else {
                         Candidate c;
@@ -434,6 +448,7 @@ public:
                         rec.decision = PWO_DEC_TGR_REJECT;  // finalised at ring end
                     }
                     append(cloud_nonground, rng);  // :284
+                    tag_part(1, false, rng_cat.data());
                     records.push_back(rec);
                 }
                 // ---- end of ring, :291-304
@@ -441,7 +456,10 @@ public:
                     if (prm.enable_TGR) {
                         temporal_ground_revert(ringwise_flatness, candidates, concentric_idx);
                     } else {
-                        for (auto &c : candidates) append(cloud_nonground, c.ground);
+                        for (auto &c : candidates) {
+                            append(cloud_nonground, c.ground);
+                            tag_part(1, false, nullptr);
+                        }
                     }
                     candidates.clear();
                     ringwise_flatness.clear();
@@ -467,6 +485,20 @@ private:
     std::vector<float> zwork;           // z column of the by-value copy (tombstones, :394)
     Plane plane;                        // normal_, pc_mean_, singular_values_, d_ (persist across bins/frames)
     std::vector<Pt> ground_pc;          // ground_pc_
+    std::vector<uint8_t> rng_cat;       // category of every entry of regionwise_nonground_: the R-VPF round that removed it, or 255
+
+    // Everything list `which` has gained since the last call is ONE part: it gets the next ordinal and, entry by entry, the
+    // categories `cats` (null: 0).  Nothing was appended: no part.
+    void tag_part(int which, bool cloud_order, const uint8_t *cats) {
+        const size_t have = (which ? cloud_nonground : cloud_ground).size(), done = part_of[which].size();
+        if (have == done) return;
+        const int32_t ordinal = (int32_t)part_in_cloud_order[which].size();
+        part_in_cloud_order[which].push_back(cloud_order ? 1 : 0);
+        for (size_t i = done; i < have; ++i) {
+            part_of[which].push_back(ordinal);
+            cat_of[which].push_back(cats ? cats[i - done] : (uint8_t)0);
+        }
+    }
 
     static void append(std::vector<Pt> &dst, const std::vector<Pt> &src) {  // addCloud, :28-31
         dst.insert(dst.end(), src.begin(), src.end());
@@ -487,6 +519,7 @@ private:
                 zwork[(size_t)i] = std::numeric_limits<float>::min();  // :394 tombstone
             }
         }
+        tag_part(1, true, nullptr);
     }
 
     // ------------------------------------------------------------------ pc2czm, :578-622
@@ -519,6 +552,7 @@ private:
                 cloud_nonground.push_back(Pt{x, y, z, i});  // :618
             }
         }
+        tag_part(1, true, nullptr);
     }
 
     // ------------------------------------------------------------------ seeds, :77-149
@@ -680,6 +714,7 @@ private:
         ground_pc.clear();
         dst.clear();
         non_ground_dst.clear();
+        rng_cat.clear();
         std::vector<Pt> work = src;  // src_wo_verticals
 
         if (prm.enable_RVPF) {  // :482-508
@@ -691,9 +726,10 @@ private:
                     tmp.swap(work);
                     for (const Pt &p : tmp) {
                         const double dist = point_to_plane(p);
-                        if (std::abs(dist) < prm.th_dist_v)
+                        if (std::abs(dist) < prm.th_dist_v) {
                             non_ground_dst.push_back(p);
-                        else
+                            rng_cat.push_back((uint8_t)(i + 1 < 255 ? i + 1 : 254));
+                        } else
                             work.push_back(p);
                     }
                 } else {
@@ -710,10 +746,12 @@ private:
                 if (i < prm.num_iter - 1) {
                     if (dist < prm.th_dist) ground_pc.push_back(p);
                 } else {
-                    if (dist < prm.th_dist)
+                    if (dist < prm.th_dist) {
                         dst.push_back(p);
-                    else
+                    } else {
                         non_ground_dst.push_back(p);
+                        rng_cat.push_back(255);
+                    }
                 }
             }
             if (i < prm.num_iter - 1)
@@ -747,9 +785,11 @@ private:
             if (concentric_idx < prm.num_rings_of_interest) {
                 if (revert) {
                     append(cloud_ground, c.ground);
+                    tag_part(0, false, nullptr);
                     records[(size_t)c.patch_slot].decision = PWO_DEC_TGR_REVERT;
                 } else {
                     append(cloud_nonground, c.ground);
+                    tag_part(1, false, nullptr);
                 }
             }
         }
@@ -916,6 +956,14 @@ long long pwo_ext_quantise_z(float v, double z0, int shift, double zr) {
     return fxp_quantise_z(v, z0, zr, shift);
 }
 double pwo_ext_z_origin(double lpr) { return fxp_z_origin(lpr); }
+int pwo_ext_num_list_parts(void *h, int which) { return (int)((Oracle *)h)->part_in_cloud_order[which ? 1 : 0].size(); }
+void pwo_ext_get_list_keys(void *h, int which, int32_t *part, uint8_t *category, uint8_t *part_in_cloud_order) {
+    const Oracle *o = (Oracle *)h;
+    const int w = which ? 1 : 0;
+    std::copy(o->part_of[w].begin(), o->part_of[w].end(), part);
+    std::copy(o->cat_of[w].begin(), o->cat_of[w].end(), category);
+    std::copy(o->part_in_cloud_order[w].begin(), o->part_in_cloud_order[w].end(), part_in_cloud_order);
+}
 
 double pwo_bench(const pwo_params *p, int arith, const float *const *frames, const int *n_points, int cols,
                  int num_distinct, int total, int threads, double *sum_call_seconds) {

@@ -2124,7 +2124,7 @@ __global__ __launch_bounds__(kEmitBlock, 8) void k_emit(PwppBatch Bt, unsigned l
                                 if (p0 + (unsigned)t < pn) load_point(fd, vv[t], x, y, zt, w);
                                 vv[t] |= (int)((zb & 0xffu) << 24);
                             }
-                            zk[q][t] = z_key(zt);
+                            zk[q][t] = z_key(zt == 0.0f ? 0.0f : zt);  // (-0 and +0 compare equal: cloud order)
                         }
                     }
                 }
@@ -2202,7 +2202,8 @@ __global__ __launch_bounds__(kEmitBlock, 8) void k_emit(PwppBatch Bt, unsigned l
 // removed, round by round, each round ascending in z, then the rest ascending in z (ref :500,:532);
 // small bins, RNR hits and out-of-range points in cloud order.  This kernel sorts every sub-list of
 // out_idx by (R-VPF round, z, cloud index).  Equal z: the reference's std::sort is unstable, so its
-// order among ties is an artefact of libstdc++; ties come out in cloud order here.
+// order among ties is an artefact of libstdc++; ties come out in cloud order here (-0 and +0 tie: its comparator is a.z < b.z,
+// and k_emit forms the key from the canonical zero).
 // One workgroup per (frame, bin); sub-lists up to 4096 entries are sorted in LDS (bitonic), longer
 // ones tile by tile and then merged through two scratch arrays indexed like out_idx.
 // ------------------------------------------------------------------------------------------

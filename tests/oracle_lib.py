@@ -103,6 +103,8 @@ class _Lib:
             L.pwo_ext_quantise_z.argtypes = [ctypes.c_float, ctypes.c_double, ctypes.c_int, ctypes.c_double]
             L.pwo_ext_z_origin.restype = ctypes.c_double
             L.pwo_ext_z_origin.argtypes = [ctypes.c_double]
+            L.pwo_ext_num_list_parts.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.pwo_ext_get_list_keys.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3
 
     def default_params(self):
         p = Params()
@@ -148,6 +150,9 @@ class Result:
         self.elevation_thr = self.flatness_thr = None
         self.hist_elev = self.hist_flat = None
         self.records = None
+        # restatement only: per list entry the ordinal of its part and its sort category, per part whether it is in cloud order
+        self.ground_part = self.ground_cat = self.ground_part_cloud = None
+        self.nonground_part = self.nonground_cat = self.nonground_part_cloud = None
 
 
 class Estimator:
@@ -223,6 +228,13 @@ class Estimator:
             r.records = np.zeros(k, RECORD_DTYPE)
             if k:
                 L.pwo_ext_get_records(h, _vp(r.records))
+            for which, name, count in ((0, "ground", ng), (1, "nonground", nn)):
+                part, cat = np.zeros(count, np.int32), np.zeros(count, np.uint8)
+                cloud = np.zeros(L.pwo_ext_num_list_parts(h, which), np.uint8)
+                L.pwo_ext_get_list_keys(h, which, _vp(part), _vp(cat), _vp(cloud))
+                setattr(r, name + "_part", part)
+                setattr(r, name + "_cat", cat)
+                setattr(r, name + "_part_cloud", cloud.astype(bool))
         return r
 
 
