@@ -2327,6 +2327,19 @@ int mem_args(int mem, const char *who) {
     if (mem == PWPP_MEM_HOST || mem == PWPP_MEM_DEVICE) return PWPP_OK;
     return fail(PWPP_E_ARG, "mem %d: %s PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem, who);
 }
+
+// What PWPP_MEM_DEVICE asks of the caller's arrays (after mem): the first of `a` that is off its alignment, mask + 1 bytes, is named.
+struct Aligned {
+    const void *p;
+    unsigned mask;
+    const char *name;
+};
+int alignment_args(int mem, std::initializer_list<Aligned> a) {
+    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
+    for (const Aligned &x : a)
+        if (reinterpret_cast<uintptr_t>(x.p) & x.mask) return fail(PWPP_E_ARG, "the %s must be %d-byte aligned", x.name, (int)x.mask + 1);
+    return PWPP_OK;
+}
 }  // namespace
 
 int pwpp_query_ground(pwpp_handle *h, const float *xyz, const int32_t *frame, int64_t m, int mem, pwpp_ground_sample *out) {
@@ -2433,7 +2446,8 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
 // Each has two entry points: pwpp_*_grid works on the caller's image, pwpp_*_obstacles on the one it first rasterises from the last call's
 // non-ground lists.  An operator states its sections once (*_sections: the kernels' working words and the tables the call built for them
 // first -- upload sections, copied by Staging::begin() -- then what the call stages) and its launch once (*_launch: the launcher's call alone);
-// an entry point checks its arguments, declares the sections and runs one of three tails: run_on_image, run_on_obstacles, run_on_visibility.
+// an entry point checks its arguments, declares the sections and runs one of four tails: run_on_image, run_on_obstacles, run_on_visibility
+// (further down: the obstacle tail under the visibility operator), run_on_ground (the elevation fusion and the terrain on the ground raster).
 
 // The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
 // From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
@@ -2464,6 +2478,28 @@ int run_on_obstacles(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, flo
     if (lrc == 0) lrc = op(scan);
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
+
+// On the ground raster: pwpp_rasterize_ground into the sections s_height and (-1: none) s_patch, then `op` (a HIP error code), one sequence.
+template <class Op>
+int run_on_ground(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, int frame_first, int frames, int s_height, int s_patch, Op op) {
+    int rc = st.begin();
+    if (rc) return rc;
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    if ((rc = ground_view(h, v))) return rc;
+    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), s_patch < 0 ? nullptr : st.dev<int32_t>(s_patch), h->stream);
+    if (lrc == 0) lrc = op();
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// What the operators on the ground raster check first of the frames and the grid, before their own arguments; `who` as in mem_args.
+int ground_first_args(const pwpp_ground_grid *g, int frames, const char *who) {
+    if (frames < 1 || g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, g->nx, g->ny);
+    if (const int rc = side_args(g->nx, g->ny, who)) return rc;
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    return PWPP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2476,13 +2512,7 @@ int pwpp_rasterize_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_f
     if (rc) return rc;
     Staging st(h, h->d_ground_stage, mem);
     const int s_height = st.add(cells, height, Staging::kOut), s_patch = st.add(patch ? cells : 0, patch, Staging::kOut);
-    if ((rc = st.begin())) return rc;
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
-    if ((rc = ground_view(h, v))) return rc;
-    const int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), st.dev<int32_t>(s_patch), h->stream);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    return run_on_ground(h, st, g, frame_first, frames, s_height, s_patch, [] { return 0; });
 }
 
 // The non-ground points of the last call per cell of the grid: count, then top, then unref.
@@ -2512,8 +2542,7 @@ int cluster_param_args(int mem, int min_count, int connectivity, const void *clu
     if (connectivity != 4 && connectivity != 8) return fail(PWPP_E_ARG, "connectivity %d: 4 or 8 expected", connectivity);
     if (max_clusters < 0) return fail(PWPP_E_ARG, "max_clusters %d", max_clusters);
     if (max_clusters > 0 && !clusters) return fail(PWPP_E_ARG, "null cluster table with max_clusters %d", max_clusters);
-    if (mem == PWPP_MEM_DEVICE && (reinterpret_cast<uintptr_t>(clusters) & 7u)) return fail(PWPP_E_ARG, "the cluster table must be 8-byte aligned");
-    return PWPP_OK;
+    return alignment_args(mem, {{clusters, 7u, "cluster table"}});
 }
 
 constexpr size_t kClusterRowWords = sizeof(pwpp_obstacle_cluster) / 4;
@@ -2774,7 +2803,7 @@ int map_grid_args(const pwpp_ground_grid *g, const M *m, int n_maps, const char 
 struct FrameMaps {
     const int32_t *map_of_frame;  // (null: one map for all, or frame i's is map i)
     int n_maps;
-    int32_t operator()(int i) const { return map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i); }
+    int32_t operator()(int i) const { return pwpp_map_of_frame(map_of_frame, n_maps, i); }
     int args(int frames) const {
         if (!map_of_frame && n_maps != 1 && n_maps != frames)
             return fail(PWPP_E_ARG, "null map_of_frame with %d maps for %d frames: 1 map or one per frame expected", n_maps, frames);
@@ -2783,89 +2812,105 @@ struct FrameMaps {
                 return fail(PWPP_E_ARG, "map_of_frame %d names map %d: -1 (skipped) .. %d expected", i, map_of_frame[i], n_maps - 1);
         return PWPP_OK;
     }
-    // the CSR of the checked rule: a counting sort of the frames by their map keeps each map's frames in ascending order
-    void lists(int frames, std::vector<int32_t> &begin, std::vector<int32_t> &list) const {
-        begin.assign((size_t)n_maps + 1, 0);
-        int listed = 0;
-        for (int i = 0; i < frames; ++i)
-            if ((*this)(i) >= 0) ++begin[(size_t)(*this)(i) + 1], ++listed;
-        for (int k = 0; k < n_maps; ++k) begin[(size_t)k + 1] += begin[k];
-        list.assign((size_t)listed, 0);
-        std::vector<int32_t> next(begin.begin(), begin.end() - 1);
-        for (int i = 0; i < frames; ++i)
-            if ((*this)(i) >= 0) list[(size_t)next[(size_t)(*this)(i)]++] = i;
-    }
 };
 
-// whether a shift array moves any map, and whether two of the caller's byte ranges meet (a null one meets nothing)
-bool any_shift(const int32_t *shift, int n_maps) {
-    for (int k = 0; shift && k < n_maps; ++k)
-        if (shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0) return true;
-    return false;
-}
+// whether two of the caller's byte ranges meet (a null one meets nothing)
 bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return a && b && pa < pb + nb && pb < pa + na;
 }
 
-// What a checked call hands to the kernel besides its images: the geometry, the parameters and the words to upload -- the poses
-// first (8-byte aligned at the section's start), then begin[n_maps + 1], the frame list and the shifts (none: no words).
-struct FusionPlan {
+// What an operator checks of the caller's arrays among each other: no two may meet, except that the two of a pair of `in_place`
+// ({input, output} as indices, input first) may be the same array -- the update in place -- unless a shift moves a map (`moved`).
+struct Range {
+    const void *p;
+    size_t bytes;
+    const char *name;
+};
+int range_args(std::initializer_list<Range> ranges, std::initializer_list<std::pair<int, int>> in_place, bool moved) {
+    const Range *r = ranges.begin();
+    for (int i = 0, n = (int)ranges.size(); i < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            if (!ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) continue;
+            const bool pair = std::find(in_place.begin(), in_place.end(), std::make_pair(i, j)) != in_place.end();
+            if (pair && r[i].p == r[j].p) {
+                if (moved) return fail(PWPP_E_ARG, "%s == %s with a shift that is not {0, 0}: a shifted update needs a second array", r[j].name, r[i].name);
+                continue;
+            }
+            return fail(PWPP_E_ARG, "%s and %s overlap%s", r[i].name, r[j].name, pair ? " without being equal" : "");
+        }
+    return PWPP_OK;
+}
+
+// "Frames into maps under poses" (both fusions): what a checked call hands to the kernel besides its images and own parameters -- geometry,
+// counts and the words to upload: the poses, `per_pose` more doubles for each (z_offset: 1), begin[n_maps + 1], frame list, shifts (none: no words).
+struct MapPlan {
     PwppFusionGeometry G;
-    PwppFusionParams P;
-    int n_poses = 0, n_maps = 0, listed = 0;
-    bool shifted = false;  // a shift array was given
+    int n_poses = 0, n_maps = 0, listed = 0, per_pose = 0;
+    bool shifted = false;  // a shift array was given ...
+    bool moved = false;    // ... and moves a map: one entry is not 0
     size_t map_cells = 0;  // NX * NY * n_maps
     std::vector<uint32_t> words;
-    size_t at_begin() const { return (size_t)n_poses * 12; }
+    size_t at_per_pose() const { return (size_t)n_poses * 12; }
+    size_t at_begin() const { return at_per_pose() + (size_t)n_poses * 2 * (size_t)per_pose; }
     size_t at_list() const { return at_begin() + (size_t)n_maps + 1; }
     size_t at_shift() const { return at_list() + (size_t)listed; }
 };
 
+// Filled in two steps around an operator's own checks, as the documented order of rejection has it: map_grid_args, its parameters, THEN
+// map_plan_args; its arrays (range_args with plan.moved), THEN map_plan_words (`extra`: n_poses * per_pose doubles, or null: zeros).
+extern "C++" template <class M>  // (pwpp_fusion_map or pwpp_height_map, as in map_grid_args)
+int map_plan_args(const pwpp_ground_grid *g, const M *m, int frames, int n_poses, int per_pose, const int32_t *map_of_frame, int n_maps, const int32_t *shift,
+                  MapPlan &plan) {
+    if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
+    if (const int rc = FrameMaps{map_of_frame, n_maps}.args(frames)) return rc;
+    for (int k = 0; shift && k < n_maps; ++k) plan.moved = plan.moved || shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0;
+    plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
+    pwpp_fuse_reciprocal(g->cell, plan.G.inv_cell);
+    plan.n_poses = n_poses, plan.n_maps = n_maps, plan.per_pose = per_pose, plan.shifted = shift != nullptr;
+    return PWPP_OK;
+}
+int map_plan_words(int frames, const double *pose, const double *extra, const int32_t *map_of_frame, const int32_t *shift, MapPlan &plan) {
+    try {
+        std::vector<int32_t> begin, list;
+        pwpp_map_lists(map_of_frame, plan.n_maps, frames, begin, list);
+        plan.listed = (int)list.size();
+        plan.words.assign(plan.at_shift() + (shift ? 2 * (size_t)plan.n_maps : 0), 0u);
+        std::memcpy(plan.words.data(), pose, (size_t)plan.n_poses * 6 * sizeof(double));
+        if (extra) std::memcpy(plan.words.data() + plan.at_per_pose(), extra, (size_t)plan.n_poses * (size_t)plan.per_pose * sizeof(double));
+        std::memcpy(plan.words.data() + plan.at_begin(), begin.data(), begin.size() * sizeof(int32_t));
+        if (plan.listed) std::memcpy(plan.words.data() + plan.at_list(), list.data(), list.size() * sizeof(int32_t));
+        if (shift) std::memcpy(plan.words.data() + plan.at_shift(), shift, 2 * (size_t)plan.n_maps * sizeof(int32_t));
+    } catch (const std::bad_alloc &) {
+        return fail(PWPP_E_NOMEM, "no host memory for the lists of %d maps and %d frames", plan.n_maps, frames);
+    }
+    return PWPP_OK;
+}
+
 // What both entry points check of the map, the poses, the frame lists, the shifts and the overlaps, in the header's order, after
-// the frame images' own checks (frames >= 1); fills the plan.  Touches no handle.
+// the frame images' own checks (frames >= 1); fills the plan and the parameters.  Touches no handle.
 int fusion_args(const pwpp_ground_grid *g, int frames, const double *pose, int n_poses, const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps,
-                const int32_t *shift, const int16_t *map_in, const int16_t *map_out, const int8_t *map_occupancy, FusionPlan &plan) {
+                const int32_t *shift, const int16_t *map_in, const int16_t *map_out, const int8_t *map_occupancy, MapPlan &plan, PwppFusionParams &P) {
     if (const int rc = map_grid_args(g, m, n_maps, kFusionWho, plan.map_cells)) return rc;
     if (m->hit < 0 || m->hit > 32767 || m->miss < 0 || m->miss > 32767) return fail(PWPP_E_ARG, "hit %d, miss %d: 0 .. 32767 expected", m->hit, m->miss);
     if (m->l_min < -32768 || m->l_min > 0 || m->l_max < 0 || m->l_max > 32767)
         return fail(PWPP_E_ARG, "clamps l_min %d, l_max %d: -32768 <= l_min <= 0 <= l_max <= 32767 expected", m->l_min, m->l_max);
     if (m->free_at < -32768 || m->free_at >= m->occupied_at || m->occupied_at > 32767)
         return fail(PWPP_E_ARG, "thresholds free_at %d, occupied_at %d: -32768 <= free_at < occupied_at <= 32767 expected", m->free_at, m->occupied_at);
-    if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
-    const FrameMaps map_of{map_of_frame, n_maps};
-    if (const int rc = map_of.args(frames)) return rc;
-    const bool moved = any_shift(shift, n_maps);
+    if (const int rc = map_plan_args(g, m, frames, n_poses, 0, map_of_frame, n_maps, shift, plan)) return rc;
     const size_t map_bytes = plan.map_cells * sizeof(int16_t);
-    if (map_in == map_out && moved) return fail(PWPP_E_ARG, "map_out == map_in with a shift that is not {0, 0}: a shifted update needs a second array");
-    if (map_in != map_out && ranges_overlap(map_in, map_bytes, map_out, map_bytes)) return fail(PWPP_E_ARG, "map_in and map_out overlap without being equal");
+    if (const int rc = range_args({{map_in, map_bytes, "map_in"}, {map_out, map_bytes, "map_out"}}, {{0, 1}}, plan.moved)) return rc;
     if (ranges_overlap(map_occupancy, plan.map_cells, map_out, map_bytes) || ranges_overlap(map_occupancy, plan.map_cells, map_in, map_bytes))
         return fail(PWPP_E_ARG, "map_occupancy overlaps %s", ranges_overlap(map_occupancy, plan.map_cells, map_out, map_bytes) ? "map_out" : "map_in");
-
-    plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
-    pwpp_fuse_reciprocal(g->cell, plan.G.inv_cell);
-    plan.P = PwppFusionParams{m->hit, m->miss, m->l_min, m->l_max, m->occupied_at, m->free_at};
-    plan.n_poses = n_poses, plan.n_maps = n_maps, plan.shifted = shift != nullptr;
-    try {
-    std::vector<int32_t> begin, list;
-    map_of.lists(frames, begin, list);
-    plan.listed = (int)list.size();
-    plan.words.assign(plan.at_shift() + (shift ? 2 * (size_t)n_maps : 0), 0u);
-    std::memcpy(plan.words.data(), pose, (size_t)n_poses * 6 * sizeof(double));
-    std::memcpy(plan.words.data() + plan.at_begin(), begin.data(), begin.size() * sizeof(int32_t));
-    if (plan.listed) std::memcpy(plan.words.data() + plan.at_list(), list.data(), list.size() * sizeof(int32_t));
-    if (shift) std::memcpy(plan.words.data() + plan.at_shift(), shift, 2 * (size_t)n_maps * sizeof(int32_t));
-    } catch (const std::bad_alloc &) {
-        return fail(PWPP_E_NOMEM, "no host memory for the lists of %d maps and %d frames", n_maps, frames);
-    }
-    return PWPP_OK;
+    P = PwppFusionParams{m->hit, m->miss, m->l_min, m->l_max, m->occupied_at, m->free_at};
+    return map_plan_words(frames, pose, nullptr, map_of_frame, shift, plan);
 }
 
 // (the plan's words first: they move into the staging; `occ` is the frame bytes' section: the caller's, or the visibility's)
 struct FusionSections {
     int up, occ, map_in, map_out, map_occ;
 };
-FusionSections fusion_sections(Staging &st, FusionPlan &plan, int s_occ, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
+FusionSections fusion_sections(Staging &st, MapPlan &plan, int s_occ, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
     FusionSections s;
     const size_t map_words = (plan.map_cells + 1) / 2, map_bytes = plan.map_cells * sizeof(int16_t);
     s.up = st.add_upload(std::move(plan.words));
@@ -2875,9 +2920,9 @@ FusionSections fusion_sections(Staging &st, FusionPlan &plan, int s_occ, const i
     s.map_occ = st.add(map_occupancy ? (plan.map_cells + 3) / 4 : 0, map_occupancy, Staging::kOut, map_occupancy ? plan.map_cells : 0);
     return s;
 }
-int fusion_launch(pwpp_handle *h, const Staging &st, const FusionSections &s, const FusionPlan &plan, int frames) {
+int fusion_launch(pwpp_handle *h, const Staging &st, const FusionSections &s, const MapPlan &plan, const PwppFusionParams &P, int frames) {
     const int32_t *words = st.dev<const int32_t>(s.up);
-    return pwpp_launch_fuse_grid(&plan.G, &plan.P, frames, st.dev<const int8_t>(s.occ), st.dev<const double>(s.up), plan.n_poses, plan.n_maps,
+    return pwpp_launch_fuse_grid(&plan.G, &P, frames, st.dev<const int8_t>(s.occ), st.dev<const double>(s.up), plan.n_poses, plan.n_maps,
                                  words + plan.at_begin(), words + plan.at_list(), plan.listed, plan.shifted ? words + plan.at_shift() : nullptr,
                                  st.dev<const int16_t>(s.map_in), st.dev<int16_t>(s.map_out), st.dev<int8_t>(s.map_occ), h->fusion_path, h->stream);
 }
@@ -2893,13 +2938,14 @@ int pwpp_fuse_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int me
     int rc = image_args(g->nx, g->ny, frames, kFusionWho, cells);
     if (rc) return rc;
     if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the fusion's frame grid takes 0", g->flags);
-    FusionPlan plan;
-    if ((rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan))) return rc;
+    MapPlan plan;
+    PwppFusionParams P;
+    if ((rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan, P))) return rc;
     if ((rc = mem_args(mem, kFusionWho))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const int s_occ = st.add((cells + 3) / 4, occupancy, Staging::kIn, cells);
     const FusionSections s = fusion_sections(st, plan, s_occ, map_in, map_out, map_occupancy);
-    return run_on_image(h, st, [&] { return fusion_launch(h, st, s, plan, frames); });
+    return run_on_image(h, st, [&] { return fusion_launch(h, st, s, plan, P, frames); });
 }
 
 // pwpp_visibility_obstacles and pwpp_fuse_grid on its bytes (run_on_visibility).
@@ -2911,14 +2957,15 @@ int pwpp_fuse_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, 
     if (!g || !origin_xy || !pose || !m || !map_out)
         return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!origin_xy ? "origin" : (!pose ? "pose" : (!m ? "map description" : "map_out"))));
     std::vector<int32_t> org;
-    FusionPlan plan;
+    MapPlan plan;
+    PwppFusionParams P;
     int rc = visibility_first_args(g, h_min, h_max, min_count, origin_xy, n_origins, max_range, frames, org);
-    if (rc || (rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan))) return rc;
+    if (rc || (rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan, P))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     return run_on_visibility(h, g, h_min, h_max, min_count, org, max_range, frame_first, frames, mem, cells, occupancy, [&](Staging &st, int s_occ) {
         const FusionSections s = fusion_sections(st, plan, s_occ, map_in, map_out, map_occupancy);
-        return [&, s] { return fusion_launch(h, st, s, plan, frames); };
+        return [&, s] { return fusion_launch(h, st, s, plan, P, frames); };
     });
 }
 
@@ -2974,12 +3021,7 @@ int match_args(const pwpp_ground_grid *g, int frames, const double *candidates, 
 }
 
 // (after mem: what PWPP_MEM_DEVICE asks of the result arrays; the map is 2-byte aligned and the bytes byte aligned, no more)
-int match_alignment_args(int mem, const void *best, const void *scores) {
-    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
-    if (reinterpret_cast<uintptr_t>(best) & 7u) return fail(PWPP_E_ARG, "the best rows must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(scores) & 7u) return fail(PWPP_E_ARG, "the scores must be 8-byte aligned");
-    return PWPP_OK;
-}
+int match_alignment_args(int mem, const void *best, const void *scores) { return alignment_args(mem, {{best, 7u, "best rows"}, {scores, 7u, "scores"}}); }
 
 // (the plan's words, which move into the staging, and the kernels' working words first -- cell list, counts and workgroup bests are kKept like every operator's
 // work words: theirs alone, in the buffer whatever the memory kind; `occ` is the frame bytes' section: the caller's, or the visibility's)
@@ -3058,87 +3100,34 @@ namespace {
 static_assert(sizeof(pwpp_height_map) == 40, "pwpp_height_map is 40 bytes");
 constexpr const char *kElevationWho = "the elevation fusion takes";
 
-// What a checked call hands to the kernel besides its images: the geometry, the update's parameters and the words to upload -- the
-// poses first, then the offsets (both 8-byte aligned at the section's start; zeros without z_offset), begin[n_maps + 1], the frame
-// list and the shifts (none: no words).
-struct HeightPlan {
-    PwppFusionGeometry G;
-    PwppElevationParams P;
-    int n_poses = 0, n_maps = 0, listed = 0;
-    bool shifted = false;  // a shift array was given
-    size_t map_cells = 0;  // NX * NY * n_maps
-    std::vector<uint32_t> words;
-    size_t at_offset() const { return (size_t)n_poses * 12; }
-    size_t at_begin() const { return at_offset() + (size_t)n_poses * 2; }
-    size_t at_list() const { return at_begin() + (size_t)n_maps + 1; }
-    size_t at_shift() const { return at_list() + (size_t)listed; }
-};
-
 // What both entry points check of the map, the poses, the frame lists, the shifts, the inputs and the overlaps, in the header's
-// order, after the frame images' own checks (frames >= 1); fills the plan.  Touches no handle.
+// order, after the frame images' own checks (frames >= 1); fills the plan (one more double for every pose: z_offset, zeros
+// without it) and the parameters.  Touches no handle.
 int height_args(const pwpp_ground_grid *g, int frames, const double *pose, const double *z_offset, int n_poses, const int32_t *map_of_frame,
                 const pwpp_height_map *m, int n_maps, const int32_t *shift, const int32_t *sum_in, const int16_t *n_in, const int32_t *sum_out,
-                const int16_t *n_out, const float *mean, HeightPlan &plan) {
+                const int16_t *n_out, const float *mean, MapPlan &plan, PwppElevationParams &P) {
     if (const int rc = map_grid_args(g, m, n_maps, kElevationWho, plan.map_cells)) return rc;
     if (m->n_max < 1 || m->n_max > PWPP_ELEV_MAX_N) return fail(PWPP_E_ARG, "n_max %d: 1 .. 1023 expected", m->n_max);
     if (m->pad_ != 0) return fail(PWPP_E_ARG, "pad_ %d of the height map: 0 expected", m->pad_);
-    if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
-    const FrameMaps map_of{map_of_frame, n_maps};
-    if (const int rc = map_of.args(frames)) return rc;
+    if (const int rc = map_plan_args(g, m, frames, n_poses, 1, map_of_frame, n_maps, shift, plan)) return rc;
     if (!sum_in != !n_in) return fail(PWPP_E_ARG, "null %s with a %s: both or neither expected", sum_in ? "n_in" : "sum_in", sum_in ? "sum_in" : "n_in");
-    const bool moved = any_shift(shift, n_maps);
-    struct Range {
-        const void *p;
-        size_t bytes;
-        const char *name;
-    };
-    const Range r[5] = {{sum_in, plan.map_cells * 4, "sum_in"}, {n_in, plan.map_cells * 2, "n_in"}, {sum_out, plan.map_cells * 4, "sum_out"},
-                        {n_out, plan.map_cells * 2, "n_out"}, {mean, plan.map_cells * 4, "mean"}};
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j) {
-            if (!ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) continue;
-            if (j == i + 2 && i < 2 && r[i].p == r[j].p) {  // sum_out == sum_in, n_out == n_in: in place
-                if (moved) return fail(PWPP_E_ARG, "%s == %s with a shift that is not {0, 0}: a shifted update needs a second array", r[j].name, r[i].name);
-                continue;
-            }
-            return fail(PWPP_E_ARG, "%s and %s overlap%s", r[i].name, r[j].name, j == i + 2 && i < 2 ? " without being equal" : "");
-        }
-
-    plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
-    pwpp_fuse_reciprocal(g->cell, plan.G.inv_cell);
-    plan.P = pwpp_elev_magic(m->n_max);
-    plan.n_poses = n_poses, plan.n_maps = n_maps, plan.shifted = shift != nullptr;
-    try {
-        std::vector<int32_t> begin, list;
-        map_of.lists(frames, begin, list);
-        plan.listed = (int)list.size();
-        plan.words.assign(plan.at_shift() + (shift ? 2 * (size_t)n_maps : 0), 0u);
-        std::memcpy(plan.words.data(), pose, (size_t)n_poses * 6 * sizeof(double));
-        if (z_offset) std::memcpy(plan.words.data() + plan.at_offset(), z_offset, (size_t)n_poses * sizeof(double));
-        std::memcpy(plan.words.data() + plan.at_begin(), begin.data(), begin.size() * sizeof(int32_t));
-        if (plan.listed) std::memcpy(plan.words.data() + plan.at_list(), list.data(), list.size() * sizeof(int32_t));
-        if (shift) std::memcpy(plan.words.data() + plan.at_shift(), shift, 2 * (size_t)n_maps * sizeof(int32_t));
-    } catch (const std::bad_alloc &) {
-        return fail(PWPP_E_NOMEM, "no host memory for the lists of %d maps and %d frames", n_maps, frames);
-    }
-    return PWPP_OK;
+    const size_t words = plan.map_cells * 4, halves = plan.map_cells * 2;  // (bytes; sum_out == sum_in, n_out == n_in: in place)
+    const int rc = range_args({{sum_in, words, "sum_in"}, {n_in, halves, "n_in"}, {sum_out, words, "sum_out"}, {n_out, halves, "n_out"}, {mean, words, "mean"}},
+                              {{0, 2}, {1, 3}}, plan.moved);
+    P = pwpp_elev_magic(m->n_max);
+    return rc ? rc : map_plan_words(frames, pose, z_offset, map_of_frame, shift, plan);
 }
 
-// (after mem: what PWPP_MEM_DEVICE asks of the arrays -- words 4-byte, counts 2-byte aligned, no more)
+// (after mem: what PWPP_MEM_DEVICE asks of the arrays -- words 4-byte, counts 2-byte aligned, no more; named in this order)
 int height_alignment_args(int mem, const void *height, const void *sum_in, const void *n_in, const void *sum_out, const void *n_out, const void *mean) {
-    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
-    const auto off = [](const void *p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-    if (off(height, 3u) || off(sum_in, 3u) || off(sum_out, 3u) || off(mean, 3u))
-        return fail(PWPP_E_ARG, "the %s must be 4-byte aligned", off(height, 3u) ? "height images" : (off(mean, 3u) ? "mean" : "sums"));
-    if (off(n_in, 1u) || off(n_out, 1u)) return fail(PWPP_E_ARG, "the counts must be 2-byte aligned");
-    return PWPP_OK;
+    return alignment_args(mem, {{height, 3u, "height images"}, {mean, 3u, "mean"}, {sum_in, 3u, "sums"}, {sum_out, 3u, "sums"}, {n_in, 1u, "counts"}, {n_out, 1u, "counts"}});
 }
 
 // (the plan's words first: they move into the staging; `height` is the frame images' section: the caller's, or the ground raster's)
 struct HeightSections {
     int up, height, sum_in, n_in, sum_out, n_out, mean;
 };
-HeightSections height_sections(Staging &st, HeightPlan &plan, int s_height, const int32_t *sum_in, const int16_t *n_in, int32_t *sum_out, int16_t *n_out,
+HeightSections height_sections(Staging &st, MapPlan &plan, int s_height, const int32_t *sum_in, const int16_t *n_in, int32_t *sum_out, int16_t *n_out,
                                float *mean) {
     HeightSections s;
     const size_t n_words = (plan.map_cells + 1) / 2, n_bytes = plan.map_cells * sizeof(int16_t);
@@ -3151,10 +3140,10 @@ HeightSections height_sections(Staging &st, HeightPlan &plan, int s_height, cons
     s.mean = st.add(mean ? plan.map_cells : 0, mean, Staging::kOut);
     return s;
 }
-int height_launch(pwpp_handle *h, const Staging &st, const HeightSections &s, const HeightPlan &plan, int frames) {
+int height_launch(pwpp_handle *h, const Staging &st, const HeightSections &s, const MapPlan &plan, const PwppElevationParams &P, int frames) {
     const int32_t *words = st.dev<const int32_t>(s.up);
-    return pwpp_launch_fuse_height(&plan.G, &plan.P, frames, st.dev<const float>(s.height), st.dev<const double>(s.up),
-                                   reinterpret_cast<const double *>(words + plan.at_offset()), plan.n_poses, plan.n_maps, words + plan.at_begin(),
+    return pwpp_launch_fuse_height(&plan.G, &P, frames, st.dev<const float>(s.height), st.dev<const double>(s.up),
+                                   reinterpret_cast<const double *>(words + plan.at_per_pose()), plan.n_poses, plan.n_maps, words + plan.at_begin(),
                                    words + plan.at_list(), plan.listed, plan.shifted ? words + plan.at_shift() : nullptr, st.dev<const int32_t>(s.sum_in),
                                    st.dev<const int16_t>(s.n_in), st.dev<int32_t>(s.sum_out), st.dev<int16_t>(s.n_out), st.dev<float>(s.mean),
                                    h->elevation_path, h->stream);
@@ -3173,14 +3162,15 @@ int pwpp_fuse_height_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames,
     int rc = image_args(g->nx, g->ny, frames, kElevationWho, cells);
     if (rc) return rc;
     if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the elevation fusion's frame grid takes 0", g->flags);
-    HeightPlan plan;
-    if ((rc = height_args(g, frames, pose, z_offset, n_poses, map_of_frame, m, n_maps, shift, sum_in, n_in, sum_out, n_out, mean, plan))) return rc;
+    MapPlan plan;
+    PwppElevationParams P;
+    if ((rc = height_args(g, frames, pose, z_offset, n_poses, map_of_frame, m, n_maps, shift, sum_in, n_in, sum_out, n_out, mean, plan, P))) return rc;
     if ((rc = mem_args(mem, kElevationWho))) return rc;
     if ((rc = height_alignment_args(mem, height, sum_in, n_in, sum_out, n_out, mean))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const int s_height = st.add(cells, height, Staging::kIn);
     const HeightSections s = height_sections(st, plan, s_height, sum_in, n_in, sum_out, n_out, mean);
-    return run_on_image(h, st, [&] { return height_launch(h, st, s, plan, frames); });
+    return run_on_image(h, st, [&] { return height_launch(h, st, s, plan, P, frames); });
 }
 
 // pwpp_rasterize_ground into a section of the cluster buffer (or the caller's images) and pwpp_fuse_height_grid on it, one enqueued sequence.
@@ -3189,26 +3179,18 @@ int pwpp_fuse_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first,
                      int32_t *sum_out, int16_t *n_out, float *mean, float *height) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (const char *what = height_null(g, g, "", pose, m, sum_out, n_out)) return fail(PWPP_E_ARG, "null %s", what);
-    if (frames < 1 || g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, g->nx, g->ny);
-    int rc = side_args(g->nx, g->ny, kElevationWho);
+    int rc = ground_first_args(g, frames, kElevationWho);
     if (rc) return rc;
-    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
-    HeightPlan plan;
-    if ((rc = height_args(g, frames, pose, z_offset, n_poses, map_of_frame, m, n_maps, shift, sum_in, n_in, sum_out, n_out, mean, plan))) return rc;
+    MapPlan plan;
+    PwppElevationParams P;
+    if ((rc = height_args(g, frames, pose, z_offset, n_poses, map_of_frame, m, n_maps, shift, sum_in, n_in, sum_out, n_out, mean, plan, P))) return rc;
     size_t cells = 0;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     if ((rc = height_alignment_args(mem, height, sum_in, n_in, sum_out, n_out, mean))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const int s_height = add_image(st, cells, height, true);
     const HeightSections s = height_sections(st, plan, s_height, sum_in, n_in, sum_out, n_out, mean);
-    if ((rc = st.begin())) return rc;
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
-    if ((rc = ground_view(h, v))) return rc;
-    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), nullptr, h->stream);
-    if (lrc == 0) lrc = height_launch(h, st, s, plan, frames);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    return run_on_ground(h, st, g, frame_first, frames, s_height, -1, [&] { return height_launch(h, st, s, plan, P, frames); });
 }
 
 // ---- terrain analysis: step, slope, roughness and cost of the window around every cell of a height image --------------------------
@@ -3227,27 +3209,15 @@ int terrain_args(const pwpp_terrain_params *p, double cell, size_t cells, const 
         return fail(PWPP_E_ARG, "limits %g (step), %g (slope), %g (rough): each > 0 expected, +inf allowed, not a NaN", (double)p->step_max,
                     (double)p->slope_max, (double)p->rough_max);
     if (p->pad_ != 0) return fail(PWPP_E_ARG, "pad_ %d of the terrain parameters: 0 expected", p->pad_);
-    struct Range {
-        const void *p;
-        size_t bytes;
-        const char *name;
-    };
-    const Range r[6] = {{height, cells * 4, "height"}, {step, cells * 4, "step"}, {slope, cells * 4, "slope"},
-                        {rough, cells * 4, "rough"},   {count, cells, "count"},   {cost, cells, "cost"}};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 6; ++j)
-            if (ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) return fail(PWPP_E_ARG, "%s and %s overlap", r[i].name, r[j].name);
     rule = PwppTerrainRule{p->radius, p->min_known, p->step_max, p->slope_max, p->rough_max, 1024.0 * cell};
-    return PWPP_OK;
+    const size_t floats = cells * 4;  // (bytes)
+    return range_args({{height, floats, "height"}, {step, floats, "step"}, {slope, floats, "slope"}, {rough, floats, "rough"}, {count, cells, "count"}, {cost, cells, "cost"}},
+                      {}, false);
 }
 
 // (after mem: what PWPP_MEM_DEVICE asks of the arrays -- floats 4-byte aligned, bytes anywhere)
 int terrain_alignment_args(int mem, const void *height, const void *step, const void *slope, const void *rough) {
-    if (mem != PWPP_MEM_DEVICE) return PWPP_OK;
-    const auto off = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
-    if (off(height) || off(step) || off(slope) || off(rough))
-        return fail(PWPP_E_ARG, "the %s must be 4-byte aligned", off(height) ? "height images" : (off(step) ? "step" : (off(slope) ? "slope" : "rough")));
-    return PWPP_OK;
+    return alignment_args(mem, {{height, 3u, "height images"}, {step, 3u, "step"}, {slope, 3u, "slope"}, {rough, 3u, "rough"}});
 }
 
 // (`height` is the height images' section: the caller's, or the ground raster's)
@@ -3296,10 +3266,8 @@ int pwpp_terrain_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_fir
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !p) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : "terrain parameters");
     if (!step && !slope && !rough && !count && !cost) return fail(PWPP_E_ARG, "null outputs: at least one of step, slope, rough, count and cost expected");
-    if (frames < 1 || g->nx < 1 || g->ny < 1) return fail(PWPP_E_ARG, "%d frames of %d x %d cells", frames, g->nx, g->ny);
-    int rc = side_args(g->nx, g->ny, kTerrainWho);
+    int rc = ground_first_args(g, frames, kTerrainWho);
     if (rc) return rc;
-    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
     PwppTerrainRule rule;
     // (the byte ranges of the overlap check: sides <= 2^15 and frames < 2^31, the product fits 64 bits; ground_grid_args names one beyond 2^31)
     size_t cells = (size_t)g->nx * (size_t)g->ny * (size_t)frames;
@@ -3309,14 +3277,7 @@ int pwpp_terrain_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_fir
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const int s_height = add_image(st, cells, height, true);
     const TerrainSections s = terrain_sections(st, cells, s_height, step, slope, rough, count, cost);
-    if ((rc = st.begin())) return rc;
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
-    if ((rc = ground_view(h, v))) return rc;
-    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), nullptr, h->stream);
-    if (lrc == 0) lrc = terrain_launch(h, st, s, rule, g->nx, g->ny, frames);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    return run_on_ground(h, st, g, frame_first, frames, s_height, -1, [&] { return terrain_launch(h, st, s, rule, g->nx, g->ny, frames); });
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

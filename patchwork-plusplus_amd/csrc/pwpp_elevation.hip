@@ -4,8 +4,8 @@
 // operation on the handle's stream, like the occupancy fusion: nothing of the estimate pipeline is read or written.
 //
 // One launch per call:
-//   k_fuse_height   a workgroup per (map, run of 256 cells in row-major order), a lane per map cell, as in k_fuse.  The lane reads
-//            its start -- the shifted cell of sum_in and n_in, normalised, or nothing -- keeps sum and n in registers while it walks
+//   k_fuse_height   a workgroup per (map, run of 256 cells in row-major order), a lane per map cell, as in k_fuse (pwpp_map_lane of
+//            pwpp_fusion.h).  The lane reads its start -- the shifted cell of sum_in and n_in, normalised, or nothing -- keeps sum and n in registers while it walks
 //            the frames of its map in ascending order (the CSR the host built from map_of_frame), and stores sum, n and the mean
 //            once.  A gather: a map cell asks the frames at its centre, a frame cell never writes.  The pose and the offset of a
 //            frame and the list are the same for every lane of a workgroup: scalar loads.
@@ -26,7 +26,6 @@
 
 namespace {
 
-constexpr int kElevBlock = PWPP_FUSE_RUN;
 // What option "elevation_path" = 0 means: path 2 (true) or path 1 (false).  Decided by tools/elevation_fusion_cost.py
 // (profiles/elevation_fusion_cost.txt), not in advance.
 constexpr bool kElevationDefaultFast = true;
@@ -34,31 +33,22 @@ constexpr bool kElevationDefaultFast = true;
 struct ElevCall {
     PwppFusionGeometry G;
     PwppElevationParams P;
-    int32_t per_map;  // NX * NY (<= 2^30)
-    int32_t runs;     // ceil(per_map / 256): block = map * runs + run
-    int32_t n_maps, frames, n_poses, listed;
+    PwppMapRuns R;
 };
 
 // grid (n_maps * runs)
 template <bool RECIP, bool FAST>
-__global__ __launch_bounds__(kElevBlock) void k_fuse_height(ElevCall C, const float *height, const double *poses, const double *z_offset, const int32_t *begin,
-                                                            const int32_t *list, const int32_t *shift, const int32_t *sum_in, const int16_t *n_in,
-                                                            int32_t *sum_out, int16_t *n_out, uint32_t *mean) {
-    const unsigned b = blockIdx.x, run = b % (unsigned)C.runs, k = b / (unsigned)C.runs;
-    if (k >= (unsigned)C.n_maps) return;
-    const int c = (int)run * kElevBlock + (int)threadIdx.x;  // (per_map <= 2^30)
-    if (c >= C.per_map) return;
-    const int jy = c / C.G.NX, jx = c - jy * C.G.NX;
-    const size_t mbase = (size_t)k * (size_t)C.per_map;
-    const int32_t sx = shift ? shift[2 * (size_t)k] : 0, sy = shift ? shift[2 * (size_t)k + 1] : 0;
-    int32_t sum = 0, n = 0;
-    pwpp_elev_start(sum_in ? sum_in + mbase : nullptr, n_in ? n_in + mbase : nullptr, jx, jy, sx, sy, C.G.NX, C.G.NY, C.P.n_max, sum, n);
-    // the map's frames: begin is ascending and ends at `listed` (the host built it); the clamps bound the loop all the same
-    const int32_t first = max(begin[k], 0), last = min(begin[(size_t)k + 1], C.listed);
-    pwpp_elev_cell<RECIP, FAST>(C.G, C.P, sum, n, jx, jy, height, C.frames, poses, z_offset, C.n_poses, list, first, last);
-    sum_out[mbase + (size_t)c] = sum;
-    n_out[mbase + (size_t)c] = (int16_t)n;
-    if (mean) mean[mbase + (size_t)c] = pwpp_elev_mean_bits(sum, n);
+__global__ __launch_bounds__(PWPP_FUSE_RUN) void k_fuse_height(ElevCall C, const float *height, const double *poses, const double *z_offset, const int32_t *begin,
+                                                               const int32_t *list, const int32_t *shift, const int32_t *sum_in, const int16_t *n_in,
+                                                               int32_t *sum_out, int16_t *n_out, uint32_t *mean) {
+    pwpp_map_lane(C.R, C.G.NX, blockIdx.x, threadIdx.x, shift, begin, [&](const PwppMapLane &l) {
+        int32_t sum = 0, n = 0;
+        pwpp_elev_start(sum_in ? sum_in + l.mbase : nullptr, n_in ? n_in + l.mbase : nullptr, l.jx, l.jy, l.sx, l.sy, C.G.NX, C.G.NY, C.P.n_max, sum, n);
+        pwpp_elev_cell<RECIP, FAST>(C.G, C.P, sum, n, l.jx, l.jy, height, C.R.frames, poses, z_offset, C.R.n_poses, list, l.first, l.last);
+        sum_out[l.mbase + (size_t)l.c] = sum;
+        n_out[l.mbase + (size_t)l.c] = (int16_t)n;
+        if (mean) mean[l.mbase + (size_t)l.c] = pwpp_elev_mean_bits(sum, n);
+    });
 }
 
 }  // namespace
@@ -74,14 +64,11 @@ extern "C" int pwpp_launch_fuse_height(const PwppFusionGeometry *G, const PwppEl
                                        int path, hipStream_t stream) {
     ElevCall C;
     C.G = *G, C.P = *P;
-    C.per_map = G->NX * G->NY;
-    C.runs = (C.per_map + kElevBlock - 1) / kElevBlock;
-    C.n_maps = n_maps, C.frames = frames, C.n_poses = n_poses, C.listed = listed;
-    const int64_t blocks = (int64_t)n_maps * C.runs;
-    if (blocks > INT32_MAX) return (int)hipErrorInvalidConfiguration;
+    const int64_t blocks = pwpp_map_runs(*G, n_maps, frames, n_poses, listed, C.R);
+    if (blocks < 0) return (int)hipErrorInvalidConfiguration;
     const bool fast = path == 0 ? kElevationDefaultFast : path == 2;
     uint32_t *bits = reinterpret_cast<uint32_t *>(mean);
-    const dim3 grid((unsigned)blocks), block(kElevBlock);
+    const dim3 grid((unsigned)blocks), block(PWPP_FUSE_RUN);
     if (!fast)
         hipLaunchKernelGGL((k_fuse_height<false, false>), grid, block, 0, stream, C, height, poses, z_offset, begin, list, shift, sum_in, n_in, sum_out, n_out, bits);
     else if (G->inv_cell != 0.0)

@@ -18,11 +18,15 @@
 // THE UPDATE in int32: occupied L = min(L + hit, l_max), free L = max(L - miss, l_min).  With an int16 L and hit, miss in
 // 0 .. 32767 neither sum leaves int32, and the result lies in the int16 range again: min(L + hit, l_max) <= 32767 and >= L,
 // max(L - miss, l_min) >= -32768 and <= L.
+// THE DEALING of map cells to lanes and the CSR of each map's frames, for this fusion and pwpp_elevation.h's: pwpp_map_runs, _lane, _lists.
 #ifndef PWPP_FUSION_H
 #define PWPP_FUSION_H
 
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "pwpp_unionfind.h"  // PWPP_HD
 
@@ -53,6 +57,59 @@ inline bool pwpp_fuse_reciprocal(double cell, double &inv) {
     if (!(cell > 0.0) || !isfinite(cell) || frexp(cell, &e) != 0.5 || e < -1020 || e > 1020) return false;
     inv = 1.0 / cell;
     return true;
+}
+
+// ---- THE LANE OF A MAP RUN, for both fusions: a workgroup per (map, run of PWPP_FUSE_RUN cells in row-major order), block = map * runs +
+// run, a lane per map cell, each map's frames from the CSR of map_of_frame.  The counts of a call, the tail of the kernels' argument structs:
+struct PwppMapRuns {
+    int32_t per_map, runs;  // NX * NY (<= 2^30); ceil(per_map / PWPP_FUSE_RUN)
+    int32_t n_maps, frames, n_poses, listed;
+};
+
+// fills the counts; returns the number of workgroups, or -1 where a grid cannot hold them
+inline int64_t pwpp_map_runs(const PwppFusionGeometry &G, int n_maps, int frames, int n_poses, int listed, PwppMapRuns &R) {
+    R.per_map = G.NX * G.NY, R.runs = (R.per_map + PWPP_FUSE_RUN - 1) / PWPP_FUSE_RUN;
+    R.n_maps = n_maps, R.frames = frames, R.n_poses = n_poses, R.listed = listed;
+    const int64_t blocks = (int64_t)n_maps * R.runs;
+    return blocks > INT32_MAX ? -1 : blocks;
+}
+
+// What a lane works on: cell c = (jx, jy) of map k, whose cells begin at mbase; the map's shift; its frames list[first .. last).
+struct PwppMapLane {
+    int32_t k, c, jx, jy, sx, sy, first, last;
+    size_t mbase;
+};
+// Calls cell(const PwppMapLane &) for the cell of lane `lane` of workgroup `block`, or not at all: the lane has no cell.  `shift`: n_maps x
+// {sx, sy}, or null: none.  `begin` is ascending and ends at `listed` (the host built it); the clamps bound the loop all the same.
+template <class Cell>
+PWPP_HD inline void pwpp_map_lane(const PwppMapRuns &R, int NX, unsigned block, unsigned lane, const int32_t *shift, const int32_t *begin, Cell cell) {
+    const unsigned run = block % (unsigned)R.runs, k = block / (unsigned)R.runs;
+    if (k >= (unsigned)R.n_maps) return;
+    const int c = (int)run * PWPP_FUSE_RUN + (int)lane;  // (per_map <= 2^30)
+    if (c >= R.per_map) return;
+    PwppMapLane l;
+    l.k = (int32_t)k, l.c = c;
+    l.jy = c / NX, l.jx = c - l.jy * NX;
+    l.mbase = (size_t)k * (size_t)R.per_map;
+    l.sx = shift ? shift[2 * (size_t)k] : 0, l.sy = shift ? shift[2 * (size_t)k + 1] : 0;
+    const int32_t b0 = begin[k], b1 = begin[(size_t)k + 1];
+    l.first = b0 > 0 ? b0 : 0, l.last = b1 < R.listed ? b1 : R.listed;
+    cell(l);
+}
+
+// ---- which map frame i updates under the caller's map_of_frame (null: one map for all, or frame i's is map i; -1: none), and the
+// CSR of that rule: a counting sort of the frames by their map keeps each map's frames in ascending order.  begin[n_maps + 1], list[].
+inline int32_t pwpp_map_of_frame(const int32_t *map_of_frame, int n_maps, int i) { return map_of_frame ? map_of_frame[i] : (n_maps == 1 ? 0 : i); }
+inline void pwpp_map_lists(const int32_t *map_of_frame, int n_maps, int frames, std::vector<int32_t> &begin, std::vector<int32_t> &list) {
+    begin.assign((size_t)n_maps + 1, 0);
+    int listed = 0;
+    for (int i = 0; i < frames; ++i)
+        if (pwpp_map_of_frame(map_of_frame, n_maps, i) >= 0) ++begin[(size_t)pwpp_map_of_frame(map_of_frame, n_maps, i) + 1], ++listed;
+    for (int k = 0; k < n_maps; ++k) begin[(size_t)k + 1] += begin[k];
+    list.assign((size_t)listed, 0);
+    std::vector<int32_t> next(begin.begin(), begin.end() - 1);
+    for (int i = 0; i < frames; ++i)
+        if (pwpp_map_of_frame(map_of_frame, n_maps, i) >= 0) list[(size_t)next[(size_t)pwpp_map_of_frame(map_of_frame, n_maps, i)]++] = i;
 }
 
 // ---- the start of a cell: the shifted read.  (jx + sx, jy + sy) in 64 bits: |sx| may be anything an int32 holds.

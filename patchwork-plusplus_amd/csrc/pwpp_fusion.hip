@@ -4,7 +4,8 @@
 // pipeline is read or written.
 //
 // One launch per call:
-//   k_fuse   a workgroup per (map, run of 256 cells in row-major order), a lane per map cell.  The lane reads its start -- the
+//   k_fuse   a workgroup per (map, run of 256 cells in row-major order), a lane per map cell: the dealing that pwpp_map_lane of
+//            pwpp_fusion.h states, for the elevation fusion's kernel as well.  The lane reads its start -- the
 //            shifted cell of map_in, or 0 -- keeps L in a register while it walks the frames of its map in ascending order (the CSR
 //            the host built from map_of_frame: begin[n_maps + 1], list[]), and stores L once as an int16 and once as the derived
 //            byte.  The operator is a gather: a map cell asks the frames, a frame cell never writes.  The pose of a frame and the
@@ -26,31 +27,27 @@
 
 namespace {
 
-constexpr int kFuseBlock = PWPP_FUSE_RUN;
-
 struct FuseCall {
     PwppFusionGeometry G;
     PwppFusionParams P;
-    int32_t per_map;  // NX * NY (<= 2^30)
-    int32_t runs;     // ceil(per_map / 256): block = map * runs + run
-    int32_t n_maps, frames, n_poses, listed;
+    PwppMapRuns R;
 };
 
 // grid (n_maps * runs)
 template <bool RECIP>
-__global__ __launch_bounds__(kFuseBlock) void k_fuse(FuseCall C, const int8_t *occupancy, const double *poses, const int32_t *begin, const int32_t *list,
-                                                     const int32_t *shift, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
-    const unsigned b = blockIdx.x, run = b % (unsigned)C.runs, k = b / (unsigned)C.runs;
-    if (k >= (unsigned)C.n_maps) return;
-    const int c = (int)run * kFuseBlock + (int)threadIdx.x;  // (per_map <= 2^30)
-    if (c >= C.per_map) return;
+__global__ __launch_bounds__(PWPP_FUSE_RUN) void k_fuse(FuseCall C, const int8_t *occupancy, const double *poses, const int32_t *begin, const int32_t *list,
+                                                        const int32_t *shift, const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy) {
+    // pwpp_map_lane spelt out: every form of the call moved this kernel's frame loop and slowed it (profiles/map_plan_refactor_ab.txt)
+    const unsigned b = blockIdx.x, run = b % (unsigned)C.R.runs, k = b / (unsigned)C.R.runs;
+    if (k >= (unsigned)C.R.n_maps) return;
+    const int c = (int)run * PWPP_FUSE_RUN + (int)threadIdx.x;  // (per_map <= 2^30)
+    if (c >= C.R.per_map) return;
     const int jy = c / C.G.NX, jx = c - jy * C.G.NX;
-    const size_t mbase = (size_t)k * (size_t)C.per_map;
+    const size_t mbase = (size_t)k * (size_t)C.R.per_map;
     const int32_t sx = shift ? shift[2 * (size_t)k] : 0, sy = shift ? shift[2 * (size_t)k + 1] : 0;
     int32_t L = pwpp_fuse_start(map_in ? map_in + mbase : nullptr, jx, jy, sx, sy, C.G.NX, C.G.NY);
-    // the map's frames: begin is ascending and ends at `listed` (the host built it); the clamps bound the loop all the same
-    const int32_t first = max(begin[k], 0), last = min(begin[(size_t)k + 1], C.listed);
-    L = pwpp_fuse_cell<RECIP>(C.G, C.P, L, jx, jy, occupancy, C.frames, poses, C.n_poses, list, first, last);
+    const int32_t first = max(begin[k], 0), last = min(begin[(size_t)k + 1], C.R.listed);
+    L = pwpp_fuse_cell<RECIP>(C.G, C.P, L, jx, jy, occupancy, C.R.frames, poses, C.R.n_poses, list, first, last);
     map_out[mbase + (size_t)c] = (int16_t)L;
     if (map_occupancy) map_occupancy[mbase + (size_t)c] = pwpp_fuse_byte(L, C.P);
 }
@@ -66,14 +63,11 @@ extern "C" int pwpp_launch_fuse_grid(const PwppFusionGeometry *G, const PwppFusi
                                      const int16_t *map_in, int16_t *map_out, int8_t *map_occupancy, int path, hipStream_t stream) {
     FuseCall C;
     C.G = *G, C.P = *P;
-    C.per_map = G->NX * G->NY;
-    C.runs = (C.per_map + kFuseBlock - 1) / kFuseBlock;
-    C.n_maps = n_maps, C.frames = frames, C.n_poses = n_poses, C.listed = listed;
-    const int64_t blocks = (int64_t)n_maps * C.runs;
-    if (blocks > INT32_MAX) return (int)hipErrorInvalidConfiguration;
+    const int64_t blocks = pwpp_map_runs(*G, n_maps, frames, n_poses, listed, C.R);
+    if (blocks < 0) return (int)hipErrorInvalidConfiguration;
     if (path == 0 && G->inv_cell != 0.0)
-        hipLaunchKernelGGL(k_fuse<true>, dim3((unsigned)blocks), dim3(kFuseBlock), 0, stream, C, occupancy, poses, begin, list, shift, map_in, map_out, map_occupancy);
+        hipLaunchKernelGGL(k_fuse<true>, dim3((unsigned)blocks), dim3(PWPP_FUSE_RUN), 0, stream, C, occupancy, poses, begin, list, shift, map_in, map_out, map_occupancy);
     else
-        hipLaunchKernelGGL(k_fuse<false>, dim3((unsigned)blocks), dim3(kFuseBlock), 0, stream, C, occupancy, poses, begin, list, shift, map_in, map_out, map_occupancy);
+        hipLaunchKernelGGL(k_fuse<false>, dim3((unsigned)blocks), dim3(PWPP_FUSE_RUN), 0, stream, C, occupancy, poses, begin, list, shift, map_in, map_out, map_occupancy);
     return (int)hipGetLastError();
 }

@@ -102,33 +102,31 @@ Maps brute_force(const Case &c) {
 // the kernel's sequence with the header's functions
 template <bool RECIP, bool FAST>
 Maps as_the_kernel(const Case &c, bool in_place) {
-    const int per_map = c.G.NX * c.G.NY, runs = (per_map + PWPP_FUSE_RUN - 1) / PWPP_FUSE_RUN;
     const PwppElevationParams P = pwpp_elev_magic(c.n_max);
-    std::vector<int32_t> begin((size_t)c.n_maps + 1, 0);
-    int listed = 0;
-    for (int f = 0; f < c.frames; ++f)
-        if (c.map_of_frame[f] >= 0) ++begin[(size_t)c.map_of_frame[f] + 1], ++listed;
-    for (int k = 0; k < c.n_maps; ++k) begin[(size_t)k + 1] += begin[k];
-    std::vector<int32_t> list((size_t)listed), next(begin.begin(), begin.end() - 1);
-    for (int f = 0; f < c.frames; ++f)
-        if (c.map_of_frame[f] >= 0) list[(size_t)next[(size_t)c.map_of_frame[f]]++] = f;
-    const size_t all = (size_t)c.n_maps * per_map;
+    // the CSR, the counts and the dealing are the shipped ones (pwpp_map_lists, pwpp_map_runs, pwpp_map_lane of pwpp_fusion.h)
+    std::vector<int32_t> begin, list;
+    pwpp_map_lists(c.map_of_frame.data(), c.n_maps, c.frames, begin, list);
+    PwppMapRuns R;
+    const int64_t blocks = pwpp_map_runs(c.G, c.n_maps, c.frames, c.n_poses, (int)list.size(), R);
+    const size_t all = (size_t)c.n_maps * R.per_map;
     Maps m{std::vector<int32_t>(all), std::vector<int16_t>(all), std::vector<uint32_t>(all)};
     if (in_place) m.sum = c.sum_in, m.n = c.n_in;  // (outputs == inputs: every cell read and written by its own lane)
     const int32_t *s_in = c.sum_in.empty() ? nullptr : (in_place ? m.sum.data() : c.sum_in.data());
     const int16_t *n_in = c.n_in.empty() ? nullptr : (in_place ? m.n.data() : c.n_in.data());
-    for (int b = 0; b < c.n_maps * runs; ++b)
-        for (int lane = 0; lane < PWPP_FUSE_RUN; ++lane) {
-            const int run = b % runs, k = b / runs, cell = run * PWPP_FUSE_RUN + lane;
-            if (cell >= per_map) continue;
-            const int jy = cell / c.G.NX, jx = cell - jy * c.G.NX;
-            const size_t base = (size_t)k * per_map;
-            int32_t sum = 0, n = 0;
-            pwpp_elev_start(s_in ? s_in + base : nullptr, n_in ? n_in + base : nullptr, jx, jy, c.shift[2 * k], c.shift[2 * k + 1], c.G.NX, c.G.NY, c.n_max, sum, n);
-            pwpp_elev_cell<RECIP, FAST>(c.G, P, sum, n, jx, jy, c.height.data(), c.frames, c.poses.data(), c.z_offset.data(), c.n_poses, list.data(), begin[k],
-                                        begin[(size_t)k + 1]);
-            m.sum[base + cell] = sum, m.n[base + cell] = (int16_t)n, m.mean[base + cell] = pwpp_elev_mean_bits(sum, n);
-        }
+    std::vector<int> dealt(all, 0);
+    for (int64_t b = 0; b < blocks; ++b)
+        for (unsigned lane = 0; lane < PWPP_FUSE_RUN; ++lane)
+            pwpp_map_lane(R, c.G.NX, (unsigned)b, lane, c.shift.data(), begin.data(), [&](const PwppMapLane &l) {
+                int32_t sum = 0, n = 0;
+                pwpp_elev_start(s_in ? s_in + l.mbase : nullptr, n_in ? n_in + l.mbase : nullptr, l.jx, l.jy, l.sx, l.sy, c.G.NX, c.G.NY, c.n_max, sum, n);
+                pwpp_elev_cell<RECIP, FAST>(c.G, P, sum, n, l.jx, l.jy, c.height.data(), c.frames, c.poses.data(), c.z_offset.data(), c.n_poses, list.data(),
+                                            l.first, l.last);
+                const size_t at = l.mbase + l.c;
+                m.sum[at] = sum, m.n[at] = (int16_t)n, m.mean[at] = pwpp_elev_mean_bits(sum, n);
+                ++dealt[at];
+            });
+    for (int n : dealt)
+        if (n != 1) std::abort();  // (every cell of every map dealt to exactly one lane)
     return m;
 }
 
@@ -189,11 +187,13 @@ int main() {
         c.G.cell = frame_cells[uni(0, 3)], c.G.CELL = cells[uni(0, 2)];
         const bool recip = pwpp_fuse_reciprocal(c.G.cell, c.G.inv_cell);  // (0.3: the division alone)
         c.G.nx = uni(1, 20), c.G.ny = uni(1, 20), c.G.NX = t % 7 == 0 ? uni(250, 300) : uni(1, 24), c.G.NY = t % 7 == 0 ? uni(1, 3) : uni(1, 24);
+        const int edge[5][3] = {{1, 1, 1}, {255, 1, 1}, {256, 1, 1}, {257, 1, 1}, {257, 1, 2}};
+        if (t < 5) c.G.NX = edge[t][0], c.G.NY = edge[t][1];  // (the shapes at which the dealing can go wrong: tools/fusion_check.cpp)
         c.G.x0 = -0.5 * c.G.cell * c.G.nx, c.G.y0 = -0.5 * c.G.cell * c.G.ny;
         c.G.X0 = -0.5 * c.G.CELL * c.G.NX + uni(-2, 2) * c.G.CELL, c.G.Y0 = -0.5 * c.G.CELL * c.G.NY;
         const int n_maxes[6] = {1, 2, 3, 7, 100, 1023};
         c.n_max = n_maxes[uni(0, 5)];
-        c.frames = uni(1, 12), c.n_maps = uni(1, 3);
+        c.frames = uni(1, 12), c.n_maps = t < 5 ? edge[t][2] : uni(1, 3);
         c.n_poses = uni(0, 1) ? 1 : c.frames;
         c.height.resize((size_t)c.frames * c.G.nx * c.G.ny);
         const float special[] = {(float)inf, (float)-inf, 0.5f / 1024, 1.5f / 1024, -2.5f / 1024, -0.0f, 1024.0f, -1024.0f, beyond, -beyond, 1000.25f, -999.75f};

@@ -90,30 +90,27 @@ Maps brute_force(const Case &c) {
 // the kernel's sequence with the header's functions
 template <bool RECIP>
 Maps as_the_kernel(const Case &c, bool in_place) {
-    const int per_map = c.G.NX * c.G.NY, runs = (per_map + PWPP_FUSE_RUN - 1) / PWPP_FUSE_RUN;
-    // the CSR the host side builds: a counting sort
-    std::vector<int32_t> begin((size_t)c.n_maps + 1, 0);
-    int listed = 0;
-    for (int f = 0; f < c.frames; ++f)
-        if (c.map_of_frame[f] >= 0) ++begin[(size_t)c.map_of_frame[f] + 1], ++listed;
-    for (int k = 0; k < c.n_maps; ++k) begin[(size_t)k + 1] += begin[k];
-    std::vector<int32_t> list((size_t)listed), next(begin.begin(), begin.end() - 1);
-    for (int f = 0; f < c.frames; ++f)
-        if (c.map_of_frame[f] >= 0) list[(size_t)next[(size_t)c.map_of_frame[f]]++] = f;
-    Maps m{std::vector<int16_t>((size_t)c.n_maps * per_map), std::vector<int8_t>((size_t)c.n_maps * per_map)};
+    // the CSR, the counts and the dealing are the shipped ones (pwpp_map_lists, pwpp_map_runs, pwpp_map_lane)
+    std::vector<int32_t> begin, list;
+    pwpp_map_lists(c.map_of_frame.data(), c.n_maps, c.frames, begin, list);
+    PwppMapRuns R;
+    const int64_t blocks = pwpp_map_runs(c.G, c.n_maps, c.frames, c.n_poses, (int)list.size(), R);
+    const size_t all = (size_t)c.n_maps * R.per_map;
+    Maps m{std::vector<int16_t>(all), std::vector<int8_t>(all)};
     if (in_place) m.L = c.map_in;  // (map_out == map_in: every cell read and written by its own lane)
     const int16_t *in = c.map_in.empty() ? nullptr : (in_place ? m.L.data() : c.map_in.data());
-    for (int b = 0; b < c.n_maps * runs; ++b)
-        for (int lane = 0; lane < PWPP_FUSE_RUN; ++lane) {
-            const int run = b % runs, k = b / runs, cell = run * PWPP_FUSE_RUN + lane;
-            if (cell >= per_map) continue;
-            const int jy = cell / c.G.NX, jx = cell - jy * c.G.NX;
-            const size_t base = (size_t)k * per_map;
-            int32_t L = pwpp_fuse_start(in ? in + base : nullptr, jx, jy, c.shift[2 * k], c.shift[2 * k + 1], c.G.NX, c.G.NY);
-            L = pwpp_fuse_cell<RECIP>(c.G, c.P, L, jx, jy, c.occupancy.data(), c.frames, c.poses.data(), c.n_poses, list.data(), begin[k], begin[(size_t)k + 1]);
-            m.L[base + cell] = (int16_t)L;
-            m.byte[base + cell] = pwpp_fuse_byte(L, c.P);
-        }
+    std::vector<int> dealt(all, 0);
+    for (int64_t b = 0; b < blocks; ++b)
+        for (unsigned lane = 0; lane < PWPP_FUSE_RUN; ++lane)
+            pwpp_map_lane(R, c.G.NX, (unsigned)b, lane, c.shift.data(), begin.data(), [&](const PwppMapLane &l) {
+                int32_t L = pwpp_fuse_start(in ? in + l.mbase : nullptr, l.jx, l.jy, l.sx, l.sy, c.G.NX, c.G.NY);
+                L = pwpp_fuse_cell<RECIP>(c.G, c.P, L, l.jx, l.jy, c.occupancy.data(), c.frames, c.poses.data(), c.n_poses, list.data(), l.first, l.last);
+                m.L[l.mbase + l.c] = (int16_t)L;
+                m.byte[l.mbase + l.c] = pwpp_fuse_byte(L, c.P);
+                ++dealt[l.mbase + l.c];
+            });
+    for (int n : dealt)
+        if (n != 1) std::abort();  // (every cell of every map dealt to exactly one lane)
     return m;
 }
 
@@ -132,13 +129,16 @@ int main() {
         const bool recip = pwpp_fuse_reciprocal(c.G.cell, c.G.inv_cell);  // (0.3: the division alone)
         if (recip != (c.G.cell != 0.3)) ++mismatches;
         c.G.nx = uni(1, 20), c.G.ny = uni(1, 20), c.G.NX = t % 7 == 0 ? uni(250, 300) : uni(1, 24), c.G.NY = t % 7 == 0 ? uni(1, 3) : uni(1, 24);
+        // the shapes at which the dealing can go wrong: one cell; a lane short of a run, a run, a run and a lane; the last in two maps
+        const int edge[5][3] = {{1, 1, 1}, {255, 1, 1}, {256, 1, 1}, {257, 1, 1}, {257, 1, 2}};
+        if (t < 5) c.G.NX = edge[t][0], c.G.NY = edge[t][1];
         c.G.x0 = -0.5 * c.G.cell * c.G.nx, c.G.y0 = -0.5 * c.G.cell * c.G.ny;
         c.G.X0 = -0.5 * c.G.CELL * c.G.NX + uni(-2, 2) * c.G.CELL, c.G.Y0 = -0.5 * c.G.CELL * c.G.NY;
         const bool extreme = t % 5 == 0;
         c.P.hit = extreme ? (uni(0, 1) ? 32767 : 0) : uni(0, 300), c.P.miss = extreme ? (uni(0, 1) ? 32767 : 0) : uni(0, 300);
         c.P.l_min = extreme ? -32768 : -uni(0, 500), c.P.l_max = extreme ? 32767 : uni(0, 500);
         c.P.free_at = extreme ? -32768 : uni(-300, 100), c.P.occupied_at = extreme ? 32767 : c.P.free_at + uni(1, 200);
-        c.frames = uni(1, 6), c.n_maps = uni(1, 3);
+        c.frames = uni(1, 6), c.n_maps = t < 5 ? edge[t][2] : uni(1, 3);
         c.n_poses = uni(0, 1) ? 1 : c.frames;
         c.occupancy.resize((size_t)c.frames * c.G.nx * c.G.ny);
         const int fill = uni(0, 3);
