@@ -1023,6 +1023,94 @@ PWPP_API int pwpp_terrain_ground(pwpp_handle *h, const pwpp_ground_grid *g /* fl
                                  const pwpp_terrain_params *p, float *step, float *slope, float *rough, uint8_t *count, int8_t *cost,
                                  float *height /* the per-frame images, may be NULL: kept in the handle's buffer */);
 
+/* ---- cost to reach: exact shortest paths over a cost image from one source cell per frame (pwpp_reach_grid, pwpp_reach_ground) ----
+ * The first thing a planner asks of a cost image: what does it cost to get from where the vehicle stands to every cell, and through
+ * which neighbour.  For every frame these calls give that field over the 8-connected cells in integers.  With positive integer
+ * step costs the field is the one fixed point of the relaxation, so every schedule of the kernels gives the same bytes as a
+ * Dijkstra on the host; no floating point is involved.  Each frame is on its own; frames never influence each other.
+ *   cost      cost[f][iy][ix], an int8 in the value range of the terrain operator's `cost` and the visibility operator's
+ *             `occupancy`: c < 0 unknown, 0 .. 100 a traversal cost, anything >= lethal impassable.
+ *   params    base 1 .. 255, what a cell of free ground costs; lethal 1 .. 101 (101: no value is lethal); unknown -1 .. 100 (-1: an
+ *             unknown cell is impassable; otherwise it counts as that cost byte, and the lethal rule applies to it as to any
+ *             cost); clearance2 >= 0, read only when dist2 != NULL; max_reach >= 0 (0: unlimited); pad_ 0.
+ *   passable  A cell is passable iff its (possibly substituted) cost is in 0 .. lethal - 1 and (dist2 == NULL or dist2[cell] >
+ *             clearance2).  dist2 is the image of pwpp_distance_grid (squared cells, PWPP_DIST_BEYOND allowed); with it,
+ *             clearance2 = 0 blocks the occupied cells themselves.  The source cell is passable whatever its bytes say -- it holds
+ *             the vehicle -- as the visibility operator's origin never blocks.
+ *   term      t(cell) = base + cost for a passable cell; t = base for a source that is passable only by the rule above.  t <= base + 100.
+ *   step      from a to one of its 8 neighbours b, both passable and inside the image: step(a, b) = w * (t(a) + t(b)), w = 5 across
+ *             an edge and w = 7 across a corner.  A corner step exists only if both cells that share an edge with a and with b are
+ *             passable: paths do not cut corners and do not squeeze between two diagonal blocked cells, the stance of the
+ *             visibility walk.  step is symmetric, so the field from a goal equals the field to it.  The weights 5 and 7 are the
+ *             contract, not an approximation of anything.
+ *   reach     reach[f][iy][ix], an int32: the minimum over all step paths from the frame's source of the sum of steps; 0 at the
+ *             source; PWPP_REACH_NONE where no path exists.
+ *   from      from[f][iy][ix], an int32, may be NULL: among the neighbours n with an existing step n -> c and reach[n] + step(n, c)
+ *             == reach[c], the smallest index jy * nx + jx.  The source's own index at the source; -1 where reach is
+ *             PWPP_REACH_NONE.  A function of the reach image and the passability alone.  Following from ends at the source,
+ *             because reach strictly decreases along it.
+ *   max_reach > 0: every cell whose true value exceeds it reports PWPP_REACH_NONE / -1, and every other cell exactly what the
+ *             unlimited call gives (every prefix of a shortest path is no dearer than the path): it bounds the work and is not an
+ *             approximation.
+ *   range     14 * (base + 100) * (nx * ny - 1) <= 2^31 - 2, evaluated in 64 bits; otherwise PWPP_E_ARG, naming the product.  It
+ *             keeps every true value below PWPP_REACH_NONE in 32 bits (csrc/pwpp_reach.h has the proof).
+ *   sources   one cell per frame, given as the visibility's origins are: n_sources is 1 (for every frame) or `frames`.
+ *             pwpp_reach_grid: n_sources x {sx, sy}, host memory whatever `mem`, copied at the call.  pwpp_reach_ground: metres,
+ *             turned into cells by the raster's cell rule.  A source outside the image, a position that is not finite, any other
+ *             count: PWPP_E_ARG, naming the entry.
+ *   reach_ground  enqueues pwpp_rasterize_ground(g, frame_first, frames), pwpp_terrain_grid for its cost alone and the reach, as
+ *             one sequence.  The cost image is exactly what pwpp_terrain_ground gives, written for the caller where asked for and
+ *             kept in the handle's cluster buffer otherwise.  No dist2 in this call.  Before any estimate call: PWPP_E_STATE.
+ *   mem       PWPP_MEM_HOST: every image is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- dist2, reach and from 4-byte aligned, the cost bytes at any address -- enqueued on
+ *             the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order.  pwpp_reach_grid: a null handle, cost, parameters,
+ *             source, reach; frames or a side < 1, a side > 32768, nx * ny * frames beyond 2^31; base, lethal, unknown, clearance2
+ *             (with dist2 only), max_reach, pad_; the range; the count of sources, then the first source outside the image; two of
+ *             the caller's images overlapping; mem; in PWPP_MEM_DEVICE an int32 image below its alignment.  pwpp_reach_ground: a
+ *             null handle, grid, terrain parameters, reach parameters, source, reach; frames or a side < 1, a side > 32768,
+ *             g->flags other than 0 or PWPP_GRID_GROUND_ONLY; the terrain parameters as pwpp_terrain_ground names them; the reach
+ *             parameters and the range as above; the grid's origin and cell; the count of sources, then the first that is not
+ *             finite or lies outside the grid; the overlaps; then what pwpp_rasterize_ground checks -- mem, PWPP_E_STATE before
+ *             any estimate call, the frame range, the product beyond 2^31 -- and the alignment.
+ *   defect    Every loop of the kernels has a bound derived from the image (at most nx * ny + 1 sweeps over the image or passes over
+ *             its tiles, at most tile cells + 1 sweeps per visit of a tile).  By the fixed-point argument only a defect of the
+ *             library can reach it; then no kernel loops on: PWPP_MEM_HOST returns PWPP_E_HIP, "internal error", and in
+ *             PWPP_MEM_DEVICE reach is PWPP_REACH_NONE at the source of such a frame, which no result has.  The from pass does not
+ *             write the field: a value it finds no predecessor for (a defect too) is reported the same way in PWPP_MEM_HOST and
+ *             shows in PWPP_MEM_DEVICE as from = -1 beside a reach that is not PWPP_REACH_NONE, which no result has either.
+ *   buffers   Working memory -- a uint16 per cell, one word, the uploaded sources -- and in PWPP_MEM_HOST the staged images lie in the
+ *             cluster buffer; counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.  pwpp_reach_grid needs a handle for
+ *             its stream and this buffer only.
+ * The same bytes for every mem, alignment and value of the option "reach_path".  With neither function called nothing is
+ * allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_REACH 1
+#define PWPP_REACH_NONE 0x7fffffff
+typedef struct pwpp_reach_params {   /* 24 bytes */
+    int32_t base;        /* what a cell of free ground costs; 1 .. 255 */
+    int32_t lethal;      /* a cost byte >= lethal is impassable; 1 .. 101 (101: none is) */
+    int32_t unknown;     /* -1: an unknown cell (cost < 0) is impassable; 0 .. 100: it counts as this cost byte */
+    int32_t clearance2;  /* with dist2: passable needs dist2 > clearance2 (squared cells); >= 0 */
+    int32_t max_reach;   /* 0: unlimited; > 0: cells beyond it report PWPP_REACH_NONE */
+    int32_t pad_;        /* 0 */
+} pwpp_reach_params;
+
+/* any cost images: needs a handle (stream, buffer), no estimate call -- like pwpp_terrain_grid */
+PWPP_API int pwpp_reach_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost /* [frames][ny][nx] */,
+                             const int32_t *dist2 /* same shape, may be NULL */, const pwpp_reach_params *p,
+                             const int32_t *source /* host: n_sources x {sx, sy} */, int n_sources /* 1 or frames */,
+                             int32_t *reach /* same shape */, int32_t *from /* same shape, may be NULL */);
+/* rasterize_ground + the terrain's cost + reach for frames of the LAST estimate call, one enqueued sequence -- like pwpp_terrain_ground */
+PWPP_API int pwpp_reach_ground(pwpp_handle *h, const pwpp_ground_grid *g /* flags: 0 or PWPP_GRID_GROUND_ONLY */, int frame_first, int frames, int mem,
+                               const pwpp_terrain_params *terrain_params, const pwpp_reach_params *reach_params,
+                               const double *source_xy /* host: n_sources x {x, y}, metres */, int n_sources, int32_t *reach, int32_t *from /* may be NULL */,
+                               int8_t *cost /* the terrain's cost bytes, may be NULL: kept in the handle's buffer */);
+/* The raster's cell rule for one position in metres, as pwpp_reach_ground applies it to a source and pwpp_visibility_obstacles to an
+ * origin: cell (ix, iy) of the grid's origin, cell size and sides (flags are not read), for a caller of pwpp_reach_grid who has metres.
+ * PWPP_E_ARG, named: a null grid or result, a grid without cells or with an origin or cell size that is not finite and positive, a
+ * position that is not finite, a position outside the grid.  Needs no handle and touches no device. */
+PWPP_API int pwpp_grid_cell_of(const pwpp_ground_grid *g, double x, double y, int32_t *ix, int32_t *iy);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1165,6 +1253,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *   "terrain_path"        how the terrain analysis sums a window (pwpp_terrain_grid, pwpp_terrain_ground): "1": every lane walks its whole
  *                         window in LDS (the yardstick); "2": separable, the sums of every row over dx first, then 2r+1 rows combined with
  *                         their dy; "0" (default): per radius what tools/terrain_cost.py decided.  The same bytes for every value.
+ *   "reach_path"          how the cost-to-reach field is relaxed (pwpp_reach_grid, pwpp_reach_ground), a workgroup per frame either way:
+ *                         "1": sweeps over the frame's cells in global memory until a sweep changes nothing (the yardstick); "2": the
+ *                         frame's tiles of 32 x 32 cells, each relaxed in LDS with a halo of one cell, a tile revisited when a
+ *                         neighbour's border changed; "0" (default): what tools/reach_cost.py decided.  The same bytes for every value.
  *   "match_path"          how the scan match reads the map (pwpp_match_grid, pwpp_match_obstacles): "1": every map read comes from
  *                         global memory (the yardstick of tools/scan_match_cost.py); "2": the rectangle of the map that the
  *                         landings of a (frame, candidate) reach under the window is copied into LDS once per workgroup where it

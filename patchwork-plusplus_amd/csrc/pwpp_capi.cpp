@@ -28,6 +28,7 @@
 #include "pwpp_elevation.h"
 #include "pwpp_fusion.h"
 #include "pwpp_match.h"
+#include "pwpp_reach.h"
 #include "pwpp_terrain.h"
 #include "pwpp_visibility.h"
 
@@ -255,6 +256,7 @@ struct pwpp_handle {
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
+    int reach_path = 0;             // option "reach_path": 0 = what tools/reach_cost.py decided; 1 = sweeps over global memory, a workgroup per frame (yardstick); 2 = the frame's tiles relaxed in LDS, dirty tiles revisited
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
     std::vector<std::vector<uint32_t>> uploads;  // the tables the last call that uploaded any built for its kernels: the sources of their copies (Staging::add_upload)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
@@ -2132,6 +2134,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "terrain_path=%s: 0, 1 or 2 expected", value);
         h->terrain_path = v;
+    } else if (k == "reach_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "reach_path=%s: 0, 1 or 2 expected", value);
+        h->reach_path = v;
     } else if (k == "match_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
@@ -2447,7 +2453,7 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
 // non-ground lists.  An operator states its sections once (*_sections: the kernels' working words and the tables the call built for them
 // first -- upload sections, copied by Staging::begin() -- then what the call stages) and its launch once (*_launch: the launcher's call alone);
 // an entry point checks its arguments, declares the sections and runs one of four tails: run_on_image, run_on_obstacles, run_on_visibility
-// (further down: the obstacle tail under the visibility operator), run_on_ground (the elevation fusion and the terrain on the ground raster).
+// (further down: the obstacle tail under the visibility operator), run_on_ground (the elevation fusion, the terrain and the reach on the ground raster).
 
 // The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
 // From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
@@ -2684,6 +2690,21 @@ int visibility_origin_count(int n_origins, int frames) {
     return PWPP_OK;
 }
 
+// Positions in metres, one per frame or one for all (the visibility's origins, the reach's sources; `what` names one), as cells of
+// the checked grid by the raster's cell rule: `out`: n x {ix, iy}.
+int frame_cells_of(const pwpp_ground_grid *g, const double *xy, int n, const char *what, std::vector<int32_t> &out) {
+    out.assign(2 * (size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        const double x = xy[2 * i], y = xy[2 * i + 1];
+        int ox = 0, oy = 0;
+        if (!std::isfinite(x) || !std::isfinite(y)) return fail(PWPP_E_ARG, "%s %d, (%g, %g), is not finite", what, i, x, y);
+        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
+            return fail(PWPP_E_ARG, "%s %d, (%g, %g) m, lies outside the grid", what, i, x, y);
+        out[2 * i] = ox, out[2 * i + 1] = oy;
+    }
+    return PWPP_OK;
+}
+
 // What the entry points that rasterise first check of the band, the grid, min_count, max_range and the origins in metres, which
 // they turn into cells (`org`: n_origins x {ox, oy}).
 int visibility_origin_args(const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins, int max_range,
@@ -2693,16 +2714,13 @@ int visibility_origin_args(const pwpp_ground_grid *g, float h_min, float h_max, 
     if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
     if ((rc = visibility_origin_count(n_origins, frames))) return rc;
-    org.assign(2 * (size_t)n_origins, 0);
-    for (int i = 0; i < n_origins; ++i) {
-        const double x = origin_xy[2 * i], y = origin_xy[2 * i + 1];
-        int ox = 0, oy = 0;
-        if (!std::isfinite(x) || !std::isfinite(y)) return fail(PWPP_E_ARG, "origin %d, (%g, %g), is not finite", i, x, y);
-        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
-            return fail(PWPP_E_ARG, "origin %d, (%g, %g) m, lies outside the grid", i, x, y);
-        org[2 * i] = ox, org[2 * i + 1] = oy;
-    }
-    return PWPP_OK;
+    return frame_cells_of(g, origin_xy, n_origins, "origin", org);
+}
+
+// The section of the cells given one per frame (the visibility's origins, the reach's sources): n x {x, y} as an upload; one cell
+// travels as an argument of the launch and has no words.
+int frame_cells_section(Staging &st, const std::vector<int32_t> &xy) {
+    return xy.size() > 2 ? st.add_upload(std::vector<uint32_t>(xy.begin(), xy.end())) : st.add(0, nullptr, Staging::kKept);
 }
 
 // (the kernels' bit image and the origins first; `org`: the origin cells, n_origins x {ox, oy}, checked; `keep`: an image the
@@ -2714,7 +2732,7 @@ VisibilitySections visibility_sections(pwpp_handle *h, Staging &st, int nx, int 
                                        const std::vector<int32_t> &org, int32_t *first, int8_t *occupancy, bool keep = false) {
     VisibilitySections s;
     s.work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
-    s.org = org.size() > 2 ? st.add_upload(std::vector<uint32_t>(org.begin(), org.end())) : st.add(0, nullptr, Staging::kKept);  // (one origin: no words)
+    s.org = frame_cells_section(st, org);
     s.count = add_image(st, cells, count, from_raster), s.first = st.add(cells, first, keep && !first ? Staging::kKept : Staging::kOut);
     if (keep && !occupancy) s.occ = st.add((cells + 3) / 4, nullptr, Staging::kKept);
     else s.occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
@@ -3278,6 +3296,138 @@ int pwpp_terrain_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_fir
     const int s_height = add_image(st, cells, height, true);
     const TerrainSections s = terrain_sections(st, cells, s_height, step, slope, rough, count, cost);
     return run_on_ground(h, st, g, frame_first, frames, s_height, -1, [&] { return terrain_launch(h, st, s, rule, g->nx, g->ny, frames); });
+}
+
+// ---- cost to reach: the cheapest sum of steps from the frame's source to every cell of a cost image, and the neighbour it comes through ----
+namespace {
+static_assert(sizeof(pwpp_reach_params) == 24, "pwpp_reach_params is 24 bytes");
+static_assert(PWPP_REACH_NONE == (int32_t)PWPP_REACH_UNREACHED && PWPP_DIST_BEYOND == PWPP_REACH_DIST_BEYOND, "the kernels' values");
+constexpr const char *kReachWho = "the reach takes";
+
+// What both entry points check of the parameters and the range, in the header's order, after the image's own checks; fills the
+// rule.  Touches no handle.
+int reach_param_args(const pwpp_reach_params *p, int nx, int ny, bool with_dist2, PwppReachRule &rule) {
+    if (p->base < 1 || p->base > 255) return fail(PWPP_E_ARG, "base %d: 1 .. 255 expected", p->base);
+    if (p->lethal < 1 || p->lethal > 101) return fail(PWPP_E_ARG, "lethal %d: 1 .. 101 expected (101: no value is lethal)", p->lethal);
+    if (p->unknown < -1 || p->unknown > 100) return fail(PWPP_E_ARG, "unknown %d: -1 (impassable) .. 100 expected", p->unknown);
+    if (with_dist2 && p->clearance2 < 0) return fail(PWPP_E_ARG, "clearance2 %d: at least 0 expected", p->clearance2);
+    if (p->max_reach < 0) return fail(PWPP_E_ARG, "max_reach %d: 0 (unlimited) or more expected", p->max_reach);
+    if (p->pad_ != 0) return fail(PWPP_E_ARG, "pad_ %d of the reach parameters: 0 expected", p->pad_);
+    int64_t worst = 0;
+    if (!pwpp_reach_range_ok(p->base, nx, ny, worst))
+        return fail(PWPP_E_ARG, "14 * (base + 100) * (%d * %d - 1) = %lld with base %d exceeds 2^31 - 2: a reach would not fit 32 bits", nx, ny,
+                    (long long)worst, p->base);
+    rule = PwppReachRule{p->base, p->lethal, p->unknown, with_dist2 ? p->clearance2 : 0, p->max_reach, with_dist2 ? 1 : 0};
+    return PWPP_OK;
+}
+
+// ... and of the number of sources
+int reach_source_count(int n_sources, int frames) {
+    if (n_sources < 1 || (n_sources != 1 && n_sources != frames)) return fail(PWPP_E_ARG, "%d sources for %d frames: 1 or one per frame expected", n_sources, frames);
+    return PWPP_OK;
+}
+
+// (the working image, the defect word and the sources first; `src`: the source cells, n_sources x {sx, sy}, checked; `cost` is the
+// cost bytes' section: the caller's, or the terrain's.  In PWPP_MEM_HOST the defect word comes back with the images.)
+struct ReachSections {
+    int term, flag, src, cost, dist2, reach, from;
+};
+ReachSections reach_sections(Staging &st, int mem, int nx, int ny, int frames, size_t cells, int s_cost, const std::vector<int32_t> &src, const int32_t *dist2,
+                             int32_t *reach, int32_t *from, uint32_t *flag_host) {
+    ReachSections s;
+    s.term = st.add(pwpp_reach_work_words(nx, ny, frames), nullptr, Staging::kKept);
+    s.flag = mem == PWPP_MEM_HOST ? st.add(1, flag_host, Staging::kOut) : st.add(1, nullptr, Staging::kKept);
+    s.src = frame_cells_section(st, src);
+    s.cost = s_cost;
+    s.dist2 = st.add(dist2 ? cells : 0, dist2, Staging::kIn);
+    s.reach = st.add(cells, reach, Staging::kOut);
+    s.from = st.add(from ? cells : 0, from, Staging::kOut);
+    return s;
+}
+// (one source travels as an argument; one per frame lies in its section)
+int reach_launch(pwpp_handle *h, const Staging &st, const ReachSections &s, const PwppReachRule &rule, int nx, int ny, int frames, const std::vector<int32_t> &src) {
+    return pwpp_launch_reach(&rule, nx, ny, frames, st.dev<const int8_t>(s.cost), rule.use_dist2 ? st.dev<const int32_t>(s.dist2) : nullptr, src[0], src[1],
+                             src.size() > 2 ? st.dev<const int32_t>(s.src) : nullptr, st.dev<int32_t>(s.reach), st.dev<int32_t>(s.from),
+                             st.dev<uint16_t>(s.term), st.dev<uint32_t>(s.flag), h->reach_path, h->stream);
+}
+// (PWPP_MEM_HOST, after the images came back: a kernel that met a loop bound)
+int reach_defect(int rc, uint32_t flag_host) {
+    if (rc == PWPP_OK && flag_host != 0) return fail(PWPP_E_HIP, "internal error: a reach kernel met the bound of its sweeps (a defect, not an input)");
+    return rc;
+}
+}  // namespace
+
+int pwpp_reach_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost, const int32_t *dist2, const pwpp_reach_params *p,
+                    const int32_t *source, int n_sources, int32_t *reach, int32_t *from) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!cost || !p || !source || !reach)
+        return fail(PWPP_E_ARG, "null %s", !cost ? "cost image" : (!p ? "reach parameters" : (!source ? "source" : "reach image")));
+    size_t cells = 0;
+    int rc = image_args(nx, ny, frames, kReachWho, cells);
+    if (rc) return rc;
+    PwppReachRule rule;
+    if ((rc = reach_param_args(p, nx, ny, dist2 != nullptr, rule))) return rc;
+    if ((rc = reach_source_count(n_sources, frames))) return rc;
+    for (int i = 0; i < n_sources; ++i)
+        if (source[2 * i] < 0 || source[2 * i] >= nx || source[2 * i + 1] < 0 || source[2 * i + 1] >= ny)
+            return fail(PWPP_E_ARG, "source %d, cell (%d, %d), lies outside the %d x %d cells", i, source[2 * i], source[2 * i + 1], nx, ny);
+    if ((rc = range_args({{cost, cells, "cost"}, {dist2, cells * 4, "dist2"}, {reach, cells * 4, "reach"}, {from, cells * 4, "from"}}, {}, false))) return rc;
+    if ((rc = mem_args(mem, kReachWho))) return rc;
+    if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}, {reach, 3u, "reach image"}, {from, 3u, "from image"}}))) return rc;
+    const std::vector<int32_t> src(source, source + 2 * (size_t)n_sources);
+    uint32_t flag_host = 0;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_cost = st.add((cells + 3) / 4, cost, Staging::kIn, cells);
+    const ReachSections s = reach_sections(st, mem, nx, ny, frames, cells, s_cost, src, dist2, reach, from, &flag_host);
+    return reach_defect(run_on_image(h, st, [&] { return reach_launch(h, st, s, rule, nx, ny, frames, src); }), flag_host);
+}
+
+// pwpp_rasterize_ground into a section of the cluster buffer, pwpp_terrain_grid for its cost bytes alone (kept there too unless the caller asks for
+// them) and pwpp_reach_grid on those, one enqueued sequence.
+int pwpp_reach_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, const pwpp_terrain_params *tp, const pwpp_reach_params *p,
+                      const double *source_xy, int n_sources, int32_t *reach, int32_t *from, int8_t *cost) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !tp || !p || !source_xy || !reach)
+        return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!tp ? "terrain parameters" : (!p ? "reach parameters" : (!source_xy ? "source" : "reach image"))));
+    int rc = ground_first_args(g, frames, kReachWho);
+    if (rc) return rc;
+    PwppTerrainRule terrain_rule;
+    PwppReachRule rule;
+    size_t cells = (size_t)g->nx * (size_t)g->ny * (size_t)frames;  // (as in pwpp_terrain_ground: fits 64 bits; ground_grid_args names one beyond 2^31)
+    if ((rc = terrain_args(tp, g->cell, cells, nullptr, nullptr, nullptr, nullptr, nullptr, cost, terrain_rule))) return rc;
+    if ((rc = reach_param_args(p, g->nx, g->ny, false, rule))) return rc;
+    if ((rc = grid_geometry_args(g))) return rc;  // (the sources need the grid)
+    if ((rc = reach_source_count(n_sources, frames))) return rc;
+    std::vector<int32_t> src;
+    if ((rc = frame_cells_of(g, source_xy, n_sources, "source", src))) return rc;
+    if ((rc = range_args({{cost, cells, "cost"}, {reach, cells * 4, "reach"}, {from, cells * 4, "from"}}, {}, false))) return rc;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = alignment_args(mem, {{reach, 3u, "reach image"}, {from, 3u, "from image"}}))) return rc;
+    uint32_t flag_host = 0;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_height = add_image(st, cells, nullptr, true);
+    const int none = st.add(0, nullptr, Staging::kOut);  // (an output of the terrain analysis that nobody asks for: a null pointer)
+    const int s_cost = cost ? st.add((cells + 3) / 4, cost, Staging::kOut, cells) : st.add((cells + 3) / 4, nullptr, Staging::kKept);
+    const TerrainSections t{s_height, none, none, none, none, s_cost};
+    const ReachSections s = reach_sections(st, mem, g->nx, g->ny, frames, cells, s_cost, src, nullptr, reach, from, &flag_host);
+    return reach_defect(run_on_ground(h, st, g, frame_first, frames, s_height, -1,
+                                      [&] {
+                                          const int lrc = terrain_launch(h, st, t, terrain_rule, g->nx, g->ny, frames);
+                                          return lrc != 0 ? lrc : reach_launch(h, st, s, rule, g->nx, g->ny, frames, src);
+                                      }),
+                        flag_host);
+}
+
+// The raster's cell rule for one position, as the origins and sources in metres go through it (frame_cells_of): for a caller
+// who has a position in metres and a call that takes cells.  Reads the grid's origin, cell size and sides alone; no handle.
+int pwpp_grid_cell_of(const pwpp_ground_grid *g, double x, double y, int32_t *ix, int32_t *iy) {
+    if (!g || !ix || !iy) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : "cell");
+    if (const int rc = grid_geometry_args(g)) return rc;
+    const double xy[2] = {x, y};
+    std::vector<int32_t> cell;
+    if (const int rc = frame_cells_of(g, xy, 1, "position", cell)) return rc;
+    *ix = cell[0], *iy = cell[1];
+    return PWPP_OK;
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

@@ -526,6 +526,46 @@ public:
                                 t.count.data(), t.cost.data()));
         return terrain_sized(t);
     }
+    // ... and what it costs to get there from where the vehicle stands (pwpp_reach_ground, pwpp_reach_grid): per cell the cheapest sum of
+    // steps from the source's cell over the 8-connected passable cells of the terrain cost -- a step from a to b costs 5 (across an
+    // edge) or 7 (across a corner) times (base + cost(a)) + (base + cost(b)), corners are never cut -- PWPP_REACH_NONE where there is
+    // no path, and the index iy * nx + ix of the neighbour the cheapest path comes through (the source: its own; -1: none).
+    // reach / (10 base) * cell is a path length in metres on free ground.
+    struct ReachParams {
+        int base, lethal, unknown, clearance2, max_reach;  // 1 .. 255; 1 .. 101; -1 (impassable) .. 100; >= 0, unused here: no dist2; 0: unlimited
+        ReachParams() : base(1), lethal(100), unknown(-1), clearance2(0), max_reach(0) {}  // (a constructor: as TerrainParams)
+    };
+    struct Reach {
+        int nx = 0, ny = 0;
+        std::vector<int32_t> reach, from;  // ny x nx, row-major: row iy, column ix
+    };
+    // (on the terrain cost of the last frame's elevation image over the grid (x0, y0, cell, nx, ny); the source in metres)
+    Reach getReach(double x0, double y0, double cell, int nx, int ny, const TerrainParams &terrain_params = TerrainParams(),
+                   const ReachParams &reach_params = ReachParams(), double source_x = 0.0, double source_y = 0.0, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        const pwpp_terrain_params tp = {terrain_params.radius, terrain_params.min_known, terrain_params.step_max, terrain_params.slope_max, terrain_params.rough_max, 0};
+        const pwpp_reach_params rp = {reach_params.base, reach_params.lethal, reach_params.unknown, reach_params.clearance2, reach_params.max_reach, 0};
+        const double source[2] = {source_x, source_y};
+        Reach r = reach_images(nx, ny);
+        check(pwpp_reach_ground(h_, &g, 0, 1, PWPP_MEM_HOST, &tp, &rp, source, 1, r.reach.data(), r.from.data(), nullptr));
+        return reach_sized(r);
+    }
+    // (on the terrain cost of the mean of a fused elevation map; the source in metres in the map's frame)
+    Reach fusedReach(const FusedElevationMap &map, const TerrainParams &terrain_params = TerrainParams(), const ReachParams &reach_params = ReachParams(),
+                     double source_x = 0.0, double source_y = 0.0) {
+        const pwpp_terrain_params tp = {terrain_params.radius, terrain_params.min_known, terrain_params.step_max, terrain_params.slope_max, terrain_params.rough_max, 0};
+        const pwpp_reach_params rp = {reach_params.base, reach_params.lethal, reach_params.unknown, reach_params.clearance2, reach_params.max_reach, 0};
+        Reach r = reach_images(map.nx, map.ny);
+        const size_t cells = (size_t)r.nx * (size_t)r.ny;
+        if (map.mean.size() != cells || map.mean.empty()) throw std::invalid_argument("fusedReach: the map has no mean image of ny x nx cells");
+        const pwpp_ground_grid g = {map.x0, map.y0, map.cell, map.nx, map.ny, 0, 0};
+        int32_t source[2] = {0, 0};
+        check(pwpp_grid_cell_of(&g, source_x, source_y, &source[0], &source[1]));  // (the raster's cell rule; the library names a position it refuses)
+        std::vector<int8_t> cost(cells);
+        check(pwpp_terrain_grid(h_, map.nx, map.ny, 1, map.cell, PWPP_MEM_HOST, map.mean.data(), &tp, nullptr, nullptr, nullptr, nullptr, cost.data()));
+        check(pwpp_reach_grid(h_, map.nx, map.ny, 1, PWPP_MEM_HOST, cost.data(), nullptr, &rp, source, 1, r.reach.data(), r.from.data()));
+        return reach_sized(r);
+    }
     // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},
     // the prior first) and every shift of [-wx, wx] x [-wy, wy] map cells, the sum of log_odds under the occupied cells of the
     // frame's visibility bytes; the best by the contract's order, and `pose`, the winning candidate moved by the winning shift
@@ -632,6 +672,19 @@ private:
         const size_t cells = (size_t)t.nx * (size_t)t.ny;
         t.step.resize(cells), t.slope.resize(cells), t.rough.resize(cells), t.count.resize(cells), t.cost.resize(cells);
         return t;
+    }
+    // (the two images of a reach call, with room for one cell where the grid has none, as terrain_images)
+    static Reach reach_images(int nx, int ny) {
+        Reach r;
+        r.nx = nx > 0 ? nx : 0, r.ny = ny > 0 ? ny : 0;
+        const size_t cells = (size_t)r.nx * (size_t)r.ny, room = cells ? cells : 1;
+        r.reach.assign(room, PWPP_REACH_NONE), r.from.assign(room, -1);
+        return r;
+    }
+    static Reach &reach_sized(Reach &r) {
+        const size_t cells = (size_t)r.nx * (size_t)r.ny;
+        r.reach.resize(cells), r.from.resize(cells);
+        return r;
     }
 #ifdef PWPP_HAVE_EIGEN
     static Eigen::MatrixX3f to_eigen(const Cloud &c) {

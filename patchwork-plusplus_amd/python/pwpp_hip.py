@@ -105,6 +105,14 @@ class TerrainParams(ctypes.Structure):  # pwpp_terrain_params (24 bytes): the wi
                 ("rough_max", ctypes.c_float), ("pad_", ctypes.c_int32)]
 
 
+class ReachParams(ctypes.Structure):  # pwpp_reach_params (24 bytes): the cost of free ground, the lethal byte, the unknown cells' byte, the clearance, the limit
+    _fields_ = [("base", ctypes.c_int32), ("lethal", ctypes.c_int32), ("unknown", ctypes.c_int32), ("clearance2", ctypes.c_int32),
+                ("max_reach", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+REACH_NONE = 0x7FFFFFFF  # PWPP_REACH_NONE: no path from the source
+
+
 class MatchBest(ctypes.Structure):  # pwpp_match_best (24 bytes): the winning sum, its candidate (-1: skipped) and shift, the frame's occupied cells
     _fields_ = [("score", ctypes.c_int64), ("candidate", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("cells", ctypes.c_int32)]
 
@@ -235,6 +243,11 @@ def load():
             gp, tp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams)
             L.pwpp_terrain_grid.argtypes = [vp, ci, ci, ci, ctypes.c_double, ci, vp, tp, vp, vp, vp, vp, vp]
             L.pwpp_terrain_ground.argtypes = [vp, gp, ci, ci, ci, tp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pwpp_reach_grid"):  # (as above: an older build has no cost-to-reach field)
+            gp, tp, rp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams), ctypes.POINTER(ReachParams)
+            L.pwpp_reach_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, vp]
+            L.pwpp_reach_ground.argtypes = [vp, gp, ci, ci, ci, tp, rp, vp, ci, vp, vp, vp]
+            L.pwpp_grid_cell_of.argtypes = [gp, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -1214,6 +1227,58 @@ class Handle:
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_terrain_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, ctypes.byref(params), _dp(step_ptr),
                                                 _dp(slope_ptr), _dp(rough_ptr), _dp(count_ptr), _dp(cost_ptr), _dp(height_ptr)))
+
+    def reach_grid(self, cost, source, params, dist2=None, want_from=True):
+        """The cost-to-reach field of the (frames, ny, nx) or (ny, nx) int8 cost images (< 0: unknown, 0 .. 100, >= params.lethal:
+        impassable) under the ReachParams `params`: for every cell the cheapest sum of steps from the frame's source cell over the
+        8-connected passable cells.  source: (sx, sy) for every frame, or (frames, 2) cells; dist2: None or the int32 image of
+        distance_grid of cost's shape (passable then needs dist2 > params.clearance2).  Works before any estimate call.  Returns
+        (reach, from) of cost's shape: int32, REACH_NONE where no path exists, and the index iy * nx + ix of the neighbour the
+        cheapest path comes through (the source: its own; -1: none; None when not wanted).  The rules: include/pwpp.h."""
+        cst = np.ascontiguousarray(cost, np.int8)
+        c3 = cst.reshape((1,) + cst.shape) if cst.ndim == 2 else cst
+        if c3.ndim != 3:
+            raise ValueError("cost: a (frames, ny, nx) or (ny, nx) image expected")
+        d3 = None if dist2 is None else np.ascontiguousarray(dist2, np.int32)
+        if d3 is not None and d3.size != c3.size:
+            raise ValueError("dist2: an image of cost's shape expected")
+        src = np.ascontiguousarray(np.asarray(source, np.int32).reshape(-1, 2))
+        reach = np.empty(cst.shape, np.int32)
+        frm = np.empty(cst.shape, np.int32) if want_from else None
+        self._check(self._L.pwpp_reach_grid(self._h, c3.shape[2], c3.shape[1], c3.shape[0], MEM_HOST, _hp(c3), _hp(d3), ctypes.byref(params), _hp(src),
+                                            len(src), _hp(reach), _hp(frm)))
+        return reach, frm
+
+    def reach_grid_device(self, nx, ny, frames, cost_ptr, source, params, reach_ptr, from_ptr=0, dist2_ptr=0):
+        """reach_grid on device memory: addresses of the (frames, ny, nx) int8 cost images (any address) and of the int32 reach,
+        from and dist2 images (0: none; 4-byte aligned); source stays a host array, (sx, sy) or (frames, 2).  Enqueued on the
+        handle's stream; complete after synchronize()."""
+        src = np.ascontiguousarray(np.asarray(source, np.int32).reshape(-1, 2))
+        self._check(self._L.pwpp_reach_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(cost_ptr), _dp(dist2_ptr), ctypes.byref(params),
+                                            _vp(src) if src.size else None, len(src), _dp(reach_ptr), _dp(from_ptr)))
+
+    def reach_ground(self, x0, y0, cell, nx, ny, terrain_params, params, source_xy=(0.0, 0.0), frame_first=0, frames=None, ground_only=False,
+                     want_from=True, want_cost=False):
+        """rasterize_ground, the cost of terrain_grid and reach_grid in one call, for frames of the last estimate call.  source_xy:
+        the vehicle's position in metres in the model's frame, (x, y) for every frame or (frames, 2).  Returns (reach, from) as
+        reach_grid gives them for the (frames, ny, nx) cost images of terrain_ground; want_cost: then those int8 images too."""
+        g, frames, src = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, source_xy)
+        shape = self._grid_shape(g, frames)
+        reach = np.empty(shape, np.int32)
+        frm = np.empty(shape, np.int32) if want_from else None
+        cost = np.empty(shape, np.int8) if want_cost else None
+        self._check(self._L.pwpp_reach_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, ctypes.byref(terrain_params), ctypes.byref(params),
+                                              _hp(src), len(src), _hp(reach), _hp(frm), _hp(cost)))
+        return (reach, frm) + ((cost,) if want_cost else ())
+
+    def reach_ground_device(self, x0, y0, cell, nx, ny, terrain_params, params, source_xy, reach_ptr, from_ptr=0, cost_ptr=0, frame_first=0, frames=None,
+                            ground_only=False):
+        """reach_ground into device memory: addresses as in reach_grid_device, cost_ptr the (frames, ny, nx) int8 cost images of
+        the terrain analysis (0: kept in the handle's buffer); source_xy stays a host array.  Enqueued on the handle's stream;
+        complete after synchronize()."""
+        g, frames, src = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, source_xy)
+        self._check(self._L.pwpp_reach_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, ctypes.byref(terrain_params),
+                                              ctypes.byref(params), _vp(src) if src.size else None, len(src), _dp(reach_ptr), _dp(from_ptr), _dp(cost_ptr)))
 
     @staticmethod
     def _match_host(candidates, frames, map_of_frame):

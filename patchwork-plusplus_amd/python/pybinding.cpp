@@ -115,6 +115,12 @@ py::tuple terrain_tuple(const Terrain &t) {
                           terrain_image(t.count, t.nx, t.ny), terrain_image(t.cost, t.nx, t.ny));
 }
 
+// (reach, from) of a reach call as (ny, nx) arrays
+template <class Reach>
+py::tuple reach_tuple(const Reach &r) {
+    return py::make_tuple(terrain_image(r.reach, r.nx, r.ny), terrain_image(r.from, r.nx, r.ny));
+}
+
 PYBIND11_MODULE(pypatchworkpp, m) {
     m.doc() = "Python Patchwork++ (MI355X / HIP backend)";
     m.attr("__version__") = "0.0.1";
@@ -187,6 +193,14 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def_readwrite("step_max", &PatchWorkpp::TerrainParams::step_max)
         .def_readwrite("slope_max", &PatchWorkpp::TerrainParams::slope_max)
         .def_readwrite("rough_max", &PatchWorkpp::TerrainParams::rough_max);
+
+    py::class_<PatchWorkpp::ReachParams>(m, "ReachParams")  // the step costs and the limits of getReach and fusedReach
+        .def(py::init<>())
+        .def_readwrite("base", &PatchWorkpp::ReachParams::base)
+        .def_readwrite("lethal", &PatchWorkpp::ReachParams::lethal)
+        .def_readwrite("unknown", &PatchWorkpp::ReachParams::unknown)
+        .def_readwrite("clearance2", &PatchWorkpp::ReachParams::clearance2)
+        .def_readwrite("max_reach", &PatchWorkpp::ReachParams::max_reach);
 
     py::class_<PatchWorkpp>(m, "patchworkpp")
         .def(py::init<Params>())
@@ -292,6 +306,20 @@ PYBIND11_MODULE(pypatchworkpp, m) {
                  return terrain_tuple(s.fusedTerrain(map, params));
              },
              py::arg("map"), py::arg("params") = PatchWorkpp::TerrainParams())
+        .def("getReach",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, const PatchWorkpp::TerrainParams &terrain_params,
+                const PatchWorkpp::ReachParams &reach_params, double source_x, double source_y, bool ground_only) {
+                 return reach_tuple(s.getReach(x0, y0, cell, nx, ny, terrain_params, reach_params, source_x, source_y, ground_only));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("terrain_params") = PatchWorkpp::TerrainParams(),
+             py::arg("reach_params") = PatchWorkpp::ReachParams(), py::arg("source_x") = 0.0, py::arg("source_y") = 0.0, py::arg("ground_only") = false)
+        .def("fusedReach",
+             [](PatchWorkpp &s, const PatchWorkpp::FusedElevationMap &map, const PatchWorkpp::TerrainParams &terrain_params,
+                const PatchWorkpp::ReachParams &reach_params, double source_x, double source_y) {
+                 return reach_tuple(s.fusedReach(map, terrain_params, reach_params, source_x, source_y));
+             },
+             py::arg("map"), py::arg("terrain_params") = PatchWorkpp::TerrainParams(), py::arg("reach_params") = PatchWorkpp::ReachParams(),
+             py::arg("source_x") = 0.0, py::arg("source_y") = 0.0)
         .def("matchObstacleMap",
              [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, const std::vector<std::array<double, 6>> &candidates, int wx, int wy, double x0,
                 double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y) {
