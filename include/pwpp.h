@@ -1111,6 +1111,98 @@ PWPP_API int pwpp_reach_ground(pwpp_handle *h, const pwpp_ground_grid *g /* flag
  * position that is not finite, a position outside the grid.  Needs no handle and touches no device. */
 PWPP_API int pwpp_grid_cell_of(const pwpp_ground_grid *g, double x, double y, int32_t *ix, int32_t *iy);
 
+/* ---- cluster tracks: which cluster of this frame is which cluster of the frame before (pwpp_associate_grid, pwpp_track_obstacles) ----
+ * The labels of pwpp_label_grid are per frame: row 3 of one frame and row 3 of the next have nothing to do with each other.  These
+ * calls relate the two label images of one stream: how many cells every pair of rows shares, each row's best partner on both
+ * sides, and optionally an id that a cluster keeps from frame to frame.  Everything is an integer count or an argmax under a
+ * total order: a function of the inputs alone, the same bytes for every mem, alignment and schedule of the kernels.  Each frame
+ * pair is on its own.
+ *   inputs    per frame pair f: prev[f], an int32 label image on the grid gp; curr[f], one on the grid gc; a pose {a, b, tx, c, d, ty}
+ *             that says where a position of the previous frame lies in the current frame -- exactly the meaning of the fusion's
+ *             map-from-frame pose (pwpp_fuse_grid), with the current grid in the role of the map and the previous image in the role
+ *             of the frame.  n_poses is 1 (for every frame) or `frames`; poses are host memory whatever `mem`, copied at the call.
+ *             gc and gp are pwpp_ground_grid structures (origin, cell, sides) whose flags must be 0.  The images are as
+ *             pwpp_label_grid writes them or edited by the caller.
+ *   rows      A label l names a row iff 0 <= l < max_rows.  Every other value counts as unlabelled, on both sides, as
+ *             pwpp_box_obstacles skips it.
+ *   previous cell  of a current cell (jx, jy): its centre by the elevation fusion's rule, x = gc.x0 + ((double)jx + 0.5) * gc.cell,
+ *             carried into gp by the fusion's sample rule (the transpose as the inverse, in double, every operation rounded on its own,
+ *             the cell rule of the obstacle raster; the product with the exact reciprocal where the cell size is a power of two gives the same
+ *             bits).  Where that position lies outside the previous image, is a NaN, or the pose is not finite, the cell has no
+ *             previous cell and casts no vote, whatever the gate.
+ *   vote      A current cell c with row b and previous cell p = (px, py) votes for one previous row: the row of the labelled
+ *             previous cell d = (px + ex, py + ey) with |ex|, |ey| <= gate inside the previous image; among such cells the
+ *             smallest ex^2 + ey^2 wins, then the smallest index (py + ey) * nxp + (px + ex).  No such cell: no vote.  gate is 0 .. 4;
+ *             with gate 0 this is plain overlap.
+ *   overlap   n(a, b) is the number of current cells of row b that vote for a.  A pair (a, b) exists iff n(a, b) > 0.
+ *   links     curr_links[f][b]: cells = all current cells labelled b; links = the number of distinct a with n(a, b) > 0; other =
+ *             the a with the largest n(a, b), the smallest a on a tie, -1 when links == 0; overlap = n(other, b), or 0.
+ *             prev_links[f][a]: cells = all previous cells labelled a, whatever the pose; links = the number of distinct b with
+ *             n(a, b) > 0; other = the b with the largest n(a, b), the smallest b on a tie, -1 without one; overlap likewise.
+ *             links > 1 is a merge on the current side and a split on the previous side.  Both tables have max_rows rows per frame.
+ *   pairs     n_pairs[f] (may be NULL) is the frame's number of distinct pairs when that is at most max_pairs.  Otherwise it is
+ *             max_pairs + 1, and every row of both tables of that frame has other = -2, overlap = 0, links = 0, with cells still
+ *             exact.  Overflow is a function of the inputs alone, never of the schedule: the pairs are counted in a table of
+ *             2 * max_pairs slots per frame, and a table with at least 2 * max_pairs slots cannot fill before the count of
+ *             distinct insertions passes max_pairs.
+ *   ids       Optional: computed iff id_prev, next_id, id_curr and next_id_out are all non-null; some of them only: PWPP_E_ARG.
+ *             id_prev[f][a] and id_curr[f][b] have max_rows entries per frame, next_id[f] and next_id_out[f] one.  A current row
+ *             exists iff cells > 0.  An existing row b continues a iff curr_links[b].other == a with a >= 0, prev_links[a].other
+ *             == b, overlap >= min_overlap and id_prev[f][a] >= 0; then id_curr[f][b] = id_prev[f][a].  Every other existing row is
+ *             fresh: its id is (next_id[f] + k) & 0x7fffffff, k the number of fresh rows below b, in unsigned 32-bit arithmetic.
+ *             Rows that do not exist get -1.  next_id_out[f] = (next_id[f] + the frame's fresh rows) & 0x7fffffff.  A mutual best
+ *             is unique, so the ids of a frame stay distinct if those of id_prev were and lie below next_id (until the counter
+ *             wraps).  An overflowed frame makes every existing row fresh, by the same rule.  min_overlap >= 1 is read with or without ids.
+ *   track_obstacles  for frames of the LAST estimate call: enqueues pwpp_label_obstacles(g, h_min, h_max, min_count, connectivity,
+ *             frame_first, frames, ...) and the association of that label image against the caller's prev_label on the same grid
+ *             g (gc = gp = g with flags 0), max_rows = max_clusters, as one sequence.  label, count, top, clusters, n_clusters and
+ *             point_cluster are exactly what pwpp_label_obstacles gives; the links and ids exactly what pwpp_associate_grid gives
+ *             for those images.  Before any estimate call: PWPP_E_STATE.
+ *   state     The handle keeps nothing between calls: the previous label image, the ids and next_id are the caller's, as the maps
+ *             of the fusions are.  Feed label, id_curr and next_id_out of one step back as prev, id_prev and next_id of the next.
+ *   mem       PWPP_MEM_HOST: every array but the poses is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory, every array 4-byte aligned, enqueued on the handle's stream, complete after
+ *             pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order.  pwpp_associate_grid: a null handle, current grid,
+ *             previous grid, current image, previous image, pose, curr_links, prev_links; for gc and then for gp: frames or a side
+ *             < 1, a side > 32768, nx * ny * frames beyond 2^31; the flags of gc, then of gp; origin and cell size of gc, then of gp;
+ *             gate; min_overlap; max_rows < 1, then frames * max_rows > 2^24; max_pairs < 1, then frames * max_pairs > 2^24; the
+ *             count of poses; the partial id set; two of the caller's arrays overlapping; mem; in PWPP_MEM_DEVICE an array below its
+ *             alignment.  pwpp_track_obstacles: a null handle, grid, label image, previous label image, pose, curr_links,
+ *             prev_links; then everything pwpp_label_obstacles rejects, in its order -- PWPP_E_STATE before any estimate call among
+ *             it; then a side > 32768, grid flags other than 0, and the above from the gate on.
+ *   buffers   Working memory -- the pair tables (12 bytes a slot), two 64-bit words per row, the uploaded poses -- and in
+ *             PWPP_MEM_HOST the staged arrays lie in the cluster buffer; counted by pwpp_get_workspace_bytes, freed by
+ *             pwpp_trim_workspace.  pwpp_associate_grid needs a handle for its stream and this buffer only, like pwpp_label_grid.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of any other call changes.
+ * Not built: motion models and filtering, an assignment beyond the mutual best, track ages and deletion, velocities as an output
+ * (INTEGRATION.md says how they follow from pwpp_box_obstacles), association across more than two frames, a list of the pairs. */
+#define PWPP_HAS_CLUSTER_TRACKS 1
+typedef struct pwpp_cluster_link {   /* 16 bytes */
+    int32_t other;       /* the best partner row on the other side; -1: none; -2: the frame has more than max_pairs pairs */
+    int32_t overlap;     /* n(other, this row), or 0 */
+    int32_t cells;       /* all cells of this side's image labelled with this row */
+    int32_t links;       /* the number of partner rows with n > 0 */
+} pwpp_cluster_link;
+
+/* any label images: needs a handle (stream, buffer), no estimate call -- like pwpp_label_grid */
+PWPP_API int pwpp_associate_grid(pwpp_handle *h, const pwpp_ground_grid *gc, const pwpp_ground_grid *gp, int frames, int mem,
+                                 const int32_t *curr /* [frames][gc.ny][gc.nx] */, const int32_t *prev /* [frames][gp.ny][gp.nx] */,
+                                 const double *pose /* host: n_poses x {a, b, tx, c, d, ty} */, int n_poses /* 1 or frames */,
+                                 int gate /* 0 .. 4 */, int min_overlap /* >= 1 */, int max_rows, int max_pairs,
+                                 pwpp_cluster_link *curr_links, pwpp_cluster_link *prev_links /* [frames][max_rows] each */,
+                                 int32_t *n_pairs /* [frames], may be NULL */,
+                                 const int32_t *id_prev /* [frames][max_rows] */, const int32_t *next_id /* [frames] */,
+                                 int32_t *id_curr /* [frames][max_rows] */, int32_t *next_id_out /* [frames]; all four or none */);
+/* label_obstacles + the association against the caller's previous label image for frames of the LAST estimate call, one enqueued
+ * sequence -- like pwpp_reach_ground.  The arguments up to point_cluster are pwpp_label_obstacles'. */
+PWPP_API int pwpp_track_obstacles(pwpp_handle *h, const pwpp_ground_grid *g /* flags: 0 */, float h_min, float h_max, int min_count, int connectivity,
+                                  int frame_first, int frames, int mem, int32_t *label, int32_t *count, float *top,
+                                  pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters, int32_t *point_cluster,
+                                  const int32_t *prev_label /* [frames][ny][nx] */, const double *pose, int n_poses, int gate, int min_overlap,
+                                  int max_pairs, pwpp_cluster_link *curr_links, pwpp_cluster_link *prev_links /* [frames][max_clusters] each */,
+                                  int32_t *n_pairs, const int32_t *id_prev, const int32_t *next_id, int32_t *id_curr, int32_t *next_id_out);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU

@@ -30,6 +30,7 @@
 #include "pwpp_match.h"
 #include "pwpp_reach.h"
 #include "pwpp_terrain.h"
+#include "pwpp_tracks.h"
 #include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
@@ -1230,7 +1231,7 @@ class Staging {
     }
 
   private:
-    static constexpr int kMaxSections = 12;
+    static constexpr int kMaxSections = 20;  // (pwpp_track_obstacles declares 17: the labelling's and the association's)
     struct Section {
         size_t at, words, bytes;
         const void *user;  // (kUpload: the words, in up_ and after begin() in the handle)
@@ -3428,6 +3429,157 @@ int pwpp_grid_cell_of(const pwpp_ground_grid *g, double x, double y, int32_t *ix
     if (const int rc = frame_cells_of(g, xy, 1, "position", cell)) return rc;
     *ix = cell[0], *iy = cell[1];
     return PWPP_OK;
+}
+
+// ---- cluster tracks: the rows of a current label image against those of the previous one, and ids that persist ------------------------
+namespace {
+static_assert(sizeof(pwpp_cluster_link) == 16 && sizeof(PwppClusterLink) == 16 && alignof(pwpp_cluster_link) == 4, "pwpp_cluster_link is 16 bytes of 4-byte fields");
+static_assert(offsetof(pwpp_cluster_link, other) == offsetof(PwppClusterLink, other) && offsetof(pwpp_cluster_link, overlap) == offsetof(PwppClusterLink, overlap) &&
+                  offsetof(pwpp_cluster_link, cells) == offsetof(PwppClusterLink, cells) && offsetof(pwpp_cluster_link, links) == offsetof(PwppClusterLink, links),
+              "the kernels' row of a link table");
+constexpr const char *kTracksWho = "the association takes";
+
+// The caller's arrays of an association besides the two images: what both entry points pass on.
+struct TrackArrays {
+    const double *pose;
+    int n_poses;
+    pwpp_cluster_link *curr_links, *prev_links;
+    int32_t *n_pairs;
+    const int32_t *id_prev, *next_id;
+    int32_t *id_curr, *next_id_out;
+};
+
+// What both entry points check from the gate on, in the header's order, after the images' and grids' own checks (frames >= 1): the
+// parameters, the count of poses, the id set, the overlaps among the caller's arrays (`curr` is an output of pwpp_track_obstacles).
+// Fills the rule.  Touches no handle.
+int tracks_args(int frames, size_t cells_c, size_t cells_p, const int32_t *curr, const int32_t *prev, const TrackArrays &t, int gate, int min_overlap, int max_rows,
+                int max_pairs, PwppTracksRule &rule) {
+    if (gate < 0 || gate > PWPP_TRACKS_MAX_GATE) return fail(PWPP_E_ARG, "gate %d: 0 .. 4 expected", gate);
+    if (min_overlap < 1) return fail(PWPP_E_ARG, "min_overlap %d: at least 1 expected", min_overlap);
+    if (max_rows < 1) return fail(PWPP_E_ARG, "max_rows %d: at least 1 expected", max_rows);
+    if ((int64_t)frames * max_rows > PWPP_TRACKS_MAX_TOTAL) return fail(PWPP_E_ARG, "%d frames x max_rows %d exceed 2^24", frames, max_rows);
+    if (max_pairs < 1) return fail(PWPP_E_ARG, "max_pairs %d: at least 1 expected", max_pairs);
+    if ((int64_t)frames * max_pairs > PWPP_TRACKS_MAX_TOTAL) return fail(PWPP_E_ARG, "%d frames x max_pairs %d exceed 2^24", frames, max_pairs);
+    if (t.n_poses < 1 || (t.n_poses != 1 && t.n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", t.n_poses, frames);
+    const int given = (t.id_prev != nullptr) + (t.next_id != nullptr) + (t.id_curr != nullptr) + (t.next_id_out != nullptr);
+    if (given != 0 && given != 4)
+        return fail(PWPP_E_ARG, "null %s with other id arrays given: id_prev, next_id, id_curr and next_id_out all or none expected",
+                    !t.id_prev ? "id_prev" : (!t.next_id ? "next_id" : (!t.id_curr ? "id_curr" : "next_id_out")));
+    const size_t rows = (size_t)frames * (size_t)max_rows;
+    if (const int rc = range_args({{curr, cells_c * 4, "curr"}, {prev, cells_p * 4, "prev"}, {t.curr_links, rows * 16, "curr_links"}, {t.prev_links, rows * 16, "prev_links"},
+                                   {t.n_pairs, (size_t)frames * 4, "n_pairs"}, {t.id_prev, rows * 4, "id_prev"}, {t.next_id, (size_t)frames * 4, "next_id"},
+                                   {t.id_curr, rows * 4, "id_curr"}, {t.next_id_out, (size_t)frames * 4, "next_id_out"}},
+                                  {}, false))
+        return rc;
+    rule = PwppTracksRule{gate, min_overlap, max_rows, max_pairs, pwpp_tracks_slots(max_pairs), given == 4 ? 1 : 0};
+    return PWPP_OK;
+}
+
+// (after mem: every array of the association 4-byte aligned in PWPP_MEM_DEVICE)
+int tracks_alignment_args(int mem, const int32_t *curr, const int32_t *prev, const TrackArrays &t) {
+    return alignment_args(mem, {{curr, 3u, "curr image"}, {prev, 3u, "prev image"}, {t.curr_links, 3u, "curr_links"}, {t.prev_links, 3u, "prev_links"},
+                                {t.n_pairs, 3u, "n_pairs"}, {t.id_prev, 3u, "id_prev"}, {t.next_id, 3u, "next_id"}, {t.id_curr, 3u, "id_curr"},
+                                {t.next_id_out, 3u, "next_id_out"}});
+}
+
+// the geometry of the vote: the current grid in the role of the fusion's map, the previous one in the role of its frame images
+PwppFusionGeometry tracks_geometry(const pwpp_ground_grid *gc, const pwpp_ground_grid *gp) {
+    PwppFusionGeometry G{gc->x0, gc->y0, gc->cell, gp->x0, gp->y0, gp->cell, gc->nx, gc->ny, gp->nx, gp->ny, 0.0};
+    pwpp_fuse_reciprocal(gp->cell, G.inv_cell);
+    return G;
+}
+
+// (the kernels' working words and the uploaded poses first; `s_curr` is the current image's section: the caller's, or the labelling's)
+struct TrackSections {
+    int work, pose, curr, prev, curr_links, prev_links, n_pairs, id_prev, next_id, id_curr, next_id_out;
+};
+TrackSections track_sections(Staging &st, int frames, size_t cells_p, int s_curr, const int32_t *prev, const TrackArrays &t, const PwppTracksRule &rule) {
+    TrackSections s;
+    const size_t rows = (size_t)frames * (size_t)rule.max_rows, ids = rule.with_ids ? rows : 0, nexts = rule.with_ids ? (size_t)frames : 0;
+    s.work = st.add(pwpp_tracks_work_words(frames, rule.max_rows, rule.max_pairs), nullptr, Staging::kKept);
+    std::vector<uint32_t> words((size_t)t.n_poses * 12);
+    std::memcpy(words.data(), t.pose, (size_t)t.n_poses * 6 * sizeof(double));
+    s.pose = st.add_upload(std::move(words));
+    s.curr = s_curr;
+    s.prev = st.add(cells_p, prev, Staging::kIn);
+    s.curr_links = st.add(rows * 4, t.curr_links, Staging::kOut), s.prev_links = st.add(rows * 4, t.prev_links, Staging::kOut);
+    s.n_pairs = st.add(t.n_pairs ? (size_t)frames : 0, t.n_pairs, Staging::kOut);
+    s.id_prev = st.add(ids, t.id_prev, Staging::kIn), s.next_id = st.add(nexts, t.next_id, Staging::kIn);
+    s.id_curr = st.add(ids, t.id_curr, Staging::kOut), s.next_id_out = st.add(nexts, t.next_id_out, Staging::kOut);
+    return s;
+}
+int track_launch(pwpp_handle *h, const Staging &st, const TrackSections &s, const PwppFusionGeometry &G, const PwppTracksRule &rule, int frames, int n_poses,
+                 bool with_n_pairs) {
+    return pwpp_launch_tracks(&G, &rule, frames, st.dev<const int32_t>(s.curr), st.dev<const int32_t>(s.prev), st.dev<const double>(s.pose), n_poses,
+                              st.dev<void>(s.curr_links), st.dev<void>(s.prev_links), with_n_pairs ? st.dev<int32_t>(s.n_pairs) : nullptr,
+                              rule.with_ids ? st.dev<const int32_t>(s.id_prev) : nullptr, rule.with_ids ? st.dev<const int32_t>(s.next_id) : nullptr,
+                              rule.with_ids ? st.dev<int32_t>(s.id_curr) : nullptr, rule.with_ids ? st.dev<int32_t>(s.next_id_out) : nullptr,
+                              st.dev<uint32_t>(s.work), h->stream);
+}
+}  // namespace
+
+int pwpp_associate_grid(pwpp_handle *h, const pwpp_ground_grid *gc, const pwpp_ground_grid *gp, int frames, int mem, const int32_t *curr, const int32_t *prev,
+                        const double *pose, int n_poses, int gate, int min_overlap, int max_rows, int max_pairs, pwpp_cluster_link *curr_links,
+                        pwpp_cluster_link *prev_links, int32_t *n_pairs, const int32_t *id_prev, const int32_t *next_id, int32_t *id_curr, int32_t *next_id_out) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!gc || !gp || !curr || !prev || !pose || !curr_links || !prev_links)
+        return fail(PWPP_E_ARG, "null %s",
+                    !gc ? "current grid" : (!gp ? "previous grid" : (!curr ? "current image" : (!prev ? "previous image" : (!pose ? "pose" : (!curr_links ? "curr_links" : "prev_links"))))));
+    size_t cells_c = 0, cells_p = 0;
+    int rc = image_args(gc->nx, gc->ny, frames, kTracksWho, cells_c);
+    if (rc || (rc = image_args(gp->nx, gp->ny, frames, kTracksWho, cells_p))) return rc;
+    if (gc->flags != 0 || gp->flags != 0)
+        return fail(PWPP_E_ARG, "grid flags %d of the %s grid: the association takes 0", gc->flags != 0 ? gc->flags : gp->flags, gc->flags != 0 ? "current" : "previous");
+    if ((rc = grid_geometry_args(gc)) || (rc = grid_geometry_args(gp))) return rc;
+    const TrackArrays t{pose, n_poses, curr_links, prev_links, n_pairs, id_prev, next_id, id_curr, next_id_out};
+    PwppTracksRule rule;
+    if ((rc = tracks_args(frames, cells_c, cells_p, curr, prev, t, gate, min_overlap, max_rows, max_pairs, rule))) return rc;
+    if ((rc = mem_args(mem, kTracksWho))) return rc;
+    if ((rc = tracks_alignment_args(mem, curr, prev, t))) return rc;
+    const PwppFusionGeometry G = tracks_geometry(gc, gp);
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_curr = st.add(cells_c, curr, Staging::kIn);
+    const TrackSections s = track_sections(st, frames, cells_p, s_curr, prev, t, rule);
+    return run_on_image(h, st, [&] { return track_launch(h, st, s, G, rule, frames, n_poses, n_pairs != nullptr); });
+}
+
+// pwpp_label_obstacles as it stands, its label image kept where it lies (the caller's, or the cluster buffer's in PWPP_MEM_HOST), and
+// pwpp_associate_grid of it against the caller's previous image on the same grid, one enqueued sequence.
+int pwpp_track_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int connectivity, int frame_first, int frames, int mem,
+                         int32_t *label, int32_t *count, float *top, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters, int32_t *point_cluster,
+                         const int32_t *prev_label, const double *pose, int n_poses, int gate, int min_overlap, int max_pairs, pwpp_cluster_link *curr_links,
+                         pwpp_cluster_link *prev_links, int32_t *n_pairs, const int32_t *id_prev, const int32_t *next_id, int32_t *id_curr, int32_t *next_id_out) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label || !prev_label || !pose || !curr_links || !prev_links)
+        return fail(PWPP_E_ARG, "null %s",
+                    !g ? "grid" : (!label ? "label image" : (!prev_label ? "previous label image" : (!pose ? "pose" : (!curr_links ? "curr_links" : "prev_links")))));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
+    if ((rc = side_args(g->nx, g->ny, kTracksWho))) return rc;
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d of the current grid: the association takes 0", g->flags);
+    const TrackArrays t{pose, n_poses, curr_links, prev_links, n_pairs, id_prev, next_id, id_curr, next_id_out};
+    PwppTracksRule rule;
+    if ((rc = tracks_args(frames, cells, cells, label, prev_label, t, gate, min_overlap, max_clusters, max_pairs, rule))) return rc;
+    if ((rc = tracks_alignment_args(mem, label, prev_label, t))) return rc;
+    const PwppFusionGeometry G = tracks_geometry(g, g);
+    const int64_t base_first = h->h_base.p[frame_first];
+    const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, count, top, label, clusters, n_clusters, max_clusters);
+    const int s_pc = st.add(points, point_cluster, Staging::kOut);
+    const TrackSections ts = track_sections(st, frames, cells, s.label, prev_label, t, rule);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
+        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, max_clusters);
+        if (lrc == 0 && points != 0) {
+            lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (as pwpp_label_obstacles)
+            if (lrc == 0) lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
+        }
+        return lrc != 0 ? lrc : track_launch(h, st, ts, G, rule, frames, n_poses, n_pairs != nullptr);
+    });
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

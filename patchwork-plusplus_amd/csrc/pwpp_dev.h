@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_tracks.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -348,6 +348,11 @@ int pwpp_launch_terrain(const struct PwppTerrainRule *R, int nx, int ny, int fra
 size_t pwpp_reach_work_words(int nx, int ny, int frames);
 int pwpp_launch_reach(const struct PwppReachRule *R, int nx, int ny, int frames, const int8_t *cost, const int32_t *dist2, int sx, int sy,
                       const int32_t *sources, int32_t *reach, int32_t *from, uint16_t *term, uint32_t *flag, int path, hipStream_t stream);
+// pwpp_tracks.hip
+size_t pwpp_tracks_work_words(int frames, int max_rows, int max_pairs);
+int pwpp_launch_tracks(const struct PwppFusionGeometry *G, const struct PwppTracksRule *R, int frames, const int32_t *curr, const int32_t *prev, const double *poses,
+                       int n_poses, void *curr_links, void *prev_links, int32_t *n_pairs, const int32_t *id_prev, const int32_t *next_id, int32_t *id_curr,
+                       int32_t *next_id_out, uint32_t *work, hipStream_t stream);
 // pwpp_match.hip
 size_t pwpp_match_work_words(int nx, int ny, int frames, int n_candidates, int wx, int wy);
 int pwpp_launch_match_grid(const struct PwppMatchGeometry *G, int frames, const int8_t *occupancy, const double *candidates, int n_sets, int n_candidates,

@@ -614,6 +614,50 @@ public:
         b.clusters = std::move(c.clusters);
         return b;
     }
+    // ... and which cluster is which cluster of the call before (pwpp_track_obstacles): the labelling as getObstacleClusters gives it,
+    // associated with the label image this object kept from its previous call on a grid of the same sides, under the pose {a, b, tx,
+    // c, d, ty} that says where a position of the previous frame lies in this one (the identity: null).  ids[r] is the persistent
+    // id of cluster r: a cluster that is the mutual best partner of one of the previous call's, sharing at least min_overlap cells,
+    // keeps that one's id, every other one gets the next unused id; curr_links[r] and prev_links[r] are the rows of include/pwpp.h
+    // (links > 1: a merge, on the previous side a split).  At most max_clusters clusters are tracked; the cells of further ones
+    // count as unlabelled.  The object keeps the label image, the ids and the next id between calls -- the library's handle keeps
+    // nothing -- until resetObstacleTracks(), or a call with other sides or another max_clusters, which starts afresh.
+    struct ObstacleTracks {
+        int nx = 0, ny = 0;
+        std::vector<int32_t> label;                   // ny x nx, row-major: row iy, column ix
+        std::vector<pwpp_obstacle_cluster> clusters;  // min(count, max_clusters) rows
+        std::vector<pwpp_cluster_link> curr_links;    // one per row of clusters
+        std::vector<pwpp_cluster_link> prev_links;    // max_clusters rows: the previous call's clusters
+        std::vector<int32_t> ids;                     // one per row of clusters
+        int count = 0;                                // the true number of clusters
+        int pairs = 0;                                // the number of (previous, current) pairs sharing a cell; max_pairs + 1: too many, no links
+    };
+    ObstacleTracks trackObstacleClusters(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, const double *pose = nullptr,
+                                         int min_count = 1, int connectivity = 8, int max_clusters = 256, int gate = 1, int min_overlap = 1) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, 0, 0};
+        const double identity[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+        ObstacleTracks t;
+        t.nx = nx > 0 ? nx : 0, t.ny = ny > 0 ? ny : 0;
+        const size_t cells = (size_t)t.nx * (size_t)t.ny, rows = (size_t)(max_clusters > 0 ? max_clusters : 0);
+        if (track_label_.size() != cells || track_ids_.size() != rows || track_nx_ != t.nx) resetObstacleTracks();
+        if (track_label_.empty()) track_label_.assign(cells ? cells : 1, -1), track_ids_.assign(rows ? rows : 1, -1), track_nx_ = t.nx;
+        t.label.assign(cells ? cells : 1, -1), t.clusters.resize(rows ? rows : 1), t.curr_links.resize(rows ? rows : 1), t.prev_links.resize(rows ? rows : 1);
+        t.ids.assign(rows ? rows : 1, -1);
+        int32_t n = 0, pairs = 0, next = track_next_id_;
+        const int max_pairs = max_clusters > 0 && max_clusters <= (1 << 22) ? 4 * max_clusters : 1 << 24;
+        check(pwpp_track_obstacles(h_, &g, h_min, h_max, min_count, connectivity, 0, 1, PWPP_MEM_HOST, t.label.data(), nullptr, nullptr, t.clusters.data(), &n,
+                                   max_clusters, nullptr, track_label_.data(), pose ? pose : identity, 1, gate, min_overlap, max_pairs, t.curr_links.data(),
+                                   t.prev_links.data(), &pairs, track_ids_.data(), &track_next_id_, t.ids.data(), &next));
+        track_label_ = t.label, track_ids_ = t.ids, track_next_id_ = next;
+        t.count = n, t.pairs = pairs;
+        const size_t kept = (size_t)(n < max_clusters ? n : max_clusters);
+        t.label.resize(cells), t.clusters.resize(kept), t.curr_links.resize(kept), t.ids.resize(kept), t.prev_links.resize(rows);
+        return t;
+    }
+    void resetObstacleTracks() {
+        track_label_.clear(), track_ids_.clear();
+        track_next_id_ = 0, track_nx_ = 0;
+    }
 #ifdef PWPP_HAVE_EIGEN
     std::vector<pwpp_ground_sample> queryGround(const Eigen::MatrixX3f &positions) {
         std::vector<float> xyz((size_t)positions.rows() * 3);
@@ -659,6 +703,9 @@ public:
 private:
     patchwork::Params params_;
     pwpp_handle *h_;
+    std::vector<int32_t> track_label_, track_ids_;  // trackObstacleClusters: the previous call's label image and ids
+    int32_t track_next_id_ = 0;
+    int track_nx_ = 0;
 
     // (the five images of a terrain call, with room for one cell where the grid has none: the library names the bad argument)
     static Terrain terrain_images(int nx, int ny) {

@@ -113,6 +113,14 @@ class ReachParams(ctypes.Structure):  # pwpp_reach_params (24 bytes): the cost o
 REACH_NONE = 0x7FFFFFFF  # PWPP_REACH_NONE: no path from the source
 
 
+class ClusterLink(ctypes.Structure):  # pwpp_cluster_link (16 bytes): a row's best partner on the other side, their shared cells, its own cells, its partners
+    _fields_ = [("other", ctypes.c_int32), ("overlap", ctypes.c_int32), ("cells", ctypes.c_int32), ("links", ctypes.c_int32)]
+
+
+CLUSTER_LINK_DTYPE = np.dtype([("other", "<i4"), ("overlap", "<i4"), ("cells", "<i4"), ("links", "<i4")])
+LINK_NONE, LINK_OVERFLOWED = -1, -2  # `other` of a row without a partner; of every row of a frame with more than max_pairs pairs
+
+
 class MatchBest(ctypes.Structure):  # pwpp_match_best (24 bytes): the winning sum, its candidate (-1: skipped) and shift, the frame's occupied cells
     _fields_ = [("score", ctypes.c_int64), ("candidate", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("cells", ctypes.c_int32)]
 
@@ -248,6 +256,11 @@ def load():
             L.pwpp_reach_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, vp]
             L.pwpp_reach_ground.argtypes = [vp, gp, ci, ci, ci, tp, rp, vp, ci, vp, vp, vp]
             L.pwpp_grid_cell_of.argtypes = [gp, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "pwpp_associate_grid"):  # (as above: an older build has no cluster tracks)
+            gp = ctypes.POINTER(GroundGrid)
+            L.pwpp_associate_grid.argtypes = [vp, gp, gp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+            L.pwpp_track_obstacles.argtypes = [vp, gp, ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp,
+                                               vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
@@ -959,6 +972,103 @@ class Handle:
         self._check(self._L.pwpp_label_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity),
                                                  int(frame_first), frames, MEM_DEVICE, _dp(label_ptr), _dp(count_ptr), _dp(top_ptr),
                                                  _dp(clusters_ptr), _dp(n_clusters_ptr), int(max_clusters), _dp(point_cluster_ptr)))
+
+    @staticmethod
+    def _label_images(label, what):
+        """The (frames, ny, nx) int32 view of a (frames, ny, nx) or (ny, nx) label image."""
+        lab = np.ascontiguousarray(label, np.int32)
+        l3 = lab.reshape((1,) + lab.shape) if lab.ndim == 2 else lab
+        if l3.ndim != 3:
+            raise ValueError("%s: a (frames, ny, nx) or (ny, nx) label image expected" % what)
+        return l3
+
+    @staticmethod
+    def _id_arrays(frames, rows, id_prev, next_id):
+        """(id_prev, next_id, id_curr, next_id_out) as the library takes them: four host arrays, or four times None without id_prev."""
+        if id_prev is None and next_id is None:
+            return None, None, None, None
+        ip = np.asarray(-1 if id_prev is None else id_prev, np.int32)
+        ip = np.ascontiguousarray(np.broadcast_to(ip, (frames, rows)) if ip.ndim == 0 else ip)
+        if ip.shape != (frames, rows):
+            raise ValueError("id_prev: (frames, max_rows) expected")
+        nx = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if next_id is None else next_id, np.int32), (frames,)), np.int32)
+        return ip, nx, np.empty((frames, rows), np.int32), np.empty(frames, np.int32)
+
+    def associate_grid(self, curr, prev, pose, grid_curr, grid_prev=None, gate=0, min_overlap=1, max_rows=1, max_pairs=1, id_prev=None, next_id=None,
+                       want_n_pairs=True):
+        """Which row of the (frames, ny, nx) or (ny, nx) int32 label images `curr` is which row of `prev`: grid_curr and grid_prev
+        (None: the same) are (x0, y0, cell) of the two grids, whose sides are the images'; pose: {a, b, tx, c, d, ty} for every
+        frame or (frames, 6), where a position of the previous frame lies in the current one.  Works before any estimate call.
+        Returns (curr_links, prev_links, n_pairs): two (frames, max_rows) tables of CLUSTER_LINK_DTYPE and the (frames,) int32
+        numbers of pairs (None when not wanted); with id_prev ((frames, max_rows) int32, or one value for all) and next_id ((frames,)
+        or one value) also (id_curr, next_id_out).  The rules: include/pwpp.h."""
+        c3, p3 = self._label_images(curr, "curr"), self._label_images(prev, "prev")
+        frames = c3.shape[0]
+        gc = GroundGrid(float(grid_curr[0]), float(grid_curr[1]), float(grid_curr[2]), c3.shape[2], c3.shape[1], 0, 0)
+        gq = grid_curr if grid_prev is None else grid_prev
+        gp = GroundGrid(float(gq[0]), float(gq[1]), float(gq[2]), p3.shape[2], p3.shape[1], 0, 0)
+        poses = _host(pose, np.float64, -1, 6)
+        rows = max(int(max_rows), 0)
+        cl, pl = np.zeros((frames, rows), CLUSTER_LINK_DTYPE), np.zeros((frames, rows), CLUSTER_LINK_DTYPE)
+        n = np.zeros(max(frames, 1), np.int32) if want_n_pairs else None
+        ip, nxt, ic, nout = self._id_arrays(frames, rows, id_prev, next_id)
+        self._check(self._L.pwpp_associate_grid(self._h, ctypes.byref(gc), ctypes.byref(gp), frames, MEM_HOST, _hp(c3), _hp(p3), _hp(poses), len(poses),
+                                                int(gate), int(min_overlap), int(max_rows), int(max_pairs), _hp(cl), _hp(pl), _hp(n), _hp(ip), _hp(nxt),
+                                                _hp(ic), _hp(nout)))
+        out = (cl, pl, n[:frames] if want_n_pairs else None)
+        return out + (ic, nout) if ip is not None else out
+
+    def associate_grid_device(self, grid_curr, grid_prev, frames, curr_ptr, prev_ptr, pose, gate, min_overlap, max_rows, max_pairs, curr_links_ptr,
+                              prev_links_ptr, n_pairs_ptr=0, id_prev_ptr=0, next_id_ptr=0, id_curr_ptr=0, next_id_out_ptr=0):
+        """associate_grid on device memory: grid_curr and grid_prev are (x0, y0, cell, nx, ny); addresses of the int32 label images,
+        the two (frames, max_rows) tables of 16-byte rows, the (frames,) int32 pair counts (0: none) and the four id arrays (all or
+        0), every one 4-byte aligned; pose stays a host array.  Enqueued on the handle's stream; complete after synchronize()."""
+        gc = GroundGrid(float(grid_curr[0]), float(grid_curr[1]), float(grid_curr[2]), int(grid_curr[3]), int(grid_curr[4]), 0, 0)
+        gp = GroundGrid(float(grid_prev[0]), float(grid_prev[1]), float(grid_prev[2]), int(grid_prev[3]), int(grid_prev[4]), 0, 0)
+        poses = _host(pose, np.float64, -1, 6)
+        self._check(self._L.pwpp_associate_grid(self._h, ctypes.byref(gc), ctypes.byref(gp), int(frames), MEM_DEVICE, _dp(curr_ptr), _dp(prev_ptr),
+                                                _vp(poses) if poses.size else None, len(poses), int(gate), int(min_overlap), int(max_rows), int(max_pairs),
+                                                _dp(curr_links_ptr), _dp(prev_links_ptr), _dp(n_pairs_ptr), _dp(id_prev_ptr), _dp(next_id_ptr),
+                                                _dp(id_curr_ptr), _dp(next_id_out_ptr)))
+
+    def track_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, prev_label, pose=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0), min_count=1, connectivity=8,
+                        max_clusters=1, gate=0, min_overlap=1, max_pairs=1, id_prev=None, next_id=None, frame_first=0, frames=None):
+        """label_obstacles and associate_grid of its label image against the (frames, ny, nx) int32 `prev_label` on the same grid in
+        one call, for frames of the last estimate call; max_rows is max_clusters.  Returns (label, clusters, n_clusters, curr_links,
+        prev_links, n_pairs) and, with id_prev and next_id, (id_curr, next_id_out): feed label, id_curr and next_id_out back as
+        prev_label, id_prev and next_id of the next step."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        shape = self._grid_shape(g, frames)
+        label = np.empty(shape, np.int32)
+        prev = np.ascontiguousarray(prev_label, np.int32)
+        if prev.size != label.size:
+            raise ValueError("prev_label: (frames, ny, nx) expected")
+        rows = max(int(max_clusters), 0)
+        table = np.zeros((shape[0], rows), OBSTACLE_CLUSTER_DTYPE)
+        n = np.zeros(max(frames, 1), np.int32)
+        poses = _host(pose, np.float64, -1, 6)
+        cl, pl = np.zeros((shape[0], rows), CLUSTER_LINK_DTYPE), np.zeros((shape[0], rows), CLUSTER_LINK_DTYPE)
+        n_pairs = np.zeros(max(frames, 1), np.int32)
+        ip, nxt, ic, nout = self._id_arrays(shape[0], rows, id_prev, next_id)
+        self._check(self._L.pwpp_track_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity), int(frame_first),
+                                                 frames, MEM_HOST, _hp(label), None, None, _vp(table) if table.size else None, _vp(n), int(max_clusters), None,
+                                                 _hp(prev), _hp(poses), len(poses), int(gate), int(min_overlap), int(max_pairs), _hp(cl), _hp(pl),
+                                                 _hp(n_pairs), _hp(ip), _hp(nxt), _hp(ic), _hp(nout)))
+        out = (label, table, n[:shape[0]], cl, pl, n_pairs[:shape[0]])
+        return out + (ic, nout) if ip is not None else out
+
+    def track_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, min_count, connectivity, label_ptr, prev_label_ptr, pose, gate, min_overlap,
+                               max_clusters, max_pairs, curr_links_ptr, prev_links_ptr, n_pairs_ptr=0, id_prev_ptr=0, next_id_ptr=0, id_curr_ptr=0,
+                               next_id_out_ptr=0, count_ptr=0, top_ptr=0, clusters_ptr=0, n_clusters_ptr=0, point_cluster_ptr=0, frame_first=0, frames=None):
+        """track_obstacles into device memory: addresses as in label_obstacles_device and associate_grid_device; pose stays a host
+        array.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        poses = _host(pose, np.float64, -1, 6)
+        self._check(self._L.pwpp_track_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity), int(frame_first),
+                                                 frames, MEM_DEVICE, _dp(label_ptr), _dp(count_ptr), _dp(top_ptr), _dp(clusters_ptr), _dp(n_clusters_ptr),
+                                                 int(max_clusters), _dp(point_cluster_ptr), _dp(prev_label_ptr), _vp(poses) if poses.size else None, len(poses),
+                                                 int(gate), int(min_overlap), int(max_pairs), _dp(curr_links_ptr), _dp(prev_links_ptr), _dp(n_pairs_ptr),
+                                                 _dp(id_prev_ptr), _dp(next_id_ptr), _dp(id_curr_ptr), _dp(next_id_out_ptr)))
 
     def distance_grid(self, count, min_count=1, max_dist=0, cell=1.0, want_nearest=True, want_metres=True):
         """The exact Euclidean distance of every cell of a (frames, ny, nx) or (ny, nx) int32 count image to the nearest occupied

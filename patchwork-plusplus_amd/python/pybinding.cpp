@@ -160,6 +160,7 @@ PYBIND11_MODULE(pypatchworkpp, m) {
 
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_cluster, first_cell, cells, points, ix_min, ix_max, iy_min, iy_max, top, sum_ix, sum_iy);
 
+    PYBIND11_NUMPY_DTYPE(pwpp_cluster_link, other, overlap, cells, links);
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_box, points, pad_, mean_x, mean_y, cx, cy, ax, ay, length, width, sigma_long, sigma_short, h_min, h_max, z_min,
                          z_max);
 
@@ -345,6 +346,26 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("connectivity") = 8, py::arg("ground_only") = false)
+        .def("trackObstacleClusters",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, const std::array<double, 6> &pose, int min_count,
+                int connectivity, int max_clusters, int gate, int min_overlap) {
+                 const PatchWorkpp::ObstacleTracks t =
+                     s.trackObstacleClusters(x0, y0, cell, nx, ny, h_min, h_max, pose.data(), min_count, connectivity, max_clusters, gate, min_overlap);
+                 py::array_t<int32_t> label({(py::ssize_t)t.ny, (py::ssize_t)t.nx});
+                 if (!t.label.empty()) std::memcpy(label.mutable_data(), t.label.data(), t.label.size() * sizeof(int32_t));
+                 py::array_t<pwpp_obstacle_cluster> table((py::ssize_t)t.clusters.size());
+                 if (!t.clusters.empty()) std::memcpy(table.mutable_data(), t.clusters.data(), t.clusters.size() * sizeof(pwpp_obstacle_cluster));
+                 py::array_t<pwpp_cluster_link> curr_links((py::ssize_t)t.curr_links.size()), prev_links((py::ssize_t)t.prev_links.size());
+                 if (!t.curr_links.empty()) std::memcpy(curr_links.mutable_data(), t.curr_links.data(), t.curr_links.size() * sizeof(pwpp_cluster_link));
+                 if (!t.prev_links.empty()) std::memcpy(prev_links.mutable_data(), t.prev_links.data(), t.prev_links.size() * sizeof(pwpp_cluster_link));
+                 py::array_t<int32_t> ids((py::ssize_t)t.ids.size());
+                 if (!t.ids.empty()) std::memcpy(ids.mutable_data(), t.ids.data(), t.ids.size() * sizeof(int32_t));
+                 return py::make_tuple(label, table, curr_links, prev_links, ids, t.count, t.pairs);
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("pose") = std::array<double, 6>{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}}, py::arg("min_count") = 1, py::arg("connectivity") = 8,
+             py::arg("max_clusters") = 256, py::arg("gate") = 1, py::arg("min_overlap") = 1)
+        .def("resetObstacleTracks", [](PatchWorkpp &s) { s.resetObstacleTracks(); })
         .def("getGroundPoints", [](PatchWorkpp &s) { return to_numpy(s.groundPointRows()); })
         .def("getNongroundPoints", [](PatchWorkpp &s) { return to_numpy(s.nongroundPointRows()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
