@@ -50,7 +50,7 @@ constexpr int kPPT = 8;  // points per lane held in registers
 #define PWPP_W16_OCC 4  // waves per SIMD the 16-lane fit kernel is compiled for (3: 2 spilled registers instead of 77, 18 % slower alone -- profiles/r04_experiments.txt)
 #endif
 #ifndef PWPP_W16_WIDE_OCC
-#define PWPP_W16_WIDE_OCC 3  // ... on the wide grid (contract v4): sixteen totals per patch in LDS (12.4 KB per wave) allow three waves per SIMD anyway
+#define PWPP_W16_WIDE_OCC 3  // ... on the wide grid (contract v4).  4 builds (w64_occupancy gives it to the instances whose LDS fits) and loses: DESIGN.md section 5
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -357,13 +357,26 @@ __device__ __forceinline__ bool z_stripped(float z) { return (int)__float_as_uin
 //   G < 64 (small patches)              slot k of lane j = point c * 8G + k * G + j: a patch of n points fills
 //          ceil(n / G) slots of every lane, and the slots above are skipped wave-wide (with four consecutive
 //          points per lane a 20-point patch would keep 5 lanes busy for 4 slots: k_fit_w64<16,64> 0.84 -> 1.19 ms).
-// The loads are unconditional (the first points of the patch stand in beyond its end -- NOT whatever follows in
-// memory: a one-pass segment is mostly unwritten space, and fetching it cost k_fit_w64<16,64> 9 %): the compiler can
-// keep a whole chunk in flight behind the arithmetic of the previous one and wait with a counted s_waitcnt.
+// What lies beyond a part's end is never fetched (a one-pass segment is mostly unwritten space, and fetching it cost
+// k_fit_w64<16,64> 9 %; behind the last part of the last frame the planes end):
+//   G = 64  the loads are unconditional and the first points of the part stand in beyond its end;
+//   G < 64  a lane forms ONE address per plane, that of its first point, and slot k is base + k * G points -- a
+//           constant the load carries as its immediate offset (64 B apart in the z plane, 128 B in {x, y}).  A slot
+//           beyond the part's end is not loaded at all: its registers hold anything (unloaded_f32), and EVERY consumer
+//           masks by `rem` below -- lane_stage_accum, lane_strip, the band of a dual pass, chunk_act_z.  (Before:
+//           a redirected index and an address pair per slot, five address instructions per slot and ~32 registers.)
+//           In the listing every slot's loads stand under the lane mask with a branch around them for the rows that
+//           are all past their ends, one slot after the other; how many loads are in flight is then not known at
+//           compile time, so the wait before the first slot's arithmetic is for everything the chunk requested
+//           (vmcnt(1) / vmcnt(0) instead of counting down from 15): all of them were requested back to back one
+//           instruction earlier, and the kernels measure the same or better.
 // Which slots of a lane's chunk lie inside the part: slot k holds point first + k_off(k), so with
 //   rem = points of the part - index of the lane's first point          (signed; <= 0: nothing of this lane's)
 // slot k is valid iff k_off(k) < rem -- ONE compare with a constant per slot where it is needed at all: a chunk that is
 // valid in every lane of the wave needs none, but a second code path for it costs more registers than the compare).
+// what the register of a slot that is not loaded holds: some float of the compiler's choice (it moves a 0 there; an empty asm
+// statement as the placeholder saved 4 of the chunk loop's 430 vector instructions and doubled the narrow kernel's spills)
+__device__ __forceinline__ float unloaded_f32() { return __builtin_nondeterministic_value(0.0f); }
 struct ChunkZ {  // what the lowest-point pass needs
     float z[kPPT];
     int rem;
@@ -403,11 +416,21 @@ __device__ __forceinline__ unsigned chunk_valid_bits(int rem) {
 template <int G>
 __device__ __forceinline__ void load_chunk_z(ChunkZ &cp, const PatchRef &pr, const PartSel &sel) {
     const unsigned j = (unsigned)lane_id() & (G - 1);
-    cp.rem = (int)sel.n - (int)(sel.c * (8u * G) + j);
+    const unsigned first = sel.c * (8u * G) + j;
+    cp.rem = (int)sel.n - (int)first;
+    if constexpr (G < 64) {
+        const float *zp = pr.z + (sel.off + first);  // (formed for every lane, followed only below the part's end)
 #pragma unroll
-    for (int k = 0; k < kPPT; ++k) {
-        const unsigned i = sel.c * (8u * G) + (unsigned)k * G + j;
-        cp.z[k] = pr.z[sel.off + (i < sel.n ? i : 0u)];
+        for (int k = 0; k < kPPT; ++k) {
+            cp.z[k] = unloaded_f32();
+            if (k * G < cp.rem) cp.z[k] = zp[k * G];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPPT; ++k) {
+            const unsigned i = first + (unsigned)k * G;
+            cp.z[k] = pr.z[sel.off + (i < sel.n ? i : 0u)];
+        }
     }
 }
 // the slots of a ChunkZ that are inside the part and still in the patch's working set (not removed by R-VPF)
@@ -443,13 +466,18 @@ __device__ __forceinline__ void load_chunk(ChunkPts &cp, const PatchRef &pr, con
             cp.y[4 * q + 3] = b.w;
         }
     } else {
+        const unsigned first = sel.off + chunk_point<G>(sel.c, 0, j);  // (formed for every lane, followed only below the part's end)
+        const float *zp = pr.z + first;
+        const float2 *xyp = pr.xy + first;
 #pragma unroll
         for (int k = 0; k < kPPT; ++k) {
-            const unsigned i1 = chunk_point<G>(sel.c, k, j), i = sel.off + (i1 < sel.n ? i1 : 0u);
-            const float2 v = pr.xy[i];
-            cp.z[k] = pr.z[i];
-            cp.x[k] = v.x;
-            cp.y[k] = v.y;
+            cp.z[k] = cp.x[k] = cp.y[k] = unloaded_f32();
+            if (k_off<G>(k) < cp.rem) {
+                const float2 v = xyp[k_off<G>(k)];
+                cp.z[k] = zp[k_off<G>(k)];
+                cp.x[k] = v.x;
+                cp.y[k] = v.y;
+            }
         }
     }
 }
@@ -462,7 +490,7 @@ __device__ __forceinline__ unsigned chunk_slot(const PartSel &sel, int k, unsign
 //   (0,0,1), d = 0: 0*x + 0*y + 1*z + 0.0 == z for the finite x, y that binning lets through, so the per-point code has
 //   no branch on the stage.  The test itself is  s < T  in float, T = plane_test_threshold(d, thr) of the pass
 //   (pwpp_common.hpp): bit for bit the reference's  double(s) + d < thr.  A point R-VPF removed has a NaN for its z
-//   (strip_point) and fails like any NaN; a slot beyond the part's end holds a stand-in record and is masked by `rem`.
+//   (strip_point) and fails like any NaN; a slot beyond the part's end holds a stand-in record or was not loaded at all (load_chunk) and is masked by `rem`.
 // `clamp_hit` (or-ed into): some point that entered the sums lay outside z0 +- ZR, i.e. its quantised height was clamped (flag_clamped
 // below says what that means; found here, where the clamped height is formed anyway -- one compare per included point instead of four
 // per slot in a loop of its own).
@@ -1721,12 +1749,22 @@ struct W64 {
     }
 };
 
+// waves per SIMD an instance is compiled for.  16-lane rows on the wide grid: PWPP_W16_WIDE_OCC where the waves' LDS blocks fit into a
+// CU's 160 KB side by side (four per SIMD: 10 KB each, up to 48 patches per wave), one wave less where they do not (64 patches: 12.4 KB)
+template <int G, int PW, bool WIDE>
+constexpr int w64_occupancy() {
+    if (G == 64) return PWPP_W64_OCC;
+    if (!WIDE) return PWPP_W16_OCC;
+    int occ = PWPP_W16_WIDE_OCC;
+    while (occ > 1 && sizeof(typename W64<G, PW, WIDE>::Shared) * 4u * (unsigned)occ > 160u * 1024u) --occ;
+    return occ;
+}
 // G = lanes per patch in the points phases (16: four patches at a time; 64: one at a time, for
 // big bins), PW = patches owned by the wave = lanes active in the solve phase.
 // Moments per patch in LDS: rows of 16 lanes only see patches below 2048 points, whose ten totals fit
 // int64; 64-lane rows leave sixteen values (second moments as 32-bit halves, Row<64>::reduce16_scatter).
 template <int G, int PW, bool WIDE>
-__global__ __launch_bounds__(64, G == 64 ? PWPP_W64_OCC : (WIDE ? PWPP_W16_WIDE_OCC : PWPP_W16_OCC)) void k_fit_w64(PwppBatch Bt, int b_lo, int b_hi) {
+__global__ __launch_bounds__(64, (w64_occupancy<G, PW, WIDE>())) void k_fit_w64(PwppBatch Bt, int b_lo, int b_hi) {
     // ONE WAVE PER WORKGROUP: the waves never talk to each other, and a workgroup of four only starts when a CU has
     // room for all four at once -- with waves of very different lifetimes the slots of the early finishers stood empty
     // (27 % of the wave slots of k_fit_w64<64,2>, profiles/).
