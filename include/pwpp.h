@@ -1203,6 +1203,117 @@ PWPP_API int pwpp_track_obstacles(pwpp_handle *h, const pwpp_ground_grid *g /* f
                                   int max_pairs, pwpp_cluster_link *curr_links, pwpp_cluster_link *prev_links /* [frames][max_clusters] each */,
                                   int32_t *n_pairs, const int32_t *id_prev, const int32_t *next_id, int32_t *id_curr, int32_t *next_id_out);
 
+/* ---- map evidence: what the fused map holds under every cluster of a frame (pwpp_evidence_grid, pwpp_evidence_obstacles) -----------
+ * Perception gives a label image per frame, the fusion a persistent log-odds map; these calls relate the two.  Every labelled cell of
+ * a frame is carried into the map by the frame's pose and reads the map there; per cluster row the readings are counted by class
+ * and a verdict says whether the cluster is part of the world the map already knows (static) or stands where the map has seen free
+ * space (moving).  The masked occupancy bytes leave the movers out of the next fusion.  Integer counts and a verdict from integer
+ * ratios: a total function of the inputs, the same bytes for every mem, alignment, schedule and value of the option "evidence_path".
+ * estimate -> match -> visibility -> label -> evidence -> fuse the masked bytes.  Below (X0, Y0, CELL, NX, NY) are m's fields,
+ * (x0, y0, cell, nx, ny) g's.
+ *   inputs    per frame f: label[f], an int32 label image on the grid g (flags 0), as pwpp_label_grid writes it or edited by the
+ *             caller; a map-from-frame pose {a, b, tx, c, d, ty}, exactly the fusion's pose and the match's candidate; the frame's
+ *             map k by the fusion's map_of_frame rule (NULL with one map, NULL with one map per frame, or explicit; -1 skips the
+ *             frame); int16 log-odds maps map[n_maps][NY][NX] described by m, of which x0, y0, cell, nx, ny, occupied_at and free_at
+ *             are read.  n_poses is 1 (for every frame) or `frames`.  Poses and map_of_frame are HOST memory whatever mem, copied at
+ *             the call.
+ *   rows      A label l names a row iff 0 <= l < max_rows, as in pwpp_associate_grid.  Every other value is unlabelled.
+ *   landing   A labelled cell (ix, iy) lands at (Jx, Jy) by the scan match's landing (pwpp_match_grid above: the cell's centre, the
+ *             pose, the quotient by CELL, |U|, |V| < 1048576, the floor; no FMA) under the frame's pose.  The cell is LANDED iff it
+ *             lands there and 0 <= Jx < NX and 0 <= Jy < NY.  A pose that is not finite lands nothing; a skipped frame lands nothing.
+ *   reading   For a landed cell, E is the maximum of map[k][Jy + ey][Jx + ex] over |ex|, |ey| <= gate inside the map; gate is
+ *             0 .. 4, with gate 0 E is the one cell.  The maximum is chosen so that a wall displaced by a pose error of up to `gate`
+ *             cells still finds its wall -- the half-cell dilation of the fusion's four samples is a displacement of that kind --
+ *             while a mover in swept free space finds only free cells.  THE PRICE: a mover within `gate` cells of a mapped wall
+ *             reads as wall.
+ *   class     of a landed cell, the fusion's byte rule applied to E: PWPP_OCC_OCCUPIED where E >= occupied_at; otherwise
+ *             PWPP_OCC_FREE where E <= free_at; otherwise PWPP_OCC_UNKNOWN.
+ *   row       rows[f][r]: cells = all cells labelled r; landed = those that landed; occupied, free and unknown count the landed
+ *             cells by class (their sum is landed); sum = the int64 sum of E over the landed cells.  max_rows rows per frame.
+ *   verdict   from rule = {gate, min_cells, moving_share, static_share}, min_cells >= 1, the shares 1 .. 256 in 256ths, evaluated
+ *             in int64 in this order: PWPP_EVID_NONE where cells == 0; otherwise PWPP_EVID_MOVING where landed >= min_cells and
+ *             free * 256 >= moving_share * landed; otherwise PWPP_EVID_STATIC where landed >= min_cells and occupied * 256 >=
+ *             static_share * landed; otherwise PWPP_EVID_UNDECIDED.  pwpp_evidence_verdict is the same function on the host.
+ *   cell_class  Optional, int8 [frames][ny][nx]: the class byte of a labelled, landed cell, PWPP_EVID_CELL_NONE for every other cell.
+ *   occupancy_out  Optional, int8, together with occupancy_in: both or neither.  PWPP_OCC_UNKNOWN where the cell's label names a row
+ *             whose verdict is PWPP_EVID_MOVING; everywhere else the input byte verbatim, whatever its value.  These are the bytes
+ *             to hand to pwpp_fuse_grid so that the mover is not observed at all.  occupancy_out == occupancy_in, the same pointer,
+ *             is allowed: each byte is read and written by one lane.  Any other overlap among the caller's arrays is an error.
+ *   evidence_obstacles  for frames of the LAST estimate call: enqueues pwpp_label_obstacles(g, h_min, h_max, min_count, connectivity,
+ *             frame_first, frames, ...) and the evidence of that label image with max_rows = max_clusters as one sequence.  label,
+ *             count, top, clusters, n_clusters and point_cluster are exactly what pwpp_label_obstacles gives; rows, cell_class and
+ *             occupancy_out exactly what pwpp_evidence_grid gives for that image.  Entry i of pose and map_of_frame belongs to frame
+ *             frame_first + i.  Before any estimate call: PWPP_E_STATE.
+ *   state     The handle keeps nothing between calls.  A verdict joins an id of pwpp_track_obstacles by its row: both use the row
+ *             numbers of the same label image.
+ *   mem       PWPP_MEM_HOST: every array but the poses and map_of_frame is host memory, staged through the handle's cluster buffer;
+ *             synchronous.  PWPP_MEM_DEVICE: device memory -- rows 8-byte aligned, label 4, map 2, the byte images 1 -- enqueued on
+ *             the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order.  pwpp_evidence_grid: a null handle, grid, label image,
+ *             pose, map description, map, rule, rows; frames or a side of g < 1, a side > 32768, nx * ny * frames beyond 2^31; the
+ *             same three of n_maps and the map; g->flags != 0; an origin or cell of g that is not finite, the cell positive; the
+ *             same of the map; free_at < -32768, free_at >= occupied_at or occupied_at > 32767; gate outside 0 .. 4; min_cells < 1;
+ *             moving_share, then static_share outside 1 .. 256; max_rows < 1, then frames * max_rows > 2^24; the count of poses;
+ *             map_of_frame; one of occupancy_in and occupancy_out without the other; two of the caller's arrays overlapping; mem; in
+ *             PWPP_MEM_DEVICE an array below its alignment.  pwpp_evidence_obstacles: a null handle, grid, label image, pose, map
+ *             description, map, rule, rows; then everything pwpp_label_obstacles rejects, in its order -- PWPP_E_STATE before any
+ *             estimate call among it; then a side > 32768, grid flags other than 0, and the above from the map's sizes on.
+ *   buffers   The poses and the frames' maps are uploaded into the cluster buffer, where in PWPP_MEM_HOST the staged arrays lie
+ *             too; counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.  The rows themselves take the kernels' sums:
+ *             there are no working words.  pwpp_evidence_grid needs a handle for its stream and this buffer only, like
+ *             pwpp_associate_grid.
+ *   option    "evidence_path": 0 = the path the measurement chose, 1 = the sums go to the rows with global
+ *             atomics, 2 = a workgroup sums a run of cells in LDS first, where max_rows <= PWPP_EVID_LDS_ROWS: 24 bytes a row, 12
+ *             KiB, so that the tables of the eight workgroups of 256 lanes that make 8 waves a SIMD take 96 of a CU's 160 KiB;
+ *             beyond that path 2 is path 1.
+ * With neither function called nothing is allocated or launched, and no result, state or timing of any other call changes.
+ * Not built: motion models, verdicts smoothed over time (the id of pwpp_track_obstacles lets a caller do that), free-space evidence
+ * inside the match's score, erasing a trail that is already in the map. */
+#define PWPP_HAS_MAP_EVIDENCE 1
+#define PWPP_EVID_LDS_ROWS 512
+enum { PWPP_EVID_NONE = -1, PWPP_EVID_UNDECIDED = 0, PWPP_EVID_STATIC = 1, PWPP_EVID_MOVING = 2 };   /* the verdict of a row */
+enum { PWPP_EVID_CELL_NONE = -2 };   /* cell_class of a cell that is not labelled or not landed */
+typedef struct pwpp_cluster_evidence {   /* 32 bytes, 8-byte aligned */
+    int64_t sum;         /* the sum of E over the landed cells */
+    int32_t cells;       /* all cells of the image labelled with this row */
+    int32_t landed;      /* those that landed inside the map */
+    int32_t occupied;    /* landed cells by class: E >= occupied_at */
+    int32_t free;        /* ... E <= free_at */
+    int32_t unknown;     /* ... between the two */
+    int32_t verdict;     /* PWPP_EVID_* */
+} pwpp_cluster_evidence;
+typedef struct pwpp_evidence_rule {      /* 16 bytes */
+    int32_t gate;          /* 0 .. 4 map cells */
+    int32_t min_cells;     /* >= 1: fewer landed cells leave a row undecided */
+    int32_t moving_share;  /* 1 .. 256, in 256ths of the landed cells */
+    int32_t static_share;  /* 1 .. 256 */
+} pwpp_evidence_rule;
+
+/* any label images and maps: needs a handle (stream, buffer), no estimate call -- like pwpp_associate_grid */
+PWPP_API int pwpp_evidence_grid(pwpp_handle *h, const pwpp_ground_grid *g /* the label images' grid; flags must be 0 */, int frames, int mem,
+                                const int32_t *label /* [frames][g->ny][g->nx] */,
+                                const int8_t *occupancy_in /* [frames][g->ny][g->nx], or NULL with occupancy_out NULL */,
+                                const double *pose /* HOST: n_poses x {a, b, tx, c, d, ty} */, int n_poses /* 1 or frames */,
+                                const int32_t *map_of_frame /* HOST, frames entries, or NULL: the fusion's rule */,
+                                const pwpp_fusion_map *m, int n_maps, const int16_t *map /* [n_maps][m->ny][m->nx] */,
+                                const pwpp_evidence_rule *rule, int max_rows,
+                                pwpp_cluster_evidence *rows /* [frames][max_rows] */,
+                                int8_t *cell_class /* [frames][g->ny][g->nx], may be NULL */,
+                                int8_t *occupancy_out /* like occupancy_in, may be that pointer */);
+/* label_obstacles + the evidence of its label image for frames of the LAST estimate call, one enqueued sequence -- like
+ * pwpp_track_obstacles.  The arguments up to point_cluster are pwpp_label_obstacles'. */
+PWPP_API int pwpp_evidence_obstacles(pwpp_handle *h, const pwpp_ground_grid *g /* flags: 0 */, float h_min, float h_max, int min_count, int connectivity,
+                                     int frame_first, int frames, int mem, int32_t *label, int32_t *count, float *top,
+                                     pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters, int32_t *point_cluster,
+                                     const int8_t *occupancy_in, const double *pose, int n_poses, const int32_t *map_of_frame,
+                                     const pwpp_fusion_map *m, int n_maps, const int16_t *map, const pwpp_evidence_rule *rule,
+                                     pwpp_cluster_evidence *rows /* [frames][max_clusters] */, int8_t *cell_class, int8_t *occupancy_out);
+/* host only, no device needed: *verdict = PWPP_EVID_* of a row with these counts (PWPP_EVID_NONE is -1, so the verdict is no return
+ * value); PWPP_E_ARG for a null rule or verdict, a rule out of range, or counts that no row has (negative, landed > cells,
+ * occupied + free > landed) */
+PWPP_API int pwpp_evidence_verdict(const pwpp_evidence_rule *rule, int32_t cells, int32_t landed, int32_t occupied, int32_t free_cells,
+                                   int32_t *verdict);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1354,6 +1465,11 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         landings of a (frame, candidate) reach under the window is copied into LDS once per workgroup where it
  *                         holds at most 65536 cells, and read from global memory where it does not; "0" (default): whichever of
  *                         the two that tool found faster.  The results are identical bytes.
+ *   "evidence_path"       where the map evidence sums a row's counters (pwpp_evidence_grid, pwpp_evidence_obstacles): "1": in the output
+ *                         rows, with global atomics (the yardstick of tools/evidence_cost.py); "2": a workgroup sums a run of 2048
+ *                         cells in a table in LDS first where max_rows <= PWPP_EVID_LDS_ROWS, and as "1" where it is not; "0"
+ *                         (default): whichever of the two that tool found faster on 256 x 256 cells.  The results
+ *                         are identical bytes.
  *   "debug_flags"         4: timing probes of the fit chain; 8: timing probes of the binning, scan and GLE kernels;
  *                         16: exact binning arithmetic only;
  *                         128: the first pass of the history statistics always as the reference's sequential sum (no exact shortcut);

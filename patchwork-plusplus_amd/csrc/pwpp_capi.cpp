@@ -26,6 +26,7 @@
 #include "pwpp_dev.h"
 #include "pwpp_distance.h"
 #include "pwpp_elevation.h"
+#include "pwpp_evidence.h"
 #include "pwpp_fusion.h"
 #include "pwpp_match.h"
 #include "pwpp_reach.h"
@@ -258,6 +259,7 @@ struct pwpp_handle {
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
     int reach_path = 0;             // option "reach_path": 0 = what tools/reach_cost.py decided; 1 = sweeps over global memory, a workgroup per frame (yardstick); 2 = the frame's tiles relaxed in LDS, dirty tiles revisited
+    int evidence_path = 0;          // option "evidence_path": 0 = what tools/evidence_cost.py decided; 1 = the sums go to the rows with global atomics (yardstick); 2 = a workgroup sums a run of cells in LDS first where the rows fit
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
     std::vector<std::vector<uint32_t>> uploads;  // the tables the last call that uploaded any built for its kernels: the sources of their copies (Staging::add_upload)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
@@ -2143,6 +2145,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
         h->match_path = v;
+    } else if (k == "evidence_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "evidence_path=%s: 0, 1 or 2 expected", value);
+        h->evidence_path = v;
     } else if (k == "boxes_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
@@ -3580,6 +3586,189 @@ int pwpp_track_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
         }
         return lrc != 0 ? lrc : track_launch(h, st, ts, G, rule, frames, n_poses, n_pairs != nullptr);
     });
+}
+
+// ---- map evidence: what the fused map holds under the cells of every cluster row of a label image -------------------------------------
+namespace {
+static_assert(sizeof(pwpp_cluster_evidence) == 32 && sizeof(PwppClusterEvidence) == 32 && alignof(pwpp_cluster_evidence) == 8, "pwpp_cluster_evidence is 32 bytes, 8-byte aligned");
+static_assert(offsetof(pwpp_cluster_evidence, sum) == offsetof(PwppClusterEvidence, sum) && offsetof(pwpp_cluster_evidence, cells) == offsetof(PwppClusterEvidence, cells) &&
+                  offsetof(pwpp_cluster_evidence, landed) == offsetof(PwppClusterEvidence, landed) && offsetof(pwpp_cluster_evidence, occupied) == offsetof(PwppClusterEvidence, occupied) &&
+                  offsetof(pwpp_cluster_evidence, free) == offsetof(PwppClusterEvidence, free) && offsetof(pwpp_cluster_evidence, unknown) == offsetof(PwppClusterEvidence, unknown) &&
+                  offsetof(pwpp_cluster_evidence, verdict) == offsetof(PwppClusterEvidence, verdict),
+              "the kernels' row of the evidence");
+static_assert(sizeof(pwpp_evidence_rule) == sizeof(PwppEvidenceRule), "the kernels' rule");
+static_assert(PWPP_EVID_NONE == PWPP_EV_NONE && PWPP_EVID_UNDECIDED == PWPP_EV_UNDECIDED && PWPP_EVID_STATIC == PWPP_EV_STATIC && PWPP_EVID_MOVING == PWPP_EV_MOVING &&
+                  PWPP_EVID_CELL_NONE == PWPP_EV_CELL_NONE && PWPP_EVID_LDS_ROWS == PWPP_EV_LDS_ROWS,
+              "the kernels' verdicts, class byte and LDS rows");
+constexpr const char *kEvidenceWho = "the map evidence takes";
+
+// The caller's arrays of an evidence call besides the label image: what both entry points pass on.
+struct EvidenceArrays {
+    const int8_t *occ_in;
+    const double *pose;
+    int n_poses;
+    const int32_t *map_of_frame;
+    const int16_t *map;
+    pwpp_cluster_evidence *rows;
+    int8_t *cell_class, *occ_out;
+};
+
+// What a checked call hands to the kernels besides its arrays: geometry, rule, thresholds and the words to upload -- the poses
+// first (8-byte aligned at the section's start), then every frame's map, the rule of map_of_frame resolved.
+struct EvidencePlan {
+    PwppMatchGeometry G;
+    PwppEvidenceRule R;
+    int32_t occupied_at = 0, free_at = 0;
+    int n_poses = 0, max_rows = 0;
+    size_t map_cells = 0;  // NX * NY * n_maps
+    std::vector<uint32_t> words;
+    size_t at_maps() const { return (size_t)n_poses * 12; }
+};
+
+// the rule's ranges, named: one text with the kernels' launcher (pwpp_evid_rule_check)
+int evidence_rule_args(const pwpp_evidence_rule *rule, PwppEvidenceRule &R) {
+    R = PwppEvidenceRule{rule->gate, rule->min_cells, rule->moving_share, rule->static_share};
+    switch (pwpp_evid_rule_check(R)) {
+        case 1: return fail(PWPP_E_ARG, "gate %d: 0 .. 4 expected", R.gate);
+        case 2: return fail(PWPP_E_ARG, "min_cells %d: at least 1 expected", R.min_cells);
+        case 3: return fail(PWPP_E_ARG, "moving_share %d: 1 .. 256 expected", R.moving_share);
+        case 4: return fail(PWPP_E_ARG, "static_share %d: 1 .. 256 expected", R.static_share);
+        default: return PWPP_OK;
+    }
+}
+
+// What both entry points check from the map's origin on, in the header's order, after the sizes of the images and the map, the
+// grid's flags and its own geometry (frames >= 1; `label` is an output of pwpp_evidence_obstacles).  Fills the plan.  Touches no handle.
+int evidence_args(const pwpp_ground_grid *g, int frames, size_t cells, const int32_t *label, const EvidenceArrays &a, const pwpp_fusion_map *m, int n_maps,
+                  const pwpp_evidence_rule *rule, int max_rows, EvidencePlan &plan) {
+    if (!(m->cell > 0.0) || !std::isfinite(m->cell) || !std::isfinite(m->x0) || !std::isfinite(m->y0))
+        return fail(PWPP_E_ARG, "map origin and cell size must be finite, the cell size positive");
+    if (m->free_at < -32768 || m->free_at >= m->occupied_at || m->occupied_at > 32767)
+        return fail(PWPP_E_ARG, "thresholds free_at %d, occupied_at %d: -32768 <= free_at < occupied_at <= 32767 expected", m->free_at, m->occupied_at);
+    if (const int rc = evidence_rule_args(rule, plan.R)) return rc;
+    if (max_rows < 1) return fail(PWPP_E_ARG, "max_rows %d: at least 1 expected", max_rows);
+    if ((int64_t)frames * max_rows > PWPP_EV_MAX_TOTAL) return fail(PWPP_E_ARG, "%d frames x max_rows %d exceed 2^24", frames, max_rows);
+    if (a.n_poses < 1 || (a.n_poses != 1 && a.n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", a.n_poses, frames);
+    const FrameMaps map_of{a.map_of_frame, n_maps};
+    if (const int rc = map_of.args(frames)) return rc;
+    if ((a.occ_in != nullptr) != (a.occ_out != nullptr))
+        return fail(PWPP_E_ARG, "null %s with %s given: both or neither expected", a.occ_in ? "occupancy_out" : "occupancy_in", a.occ_in ? "occupancy_in" : "occupancy_out");
+    if (const int rc = range_args({{label, cells * 4, "label"}, {a.occ_in, cells, "occupancy_in"}, {a.map, plan.map_cells * sizeof(int16_t), "map"},
+                                   {a.rows, (size_t)frames * (size_t)max_rows * sizeof(pwpp_cluster_evidence), "rows"}, {a.cell_class, cells, "cell_class"},
+                                   {a.occ_out, cells, "occupancy_out"}},
+                                  {{1, 5}}, false))
+        return rc;
+    plan.G = PwppMatchGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
+    pwpp_fuse_reciprocal(m->cell, plan.G.inv_CELL);
+    plan.occupied_at = m->occupied_at, plan.free_at = m->free_at, plan.n_poses = a.n_poses, plan.max_rows = max_rows;
+    try {
+        plan.words.assign(plan.at_maps() + (size_t)frames, 0u);
+    } catch (const std::bad_alloc &) {
+        return fail(PWPP_E_NOMEM, "no host memory for %d poses and %d frames", a.n_poses, frames);
+    }
+    std::memcpy(plan.words.data(), a.pose, (size_t)a.n_poses * 6 * sizeof(double));
+    for (int i = 0; i < frames; ++i) plan.words[plan.at_maps() + (size_t)i] = (uint32_t)map_of(i);
+    return PWPP_OK;
+}
+
+// (after mem: what PWPP_MEM_DEVICE asks of the arrays; the byte images are byte aligned, no more)
+int evidence_alignment_args(int mem, const int32_t *label, const EvidenceArrays &a) {
+    return alignment_args(mem, {{a.rows, 7u, "rows"}, {label, 3u, "label image"}, {a.map, 1u, "map"}});
+}
+
+// (the plan's words first: they move into the staging; `s_label` is the label image's section: the caller's, or the labelling's)
+struct EvidenceSections {
+    int up, label, occ_in, map, rows, cell_class, occ_out;
+};
+EvidenceSections evidence_sections(Staging &st, EvidencePlan &plan, int frames, size_t cells, int s_label, const EvidenceArrays &a) {
+    EvidenceSections s;
+    s.up = st.add_upload(std::move(plan.words));
+    s.label = s_label;
+    s.occ_in = st.add(a.occ_in ? (cells + 3) / 4 : 0, a.occ_in, Staging::kIn, a.occ_in ? cells : 0);
+    s.map = st.add((plan.map_cells + 1) / 2, a.map, Staging::kIn, plan.map_cells * sizeof(int16_t));
+    s.rows = st.add((size_t)frames * (size_t)plan.max_rows * (sizeof(pwpp_cluster_evidence) / 4), a.rows, Staging::kOut);
+    s.cell_class = st.add(a.cell_class ? (cells + 3) / 4 : 0, a.cell_class, Staging::kOut, a.cell_class ? cells : 0);
+    s.occ_out = st.add(a.occ_out ? (cells + 3) / 4 : 0, a.occ_out, Staging::kOut, a.occ_out ? cells : 0);
+    return s;
+}
+int evidence_launch(pwpp_handle *h, const Staging &st, const EvidenceSections &s, const EvidencePlan &plan, int frames, const EvidenceArrays &a) {
+    return pwpp_launch_evidence(&plan.G, &plan.R, plan.occupied_at, plan.free_at, frames, st.dev<const int32_t>(s.label), a.occ_in ? st.dev<const int8_t>(s.occ_in) : nullptr,
+                                st.dev<const double>(s.up), plan.n_poses, st.dev<const int32_t>(s.up) + plan.at_maps(), st.dev<const int16_t>(s.map), plan.max_rows,
+                                st.dev<void>(s.rows), a.cell_class ? st.dev<int8_t>(s.cell_class) : nullptr, a.occ_out ? st.dev<int8_t>(s.occ_out) : nullptr,
+                                h->evidence_path, h->stream);
+}
+}  // namespace
+
+int pwpp_evidence_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int mem, const int32_t *label, const int8_t *occupancy_in, const double *pose, int n_poses,
+                       const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps, const int16_t *map, const pwpp_evidence_rule *rule, int max_rows,
+                       pwpp_cluster_evidence *rows, int8_t *cell_class, int8_t *occupancy_out) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label || !pose || !m || !map || !rule || !rows)
+        return fail(PWPP_E_ARG, "null %s",
+                    !g ? "grid" : (!label ? "label image" : (!pose ? "pose" : (!m ? "map description" : (!map ? "map" : (!rule ? "rule" : "rows"))))));
+    size_t cells = 0;
+    EvidencePlan plan;
+    int rc = image_args(g->nx, g->ny, frames, kEvidenceWho, cells);
+    if (rc || (rc = image_args(m->nx, m->ny, n_maps, kEvidenceWho, plan.map_cells))) return rc;
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the map evidence's frame grid takes 0", g->flags);
+    if ((rc = grid_geometry_args(g))) return rc;
+    const EvidenceArrays a{occupancy_in, pose, n_poses, map_of_frame, map, rows, cell_class, occupancy_out};
+    if ((rc = evidence_args(g, frames, cells, label, a, m, n_maps, rule, max_rows, plan))) return rc;
+    if ((rc = mem_args(mem, kEvidenceWho))) return rc;
+    if ((rc = evidence_alignment_args(mem, label, a))) return rc;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_label = st.add(cells, label, Staging::kIn);
+    const EvidenceSections s = evidence_sections(st, plan, frames, cells, s_label, a);
+    return run_on_image(h, st, [&] { return evidence_launch(h, st, s, plan, frames, a); });
+}
+
+// pwpp_label_obstacles as it stands, its label image kept where it lies, and pwpp_evidence_grid of it, one enqueued sequence.
+int pwpp_evidence_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int connectivity, int frame_first, int frames, int mem,
+                            int32_t *label, int32_t *count, float *top, pwpp_obstacle_cluster *clusters, int32_t *n_clusters, int max_clusters, int32_t *point_cluster,
+                            const int8_t *occupancy_in, const double *pose, int n_poses, const int32_t *map_of_frame, const pwpp_fusion_map *m, int n_maps,
+                            const int16_t *map, const pwpp_evidence_rule *rule, pwpp_cluster_evidence *rows, int8_t *cell_class, int8_t *occupancy_out) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label || !pose || !m || !map || !rule || !rows)
+        return fail(PWPP_E_ARG, "null %s",
+                    !g ? "grid" : (!label ? "label image" : (!pose ? "pose" : (!m ? "map description" : (!map ? "map" : (!rule ? "rule" : "rows"))))));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
+    if ((rc = side_args(g->nx, g->ny, kEvidenceWho))) return rc;
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the map evidence's frame grid takes 0", g->flags);
+    EvidencePlan plan;
+    if ((rc = image_args(m->nx, m->ny, n_maps, kEvidenceWho, plan.map_cells))) return rc;
+    const EvidenceArrays a{occupancy_in, pose, n_poses, map_of_frame, map, rows, cell_class, occupancy_out};
+    if ((rc = evidence_args(g, frames, cells, label, a, m, n_maps, rule, max_clusters, plan))) return rc;
+    if ((rc = evidence_alignment_args(mem, label, a))) return rc;
+    const int64_t base_first = h->h_base.p[frame_first];
+    const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, count, top, label, clusters, n_clusters, max_clusters);
+    const int s_pc = st.add(points, point_cluster, Staging::kOut);
+    const EvidenceSections es = evidence_sections(st, plan, frames, cells, s.label, a);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
+        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, max_clusters);
+        if (lrc == 0 && points != 0) {
+            lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (as pwpp_label_obstacles)
+            if (lrc == 0) lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
+        }
+        return lrc != 0 ? lrc : evidence_launch(h, st, es, plan, frames, a);
+    });
+}
+
+// Host only: the verdict of a row, by the function the kernels use.
+int pwpp_evidence_verdict(const pwpp_evidence_rule *rule, int32_t cells, int32_t landed, int32_t occupied, int32_t free_cells, int32_t *verdict) {
+    if (!rule || !verdict) return fail(PWPP_E_ARG, "null %s", rule ? "verdict" : "rule");
+    PwppEvidenceRule R;
+    if (const int rc = evidence_rule_args(rule, R)) return rc;
+    if (cells < 0 || landed < 0 || occupied < 0 || free_cells < 0 || landed > cells || (int64_t)occupied + (int64_t)free_cells > (int64_t)landed)
+        return fail(PWPP_E_ARG, "counts cells %d, landed %d, occupied %d, free %d: 0 <= occupied + free <= landed <= cells expected", cells, landed, occupied, free_cells);
+    *verdict = pwpp_evid_verdict(R, cells, landed, occupied, free_cells);
+    return PWPP_OK;
 }
 
 // ---- obstacle boxes: the counted points of every label as an oriented box --------------------------------------------------------

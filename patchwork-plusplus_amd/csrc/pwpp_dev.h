@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_tracks.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -353,6 +353,10 @@ size_t pwpp_tracks_work_words(int frames, int max_rows, int max_pairs);
 int pwpp_launch_tracks(const struct PwppFusionGeometry *G, const struct PwppTracksRule *R, int frames, const int32_t *curr, const int32_t *prev, const double *poses,
                        int n_poses, void *curr_links, void *prev_links, int32_t *n_pairs, const int32_t *id_prev, const int32_t *next_id, int32_t *id_curr,
                        int32_t *next_id_out, uint32_t *work, hipStream_t stream);
+// pwpp_evidence.hip
+int pwpp_launch_evidence(const struct PwppMatchGeometry *G, const struct PwppEvidenceRule *R, int occupied_at, int free_at, int frames, const int32_t *label,
+                         const int8_t *occ_in, const double *poses, int n_poses, const int32_t *map_of, const int16_t *map, int max_rows, void *rows,
+                         int8_t *cell_class, int8_t *occ_out, int path, hipStream_t stream);
 // pwpp_match.hip
 size_t pwpp_match_work_words(int nx, int ny, int frames, int n_candidates, int wx, int wy);
 int pwpp_launch_match_grid(const struct PwppMatchGeometry *G, int frames, const int8_t *occupancy, const double *candidates, int n_sets, int n_candidates,

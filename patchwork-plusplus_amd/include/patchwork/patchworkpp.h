@@ -658,6 +658,51 @@ public:
         track_label_.clear(), track_ids_.clear();
         track_next_id_ = 0, track_nx_ = 0;
     }
+    // ... and what a fused obstacle map holds under every cluster (pwpp_evidence_obstacles): the labelling as getObstacleClusters
+    // gives it, and per cluster the cells that land in the map under the pose {a, b, tx, c, d, ty} (map-from-frame, the pose of
+    // updateObstacleMap; the identity: null), counted by the class of the map's largest log-odds within `gate` cells, and the
+    // verdict -- PWPP_EVID_MOVING: at least moving_share / 256 of the landed cells read free; PWPP_EVID_STATIC: at least
+    // static_share / 256 read occupied; PWPP_EVID_UNDECIDED -- rows[r] belongs to clusters[r] and, by the same row, to ids[r] of
+    // trackObstacleClusters.  With `occupancy` (ny x nx bytes, those of getObstacleVisibility) `masked` is those bytes with the
+    // cells of moving clusters set to PWPP_OCC_UNKNOWN: what pwpp_fuse_grid takes so that the map is fused without its movers.
+    // The map is read, not changed; it must have been updated once.
+    struct EvidenceRule {
+        int gate, min_cells, moving_share, static_share;  // 0 .. 4; >= 1; 1 .. 256; 1 .. 256
+        EvidenceRule() : gate(1), min_cells(3), moving_share(192), static_share(192) {}  // (a constructor: as TerrainParams)
+    };
+    struct ObstacleEvidence {
+        int nx = 0, ny = 0;
+        std::vector<int32_t> label;                   // ny x nx, row-major: row iy, column ix
+        std::vector<pwpp_obstacle_cluster> clusters;  // min(count, max_clusters) rows
+        std::vector<pwpp_cluster_evidence> rows;      // one per row of clusters
+        std::vector<int8_t> cell_class;               // ny x nx: the class byte of a labelled, landed cell, PWPP_EVID_CELL_NONE elsewhere
+        std::vector<int8_t> masked;                   // ny x nx with `occupancy`, else empty
+        int count = 0;                                // the true number of clusters
+    };
+    ObstacleEvidence getObstacleEvidence(const FusedObstacleMap &map, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max,
+                                         const double *pose = nullptr, const EvidenceRule &rule = EvidenceRule(), const int8_t *occupancy = nullptr,
+                                         int min_count = 1, int connectivity = 8, int max_clusters = 256) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, 0, 0};
+        const pwpp_fusion_map m = {map.x0, map.y0, map.cell, map.nx, map.ny, map.hit, map.miss, map.l_min, map.l_max, map.occupied_at, map.free_at};
+        const pwpp_evidence_rule r = {rule.gate, rule.min_cells, rule.moving_share, rule.static_share};
+        const double identity[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+        const size_t map_cells = (size_t)(map.nx > 0 ? map.nx : 0) * (size_t)(map.ny > 0 ? map.ny : 0);
+        if (map.log_odds.size() != map_cells || map_cells == 0) throw std::runtime_error("getObstacleEvidence: the map has no log_odds of its nx x ny cells");
+        ObstacleEvidence e;
+        e.nx = nx > 0 ? nx : 0, e.ny = ny > 0 ? ny : 0;
+        const size_t cells = (size_t)e.nx * (size_t)e.ny, rows = (size_t)(max_clusters > 0 ? max_clusters : 0);
+        e.label.assign(cells ? cells : 1, -1), e.clusters.resize(rows ? rows : 1), e.rows.resize(rows ? rows : 1), e.cell_class.resize(cells ? cells : 1);
+        if (occupancy) e.masked.resize(cells ? cells : 1);
+        int32_t n = 0;
+        check(pwpp_evidence_obstacles(h_, &g, h_min, h_max, min_count, connectivity, 0, 1, PWPP_MEM_HOST, e.label.data(), nullptr, nullptr, e.clusters.data(), &n,
+                                      max_clusters, nullptr, occupancy, pose ? pose : identity, 1, nullptr, &m, 1, map.log_odds.data(), &r, e.rows.data(),
+                                      e.cell_class.data(), occupancy ? e.masked.data() : nullptr));
+        e.count = n;
+        const size_t kept = (size_t)(n < max_clusters ? n : max_clusters);
+        e.label.resize(cells), e.cell_class.resize(cells), e.clusters.resize(kept), e.rows.resize(kept);
+        if (occupancy) e.masked.resize(cells);
+        return e;
+    }
 #ifdef PWPP_HAVE_EIGEN
     std::vector<pwpp_ground_sample> queryGround(const Eigen::MatrixX3f &positions) {
         std::vector<float> xyz((size_t)positions.rows() * 3);

@@ -121,6 +121,17 @@ CLUSTER_LINK_DTYPE = np.dtype([("other", "<i4"), ("overlap", "<i4"), ("cells", "
 LINK_NONE, LINK_OVERFLOWED = -1, -2  # `other` of a row without a partner; of every row of a frame with more than max_pairs pairs
 
 
+class EvidenceRule(ctypes.Structure):  # pwpp_evidence_rule (16 bytes): the gate in map cells, the fewest landed cells of a verdict, the two shares in 256ths
+    _fields_ = [("gate", ctypes.c_int32), ("min_cells", ctypes.c_int32), ("moving_share", ctypes.c_int32), ("static_share", ctypes.c_int32)]
+
+
+CLUSTER_EVIDENCE_DTYPE = np.dtype([("sum", "<i8"), ("cells", "<i4"), ("landed", "<i4"), ("occupied", "<i4"), ("free", "<i4"), ("unknown", "<i4"),
+                                   ("verdict", "<i4")])  # pwpp_cluster_evidence (32 bytes)
+EVID_NONE, EVID_UNDECIDED, EVID_STATIC, EVID_MOVING = -1, 0, 1, 2  # PWPP_EVID_*: the verdict of a row
+EVID_CELL_NONE = -2  # PWPP_EVID_CELL_NONE: cell_class of a cell that is not labelled or not landed
+EVID_LDS_ROWS = 512  # PWPP_EVID_LDS_ROWS: the rows the option "evidence_path" = 2 keeps in LDS
+
+
 class MatchBest(ctypes.Structure):  # pwpp_match_best (24 bytes): the winning sum, its candidate (-1: skipped) and shift, the frame's occupied cells
     _fields_ = [("score", ctypes.c_int64), ("candidate", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("cells", ctypes.c_int32)]
 
@@ -261,12 +272,29 @@ def load():
             L.pwpp_associate_grid.argtypes = [vp, gp, gp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
             L.pwpp_track_obstacles.argtypes = [vp, gp, ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp,
                                                vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pwpp_evidence_grid"):  # (as above: an older build has no map evidence)
+            gp, mp, ep = ctypes.POINTER(GroundGrid), ctypes.POINTER(FusionMap), ctypes.POINTER(EvidenceRule)
+            L.pwpp_evidence_grid.argtypes = [vp, gp, ci, ci, vp, vp, vp, ci, vp, mp, ci, vp, ep, ci, vp, vp, vp]
+            L.pwpp_evidence_obstacles.argtypes = [vp, gp, ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp,
+                                                  vp, vp, ci, vp, mp, ci, vp, ep, vp, vp, vp]
+            L.pwpp_evidence_verdict.argtypes = [ep, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
         if hasattr(L, "pwpp_set_input_transforms"):  # (as above: an older build has no input transforms)
             L.pwpp_set_input_transforms.argtypes = [vp, vp, ci]
             L.pwpp_transform_points.argtypes = [vp, vp, ctypes.c_int64, vp]
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
+
+
+def evidence_verdict(rule, cells, landed, occupied, free):
+    """The verdict (EVID_*) of a row with these counts under the rule (an EvidenceRule or its four values): pwpp_evidence_verdict,
+    the function the kernels use, on the host; needs no device."""
+    L = load()
+    r = rule if isinstance(rule, EvidenceRule) else EvidenceRule(*[int(v) for v in rule])
+    v = ctypes.c_int32(0)
+    if L.pwpp_evidence_verdict(ctypes.byref(r), int(cells), int(landed), int(occupied), int(free), ctypes.byref(v)) < 0:
+        raise PwppError(L.pwpp_last_error().decode())
+    return int(v.value)
 
 
 def pinned_empty(shape, dtype=np.float32):
@@ -1069,6 +1097,89 @@ class Handle:
                                                  int(max_clusters), _dp(point_cluster_ptr), _dp(prev_label_ptr), _vp(poses) if poses.size else None, len(poses),
                                                  int(gate), int(min_overlap), int(max_pairs), _dp(curr_links_ptr), _dp(prev_links_ptr), _dp(n_pairs_ptr),
                                                  _dp(id_prev_ptr), _dp(next_id_ptr), _dp(id_curr_ptr), _dp(next_id_out_ptr)))
+
+    @staticmethod
+    def evidence_verdict(rule, cells, landed, occupied, free):
+        """The module's evidence_verdict: the verdict of a row with these counts, on the host."""
+        return evidence_verdict(rule, cells, landed, occupied, free)
+
+    @staticmethod
+    def _evidence_rule(rule):
+        """An EvidenceRule from one, or from (gate, min_cells, moving_share, static_share)."""
+        return rule if isinstance(rule, EvidenceRule) else EvidenceRule(*[int(v) for v in rule])
+
+    def evidence_grid(self, label, grid, pose, fmap, maps, rule, max_rows, occupancy=None, map_of_frame=None, want_class=False, in_place=False):
+        """What the (n_maps, NY, NX) or (NY, NX) int16 log-odds maps described by the FusionMap `fmap` hold under every row of the
+        (frames, ny, nx) or (ny, nx) int32 label images on the grid `grid` = (x0, y0, cell): pose is {a, b, tx, c, d, ty} for
+        every frame or (frames, 6), map-from-frame as in fuse_grid; rule an EvidenceRule or (gate, min_cells, moving_share,
+        static_share); map_of_frame as in fuse_grid.  Works before any estimate call.  Returns the (frames, max_rows)
+        CLUSTER_EVIDENCE_DTYPE rows; with want_class then the int8 class image; with occupancy (int8, the images' shape) then the
+        masked bytes -- written over a copy of `occupancy` itself with in_place.  The rules: include/pwpp.h."""
+        l3 = self._label_images(label, "label")
+        frames = l3.shape[0]
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), l3.shape[2], l3.shape[1], 0, 0)
+        m3 = _maps_image(maps, fmap)
+        poses, mof = _host(pose, np.float64, -1, 6), _host(map_of_frame, np.int32, -1)
+        r = self._evidence_rule(rule)
+        rows = np.zeros((frames, max(int(max_rows), 0)), CLUSTER_EVIDENCE_DTYPE)
+        cls = np.empty(l3.shape, np.int8) if want_class else None
+        occ_in = occ_out = None
+        if occupancy is not None:
+            occ_in = np.array(occupancy, np.int8).reshape(l3.shape)
+            occ_out = occ_in if in_place else np.empty(l3.shape, np.int8)
+        self._check(self._L.pwpp_evidence_grid(self._h, ctypes.byref(g), frames, MEM_HOST, _hp(l3), _hp(occ_in), _hp(poses), len(poses), _hp(mof), ctypes.byref(fmap),
+                                               m3.shape[0], _hp(m3), ctypes.byref(r), int(max_rows), _vp(rows) if rows.size else None, _hp(cls), _hp(occ_out)))
+        out = (rows,) + ((cls,) if want_class else ()) + ((occ_out,) if occupancy is not None else ())
+        return out if len(out) > 1 else rows
+
+    def evidence_grid_device(self, grid, nx, ny, frames, label_ptr, pose, fmap, n_maps, map_ptr, rule, max_rows, rows_ptr, class_ptr=0, occupancy_in_ptr=0,
+                             occupancy_out_ptr=0, map_of_frame=None):
+        """evidence_grid on device memory: addresses of the (frames, ny, nx) int32 label images (4-byte aligned), the (n_maps, NY, NX)
+        int16 maps (2-byte aligned), the (frames, max_rows) rows of 32 bytes (8-byte aligned) and (0: not wanted) the int8 class
+        image and the two int8 occupancy images, which may be one address; pose and map_of_frame stay host arrays.  Enqueued on
+        the handle's stream; complete after synchronize()."""
+        g = GroundGrid(float(grid[0]), float(grid[1]), float(grid[2]), int(nx), int(ny), 0, 0)
+        poses, mof = _host(pose, np.float64, -1, 6), _host(map_of_frame, np.int32, -1)
+        r = self._evidence_rule(rule)
+        self._check(self._L.pwpp_evidence_grid(self._h, ctypes.byref(g), int(frames), MEM_DEVICE, _dp(label_ptr), _dp(occupancy_in_ptr),
+                                               _vp(poses) if poses.size else None, len(poses), _hp(mof), ctypes.byref(fmap), int(n_maps), _dp(map_ptr), ctypes.byref(r),
+                                               int(max_rows), _dp(rows_ptr), _dp(class_ptr), _dp(occupancy_out_ptr)))
+
+    def evidence_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, fmap, maps, rule, pose=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0), min_count=1, connectivity=8,
+                           max_clusters=1, occupancy=None, map_of_frame=None, want_class=False, frame_first=0, frames=None):
+        """label_obstacles and evidence_grid of its label image in one call, for frames of the last estimate call; max_rows is
+        max_clusters.  Returns (label, clusters, n_clusters, rows), then the class image with want_class, then the masked bytes
+        with occupancy."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        shape = self._grid_shape(g, frames)
+        label = np.empty(shape, np.int32)
+        table = np.zeros((shape[0], max(int(max_clusters), 0)), OBSTACLE_CLUSTER_DTYPE)
+        n = np.zeros(max(frames, 1), np.int32)
+        m3 = _maps_image(maps, fmap)
+        poses, mof = _host(pose, np.float64, -1, 6), _host(map_of_frame, np.int32, -1)
+        r = self._evidence_rule(rule)
+        rows = np.zeros((shape[0], max(int(max_clusters), 0)), CLUSTER_EVIDENCE_DTYPE)
+        cls = np.empty(shape, np.int8) if want_class else None
+        occ_in = None if occupancy is None else np.ascontiguousarray(occupancy, np.int8).reshape(shape)
+        occ_out = None if occupancy is None else np.empty(shape, np.int8)
+        self._check(self._L.pwpp_evidence_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity), int(frame_first), frames,
+                                                    MEM_HOST, _hp(label), None, None, _vp(table) if table.size else None, _vp(n), int(max_clusters), None,
+                                                    _hp(occ_in), _hp(poses), len(poses), _hp(mof), ctypes.byref(fmap), m3.shape[0], _hp(m3), ctypes.byref(r),
+                                                    _vp(rows) if rows.size else None, _hp(cls), _hp(occ_out)))
+        return (label, table, n[:shape[0]], rows) + ((cls,) if want_class else ()) + ((occ_out,) if occupancy is not None else ())
+
+    def evidence_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, min_count, connectivity, label_ptr, pose, fmap, n_maps, map_ptr, rule, max_clusters,
+                                  rows_ptr, class_ptr=0, occupancy_in_ptr=0, occupancy_out_ptr=0, count_ptr=0, top_ptr=0, clusters_ptr=0, n_clusters_ptr=0,
+                                  point_cluster_ptr=0, map_of_frame=None, frame_first=0, frames=None):
+        """evidence_obstacles into device memory: addresses as in label_obstacles_device and evidence_grid_device; pose and
+        map_of_frame stay host arrays.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        poses, mof = _host(pose, np.float64, -1, 6), _host(map_of_frame, np.int32, -1)
+        r = self._evidence_rule(rule)
+        self._check(self._L.pwpp_evidence_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(connectivity), int(frame_first), frames,
+                                                    MEM_DEVICE, _dp(label_ptr), _dp(count_ptr), _dp(top_ptr), _dp(clusters_ptr), _dp(n_clusters_ptr), int(max_clusters),
+                                                    _dp(point_cluster_ptr), _dp(occupancy_in_ptr), _vp(poses) if poses.size else None, len(poses), _hp(mof),
+                                                    ctypes.byref(fmap), int(n_maps), _dp(map_ptr), ctypes.byref(r), _dp(rows_ptr), _dp(class_ptr), _dp(occupancy_out_ptr)))
 
     def distance_grid(self, count, min_count=1, max_dist=0, cell=1.0, want_nearest=True, want_metres=True):
         """The exact Euclidean distance of every cell of a (frames, ny, nx) or (ny, nx) int32 count image to the nearest occupied

@@ -161,6 +161,7 @@ PYBIND11_MODULE(pypatchworkpp, m) {
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_cluster, first_cell, cells, points, ix_min, ix_max, iy_min, iy_max, top, sum_ix, sum_iy);
 
     PYBIND11_NUMPY_DTYPE(pwpp_cluster_link, other, overlap, cells, links);
+    PYBIND11_NUMPY_DTYPE(pwpp_cluster_evidence, sum, cells, landed, occupied, free, unknown, verdict);
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_box, points, pad_, mean_x, mean_y, cx, cy, ax, ay, length, width, sigma_long, sigma_short, h_min, h_max, z_min,
                          z_max);
 
@@ -366,6 +367,40 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              py::arg("pose") = std::array<double, 6>{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}}, py::arg("min_count") = 1, py::arg("connectivity") = 8,
              py::arg("max_clusters") = 256, py::arg("gate") = 1, py::arg("min_overlap") = 1)
         .def("resetObstacleTracks", [](PatchWorkpp &s) { s.resetObstacleTracks(); })
+        .def("getObstacleEvidence",
+             [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max,
+                const std::array<double, 6> &pose, int gate, int min_cells, int moving_share, int static_share, py::object occupancy, int min_count,
+                int connectivity, int max_clusters) {
+                 PatchWorkpp::EvidenceRule rule;
+                 rule.gate = gate, rule.min_cells = min_cells, rule.moving_share = moving_share, rule.static_share = static_share;
+                 py::array_t<int8_t, py::array::c_style | py::array::forcecast> occ;
+                 if (!occupancy.is_none()) {
+                     occ = py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(occupancy);
+                     if (!occ || occ.size() != (py::ssize_t)(nx > 0 ? nx : 0) * (py::ssize_t)(ny > 0 ? ny : 0) || occ.size() == 0)
+                         throw std::invalid_argument("getObstacleEvidence: occupancy must hold ny x nx int8 values");
+                 }
+                 const PatchWorkpp::ObstacleEvidence e = s.getObstacleEvidence(map, x0, y0, cell, nx, ny, h_min, h_max, pose.data(), rule,
+                                                                               occupancy.is_none() ? nullptr : occ.data(), min_count, connectivity, max_clusters);
+                 py::array_t<int32_t> label({(py::ssize_t)e.ny, (py::ssize_t)e.nx});
+                 if (!e.label.empty()) std::memcpy(label.mutable_data(), e.label.data(), e.label.size() * sizeof(int32_t));
+                 py::array_t<pwpp_obstacle_cluster> table((py::ssize_t)e.clusters.size());
+                 if (!e.clusters.empty()) std::memcpy(table.mutable_data(), e.clusters.data(), e.clusters.size() * sizeof(pwpp_obstacle_cluster));
+                 py::array_t<pwpp_cluster_evidence> rows((py::ssize_t)e.rows.size());  // a structured array: one field per member
+                 if (!e.rows.empty()) std::memcpy(rows.mutable_data(), e.rows.data(), e.rows.size() * sizeof(pwpp_cluster_evidence));
+                 py::array_t<int8_t> cell_class({(py::ssize_t)e.ny, (py::ssize_t)e.nx});
+                 if (!e.cell_class.empty()) std::memcpy(cell_class.mutable_data(), e.cell_class.data(), e.cell_class.size());
+                 py::object masked = py::none();
+                 if (!occupancy.is_none()) {
+                     py::array_t<int8_t> bytes({(py::ssize_t)e.ny, (py::ssize_t)e.nx});
+                     if (!e.masked.empty()) std::memcpy(bytes.mutable_data(), e.masked.data(), e.masked.size());
+                     masked = bytes;
+                 }
+                 return py::make_tuple(label, table, rows, cell_class, masked, e.count);
+             },
+             py::arg("map"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("pose") = std::array<double, 6>{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}}, py::arg("gate") = 1, py::arg("min_cells") = 3,
+             py::arg("moving_share") = 192, py::arg("static_share") = 192, py::arg("occupancy") = py::none(), py::arg("min_count") = 1,
+             py::arg("connectivity") = 8, py::arg("max_clusters") = 256)
         .def("getGroundPoints", [](PatchWorkpp &s) { return to_numpy(s.groundPointRows()); })
         .def("getNongroundPoints", [](PatchWorkpp &s) { return to_numpy(s.nongroundPointRows()); })
         .def("getGround", [](PatchWorkpp &s) { return to_numpy(s.getGround()); })
