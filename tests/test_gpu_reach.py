@@ -3,7 +3,11 @@ Dijkstra of tests/reach_ref.py, for host and device memory (the byte images at o
 alignment) and for every value of the option "reach_path".  The tiled kernel's tile is PWPP_REACH_TILE_X x _Y cells, read from
 csrc/pwpp_reach.h, and the shapes are written for it: 1 x 1, 1 x N and N x 1, a tile exactly and one cell more or fewer each way, 2 x 2
 and 3 x 3 tiles with ragged edges; 96 x 96 for the corridors, whose paths cross tile borders many times.  References are computed once
-and shared."""
+and shared.
+
+This file stops at 9 tiles and 64 frames: the tiled kernel's dirty bits fit one word of 32 here and a call is one launch.  Frames of 34 to
+257 tiles, whose bits fill 2 to 9 words, and a call of more than 2^22 frames, which is cut into several launches, are in
+tests/test_gpu_reach_large.py."""
 import ctypes
 import functools
 

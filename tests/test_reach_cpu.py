@@ -4,8 +4,12 @@ message and its place in the order -- the range bound exactly at and one past it
 mirror in both flavours; pwpp_grid_cell_of, the raster's cell rule for one position; the properties of the restatement the GPU tests compare against (tests/reach_ref.py): the symmetries of the
 square, monotonicity, max_reach as a mask, from chains, the octile closed form; and the stand-alone program that runs the kernels'
 functions on the host against a brute force of its own (tools/reach_check.cpp), built with the address and undefined-behaviour
-sanitizers where the toolchain has them; the same program evaluates images for the restatement to compare with."""
+sanitizers where the toolchain has them; the same program evaluates images for the restatement to compare with; rr.certify, the
+check of a finished field that the frames too large for a Dijkstra are held to: accepted every result of the Dijkstra, refused every
+kind of wrong field a lost or late dirty mark would leave; and the frames of many tiles of tests/test_gpu_reach_large.py, built here
+and shown on the reference alone to use every tile and to cross the words of the tiled kernel's dirty bits."""
 import ctypes
+import functools
 import os
 import subprocess
 
@@ -416,7 +420,7 @@ def test_reach_program_builds_and_passes(checker):
     r = subprocess.run([str(checker)], capture_output=True, text=True)  # (a stand-alone child process with its own main)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 mismatches" in r.stdout
-    assert int(r.stdout.split("reach_check: ")[1].split(" cases")[0]) >= 3000
+    assert int(r.stdout.split("reach_check: ")[1].split(" cases")[0]) >= 4400   # (the word schedule's frames among them)
 
 
 @pytest.mark.parametrize("case", ["plain", "dist2", "limited", "per_frame"])
@@ -441,3 +445,381 @@ def test_the_restatement_and_the_one_text_agree_byte_for_byte(checker, tmp_path,
     assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
     reached = (want[0] != rr.NONE).sum()
     assert 300 < reached < c.size
+
+
+# ---- a finished field judged without a Dijkstra: rr.certify ----------------------------------------------------------------------
+def gpu_file_cases():
+    """(what, cost, source, params, dist2) for one frame each: every shape, image, source and rule of tests/test_gpu_reach.py."""
+    import test_gpu_reach as G   # (imported here: that file imports this one)
+    N, TX, TY = G.N, TILE_X, TILE_Y
+    for shape in G.SHAPES:
+        cost, src, p, _ = G.shape_case(*shape)
+        for f in range(2):
+            yield "shape %s, frame %d" % (G.shape_ids(shape), f), cost[f], src[f], p, None
+    for kind in ("serpentine", "spiral"):
+        yield kind, G.corridor(kind)[0], (0, 0), G.FREE, None
+    cost = G.field().copy()
+    wall = (TX, TY + 3)
+    cost[wall[1], wall[0]] = 100
+    for src in ((0, 0), (N - 1, 0), (0, N - 1), (N - 1, N - 1), (TX - 1, TY), (TX, TY - 1), (2 * TX, 2 * TY), wall):   # `wall`: a lethal source
+        yield "source %r" % (src,), cost, src, rr.params(base=3, unknown=20), None
+    cost = np.zeros((N, N), np.int8)
+    sx, sy = TX, TY - 1
+    cost[sy - 1:sy + 2, sx - 1:sx + 2] = 100
+    yield "sealed", cost.copy(), (sx, sy), rr.params(base=1), None
+    cost[sy - 1, sx - 1] = 0
+    yield "diagonal gap", cost.copy(), (sx, sy), rr.params(base=1), None
+    cost[sy - 1, sx] = 0
+    yield "edge gap", cost.copy(), (sx, sy), rr.params(base=1), None
+    cost = np.full((N, N), 100, np.int8)
+    cost[TY, 2:N - 2] = 7
+    cost[TY:N - 3, N - 3] = 9
+    cost[N - 4, 5:N - 2] = -1
+    yield "corridor", cost, (2, TY), rr.params(base=4, unknown=11), None
+    cost, src = G.field(), (N // 2, N // 2)
+    for unknown in (-1, 0, 55, 100):
+        yield "unknown %d" % unknown, cost, src, rr.params(base=5, unknown=unknown), None
+    for lethal in (1, int(cost[(cost > 30) & (cost < 60)][0]), 101):
+        yield "lethal %d" % lethal, cost, src, rr.params(base=5, lethal=lethal, unknown=0), None
+    rng = np.random.default_rng(9)
+    d2 = rng.integers(0, 30, cost.shape).astype(np.int32)
+    d2[rng.random(cost.shape) < 0.1] = rr.DIST_BEYOND
+    for clearance2 in (0, 4, 12):
+        yield "clearance2 %d" % clearance2, cost, src, rr.params(base=5, unknown=0, clearance2=clearance2), d2
+    yield "dist2 beyond everywhere", cost, src, rr.params(base=5, unknown=0, clearance2=2 ** 31 - 2), np.full(cost.shape, rr.DIST_BEYOND, np.int32)
+    free = rr.reach(cost, src, rr.params(base=5, unknown=55))[0]
+    values = np.unique(free[free != rr.NONE])
+    v = int(values[len(values) // 3])
+    for limit in (v, v - 1):
+        yield "max_reach %d" % limit, cost, src, rr.params(base=5, unknown=55, max_reach=limit), None
+    for c, base, src in ((0, 1, (0, 0)), (100, 255, (N - 1, N // 2)), (33, 7, (TX, TY))):
+        yield "uniform %d" % c, np.full((N, N), c, np.int8), src, rr.params(base=base, lethal=101), None
+    n, frames = 40, 64
+    rng = np.random.default_rng(12)
+    cost = rr.random_cost(frames, n, n, 90, lethal=0.1, unknown=0.05)
+    for f in range(0, frames, 2):
+        cost[f, n // 2, :] = 100
+        cost[f, n // 2, (7 * f) % n] = 0
+    src = np.stack([rng.integers(0, n, frames), rng.integers(0, n, frames)], axis=1).astype(np.int32)
+    for f in (0, 1, 2, 31, 62, 63):   # per-frame sources
+        yield "frame %d of 64" % f, cost[f], src[f], rr.params(base=2, unknown=30), None
+
+
+def rejected(verdict, near, reach_shape):
+    """`verdict` is a reason and a cell; the cell lies in the rectangle `near` = (x0, y0, x1, y1) or beside it (a wrong value also
+    spoils what its neighbours are offered, and the first cell in index order is named)."""
+    assert verdict is not None, "a wrong field was accepted"
+    reason, (x, y) = verdict
+    assert isinstance(reason, str) and len(reason.strip()) > 10
+    assert near[0] - 1 <= x <= near[2] + 1 and near[1] - 1 <= y <= near[3] + 1, (reason, near)
+    assert 0 <= x < reach_shape[1] and 0 <= y < reach_shape[0]
+
+
+def test_certify_accepts_the_dijkstra_result_of_every_case_of_the_gpu_file_and_the_flat_dijkstra_gives_the_same():
+    seen = 0
+    for what, cost, src, p, d2 in gpu_file_cases():
+        reach, frm = rr.reach(cost, src, p, d2)
+        assert rr.certify(cost, src, p, reach, frm, d2) is None, what
+        assert rr.certify(cost, src, p, reach, None, d2) is None, what
+        flat = rr.reach_flat(cost, src, p, d2)
+        assert flat[0].dtype == flat[1].dtype == np.int32 and flat[0].tobytes() == reach.tobytes() and flat[1].tobytes() == frm.tobytes(), what
+        t = rr.terms_array(cost, src, p, d2)
+        assert t.tolist() == rr.terms(cost, (int(src[0]), int(src[1])), p, d2), what
+        seen += 1
+    assert seen == 64
+
+
+@pytest.fixture(scope="module")
+def open_field():
+    """96 x 96, 3 x 3 tiles: random costs, few walls, the source in the first tile; (cost, source, params, reach, from), never written."""
+    cost = rr.random_cost(1, 3 * TILE_Y, 3 * TILE_X, 31, lethal=0.04, unknown=0.0)[0]
+    src, p = (5, 7), rr.params(base=2)
+    out = (cost,) + rr.reach(cost, src, p)
+    for a in out:
+        a.setflags(write=False)
+    assert (out[1] != rr.NONE).sum() > cost.size * 9 // 10 and rr.certify(cost, src, p, out[1], out[2]) is None
+    return cost, src, p, out[1], out[2]
+
+
+def test_certify_rejects_a_value_one_off_a_wrong_source_and_a_tied_from(open_field):
+    cost, src, p, reach, frm = open_field
+    for x, y in ((50, 40), (TILE_X, TILE_Y), (95, 95), (src[0] + 1, src[1])):
+        assert reach[y, x] not in (0, rr.NONE)
+        for delta in (1, -1):   # (a) raised, (b) lowered
+            bad = reach.copy()
+            bad[y, x] += delta
+            rejected(rr.certify(cost, src, p, bad, frm), (x, y, x, y), reach.shape)
+            rejected(rr.certify(cost, src, p, bad, None), (x, y, x, y), reach.shape)
+    for v in (1, -1, rr.NONE):   # (f) a source that does not hold 0
+        bad = reach.copy()
+        bad[src[1], src[0]] = v
+        verdict = rr.certify(cost, src, p, bad, frm)
+        rejected(verdict, src + src, reach.shape)
+        assert verdict[1] == src and "source" in verdict[0]
+    bad = reach.copy()   # a value on an impassable cell
+    y, x = np.argwhere(cost >= 100)[5]
+    bad[y, x] = 12345
+    rejected(rr.certify(cost, src, p, bad, frm), (x, y, x, y), reach.shape)
+    # (e) a uniform open field: one from moved to another neighbour that ties
+    n, s = 3 * TILE_X, (TILE_X, TILE_Y)
+    flat = np.zeros((n, n), np.int8)
+    q = rr.params(base=3)
+    r, f = rr.reach(flat, s, q)
+    x, y = s[0] + 1, s[1] + 2
+    first, other = (y - 1) * n + x - 1, (y - 1) * n + x   # across the corner and across the edge: 10 b + 14 b = 14 b + 10 b
+    assert f[y, x] == first and r.flat[first] + 7 * 6 == r.flat[other] + 5 * 6 == r[y, x]
+    assert rr.certify(flat, s, q, r, f) is None
+    bad = f.copy()
+    bad[y, x] = other
+    verdict = rr.certify(flat, s, q, r, bad)
+    rejected(verdict, (x, y, x, y), r.shape)
+    assert verdict[1] == (x, y) and "from" in verdict[0]
+    bad = f.copy()
+    bad[s[1], s[0]] = -1   # the source names itself
+    assert rr.certify(flat, s, q, r, bad)[1] == s
+    bad = f.copy()
+    bad[0, 0] = -1         # a reached cell without a from
+    assert rr.certify(flat, s, q, r, bad)[1] == (0, 0)
+
+
+def test_certify_rejects_a_tile_that_was_never_visited_and_a_tile_that_was_not_visited_again(open_field):
+    cost, src, p, reach, frm = open_field
+    x0, y0, x1, y1 = TILE_X, TILE_Y, 2 * TILE_X - 1, 2 * TILE_Y - 1   # the interior tile
+    tile = (slice(y0, y1 + 1), slice(x0, x1 + 1))
+    # (c) a lost dirty bit: the tile keeps its start while its neighbours have their values
+    lost = (reach.copy(), frm.copy())
+    lost[0][tile], lost[1][tile] = rr.NONE, -1
+    rejected(rr.certify(cost, src, p, *lost), (x0, y0, x1, y1), reach.shape)
+    rejected(rr.certify(cost, src, p, lost[0], None), (x0, y0, x1, y1), reach.shape)
+    # (d) values that are real path lengths but not the shortest: the tile as it is with a wall inside it that forces a detour
+    walled = cost.copy()
+    walled[y0 + 10, x0 + 1:x1] = 100
+    walled[y0 + 1:y1 - 8, x0 + 16] = 100
+    assert (walled[tile] != cost[tile]).any() and walled[y0, x0:x1 + 1].tobytes() == cost[y0, x0:x1 + 1].tobytes()
+    detour = rr.reach(walled, src, p)
+    stale = (reach.copy(), frm.copy())
+    stale[0][tile], stale[1][tile] = detour[0][tile], detour[1][tile]
+    assert (stale[0][tile] != reach[tile]).sum() > 100 and (stale[0][tile] >= reach[tile]).all()
+    longer = (stale[0][tile] != reach[tile]) & (stale[0][tile] != rr.NONE)
+    assert longer.sum() > 100, "the wall forces no detour"
+    rejected(rr.certify(cost, src, p, *stale), (x0, y0, x1, y1), reach.shape)
+    rejected(rr.certify(cost, src, p, stale[0], None), (x0, y0, x1, y1), reach.shape)
+    # ... and with the stale values alone, the walls' cells at their true values: every value a real path length of the image itself
+    only = (np.where(detour[0] == rr.NONE, reach, stale[0]), np.where(detour[0] == rr.NONE, frm, stale[1]))
+    assert (only[0][tile] != reach[tile]).sum() > 100
+    rejected(rr.certify(cost, src, p, *only), (x0, y0, x1, y1), reach.shape)
+
+
+def test_certify_rejects_both_sides_of_max_reach(open_field):
+    cost, src, p, reach, frm = open_field
+    values = np.unique(reach[reach != rr.NONE])
+    limit = int(values[len(values) // 2])
+    q = dict(p, max_reach=limit)
+    cut = (np.where(reach <= limit, reach, rr.NONE).astype(np.int32), np.where(reach <= limit, frm, -1).astype(np.int32))
+    assert rr.certify(cost, src, q, *cut) is None and rr.certify(cost, src, p, *cut) is not None
+    inside, outside = np.argwhere((reach <= limit) & (reach > 0)), np.argwhere((reach > limit) & (reach != rr.NONE))
+    for y, x in (inside[0], inside[len(inside) // 2], inside[-1], np.argwhere(reach == limit)[0]):   # (g) d <= limit left unreached
+        bad = (cut[0].copy(), cut[1].copy())
+        bad[0][y, x], bad[1][y, x] = rr.NONE, -1
+        rejected(rr.certify(cost, src, q, *bad), (x, y, x, y), reach.shape)
+    above = np.argwhere(reach == values[len(values) // 2 + 1])[0]
+    for y, x in (outside[0], outside[len(outside) // 2], outside[-1], above):   # (g) d > limit given its true d
+        bad = (cut[0].copy(), cut[1].copy())
+        bad[0][y, x], bad[1][y, x] = reach[y, x], frm[y, x]
+        verdict = rr.certify(cost, src, q, *bad)
+        rejected(verdict, (x, y, x, y), reach.shape)
+        assert verdict[1] == (x, y)   # (nothing is offered to a neighbour: every candidate through it lies above the limit too)
+
+
+# ---- the frames of many tiles that tests/test_gpu_reach_large.py asks the GPU for: built here, and judged here on the reference alone ----
+WORD = 32   # tiles per word of k_reach_tiles' dirty bits
+
+
+def frozen(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+def tile_of(x, y, nx):
+    return (y // TILE_Y) * ((nx + TILE_X - 1) // TILE_X) + x // TILE_X
+
+
+def exercised(cost, src, want, crossings=None, every_boundary=False):
+    """What the issue of the many-tile tests asks of an image before a GPU sees it, on a finished field: every tile holds a reached
+    cell, 3/4 of the cells are reached, and the chain from the dearest cell back to the source, walked tile by tile, passes between the
+    words of the dirty bits -- `crossings` times each way at least, or over every boundary between two words."""
+    ny, nx = cost.shape
+    k = rr.chain(want[0], want[1], src, TILE_X, TILE_Y)
+    tiles = ((nx + TILE_X - 1) // TILE_X) * ((ny + TILE_Y - 1) // TILE_Y)
+    assert k["every_tile"] and 4 * k["reached"] >= 3 * nx * ny, (k["every_tile"], k["reached"])
+    assert k["tiles"][0] == tile_of(src[0], src[1], nx) and len(k["tiles"]) > 1
+    if crossings is not None:
+        assert k["up"] >= crossings and k["down"] >= crossings, (k["up"], k["down"])
+    if every_boundary:
+        w = [q // WORD for q in k["tiles"]]
+        met = {(min(a, b), max(a, b)) for a, b in zip(w, w[1:]) if a != b}
+        assert all(any(lo <= b < hi for lo, hi in met) for b in range((tiles - 1) // WORD)), met
+    return k
+
+
+COMB_SHAPE = (7 * TILE_X - 5, 6 * TILE_Y - 9)   # (nx, ny): 7 x 6 = 42 tiles; the tile above or below lies 7 indices away
+COMB_P = rr.params(base=2)
+# the corners, a cell of tile 32 and one of tile 31 -- the nine first marks fall into both words -- and one of the ragged last tile
+COMB_SOURCES = ((0, 0), (COMB_SHAPE[0] - 1, COMB_SHAPE[1] - 1), (4 * TILE_X + 27, 4 * TILE_Y + 2), (3 * TILE_X + 7, 4 * TILE_Y + 9), (6 * TILE_X + 5, 5 * TILE_Y + 3))
+
+
+@functools.lru_cache(maxsize=None)
+def comb_image():
+    return frozen(rr.comb(COMB_SHAPE[1], COMB_SHAPE[0], 24, 3, 1))[0]
+
+
+@functools.lru_cache(maxsize=None)
+def comb_case(k):
+    """(cost, source, params, (reach, from)) of the two-word image for source k: a Dijkstra (rr.reach_flat; the test below holds it to
+    the heap Dijkstra of rr.reach on these very images), computed once."""
+    cost, src = comb_image(), COMB_SOURCES[k]
+    return cost, src, COMB_P, frozen(*rr.reach_flat(cost, src, COMB_P))
+
+
+STRIPS = {"row": (33 * TILE_X + 1, 3), "column": (3, 33 * TILE_Y + 1), "three_words": (65 * TILE_X + 1, 2)}   # (nx, ny): 34, 34 and 66 tiles
+STRIP_P = rr.params(base=2)
+
+
+def strip_image(kind):
+    nx, ny = STRIPS[kind]
+    c = rr.comb(min(nx, ny), max(nx, ny), 37, 1, 2 + sorted(STRIPS).index(kind))
+    return frozen(np.ascontiguousarray(c.T) if ny > nx else c)[0]
+
+
+def strip_sources(kind):
+    """Either end, and a cell of tile 31 and of tile 32."""
+    nx, ny = STRIPS[kind]
+    along = lambda a: (a, 1) if nx > ny else (1, a)
+    return ((0, 0), (nx - 1, ny - 1), along(31 * TILE_X + 30), along(32 * TILE_X + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def strip_case(kind, k):
+    cost, src = strip_image(kind), strip_sources(kind)[k]
+    return cost, src, STRIP_P, frozen(*rr.reach(cost, src, STRIP_P))
+
+
+@functools.lru_cache(maxsize=None)
+def limited_strip_cases():
+    """The 66-tile strip from a source in tile 32 under the largest max_reach, a value of the field, that leaves the reached cells in at
+    most 4 tiles, and under one less: [(cost, source, params, (reach, from))], the unlimited field masked."""
+    cost, src, p, free = strip_case("three_words", 3)
+    ny, nx = cost.shape
+    yy, xx = np.mgrid[0:ny, 0:nx]
+    tile = tile_of(xx, yy, nx)
+    values = np.unique(free[0][free[0] != rr.NONE])
+    fits = [int(v) for v in values if len(np.unique(tile[free[0] <= v])) <= 4]
+    limit = fits[-1]
+    out = []
+    for lim in (limit, limit - 1):
+        keep = free[0] <= lim
+        want = frozen(np.where(keep, free[0], rr.NONE).astype(np.int32), np.where(keep, free[1], -1).astype(np.int32))
+        out.append((cost, src, dict(p, max_reach=lim), want))
+    return out
+
+
+# (nx, ny): 257 tiles in 9 words.  The frame of the most tiles the entry points accept, 23365 x 65 cells at base 1 (2193 tiles in 69 words),
+# passes the same checks, but k_reach_tiles, one workgroup a frame, needs 53 s a call for a comb of that size (measured on an MI355X):
+# no test for a suite.
+WIDE = (257 * TILE_X - 31, 9)
+WIDE_P = rr.params(base=1)
+WIDE_SOURCES = ((4000, 4), (WIDE[0] - 1, WIDE[1] - 1))   # frame 0, uniform; frame 1, a comb from its far end: the front moves to smaller tile indices
+
+
+@functools.lru_cache(maxsize=None)
+def wide_images():
+    nx, ny = WIDE
+    return frozen(np.stack([np.full((ny, nx), 17, np.int8), rr.comb(ny, nx, 24, 3, 3)]))[0]
+
+
+def octile(nx, ny, src, t):
+    """The field of a uniform open image whose every cell has the term t."""
+    yy, xx = np.mgrid[0:ny, 0:nx]
+    dx, dy = abs(xx - src[0]), abs(yy - src[1])
+    return (2 * t * (5 * np.maximum(dx, dy) + 2 * np.minimum(dx, dy))).astype(np.int32)
+
+
+def test_the_two_word_comb_runs_back_and_forth_across_the_word_boundary():
+    cost = comb_image()
+    nx, ny = COMB_SHAPE
+    assert (nx, ny) == (219, 183) and cost.shape == (ny, nx) and len(COMB_SOURCES) == 5
+    assert [tile_of(x, y, nx) for x, y in COMB_SOURCES] == [0, 41, 32, 31, 41] and tile_of(nx - 1, ny - 1, nx) == 41
+    for k, src in enumerate(COMB_SOURCES):
+        _, _, p, want = comb_case(k)
+        assert cost[src[1], src[0]] < 100
+        found = exercised(cost, src, want, crossings=4)
+        assert found["reached"] == 38457 and found["words"] == [0, 1]
+        assert rr.certify(cost, src, p, *want) is None
+        heap = rr.reach(cost, src, p)
+        assert heap[0].tobytes() == want[0].tobytes() and heap[1].tobytes() == want[1].tobytes()
+    # the nine first marks of the sources in tiles 31 and 32 fall into both words
+    for x, y in COMB_SOURCES[2:4]:
+        marks = {tile_of(x + ex * TILE_X, y + ey * TILE_Y, nx) // WORD for ex in (-1, 0, 1) for ey in (-1, 0, 1)}
+        assert marks == {0, 1}
+
+
+@pytest.mark.parametrize("kind", sorted(STRIPS))
+def test_the_strips_cross_every_word_boundary_from_either_end(kind):
+    nx, ny = STRIPS[kind]
+    tiles = ((nx + TILE_X - 1) // TILE_X) * ((ny + TILE_Y - 1) // TILE_Y)
+    assert tiles == (66 if kind == "three_words" else 34) and (kind != "column" or (nx + TILE_X - 1) // TILE_X == 1)
+    assert [tile_of(x, y, nx) for x, y in strip_sources(kind)] == [0, tiles - 1, 31, 32]
+    for k, src in enumerate(strip_sources(kind)):
+        cost, _, p, want = strip_case(kind, k)
+        assert cost.shape == (ny, nx) and cost[src[1], src[0]] < 100
+        found = exercised(cost, src, want, every_boundary=k < 2)
+        if k == 0:
+            assert found["up"] == (tiles - 1) // WORD and found["down"] == 0 and found["tiles"] == list(range(tiles))
+        if k == 1:   # the front moves to smaller tile indices: every mark waits for the next pass
+            assert found["down"] == (tiles - 1) // WORD and found["up"] == 0 and found["tiles"] == list(range(tiles))[::-1]
+        assert rr.certify(cost, src, p, *want) is None
+    if kind == "row":
+        assert (strip_case(kind, 0)[3][0] != rr.NONE).sum() == 3115
+
+
+def test_max_reach_leaves_most_of_the_66_tiles_unvisited():
+    free = strip_case("three_words", 3)[3]
+    for n, (cost, src, p, want) in enumerate(limited_strip_cases()):
+        ny, nx = cost.shape
+        yy, xx = np.nonzero(want[0] != rr.NONE)
+        used = set(tile_of(xx, yy, nx).tolist())
+        assert 2 <= len(used) <= 4 and tile_of(src[0], src[1], nx) == 32 and 32 in used
+        assert ((want[0] == p["max_reach"]).sum() >= 1) == (n == 0)   # the limit is a value of the field; one less cuts that cell
+        got = rr.reach(cost, src, p)
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()   # the reference prunes, `want` masks
+        assert rr.certify(cost, src, p, *want) is None and rr.certify(cost, src, p, *free) is not None
+    a, b = (c[3][0] for c in limited_strip_cases())
+    assert (a != b).sum() >= 1 and (b[a != b] == rr.NONE).all()
+
+
+def test_the_frames_of_257_tiles_are_exercised_in_every_one():
+    nx, ny = WIDE
+    assert (nx, ny) == (8193, 9) and (nx + TILE_X - 1) // TILE_X == 257 and (257 + WORD - 1) // WORD == 9 and rr.range_ok(WIDE_P["base"], nx, ny)
+    cost = wide_images()
+    # frame 0: uniform, the octile closed form
+    src = WIDE_SOURCES[0]
+    want = rr.reach_flat(cost[0], src, WIDE_P)
+    assert want[0].tobytes() == octile(nx, ny, src, WIDE_P["base"] + 17).tobytes()
+    assert rr.certify(cost[0], src, WIDE_P, *want) is None
+    assert exercised(cost[0], src, want)["reached"] == nx * ny
+    bad = want[0].copy()
+    bad[ny - 1, nx - 1] += 1   # the one cell of the last tile's last row
+    assert rr.certify(cost[0], src, WIDE_P, bad, want[1])[1] == (nx - 1, ny - 1)
+    # frame 1: the comb, by both Dijkstras
+    src = WIDE_SOURCES[1]
+    want = rr.reach(cost[1], src, WIDE_P)
+    flat = rr.reach_flat(cost[1], src, WIDE_P)
+    assert flat[0].tobytes() == want[0].tobytes() and flat[1].tobytes() == want[1].tobytes()
+    assert rr.certify(cost[1], src, WIDE_P, *want) is None
+    found = exercised(cost[1], src, want, every_boundary=True)
+    assert found["words"] == list(range(9)) and sorted(set(found["tiles"])) == list(range(257)) and found["down"] >= 8 and found["hops"] > nx
+    lost = want[0].copy()
+    lost[:, 200 * TILE_X:201 * TILE_X] = rr.NONE   # tile 200 never visited
+    verdict = rr.certify(cost[1], src, WIDE_P, lost, None)
+    assert verdict is not None and 200 * TILE_X - 1 <= verdict[1][0] <= 201 * TILE_X

@@ -3,7 +3,9 @@
 //   * the sweeps of k_reach_sweep, forwards and backwards, in place;
 //   * the tiles of k_reach_tiles: a dirty tile and its clipped halo copied out, relaxed to its fixed point, the changed cells
 //     written back, the neighbours whose halo holds a changed border cell marked -- with small tiles on small images, so that every
-//     image has many, and with the kernel's own tile on larger ones;
+//     image has many, and with the kernel's own tile on larger ones; the dirty set dealt twice, as a flag per tile that is read again
+//     for every tile (relax_tiles) and as the kernel deals it, in words of 32 bits of which a pass walks a copy (relax_words), on frames
+//     of up to 625 tiles (20 words) and, with the kernel's own tile, of 34, 36 and 66 tiles: the two agree byte for byte;
 //   * the sweep bound of every schedule; the from rule; max_reach against the unlimited field masked;
 //   * the range bound at its edge, and the largest candidate it lets the kernels form in uint32.
 // Inputs: random images with lethal and unknown cells, every kind of rule, and adversarial ones (serpentines, diagonal gaps, sealed
@@ -17,6 +19,7 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pwpp_reach.h"
@@ -73,59 +76,112 @@ struct TileView {
     uint32_t t(int dx, int dy) const { return term[at + dy * w + dx]; }
     uint32_t v(int dx, int dy) const { return value[at + dy * w + dx]; }
 };
-int64_t relax_tiles(const Frame &F, const std::vector<uint16_t> &t, std::vector<uint32_t> &v, int tx, int ty) {
-    const int tiles_x = (F.nx + tx - 1) / tx, tiles_y = (F.ny + ty - 1) / ty, w = tx + 2, h = ty + 2;
-    std::vector<char> dirty((size_t)tiles_x * tiles_y, 0);
-    for (int ey = -1; ey <= 1; ++ey)  // the source's tile and the tiles around it: the source's 0 may lie in their halo, and it never changes
-        for (int ex = -1; ex <= 1; ++ex) {
-            const int ux = F.sx / tx + ex, uy = F.sy / ty + ey;
-            if (ux >= 0 && ux < tiles_x && uy >= 0 && uy < tiles_y) dirty[(size_t)uy * tiles_x + ux] = 1;
+// one visit of tile q: the tile and its clipped halo copied out, relaxed to its fixed point, the changed cells written back; `loaded()`
+// is called once the copy is made (where the kernel clears the tile's bit) and `mark(u)` for every neighbour tile whose halo holds a
+// changed border cell.  false: the visit ran past its bound.
+struct TileVisit {
+    const Frame &F;
+    const std::vector<uint16_t> &t;
+    std::vector<uint32_t> &v;
+    int tx, ty, tiles_x, tiles_y, w, h;
+    std::vector<uint16_t> lt;
+    std::vector<uint32_t> lv;
+    TileVisit(const Frame &F_, const std::vector<uint16_t> &t_, std::vector<uint32_t> &v_, int tx_, int ty_)
+        : F(F_), t(t_), v(v_), tx(tx_), ty(ty_), tiles_x((F_.nx + tx_ - 1) / tx_), tiles_y((F_.ny + ty_ - 1) / ty_), w(tx_ + 2), h(ty_ + 2), lt((size_t)w * h), lv((size_t)w * h) {}
+    // the source's tile and the tiles around it: the source's 0 may lie in their halo, and it never changes
+    template <class Mark>
+    void first_marks(Mark mark) const {
+        for (int ey = -1; ey <= 1; ++ey)
+            for (int ex = -1; ex <= 1; ++ex) {
+                const int ux = F.sx / tx + ex, uy = F.sy / ty + ey;
+                if (ux >= 0 && ux < tiles_x && uy >= 0 && uy < tiles_y) mark(uy * tiles_x + ux);
+            }
+    }
+    template <class Loaded, class Mark>
+    bool operator()(int q, Loaded loaded, Mark mark) {
+        const int qx = q % tiles_x, qy = q / tiles_x, x0 = qx * tx, y0 = qy * ty;
+        for (int i = 0; i < w * h; ++i) {
+            const int ly = i / w, lx = i - ly * w, gx = x0 + lx - 1, gy = y0 + ly - 1;
+            const bool in = gx >= 0 && gx < F.nx && gy >= 0 && gy < F.ny;
+            lt[i] = in ? t[(size_t)gy * F.nx + gx] : (uint16_t)0;
+            lv[i] = lt[i] ? v[(size_t)gy * F.nx + gx] : PWPP_REACH_UNREACHED;
         }
-    std::vector<uint16_t> lt((size_t)w * h);
-    std::vector<uint32_t> lv((size_t)w * h);
+        loaded();
+        std::vector<char> mine((size_t)tx * ty, 0);
+        for (int sweep = 1;; ++sweep) {
+            bool changed = false;
+            for (int c = 0; c < tx * ty; ++c) {
+                const int at = (c / tx + 1) * w + c % tx + 1;
+                if (lt[at] == 0) continue;
+                const TileView n{lt.data(), lv.data(), w, at};
+                const uint32_t best = pwpp_reach_best(n, (uint32_t)F.R.max_reach);
+                if (best < lv[at]) lv[at] = best, changed = true, mine[c] = 1;
+            }
+            if (!changed) break;
+            if (sweep > tx * ty + 1) return false;
+        }
+        for (int c = 0; c < tx * ty; ++c) {
+            if (!mine[c]) continue;
+            const int lx = c % tx, ly = c / tx;
+            v[(size_t)(y0 + ly) * F.nx + x0 + lx] = lv[(ly + 1) * w + lx + 1];
+            const int ddx = lx == 0 ? -1 : (lx == tx - 1 ? 1 : 0), ddy = ly == 0 ? -1 : (ly == ty - 1 ? 1 : 0);
+            // (a tile one cell wide or high: the cell is on both borders; the kernel's tile is wider than that)
+            for (int ey = -1; ey <= 1; ++ey)
+                for (int ex = -1; ex <= 1; ++ex) {
+                    const bool bx = ex == 0 || ex == ddx || (tx == 1), by = ey == 0 || ey == ddy || (ty == 1);
+                    if ((ex == 0 && ey == 0) || !bx || !by) continue;
+                    const int ux = qx + ex, uy = qy + ey;
+                    if (ux >= 0 && ux < tiles_x && uy >= 0 && uy < tiles_y) mark(uy * tiles_x + ux);
+                }
+        }
+        return true;
+    }
+};
+
+// a flag per tile, read again for every tile: a mark on a later tile is seen in the same pass, one on an earlier tile in the next
+int64_t relax_tiles(const Frame &F, const std::vector<uint16_t> &t, std::vector<uint32_t> &v, int tx, int ty) {
+    TileVisit visit(F, t, v, tx, ty);
+    std::vector<char> dirty((size_t)visit.tiles_x * visit.tiles_y, 0);
+    const auto mark = [&](int u) { dirty[u] = 1; };
+    visit.first_marks(mark);
     for (int64_t pass = 1;; ++pass) {
         bool any = false;
-        for (int q = 0; q < tiles_x * tiles_y; ++q) {
+        for (int q = 0; q < visit.tiles_x * visit.tiles_y; ++q) {
             if (!dirty[q]) continue;
             any = true;
-            dirty[q] = 0;
-            const int qx = q % tiles_x, qy = q / tiles_x, x0 = qx * tx, y0 = qy * ty;
-            for (int i = 0; i < w * h; ++i) {
-                const int ly = i / w, lx = i - ly * w, gx = x0 + lx - 1, gy = y0 + ly - 1;
-                const bool in = gx >= 0 && gx < F.nx && gy >= 0 && gy < F.ny;
-                lt[i] = in ? t[(size_t)gy * F.nx + gx] : (uint16_t)0;
-                lv[i] = lt[i] ? v[(size_t)gy * F.nx + gx] : PWPP_REACH_UNREACHED;
-            }
-            std::vector<char> mine((size_t)tx * ty, 0);
-            for (int sweep = 1;; ++sweep) {
-                bool changed = false;
-                for (int c = 0; c < tx * ty; ++c) {
-                    const int at = (c / tx + 1) * w + c % tx + 1;
-                    if (lt[at] == 0) continue;
-                    const TileView n{lt.data(), lv.data(), w, at};
-                    const uint32_t best = pwpp_reach_best(n, (uint32_t)F.R.max_reach);
-                    if (best < lv[at]) lv[at] = best, changed = true, mine[c] = 1;
-                }
-                if (!changed) break;
-                if (sweep > tx * ty + 1) return -1;
-            }
-            for (int c = 0; c < tx * ty; ++c) {
-                if (!mine[c]) continue;
-                const int lx = c % tx, ly = c / tx;
-                v[(size_t)(y0 + ly) * F.nx + x0 + lx] = lv[(ly + 1) * w + lx + 1];
-                const int ddx = lx == 0 ? -1 : (lx == tx - 1 ? 1 : 0), ddy = ly == 0 ? -1 : (ly == ty - 1 ? 1 : 0);
-                // (a tile one cell wide or high: the cell is on both borders; the kernel's tile is wider than that)
-                for (int ey = -1; ey <= 1; ++ey)
-                    for (int ex = -1; ex <= 1; ++ex) {
-                        const bool bx = ex == 0 || ex == ddx || (tx == 1), by = ey == 0 || ey == ddy || (ty == 1);
-                        if ((ex == 0 && ey == 0) || !bx || !by) continue;
-                        const int ux = qx + ex, uy = qy + ey;
-                        if (ux >= 0 && ux < tiles_x && uy >= 0 && uy < tiles_y) dirty[(size_t)uy * tiles_x + ux] = 1;
-                    }
-            }
+            if (!visit(q, [&] { dirty[q] = 0; }, mark)) return -1;
         }
         if (!any) return pass;
         if (pass > pwpp_reach_sweep_bound((int64_t)F.nx * F.ny)) return -1;
+    }
+}
+
+// k_reach_tiles' own deal of the dirty set: a bit per tile in words of 32.  Per pass and word a COPY of the word is taken once and
+// its tiles are visited lowest bit first; the visited tile's bit is cleared in the live word after its load; marks are OR-ed into the
+// live words, so one in a later word is seen in this pass and one in the word being walked or an earlier word in the next.  A pass
+// ends after the last word; the run ends with the first pass that found no bit.  `most_words`: the words of the bitmap.
+int64_t relax_words(const Frame &F, const std::vector<uint16_t> &t, std::vector<uint32_t> &v, int tx, int ty, int *most_words = nullptr) {
+    TileVisit visit(F, t, v, tx, ty);
+    const int tiles = visit.tiles_x * visit.tiles_y, words = (tiles + 31) >> 5;
+    if (most_words) *most_words = words;
+    std::vector<uint32_t> dirty((size_t)words, 0u);
+    const auto mark = [&](int u) { dirty[(size_t)(u >> 5)] |= 1u << (u & 31); };
+    visit.first_marks(mark);
+    const int64_t bound = pwpp_reach_sweep_bound((int64_t)F.nx * F.ny);
+    for (int64_t pass = 0;; ++pass) {
+        if (pass >= bound) return -1;
+        bool any = false;
+        for (int w = 0; w < words; ++w) {
+            uint32_t bits = dirty[(size_t)w];
+            while (bits != 0) {
+                const int low = __builtin_ctz(bits), q = (w << 5) + low;
+                bits &= bits - 1;
+                any = true;
+                if (q >= tiles) return -2;  // (a bit beyond the last tile: never set)
+                if (!visit(q, [&] { dirty[(size_t)w] &= ~(1u << low); }, mark)) return -1;
+            }
+        }
+        if (!any) return pass + 1;  // (the passes run, the empty one among them)
     }
 }
 
@@ -243,6 +299,34 @@ void check_frame(const Frame &F) {
     }
 }
 
+// The word schedule against the brute force, against its bound and, byte for byte, against relax_tiles, for every tile size given.
+int g_most_words = 0;
+void check_words(const Frame &F, const std::vector<std::pair<int, int>> &tile_sizes) {
+    ++g_cases;
+    const std::vector<uint16_t> t = terms_of(F);
+    std::vector<int64_t> d;
+    std::vector<int32_t> bf;
+    brute(F, d, bf);
+    std::vector<uint32_t> want((size_t)F.nx * F.ny);
+    for (size_t i = 0; i < want.size(); ++i) want[i] = d[i] == INT64_MAX ? PWPP_REACH_UNREACHED : (uint32_t)d[i];
+    for (const auto &ts : tile_sizes) {
+        std::vector<uint32_t> a = start_of(F), b = a;
+        int words = 0;
+        const int64_t na = relax_tiles(F, t, a, ts.first, ts.second), nb = relax_words(F, t, b, ts.first, ts.second, &words);
+        g_most_words = std::max(g_most_words, words);
+        expect(na > 0 && nb > 0 && nb <= pwpp_reach_sweep_bound((int64_t)F.nx * F.ny), "the word schedule ran past its bound");
+        expect(b == want, "the word schedule's reach differs from the brute force");
+        expect(a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(uint32_t)) == 0, "the word schedule and the flag schedule differ");
+        if (b != want && g_bad < 4)
+            for (size_t i = 0; i < b.size(); ++i)
+                if (b[i] != want[i]) {
+                    std::printf("  words, tile %d x %d, %d x %d, source (%d, %d), cell %zu: %u, brute %u\n", ts.first, ts.second, F.nx, F.ny, F.sx, F.sy, i, b[i], want[i]);
+                    break;
+                }
+        expect(from_of(F, t, b) == bf, "from of the word schedule differs from the brute force");
+    }
+}
+
 Frame random_frame(std::mt19937 &rng, int nx, int ny) {
     Frame F;
     F.nx = nx, F.ny = ny;
@@ -323,6 +407,63 @@ void adversarial_cases() {
         relax_sweeps(F, terms_of(F), v, false);
         expect(v[3] == 2u * 5u * 6u, "a corner was cut");
     }
+}
+
+// walls one cell thick across the image every `pitch` cells, each open for `gap` cells alternately at one end and the other: the path runs
+// the whole image back and forth, through every tile, and on into tiles of smaller index as often as into tiles of larger index
+void comb_walls(Frame &F, int pitch, int gap, bool across_x) {
+    const int along = across_x ? F.nx : F.ny, other = across_x ? F.ny : F.nx;
+    for (int k = 0, p = pitch; p < along - 1; p += pitch, ++k)
+        for (int o = 0; o < other; ++o) {
+            const bool open = k % 2 == 0 ? o >= other - gap : o < gap;
+            const int x = across_x ? p : o, y = across_x ? o : p;
+            if (x == F.sx && y == F.sy) continue;
+            F.cost[(size_t)y * F.nx + x] = (int8_t)(open ? 0 : 100);
+        }
+}
+
+// frames of hundreds of tiles: the dirty bitmap has many words, the source's first marks and a tile's marks fall into two of them
+void word_cases() {
+    std::mt19937 rng(40077);
+    const std::vector<std::pair<int, int>> small = {{2, 2}, {3, 2}};
+    for (int k = 0; k < 48; ++k) {
+        Frame F = random_frame(rng, 20 + (int)(rng() % 31), 20 + (int)(rng() % 31));
+        if (k % 3 != 0) comb_walls(F, 3 + (int)(rng() % 6), 1 + (int)(rng() % 2), k % 3 == 1);
+        if (k % 4 == 0) F.sx = F.nx - 1, F.sy = F.ny - 1;  // the front moves to smaller tile indices: every mark waits a pass
+        check_words(F, small);
+        if (k % 6 == 0) {  // under max_reach most tiles are never visited
+            std::vector<uint32_t> v = start_of(F);
+            relax_sweeps(F, terms_of(F), v, false);
+            std::vector<uint32_t> got;
+            for (uint32_t x : v)
+                if (x != PWPP_REACH_UNREACHED && x > 1) got.push_back(x);
+            if (!got.empty()) {
+                std::sort(got.begin(), got.end());
+                F.R.max_reach = (int32_t)got[got.size() / 4];
+                check_words(F, small);
+            }
+        }
+    }
+    {
+        Frame F = random_frame(rng, 50, 50);  // 625 and 425 tiles
+        comb_walls(F, 4, 1, true);
+        check_words(F, small);
+    }
+    // the kernel's own tile on frames of more than 32 tiles: rows and columns of 34 and 66 tiles from either end, 6 x 6 tiles
+    const std::vector<std::pair<int, int>> own = {{PWPP_REACH_TILE_X, PWPP_REACH_TILE_Y}};
+    const int sides[4][2] = {{33 * PWPP_REACH_TILE_X + 1, 3}, {3, 33 * PWPP_REACH_TILE_Y + 1}, {65 * PWPP_REACH_TILE_X + 1, 2}, {5 * PWPP_REACH_TILE_X + 3, 5 * PWPP_REACH_TILE_Y + 1}};
+    for (int k = 0; k < 4; ++k)
+        for (int end = 0; end < 2; ++end) {
+            if (k == 3 && end == 1) continue;  // (the brute force scans every cell for every cell)
+            Frame F = random_frame(rng, sides[k][0], sides[k][1]);
+            F.R = PwppReachRule{2, 100, 30, 0, 0, 0};
+            F.dist2.clear();
+            for (auto &c : F.cost) c = (int8_t)(rng() % 100);
+            F.sx = end ? F.nx - 1 : 0, F.sy = end ? F.ny - 1 : 0;
+            comb_walls(F, k == 3 ? 24 : 37, k == 3 ? 3 : 1, F.nx >= F.ny);
+            check_words(F, own);
+        }
+    expect(g_most_words > 13, "no frame with more than 13 words of dirty bits");
 }
 
 void range_cases() {
@@ -414,6 +555,7 @@ int main(int argc, char **argv) {
     random_cases();
     adversarial_cases();
     range_cases();
+    word_cases();
     std::printf("reach_check: %ld cases, %ld mismatches\n", g_cases, g_bad);
     return g_bad == 0 ? 0 : 1;
 }
