@@ -1314,6 +1314,102 @@ PWPP_API int pwpp_evidence_obstacles(pwpp_handle *h, const pwpp_ground_grid *g /
 PWPP_API int pwpp_evidence_verdict(const pwpp_evidence_rule *rule, int32_t cells, int32_t landed, int32_t occupied, int32_t free_cells,
                                    int32_t *verdict);
 
+/* ---- costmap: occupancy, inflated obstacle distance and terrain cost folded into one cost byte (pwpp_costmap_grid, pwpp_costmap_obstacles) ----
+ * The layers of a navigation costmap exist as separate images in separate value ranges: the visibility's (or the fusion's) occupancy
+ * byte, the exact dist2 to the nearest obstacle, the terrain's traversability cost.  These calls join them into the one int8 cost
+ * image pwpp_reach_grid takes.  The graded cost near an obstacle -- the inflation -- is DATA, not arithmetic: a table of bytes
+ * indexed by the integer dist2, supplied by the caller (pwpp_costmap_curve builds a common one on the host).  The device gathers
+ * and folds integers, so the costmap is a function of its inputs alone and bit-reproducible.  Cells and frames never influence
+ * each other.
+ *   params    layers: a bit mask, not 0, of PWPP_COSTMAP_OCCUPANCY (1), PWPP_COSTMAP_INFLATION (2), PWPP_COSTMAP_TERRAIN (4);
+ *             occupancy_unknown and terrain_unknown -1 .. 100; unknown_below 1 .. 101; pad_ 0.
+ *   curve     uint8 curve[n_curve], host memory whatever `mem`, copied at the call; 1 <= n_curve <= PWPP_COSTMAP_MAX_CURVE (4097:
+ *             dist2 up to 64^2, a radius of 64 cells); every entry 0 .. 100.  Read only with PWPP_COSTMAP_INFLATION: without it
+ *             curve may be NULL and n_curve 0, and neither is looked at.
+ *   inputs    per cell o (the occupancy byte), t (the terrain byte) and d (dist2), each read only when its layer is enabled.
+ *   occupancy o == PWPP_OCC_OCCUPIED gives 100; o == PWPP_OCC_FREE gives 0; any other byte is unknown, as the fusion reads it.
+ *   inflation (uint32)d < n_curve ? curve[d] : 0.  Never unknown: PWPP_DIST_BEYOND and any negative word read 0.
+ *   terrain   t < 0 is unknown; t > 100 counts as 100; otherwise the value is t.
+ *   unknown   An unknown occupancy value becomes occupancy_unknown if that is >= 0 and otherwise stays unknown; an unknown terrain
+ *             value likewise with terrain_unknown.
+ *   fold      m = the maximum of the known values of the enabled layers, or 0 if none is known.  cost = -1 if some enabled layer
+ *             is still unknown and m < unknown_below; otherwise cost = m.  unknown_below 101: unknown always wins; 100: a lethal
+ *             cell shows through an unknown one; 1: any positive cost does.  cost is in pwpp_reach_grid's input range:
+ *             lethal = 100 blocks the obstacles, `unknown` handles -1.
+ *   why       optional uint8 image: bits 1, 2 and 4 are set for each enabled layer whose known value equals m, when m > 0; bit 8
+ *             (PWPP_COSTMAP_WHY_UNKNOWN) iff some enabled layer stayed unknown.  It does not depend on whether cost came out -1.
+ *   own distances  PWPP_COSTMAP_INFLATION with dist2 == NULL (pwpp_costmap_grid): occupancy must be given and is read for this
+ *             purpose even where PWPP_COSTMAP_OCCUPANCY is not among the layers.  The call widens (o == PWPP_OCC_OCCUPIED) to an
+ *             int32 count image in the cluster buffer and runs pwpp_distance_grid's kernels on it with min_count 1 and max_dist =
+ *             max(1, R), R the least integer with R * R >= n_curve - 1.  The result is byte for byte that of passing the uncapped
+ *             dist2: every value the cap turns into PWPP_DIST_BEYOND exceeds n_curve - 1 and reads 0 either way.  A fused
+ *             map_occupancy becomes a costmap this way without leaving the device (sides <= 32768 as for every distance).
+ *   costmap_obstacles  one enqueued sequence for frames of the LAST estimate call, only the stages the enabled layers need:
+ *             pwpp_rasterize_obstacles (OCCUPANCY or INFLATION); the visibility's byte (OCCUPANCY: origin_xy, n_origins and
+ *             max_range as pwpp_visibility_obstacles takes them, otherwise not read); the distances with the cap above from the
+ *             COUNT image and min_count (INFLATION: what pwpp_distance_obstacles gives with that max_dist; the inflation reads the
+ *             same bytes off the uncapped image); pwpp_rasterize_ground and the terrain's cost alone (TERRAIN: terrain_params as
+ *             pwpp_terrain_ground takes them, NULL allowed otherwise); the fold.  occupancy, dist2 and terrain are written for the
+ *             caller where asked for and their layer ran, kept in the handle's cluster buffer otherwise; each is exactly what the
+ *             stand-alone call gives.  Before any estimate call: PWPP_E_STATE.  The call does not run the reach: pwpp_reach_grid
+ *             on the device cost image right after it, on the same stream with no synchronise between, is the planner's chain.
+ *   mem       PWPP_MEM_HOST: every image is host memory, staged through the handle's cluster buffer; synchronous.
+ *             PWPP_MEM_DEVICE: device memory -- dist2 4-byte aligned, every byte image at any address, each at its own --
+ *             enqueued on the handle's stream, complete after pwpp_synchronize.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order.  pwpp_costmap_grid: a null handle, parameters, cost;
+ *             frames or a side < 1, a side > 32768, nx * ny * frames beyond 2^31; layers, occupancy_unknown, terrain_unknown,
+ *             unknown_below, pad_; with INFLATION a null curve, n_curve outside 1 .. 4097, the first entry above 100; the image
+ *             of an enabled layer that is null -- occupancy (also: INFLATION without dist2), then terrain; two of the caller's
+ *             images overlapping; mem; in PWPP_MEM_DEVICE a dist2 below its alignment.  pwpp_costmap_obstacles: a null handle,
+ *             grid, parameters, cost; the parameters and the curve as above; with OCCUPANCY a null origin, with TERRAIN null
+ *             terrain parameters; frames or a side < 1, a side > 32768, g->flags other than 0 or PWPP_GRID_GROUND_ONLY; with
+ *             OCCUPANCY or INFLATION the height band and min_count; with OCCUPANCY the grid's origin and cell, max_range, the
+ *             count of origins, then the first that is not finite or lies outside the grid; with TERRAIN the terrain parameters
+ *             as pwpp_terrain_ground names them; the overlaps; then what pwpp_rasterize_ground checks -- the grid's origin and
+ *             cell, mem, PWPP_E_STATE before any estimate call, the frame range, the product beyond 2^31 -- and the alignment.
+ *   buffers   The uploaded table (at most 1025 words), the count image and the distance kernels' working image of the own
+ *             distances, the chain's kept images and in PWPP_MEM_HOST the staged images lie in the cluster buffer; counted by
+ *             pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.  pwpp_costmap_grid needs a handle for its stream and this
+ *             buffer only.
+ *   host only pwpp_costmap_cell is the rule for one cell, compiled from the text the kernels are compiled from: o and t are read
+ *             as int8 values, cost and why may each be NULL; the parameters and the curve are checked as above.
+ *             pwpp_costmap_curve fills a common table: cell > 0, 0 <= inscribed <= radius, decay >= 0, all finite, peak 0 .. 99.
+ *             n_curve - 1 is the largest integer d with sqrt((double)d) * cell <= radius, and radius / cell beyond 64 is
+ *             PWPP_E_ARG; curve[d] = 100 where sqrt(d) * cell <= inscribed, otherwise (int)floor(peak * exp(-decay * (sqrt(d) *
+ *             cell - inscribed))), with the C library's exp.  Returns n_curve, or PWPP_E_ARG (capacity < n_curve included).  The
+ *             table it returns is what the device is handed and is the contract; the helper is a convenience.
+ * The same bytes for every mem, alignment and value of the option "costmap_path".  With none of these functions called nothing is
+ * allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_COSTMAP 1
+#define PWPP_COSTMAP_OCCUPANCY 1
+#define PWPP_COSTMAP_INFLATION 2
+#define PWPP_COSTMAP_TERRAIN   4
+#define PWPP_COSTMAP_WHY_UNKNOWN 8
+#define PWPP_COSTMAP_MAX_CURVE 4097
+typedef struct pwpp_costmap_params {   /* 24 bytes */
+    int32_t layers;             /* a mask of PWPP_COSTMAP_OCCUPANCY, _INFLATION, _TERRAIN; not 0 */
+    int32_t occupancy_unknown;  /* -1: an unknown occupancy byte stays unknown; 0 .. 100: it counts as this value */
+    int32_t terrain_unknown;    /* the same for a terrain byte < 0 */
+    int32_t unknown_below;      /* a cell with an unknown layer is -1 unless its maximum reaches this; 1 .. 101 */
+    int32_t pad_[2];            /* 0 */
+} pwpp_costmap_params;
+
+/* any images: needs a handle (stream, buffer), no estimate call -- like pwpp_reach_grid */
+PWPP_API int pwpp_costmap_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *occupancy /* [frames][ny][nx], may be NULL */,
+                               const int8_t *terrain /* same shape, may be NULL */, const int32_t *dist2 /* same shape, may be NULL */,
+                               const pwpp_costmap_params *p, const uint8_t *curve /* host: n_curve entries */, int n_curve,
+                               int8_t *cost /* same shape */, uint8_t *why /* same shape, may be NULL */);
+/* the layers' stages and the fold for frames of the LAST estimate call, one enqueued sequence -- like pwpp_reach_ground */
+PWPP_API int pwpp_costmap_obstacles(pwpp_handle *h, const pwpp_ground_grid *g /* flags: 0 or PWPP_GRID_GROUND_ONLY */, float h_min, float h_max, int min_count,
+                                    const double *origin_xy /* host: n_origins x {x, y}, metres */, int n_origins, int max_range,
+                                    const pwpp_terrain_params *terrain_params, const pwpp_costmap_params *p, const uint8_t *curve, int n_curve,
+                                    int frame_first, int frames, int mem, int8_t *cost, uint8_t *why /* may be NULL */,
+                                    int8_t *occupancy /* may be NULL: kept */, int32_t *dist2 /* may be NULL: kept */, int8_t *terrain /* may be NULL: kept */);
+PWPP_API int pwpp_costmap_cell(const pwpp_costmap_params *p, const uint8_t *curve, int n_curve, int o, int t, int32_t d,
+                               int32_t *cost, uint32_t *why);   /* host only */
+PWPP_API int pwpp_costmap_curve(double cell, double inscribed, double radius, double decay, int peak /* 0 .. 99 */,
+                                uint8_t *curve, int capacity);  /* host only; returns n_curve */
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1460,6 +1556,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         "1": sweeps over the frame's cells in global memory until a sweep changes nothing (the yardstick); "2": the
  *                         frame's tiles of 32 x 32 cells, each relaxed in LDS with a halo of one cell, a tile revisited when a
  *                         neighbour's border changed; "0" (default): what tools/reach_cost.py decided.  The same bytes for every value.
+ *   "costmap_path"        how the costmap's fold is dealt (pwpp_costmap_grid, pwpp_costmap_obstacles): "1": a lane per cell, the inflation
+ *                         curve read from global memory (the yardstick); "2": the curve staged once per workgroup into LDS, four
+ *                         consecutive cells a lane, the byte images as one dword where their address allows; "0" (default): what
+ *                         tools/costmap_cost.py decided -- "2" for a call of 2^24 cells or more, "1" below.  The same bytes for every value.
  *   "match_path"          how the scan match reads the map (pwpp_match_grid, pwpp_match_obstacles): "1": every map read comes from
  *                         global memory (the yardstick of tools/scan_match_cost.py); "2": the rectangle of the map that the
  *                         landings of a (frame, candidate) reach under the window is copied into LDS once per workgroup where it

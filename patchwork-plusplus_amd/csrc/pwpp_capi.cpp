@@ -29,6 +29,7 @@
 #include "pwpp_evidence.h"
 #include "pwpp_fusion.h"
 #include "pwpp_match.h"
+#include "pwpp_costmap.h"
 #include "pwpp_reach.h"
 #include "pwpp_terrain.h"
 #include "pwpp_tracks.h"
@@ -258,6 +259,7 @@ struct pwpp_handle {
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
+    int costmap_path = 0;           // option "costmap_path": 0 = what tools/costmap_cost.py decided (2 from PWPP_COSTMAP_QUADS_FROM_CELLS cells a call, 1 below); 1 = a lane per cell, the curve read from global memory (yardstick); 2 = the curve staged in LDS, four cells a lane
     int reach_path = 0;             // option "reach_path": 0 = what tools/reach_cost.py decided; 1 = sweeps over global memory, a workgroup per frame (yardstick); 2 = the frame's tiles relaxed in LDS, dirty tiles revisited
     int evidence_path = 0;          // option "evidence_path": 0 = what tools/evidence_cost.py decided; 1 = the sums go to the rows with global atomics (yardstick); 2 = a workgroup sums a run of cells in LDS first where the rows fit
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
@@ -2141,6 +2143,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "reach_path=%s: 0, 1 or 2 expected", value);
         h->reach_path = v;
+    } else if (k == "costmap_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "costmap_path=%s: 0, 1 or 2 expected", value);
+        h->costmap_path = v;
     } else if (k == "match_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
@@ -2461,6 +2467,7 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
 // first -- upload sections, copied by Staging::begin() -- then what the call stages) and its launch once (*_launch: the launcher's call alone);
 // an entry point checks its arguments, declares the sections and runs one of four tails: run_on_image, run_on_obstacles, run_on_visibility
 // (further down: the obstacle tail under the visibility operator), run_on_ground (the elevation fusion, the terrain and the reach on the ground raster).
+// The costmap's chain needs both rasters in one staging: it enqueues what run_on_obstacles and run_on_ground enqueue (enqueue_on_*) between one begin() and one end().
 
 // The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
 // From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
@@ -2478,32 +2485,46 @@ int run_on_image(pwpp_handle *h, Staging &st, Op op) {
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
+// What run_on_obstacles enqueues between st.begin() and st.end(): the raster and `op`.  On its own for a call that chains both rasters
+// in one staging (the costmap).
+template <class Op>
+int enqueue_on_obstacles(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int s_count, int s_top,
+                         Op op) {
+    PwppObstacleScan scan;
+    if (const int rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan)) return rc;
+    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), s_top < 0 ? nullptr : st.dev<float>(s_top), nullptr, h->stream);
+    if (lrc == 0) lrc = op(scan);
+    return lrc != 0 ? launch_failed(h, lrc) : PWPP_OK;
+}
+
 // On the obstacle grid: pwpp_rasterize_obstacles into the sections s_count and (-1: none) s_top, then the operator and whatever
 // the entry point appends (`op`: it sees the scan and returns a HIP error code), enqueued as one sequence.
 template <class Op>
 int run_on_obstacles(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int s_count, int s_top,
                      Op op) {
     int rc = st.begin();
-    if (rc) return rc;
-    PwppObstacleScan scan;
-    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
-    int lrc = pwpp_launch_obstacle_raster(&scan, st.dev<int32_t>(s_count), s_top < 0 ? nullptr : st.dev<float>(s_top), nullptr, h->stream);
-    if (lrc == 0) lrc = op(scan);
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    if (rc || (rc = enqueue_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s_count, s_top, op))) return rc;
+    return st.end();
+}
+
+// What run_on_ground enqueues between st.begin() and st.end(), as enqueue_on_obstacles is to run_on_obstacles.
+template <class Op>
+int enqueue_on_ground(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, int frame_first, int frames, int s_height, int s_patch, Op op) {
+    PwppGroundView v;
+    PwppGroundGrid grid;
+    std::memcpy(&grid, g, sizeof(grid));
+    if (const int rc = ground_view(h, v)) return rc;
+    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), s_patch < 0 ? nullptr : st.dev<int32_t>(s_patch), h->stream);
+    if (lrc == 0) lrc = op();
+    return lrc != 0 ? launch_failed(h, lrc) : PWPP_OK;
 }
 
 // On the ground raster: pwpp_rasterize_ground into the sections s_height and (-1: none) s_patch, then `op` (a HIP error code), one sequence.
 template <class Op>
 int run_on_ground(pwpp_handle *h, Staging &st, const pwpp_ground_grid *g, int frame_first, int frames, int s_height, int s_patch, Op op) {
     int rc = st.begin();
-    if (rc) return rc;
-    PwppGroundView v;
-    PwppGroundGrid grid;
-    std::memcpy(&grid, g, sizeof(grid));
-    if ((rc = ground_view(h, v))) return rc;
-    int lrc = pwpp_launch_ground_raster(&v, &grid, frame_first, frames, st.dev<float>(s_height), s_patch < 0 ? nullptr : st.dev<int32_t>(s_patch), h->stream);
-    if (lrc == 0) lrc = op();
-    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+    if (rc || (rc = enqueue_on_ground(h, st, g, frame_first, frames, s_height, s_patch, op))) return rc;
+    return st.end();
 }
 
 // What the operators on the ground raster check first of the frames and the grid, before their own arguments; `who` as in mem_args.
@@ -3435,6 +3456,202 @@ int pwpp_grid_cell_of(const pwpp_ground_grid *g, double x, double y, int32_t *ix
     if (const int rc = frame_cells_of(g, xy, 1, "position", cell)) return rc;
     *ix = cell[0], *iy = cell[1];
     return PWPP_OK;
+}
+
+// ---- costmap: the occupancy byte, the inflated obstacle distance and the terrain's cost byte folded into one cost byte ----------------
+namespace {
+static_assert(sizeof(pwpp_costmap_params) == 24, "pwpp_costmap_params is 24 bytes");
+static_assert(PWPP_COSTMAP_OCCUPANCY == PWPP_COSTMAP_LAYER_OCCUPANCY && PWPP_COSTMAP_INFLATION == PWPP_COSTMAP_LAYER_INFLATION &&
+                  PWPP_COSTMAP_TERRAIN == PWPP_COSTMAP_LAYER_TERRAIN && PWPP_COSTMAP_MAX_CURVE == PWPP_COSTMAP_CURVE_MAX &&
+                  (unsigned)PWPP_COSTMAP_WHY_UNKNOWN == PWPP_COSTMAP_WHY_UNKNOWN_BIT && PWPP_OCC_OCCUPIED == 100 && PWPP_OCC_FREE == 0,
+              "the kernels' values");
+constexpr const char *kCostmapWho = "the costmap takes";
+
+// What every costmap function checks of the parameters and the curve, in the header's order; fills the rule.  Touches no handle.
+int costmap_param_args(const pwpp_costmap_params *p, const uint8_t *curve, int n_curve, PwppCostmapRule &rule) {
+    const int32_t all = PWPP_COSTMAP_OCCUPANCY | PWPP_COSTMAP_INFLATION | PWPP_COSTMAP_TERRAIN;
+    if (p->layers == 0 || (p->layers & ~all)) return fail(PWPP_E_ARG, "layers %d: a mask of 1 (occupancy), 2 (inflation) and 4 (terrain) expected, not 0", p->layers);
+    if (p->occupancy_unknown < -1 || p->occupancy_unknown > 100) return fail(PWPP_E_ARG, "occupancy_unknown %d: -1 (stays unknown) .. 100 expected", p->occupancy_unknown);
+    if (p->terrain_unknown < -1 || p->terrain_unknown > 100) return fail(PWPP_E_ARG, "terrain_unknown %d: -1 (stays unknown) .. 100 expected", p->terrain_unknown);
+    if (p->unknown_below < 1 || p->unknown_below > 101) return fail(PWPP_E_ARG, "unknown_below %d: 1 .. 101 expected (101: unknown always wins)", p->unknown_below);
+    if (p->pad_[0] != 0 || p->pad_[1] != 0) return fail(PWPP_E_ARG, "pad_ {%d, %d} of the costmap parameters: 0 expected", p->pad_[0], p->pad_[1]);
+    rule = PwppCostmapRule{p->layers, p->occupancy_unknown, p->terrain_unknown, p->unknown_below, 0};
+    if (!(p->layers & PWPP_COSTMAP_INFLATION)) return PWPP_OK;
+    if (!curve) return fail(PWPP_E_ARG, "null curve with the inflation layer");
+    if (n_curve < 1 || n_curve > PWPP_COSTMAP_MAX_CURVE) return fail(PWPP_E_ARG, "n_curve %d: 1 .. 4097 expected", n_curve);
+    for (int i = 0; i < n_curve; ++i)
+        if (curve[i] > 100) return fail(PWPP_E_ARG, "curve entry %d is %d: 0 .. 100 expected", i, (int)curve[i]);
+    rule.n_curve = n_curve;
+    return PWPP_OK;
+}
+
+// the table as the kernels read it: whole words, the bytes behind n_curve 0 (no words without the inflation layer)
+void costmap_curve_words(const PwppCostmapRule &rule, const uint8_t *curve, std::vector<uint32_t> &words) {
+    words.assign(((size_t)rule.n_curve + 3) / 4, 0u);
+    if (rule.n_curve > 0) std::memcpy(words.data(), curve, (size_t)rule.n_curve);
+}
+
+// (the table first; `occ`, `terrain`, `dist2`: the sections of the layers' images -- the caller's, or a stage's)
+struct CostmapSections {
+    int curve, occ, terrain, dist2, cost, why;
+};
+CostmapSections costmap_sections(Staging &st, size_t cells, const PwppCostmapRule &rule, const uint8_t *curve, int s_occ, int s_terrain, int s_dist2, int8_t *cost,
+                                 uint8_t *why) {
+    CostmapSections s;
+    std::vector<uint32_t> words;
+    costmap_curve_words(rule, curve, words);
+    s.curve = rule.n_curve > 0 ? st.add_upload(std::move(words)) : st.add(0, nullptr, Staging::kKept);
+    s.occ = s_occ, s.terrain = s_terrain, s.dist2 = s_dist2;
+    s.cost = st.add((cells + 3) / 4, cost, Staging::kOut, cells);
+    s.why = st.add(why ? (cells + 3) / 4 : 0, why, Staging::kOut, why ? cells : 0);
+    return s;
+}
+int costmap_launch(pwpp_handle *h, const Staging &st, const CostmapSections &s, const PwppCostmapRule &rule, size_t cells) {
+    return pwpp_launch_costmap(&rule, cells, (rule.layers & PWPP_COSTMAP_OCCUPANCY) ? st.dev<const int8_t>(s.occ) : nullptr,
+                               (rule.layers & PWPP_COSTMAP_TERRAIN) ? st.dev<const int8_t>(s.terrain) : nullptr,
+                               (rule.layers & PWPP_COSTMAP_INFLATION) ? st.dev<const int32_t>(s.dist2) : nullptr,
+                               rule.n_curve > 0 ? st.dev<const uint32_t>(s.curve) : nullptr, st.dev<int8_t>(s.cost), st.dev<uint8_t>(s.why), h->costmap_path, h->stream);
+}
+
+// The sections of the distances a costmap call computes: the kernels' working image, the count (kept, unless `s_count` names the
+// raster's) and dist2 -- the caller's where given, else kept.
+DistanceSections costmap_distance_sections(Staging &st, int nx, int ny, int frames, size_t cells, int s_count, int32_t *dist2) {
+    DistanceSections s;
+    s.work = st.add(pwpp_distance_work_words(nx, ny, frames), nullptr, Staging::kKept);
+    s.count = s_count >= 0 ? s_count : st.add(cells, nullptr, Staging::kKept);
+    s.dist2 = dist2 ? st.add(cells, dist2, Staging::kOut) : st.add(cells, nullptr, Staging::kKept);
+    s.nearest = s.metres = st.add(0, nullptr, Staging::kOut);  // (outputs nobody asks for: null pointers)
+    return s;
+}
+}  // namespace
+
+int pwpp_costmap_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *occupancy, const int8_t *terrain, const int32_t *dist2,
+                      const pwpp_costmap_params *p, const uint8_t *curve, int n_curve, int8_t *cost, uint8_t *why) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!p || !cost) return fail(PWPP_E_ARG, "null %s", !p ? "costmap parameters" : "cost image");
+    size_t cells = 0;
+    int rc = image_args(nx, ny, frames, kCostmapWho, cells);
+    if (rc) return rc;
+    PwppCostmapRule rule;
+    if ((rc = costmap_param_args(p, curve, n_curve, rule))) return rc;
+    const bool inflate = (rule.layers & PWPP_COSTMAP_INFLATION) != 0, own_distances = inflate && !dist2;
+    if (!occupancy && ((rule.layers & PWPP_COSTMAP_OCCUPANCY) || own_distances))
+        return fail(PWPP_E_ARG, "null occupancy image %s", (rule.layers & PWPP_COSTMAP_OCCUPANCY) ? "with the occupancy layer" : "with the inflation layer and no dist2 image");
+    if (!terrain && (rule.layers & PWPP_COSTMAP_TERRAIN)) return fail(PWPP_E_ARG, "null terrain image with the terrain layer");
+    if ((rc = range_args({{occupancy, cells, "occupancy"}, {terrain, cells, "terrain"}, {dist2, cells * 4, "dist2"}, {cost, cells, "cost"}, {why, cells, "why"}}, {}, false)))
+        return rc;
+    if ((rc = mem_args(mem, kCostmapWho))) return rc;
+    if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}}))) return rc;
+    const size_t byte_words = (cells + 3) / 4;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    // (an image whose layer is off is not read: it is not staged either)
+    if (!(rule.layers & PWPP_COSTMAP_OCCUPANCY) && !own_distances) occupancy = nullptr;
+    if (!(rule.layers & PWPP_COSTMAP_TERRAIN)) terrain = nullptr;
+    const int s_occ = st.add(occupancy ? byte_words : 0, occupancy, Staging::kIn, occupancy ? cells : 0);
+    const int s_terrain = st.add(terrain ? byte_words : 0, terrain, Staging::kIn, terrain ? cells : 0);
+    DistanceSections d{};
+    if (own_distances) d = costmap_distance_sections(st, nx, ny, frames, cells, -1, nullptr);
+    else d.dist2 = st.add(dist2 && inflate ? cells : 0, inflate ? dist2 : nullptr, Staging::kIn);
+    const CostmapSections s = costmap_sections(st, cells, rule, curve, s_occ, s_terrain, d.dist2, cost, why);
+    return run_on_image(h, st, [&] {
+        if (own_distances) {
+            int lrc = pwpp_launch_costmap_occupied(cells, st.dev<const int8_t>(s_occ), st.dev<int32_t>(d.count), h->stream);
+            if (lrc == 0) lrc = distance_launch(h, st, d, nx, ny, frames, 1, pwpp_costmap_cap(rule.n_curve), 1.0);
+            if (lrc != 0) return lrc;
+        }
+        return costmap_launch(h, st, s, rule, cells);
+    });
+}
+
+// The stages the enabled layers need -- obstacle raster, visibility, distances, ground raster, the terrain's cost -- and the fold, one enqueued sequence.
+int pwpp_costmap_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins,
+                           int max_range, const pwpp_terrain_params *tp, const pwpp_costmap_params *p, const uint8_t *curve, int n_curve, int frame_first,
+                           int frames, int mem, int8_t *cost, uint8_t *why, int8_t *occupancy, int32_t *dist2, int8_t *terrain) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !p || !cost) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!p ? "costmap parameters" : "cost image"));
+    PwppCostmapRule rule;
+    int rc = costmap_param_args(p, curve, n_curve, rule);
+    if (rc) return rc;
+    const bool with_occ = (rule.layers & PWPP_COSTMAP_OCCUPANCY) != 0, inflate = (rule.layers & PWPP_COSTMAP_INFLATION) != 0,
+               with_terrain = (rule.layers & PWPP_COSTMAP_TERRAIN) != 0;
+    if (with_occ && !origin_xy) return fail(PWPP_E_ARG, "null origin with the occupancy layer");
+    if (with_terrain && !tp) return fail(PWPP_E_ARG, "null terrain parameters with the terrain layer");
+    if ((rc = ground_first_args(g, frames, kCostmapWho))) return rc;
+    if (with_occ || inflate) {
+        if ((rc = obstacle_band_args(g, h_min, h_max)) || (rc = min_count_args(min_count))) return rc;
+    }
+    std::vector<int32_t> org;
+    if (with_occ && (rc = visibility_origin_args(g, h_min, h_max, min_count, origin_xy, n_origins, max_range, frames, org))) return rc;
+    // (a layer that is off runs no stage: its image is not written, and its pointer is not looked at)
+    if (!with_occ) occupancy = nullptr;
+    if (!inflate) dist2 = nullptr;
+    if (!with_terrain) terrain = nullptr;
+    PwppTerrainRule terrain_rule;
+    size_t cells = (size_t)g->nx * (size_t)g->ny * (size_t)frames;  // (as in pwpp_terrain_ground: fits 64 bits; ground_grid_args names one beyond 2^31)
+    if (with_terrain && (rc = terrain_args(tp, g->cell, cells, nullptr, nullptr, nullptr, nullptr, nullptr, terrain, terrain_rule))) return rc;
+    if ((rc = range_args({{occupancy, cells, "occupancy"}, {terrain, cells, "terrain"}, {dist2, cells * 4, "dist2"}, {cost, cells, "cost"}, {why, cells, "why"}}, {}, false)))
+        return rc;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}}))) return rc;
+    const size_t byte_words = (cells + 3) / 4;
+    const int nx = g->nx, ny = g->ny;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    VisibilitySections v{};
+    DistanceSections d{};
+    TerrainSections t{};
+    v.count = -1;
+    if (with_occ) v = visibility_sections(h, st, nx, ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
+    if (inflate) d = costmap_distance_sections(st, nx, ny, frames, cells, v.count, dist2);
+    if (with_terrain) {
+        const int s_height = add_image(st, cells, nullptr, true);
+        const int none = st.add(0, nullptr, Staging::kOut);  // (the outputs of the terrain analysis that nobody asks for: null pointers)
+        const int s_cost = terrain ? st.add(byte_words, terrain, Staging::kOut, cells) : st.add(byte_words, nullptr, Staging::kKept);
+        t = TerrainSections{s_height, none, none, none, none, s_cost};
+    }
+    const CostmapSections s = costmap_sections(st, cells, rule, curve, v.occ, t.cost, d.dist2, cost, why);
+    if ((rc = st.begin())) return rc;
+    if (with_occ || inflate)
+        rc = enqueue_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, inflate ? d.count : v.count, -1, [&](const PwppObstacleScan &) {
+            const int lrc = with_occ ? visibility_launch(h, st, v, nx, ny, frames, min_count, org, max_range) : 0;
+            return lrc != 0 || !inflate ? lrc : distance_launch(h, st, d, nx, ny, frames, min_count, pwpp_costmap_cap(rule.n_curve), g->cell);
+        });
+    if (rc == PWPP_OK && with_terrain)
+        rc = enqueue_on_ground(h, st, g, frame_first, frames, t.height, -1, [&] { return terrain_launch(h, st, t, terrain_rule, nx, ny, frames); });
+    if (rc) return rc;
+    const int lrc = costmap_launch(h, st, s, rule, cells);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// The rule for one cell on the host: pwpp_costmap_fold, the function the kernels call.
+int pwpp_costmap_cell(const pwpp_costmap_params *p, const uint8_t *curve, int n_curve, int o, int t, int32_t d, int32_t *cost, uint32_t *why) {
+    if (!p) return fail(PWPP_E_ARG, "null costmap parameters");
+    PwppCostmapRule rule;
+    if (const int rc = costmap_param_args(p, curve, n_curve, rule)) return rc;
+    int32_t c;
+    uint32_t w;
+    pwpp_costmap_fold(rule, curve, (int)(int8_t)o, (int)(int8_t)t, d, c, w);
+    if (cost) *cost = c;
+    if (why) *why = w;
+    return PWPP_OK;
+}
+
+// A common inflation table: 100 inside the inscribed radius, then peak * exp(-decay * (distance - inscribed)) down to `radius`.
+int pwpp_costmap_curve(double cell, double inscribed, double radius, double decay, int peak, uint8_t *curve, int capacity) {
+    if (!curve) return fail(PWPP_E_ARG, "null curve");
+    if (!(cell > 0.0) || !std::isfinite(cell)) return fail(PWPP_E_ARG, "cell size %g: finite and positive expected", cell);
+    if (!(inscribed >= 0.0) || !(radius >= inscribed) || !std::isfinite(radius))
+        return fail(PWPP_E_ARG, "inscribed %g and radius %g: 0 <= inscribed <= radius expected, both finite", inscribed, radius);
+    if (!(decay >= 0.0) || !std::isfinite(decay)) return fail(PWPP_E_ARG, "decay %g: finite and at least 0 expected", decay);
+    if (peak < 0 || peak > 99) return fail(PWPP_E_ARG, "peak %d: 0 .. 99 expected", peak);
+    int n = 1;  // (d = 0 is always inside: 0 <= radius)
+    while (n <= PWPP_COSTMAP_MAX_CURVE && std::sqrt((double)n) * cell <= radius) ++n;  // (sqrt(d) * cell rises with d: the first d outside ends the table)
+    if (n > PWPP_COSTMAP_MAX_CURVE) return fail(PWPP_E_ARG, "radius %g with cells of %g: the curve would have more than 4097 entries", radius, cell);
+    if (capacity < n) return fail(PWPP_E_ARG, "capacity %d: the curve has %d entries", capacity, n);
+    for (int d = 0; d < n; ++d) {
+        const double r = std::sqrt((double)d) * cell;
+        curve[d] = r <= inscribed ? (uint8_t)100 : (uint8_t)(int)std::floor((double)peak * std::exp(-decay * (r - inscribed)));
+    }
+    return n;
 }
 
 // ---- cluster tracks: the rows of a current label image against those of the previous one, and ids that persist ------------------------

@@ -348,6 +348,10 @@ int pwpp_launch_terrain(const struct PwppTerrainRule *R, int nx, int ny, int fra
 size_t pwpp_reach_work_words(int nx, int ny, int frames);
 int pwpp_launch_reach(const struct PwppReachRule *R, int nx, int ny, int frames, const int8_t *cost, const int32_t *dist2, int sx, int sy,
                       const int32_t *sources, int32_t *reach, int32_t *from, uint16_t *term, uint32_t *flag, int path, hipStream_t stream);
+// pwpp_costmap.hip
+int pwpp_launch_costmap_occupied(size_t cells, const int8_t *occupancy, int32_t *count, hipStream_t stream);
+int pwpp_launch_costmap(const struct PwppCostmapRule *R, size_t cells, const int8_t *occupancy, const int8_t *terrain, const int32_t *dist2,
+                        const uint32_t *curve_words, int8_t *cost, uint8_t *why, int path, hipStream_t stream);
 // pwpp_tracks.hip
 size_t pwpp_tracks_work_words(int frames, int max_rows, int max_pairs);
 int pwpp_launch_tracks(const struct PwppFusionGeometry *G, const struct PwppTracksRule *R, int frames, const int32_t *curr, const int32_t *prev, const double *poses,

@@ -566,6 +566,63 @@ public:
         check(pwpp_reach_grid(h_, map.nx, map.ny, 1, PWPP_MEM_HOST, cost.data(), nullptr, &rp, source, 1, r.reach.data(), r.from.data()));
         return reach_sized(r);
     }
+    // ... and the one cost image a planner takes (pwpp_costmap_obstacles, pwpp_costmap_grid): per cell the largest of the occupancy byte's
+    // value (occupied 100, free 0), the inflation curve[dist2] to the nearest obstacle -- a table of bytes 0 .. 100 indexed by the
+    // squared distance in cells, at most PWPP_COSTMAP_MAX_CURVE entries (inflationCurve builds a common one) -- and the terrain's cost
+    // byte; -1 where an enabled layer is unknown and the largest known value is below unknown_below.  why: bits 1, 2, 4 for the
+    // layers that set the cost, 8 where a layer stayed unknown.  The image is what getReach's field would be computed on.
+    struct CostmapParams {
+        int layers;                                               // a mask of PWPP_COSTMAP_OCCUPANCY, _INFLATION, _TERRAIN
+        int occupancy_unknown, terrain_unknown, unknown_below;    // -1 (stays unknown) .. 100, twice; 1 .. 101
+        CostmapParams() : layers(7), occupancy_unknown(-1), terrain_unknown(-1), unknown_below(101) {}  // (a constructor: as TerrainParams)
+    };
+    struct Costmap {
+        int nx = 0, ny = 0;
+        std::vector<int8_t> cost;  // ny x nx, row-major: row iy, column ix
+        std::vector<uint8_t> why;  // same shape
+    };
+    // (the table of pwpp_costmap_curve: 100 up to `inscribed` metres, then floor(peak * exp(-decay * (distance - inscribed))) up to `radius`)
+    static std::vector<uint8_t> inflationCurve(double cell, double inscribed, double radius, double decay, int peak = 99) {
+        std::vector<uint8_t> curve(PWPP_COSTMAP_MAX_CURVE);
+        const int n = pwpp_costmap_curve(cell, inscribed, radius, decay, peak, curve.data(), (int)curve.size());
+        check(n);
+        curve.resize((size_t)n);
+        return curve;
+    }
+    // (on the last frame over the grid (x0, y0, cell, nx, ny): its visibility bytes, obstacle distances and terrain cost, as the layers ask)
+    Costmap getCostmap(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, const std::vector<uint8_t> &curve,
+                       const CostmapParams &params = CostmapParams(), const TerrainParams &terrain_params = TerrainParams(), int min_count = 1,
+                       int max_range = 0, double origin_x = 0.0, double origin_y = 0.0, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        const pwpp_terrain_params tp = {terrain_params.radius, terrain_params.min_known, terrain_params.step_max, terrain_params.slope_max, terrain_params.rough_max, 0};
+        const pwpp_costmap_params cp = {params.layers, params.occupancy_unknown, params.terrain_unknown, params.unknown_below, {0, 0}};
+        const double origin[2] = {origin_x, origin_y};
+        Costmap c = costmap_images(nx, ny);
+        check(pwpp_costmap_obstacles(h_, &g, h_min, h_max, min_count, origin, 1, max_range, &tp, &cp, curve.empty() ? nullptr : curve.data(), (int)curve.size(), 0, 1,
+                                     PWPP_MEM_HOST, c.cost.data(), c.why.data(), nullptr, nullptr, nullptr));
+        return costmap_sized(c);
+    }
+    // (on a fused obstacle map's bytes -- the distances are computed from them on the device -- and, where given, the terrain cost of
+    // the mean of a fused elevation map on the SAME grid)
+    Costmap fusedCostmap(const FusedObstacleMap &map, const FusedElevationMap *elevation, const std::vector<uint8_t> &curve,
+                         const CostmapParams &params = CostmapParams(), const TerrainParams &terrain_params = TerrainParams()) {
+        const pwpp_terrain_params tp = {terrain_params.radius, terrain_params.min_known, terrain_params.step_max, terrain_params.slope_max, terrain_params.rough_max, 0};
+        const pwpp_costmap_params cp = {params.layers, params.occupancy_unknown, params.terrain_unknown, params.unknown_below, {0, 0}};
+        Costmap c = costmap_images(map.nx, map.ny);
+        const size_t cells = (size_t)c.nx * (size_t)c.ny;
+        if (map.occupancy.size() != cells || map.occupancy.empty()) throw std::invalid_argument("fusedCostmap: the map has no occupancy image of ny x nx cells");
+        std::vector<int8_t> terrain;
+        if (elevation) {
+            if (elevation->x0 != map.x0 || elevation->y0 != map.y0 || elevation->cell != map.cell || elevation->nx != map.nx || elevation->ny != map.ny)
+                throw std::invalid_argument("fusedCostmap: the elevation map's grid is not the obstacle map's");
+            if (elevation->mean.size() != cells) throw std::invalid_argument("fusedCostmap: the elevation map has no mean image of ny x nx cells");
+            terrain.resize(cells);
+            check(pwpp_terrain_grid(h_, map.nx, map.ny, 1, map.cell, PWPP_MEM_HOST, elevation->mean.data(), &tp, nullptr, nullptr, nullptr, nullptr, terrain.data()));
+        }
+        check(pwpp_costmap_grid(h_, map.nx, map.ny, 1, PWPP_MEM_HOST, map.occupancy.data(), elevation ? terrain.data() : nullptr, nullptr, &cp,
+                                curve.empty() ? nullptr : curve.data(), (int)curve.size(), c.cost.data(), c.why.data()));
+        return costmap_sized(c);
+    }
     // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},
     // the prior first) and every shift of [-wx, wx] x [-wy, wy] map cells, the sum of log_odds under the occupied cells of the
     // frame's visibility bytes; the best by the contract's order, and `pose`, the winning candidate moved by the winning shift
@@ -777,6 +834,19 @@ private:
         const size_t cells = (size_t)r.nx * (size_t)r.ny;
         r.reach.resize(cells), r.from.resize(cells);
         return r;
+    }
+    // (the two images of a costmap call, with room for one cell where the grid has none, as terrain_images)
+    static Costmap costmap_images(int nx, int ny) {
+        Costmap c;
+        c.nx = nx > 0 ? nx : 0, c.ny = ny > 0 ? ny : 0;
+        const size_t cells = (size_t)c.nx * (size_t)c.ny, room = cells ? cells : 1;
+        c.cost.assign(room, -1), c.why.assign(room, 0);
+        return c;
+    }
+    static Costmap &costmap_sized(Costmap &c) {
+        const size_t cells = (size_t)c.nx * (size_t)c.ny;
+        c.cost.resize(cells), c.why.resize(cells);
+        return c;
     }
 #ifdef PWPP_HAVE_EIGEN
     static Eigen::MatrixX3f to_eigen(const Cloud &c) {

@@ -113,6 +113,16 @@ class ReachParams(ctypes.Structure):  # pwpp_reach_params (24 bytes): the cost o
 REACH_NONE = 0x7FFFFFFF  # PWPP_REACH_NONE: no path from the source
 
 
+class CostmapParams(ctypes.Structure):  # pwpp_costmap_params (24 bytes): the layers' mask, what an unknown occupancy / terrain byte counts as, when unknown wins
+    _fields_ = [("layers", ctypes.c_int32), ("occupancy_unknown", ctypes.c_int32), ("terrain_unknown", ctypes.c_int32),
+                ("unknown_below", ctypes.c_int32), ("pad_", ctypes.c_int32 * 2)]
+
+
+COSTMAP_OCCUPANCY, COSTMAP_INFLATION, COSTMAP_TERRAIN = 1, 2, 4  # PWPP_COSTMAP_*: the layers, and their bits of `why`
+COSTMAP_WHY_UNKNOWN = 8  # PWPP_COSTMAP_WHY_UNKNOWN: the bit of `why` of a cell with a layer that stayed unknown
+COSTMAP_MAX_CURVE = 4097  # PWPP_COSTMAP_MAX_CURVE: the longest inflation table, dist2 0 .. 64^2
+
+
 class ClusterLink(ctypes.Structure):  # pwpp_cluster_link (16 bytes): a row's best partner on the other side, their shared cells, its own cells, its partners
     _fields_ = [("other", ctypes.c_int32), ("overlap", ctypes.c_int32), ("cells", ctypes.c_int32), ("links", ctypes.c_int32)]
 
@@ -267,6 +277,13 @@ def load():
             L.pwpp_reach_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, vp]
             L.pwpp_reach_ground.argtypes = [vp, gp, ci, ci, ci, tp, rp, vp, ci, vp, vp, vp]
             L.pwpp_grid_cell_of.argtypes = [gp, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "pwpp_costmap_grid"):  # (as above: an older build has no costmap)
+            gp, tp, cp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams), ctypes.POINTER(CostmapParams)
+            cf, cd, i32 = ctypes.c_float, ctypes.c_double, ctypes.c_int32
+            L.pwpp_costmap_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, cp, vp, ci, vp, vp]
+            L.pwpp_costmap_obstacles.argtypes = [vp, gp, cf, cf, ci, vp, ci, ci, tp, cp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+            L.pwpp_costmap_cell.argtypes = [cp, vp, ci, ci, ci, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint32)]
+            L.pwpp_costmap_curve.argtypes = [cd, cd, cd, cd, ci, vp, ci]
         if hasattr(L, "pwpp_associate_grid"):  # (as above: an older build has no cluster tracks)
             gp = ctypes.POINTER(GroundGrid)
             L.pwpp_associate_grid.argtypes = [vp, gp, gp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -284,6 +301,34 @@ def load():
         L.pwpp_kernel_name.argtypes = [ci]
         _lib = L
     return _lib
+
+
+def _curve(curve):  # the inflation table as the library reads it, None staying None
+    return None if curve is None else np.ascontiguousarray(np.asarray(curve, np.uint8).reshape(-1))
+
+
+def costmap_cell(params, curve, o, t, d):
+    """(cost, why) of one cell with the occupancy byte o, the terrain byte t and the squared distance d under the CostmapParams
+    `params` and the uint8 table `curve` (None without the inflation layer): pwpp_costmap_cell, the function the kernels use, on
+    the host; needs no device."""
+    L = load()
+    cv = _curve(curve)
+    c, w = ctypes.c_int32(0), ctypes.c_uint32(0)
+    if L.pwpp_costmap_cell(ctypes.byref(params), _hp(cv), 0 if cv is None else len(cv), int(o), int(t), int(d), ctypes.byref(c), ctypes.byref(w)) < 0:
+        raise PwppError("pwpp error: %s" % L.pwpp_last_error().decode())
+    return c.value, w.value
+
+
+def costmap_curve(cell, inscribed, radius, decay, peak, capacity=COSTMAP_MAX_CURVE):
+    """The common inflation table for cells of `cell` metres (pwpp_costmap_curve): uint8 entries indexed by the squared distance in
+    cells, 100 up to the inscribed radius, then floor(peak * exp(-decay * (distance - inscribed))) up to `radius`, all in metres;
+    peak 0 .. 99.  Needs no device."""
+    L = load()
+    out = np.zeros(max(int(capacity), 1), np.uint8)
+    n = L.pwpp_costmap_curve(float(cell), float(inscribed), float(radius), float(decay), int(peak), _vp(out), int(capacity))
+    if n < 0:
+        raise PwppError("pwpp error %d: %s" % (n, L.pwpp_last_error().decode()))
+    return out[:n].copy()
 
 
 def evidence_verdict(rule, cells, landed, occupied, free):
@@ -1500,6 +1545,76 @@ class Handle:
         g, frames, src = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, source_xy)
         self._check(self._L.pwpp_reach_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, ctypes.byref(terrain_params),
                                               ctypes.byref(params), _vp(src) if src.size else None, len(src), _dp(reach_ptr), _dp(from_ptr), _dp(cost_ptr)))
+
+    def costmap_grid(self, params, occupancy=None, terrain=None, dist2=None, curve=None, want_why=False):
+        """The costmap of (frames, ny, nx) or (ny, nx) images under the CostmapParams `params`: the int8 occupancy bytes, the int8
+        terrain cost bytes and the int32 dist2 image, each needed only with its layer, and the uint8 inflation table `curve`
+        indexed by dist2.  With the inflation layer and dist2 None the distances are computed from (occupancy == OCC_OCCUPIED) on
+        the device.  Works before any estimate call.  Returns the int8 cost image (-1: unknown, 0 .. 100), with want_why (cost,
+        why): the uint8 image of the layers that set the cost.  The rules: include/pwpp.h."""
+        given = [a for a in (occupancy, terrain, dist2) if a is not None]
+        if not given:
+            raise ValueError("at least one of occupancy, terrain and dist2 expected")
+        shape = tuple(np.shape(given[0]))
+        shape3 = (1,) + shape if len(shape) == 2 else shape
+        if len(shape3) != 3:
+            raise ValueError("(frames, ny, nx) or (ny, nx) images expected")
+        imgs = []
+        for a, dtype in ((occupancy, np.int8), (terrain, np.int8), (dist2, np.int32)):
+            a = None if a is None else np.ascontiguousarray(a, dtype)
+            if a is not None and a.shape != shape:
+                raise ValueError("occupancy, terrain and dist2: images of one shape expected")
+            imgs.append(a)
+        cv = _curve(curve)
+        cost = np.empty(shape, np.int8)
+        why = np.empty(shape, np.uint8) if want_why else None
+        self._check(self._L.pwpp_costmap_grid(self._h, shape3[2], shape3[1], shape3[0], MEM_HOST, _hp(imgs[0]), _hp(imgs[1]), _hp(imgs[2]),
+                                              ctypes.byref(params), _hp(cv), 0 if cv is None else len(cv), _hp(cost), _hp(why)))
+        return (cost, why) if want_why else cost
+
+    def costmap_grid_device(self, nx, ny, frames, params, cost_ptr, occupancy_ptr=0, terrain_ptr=0, dist2_ptr=0, curve=None, why_ptr=0):
+        """costmap_grid on device memory: addresses of the (frames, ny, nx) int8 occupancy and terrain images, the int8 cost and the
+        uint8 why image (any address each) and of the int32 dist2 image (4-byte aligned); 0: none.  curve stays a host array.
+        Enqueued on the handle's stream; complete after synchronize()."""
+        cv = _curve(curve)
+        self._check(self._L.pwpp_costmap_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(occupancy_ptr), _dp(terrain_ptr), _dp(dist2_ptr),
+                                              ctypes.byref(params), _hp(cv), 0 if cv is None else len(cv), _dp(cost_ptr), _dp(why_ptr)))
+
+    def costmap_obstacles(self, x0, y0, cell, nx, ny, params, h_min=-np.inf, h_max=np.inf, min_count=1, origin_xy=(0.0, 0.0), max_range=0,
+                          terrain_params=None, curve=None, frame_first=0, frames=None, ground_only=False, want_why=False, want_layers=False):
+        """The costmap of frames of the last estimate call in one call: rasterize_obstacles, the visibility's bytes, the distances
+        (capped at the table's reach), rasterize_ground and the terrain's cost -- only what the layers of the CostmapParams `params`
+        need -- and the fold.  origin_xy and max_range as visibility_obstacles takes them, terrain_params a TerrainParams (needed
+        with the terrain layer), curve the uint8 inflation table.  Returns the tuple (cost,) of the int8 (frames, ny, nx) cost
+        images; with want_why followed by the uint8 why images; with want_layers followed by occupancy, dist2 and terrain, None
+        for a layer that is off."""
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
+        shape = self._grid_shape(g, frames)
+        cv = _curve(curve)
+        cost = np.empty(shape, np.int8)
+        why = np.empty(shape, np.uint8) if want_why else None
+        layers = [None, None, None]
+        if want_layers:
+            for k, (bit, dtype) in enumerate(((COSTMAP_OCCUPANCY, np.int8), (COSTMAP_INFLATION, np.int32), (COSTMAP_TERRAIN, np.int8))):
+                layers[k] = np.empty(shape, dtype) if params.layers & bit else None
+        self._check(self._L.pwpp_costmap_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _hp(org), len(org), int(max_range),
+                                                   None if terrain_params is None else ctypes.byref(terrain_params), ctypes.byref(params), _hp(cv),
+                                                   0 if cv is None else len(cv), int(frame_first), frames, MEM_HOST, _hp(cost), _hp(why), _hp(layers[0]),
+                                                   _hp(layers[1]), _hp(layers[2])))
+        return (cost,) + ((why,) if want_why else ()) + (tuple(layers) if want_layers else ())
+
+    def costmap_obstacles_device(self, x0, y0, cell, nx, ny, params, cost_ptr, h_min=-np.inf, h_max=np.inf, min_count=1, origin_xy=(0.0, 0.0), max_range=0,
+                                 terrain_params=None, curve=None, why_ptr=0, occupancy_ptr=0, dist2_ptr=0, terrain_ptr=0, frame_first=0, frames=None,
+                                 ground_only=False):
+        """costmap_obstacles into device memory: addresses as in costmap_grid_device; occupancy_ptr, dist2_ptr and terrain_ptr the
+        layers' images (0: kept in the handle's buffer).  Enqueued on the handle's stream; complete after synchronize(): a
+        reach_grid_device on cost_ptr may follow at once."""
+        g, frames, org = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, origin_xy)
+        cv = _curve(curve)
+        self._check(self._L.pwpp_costmap_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), _vp(org) if org.size else None,
+                                                   len(org), int(max_range), None if terrain_params is None else ctypes.byref(terrain_params),
+                                                   ctypes.byref(params), _hp(cv), 0 if cv is None else len(cv), int(frame_first), frames, MEM_DEVICE,
+                                                   _dp(cost_ptr), _dp(why_ptr), _dp(occupancy_ptr), _dp(dist2_ptr), _dp(terrain_ptr)))
 
     @staticmethod
     def _match_host(candidates, frames, map_of_frame):

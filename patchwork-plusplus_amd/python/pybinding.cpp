@@ -121,6 +121,20 @@ py::tuple reach_tuple(const Reach &r) {
     return py::make_tuple(terrain_image(r.reach, r.nx, r.ny), terrain_image(r.from, r.nx, r.ny));
 }
 
+// (cost, why) of a costmap call as (ny, nx) arrays
+template <class Costmap>
+py::tuple costmap_tuple(const Costmap &c) {
+    return py::make_tuple(terrain_image(c.cost, c.nx, c.ny), terrain_image(c.why, c.nx, c.ny));
+}
+
+// the inflation table of a costmap call from any sequence of integers 0 .. 255
+std::vector<uint8_t> curve_of(const py::object &curve) {
+    if (curve.is_none()) return {};
+    const auto a = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(curve);
+    if (!a) throw std::invalid_argument("curve: a sequence of bytes expected");
+    return std::vector<uint8_t>(a.data(), a.data() + a.size());
+}
+
 PYBIND11_MODULE(pypatchworkpp, m) {
     m.doc() = "Python Patchwork++ (MI355X / HIP backend)";
     m.attr("__version__") = "0.0.1";
@@ -203,6 +217,13 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def_readwrite("unknown", &PatchWorkpp::ReachParams::unknown)
         .def_readwrite("clearance2", &PatchWorkpp::ReachParams::clearance2)
         .def_readwrite("max_reach", &PatchWorkpp::ReachParams::max_reach);
+
+    py::class_<PatchWorkpp::CostmapParams>(m, "CostmapParams")  // the layers and the unknown rules of getCostmap and fusedCostmap
+        .def(py::init<>())
+        .def_readwrite("layers", &PatchWorkpp::CostmapParams::layers)
+        .def_readwrite("occupancy_unknown", &PatchWorkpp::CostmapParams::occupancy_unknown)
+        .def_readwrite("terrain_unknown", &PatchWorkpp::CostmapParams::terrain_unknown)
+        .def_readwrite("unknown_below", &PatchWorkpp::CostmapParams::unknown_below);
 
     py::class_<PatchWorkpp>(m, "patchworkpp")
         .def(py::init<Params>())
@@ -322,6 +343,31 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("map"), py::arg("terrain_params") = PatchWorkpp::TerrainParams(), py::arg("reach_params") = PatchWorkpp::ReachParams(),
              py::arg("source_x") = 0.0, py::arg("source_y") = 0.0)
+        .def_static("inflationCurve",
+                    [](double cell, double inscribed, double radius, double decay, int peak) {
+                        const std::vector<uint8_t> c = PatchWorkpp::inflationCurve(cell, inscribed, radius, decay, peak);
+                        py::array_t<uint8_t> out((py::ssize_t)c.size());
+                        std::copy(c.begin(), c.end(), out.mutable_data());
+                        return out;
+                    },
+                    py::arg("cell"), py::arg("inscribed"), py::arg("radius"), py::arg("decay"), py::arg("peak") = 99)
+        .def("getCostmap",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, const py::object &curve,
+                const PatchWorkpp::CostmapParams &params, const PatchWorkpp::TerrainParams &terrain_params, int min_count, int max_range, double origin_x,
+                double origin_y, bool ground_only) {
+                 return costmap_tuple(s.getCostmap(x0, y0, cell, nx, ny, h_min, h_max, curve_of(curve), params, terrain_params, min_count, max_range, origin_x,
+                                                   origin_y, ground_only));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"), py::arg("curve") = py::none(),
+             py::arg("params") = PatchWorkpp::CostmapParams(), py::arg("terrain_params") = PatchWorkpp::TerrainParams(), py::arg("min_count") = 1,
+             py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0, py::arg("ground_only") = false)
+        .def("fusedCostmap",
+             [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, const PatchWorkpp::FusedElevationMap *elevation, const py::object &curve,
+                const PatchWorkpp::CostmapParams &params, const PatchWorkpp::TerrainParams &terrain_params) {
+                 return costmap_tuple(s.fusedCostmap(map, elevation, curve_of(curve), params, terrain_params));
+             },
+             py::arg("map"), py::arg("elevation") = static_cast<const PatchWorkpp::FusedElevationMap *>(nullptr), py::arg("curve") = py::none(),
+             py::arg("params") = PatchWorkpp::CostmapParams(), py::arg("terrain_params") = PatchWorkpp::TerrainParams())
         .def("matchObstacleMap",
              [](PatchWorkpp &s, const PatchWorkpp::FusedObstacleMap &map, const std::vector<std::array<double, 6>> &candidates, int wx, int wy, double x0,
                 double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y) {
