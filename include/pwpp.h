@@ -1410,6 +1410,92 @@ PWPP_API int pwpp_costmap_cell(const pwpp_costmap_params *p, const uint8_t *curv
 PWPP_API int pwpp_costmap_curve(double cell, double inscribed, double radius, double decay, int peak /* 0 .. 99 */,
                                 uint8_t *curve, int capacity);  /* host only; returns n_curve */
 
+/* ---- routes: the from chain of the reach field walked, summarised and shortcut on the device (pwpp_route_grid, pwpp_plan_grid) ----
+ * pwpp_reach_grid gives every cell its cost and the neighbour it comes through; a controller wants the way itself: which cells,
+ * how long, how close to an obstacle, how dear at its worst, and the few waypoints a tracker follows instead of a staircase of
+ * cells.  These calls follow `from` on the device for any number of starts per frame and return a row of 32 bytes, the cells and
+ * the waypoints per route -- the from image (4 bytes a cell) never has to reach the host.  Integers only: the same bytes whatever
+ * the schedule.  Frames, and the routes of a frame, are on their own.
+ *   terms, steps  exactly those of pwpp_reach_grid (above): the same cost, dist2, pwpp_reach_params and corner rule give t(cell) and
+ *             step(a, b); max_reach is not read.  The frame's source has its term wherever it is read -- on a line that merely passes
+ *             over it too.  The range check of pwpp_reach_grid applies: every sum below stays under 2^31.
+ *   route     of a start s: r_0 = s, r_{i+1} = from[r_i], ending at the cell that names itself, which must be the frame's source.
+ *             Every list runs in this order, from the start to the source.  step is symmetric: a caller who wants "vehicle to
+ *             goal" puts the field's source at the goal and the start at the vehicle, and reads the lists as they are.
+ *   status    PWPP_ROUTE_NONE: from[s] == -1.  Every other field of the row is 0, min_dist2 is PWPP_DIST_BEYOND, both lists are all -1.
+ *             PWPP_ROUTE_BROKEN: a hop from c to n = from[c] is not a step of the contract -- n outside [0, nx ny); n not one of
+ *             the 8 neighbours of c; n == c away from the source (the chain ends at a cell other than the source); t(c) or t(n)
+ *             is 0; a cut corner; or nx ny - 1 hops were taken without arriving.  The row then holds what the valid hops up to c
+ *             accumulated: `cells` counts up to and including c, max_term and min_dist2 cover those cells, the cell list holds that
+ *             prefix, `waypoints` is 0 and its list all -1.  A from image of pwpp_reach_grid on the same inputs never gives
+ *             PWPP_ROUTE_BROKEN.  The hop bound is the only loop bound of the walk; no kernel loops on past it.
+ *             PWPP_ROUTE_OK: otherwise.  Then cost == reach[s].
+ *   lists     The cell list of a route holds its first min(cells, max_cells) indices iy * nx + ix and -1 behind them; the waypoint
+ *             list the same with max_waypoints.  The row's counts are of the whole route: cells > max_cells is how a caller sees a
+ *             truncation.  Neither limit changes any other value.  A limit of 0: no list, the pointer may be NULL.
+ *   waypoints indices into the route: w_0 = 0; from w_i = a < cells - 1, w_{i+1} is the largest b in (a, min(a + look, cells - 1)]
+ *             for which b == a + 1 or the line r_a -> r_b is clear.  The line is that of the visibility operator (above), from the
+ *             earlier cell to the later: with n = max(|dx|, |dy|) the points P_k, k = 0 .. n.  It is clear iff for every k = 1 .. n:
+ *             0 < t(P_k) <= base + line_cost, and wherever both coordinates moved both cells the step squeezes between have t > 0
+ *             -- the reach's corner rule, stricter than the visibility's.  The last waypoint is the source.  Stored waypoints are
+ *             cell indices.  It follows that the polyline, rasterised by the same line, is a legal step path of the reach contract
+ *             from the start to the source; that look = 1 returns the route itself; and that on an open field of one cost byte
+ *             <= line_cost with look >= cells - 1 every route has 2 waypoints, 1 where the start is the source.  max_waypoints
+ *             == 0: no search, `waypoints` of the row is 0.  (csrc/pwpp_route.h has the proofs.)
+ *   row       status; cells; cost, the sum of the steps; edge_steps and corner_steps (the length in metres is cell * (edge_steps +
+ *             sqrt(2) corner_steps), left to the caller: no floating point here); max_term, the largest t over the cells;
+ *             min_dist2, the smallest dist2 over them (PWPP_DIST_BEYOND without a dist2 image); waypoints.
+ *   starts    n_start_sets x n_starts x {x, y} cells, host memory whatever `mem`, copied at the call, like the sources;
+ *             n_start_sets is 1 (one set for every frame) or `frames`; n_starts 1 .. 65536; frames * n_starts * max(max_cells,
+ *             max_waypoints, 1) <= 2^31 - 1.  Starts may repeat and may be the source.
+ *   plan_grid pwpp_reach_grid and pwpp_route_grid on its from as one enqueued sequence: byte for byte what the two calls give.
+ *             reach and from may be NULL and then stay in the handle's buffer: the field never leaves the device.
+ *   mem       as pwpp_reach_grid: PWPP_MEM_DEVICE asks 4-byte alignment of dist2, reach, from, the rows and both lists; the cost
+ *             bytes lie at any address.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, cost, reach parameters, source, from
+ *             (pwpp_route_grid), start, route parameters, routes; then what pwpp_reach_grid checks of the images, its parameters,
+ *             the range and the sources; max_cells, max_waypoints, look, line_cost; the count of start sets, of starts, the product
+ *             beyond 2^31 - 1; the first start outside the image, naming the entry; a null list with its limit > 0; two of the
+ *             caller's arrays overlapping; mem; in PWPP_MEM_DEVICE an int32 array below its alignment.
+ *   buffers   The uploaded starts and sources, in pwpp_plan_grid the reach's working memory and the images the caller did not ask
+ *             for, and in PWPP_MEM_HOST the staged arrays lie in the cluster buffer; counted by pwpp_get_workspace_bytes, freed
+ *             by pwpp_trim_workspace.
+ * The same bytes for every mem, alignment and value of the option "route_path".  With neither function called nothing is
+ * allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_ROUTES 1
+#define PWPP_ROUTE_OK 0
+#define PWPP_ROUTE_NONE 1
+#define PWPP_ROUTE_BROKEN 2
+typedef struct pwpp_route_params {   /* 16 bytes */
+    int32_t max_cells;      /* cells stored per route, >= 0 (0: no cell list; `cells` may be NULL) */
+    int32_t max_waypoints;  /* waypoints stored per route, >= 0 (0: no shortcut search; `waypoints` may be NULL) */
+    int32_t look;           /* how many cells ahead a shortcut may reach; 1 .. 256 */
+    int32_t line_cost;      /* a shortcut line crosses only cells with t <= base + line_cost; 0 .. 100 */
+} pwpp_route_params;
+typedef struct pwpp_route {          /* 32 bytes: one row per (frame, start) */
+    int32_t status;        /* PWPP_ROUTE_OK, PWPP_ROUTE_NONE, PWPP_ROUTE_BROKEN */
+    int32_t cells;         /* cells of the whole route, start and source included, whatever max_cells */
+    int32_t cost;          /* the sum of the steps along it: equals reach[start] */
+    int32_t edge_steps, corner_steps;
+    int32_t max_term;      /* the largest t over its cells */
+    int32_t min_dist2;     /* the smallest dist2 over its cells; PWPP_DIST_BEYOND without a dist2 image */
+    int32_t waypoints;     /* waypoints of the whole route, whatever max_waypoints; 0 with max_waypoints == 0 */
+} pwpp_route;
+
+/* follow a given from image: needs a handle (stream, buffer), no estimate call -- like pwpp_reach_grid */
+PWPP_API int pwpp_route_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost /* [frames][ny][nx] */,
+                             const int32_t *dist2 /* same shape, may be NULL */, const pwpp_reach_params *p,
+                             const int32_t *source /* host: n_sources x {sx, sy} */, int n_sources /* 1 or frames */,
+                             const int32_t *from /* same shape: of pwpp_reach_grid */,
+                             const int32_t *start /* host: n_start_sets x n_starts x {x, y} */, int n_start_sets /* 1 or frames */, int n_starts,
+                             const pwpp_route_params *route_params, pwpp_route *routes /* [frames][n_starts] */,
+                             int32_t *cells /* [frames][n_starts][max_cells] */, int32_t *waypoints /* [frames][n_starts][max_waypoints] */);
+/* cost image -> field -> routes, one enqueued sequence */
+PWPP_API int pwpp_plan_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost, const int32_t *dist2, const pwpp_reach_params *p,
+                            const int32_t *source, int n_sources, const int32_t *start, int n_start_sets, int n_starts,
+                            const pwpp_route_params *route_params, pwpp_route *routes, int32_t *cells, int32_t *waypoints,
+                            int32_t *reach /* may be NULL: kept in the handle's buffer */, int32_t *from /* may be NULL: kept */);
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1556,6 +1642,10 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         "1": sweeps over the frame's cells in global memory until a sweep changes nothing (the yardstick); "2": the
  *                         frame's tiles of 32 x 32 cells, each relaxed in LDS with a halo of one cell, a tile revisited when a
  *                         neighbour's border changed; "0" (default): what tools/reach_cost.py decided.  The same bytes for every value.
+ *   "route_path"          how the routes are dealt (pwpp_route_grid, pwpp_plan_grid): "1": a lane per route, wholly serial, the waypoints by
+ *                         a second walk through from (the yardstick); "2": a wave per route -- every lane takes the hops, the route's
+ *                         last 512 cells lie in LDS, the shortcut candidates go to the lanes from the far end and a ballot picks the
+ *                         largest clear one; "0" (default): what tools/route_cost.py decided.  The same bytes for every value.
  *   "costmap_path"        how the costmap's fold is dealt (pwpp_costmap_grid, pwpp_costmap_obstacles): "1": a lane per cell, the inflation
  *                         curve read from global memory (the yardstick); "2": the curve staged once per workgroup into LDS, four
  *                         consecutive cells a lane, the byte images as one dword where their address allows; "0" (default): what

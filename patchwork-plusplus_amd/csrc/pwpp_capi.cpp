@@ -31,6 +31,7 @@
 #include "pwpp_match.h"
 #include "pwpp_costmap.h"
 #include "pwpp_reach.h"
+#include "pwpp_route.h"
 #include "pwpp_terrain.h"
 #include "pwpp_tracks.h"
 #include "pwpp_visibility.h"
@@ -260,6 +261,7 @@ struct pwpp_handle {
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
     int costmap_path = 0;           // option "costmap_path": 0 = what tools/costmap_cost.py decided (2 from PWPP_COSTMAP_QUADS_FROM_CELLS cells a call, 1 below); 1 = a lane per cell, the curve read from global memory (yardstick); 2 = the curve staged in LDS, four cells a lane
+    int route_path = 0;             // option "route_path": 0 = what tools/route_cost.py decided; 1 = a lane per route, wholly serial (yardstick); 2 = a wave per route, the route's last cells in LDS, the shortcut candidates dealt to the lanes
     int reach_path = 0;             // option "reach_path": 0 = what tools/reach_cost.py decided; 1 = sweeps over global memory, a workgroup per frame (yardstick); 2 = the frame's tiles relaxed in LDS, dirty tiles revisited
     int evidence_path = 0;          // option "evidence_path": 0 = what tools/evidence_cost.py decided; 1 = the sums go to the rows with global atomics (yardstick); 2 = a workgroup sums a run of cells in LDS first where the rows fit
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
@@ -2143,6 +2145,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "reach_path=%s: 0, 1 or 2 expected", value);
         h->reach_path = v;
+    } else if (k == "route_path") {
+        const int v = std::atoi(value);
+        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "route_path=%s: 0, 1 or 2 expected", value);
+        h->route_path = v;
     } else if (k == "costmap_path") {
         const int v = std::atoi(value);
         if (v < 0 || v > 2) return fail(PWPP_E_ARG, "costmap_path=%s: 0, 1 or 2 expected", value);
@@ -3356,20 +3362,21 @@ int reach_source_count(int n_sources, int frames) {
 }
 
 // (the working image, the defect word and the sources first; `src`: the source cells, n_sources x {sx, sy}, checked; `cost` is the
-// cost bytes' section: the caller's, or the terrain's.  In PWPP_MEM_HOST the defect word comes back with the images.)
+// cost bytes' section: the caller's, or the terrain's.  In PWPP_MEM_HOST the defect word comes back with the images.  `keep`: both
+// images lie in the buffer where the caller gives no pointer -- the routes read them there.)
 struct ReachSections {
     int term, flag, src, cost, dist2, reach, from;
 };
 ReachSections reach_sections(Staging &st, int mem, int nx, int ny, int frames, size_t cells, int s_cost, const std::vector<int32_t> &src, const int32_t *dist2,
-                             int32_t *reach, int32_t *from, uint32_t *flag_host) {
+                             int32_t *reach, int32_t *from, uint32_t *flag_host, bool keep = false) {
     ReachSections s;
     s.term = st.add(pwpp_reach_work_words(nx, ny, frames), nullptr, Staging::kKept);
     s.flag = mem == PWPP_MEM_HOST ? st.add(1, flag_host, Staging::kOut) : st.add(1, nullptr, Staging::kKept);
     s.src = frame_cells_section(st, src);
     s.cost = s_cost;
     s.dist2 = st.add(dist2 ? cells : 0, dist2, Staging::kIn);
-    s.reach = st.add(cells, reach, Staging::kOut);
-    s.from = st.add(from ? cells : 0, from, Staging::kOut);
+    s.reach = st.add(cells, reach, keep && !reach ? Staging::kKept : Staging::kOut);
+    s.from = st.add(from || keep ? cells : 0, from, keep && !from ? Staging::kKept : Staging::kOut);
     return s;
 }
 // (one source travels as an argument; one per frame lies in its section)
@@ -3456,6 +3463,144 @@ int pwpp_grid_cell_of(const pwpp_ground_grid *g, double x, double y, int32_t *ix
     if (const int rc = frame_cells_of(g, xy, 1, "position", cell)) return rc;
     *ix = cell[0], *iy = cell[1];
     return PWPP_OK;
+}
+
+// ---- routes: the from chain of the reach field walked, summarised and shortcut for every (frame, start) ----
+namespace {
+static_assert(sizeof(pwpp_route_params) == 16 && sizeof(pwpp_route) == 32 && sizeof(PwppRouteRow) == 32 && sizeof(PwppRouteRule) == 16, "the rows and the rule as the kernels see them");
+static_assert(PWPP_ROUTE_OK == PWPP_ROUTE_STATUS_OK && PWPP_ROUTE_NONE == PWPP_ROUTE_STATUS_NONE && PWPP_ROUTE_BROKEN == PWPP_ROUTE_STATUS_BROKEN, "the kernels' values");
+
+// What both entry points check of the route's own arguments, in the header's order, after the reach's; fills the rule and `st`, the
+// start cells n_start_sets x n_starts x {x, y}.  Touches no handle.
+int route_args(const pwpp_route_params *q, int nx, int ny, int frames, const int32_t *start, int n_start_sets, int n_starts, const int32_t *cells,
+               const int32_t *waypoints, PwppRouteRule &rule, std::vector<uint32_t> &st) {
+    if (q->max_cells < 0) return fail(PWPP_E_ARG, "max_cells %d: 0 (no cell list) or more expected", q->max_cells);
+    if (q->max_waypoints < 0) return fail(PWPP_E_ARG, "max_waypoints %d: 0 (no shortcut search) or more expected", q->max_waypoints);
+    if (q->look < 1 || q->look > PWPP_ROUTE_MAX_LOOK) return fail(PWPP_E_ARG, "look %d: 1 .. %d expected", q->look, PWPP_ROUTE_MAX_LOOK);
+    if (q->line_cost < 0 || q->line_cost > 100) return fail(PWPP_E_ARG, "line_cost %d: 0 .. 100 expected", q->line_cost);
+    if (n_start_sets < 1 || (n_start_sets != 1 && n_start_sets != frames))
+        return fail(PWPP_E_ARG, "%d start sets for %d frames: 1 or one per frame expected", n_start_sets, frames);
+    if (n_starts < 1 || n_starts > PWPP_ROUTE_MAX_STARTS) return fail(PWPP_E_ARG, "%d starts: 1 .. %d expected", n_starts, PWPP_ROUTE_MAX_STARTS);
+    const int64_t per_route = std::max<int64_t>(std::max(q->max_cells, q->max_waypoints), 1);
+    if ((int64_t)frames * (int64_t)n_starts > (int64_t)INT32_MAX / per_route)
+        return fail(PWPP_E_ARG, "%d frames x %d starts x %lld list entries exceed 2^31 - 1", frames, n_starts, (long long)per_route);
+    for (int k = 0; k < n_start_sets; ++k)
+        for (int i = 0; i < n_starts; ++i) {
+            const int32_t *s = start + 2 * ((size_t)k * (size_t)n_starts + (size_t)i);
+            if (s[0] < 0 || s[0] >= nx || s[1] < 0 || s[1] >= ny)
+                return fail(PWPP_E_ARG, "start %d of set %d, cell (%d, %d), lies outside the %d x %d cells", i, k, s[0], s[1], nx, ny);
+        }
+    if (q->max_cells > 0 && !cells) return fail(PWPP_E_ARG, "null cell lists with max_cells %d", q->max_cells);
+    if (q->max_waypoints > 0 && !waypoints) return fail(PWPP_E_ARG, "null waypoint lists with max_waypoints %d", q->max_waypoints);
+    rule = PwppRouteRule{q->max_cells, q->max_waypoints, q->look, q->line_cost};
+    st.assign(start, start + 2 * (size_t)n_start_sets * (size_t)n_starts);
+    return PWPP_OK;
+}
+
+// (the uploaded starts first, then the rows and the lists; a list without entries has no words and a null pointer)
+struct RouteSections {
+    int start, rows, cells, wps;
+};
+RouteSections route_sections(Staging &st, std::vector<uint32_t> &&starts, size_t routes, const PwppRouteRule &rule, pwpp_route *rows, int32_t *cells,
+                             int32_t *waypoints) {
+    RouteSections s;
+    s.start = st.add_upload(std::move(starts));
+    s.rows = st.add(routes * 8, rows, Staging::kOut);
+    s.cells = st.add(routes * (size_t)rule.max_cells, rule.max_cells > 0 ? cells : nullptr, Staging::kOut);
+    s.wps = st.add(routes * (size_t)rule.max_waypoints, rule.max_waypoints > 0 ? waypoints : nullptr, Staging::kOut);
+    return s;
+}
+int route_launch(pwpp_handle *h, const Staging &st, const ReachSections &r, const RouteSections &s, const PwppReachRule &rule, const PwppRouteRule &route,
+                 int nx, int ny, int frames, const std::vector<int32_t> &src, int n_start_sets, int n_starts) {
+    return pwpp_launch_routes(&rule, &route, nx, ny, frames, st.dev<const int8_t>(r.cost), rule.use_dist2 ? st.dev<const int32_t>(r.dist2) : nullptr,
+                              src[0], src[1], src.size() > 2 ? st.dev<const int32_t>(r.src) : nullptr,
+                              st.dev<const int32_t>(r.from), st.dev<const int32_t>(s.start), n_start_sets, n_starts, st.dev<void>(s.rows), st.dev<int32_t>(s.cells),
+                              st.dev<int32_t>(s.wps), h->route_path, h->stream);
+}
+
+// what both entry points check between the null pointers and the overlaps
+int route_common_args(int nx, int ny, int frames, const int32_t *dist2, const pwpp_reach_params *p, const int32_t *source, int n_sources, const pwpp_route_params *q,
+                      const int32_t *start, int n_start_sets, int n_starts, const int32_t *cells, const int32_t *waypoints, size_t &n_cells, PwppReachRule &rule,
+                      PwppRouteRule &route, std::vector<uint32_t> &starts) {
+    int rc = image_args(nx, ny, frames, kReachWho, n_cells);
+    if (rc) return rc;
+    if ((rc = reach_param_args(p, nx, ny, dist2 != nullptr, rule))) return rc;
+    if ((rc = reach_source_count(n_sources, frames))) return rc;
+    for (int i = 0; i < n_sources; ++i)
+        if (source[2 * i] < 0 || source[2 * i] >= nx || source[2 * i + 1] < 0 || source[2 * i + 1] >= ny)
+            return fail(PWPP_E_ARG, "source %d, cell (%d, %d), lies outside the %d x %d cells", i, source[2 * i], source[2 * i + 1], nx, ny);
+    return route_args(q, nx, ny, frames, start, n_start_sets, n_starts, cells, waypoints, route, starts);
+}
+}  // namespace
+
+int pwpp_route_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost, const int32_t *dist2, const pwpp_reach_params *p,
+                    const int32_t *source, int n_sources, const int32_t *from, const int32_t *start, int n_start_sets, int n_starts, const pwpp_route_params *q,
+                    pwpp_route *routes, int32_t *cells, int32_t *waypoints) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!cost || !p || !source || !from || !start || !q || !routes)
+        return fail(PWPP_E_ARG, "null %s",
+                    !cost ? "cost image" : (!p ? "reach parameters" : (!source ? "source" : (!from ? "from image" : (!start ? "start" : (!q ? "route parameters" : "routes"))))));
+    size_t n_cells = 0;
+    PwppReachRule rule;
+    PwppRouteRule route;
+    std::vector<uint32_t> starts;
+    int rc = route_common_args(nx, ny, frames, dist2, p, source, n_sources, q, start, n_start_sets, n_starts, cells, waypoints, n_cells, rule, route, starts);
+    if (rc) return rc;
+    const size_t n_routes = (size_t)frames * (size_t)n_starts;
+    if ((rc = range_args({{cost, n_cells, "cost"}, {dist2, n_cells * 4, "dist2"}, {from, n_cells * 4, "from"}, {routes, n_routes * 32, "routes"},
+                          {route.max_cells > 0 ? cells : nullptr, n_routes * 4 * (size_t)route.max_cells, "cells"},
+                          {route.max_waypoints > 0 ? waypoints : nullptr, n_routes * 4 * (size_t)route.max_waypoints, "waypoints"}}, {}, false)))
+        return rc;
+    if ((rc = mem_args(mem, "the routes take"))) return rc;
+    if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}, {from, 3u, "from image"}, {routes, 3u, "routes"}, {route.max_cells > 0 ? cells : nullptr, 3u, "cell lists"},
+                                   {route.max_waypoints > 0 ? waypoints : nullptr, 3u, "waypoint lists"}})))
+        return rc;
+    const std::vector<int32_t> src(source, source + 2 * (size_t)n_sources);
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    ReachSections r{};
+    r.cost = st.add((n_cells + 3) / 4, cost, Staging::kIn, n_cells);
+    r.src = frame_cells_section(st, src);
+    r.dist2 = st.add(dist2 ? n_cells : 0, dist2, Staging::kIn);
+    r.from = st.add(n_cells, from, Staging::kIn);
+    const RouteSections s = route_sections(st, std::move(starts), n_routes, route, routes, cells, waypoints);
+    return run_on_image(h, st, [&] { return route_launch(h, st, r, s, rule, route, nx, ny, frames, src, n_start_sets, n_starts); });
+}
+
+// pwpp_reach_grid -- reach and from kept in the cluster buffer unless the caller asks for them -- and pwpp_route_grid on its from, one enqueued
+// sequence.
+int pwpp_plan_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost, const int32_t *dist2, const pwpp_reach_params *p,
+                   const int32_t *source, int n_sources, const int32_t *start, int n_start_sets, int n_starts, const pwpp_route_params *q, pwpp_route *routes,
+                   int32_t *cells, int32_t *waypoints, int32_t *reach, int32_t *from) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!cost || !p || !source || !start || !q || !routes)
+        return fail(PWPP_E_ARG, "null %s", !cost ? "cost image" : (!p ? "reach parameters" : (!source ? "source" : (!start ? "start" : (!q ? "route parameters" : "routes")))));
+    size_t n_cells = 0;
+    PwppReachRule rule;
+    PwppRouteRule route;
+    std::vector<uint32_t> starts;
+    int rc = route_common_args(nx, ny, frames, dist2, p, source, n_sources, q, start, n_start_sets, n_starts, cells, waypoints, n_cells, rule, route, starts);
+    if (rc) return rc;
+    const size_t n_routes = (size_t)frames * (size_t)n_starts;
+    if ((rc = range_args({{cost, n_cells, "cost"}, {dist2, n_cells * 4, "dist2"}, {reach, n_cells * 4, "reach"}, {from, n_cells * 4, "from"}, {routes, n_routes * 32, "routes"},
+                          {route.max_cells > 0 ? cells : nullptr, n_routes * 4 * (size_t)route.max_cells, "cells"},
+                          {route.max_waypoints > 0 ? waypoints : nullptr, n_routes * 4 * (size_t)route.max_waypoints, "waypoints"}}, {}, false)))
+        return rc;
+    if ((rc = mem_args(mem, "the routes take"))) return rc;
+    if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}, {reach, 3u, "reach image"}, {from, 3u, "from image"}, {routes, 3u, "routes"},
+                                   {route.max_cells > 0 ? cells : nullptr, 3u, "cell lists"}, {route.max_waypoints > 0 ? waypoints : nullptr, 3u, "waypoint lists"}})))
+        return rc;
+    const std::vector<int32_t> src(source, source + 2 * (size_t)n_sources);
+    uint32_t flag_host = 0;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_cost = st.add((n_cells + 3) / 4, cost, Staging::kIn, n_cells);
+    const ReachSections r = reach_sections(st, mem, nx, ny, frames, n_cells, s_cost, src, dist2, reach, from, &flag_host, true);
+    const RouteSections s = route_sections(st, std::move(starts), n_routes, route, routes, cells, waypoints);
+    return reach_defect(run_on_image(h, st,
+                                     [&] {
+                                         const int lrc = reach_launch(h, st, r, rule, nx, ny, frames, src);
+                                         return lrc != 0 ? lrc : route_launch(h, st, r, s, rule, route, nx, ny, frames, src, n_start_sets, n_starts);
+                                     }),
+                        flag_host);
 }
 
 // ---- costmap: the occupancy byte, the inflated obstacle distance and the terrain's cost byte folded into one cost byte ----------------

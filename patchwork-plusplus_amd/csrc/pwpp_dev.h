@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -348,6 +348,10 @@ int pwpp_launch_terrain(const struct PwppTerrainRule *R, int nx, int ny, int fra
 size_t pwpp_reach_work_words(int nx, int ny, int frames);
 int pwpp_launch_reach(const struct PwppReachRule *R, int nx, int ny, int frames, const int8_t *cost, const int32_t *dist2, int sx, int sy,
                       const int32_t *sources, int32_t *reach, int32_t *from, uint16_t *term, uint32_t *flag, int path, hipStream_t stream);
+// pwpp_route.hip
+int pwpp_launch_routes(const struct PwppReachRule *R, const struct PwppRouteRule *P, int nx, int ny, int frames, const int8_t *cost, const int32_t *dist2,
+                       int sx, int sy, const int32_t *sources, const int32_t *from, const int32_t *starts, int n_start_sets, int n_starts,
+                       void *rows, int32_t *cells, int32_t *waypoints, int path, hipStream_t stream);
 // pwpp_costmap.hip
 int pwpp_launch_costmap_occupied(size_t cells, const int8_t *occupancy, int32_t *count, hipStream_t stream);
 int pwpp_launch_costmap(const struct PwppCostmapRule *R, size_t cells, const int8_t *occupancy, const int8_t *terrain, const int32_t *dist2,

@@ -60,6 +60,25 @@ int main(int argc, char **argv) {
     printf("points %d ground %d nonground %d patches %d height %.6f time_us %.1f\n", n, (int)n_ground, (int)n_nonground,
            (int)n_patches, pwpp_get_height(h), pwpp_get_time_us(h));
     free(ground);
+
+    /* A route (pwpp_plan_grid, no reference counterpart): 9 x 9 cells of free ground with a wall across column 4 that is open in its
+     * last row; the field from the goal at (8, 0), the chain of `from` from the vehicle at (0, 0) and its waypoints, one call. */
+    {
+        int8_t cost[81] = {0};
+        const pwpp_reach_params reach_params = {1, 100, -1, 0, 0, 0};
+        const pwpp_route_params route_params = {0, 8, 64, 0};
+        const int32_t goal[2] = {8, 0}, vehicle[2] = {0, 0};
+        pwpp_route route;
+        int32_t waypoints[8];
+        int y, k;
+        for (y = 0; y < 8; ++y) cost[9 * y + 4] = 100;
+        if (pwpp_plan_grid(h, 9, 9, 1, PWPP_MEM_HOST, cost, NULL, &reach_params, goal, 1, vehicle, 1, 1, &route_params, &route, NULL, waypoints, NULL, NULL) != PWPP_OK)
+            return fail("pwpp_plan_grid");
+        printf("route round a wall: status %d, %d cells, cost %d, %d edge and %d corner steps, %d waypoints:", (int)route.status, (int)route.cells, (int)route.cost,
+               (int)route.edge_steps, (int)route.corner_steps, (int)route.waypoints);
+        for (k = 0; k < route.waypoints && k < 8; ++k) printf(" (%d, %d)", (int)(waypoints[k] % 9), (int)(waypoints[k] / 9));
+        printf("\n");
+    }
     pwpp_destroy(h);
 
     /* A tilted sensor (pwpp_set_input_transforms, no reference counterpart): the same frame as a LiDAR pitched by 5 degrees and

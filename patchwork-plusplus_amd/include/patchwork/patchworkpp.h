@@ -623,6 +623,58 @@ public:
                                 curve.empty() ? nullptr : curve.data(), (int)curve.size(), c.cost.data(), c.why.data()));
         return costmap_sized(c);
     }
+    // ... and the way itself (pwpp_plan_grid): for every start position the chain of `from` of the reach field from the start's cell to the
+    // source's, one row of sums per route (status PWPP_ROUTE_OK / _NONE / _BROKEN, cells, cost == reach[start], edge and corner steps --
+    // length = cell * (edge_steps + sqrt(2) corner_steps) -- the largest term, waypoints), the cells, and the waypoints a controller
+    // tracks: greedy shortcuts of at most `look` cells whose line crosses only cells with a term <= base + line_cost and cuts no corner.
+    // Lists run from the start to the source (step costs are symmetric: put the source at the goal); -1 / NaN behind a list's end.
+    struct RouteParams {
+        int max_cells, max_waypoints, look, line_cost;  // >= 0, twice (0: no list); 1 .. 256; 0 .. 100
+        RouteParams() : max_cells(1024), max_waypoints(64), look(64), line_cost(0) {}  // (a constructor: as TerrainParams)
+    };
+    struct Routes {
+        int n = 0, max_cells = 0, max_waypoints = 0;
+        std::vector<pwpp_route> rows;           // n
+        std::vector<int32_t> cells, waypoints;  // n x max_cells, n x max_waypoints: cell indices iy * nx + ix
+        std::vector<double> waypoints_xy;       // n x max_waypoints x {x, y}: the centres of those cells in metres
+    };
+    // (on the terrain cost of the last frame's elevation image over the grid (x0, y0, cell, nx, ny); starts_xy: n x {x, y} in metres, the source in metres)
+    Routes getRoutes(double x0, double y0, double cell, int nx, int ny, const std::vector<double> &starts_xy, const TerrainParams &terrain_params = TerrainParams(),
+                     const ReachParams &reach_params = ReachParams(), const RouteParams &route_params = RouteParams(), double source_x = 0.0, double source_y = 0.0,
+                     bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        const pwpp_terrain_params tp = {terrain_params.radius, terrain_params.min_known, terrain_params.step_max, terrain_params.slope_max, terrain_params.rough_max, 0};
+        const size_t cells = (size_t)(nx > 0 ? nx : 0) * (size_t)(ny > 0 ? ny : 0);
+        std::vector<int8_t> cost(cells ? cells : 1);  // (room for one cell where the grid has none: the library names the grid)
+        check(pwpp_terrain_ground(h_, &g, 0, 1, PWPP_MEM_HOST, &tp, nullptr, nullptr, nullptr, nullptr, cost.data(), nullptr));
+        cost.resize(cells);
+        return planRoutes(cost, x0, y0, cell, nx, ny, starts_xy, reach_params, route_params, source_x, source_y);
+    }
+    // (on any cost image of ny x nx cells over that grid -- a Costmap's cost)
+    Routes planRoutes(const std::vector<int8_t> &cost, double x0, double y0, double cell, int nx, int ny, const std::vector<double> &starts_xy,
+                      const ReachParams &reach_params = ReachParams(), const RouteParams &route_params = RouteParams(), double source_x = 0.0, double source_y = 0.0) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, 0, 0};
+        const pwpp_reach_params rp = {reach_params.base, reach_params.lethal, reach_params.unknown, reach_params.clearance2, reach_params.max_reach, 0};
+        const pwpp_route_params qp = {route_params.max_cells, route_params.max_waypoints, route_params.look, route_params.line_cost};
+        if (starts_xy.empty() || starts_xy.size() % 2 != 0) throw std::invalid_argument("planRoutes: starts_xy holds n x {x, y}, n >= 1");
+        if (nx < 1 || ny < 1 || cost.size() != (size_t)nx * (size_t)ny) throw std::invalid_argument("planRoutes: the cost image has not ny x nx cells");
+        Routes r;
+        r.n = (int)(starts_xy.size() / 2), r.max_cells = qp.max_cells > 0 ? qp.max_cells : 0, r.max_waypoints = qp.max_waypoints > 0 ? qp.max_waypoints : 0;
+        int32_t source[2] = {0, 0};
+        check(pwpp_grid_cell_of(&g, source_x, source_y, &source[0], &source[1]));  // (the raster's cell rule; the library names a position it refuses)
+        std::vector<int32_t> start(starts_xy.size());
+        for (int i = 0; i < r.n; ++i) check(pwpp_grid_cell_of(&g, starts_xy[2 * (size_t)i], starts_xy[2 * (size_t)i + 1], &start[2 * (size_t)i], &start[2 * (size_t)i + 1]));
+        r.rows.resize((size_t)r.n), r.cells.assign((size_t)r.n * (size_t)r.max_cells, -1), r.waypoints.assign((size_t)r.n * (size_t)r.max_waypoints, -1);
+        check(pwpp_plan_grid(h_, nx, ny, 1, PWPP_MEM_HOST, cost.data(), nullptr, &rp, source, 1, start.data(), 1, r.n, &qp, r.rows.data(),
+                             r.max_cells ? r.cells.data() : nullptr, r.max_waypoints ? r.waypoints.data() : nullptr, nullptr, nullptr));
+        r.waypoints_xy.assign(2 * r.waypoints.size(), std::numeric_limits<double>::quiet_NaN());
+        for (size_t i = 0; i < r.waypoints.size(); ++i)
+            if (r.waypoints[i] >= 0) {
+                r.waypoints_xy[2 * i] = x0 + ((double)(r.waypoints[i] % nx) + 0.5) * cell;
+                r.waypoints_xy[2 * i + 1] = y0 + ((double)(r.waypoints[i] / nx) + 0.5) * cell;
+            }
+        return r;
+    }
     // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},
     // the prior first) and every shift of [-wx, wx] x [-wy, wy] map cells, the sum of log_odds under the occupied cells of the
     // frame's visibility bytes; the best by the contract's order, and `pose`, the winning candidate moved by the winning shift

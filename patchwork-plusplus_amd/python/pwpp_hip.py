@@ -113,6 +113,14 @@ class ReachParams(ctypes.Structure):  # pwpp_reach_params (24 bytes): the cost o
 REACH_NONE = 0x7FFFFFFF  # PWPP_REACH_NONE: no path from the source
 
 
+class RouteParams(ctypes.Structure):  # pwpp_route_params (16 bytes): the cells and waypoints stored per route, how far a shortcut looks, what its line may cross
+    _fields_ = [("max_cells", ctypes.c_int32), ("max_waypoints", ctypes.c_int32), ("look", ctypes.c_int32), ("line_cost", ctypes.c_int32)]
+
+
+ROUTE_OK, ROUTE_NONE, ROUTE_BROKEN = 0, 1, 2  # PWPP_ROUTE_*: the status of a route
+ROUTE_DTYPE = np.dtype([(n, "<i4") for n in ("status", "cells", "cost", "edge_steps", "corner_steps", "max_term", "min_dist2", "waypoints")])  # pwpp_route (32 bytes)
+
+
 class CostmapParams(ctypes.Structure):  # pwpp_costmap_params (24 bytes): the layers' mask, what an unknown occupancy / terrain byte counts as, when unknown wins
     _fields_ = [("layers", ctypes.c_int32), ("occupancy_unknown", ctypes.c_int32), ("terrain_unknown", ctypes.c_int32),
                 ("unknown_below", ctypes.c_int32), ("pad_", ctypes.c_int32 * 2)]
@@ -277,6 +285,10 @@ def load():
             L.pwpp_reach_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, vp]
             L.pwpp_reach_ground.argtypes = [vp, gp, ci, ci, ci, tp, rp, vp, ci, vp, vp, vp]
             L.pwpp_grid_cell_of.argtypes = [gp, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "pwpp_route_grid"):  # (as above: an older build has no routes)
+            rp, qp = ctypes.POINTER(ReachParams), ctypes.POINTER(RouteParams)
+            L.pwpp_route_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, vp, ci, ci, qp, vp, vp, vp]
+            L.pwpp_plan_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, ci, ci, qp, vp, vp, vp, vp, vp]
         if hasattr(L, "pwpp_costmap_grid"):  # (as above: an older build has no costmap)
             gp, tp, cp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams), ctypes.POINTER(CostmapParams)
             cf, cd, i32 = ctypes.c_float, ctypes.c_double, ctypes.c_int32
@@ -1545,6 +1557,84 @@ class Handle:
         g, frames, src = self._look(x0, y0, cell, nx, ny, frame_first, frames, ground_only, source_xy)
         self._check(self._L.pwpp_reach_ground(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, ctypes.byref(terrain_params),
                                               ctypes.byref(params), _vp(src) if src.size else None, len(src), _dp(reach_ptr), _dp(from_ptr), _dp(cost_ptr)))
+
+    @staticmethod
+    def _starts(start, frames):
+        """The starts as the calls take them: (n_starts, 2) for every frame or (frames, n_starts, 2) -> (array, n_start_sets, n_starts)."""
+        st = np.ascontiguousarray(np.asarray(start, np.int32))
+        if st.ndim == 1:
+            st = st.reshape(1, 2)
+        if st.ndim not in (2, 3) or st.shape[-1] != 2:
+            raise ValueError("start: (x, y), (n_starts, 2) or (frames, n_starts, 2) cells expected")
+        return st, (1 if st.ndim == 2 else st.shape[0]), st.shape[-2]
+
+    def route_grid(self, cost, source, params, frm, start, route_params, dist2=None):
+        """The routes on a reach field: for every frame of the (frames, ny, nx) or (ny, nx) int8 cost images and every start cell the
+        chain of `frm` (the from image of reach_grid on the same cost, source, ReachParams `params` and dist2) from the start to the
+        frame's source.  start: (x, y), (n_starts, 2) cells for every frame or (frames, n_starts, 2).  Returns (routes, cells,
+        waypoints): a (frames, n_starts) array of ROUTE_DTYPE rows, the (frames, n_starts, max_cells) int32 cell indices and the
+        (frames, n_starts, max_waypoints) int32 waypoint cells of the RouteParams `route_params`, -1 behind a list's end (None for a
+        limit of 0).  The rules: include/pwpp.h."""
+        cst = np.ascontiguousarray(cost, np.int8)
+        c3 = cst.reshape((1,) + cst.shape) if cst.ndim == 2 else cst
+        if c3.ndim != 3:
+            raise ValueError("cost: a (frames, ny, nx) or (ny, nx) image expected")
+        d3 = None if dist2 is None else np.ascontiguousarray(dist2, np.int32)
+        f3 = np.ascontiguousarray(frm, np.int32)
+        if f3.size != c3.size or (d3 is not None and d3.size != c3.size):
+            raise ValueError("from, dist2: images of cost's shape expected")
+        src = np.ascontiguousarray(np.asarray(source, np.int32).reshape(-1, 2))
+        st, sets, n = self._starts(start, c3.shape[0])
+        routes, cells, wps = self._route_outputs(c3.shape[0], n, route_params)
+        self._check(self._L.pwpp_route_grid(self._h, c3.shape[2], c3.shape[1], c3.shape[0], MEM_HOST, _hp(c3), _hp(d3), ctypes.byref(params), _hp(src),
+                                            len(src), _hp(f3), _hp(st), sets, n, ctypes.byref(route_params), _hp(routes), _hp(cells), _hp(wps)))
+        return routes, cells, wps
+
+    @staticmethod
+    def _route_outputs(frames, n, q):
+        routes = np.empty((frames, n), ROUTE_DTYPE)
+        cells = np.empty((frames, n, q.max_cells), np.int32) if q.max_cells > 0 else None
+        wps = np.empty((frames, n, q.max_waypoints), np.int32) if q.max_waypoints > 0 else None
+        return routes, cells, wps
+
+    def route_grid_device(self, nx, ny, frames, cost_ptr, source, params, from_ptr, start, route_params, routes_ptr, cells_ptr=0, waypoints_ptr=0, dist2_ptr=0):
+        """route_grid on device memory: addresses of the (frames, ny, nx) int8 cost images (any address), of the int32 from and dist2
+        images, of the (frames, n_starts) rows of 32 bytes and of the int32 lists (0: none; 4-byte aligned); source and start stay
+        host arrays.  Enqueued on the handle's stream; complete after synchronize()."""
+        src = np.ascontiguousarray(np.asarray(source, np.int32).reshape(-1, 2))
+        st, sets, n = self._starts(start, frames)
+        self._check(self._L.pwpp_route_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(cost_ptr), _dp(dist2_ptr), ctypes.byref(params),
+                                            _vp(src) if src.size else None, len(src), _dp(from_ptr), _vp(st) if st.size else None, sets, n,
+                                            ctypes.byref(route_params), _dp(routes_ptr), _dp(cells_ptr), _dp(waypoints_ptr)))
+
+    def plan_grid(self, cost, source, params, start, route_params, dist2=None, want_field=False):
+        """reach_grid and route_grid on its from in one call: (routes, cells, waypoints) as route_grid returns them; want_field: then
+        (reach, from) as reach_grid returns them too -- otherwise the field stays on the device."""
+        cst = np.ascontiguousarray(cost, np.int8)
+        c3 = cst.reshape((1,) + cst.shape) if cst.ndim == 2 else cst
+        if c3.ndim != 3:
+            raise ValueError("cost: a (frames, ny, nx) or (ny, nx) image expected")
+        d3 = None if dist2 is None else np.ascontiguousarray(dist2, np.int32)
+        if d3 is not None and d3.size != c3.size:
+            raise ValueError("dist2: an image of cost's shape expected")
+        src = np.ascontiguousarray(np.asarray(source, np.int32).reshape(-1, 2))
+        st, sets, n = self._starts(start, c3.shape[0])
+        routes, cells, wps = self._route_outputs(c3.shape[0], n, route_params)
+        reach = np.empty(cst.shape, np.int32) if want_field else None
+        frm = np.empty(cst.shape, np.int32) if want_field else None
+        self._check(self._L.pwpp_plan_grid(self._h, c3.shape[2], c3.shape[1], c3.shape[0], MEM_HOST, _hp(c3), _hp(d3), ctypes.byref(params), _hp(src), len(src),
+                                           _hp(st), sets, n, ctypes.byref(route_params), _hp(routes), _hp(cells), _hp(wps), _hp(reach), _hp(frm)))
+        return (routes, cells, wps) + ((reach, frm) if want_field else ())
+
+    def plan_grid_device(self, nx, ny, frames, cost_ptr, source, params, start, route_params, routes_ptr, cells_ptr=0, waypoints_ptr=0, dist2_ptr=0,
+                         reach_ptr=0, from_ptr=0):
+        """plan_grid on device memory: addresses as in route_grid_device; reach_ptr, from_ptr: the int32 images of the field (0: kept in
+        the handle's buffer).  Enqueued on the handle's stream; complete after synchronize()."""
+        src = np.ascontiguousarray(np.asarray(source, np.int32).reshape(-1, 2))
+        st, sets, n = self._starts(start, frames)
+        self._check(self._L.pwpp_plan_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(cost_ptr), _dp(dist2_ptr), ctypes.byref(params),
+                                           _vp(src) if src.size else None, len(src), _vp(st) if st.size else None, sets, n, ctypes.byref(route_params),
+                                           _dp(routes_ptr), _dp(cells_ptr), _dp(waypoints_ptr), _dp(reach_ptr), _dp(from_ptr)))
 
     def costmap_grid(self, params, occupancy=None, terrain=None, dist2=None, curve=None, want_why=False):
         """The costmap of (frames, ny, nx) or (ny, nx) images under the CostmapParams `params`: the int8 occupancy bytes, the int8

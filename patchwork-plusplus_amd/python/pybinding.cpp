@@ -121,6 +121,25 @@ py::tuple reach_tuple(const Reach &r) {
     return py::make_tuple(terrain_image(r.reach, r.nx, r.ny), terrain_image(r.from, r.nx, r.ny));
 }
 
+// (rows (n, 8) int32 -- status, cells, cost, edge_steps, corner_steps, max_term, min_dist2, waypoints --, cells (n, max_cells), waypoints
+// (n, max_waypoints), waypoints_xy (n, max_waypoints, 2)) of a routes call
+template <class Routes>
+py::tuple routes_tuple(const Routes &r) {
+    py::array_t<int32_t> rows({(py::ssize_t)r.n, (py::ssize_t)8}), cells({(py::ssize_t)r.n, (py::ssize_t)r.max_cells}), wps({(py::ssize_t)r.n, (py::ssize_t)r.max_waypoints});
+    py::array_t<double> xy({(py::ssize_t)r.n, (py::ssize_t)r.max_waypoints, (py::ssize_t)2});
+    if (!r.rows.empty()) std::memcpy(rows.mutable_data(), r.rows.data(), r.rows.size() * sizeof(r.rows[0]));
+    std::copy(r.cells.begin(), r.cells.end(), cells.mutable_data());
+    std::copy(r.waypoints.begin(), r.waypoints.end(), wps.mutable_data());
+    std::copy(r.waypoints_xy.begin(), r.waypoints_xy.end(), xy.mutable_data());
+    return py::make_tuple(rows, cells, wps, xy);
+}
+// n x {x, y} positions in metres from any sequence of numbers
+std::vector<double> positions_of(const py::object &xy) {
+    const auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(xy);
+    if (!a || a.size() % 2 != 0) throw std::invalid_argument("starts_xy: n x {x, y} expected");
+    return std::vector<double>(a.data(), a.data() + a.size());
+}
+
 // (cost, why) of a costmap call as (ny, nx) arrays
 template <class Costmap>
 py::tuple costmap_tuple(const Costmap &c) {
@@ -210,6 +229,12 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def_readwrite("slope_max", &PatchWorkpp::TerrainParams::slope_max)
         .def_readwrite("rough_max", &PatchWorkpp::TerrainParams::rough_max);
 
+    py::class_<PatchWorkpp::RouteParams>(m, "RouteParams")  // the list limits and the shortcut rule of getRoutes and planRoutes
+        .def(py::init<>())
+        .def_readwrite("max_cells", &PatchWorkpp::RouteParams::max_cells)
+        .def_readwrite("max_waypoints", &PatchWorkpp::RouteParams::max_waypoints)
+        .def_readwrite("look", &PatchWorkpp::RouteParams::look)
+        .def_readwrite("line_cost", &PatchWorkpp::RouteParams::line_cost);
     py::class_<PatchWorkpp::ReachParams>(m, "ReachParams")  // the step costs and the limits of getReach and fusedReach
         .def(py::init<>())
         .def_readwrite("base", &PatchWorkpp::ReachParams::base)
@@ -343,6 +368,25 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("map"), py::arg("terrain_params") = PatchWorkpp::TerrainParams(), py::arg("reach_params") = PatchWorkpp::ReachParams(),
              py::arg("source_x") = 0.0, py::arg("source_y") = 0.0)
+        .def("getRoutes",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, const py::object &starts_xy, const PatchWorkpp::TerrainParams &terrain_params,
+                const PatchWorkpp::ReachParams &reach_params, const PatchWorkpp::RouteParams &route_params, double source_x, double source_y, bool ground_only) {
+                 return routes_tuple(s.getRoutes(x0, y0, cell, nx, ny, positions_of(starts_xy), terrain_params, reach_params, route_params, source_x, source_y, ground_only));
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("starts_xy"), py::arg("terrain_params") = PatchWorkpp::TerrainParams(),
+             py::arg("reach_params") = PatchWorkpp::ReachParams(), py::arg("route_params") = PatchWorkpp::RouteParams(), py::arg("source_x") = 0.0,
+             py::arg("source_y") = 0.0, py::arg("ground_only") = false)
+        .def("planRoutes",
+             [](PatchWorkpp &s, const py::object &cost, double x0, double y0, double cell, int nx, int ny, const py::object &starts_xy,
+                const PatchWorkpp::ReachParams &reach_params, const PatchWorkpp::RouteParams &route_params, double source_x, double source_y) {
+                 const auto c = py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(cost);
+                 if (!c) throw std::invalid_argument("cost: an int8 image expected");
+                 return routes_tuple(s.planRoutes(std::vector<int8_t>(c.data(), c.data() + c.size()), x0, y0, cell, nx, ny, positions_of(starts_xy), reach_params,
+                                                  route_params, source_x, source_y));
+             },
+             py::arg("cost"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("starts_xy"),
+             py::arg("reach_params") = PatchWorkpp::ReachParams(), py::arg("route_params") = PatchWorkpp::RouteParams(), py::arg("source_x") = 0.0,
+             py::arg("source_y") = 0.0)
         .def_static("inflationCurve",
                     [](double cell, double inscribed, double radius, double decay, int peak) {
                         const std::vector<uint8_t> c = PatchWorkpp::inflationCurve(cell, inscribed, radius, decay, peak);
