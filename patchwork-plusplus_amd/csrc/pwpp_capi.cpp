@@ -1204,6 +1204,12 @@ class Staging {
         if (dir == kKept || dir == kUpload || host_) words_ += (words + align_ - 1) / align_ * align_;
         return n_++;
     }
+    // A byte image of `bytes` bytes (occupancy, cost, a class per cell): whole words in the buffer, the bytes copied.  An optional one that is absent --
+    // no pointer, and not kKept -- declares 0 words like any absent array.
+    int add_bytes(size_t bytes, const void *user, Dir dir) {
+        const bool present = user || dir == kKept;
+        return add(present ? (bytes + 3) / 4 : 0, user, dir, present ? bytes : 0);
+    }
     int add_upload(std::vector<uint32_t> &&words) {  // (a vector's words stay where they are when it moves)
         up_.push_back(std::move(words));
         return add(up_.back().size(), up_.back().data(), kUpload);
@@ -1259,6 +1265,33 @@ int set_output(pwpp_handle *h, Output which, int on) {
     if (rc) return rc;
     h->outputs = on ? h->outputs | bit(which) : h->outputs & ~bit(which);
     return PWPP_OK;
+}
+
+// The options that pick a kernel variant, 0 .. max: what a value means stands at the handle's member.
+struct PathOption {
+    const char *name;
+    int pwpp_handle::*member;
+    int max;
+};
+constexpr PathOption kPathOptions[] = {
+    {"records_path", &pwpp_handle::records_path, 2},
+    {"clusters_path", &pwpp_handle::clusters_path, 1},
+    {"distance_path", &pwpp_handle::distance_path, 1},
+    {"visibility_path", &pwpp_handle::visibility_path, 1},
+    {"fusion_path", &pwpp_handle::fusion_path, 1},
+    {"elevation_path", &pwpp_handle::elevation_path, 2},
+    {"terrain_path", &pwpp_handle::terrain_path, 2},
+    {"reach_path", &pwpp_handle::reach_path, 2},
+    {"route_path", &pwpp_handle::route_path, 2},
+    {"costmap_path", &pwpp_handle::costmap_path, 2},
+    {"match_path", &pwpp_handle::match_path, 2},
+    {"evidence_path", &pwpp_handle::evidence_path, 2},
+    {"boxes_path", &pwpp_handle::boxes_path, 2},
+};
+const PathOption *path_option(const std::string &name) {
+    for (const PathOption &o : kPathOptions)
+        if (name == o.name) return &o;
+    return nullptr;
 }
 
 }  // namespace
@@ -2113,58 +2146,10 @@ int pwpp_set_option(pwpp_handle *h, const char *name, const char *value) {
         HIPCHK(hipMemsetAsync(h->d_bin_max.p, 0, (size_t)PWPP_NUM_PARTS(h->dp.num_bins) * sizeof(uint32_t), h->stream));
         h->have_observation = false;
         h->table_stale = true;
-    } else if (k == "records_path") {
+    } else if (const PathOption *o = path_option(k)) {
         const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "records_path=%s: 0, 1 or 2 expected", value);
-        h->records_path = v;
-    } else if (k == "clusters_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "clusters_path=%s: 0 or 1 expected", value);
-        h->clusters_path = v;
-    } else if (k == "distance_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "distance_path=%s: 0 or 1 expected", value);
-        h->distance_path = v;
-    } else if (k == "visibility_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "visibility_path=%s: 0 or 1 expected", value);
-        h->visibility_path = v;
-    } else if (k == "fusion_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 1) return fail(PWPP_E_ARG, "fusion_path=%s: 0 or 1 expected", value);
-        h->fusion_path = v;
-    } else if (k == "elevation_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "elevation_path=%s: 0, 1 or 2 expected", value);
-        h->elevation_path = v;
-    } else if (k == "terrain_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "terrain_path=%s: 0, 1 or 2 expected", value);
-        h->terrain_path = v;
-    } else if (k == "reach_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "reach_path=%s: 0, 1 or 2 expected", value);
-        h->reach_path = v;
-    } else if (k == "route_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "route_path=%s: 0, 1 or 2 expected", value);
-        h->route_path = v;
-    } else if (k == "costmap_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "costmap_path=%s: 0, 1 or 2 expected", value);
-        h->costmap_path = v;
-    } else if (k == "match_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "match_path=%s: 0, 1 or 2 expected", value);
-        h->match_path = v;
-    } else if (k == "evidence_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "evidence_path=%s: 0, 1 or 2 expected", value);
-        h->evidence_path = v;
-    } else if (k == "boxes_path") {
-        const int v = std::atoi(value);
-        if (v < 0 || v > 2) return fail(PWPP_E_ARG, "boxes_path=%s: 0, 1 or 2 expected", value);
-        h->boxes_path = v;
+        if (v < 0 || v > o->max) return fail(PWPP_E_ARG, o->max == 1 ? "%s=%s: 0 or 1 expected" : "%s=%s: 0, 1 or 2 expected", o->name, value);
+        h->*(o->member) = v;
     } else if (k == "debug_flags") {
         const int v = std::atoi(value);
         //  the fit-chain probes (4) and the binning / scan / GLE probes (8) write the same 64-entry array
@@ -2353,6 +2338,20 @@ int mem_args(int mem, const char *who) {
     return fail(PWPP_E_ARG, "mem %d: %s PWPP_MEM_HOST or PWPP_MEM_DEVICE", mem, who);
 }
 
+// What a call checks of the number of things it takes one for all frames or one per frame (`noun`: "origins", "poses", "start sets") ...
+int per_frame_count_args(int n, int frames, const char *noun) {
+    if (n < 1 || (n != 1 && n != frames)) return fail(PWPP_E_ARG, "%d %s for %d frames: 1 or one per frame expected", n, noun, frames);
+    return PWPP_OK;
+}
+
+// ... and of such a list of cells, n x {x, y}, on an image of nx x ny cells (`noun`: "origin", "source"): the first one outside is named
+int cells_inside_args(const int32_t *xy, int n, int nx, int ny, const char *noun) {
+    for (int i = 0; i < n; ++i)
+        if (xy[2 * i] < 0 || xy[2 * i] >= nx || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= ny)
+            return fail(PWPP_E_ARG, "%s %d, cell (%d, %d), lies outside the %d x %d cells", noun, i, xy[2 * i], xy[2 * i + 1], nx, ny);
+    return PWPP_OK;
+}
+
 // What PWPP_MEM_DEVICE asks of the caller's arrays (after mem): the first of `a` that is off its alignment, mask + 1 bytes, is named.
 struct Aligned {
     const void *p;
@@ -2471,9 +2470,13 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
 // Each has two entry points: pwpp_*_grid works on the caller's image, pwpp_*_obstacles on the one it first rasterises from the last call's
 // non-ground lists.  An operator states its sections once (*_sections: the kernels' working words and the tables the call built for them
 // first -- upload sections, copied by Staging::begin() -- then what the call stages) and its launch once (*_launch: the launcher's call alone);
-// an entry point checks its arguments, declares the sections and runs one of four tails: run_on_image, run_on_obstacles, run_on_visibility
-// (further down: the obstacle tail under the visibility operator), run_on_ground (the elevation fusion, the terrain and the reach on the ground raster).
+// an entry point checks its arguments, declares the sections and runs one of five tails: run_on_image, run_on_obstacles, run_on_visibility
+// (further down: the obstacle tail under the visibility operator), run_on_labels (further down: the obstacle tail under the labelling and its per-point
+// scatter, for the tracks and the map evidence), run_on_ground (the elevation fusion, the terrain and the reach on the ground raster).
 // The costmap's chain needs both rasters in one staging: it enqueues what run_on_obstacles and run_on_ground enqueue (enqueue_on_*) between one begin() and one end().
+// Stated once for all of them: a count given "1 or one per frame" (per_frame_count_args) and a list of cells inside the image (cells_inside_args), a byte
+// image's section (Staging::add_bytes), the first checks of a labelling (label_first_args) and of a reach on a caller's image (reach_image_args), the
+// terrain analysis as a stage for its cost bytes alone (terrain_cost_sections), the reach's sections for the field and for the routes (reach_sections).
 
 // The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
 // From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
@@ -2605,6 +2608,50 @@ int cluster_launch(pwpp_handle *h, const Staging &st, const ClusterSections &s, 
     return pwpp_launch_label_grid(nx, ny, frames, st.dev<const int32_t>(s.count), st.dev<const float>(s.top), min_count, connectivity, h->clusters_path,
                                   st.dev<int32_t>(s.label), st.dev<void>(s.table), st.dev<int32_t>(s.n), max_clusters, st.dev<uint32_t>(s.work), h->stream);
 }
+
+// The caller's arrays of a labelling of the obstacle grid: what pwpp_label_obstacles and the entry points that append to it pass on.
+struct LabelArrays {
+    int32_t *label, *count;
+    float *top;
+    pwpp_obstacle_cluster *clusters;
+    int32_t *n_clusters;
+    int max_clusters;
+    int32_t *point_cluster;
+};
+
+// What those entry points check first, in this order, after their null pointers; lands the call in flight.  `side_who`: the operator the entry
+// point appends takes at most 32768 cells a side (side_args, `who` as in mem_args); null: nothing is appended.  `cells`: nx * ny * frames.
+int label_first_args(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int connectivity, int frame_first, int frames, int mem,
+                     const LabelArrays &a, const char *side_who, size_t &cells) {
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    if ((rc = cluster_param_args(mem, min_count, connectivity, a.clusters, a.max_clusters))) return rc;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
+    return side_who ? side_args(g->nx, g->ny, side_who) : PWPP_OK;
+}
+
+// The fifth tail, for the operators on the label image of the obstacle grid: raster, labelling, the per-point scatter and the operator, as one enqueued
+// sequence (run_on_obstacles).  The label image stays where it lies: the caller's, or the cluster buffer's in PWPP_MEM_HOST.  `declare` adds its sections
+// behind the labelling's -- it is told the label image's -- and returns its launch; the arguments are checked (label_first_args).
+extern "C++" template <class Declare>  // (the entry points' extern "C" block is open around this namespace)
+int run_on_labels(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int connectivity, int frame_first, int frames, int mem,
+                  size_t cells, const LabelArrays &a, Declare declare) {
+    const int64_t base_first = h->h_base.p[frame_first];
+    const size_t points = a.point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, a.count, a.top, a.label, a.clusters, a.n_clusters, a.max_clusters);
+    const int s_pc = st.add(points, a.point_cluster, Staging::kOut);
+    const auto launch = declare(st, s.label);
+    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
+        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, a.max_clusters);
+        if (lrc == 0 && points != 0) {
+            lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (-1: every point that is not a counted one)
+            if (lrc == 0) lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
+        }
+        return lrc != 0 ? lrc : launch();
+    });
+}
 }  // namespace
 
 int pwpp_label_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, const float *top, int min_count, int connectivity,
@@ -2627,23 +2674,10 @@ int pwpp_label_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
                          int32_t *point_cluster) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !label) return fail(PWPP_E_ARG, "null %s", g ? "label image" : "grid");
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
-    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    const LabelArrays a{label, count, top, clusters, n_clusters, max_clusters, point_cluster};
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
-    const int64_t base_first = h->h_base.p[frame_first];
-    const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
-    Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, count, top, label, clusters, n_clusters, max_clusters);
-    const int s_pc = st.add(points, point_cluster, Staging::kOut);
-    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
-        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, max_clusters);
-        if (lrc != 0 || points == 0) return lrc;
-        lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (-1: every point that is not a counted one)
-        return lrc != 0 ? lrc : pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
-    });
+    if (const int rc = label_first_args(h, g, h_min, h_max, min_count, connectivity, frame_first, frames, mem, a, nullptr, cells)) return rc;
+    return run_on_labels(h, g, h_min, h_max, min_count, connectivity, frame_first, frames, mem, cells, a, [](Staging &, int) { return [] { return 0; }; });
 }
 
 // ---- obstacle distances: every cell's distance to the nearest occupied cell, and that cell ----------------------------------------
@@ -2711,16 +2745,10 @@ namespace {
 static_assert(PWPP_VIS_NONE == PWPP_VIS_FIRST_NONE && PWPP_VIS_BEYOND == PWPP_VIS_FIRST_BEYOND, "the kernels' values of first");
 static_assert(PWPP_OCC_FREE == PWPP_VIS_FREE && PWPP_OCC_OCCUPIED == PWPP_VIS_OCCUPIED && PWPP_OCC_UNKNOWN == PWPP_VIS_UNKNOWN, "the kernels' occupancy bytes");
 constexpr const char *kVisibilityWho = "the visibility takes";
-// what both entry points check of min_count and max_range ...
+// what both entry points check of min_count and max_range
 int visibility_param_args(int min_count, int max_range) {
     if (const int rc = min_count_args(min_count)) return rc;
     if (max_range < 0 || max_range > PWPP_VIS_MAX_SIDE) return fail(PWPP_E_ARG, "max_range %d: 0 (unlimited) .. 32768 cells expected", max_range);
-    return PWPP_OK;
-}
-
-// ... and of the number of origins
-int visibility_origin_count(int n_origins, int frames) {
-    if (n_origins < 1 || (n_origins != 1 && n_origins != frames)) return fail(PWPP_E_ARG, "%d origins for %d frames: 1 or one per frame expected", n_origins, frames);
     return PWPP_OK;
 }
 
@@ -2747,7 +2775,7 @@ int visibility_origin_args(const pwpp_ground_grid *g, float h_min, float h_max, 
     if (rc || (rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
     if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
-    if ((rc = visibility_origin_count(n_origins, frames))) return rc;
+    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
     return frame_cells_of(g, origin_xy, n_origins, "origin", org);
 }
 
@@ -2768,8 +2796,7 @@ VisibilitySections visibility_sections(pwpp_handle *h, Staging &st, int nx, int 
     s.work = st.add(pwpp_visibility_work_words(nx, ny, frames, h->visibility_path), nullptr, Staging::kKept);
     s.org = frame_cells_section(st, org);
     s.count = add_image(st, cells, count, from_raster), s.first = st.add(cells, first, keep && !first ? Staging::kKept : Staging::kOut);
-    if (keep && !occupancy) s.occ = st.add((cells + 3) / 4, nullptr, Staging::kKept);
-    else s.occ = st.add(occupancy ? (cells + 3) / 4 : 0, occupancy, Staging::kOut, occupancy ? cells : 0);
+    s.occ = st.add_bytes(cells, occupancy, keep && !occupancy ? Staging::kKept : Staging::kOut);
     return s;
 }
 // (one origin travels as an argument; one per frame lies in its section)
@@ -2809,10 +2836,8 @@ int pwpp_visibility_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, co
     int rc = image_args(nx, ny, frames, kVisibilityWho, cells);
     if (rc) return rc;
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
-    if ((rc = visibility_origin_count(n_origins, frames))) return rc;
-    for (int i = 0; i < n_origins; ++i)
-        if (origin[2 * i] < 0 || origin[2 * i] >= nx || origin[2 * i + 1] < 0 || origin[2 * i + 1] >= ny)
-            return fail(PWPP_E_ARG, "origin %d, cell (%d, %d), lies outside the %d x %d cells", i, origin[2 * i], origin[2 * i + 1], nx, ny);
+    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
+    if ((rc = cells_inside_args(origin, n_origins, nx, ny, "origin"))) return rc;
     if ((rc = mem_args(mem, kVisibilityWho))) return rc;
     const std::vector<int32_t> org(origin, origin + 2 * (size_t)n_origins);
     Staging st(h, h->d_clusters, mem, kClusterAlign);
@@ -2914,7 +2939,7 @@ struct MapPlan {
 extern "C++" template <class M>  // (pwpp_fusion_map or pwpp_height_map, as in map_grid_args)
 int map_plan_args(const pwpp_ground_grid *g, const M *m, int frames, int n_poses, int per_pose, const int32_t *map_of_frame, int n_maps, const int32_t *shift,
                   MapPlan &plan) {
-    if (n_poses < 1 || (n_poses != 1 && n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", n_poses, frames);
+    if (const int rc = per_frame_count_args(n_poses, frames, "poses")) return rc;
     if (const int rc = FrameMaps{map_of_frame, n_maps}.args(frames)) return rc;
     for (int k = 0; shift && k < n_maps; ++k) plan.moved = plan.moved || shift[2 * (size_t)k] != 0 || shift[2 * (size_t)k + 1] != 0;
     plan.G = PwppFusionGeometry{m->x0, m->y0, m->cell, g->x0, g->y0, g->cell, m->nx, m->ny, g->nx, g->ny, 0.0};
@@ -2969,7 +2994,7 @@ FusionSections fusion_sections(Staging &st, MapPlan &plan, int s_occ, const int1
     s.occ = s_occ;
     s.map_in = st.add(map_in ? map_words : 0, map_in, Staging::kIn, map_in ? map_bytes : 0);
     s.map_out = st.add(map_words, map_out, Staging::kOut, map_bytes);
-    s.map_occ = st.add(map_occupancy ? (plan.map_cells + 3) / 4 : 0, map_occupancy, Staging::kOut, map_occupancy ? plan.map_cells : 0);
+    s.map_occ = st.add_bytes(plan.map_cells, map_occupancy, Staging::kOut);
     return s;
 }
 int fusion_launch(pwpp_handle *h, const Staging &st, const FusionSections &s, const MapPlan &plan, const PwppFusionParams &P, int frames) {
@@ -2995,7 +3020,7 @@ int pwpp_fuse_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int me
     if ((rc = fusion_args(g, frames, pose, n_poses, map_of_frame, m, n_maps, shift, map_in, map_out, map_occupancy, plan, P))) return rc;
     if ((rc = mem_args(mem, kFusionWho))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_occ = st.add((cells + 3) / 4, occupancy, Staging::kIn, cells);
+    const int s_occ = st.add_bytes(cells, occupancy, Staging::kIn);
     const FusionSections s = fusion_sections(st, plan, s_occ, map_in, map_out, map_occupancy);
     return run_on_image(h, st, [&] { return fusion_launch(h, st, s, plan, P, frames); });
 }
@@ -3046,8 +3071,7 @@ int match_args(const pwpp_ground_grid *g, int frames, const double *candidates, 
                const pwpp_fusion_map *m, int n_maps, int wx, int wy, const int64_t *scores, MatchPlan &plan) {
     if (const int rc = map_grid_args(g, m, n_maps, kMatchWho, plan.map_cells)) return rc;
     if (n_candidates < 1 || n_candidates > PWPP_MATCH_MAX_CANDIDATES) return fail(PWPP_E_ARG, "%d candidates: 1 .. 256 expected", n_candidates);
-    if (n_sets < 1 || (n_sets != 1 && n_sets != frames))
-        return fail(PWPP_E_ARG, "%d candidate sets for %d frames: 1 or one per frame expected", n_sets, frames);
+    if (const int rc = per_frame_count_args(n_sets, frames, "candidate sets")) return rc;
     if (wx < 0 || wx > PWPP_MATCH_MAX_WINDOW || wy < 0 || wy > PWPP_MATCH_MAX_WINDOW)
         return fail(PWPP_E_ARG, "window wx %d, wy %d: 0 .. 64 cells expected", wx, wy);
     if ((int64_t)frames * (int64_t)n_candidates > ((int64_t)1 << 24))
@@ -3113,7 +3137,7 @@ int pwpp_match_grid(pwpp_handle *h, const pwpp_ground_grid *g, int frames, int m
     if ((rc = mem_args(mem, kMatchWho))) return rc;
     if ((rc = match_alignment_args(mem, best, scores))) return rc;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_occ = st.add((cells + 3) / 4, occupancy, Staging::kIn, cells);
+    const int s_occ = st.add_bytes(cells, occupancy, Staging::kIn);
     const MatchSections s = match_sections(st, plan, frames, s_occ, map, best, scores);
     return run_on_image(h, st, [&] { return match_launch(h, st, s, plan, frames); });
 }
@@ -3278,13 +3302,21 @@ struct TerrainSections {
 };
 TerrainSections terrain_sections(Staging &st, size_t cells, int s_height, float *step, float *slope, float *rough, uint8_t *count, int8_t *cost) {
     TerrainSections s;
-    const size_t byte_words = (cells + 3) / 4;
     s.height = s_height;
     s.step = st.add(step ? cells : 0, step, Staging::kOut);
     s.slope = st.add(slope ? cells : 0, slope, Staging::kOut);
     s.rough = st.add(rough ? cells : 0, rough, Staging::kOut);
-    s.count = st.add(count ? byte_words : 0, count, Staging::kOut, count ? cells : 0);
-    s.cost = st.add(cost ? byte_words : 0, cost, Staging::kOut, cost ? cells : 0);
+    s.count = st.add_bytes(cells, count, Staging::kOut);
+    s.cost = st.add_bytes(cells, cost, Staging::kOut);
+    return s;
+}
+// The analysis as a stage of a longer chain, for its cost bytes alone (the reach and the costmap on the ground raster): the raster's height kept in the
+// buffer, one section without words for the four outputs nobody asks for -- null pointers -- and the cost: the caller's where given, else kept too.
+TerrainSections terrain_cost_sections(Staging &st, size_t cells, int8_t *cost) {
+    TerrainSections s;
+    s.height = add_image(st, cells, nullptr, true);
+    s.step = s.slope = s.rough = s.count = st.add(0, nullptr, Staging::kOut);
+    s.cost = st.add_bytes(cells, cost, cost ? Staging::kOut : Staging::kKept);
     return s;
 }
 int terrain_launch(pwpp_handle *h, const Staging &st, const TerrainSections &s, const PwppTerrainRule &rule, int nx, int ny, int frames) {
@@ -3355,28 +3387,44 @@ int reach_param_args(const pwpp_reach_params *p, int nx, int ny, bool with_dist2
     return PWPP_OK;
 }
 
-// ... and of the number of sources
-int reach_source_count(int n_sources, int frames) {
-    if (n_sources < 1 || (n_sources != 1 && n_sources != frames)) return fail(PWPP_E_ARG, "%d sources for %d frames: 1 or one per frame expected", n_sources, frames);
-    return PWPP_OK;
+// What the entry points on a caller's cost image check first, in the header's order, after their null pointers: the image's shape
+// (`cells`: nx * ny * frames), the parameters, the number of sources and the source cells.  Touches no handle.
+int reach_image_args(int nx, int ny, int frames, const int32_t *dist2, const pwpp_reach_params *p, const int32_t *source, int n_sources, size_t &cells,
+                     PwppReachRule &rule) {
+    int rc = image_args(nx, ny, frames, kReachWho, cells);
+    if (rc) return rc;
+    if ((rc = reach_param_args(p, nx, ny, dist2 != nullptr, rule))) return rc;
+    if ((rc = per_frame_count_args(n_sources, frames, "sources"))) return rc;
+    return cells_inside_args(source, n_sources, nx, ny, "source");
 }
 
+// What becomes of the field (reach, from) of a call: written for the caller (from where asked for); ... and kept in the buffer where the caller gives
+// no pointer -- the routes read it there; or not computed at all: the caller's `from` is read by the routes, and there is no working image, defect
+// word or reach section.
+enum class ReachField { kWritten, kKept, kRead };
+
 // (the working image, the defect word and the sources first; `src`: the source cells, n_sources x {sx, sy}, checked; `cost` is the
-// cost bytes' section: the caller's, or the terrain's.  In PWPP_MEM_HOST the defect word comes back with the images.  `keep`: both
-// images lie in the buffer where the caller gives no pointer -- the routes read them there.)
+// cost bytes' section: the caller's, or the terrain's.  In PWPP_MEM_HOST the defect word comes back with the images.)
 struct ReachSections {
     int term, flag, src, cost, dist2, reach, from;
 };
 ReachSections reach_sections(Staging &st, int mem, int nx, int ny, int frames, size_t cells, int s_cost, const std::vector<int32_t> &src, const int32_t *dist2,
-                             int32_t *reach, int32_t *from, uint32_t *flag_host, bool keep = false) {
-    ReachSections s;
-    s.term = st.add(pwpp_reach_work_words(nx, ny, frames), nullptr, Staging::kKept);
-    s.flag = mem == PWPP_MEM_HOST ? st.add(1, flag_host, Staging::kOut) : st.add(1, nullptr, Staging::kKept);
+                             int32_t *reach, const int32_t *from, uint32_t *flag_host, ReachField field = ReachField::kWritten) {
+    ReachSections s{};
+    const bool computed = field != ReachField::kRead, keep = field == ReachField::kKept;
+    if (computed) {
+        s.term = st.add(pwpp_reach_work_words(nx, ny, frames), nullptr, Staging::kKept);
+        s.flag = mem == PWPP_MEM_HOST ? st.add(1, flag_host, Staging::kOut) : st.add(1, nullptr, Staging::kKept);
+    }
     s.src = frame_cells_section(st, src);
     s.cost = s_cost;
     s.dist2 = st.add(dist2 ? cells : 0, dist2, Staging::kIn);
-    s.reach = st.add(cells, reach, keep && !reach ? Staging::kKept : Staging::kOut);
-    s.from = st.add(from || keep ? cells : 0, from, keep && !from ? Staging::kKept : Staging::kOut);
+    if (computed) {
+        s.reach = st.add(cells, reach, keep && !reach ? Staging::kKept : Staging::kOut);
+        s.from = st.add(from || keep ? cells : 0, from, keep && !from ? Staging::kKept : Staging::kOut);
+    } else {
+        s.from = st.add(cells, from, Staging::kIn);
+    }
     return s;
 }
 // (one source travels as an argument; one per frame lies in its section)
@@ -3398,21 +3446,16 @@ int pwpp_reach_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const i
     if (!cost || !p || !source || !reach)
         return fail(PWPP_E_ARG, "null %s", !cost ? "cost image" : (!p ? "reach parameters" : (!source ? "source" : "reach image")));
     size_t cells = 0;
-    int rc = image_args(nx, ny, frames, kReachWho, cells);
-    if (rc) return rc;
     PwppReachRule rule;
-    if ((rc = reach_param_args(p, nx, ny, dist2 != nullptr, rule))) return rc;
-    if ((rc = reach_source_count(n_sources, frames))) return rc;
-    for (int i = 0; i < n_sources; ++i)
-        if (source[2 * i] < 0 || source[2 * i] >= nx || source[2 * i + 1] < 0 || source[2 * i + 1] >= ny)
-            return fail(PWPP_E_ARG, "source %d, cell (%d, %d), lies outside the %d x %d cells", i, source[2 * i], source[2 * i + 1], nx, ny);
+    int rc = reach_image_args(nx, ny, frames, dist2, p, source, n_sources, cells, rule);
+    if (rc) return rc;
     if ((rc = range_args({{cost, cells, "cost"}, {dist2, cells * 4, "dist2"}, {reach, cells * 4, "reach"}, {from, cells * 4, "from"}}, {}, false))) return rc;
     if ((rc = mem_args(mem, kReachWho))) return rc;
     if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}, {reach, 3u, "reach image"}, {from, 3u, "from image"}}))) return rc;
     const std::vector<int32_t> src(source, source + 2 * (size_t)n_sources);
     uint32_t flag_host = 0;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_cost = st.add((cells + 3) / 4, cost, Staging::kIn, cells);
+    const int s_cost = st.add_bytes(cells, cost, Staging::kIn);
     const ReachSections s = reach_sections(st, mem, nx, ny, frames, cells, s_cost, src, dist2, reach, from, &flag_host);
     return reach_defect(run_on_image(h, st, [&] { return reach_launch(h, st, s, rule, nx, ny, frames, src); }), flag_host);
 }
@@ -3432,7 +3475,7 @@ int pwpp_reach_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first
     if ((rc = terrain_args(tp, g->cell, cells, nullptr, nullptr, nullptr, nullptr, nullptr, cost, terrain_rule))) return rc;
     if ((rc = reach_param_args(p, g->nx, g->ny, false, rule))) return rc;
     if ((rc = grid_geometry_args(g))) return rc;  // (the sources need the grid)
-    if ((rc = reach_source_count(n_sources, frames))) return rc;
+    if ((rc = per_frame_count_args(n_sources, frames, "sources"))) return rc;
     std::vector<int32_t> src;
     if ((rc = frame_cells_of(g, source_xy, n_sources, "source", src))) return rc;
     if ((rc = range_args({{cost, cells, "cost"}, {reach, cells * 4, "reach"}, {from, cells * 4, "from"}}, {}, false))) return rc;
@@ -3440,12 +3483,9 @@ int pwpp_reach_ground(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first
     if ((rc = alignment_args(mem, {{reach, 3u, "reach image"}, {from, 3u, "from image"}}))) return rc;
     uint32_t flag_host = 0;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_height = add_image(st, cells, nullptr, true);
-    const int none = st.add(0, nullptr, Staging::kOut);  // (an output of the terrain analysis that nobody asks for: a null pointer)
-    const int s_cost = cost ? st.add((cells + 3) / 4, cost, Staging::kOut, cells) : st.add((cells + 3) / 4, nullptr, Staging::kKept);
-    const TerrainSections t{s_height, none, none, none, none, s_cost};
-    const ReachSections s = reach_sections(st, mem, g->nx, g->ny, frames, cells, s_cost, src, nullptr, reach, from, &flag_host);
-    return reach_defect(run_on_ground(h, st, g, frame_first, frames, s_height, -1,
+    const TerrainSections t = terrain_cost_sections(st, cells, cost);
+    const ReachSections s = reach_sections(st, mem, g->nx, g->ny, frames, cells, t.cost, src, nullptr, reach, from, &flag_host);
+    return reach_defect(run_on_ground(h, st, g, frame_first, frames, t.height, -1,
                                       [&] {
                                           const int lrc = terrain_launch(h, st, t, terrain_rule, g->nx, g->ny, frames);
                                           return lrc != 0 ? lrc : reach_launch(h, st, s, rule, g->nx, g->ny, frames, src);
@@ -3478,8 +3518,7 @@ int route_args(const pwpp_route_params *q, int nx, int ny, int frames, const int
     if (q->max_waypoints < 0) return fail(PWPP_E_ARG, "max_waypoints %d: 0 (no shortcut search) or more expected", q->max_waypoints);
     if (q->look < 1 || q->look > PWPP_ROUTE_MAX_LOOK) return fail(PWPP_E_ARG, "look %d: 1 .. %d expected", q->look, PWPP_ROUTE_MAX_LOOK);
     if (q->line_cost < 0 || q->line_cost > 100) return fail(PWPP_E_ARG, "line_cost %d: 0 .. 100 expected", q->line_cost);
-    if (n_start_sets < 1 || (n_start_sets != 1 && n_start_sets != frames))
-        return fail(PWPP_E_ARG, "%d start sets for %d frames: 1 or one per frame expected", n_start_sets, frames);
+    if (const int rc = per_frame_count_args(n_start_sets, frames, "start sets")) return rc;
     if (n_starts < 1 || n_starts > PWPP_ROUTE_MAX_STARTS) return fail(PWPP_E_ARG, "%d starts: 1 .. %d expected", n_starts, PWPP_ROUTE_MAX_STARTS);
     const int64_t per_route = std::max<int64_t>(std::max(q->max_cells, q->max_waypoints), 1);
     if ((int64_t)frames * (int64_t)n_starts > (int64_t)INT32_MAX / per_route)
@@ -3518,17 +3557,11 @@ int route_launch(pwpp_handle *h, const Staging &st, const ReachSections &r, cons
                               st.dev<int32_t>(s.wps), h->route_path, h->stream);
 }
 
-// what both entry points check between the null pointers and the overlaps
+// what both entry points check between the null pointers and the overlaps: what pwpp_reach_grid checks there, then the routes' own
 int route_common_args(int nx, int ny, int frames, const int32_t *dist2, const pwpp_reach_params *p, const int32_t *source, int n_sources, const pwpp_route_params *q,
                       const int32_t *start, int n_start_sets, int n_starts, const int32_t *cells, const int32_t *waypoints, size_t &n_cells, PwppReachRule &rule,
                       PwppRouteRule &route, std::vector<uint32_t> &starts) {
-    int rc = image_args(nx, ny, frames, kReachWho, n_cells);
-    if (rc) return rc;
-    if ((rc = reach_param_args(p, nx, ny, dist2 != nullptr, rule))) return rc;
-    if ((rc = reach_source_count(n_sources, frames))) return rc;
-    for (int i = 0; i < n_sources; ++i)
-        if (source[2 * i] < 0 || source[2 * i] >= nx || source[2 * i + 1] < 0 || source[2 * i + 1] >= ny)
-            return fail(PWPP_E_ARG, "source %d, cell (%d, %d), lies outside the %d x %d cells", i, source[2 * i], source[2 * i + 1], nx, ny);
+    if (const int rc = reach_image_args(nx, ny, frames, dist2, p, source, n_sources, n_cells, rule)) return rc;
     return route_args(q, nx, ny, frames, start, n_start_sets, n_starts, cells, waypoints, route, starts);
 }
 }  // namespace
@@ -3557,11 +3590,8 @@ int pwpp_route_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const i
         return rc;
     const std::vector<int32_t> src(source, source + 2 * (size_t)n_sources);
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    ReachSections r{};
-    r.cost = st.add((n_cells + 3) / 4, cost, Staging::kIn, n_cells);
-    r.src = frame_cells_section(st, src);
-    r.dist2 = st.add(dist2 ? n_cells : 0, dist2, Staging::kIn);
-    r.from = st.add(n_cells, from, Staging::kIn);
+    const int s_cost = st.add_bytes(n_cells, cost, Staging::kIn);
+    const ReachSections r = reach_sections(st, mem, nx, ny, frames, n_cells, s_cost, src, dist2, nullptr, from, nullptr, ReachField::kRead);
     const RouteSections s = route_sections(st, std::move(starts), n_routes, route, routes, cells, waypoints);
     return run_on_image(h, st, [&] { return route_launch(h, st, r, s, rule, route, nx, ny, frames, src, n_start_sets, n_starts); });
 }
@@ -3592,8 +3622,8 @@ int pwpp_plan_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const in
     const std::vector<int32_t> src(source, source + 2 * (size_t)n_sources);
     uint32_t flag_host = 0;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const int s_cost = st.add((n_cells + 3) / 4, cost, Staging::kIn, n_cells);
-    const ReachSections r = reach_sections(st, mem, nx, ny, frames, n_cells, s_cost, src, dist2, reach, from, &flag_host, true);
+    const int s_cost = st.add_bytes(n_cells, cost, Staging::kIn);
+    const ReachSections r = reach_sections(st, mem, nx, ny, frames, n_cells, s_cost, src, dist2, reach, from, &flag_host, ReachField::kKept);
     const RouteSections s = route_sections(st, std::move(starts), n_routes, route, routes, cells, waypoints);
     return reach_defect(run_on_image(h, st,
                                      [&] {
@@ -3647,8 +3677,8 @@ CostmapSections costmap_sections(Staging &st, size_t cells, const PwppCostmapRul
     costmap_curve_words(rule, curve, words);
     s.curve = rule.n_curve > 0 ? st.add_upload(std::move(words)) : st.add(0, nullptr, Staging::kKept);
     s.occ = s_occ, s.terrain = s_terrain, s.dist2 = s_dist2;
-    s.cost = st.add((cells + 3) / 4, cost, Staging::kOut, cells);
-    s.why = st.add(why ? (cells + 3) / 4 : 0, why, Staging::kOut, why ? cells : 0);
+    s.cost = st.add_bytes(cells, cost, Staging::kOut);
+    s.why = st.add_bytes(cells, why, Staging::kOut);
     return s;
 }
 int costmap_launch(pwpp_handle *h, const Staging &st, const CostmapSections &s, const PwppCostmapRule &rule, size_t cells) {
@@ -3687,13 +3717,11 @@ int pwpp_costmap_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const
         return rc;
     if ((rc = mem_args(mem, kCostmapWho))) return rc;
     if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}}))) return rc;
-    const size_t byte_words = (cells + 3) / 4;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     // (an image whose layer is off is not read: it is not staged either)
     if (!(rule.layers & PWPP_COSTMAP_OCCUPANCY) && !own_distances) occupancy = nullptr;
     if (!(rule.layers & PWPP_COSTMAP_TERRAIN)) terrain = nullptr;
-    const int s_occ = st.add(occupancy ? byte_words : 0, occupancy, Staging::kIn, occupancy ? cells : 0);
-    const int s_terrain = st.add(terrain ? byte_words : 0, terrain, Staging::kIn, terrain ? cells : 0);
+    const int s_occ = st.add_bytes(cells, occupancy, Staging::kIn), s_terrain = st.add_bytes(cells, terrain, Staging::kIn);
     DistanceSections d{};
     if (own_distances) d = costmap_distance_sections(st, nx, ny, frames, cells, -1, nullptr);
     else d.dist2 = st.add(dist2 && inflate ? cells : 0, inflate ? dist2 : nullptr, Staging::kIn);
@@ -3738,7 +3766,6 @@ int pwpp_costmap_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_mi
         return rc;
     if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}}))) return rc;
-    const size_t byte_words = (cells + 3) / 4;
     const int nx = g->nx, ny = g->ny;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     VisibilitySections v{};
@@ -3747,12 +3774,7 @@ int pwpp_costmap_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_mi
     v.count = -1;
     if (with_occ) v = visibility_sections(h, st, nx, ny, frames, cells, true, nullptr, org, nullptr, occupancy, true);
     if (inflate) d = costmap_distance_sections(st, nx, ny, frames, cells, v.count, dist2);
-    if (with_terrain) {
-        const int s_height = add_image(st, cells, nullptr, true);
-        const int none = st.add(0, nullptr, Staging::kOut);  // (the outputs of the terrain analysis that nobody asks for: null pointers)
-        const int s_cost = terrain ? st.add(byte_words, terrain, Staging::kOut, cells) : st.add(byte_words, nullptr, Staging::kKept);
-        t = TerrainSections{s_height, none, none, none, none, s_cost};
-    }
+    if (with_terrain) t = terrain_cost_sections(st, cells, terrain);
     const CostmapSections s = costmap_sections(st, cells, rule, curve, v.occ, t.cost, d.dist2, cost, why);
     if ((rc = st.begin())) return rc;
     if (with_occ || inflate)
@@ -3828,7 +3850,7 @@ int tracks_args(int frames, size_t cells_c, size_t cells_p, const int32_t *curr,
     if ((int64_t)frames * max_rows > PWPP_TRACKS_MAX_TOTAL) return fail(PWPP_E_ARG, "%d frames x max_rows %d exceed 2^24", frames, max_rows);
     if (max_pairs < 1) return fail(PWPP_E_ARG, "max_pairs %d: at least 1 expected", max_pairs);
     if ((int64_t)frames * max_pairs > PWPP_TRACKS_MAX_TOTAL) return fail(PWPP_E_ARG, "%d frames x max_pairs %d exceed 2^24", frames, max_pairs);
-    if (t.n_poses < 1 || (t.n_poses != 1 && t.n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", t.n_poses, frames);
+    if (const int rc = per_frame_count_args(t.n_poses, frames, "poses")) return rc;
     const int given = (t.id_prev != nullptr) + (t.next_id != nullptr) + (t.id_curr != nullptr) + (t.next_id_out != nullptr);
     if (given != 0 && given != 4)
         return fail(PWPP_E_ARG, "null %s with other id arrays given: id_prev, next_id, id_curr and next_id_out all or none expected",
@@ -3921,32 +3943,19 @@ int pwpp_track_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min,
     if (!g || !label || !prev_label || !pose || !curr_links || !prev_links)
         return fail(PWPP_E_ARG, "null %s",
                     !g ? "grid" : (!label ? "label image" : (!prev_label ? "previous label image" : (!pose ? "pose" : (!curr_links ? "curr_links" : "prev_links")))));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
-    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    const LabelArrays a{label, count, top, clusters, n_clusters, max_clusters, point_cluster};
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
-    if ((rc = side_args(g->nx, g->ny, kTracksWho))) return rc;
+    int rc = label_first_args(h, g, h_min, h_max, min_count, connectivity, frame_first, frames, mem, a, kTracksWho, cells);
+    if (rc) return rc;
     if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d of the current grid: the association takes 0", g->flags);
     const TrackArrays t{pose, n_poses, curr_links, prev_links, n_pairs, id_prev, next_id, id_curr, next_id_out};
     PwppTracksRule rule;
     if ((rc = tracks_args(frames, cells, cells, label, prev_label, t, gate, min_overlap, max_clusters, max_pairs, rule))) return rc;
     if ((rc = tracks_alignment_args(mem, label, prev_label, t))) return rc;
     const PwppFusionGeometry G = tracks_geometry(g, g);
-    const int64_t base_first = h->h_base.p[frame_first];
-    const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
-    Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, count, top, label, clusters, n_clusters, max_clusters);
-    const int s_pc = st.add(points, point_cluster, Staging::kOut);
-    const TrackSections ts = track_sections(st, frames, cells, s.label, prev_label, t, rule);
-    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
-        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, max_clusters);
-        if (lrc == 0 && points != 0) {
-            lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (as pwpp_label_obstacles)
-            if (lrc == 0) lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
-        }
-        return lrc != 0 ? lrc : track_launch(h, st, ts, G, rule, frames, n_poses, n_pairs != nullptr);
+    return run_on_labels(h, g, h_min, h_max, min_count, connectivity, frame_first, frames, mem, cells, a, [&](Staging &st, int s_label) {
+        const TrackSections ts = track_sections(st, frames, cells, s_label, prev_label, t, rule);
+        return [&, ts] { return track_launch(h, st, ts, G, rule, frames, n_poses, n_pairs != nullptr); };
     });
 }
 
@@ -4010,7 +4019,7 @@ int evidence_args(const pwpp_ground_grid *g, int frames, size_t cells, const int
     if (const int rc = evidence_rule_args(rule, plan.R)) return rc;
     if (max_rows < 1) return fail(PWPP_E_ARG, "max_rows %d: at least 1 expected", max_rows);
     if ((int64_t)frames * max_rows > PWPP_EV_MAX_TOTAL) return fail(PWPP_E_ARG, "%d frames x max_rows %d exceed 2^24", frames, max_rows);
-    if (a.n_poses < 1 || (a.n_poses != 1 && a.n_poses != frames)) return fail(PWPP_E_ARG, "%d poses for %d frames: 1 or one per frame expected", a.n_poses, frames);
+    if (const int rc = per_frame_count_args(a.n_poses, frames, "poses")) return rc;
     const FrameMaps map_of{a.map_of_frame, n_maps};
     if (const int rc = map_of.args(frames)) return rc;
     if ((a.occ_in != nullptr) != (a.occ_out != nullptr))
@@ -4046,11 +4055,11 @@ EvidenceSections evidence_sections(Staging &st, EvidencePlan &plan, int frames, 
     EvidenceSections s;
     s.up = st.add_upload(std::move(plan.words));
     s.label = s_label;
-    s.occ_in = st.add(a.occ_in ? (cells + 3) / 4 : 0, a.occ_in, Staging::kIn, a.occ_in ? cells : 0);
+    s.occ_in = st.add_bytes(cells, a.occ_in, Staging::kIn);
     s.map = st.add((plan.map_cells + 1) / 2, a.map, Staging::kIn, plan.map_cells * sizeof(int16_t));
     s.rows = st.add((size_t)frames * (size_t)plan.max_rows * (sizeof(pwpp_cluster_evidence) / 4), a.rows, Staging::kOut);
-    s.cell_class = st.add(a.cell_class ? (cells + 3) / 4 : 0, a.cell_class, Staging::kOut, a.cell_class ? cells : 0);
-    s.occ_out = st.add(a.occ_out ? (cells + 3) / 4 : 0, a.occ_out, Staging::kOut, a.occ_out ? cells : 0);
+    s.cell_class = st.add_bytes(cells, a.cell_class, Staging::kOut);
+    s.occ_out = st.add_bytes(cells, a.occ_out, Staging::kOut);
     return s;
 }
 int evidence_launch(pwpp_handle *h, const Staging &st, const EvidenceSections &s, const EvidencePlan &plan, int frames, const EvidenceArrays &a) {
@@ -4093,32 +4102,19 @@ int pwpp_evidence_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_m
     if (!g || !label || !pose || !m || !map || !rule || !rows)
         return fail(PWPP_E_ARG, "null %s",
                     !g ? "grid" : (!label ? "label image" : (!pose ? "pose" : (!m ? "map description" : (!map ? "map" : (!rule ? "rule" : "rows"))))));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
-    if ((rc = cluster_param_args(mem, min_count, connectivity, clusters, max_clusters))) return rc;
+    const LabelArrays l{label, count, top, clusters, n_clusters, max_clusters, point_cluster};
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
-    if ((rc = side_args(g->nx, g->ny, kEvidenceWho))) return rc;
+    int rc = label_first_args(h, g, h_min, h_max, min_count, connectivity, frame_first, frames, mem, l, kEvidenceWho, cells);
+    if (rc) return rc;
     if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: the map evidence's frame grid takes 0", g->flags);
     EvidencePlan plan;
     if ((rc = image_args(m->nx, m->ny, n_maps, kEvidenceWho, plan.map_cells))) return rc;
     const EvidenceArrays a{occupancy_in, pose, n_poses, map_of_frame, map, rows, cell_class, occupancy_out};
     if ((rc = evidence_args(g, frames, cells, label, a, m, n_maps, rule, max_clusters, plan))) return rc;
     if ((rc = evidence_alignment_args(mem, label, a))) return rc;
-    const int64_t base_first = h->h_base.p[frame_first];
-    const size_t points = point_cluster ? (size_t)(h->h_base.p[frame_first + frames] - base_first) : 0;
-    Staging st(h, h->d_clusters, mem, kClusterAlign);
-    const ClusterSections s = cluster_sections(st, g->nx, g->ny, frames, cells, true, count, top, label, clusters, n_clusters, max_clusters);
-    const int s_pc = st.add(points, point_cluster, Staging::kOut);
-    const EvidenceSections es = evidence_sections(st, plan, frames, cells, s.label, a);
-    return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s.top, [&](const PwppObstacleScan &scan) {
-        int lrc = cluster_launch(h, st, s, g->nx, g->ny, frames, min_count, connectivity, max_clusters);
-        if (lrc == 0 && points != 0) {
-            lrc = (int)hipMemsetAsync(st.dev<int32_t>(s_pc), 0xff, points * sizeof(int32_t), h->stream);  // (as pwpp_label_obstacles)
-            if (lrc == 0) lrc = pwpp_launch_point_cluster(&scan, st.dev<int32_t>(s.label), st.dev<int32_t>(s_pc), base_first, h->stream);
-        }
-        return lrc != 0 ? lrc : evidence_launch(h, st, es, plan, frames, a);
+    return run_on_labels(h, g, h_min, h_max, min_count, connectivity, frame_first, frames, mem, cells, l, [&](Staging &st, int s_label) {
+        const EvidenceSections es = evidence_sections(st, plan, frames, cells, s_label, a);
+        return [&, es] { return evidence_launch(h, st, es, plan, frames, a); };
     });
 }
 
