@@ -89,6 +89,31 @@ PWPP_HD inline unsigned long long pwpp_dist_scan_all(Column &col, int ix, int iy
     return best;
 }
 
+// ---- how pass 2 is dealt -------------------------------------------------------------------------------------------------------
+#define PWPP_DIST_STRIP 64       // columns of a strip = lanes of a wave
+#define PWPP_DIST_LDS_ROWS 512   // rows of a strip in LDS at most: 128 KiB of the CU's 160
+#define PWPP_DIST_TALL_TILE 256  // rows of a workgroup's tile when the strip is read from global memory
+
+// A column is cut into row_tiles tiles of tile_rows rows.  With lds != 0 the tile's rows and `halo` more on either side, clipped
+// to the image, min(ny, tile_rows + 2 * halo) <= PWPP_DIST_LDS_ROWS of them, are in LDS: the whole column when it fits; a taller
+// one with a cap in tiles with a halo of max_dist rows (pwpp_dist_scan_outward never leaves it); else, and on path 1 (the
+// yardstick), the rows are read from global memory.
+struct PwppDistPlan {
+    int32_t lds, tile_rows, halo, row_tiles;
+};
+PWPP_HD inline PwppDistPlan pwpp_dist_plan(int ny, int max_dist, int path) {
+    PwppDistPlan p;
+    if (path == 0 && ny <= PWPP_DIST_LDS_ROWS) {
+        p.lds = 1, p.tile_rows = ny, p.halo = 0;
+    } else if (path == 0 && max_dist > 0 && 2 * max_dist + PWPP_DIST_STRIP <= PWPP_DIST_LDS_ROWS) {
+        p.lds = 1, p.tile_rows = PWPP_DIST_LDS_ROWS - 2 * max_dist, p.halo = max_dist;
+    } else {
+        p.lds = 0, p.tile_rows = PWPP_DIST_TALL_TILE, p.halo = 0;
+    }
+    p.row_tiles = (ny + p.tile_rows - 1) / p.tile_rows;
+    return p;
+}
+
 // the two integer outputs of a cell from its minimum key: beyond the cap (or no occupied cell at all) PWPP_DIST_NONE and -1
 PWPP_HD inline void pwpp_dist_of_key(unsigned long long key, uint32_t cap2, int32_t &dist2, int32_t &nearest) {
     const uint32_t d2 = (uint32_t)(key >> 32);

@@ -26,9 +26,7 @@ namespace {
 constexpr int kRowBlock = 256;   // pass 1: four waves, a row each
 constexpr int kColBlock = 1024;  // pass 2: sixteen waves share the strip's rows in LDS: 64 KiB for 256 rows, two workgroups a CU
 constexpr int kColWaves = kColBlock / 64;
-constexpr int kStrip = 64;       // columns of a strip = lanes of a wave
-constexpr int kLdsRows = 512;    // rows of a strip in LDS at most: 128 KiB of the CU's 160
-constexpr int kTallTile = 256;   // rows of a workgroup's tile when the strip is read from global memory
+constexpr int kStrip = PWPP_DIST_STRIP;  // columns of a strip = lanes of a wave
 
 struct DistImage {
     int32_t nx, ny;
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(kColBlock) void k_dist_cols(DistImage I, double cel
     const int t0 = (int)t * I.tile_rows, t1 = min(I.ny, t0 + I.tile_rows);
     const int row0 = max(0, t0 - I.halo), row1 = min(I.ny, t1 + I.halo);
     const bool lds = PATH == 0 && I.lds != 0;
-    if (lds) {  // (row1 - row0 <= kLdsRows: the launcher's choice of tile_rows and halo)
+    if (lds) {  // (row1 - row0 <= PWPP_DIST_LDS_ROWS: pwpp_dist_plan's choice of tile_rows and halo)
         for (int jy = row0 + w; jy < row1; jy += kColWaves) s_gx[(jy - row0) * kStrip + lane] = ix < I.nx ? g[jy * I.nx + ix] : -1;
         __syncthreads();
     }
@@ -131,16 +129,8 @@ extern "C" int pwpp_launch_distance_grid(int nx, int ny, int frames, const int32
     DistImage I;
     I.nx = nx, I.ny = ny, I.per_frame = nx * ny, I.min_count = min_count, I.cap2 = pwpp_dist_cap2(max_dist);
     I.strips = (nx + kStrip - 1) / kStrip;
-    // The rows of a tile in LDS: the whole column when it fits; a taller one with a cap in tiles with a halo of max_dist rows (the
-    // scan never leaves it); else from global memory.
-    if (path == 0 && ny <= kLdsRows) {
-        I.lds = 1, I.tile_rows = ny, I.halo = 0;
-    } else if (path == 0 && max_dist > 0 && 2 * max_dist + kStrip <= kLdsRows) {
-        I.lds = 1, I.tile_rows = kLdsRows - 2 * max_dist, I.halo = max_dist;
-    } else {
-        I.lds = 0, I.tile_rows = kTallTile, I.halo = 0;
-    }
-    I.row_tiles = (ny + I.tile_rows - 1) / I.tile_rows;
+    const PwppDistPlan plan = pwpp_dist_plan(ny, max_dist, path);  // (the rows of a tile in LDS, or from global memory)
+    I.lds = plan.lds, I.tile_rows = plan.tile_rows, I.halo = plan.halo, I.row_tiles = plan.row_tiles;
     const int64_t rows = (int64_t)frames * ny, row_blocks = (rows + kRowBlock / 64 - 1) / (kRowBlock / 64);
     const int64_t col_blocks = (int64_t)frames * I.strips * I.row_tiles;
     if (row_blocks > INT32_MAX || col_blocks > INT32_MAX) return (int)hipErrorInvalidConfiguration;
