@@ -1496,6 +1496,81 @@ PWPP_API int pwpp_plan_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
                             const pwpp_route_params *route_params, pwpp_route *routes, int32_t *cells, int32_t *waypoints,
                             int32_t *reach /* may be NULL: kept in the handle's buffer */, int32_t *from /* may be NULL: kept */);
 
+/* ---- oriented vehicle footprint: poses checked and trajectories scored against the cost image on the device (pwpp_footprint_grid) ----
+ * The costmap's inflation, the reach's clearance2 and a route's min_dist2 all speak of a point with a round collar.  A car of 4.5 m x
+ * 1.8 m has an inscribed radius of 0.9 m and a circumscribed one of about 2.4 m; whether a cell between them is free depends on the
+ * heading.  This call lays the vehicle's rectangle over the cost image at every pose of a fan of candidate trajectories and returns a
+ * row of 32 bytes per pose and per trajectory -- cost, dist2 and reach never have to reach the host.  Integers only, no angle: a
+ * heading is an integer vector.  The same bytes whatever the schedule.  Frames, and the trajectories of a frame, are on their own.
+ *   ticks     A tick is 1/PWPP_FOOT_SUB = 1/16 of a cell side.  Cell (ix, iy) covers the ticks [16 ix, 16 ix + 16) in x, [16 iy, 16 iy + 16)
+ *             in y; its centre is q = (16 ix + 8, 16 iy + 8).  Tick coordinates may be negative or lie beyond the image.
+ *   pose      {px, py, ux, uy}: the reference point p in ticks, |px|, |py| <= 2^20; the heading u, any integer vector with |ux|, |uy| <=
+ *             1024, of which only the direction matters.  u == (0, 0) is no pose: status PWPP_FOOT_SKIPPED -- how ragged trajectories
+ *             are padded.
+ *   footprint the rectangle [-rear, front] along u and [-half_width, half_width] across it, in ticks, each of the three 0 ..
+ *             PWPP_FOOT_MAX_EXTENT (64 cells, the costmap's largest radius); rear != front puts p on a rear axle.
+ *   covered   With d = q - p, a = ux dx + uy dy, b = ux dy - uy dx, n2 = ux^2 + uy^2, all in int64: a cell is covered iff
+ *             (a >= 0 ? a^2 <= front^2 n2 : a^2 <= rear^2 n2) and b^2 <= half_width^2 n2.  Equality is inside.
+ *             Lemma 1: a covered cell has max(|dx|, |dy|) <= max(front, rear) + half_width <= 2048; only that window is visited and
+ *             every product stays below 2^45.  Lemma 2: a footprint padded by 12 ticks on every side covers every cell that the
+ *             unpadded rectangle touches at all (8 sqrt(2) < 12): the caller's knob for a conservative check.  (csrc/pwpp_footprint.h
+ *             has the proofs.)
+ *   pose row  over the pose's covered cells: `covered`, all of them, inside the image or not; `outside`, those with ix or iy outside
+ *             the image (no address is formed for them).  For the covered cells inside, t = the term of the reach contract (above)
+ *             from the same cost, dist2 and pwpp_reach_params, with no source exception: `blocked`, the count with t == 0; `unknown`,
+ *             the count with a cost byte < 0, whatever p->unknown substitutes; max_term, the largest t (0 without one); min_dist2,
+ *             the smallest dist2 over all of them, blocked ones too (PWPP_DIST_BEYOND without a dist2 image or without such a cell);
+ *             `hit`, the smallest index iy nx + ix of a blocked cell, or -1.  status: PWPP_FOOT_HIT iff blocked > 0, or outside > 0
+ *             with PWPP_FOOT_OUTSIDE_BLOCKS in flags; else PWPP_FOOT_FREE.  A skipped pose's row is {PWPP_FOOT_SKIPPED, 0, 0, 0, 0, 0,
+ *             PWPP_DIST_BEYOND, -1}.  max_reach of p is not read.
+ *   traj row  of frame f and trajectory j, over the poses of set 0 or of set f: first_hit, the smallest step whose status is HIT, or
+ *             -1.  The free prefix: the steps that are not skipped and lie before first_hit (all that are not skipped without one).
+ *             free_steps, its size; `last`, its largest step, or -1; max_term and sum_term, the maximum and the sum of its poses'
+ *             max_term; `unknown`, the sum of their unknown; min_dist2, the minimum of theirs; reach_last, reach[f] at the cell
+ *             (px >> 4, py >> 4) of pose `last` (an arithmetic shift) where reach was given, last >= 0 and that cell lies inside, else
+ *             PWPP_REACH_NONE.  With 4096 steps every sum stays below 2^31 (355 x 4096; 66049 x 4096).  Every field is a min, a max,
+ *             a sum or an ordered pick: the same bytes whatever the deal.
+ *   limits    n_sets 1 or `frames`; n_traj 1 .. 65536; n_steps 1 .. PWPP_FOOT_MAX_STEPS; frames x n_traj x n_steps <= 2^26; the sides,
+ *             the frames and their product as pwpp_reach_grid has them.  The range check of pwpp_reach_grid is not made: nothing is
+ *             summed over the image.
+ *   mem       as pwpp_route_grid: PWPP_MEM_HOST stages every array through the cluster buffer and returns when the rows are there;
+ *             PWPP_MEM_DEVICE enqueues on the handle's stream, the cost bytes lie at any address, dist2, reach and both row arrays are
+ *             4-byte aligned.  `poses` is host memory whatever `mem` and is copied at the call.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    PWPP_E_ARG, named before the device is touched, in this order: a null handle, cost, reach parameters, footprint
+ *             parameters, poses; the image's shape; the reach parameters as pwpp_reach_grid names them, without the range; front,
+ *             rear, half_width, unknown flag bits, pad_ not 0; the count of sets, of trajectories, of steps, their product beyond
+ *             2^26; the first pose entry out of range, naming set, trajectory and step; both row arrays null; two of the caller's
+ *             arrays overlapping; mem; in PWPP_MEM_DEVICE an int32 array below its alignment.
+ *   buffers   The uploaded poses, in PWPP_MEM_HOST the staged arrays and on "footprint_path" 1 the pose rows of a call that asks for
+ *             trajectory rows alone lie in the cluster buffer; counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ *   helpers   pwpp_footprint_covers: the coverage rule itself for any cell, 1 or 0 (PWPP_E_ARG: a null pointer, parameters or a pose
+ *             out of range; u == (0, 0) covers nothing).  pwpp_footprint_pose: a convenience, not the contract: px = (int)floor((x -
+ *             g->x0) / g->cell * 16), py alike, ux = lround(1024 cos yaw), uy = lround(1024 sin yaw); PWPP_E_ARG for a value that is
+ *             not finite or a p beyond 2^20.
+ * The same bytes for every mem, alignment and value of the option "footprint_path".  With the function never called nothing is
+ * allocated or launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_FOOTPRINT 1
+#define PWPP_FOOT_SUB 16            /* ticks per cell side */
+#define PWPP_FOOT_MAX_EXTENT 1024   /* ticks: 64 cells, the costmap's largest radius */
+#define PWPP_FOOT_MAX_STEPS 4096
+#define PWPP_FOOT_FREE 0
+#define PWPP_FOOT_HIT 1
+#define PWPP_FOOT_SKIPPED 2
+#define PWPP_FOOT_OUTSIDE_BLOCKS 1  /* flags */
+typedef struct pwpp_footprint_params { int32_t front, rear, half_width, flags, pad_[2]; } pwpp_footprint_params;   /* 24 bytes */
+typedef struct pwpp_footprint_pose_row { int32_t status, covered, outside, blocked, unknown, max_term, min_dist2, hit; } pwpp_footprint_pose_row;       /* 32 bytes */
+typedef struct pwpp_footprint_traj_row { int32_t first_hit, free_steps, last, max_term, sum_term, unknown, min_dist2, reach_last; } pwpp_footprint_traj_row; /* 32 bytes */
+
+/* needs a handle (stream, buffer), no estimate call -- like pwpp_route_grid */
+PWPP_API int pwpp_footprint_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
+        const int8_t *cost /* [frames][ny][nx] */, const int32_t *dist2 /* same shape, may be NULL */,
+        const int32_t *reach /* same shape, may be NULL */, const pwpp_reach_params *p, const pwpp_footprint_params *fp,
+        const int32_t *poses /* HOST: [n_sets][n_traj][n_steps][4] = {px, py, ux, uy} */, int n_sets /* 1 or frames */, int n_traj, int n_steps,
+        pwpp_footprint_pose_row *pose_rows /* [frames][n_traj][n_steps], may be NULL */,
+        pwpp_footprint_traj_row *traj_rows /* [frames][n_traj], may be NULL; not both NULL */);
+PWPP_API int pwpp_footprint_covers(const pwpp_footprint_params *fp, const int32_t pose[4], int ix, int iy);  /* host only: 1, 0 or PWPP_E_ARG */
+PWPP_API int pwpp_footprint_pose(const pwpp_ground_grid *g, double x, double y, double yaw, int32_t pose[4]); /* host only, a convenience */
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1646,6 +1721,13 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         a second walk through from (the yardstick); "2": a wave per route -- every lane takes the hops, the route's
  *                         last 512 cells lie in LDS, the shortcut candidates go to the lanes from the far end and a ballot picks the
  *                         largest clear one; "0" (default): what tools/route_cost.py decided.  The same bytes for every value.
+ *   "footprint_path"      how the footprints are dealt (pwpp_footprint_grid): "1": a lane per pose, serial over its window, then a lane per
+ *                         trajectory over the pose rows (the yardstick); "2": a wave per trajectory -- its steps fill the wave's lanes
+ *                         first, the cells of a pose's window are dealt to the lanes the steps leave over, the folds cross the
+ *                         lanes by shuffles and the trajectory's summary stays in registers; "0" (default): what
+ *                         tools/footprint_cost.py decided -- "2" for a call whose max(front, rear) + half_width is 504 ticks or more
+ *                         and that asks for no pose rows (it stops a trajectory at its first hit) or reads dist2, "1" otherwise.
+ *                         The same bytes for every value.
  *   "costmap_path"        how the costmap's fold is dealt (pwpp_costmap_grid, pwpp_costmap_obstacles): "1": a lane per cell, the inflation
  *                         curve read from global memory (the yardstick); "2": the curve staged once per workgroup into LDS, four
  *                         consecutive cells a lane, the byte images as one dword where their address allows; "0" (default): what

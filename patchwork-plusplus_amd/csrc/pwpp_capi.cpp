@@ -32,6 +32,7 @@
 #include "pwpp_costmap.h"
 #include "pwpp_reach.h"
 #include "pwpp_route.h"
+#include "pwpp_footprint.h"
 #include "pwpp_terrain.h"
 #include "pwpp_tracks.h"
 #include "pwpp_visibility.h"
@@ -262,6 +263,7 @@ struct pwpp_handle {
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
     int costmap_path = 0;           // option "costmap_path": 0 = what tools/costmap_cost.py decided (2 from PWPP_COSTMAP_QUADS_FROM_CELLS cells a call, 1 below); 1 = a lane per cell, the curve read from global memory (yardstick); 2 = the curve staged in LDS, four cells a lane
     int route_path = 0;             // option "route_path": 0 = what tools/route_cost.py decided; 1 = a lane per route, wholly serial (yardstick); 2 = a wave per route, the route's last cells in LDS, the shortcut candidates dealt to the lanes
+    int footprint_path = 0;         // option "footprint_path": 0 = what tools/footprint_cost.py decided (2 under a large footprint for trajectory rows alone or with dist2, 1 otherwise); 1 = a lane per pose, then a lane per trajectory over the pose rows (yardstick); 2 = a wave per trajectory, small windows packed, the folds by shuffles
     int reach_path = 0;             // option "reach_path": 0 = what tools/reach_cost.py decided; 1 = sweeps over global memory, a workgroup per frame (yardstick); 2 = the frame's tiles relaxed in LDS, dirty tiles revisited
     int evidence_path = 0;          // option "evidence_path": 0 = what tools/evidence_cost.py decided; 1 = the sums go to the rows with global atomics (yardstick); 2 = a workgroup sums a run of cells in LDS first where the rows fit
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
@@ -1283,6 +1285,7 @@ constexpr PathOption kPathOptions[] = {
     {"terrain_path", &pwpp_handle::terrain_path, 2},
     {"reach_path", &pwpp_handle::reach_path, 2},
     {"route_path", &pwpp_handle::route_path, 2},
+    {"footprint_path", &pwpp_handle::footprint_path, 2},
     {"costmap_path", &pwpp_handle::costmap_path, 2},
     {"match_path", &pwpp_handle::match_path, 2},
     {"evidence_path", &pwpp_handle::evidence_path, 2},
@@ -3371,8 +3374,8 @@ static_assert(PWPP_REACH_NONE == (int32_t)PWPP_REACH_UNREACHED && PWPP_DIST_BEYO
 constexpr const char *kReachWho = "the reach takes";
 
 // What both entry points check of the parameters and the range, in the header's order, after the image's own checks; fills the
-// rule.  Touches no handle.
-int reach_param_args(const pwpp_reach_params *p, int nx, int ny, bool with_dist2, PwppReachRule &rule) {
+// rule.  Touches no handle.  (`with_range` false: the footprints, which sum nothing over the image.)
+int reach_param_args(const pwpp_reach_params *p, int nx, int ny, bool with_dist2, PwppReachRule &rule, bool with_range = true) {
     if (p->base < 1 || p->base > 255) return fail(PWPP_E_ARG, "base %d: 1 .. 255 expected", p->base);
     if (p->lethal < 1 || p->lethal > 101) return fail(PWPP_E_ARG, "lethal %d: 1 .. 101 expected (101: no value is lethal)", p->lethal);
     if (p->unknown < -1 || p->unknown > 100) return fail(PWPP_E_ARG, "unknown %d: -1 (impassable) .. 100 expected", p->unknown);
@@ -3380,7 +3383,7 @@ int reach_param_args(const pwpp_reach_params *p, int nx, int ny, bool with_dist2
     if (p->max_reach < 0) return fail(PWPP_E_ARG, "max_reach %d: 0 (unlimited) or more expected", p->max_reach);
     if (p->pad_ != 0) return fail(PWPP_E_ARG, "pad_ %d of the reach parameters: 0 expected", p->pad_);
     int64_t worst = 0;
-    if (!pwpp_reach_range_ok(p->base, nx, ny, worst))
+    if (with_range && !pwpp_reach_range_ok(p->base, nx, ny, worst))
         return fail(PWPP_E_ARG, "14 * (base + 100) * (%d * %d - 1) = %lld with base %d exceeds 2^31 - 2: a reach would not fit 32 bits", nx, ny,
                     (long long)worst, p->base);
     rule = PwppReachRule{p->base, p->lethal, p->unknown, with_dist2 ? p->clearance2 : 0, p->max_reach, with_dist2 ? 1 : 0};
@@ -3631,6 +3634,94 @@ int pwpp_plan_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const in
                                          return lrc != 0 ? lrc : route_launch(h, st, r, s, rule, route, nx, ny, frames, src, n_start_sets, n_starts);
                                      }),
                         flag_host);
+}
+
+// ---- oriented vehicle footprint: the rectangle of every pose laid over the cost image, every trajectory's free prefix summed up ----
+namespace {
+static_assert(sizeof(pwpp_footprint_params) == 24 && sizeof(pwpp_footprint_pose_row) == 32 && sizeof(pwpp_footprint_traj_row) == 32 && sizeof(PwppFootPoseRow) == 32 &&
+                  sizeof(PwppFootTrajRow) == 32 && sizeof(PwppFootPose) == 16 && sizeof(PwppFootRule) == 16,
+              "the rows, the pose and the rule as the kernels see them");
+static_assert(PWPP_FOOT_FREE == PWPP_FOOT_STATUS_FREE && PWPP_FOOT_HIT == PWPP_FOOT_STATUS_HIT && PWPP_FOOT_SKIPPED == PWPP_FOOT_STATUS_SKIPPED &&
+                  PWPP_FOOT_OUTSIDE_BLOCKS == PWPP_FOOT_FLAG_OUTSIDE_BLOCKS && PWPP_FOOT_SUB == PWPP_FOOT_TICKS && PWPP_FOOT_MAX_EXTENT == PWPP_FOOT_EXTENT_MAX &&
+                  PWPP_FOOT_MAX_STEPS == PWPP_FOOT_STEPS_MAX,
+              "the kernels' values");
+
+// What every footprint function checks of the parameters, in the header's order; fills the rule.  Touches no handle.
+int footprint_param_args(const pwpp_footprint_params *fp, PwppFootRule &rule) {
+    if (fp->front < 0 || fp->front > PWPP_FOOT_MAX_EXTENT) return fail(PWPP_E_ARG, "front %d: 0 .. %d ticks expected", fp->front, PWPP_FOOT_MAX_EXTENT);
+    if (fp->rear < 0 || fp->rear > PWPP_FOOT_MAX_EXTENT) return fail(PWPP_E_ARG, "rear %d: 0 .. %d ticks expected", fp->rear, PWPP_FOOT_MAX_EXTENT);
+    if (fp->half_width < 0 || fp->half_width > PWPP_FOOT_MAX_EXTENT) return fail(PWPP_E_ARG, "half_width %d: 0 .. %d ticks expected", fp->half_width, PWPP_FOOT_MAX_EXTENT);
+    if (fp->flags & ~(int32_t)PWPP_FOOT_OUTSIDE_BLOCKS) return fail(PWPP_E_ARG, "footprint flags %d: 0 or PWPP_FOOT_OUTSIDE_BLOCKS", fp->flags);
+    if (fp->pad_[0] != 0 || fp->pad_[1] != 0) return fail(PWPP_E_ARG, "pad_ {%d, %d} of the footprint parameters: 0 expected", fp->pad_[0], fp->pad_[1]);
+    rule = PwppFootRule{fp->front, fp->rear, fp->half_width, fp->flags};
+    return PWPP_OK;
+}
+}  // namespace
+
+int pwpp_footprint_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int8_t *cost, const int32_t *dist2, const int32_t *reach, const pwpp_reach_params *p,
+                        const pwpp_footprint_params *fp, const int32_t *poses, int n_sets, int n_traj, int n_steps, pwpp_footprint_pose_row *pose_rows,
+                        pwpp_footprint_traj_row *traj_rows) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!cost || !p || !fp || !poses) return fail(PWPP_E_ARG, "null %s", !cost ? "cost image" : (!p ? "reach parameters" : (!fp ? "footprint parameters" : "poses")));
+    size_t n_cells = 0;
+    PwppReachRule rule;
+    PwppFootRule foot;
+    int rc = image_args(nx, ny, frames, kReachWho, n_cells);
+    if (rc) return rc;
+    if ((rc = reach_param_args(p, nx, ny, dist2 != nullptr, rule, false))) return rc;
+    if ((rc = footprint_param_args(fp, foot))) return rc;
+    if ((rc = per_frame_count_args(n_sets, frames, "pose sets"))) return rc;
+    if (n_traj < 1 || n_traj > PWPP_FOOT_TRAJ_MAX) return fail(PWPP_E_ARG, "%d trajectories: 1 .. %d expected", n_traj, PWPP_FOOT_TRAJ_MAX);
+    if (n_steps < 1 || n_steps > PWPP_FOOT_MAX_STEPS) return fail(PWPP_E_ARG, "%d steps: 1 .. %d expected", n_steps, PWPP_FOOT_MAX_STEPS);
+    if ((int64_t)frames * (int64_t)n_traj > PWPP_FOOT_POSES_MAX / n_steps)
+        return fail(PWPP_E_ARG, "%d frames x %d trajectories x %d steps exceed 2^26", frames, n_traj, n_steps);
+    const size_t n_trajs = (size_t)frames * (size_t)n_traj, n_poses = n_trajs * (size_t)n_steps, n_given = (size_t)n_sets * (size_t)n_traj * (size_t)n_steps;
+    for (size_t i = 0; i < n_given; ++i)
+        if (!pwpp_foot_pose_in_range(poses + 4 * i)) {
+            const int32_t *q = poses + 4 * i;
+            return fail(PWPP_E_ARG, "pose of set %d, trajectory %d, step %d, {%d, %d, %d, %d}: |px|, |py| <= 2^20 and |ux|, |uy| <= 1024 expected",
+                        (int)(i / ((size_t)n_traj * (size_t)n_steps)), (int)(i / (size_t)n_steps % (size_t)n_traj), (int)(i % (size_t)n_steps), q[0], q[1], q[2], q[3]);
+        }
+    if (!pose_rows && !traj_rows) return fail(PWPP_E_ARG, "null pose rows and null trajectory rows: one of them expected");
+    if ((rc = range_args({{cost, n_cells, "cost"}, {dist2, n_cells * 4, "dist2"}, {reach, n_cells * 4, "reach"}, {pose_rows, n_poses * 32, "pose rows"},
+                          {traj_rows, n_trajs * 32, "trajectory rows"}}, {}, false)))
+        return rc;
+    if ((rc = mem_args(mem, "the footprints take"))) return rc;
+    if ((rc = alignment_args(mem, {{dist2, 3u, "dist2 image"}, {reach, 3u, "reach image"}, {pose_rows, 3u, "pose rows"}, {traj_rows, 3u, "trajectory rows"}}))) return rc;
+    const bool work = traj_rows && !pose_rows && pwpp_footprint_path_of(h->footprint_path, &foot, 0, dist2 != nullptr) == 1;  // (the yardstick's rows, where the caller wants none)
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_work = st.add(work ? n_poses * 8 : 0, nullptr, Staging::kKept);
+    const int s_poses = st.add_upload(std::vector<uint32_t>(reinterpret_cast<const uint32_t *>(poses), reinterpret_cast<const uint32_t *>(poses) + 4 * n_given));
+    const int s_cost = st.add_bytes(n_cells, cost, Staging::kIn);
+    const int s_dist2 = st.add(dist2 ? n_cells : 0, dist2, Staging::kIn), s_reach = st.add(reach ? n_cells : 0, reach, Staging::kIn);
+    const int s_prow = st.add(pose_rows ? n_poses * 8 : 0, pose_rows, Staging::kOut), s_trow = st.add(traj_rows ? n_trajs * 8 : 0, traj_rows, Staging::kOut);
+    return run_on_image(h, st, [&] {
+        return pwpp_launch_footprints(&rule, &foot, nx, ny, frames, st.dev<const int8_t>(s_cost), dist2 ? st.dev<const int32_t>(s_dist2) : nullptr,
+                                      reach ? st.dev<const int32_t>(s_reach) : nullptr, st.dev<const int32_t>(s_poses), n_sets, n_traj, n_steps,
+                                      pose_rows ? st.dev<void>(s_prow) : nullptr, traj_rows ? st.dev<void>(s_trow) : nullptr, work ? st.dev<void>(s_work) : nullptr,
+                                      h->footprint_path, h->stream);
+    });
+}
+
+int pwpp_footprint_covers(const pwpp_footprint_params *fp, const int32_t pose[4], int ix, int iy) {
+    if (!fp || !pose) return fail(PWPP_E_ARG, "null %s", !fp ? "footprint parameters" : "pose");
+    PwppFootRule foot;
+    if (const int rc = footprint_param_args(fp, foot)) return rc;
+    if (!pwpp_foot_pose_in_range(pose))
+        return fail(PWPP_E_ARG, "pose {%d, %d, %d, %d}: |px|, |py| <= 2^20 and |ux|, |uy| <= 1024 expected", pose[0], pose[1], pose[2], pose[3]);
+    return pwpp_foot_covers(foot, PwppFootPose{pose[0], pose[1], pose[2], pose[3]}, ix, iy) ? 1 : 0;
+}
+
+int pwpp_footprint_pose(const pwpp_ground_grid *g, double x, double y, double yaw, int32_t pose[4]) {
+    if (!g || !pose) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : "pose");
+    if (const int rc = grid_geometry_args(g)) return rc;
+    if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(yaw)) return fail(PWPP_E_ARG, "position (%g, %g), yaw %g: finite values expected", x, y, yaw);
+    const double tx = std::floor((x - g->x0) / g->cell * PWPP_FOOT_SUB), ty = std::floor((y - g->y0) / g->cell * PWPP_FOOT_SUB);
+    if (!(std::fabs(tx) <= (double)PWPP_FOOT_P_MAX) || !(std::fabs(ty) <= (double)PWPP_FOOT_P_MAX))
+        return fail(PWPP_E_ARG, "position (%g, %g) is (%g, %g) ticks from the grid's origin: at most 2^20 expected", x, y, tx, ty);
+    pose[0] = (int32_t)tx, pose[1] = (int32_t)ty;
+    pose[2] = (int32_t)std::lround(1024.0 * std::cos(yaw)), pose[3] = (int32_t)std::lround(1024.0 * std::sin(yaw));
+    return PWPP_OK;
 }
 
 // ---- costmap: the occupancy byte, the inflated obstacle distance and the terrain's cost byte folded into one cost byte ----------------

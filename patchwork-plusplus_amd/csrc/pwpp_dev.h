@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_footprint.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -352,6 +352,11 @@ int pwpp_launch_reach(const struct PwppReachRule *R, int nx, int ny, int frames,
 int pwpp_launch_routes(const struct PwppReachRule *R, const struct PwppRouteRule *P, int nx, int ny, int frames, const int8_t *cost, const int32_t *dist2,
                        int sx, int sy, const int32_t *sources, const int32_t *from, const int32_t *starts, int n_start_sets, int n_starts,
                        void *rows, int32_t *cells, int32_t *waypoints, int path, hipStream_t stream);
+// pwpp_footprint.hip (k_foot_poses, k_foot_trajs: "footprint_path" 1; k_foot_waves: 2)
+int pwpp_footprint_path_of(int path, const struct PwppFootRule *F, int pose_rows, int with_dist2);  // what "footprint_path" resolves to for a call: 1 or 2
+int pwpp_launch_footprints(const struct PwppReachRule *R, const struct PwppFootRule *F, int nx, int ny, int frames, const int8_t *cost, const int32_t *dist2,
+                           const int32_t *reach, const int32_t *poses, int n_sets, int n_traj, int n_steps, void *pose_rows, void *traj_rows, void *work_rows,
+                           int path, hipStream_t stream);
 // pwpp_costmap.hip
 int pwpp_launch_costmap_occupied(size_t cells, const int8_t *occupancy, int32_t *count, hipStream_t stream);
 int pwpp_launch_costmap(const struct PwppCostmapRule *R, size_t cells, const int8_t *occupancy, const int8_t *terrain, const int32_t *dist2,

@@ -79,6 +79,27 @@ int main(int argc, char **argv) {
         for (k = 0; k < route.waypoints && k < 8; ++k) printf(" (%d, %d)", (int)(waypoints[k] % 9), (int)(waypoints[k] / 9));
         printf("\n");
     }
+
+    /* A footprint (pwpp_footprint_grid, no reference counterpart): the same wall; a vehicle of 3 x 1 cells (ticks of 1/16 cell, p on the
+     * rear axle) drives along row 2 towards it heading +x, and along column 1 heading +y where nothing stands in its way. */
+    {
+        int8_t cost[81] = {0};
+        const pwpp_reach_params reach_params = {1, 100, -1, 0, 0, 0};
+        const pwpp_footprint_params foot = {40, 8, 8, 0, {0, 0}};
+        int32_t poses[2][6][4];
+        pwpp_footprint_traj_row rows[2];
+        int y, k;
+        for (y = 0; y < 8; ++y) cost[9 * y + 4] = 100;
+        for (k = 0; k < 6; ++k) {
+            poses[0][k][0] = 8 + 16 * k, poses[0][k][1] = 40, poses[0][k][2] = 1, poses[0][k][3] = 0;
+            poses[1][k][0] = 24, poses[1][k][1] = 8 + 16 * k, poses[1][k][2] = 0, poses[1][k][3] = 1;
+        }
+        if (pwpp_footprint_grid(h, 9, 9, 1, PWPP_MEM_HOST, cost, NULL, NULL, &reach_params, &foot, &poses[0][0][0], 1, 2, 6, NULL, rows) != PWPP_OK)
+            return fail("pwpp_footprint_grid");
+        for (k = 0; k < 2; ++k)
+            printf("footprint along %s: first hit at step %d, %d free steps, the last one %d\n", k ? "column 1" : "row 2", (int)rows[k].first_hit, (int)rows[k].free_steps,
+                   (int)rows[k].last);
+    }
     pwpp_destroy(h);
 
     /* A tilted sensor (pwpp_set_input_transforms, no reference counterpart): the same frame as a LiDAR pitched by 5 degrees and

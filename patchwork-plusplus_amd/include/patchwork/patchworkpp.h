@@ -21,6 +21,7 @@
 #ifndef PATCHWORKPP_AMD_H
 #define PATCHWORKPP_AMD_H
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <iostream>
@@ -673,6 +674,48 @@ public:
                 r.waypoints_xy[2 * i] = x0 + ((double)(r.waypoints[i] % nx) + 0.5) * cell;
                 r.waypoints_xy[2 * i + 1] = y0 + ((double)(r.waypoints[i] / nx) + 0.5) * cell;
             }
+        return r;
+    }
+    // ... and whether the vehicle fits along the way (pwpp_footprint_grid): a fan of candidate trajectories, n_traj x n_steps poses {x, y, yaw}
+    // in metres and radians, the rectangle [-rear, front] x [-half_width, half_width] metres round each pose laid over the cost image and
+    // judged cell by cell with the reach's rule.  Per pose a row (status PWPP_FOOT_FREE / _HIT / _SKIPPED, the cells covered, outside the
+    // image, blocked and unknown, the dearest term, the first blocked cell), per trajectory the first pose that hits and the sums over
+    // the free poses before it; reach_last where a reach field is given.  A pose whose yaw is NaN is skipped: how ragged fans are padded.
+    // pad > 0 widens the rectangle by so many ticks of 1/16 cell on every side: 12 covers every cell the rectangle touches at all.
+    struct FootprintParams {
+        double front, rear, half_width;  // metres; each at most 64 cells
+        int pad;                         // ticks of 1/16 cell added on every side, >= 0
+        bool outside_blocks;             // a covered cell outside the image makes the pose a hit
+        FootprintParams() : front(3.4), rear(1.1), half_width(0.9), pad(0), outside_blocks(false) {}  // (a constructor: as TerrainParams)
+    };
+    struct Footprints {
+        int n_traj = 0, n_steps = 0;
+        std::vector<pwpp_footprint_pose_row> poses;         // n_traj x n_steps
+        std::vector<pwpp_footprint_traj_row> trajectories;  // n_traj
+    };
+    // (on any cost image of ny x nx cells over the grid (x0, y0, cell, nx, ny) -- a Costmap's cost; poses_xyyaw: n_traj x n_steps x {x, y, yaw}; reach: empty or a Reach's field)
+    Footprints checkFootprints(const std::vector<int8_t> &cost, double x0, double y0, double cell, int nx, int ny, const std::vector<double> &poses_xyyaw, int n_steps,
+                               const FootprintParams &footprint_params = FootprintParams(), const ReachParams &reach_params = ReachParams(),
+                               const std::vector<int32_t> &reach = std::vector<int32_t>()) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, 0, 0};
+        const pwpp_reach_params rp = {reach_params.base, reach_params.lethal, reach_params.unknown, reach_params.clearance2, reach_params.max_reach, 0};
+        if (n_steps < 1 || poses_xyyaw.empty() || poses_xyyaw.size() % (3 * (size_t)n_steps) != 0)
+            throw std::invalid_argument("checkFootprints: poses_xyyaw holds n_traj x n_steps x {x, y, yaw}, n_traj >= 1");
+        if (nx < 1 || ny < 1 || cost.size() != (size_t)nx * (size_t)ny) throw std::invalid_argument("checkFootprints: the cost image has not ny x nx cells");
+        if (!reach.empty() && reach.size() != cost.size()) throw std::invalid_argument("checkFootprints: the reach field has not the cost image's cells");
+        if (!(cell > 0.0) || footprint_params.pad < 0) throw std::invalid_argument("checkFootprints: a positive cell and a pad >= 0 expected");
+        const double ticks = PWPP_FOOT_SUB / cell;
+        const auto extent = [&](double metres) { return metres >= 0.0 && metres * ticks <= 2.0 * PWPP_FOOT_MAX_EXTENT ? (int32_t)std::lround(metres * ticks) + footprint_params.pad : (int32_t)-1; };
+        const pwpp_footprint_params fp = {extent(footprint_params.front), extent(footprint_params.rear), extent(footprint_params.half_width),
+                                          footprint_params.outside_blocks ? (int32_t)PWPP_FOOT_OUTSIDE_BLOCKS : 0, {0, 0}};  // (the library names an extent it refuses)
+        Footprints r;
+        r.n_steps = n_steps, r.n_traj = (int)(poses_xyyaw.size() / (3 * (size_t)n_steps));
+        std::vector<int32_t> poses(4 * (size_t)r.n_traj * (size_t)n_steps, 0);
+        for (size_t i = 0; i < poses.size() / 4; ++i)
+            if (!std::isnan(poses_xyyaw[3 * i + 2])) check(pwpp_footprint_pose(&g, poses_xyyaw[3 * i], poses_xyyaw[3 * i + 1], poses_xyyaw[3 * i + 2], &poses[4 * i]));
+        r.poses.resize((size_t)r.n_traj * (size_t)n_steps), r.trajectories.resize((size_t)r.n_traj);
+        check(pwpp_footprint_grid(h_, nx, ny, 1, PWPP_MEM_HOST, cost.data(), nullptr, reach.empty() ? nullptr : reach.data(), &rp, &fp, poses.data(), 1, r.n_traj, n_steps,
+                                  r.poses.data(), r.trajectories.data()));
         return r;
     }
     // ... and where the last frame fits that map (pwpp_match_obstacles): for every candidate pose (n_candidates x {a, b, tx, c, d, ty},

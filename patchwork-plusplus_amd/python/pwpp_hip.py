@@ -121,6 +121,17 @@ ROUTE_OK, ROUTE_NONE, ROUTE_BROKEN = 0, 1, 2  # PWPP_ROUTE_*: the status of a ro
 ROUTE_DTYPE = np.dtype([(n, "<i4") for n in ("status", "cells", "cost", "edge_steps", "corner_steps", "max_term", "min_dist2", "waypoints")])  # pwpp_route (32 bytes)
 
 
+class FootprintParams(ctypes.Structure):  # pwpp_footprint_params (24 bytes): the rectangle [-rear, front] x [-half_width, half_width] in ticks of 1/16 cell, the flags
+    _fields_ = [("front", ctypes.c_int32), ("rear", ctypes.c_int32), ("half_width", ctypes.c_int32), ("flags", ctypes.c_int32), ("pad_", ctypes.c_int32 * 2)]
+
+
+FOOT_FREE, FOOT_HIT, FOOT_SKIPPED = 0, 1, 2  # PWPP_FOOT_*: the status of a pose
+FOOT_OUTSIDE_BLOCKS = 1  # PWPP_FOOT_OUTSIDE_BLOCKS: a covered cell outside the image makes the pose a HIT
+FOOT_SUB = 16  # PWPP_FOOT_SUB: ticks per cell side
+FOOT_POSE_DTYPE = np.dtype([(n, "<i4") for n in ("status", "covered", "outside", "blocked", "unknown", "max_term", "min_dist2", "hit")])  # pwpp_footprint_pose_row (32 bytes)
+FOOT_TRAJ_DTYPE = np.dtype([(n, "<i4") for n in ("first_hit", "free_steps", "last", "max_term", "sum_term", "unknown", "min_dist2", "reach_last")])  # pwpp_footprint_traj_row (32 bytes)
+
+
 class CostmapParams(ctypes.Structure):  # pwpp_costmap_params (24 bytes): the layers' mask, what an unknown occupancy / terrain byte counts as, when unknown wins
     _fields_ = [("layers", ctypes.c_int32), ("occupancy_unknown", ctypes.c_int32), ("terrain_unknown", ctypes.c_int32),
                 ("unknown_below", ctypes.c_int32), ("pad_", ctypes.c_int32 * 2)]
@@ -289,6 +300,11 @@ def load():
             rp, qp = ctypes.POINTER(ReachParams), ctypes.POINTER(RouteParams)
             L.pwpp_route_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, vp, ci, ci, qp, vp, vp, vp]
             L.pwpp_plan_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, rp, vp, ci, vp, ci, ci, qp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pwpp_footprint_grid"):  # (as above: an older build has no footprints)
+            rp, fp, i32p = ctypes.POINTER(ReachParams), ctypes.POINTER(FootprintParams), ctypes.POINTER(ctypes.c_int32)
+            L.pwpp_footprint_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, rp, fp, vp, ci, ci, ci, vp, vp]
+            L.pwpp_footprint_covers.argtypes = [fp, i32p, ci, ci]
+            L.pwpp_footprint_pose.argtypes = [ctypes.POINTER(GroundGrid), ctypes.c_double, ctypes.c_double, ctypes.c_double, i32p]
         if hasattr(L, "pwpp_costmap_grid"):  # (as above: an older build has no costmap)
             gp, tp, cp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams), ctypes.POINTER(CostmapParams)
             cf, cd, i32 = ctypes.c_float, ctypes.c_double, ctypes.c_int32
@@ -341,6 +357,28 @@ def costmap_curve(cell, inscribed, radius, decay, peak, capacity=COSTMAP_MAX_CUR
     if n < 0:
         raise PwppError("pwpp error %d: %s" % (n, L.pwpp_last_error().decode()))
     return out[:n].copy()
+
+
+def footprint_covers(foot_params, pose, ix, iy):
+    """Whether the rectangle of the FootprintParams at the pose {px, py, ux, uy} covers cell (ix, iy): pwpp_footprint_covers, the rule
+    the kernels use, on the host; needs no device."""
+    L = load()
+    q = (ctypes.c_int32 * 4)(*[int(v) for v in pose])
+    rc = L.pwpp_footprint_covers(ctypes.byref(foot_params), q, int(ix), int(iy))
+    if rc < 0:
+        raise PwppError("pwpp error %d: %s" % (rc, L.pwpp_last_error().decode()))
+    return bool(rc)
+
+
+def footprint_pose(grid, x, y, yaw):
+    """The pose {px, py, ux, uy} of a position in metres and a yaw in radians over the GroundGrid `grid` (pwpp_footprint_pose): ticks of
+    1/16 cell from the grid's origin, floored, and the heading lround(1024 cos), lround(1024 sin).  A convenience; needs no device."""
+    L = load()
+    q = (ctypes.c_int32 * 4)()
+    rc = L.pwpp_footprint_pose(ctypes.byref(grid), float(x), float(y), float(yaw), q)
+    if rc < 0:
+        raise PwppError("pwpp error %d: %s" % (rc, L.pwpp_last_error().decode()))
+    return np.array(list(q), np.int32)
 
 
 def evidence_verdict(rule, cells, landed, occupied, free):
@@ -1635,6 +1673,46 @@ class Handle:
         self._check(self._L.pwpp_plan_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(cost_ptr), _dp(dist2_ptr), ctypes.byref(params),
                                            _vp(src) if src.size else None, len(src), _vp(st) if st.size else None, sets, n, ctypes.byref(route_params),
                                            _dp(routes_ptr), _dp(cells_ptr), _dp(waypoints_ptr), _dp(reach_ptr), _dp(from_ptr)))
+
+    @staticmethod
+    def _poses(poses, frames):
+        """The poses as the call takes them: (n_steps, 4), (n_traj, n_steps, 4) for every frame or (n_sets, n_traj, n_steps, 4) -> (array, n_sets, n_traj, n_steps)."""
+        q = np.ascontiguousarray(np.asarray(poses, np.int32))
+        while q.ndim < 4:
+            q = q.reshape((1,) + q.shape)
+        if q.ndim != 4 or q.shape[-1] != 4:
+            raise ValueError("poses: (n_steps, 4), (n_traj, n_steps, 4) or (n_sets, n_traj, n_steps, 4) entries {px, py, ux, uy} expected")
+        return q, q.shape[0], q.shape[1], q.shape[2]
+
+    def footprint_grid(self, cost, params, foot_params, poses, dist2=None, reach=None, want_poses=True, want_trajectories=True):
+        """The oriented footprint over cost images: for every frame of the (frames, ny, nx) or (ny, nx) int8 cost images, every
+        trajectory and every step the rectangle of the FootprintParams `foot_params` at the pose {px, py, ux, uy} (ticks of 1/16 cell, an
+        integer heading) judged by the ReachParams `params` (and dist2 with a clearance).  poses: (n_steps, 4), (n_traj, n_steps, 4) for
+        every frame or (frames, n_traj, n_steps, 4).  Returns (pose_rows, traj_rows): (frames, n_traj, n_steps) FOOT_POSE_DTYPE rows and
+        (frames, n_traj) FOOT_TRAJ_DTYPE rows, None for the one not wanted.  reach: the int32 field whose value at the last free pose a
+        trajectory row carries.  The rules: include/pwpp.h."""
+        cst = np.ascontiguousarray(cost, np.int8)
+        c3 = cst.reshape((1,) + cst.shape) if cst.ndim == 2 else cst
+        if c3.ndim != 3:
+            raise ValueError("cost: a (frames, ny, nx) or (ny, nx) image expected")
+        d3 = None if dist2 is None else np.ascontiguousarray(dist2, np.int32)
+        r3 = None if reach is None else np.ascontiguousarray(reach, np.int32)
+        if (d3 is not None and d3.size != c3.size) or (r3 is not None and r3.size != c3.size):
+            raise ValueError("dist2, reach: images of cost's shape expected")
+        q, sets, n_traj, n_steps = self._poses(poses, c3.shape[0])
+        prow = np.empty((c3.shape[0], n_traj, n_steps), FOOT_POSE_DTYPE) if want_poses else None
+        trow = np.empty((c3.shape[0], n_traj), FOOT_TRAJ_DTYPE) if want_trajectories else None
+        self._check(self._L.pwpp_footprint_grid(self._h, c3.shape[2], c3.shape[1], c3.shape[0], MEM_HOST, _hp(c3), _hp(d3), _hp(r3), ctypes.byref(params),
+                                                ctypes.byref(foot_params), _hp(q), sets, n_traj, n_steps, _hp(prow), _hp(trow)))
+        return prow, trow
+
+    def footprint_grid_device(self, nx, ny, frames, cost_ptr, params, foot_params, poses, pose_rows_ptr=0, traj_rows_ptr=0, dist2_ptr=0, reach_ptr=0):
+        """footprint_grid on device memory: addresses of the (frames, ny, nx) int8 cost images (any address), of the int32 dist2 and
+        reach images and of the rows of 32 bytes (0: none; 4-byte aligned); poses stay a host array.  Enqueued on the handle's stream;
+        complete after synchronize()."""
+        q, sets, n_traj, n_steps = self._poses(poses, frames)
+        self._check(self._L.pwpp_footprint_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(cost_ptr), _dp(dist2_ptr), _dp(reach_ptr), ctypes.byref(params),
+                                                ctypes.byref(foot_params), _vp(q) if q.size else None, sets, n_traj, n_steps, _dp(pose_rows_ptr), _dp(traj_rows_ptr)))
 
     def costmap_grid(self, params, occupancy=None, terrain=None, dist2=None, curve=None, want_why=False):
         """The costmap of (frames, ny, nx) or (ny, nx) images under the CostmapParams `params`: the int8 occupancy bytes, the int8

@@ -140,6 +140,16 @@ std::vector<double> positions_of(const py::object &xy) {
     return std::vector<double>(a.data(), a.data() + a.size());
 }
 
+// (pose rows (n_traj, n_steps, 8) int32 -- status, covered, outside, blocked, unknown, max_term, min_dist2, hit --, trajectory rows (n_traj, 8)
+// int32 -- first_hit, free_steps, last, max_term, sum_term, unknown, min_dist2, reach_last) of a footprint call
+template <class Footprints>
+py::tuple footprints_tuple(const Footprints &r) {
+    py::array_t<int32_t> poses({(py::ssize_t)r.n_traj, (py::ssize_t)r.n_steps, (py::ssize_t)8}), trajs({(py::ssize_t)r.n_traj, (py::ssize_t)8});
+    if (!r.poses.empty()) std::memcpy(poses.mutable_data(), r.poses.data(), r.poses.size() * sizeof(r.poses[0]));
+    if (!r.trajectories.empty()) std::memcpy(trajs.mutable_data(), r.trajectories.data(), r.trajectories.size() * sizeof(r.trajectories[0]));
+    return py::make_tuple(poses, trajs);
+}
+
 // (cost, why) of a costmap call as (ny, nx) arrays
 template <class Costmap>
 py::tuple costmap_tuple(const Costmap &c) {
@@ -235,6 +245,13 @@ PYBIND11_MODULE(pypatchworkpp, m) {
         .def_readwrite("max_waypoints", &PatchWorkpp::RouteParams::max_waypoints)
         .def_readwrite("look", &PatchWorkpp::RouteParams::look)
         .def_readwrite("line_cost", &PatchWorkpp::RouteParams::line_cost);
+    py::class_<PatchWorkpp::FootprintParams>(m, "FootprintParams")  // the vehicle's rectangle in metres, its padding in ticks, the flag of checkFootprints
+        .def(py::init<>())
+        .def_readwrite("front", &PatchWorkpp::FootprintParams::front)
+        .def_readwrite("rear", &PatchWorkpp::FootprintParams::rear)
+        .def_readwrite("half_width", &PatchWorkpp::FootprintParams::half_width)
+        .def_readwrite("pad", &PatchWorkpp::FootprintParams::pad)
+        .def_readwrite("outside_blocks", &PatchWorkpp::FootprintParams::outside_blocks);
     py::class_<PatchWorkpp::ReachParams>(m, "ReachParams")  // the step costs and the limits of getReach and fusedReach
         .def(py::init<>())
         .def_readwrite("base", &PatchWorkpp::ReachParams::base)
@@ -387,6 +404,24 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              py::arg("cost"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("starts_xy"),
              py::arg("reach_params") = PatchWorkpp::ReachParams(), py::arg("route_params") = PatchWorkpp::RouteParams(), py::arg("source_x") = 0.0,
              py::arg("source_y") = 0.0)
+        .def("checkFootprints",
+             [](PatchWorkpp &s, const py::object &cost, double x0, double y0, double cell, int nx, int ny, const py::object &poses_xyyaw,
+                const PatchWorkpp::FootprintParams &footprint_params, const PatchWorkpp::ReachParams &reach_params, const py::object &reach) {
+                 const auto c = py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(cost);
+                 if (!c) throw std::invalid_argument("cost: an int8 image expected");
+                 const auto q = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(poses_xyyaw);
+                 if (!q || q.ndim() != 3 || q.shape(2) != 3) throw std::invalid_argument("poses_xyyaw: (n_traj, n_steps, 3) expected");
+                 std::vector<int32_t> field;
+                 if (!reach.is_none()) {
+                     const auto f = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(reach);
+                     if (!f) throw std::invalid_argument("reach: an int32 image expected");
+                     field.assign(f.data(), f.data() + f.size());
+                 }
+                 return footprints_tuple(s.checkFootprints(std::vector<int8_t>(c.data(), c.data() + c.size()), x0, y0, cell, nx, ny,
+                                                           std::vector<double>(q.data(), q.data() + q.size()), (int)q.shape(1), footprint_params, reach_params, field));
+             },
+             py::arg("cost"), py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("poses_xyyaw"),
+             py::arg("footprint_params") = PatchWorkpp::FootprintParams(), py::arg("reach_params") = PatchWorkpp::ReachParams(), py::arg("reach") = py::none())
         .def_static("inflationCurve",
                     [](double cell, double inscribed, double radius, double decay, int peak) {
                         const std::vector<uint8_t> c = PatchWorkpp::inflationCurve(cell, inscribed, radius, decay, peak);
