@@ -1571,6 +1571,99 @@ PWPP_API int pwpp_footprint_grid(pwpp_handle *h, int nx, int ny, int frames, int
 PWPP_API int pwpp_footprint_covers(const pwpp_footprint_params *fp, const int32_t pose[4], int ix, int iy);  /* host only: 1, 0 or PWPP_E_ARG */
 PWPP_API int pwpp_footprint_pose(const pwpp_ground_grid *g, double x, double y, double yaw, int32_t pose[4]); /* host only, a convenience */
 
+/* ---- viewshed: line of sight that sees over low obstacles, with ground returns (pwpp_viewshed_grid, pwpp_viewshed_obstacles) ----
+ * pwpp_visibility_* (above) stops a line at the first occupied cell, however low: every kerb, bollard and parked car throws a shadow
+ * to the edge of the grid although the sensor, mounted above them, saw the road behind.  This operator walks the SAME digital line
+ * with heights: an occupied cell hides a cell behind it only if the ray from the eye to that cell's ground (or top) passes through
+ * it; and a cell whose ground sent a return back is free whatever the line says.  Per cell, integers only, each frame on its own,
+ * the same bytes whatever the schedule.  The upstream Patchwork++ has nothing of this kind.
+ *   heights   int32, all in one unit with the vertical origin of the caller's choice; PWPP_VIEW_NO_HEIGHT (INT32_MIN) is "none".
+ *             R = PWPP_VIEW_MAX_RISE = 2^20.
+ *   origin    {ox, oy, eye} per frame: the sensor's cell, inside the image, and its height.  HOST memory in both mem kinds, n_origins
+ *             1 or `frames`, copied at the call like the origins of pwpp_visibility_grid.  eye == PWPP_VIEW_NO_HEIGHT: PWPP_E_ARG,
+ *             naming the entry.
+ *   cells     A cell is occupied iff count >= min_count.  An occupied cell has the blocker rise clamp(block - eye, -R, R), computed in
+ *             64 bits; one whose block is PWPP_VIEW_NO_HEIGHT, and every occupied cell when `block` is NULL, is OPAQUE.  A cell's
+ *             target rise t is that of `block` where the cell is occupied (is its top seen?), else that of `target`, clamped alike; a
+ *             height of PWPP_VIEW_NO_HEIGHT, or a NULL image, counts as minus infinity.
+ *   walk      The line and its points P_k, k = 0 .. n, are those of pwpp_visibility_grid.  At step k = 1 .. n, in this order:
+ *             (a) if both coordinates changed and A = (x_{k-1}, y_k) and B = (x_k, y_{k-1}) are both occupied, the gap between them
+ *             is a blocker at D = 2k - 1 whose rise is the smaller of the two rises -- a finite rise counts as below opaque -- and
+ *             whose reported cell is the one with the smaller rise, on equal rises the smaller index; (b) for k < n only: if P_k is
+ *             occupied it is a blocker at D = 2k with its own rise.  The cell's own returns never hide the cell itself, and the
+ *             origin's cell never blocks.
+ *   hides     A blocker (r, D) hides the target iff it is opaque, or t is minus infinity, or r * 2n > t * D.  Strict: a grazing ray
+ *             sees.  Every product stays below 2^38.
+ *   first     In this order: PWPP_VIS_BEYOND if n > max_range > 0 (nothing on the line is read then); the reported cell of the NEAREST
+ *             blocker that hides; the cell's own index if it is occupied; PWPP_VIS_NONE.
+ *   shadow    (may be NULL) the lowest height seen at the cell: PWPP_VIEW_NO_HEIGHT when the line has no blocker or the cell is
+ *             beyond range; INT32_MAX behind an opaque blocker; otherwise eye + clamp(max over the blockers b of
+ *             ceil(r_b * 2n / D_b), -R, R + 1), the division exact (a sum beyond the int32 range saturates at INT32_MIN + 1 and
+ *             INT32_MAX - 1: only with |eye| > 2^31 - 2^20 - 2).  THEOREM: a cell whose line has a blocker is hidden iff its target rise
+ *             < shadow - eye (minus infinity is below everything, INT32_MAX above).
+ *   occupancy (may be NULL) in this order: PWPP_OCC_OCCUPIED where the cell is occupied; else PWPP_OCC_FREE where `seen` is given and
+ *             seen >= min_seen -- a WITNESSED cell: a return came back from its ground; it holds beyond max_range too; else
+ *             PWPP_OCC_FREE where first == PWPP_VIS_NONE; else PWPP_OCC_UNKNOWN.
+ *   THEOREMS  1. With block, target and seen NULL, first and occupancy are byte for byte those of pwpp_visibility_grid: every blocker
+ *             is opaque and hides, rule (b) at k = n is the cell's own index.  2. For any heights the FREE cells of
+ *             pwpp_visibility_grid are a subset of this operator's: a line without an occupied cell has no blocker.  3. max_range
+ *             changes no value inside it.  4. A kerb of height 1500 at cell 4 of a row, seen from cell 0 with eye 1700 over ground 0
+ *             (r = -200, t = -1700, D = 8: hidden iff 400 n < 13600), hides exactly the cells 5 .. 33; shadow is 1200 at cell 10 and 0
+ *             at cell 34.
+ *   units     pwpp_viewshed_units, the quantiser of the chained call, PWPP_VIEW_UNITS_PER_M = 1024: PWPP_VIEW_NO_HEIGHT for a NaN,
+ *             otherwise floor(clamp(metres * 1024.0, -2^30, 2^30) + 0.5), in double.
+ *   ground_returns   seen[f][iy][ix] = the points the frame's GROUND index list names that fall into the cell, by the cell rule of
+ *             pwpp_rasterize_obstacles on the same INPUT; when, mem, the lifetime rule and the errors are that function's, except
+ *             that g->flags must be 0 (there is no reference to blank).  Integer adds: a function of the input alone.
+ *   viewshed_obstacles   enqueues, on the handle's stream: the obstacle raster (count, top) of pwpp_rasterize_obstacles(g, h_min, h_max,
+ *             ...); the ground raster of pwpp_rasterize_ground on the same grid (g->flags 0 or PWPP_GRID_GROUND_ONLY); where min_seen >
+ *             0 the ground-returns raster (min_seen == 0: no `seen`; it reads no flags); and pwpp_viewshed_grid with target =
+ *             units(ground), block = units((double)ground + (double)top), eye = units(z) of the origin {x, y, z} in metres, x and y
+ *             turned into a cell as pwpp_visibility_obstacles turns them.  The quantiser runs on the device, the same function: a NaN
+ *             ground gives an opaque blocker and a target at minus infinity -- the 2-D answer, the conservative side.  The images
+ *             are exactly what the four calls give one after the other.
+ *   mem       as pwpp_visibility_grid: PWPP_MEM_HOST stages every image through the handle's cluster buffer, synchronous;
+ *             PWPP_MEM_DEVICE: device memory, the int32 images 4-byte aligned and no more, occupancy byte aligned, enqueued on the
+ *             handle's stream.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    pwpp_viewshed_grid: PWPP_E_ARG, named before the device is touched, in this order: a null handle, count, first or
+ *             origin; nx, ny or frames < 1; nx or ny > 32768; nx * ny * frames beyond 2^31; min_count < 1; max_range outside 0 ..
+ *             32768; min_seen < 1 with a non-null seen; the number of origins; an origin outside the image; an eye that is
+ *             PWPP_VIEW_NO_HEIGHT; mem.  pwpp_viewshed_obstacles: a null handle, grid, first or origin; everything
+ *             pwpp_visibility_obstacles rejects up to max_range; min_seen < 0; the number of origins; an origin that is not finite
+ *             (z included) or outside the grid; then what pwpp_rasterize_obstacles rejects of the frame range and mem;
+ *             PWPP_E_STATE before any estimate call.
+ *   buffers   The bit image of "viewshed_path" 2 (one bit per cell, rows padded to 32), the origins where there is one per frame, in
+ *             PWPP_MEM_HOST the staged images and in the chained call its five intermediate images lie in the cluster buffer:
+ *             counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ * pwpp_fuse_obstacles, pwpp_match_obstacles and pwpp_costmap_obstacles keep the 2-D bytes of pwpp_visibility_obstacles; feed these
+ * bytes to pwpp_fuse_grid, pwpp_match_grid and pwpp_costmap_grid instead.  The same bytes for every mem, alignment
+ * and value of the option "viewshed_path".  With none of the functions called nothing is allocated or launched, and no result, state
+ * or timing of any other call changes. */
+#define PWPP_HAS_VIEWSHED 1
+#define PWPP_VIEW_NO_HEIGHT (-2147483647 - 1)   /* INT32_MIN: no height */
+#define PWPP_VIEW_MAX_RISE 1048576              /* R = 2^20 units */
+#define PWPP_VIEW_UNITS_PER_M 1024
+
+/* any images: needs a handle (stream, buffer), no estimate call -- like pwpp_visibility_grid */
+PWPP_API int pwpp_viewshed_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
+                                const int32_t *count /* [frames][ny][nx] */, int min_count,
+                                const int32_t *block /* same shape, may be NULL */, const int32_t *target /* same shape, may be NULL */,
+                                const int32_t *seen /* same shape, may be NULL */, int min_seen,
+                                const int32_t *origin /* HOST memory, n_origins x {ox, oy, eye} */, int n_origins,
+                                int max_range /* cells, Chebyshev; 0: unlimited */,
+                                int32_t *first /* [frames][ny][nx] */, int32_t *shadow /* same shape, may be NULL */,
+                                int8_t *occupancy /* same shape, may be NULL */);
+/* the ground list of frames of the LAST estimate call per cell -- like pwpp_rasterize_obstacles */
+PWPP_API int pwpp_rasterize_ground_returns(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem,
+                                           int32_t *seen /* [frames][ny][nx] */);
+/* both rasters + ground returns + viewshed for frames of the LAST estimate call, one call -- like pwpp_visibility_obstacles */
+PWPP_API int pwpp_viewshed_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                     int min_count, int min_seen, const double *origin_xyz /* HOST, n_origins x {x, y, z} metres */,
+                                     int n_origins, int max_range, int frame_first, int frames, int mem,
+                                     int32_t *first, int32_t *shadow /* may be NULL */, int8_t *occupancy /* may be NULL */,
+                                     int32_t *count /* may be NULL: kept */);
+PWPP_API int32_t pwpp_viewshed_units(double metres);   /* host only: the quantiser */
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU
@@ -1728,6 +1821,12 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         tools/footprint_cost.py decided -- "2" for a call whose max(front, rear) + half_width is 504 ticks or more
  *                         and that asks for no pose rows (it stops a trajectory at its first hit) or reads dist2, "1" otherwise.
  *                         The same bytes for every value.
+ *   "viewshed_path"       how the viewshed tests a cell (pwpp_viewshed_grid, pwpp_viewshed_obstacles), a lane per cell either way: "1":
+ *                         every test reads count and every rise reads block in global memory (the yardstick); "2": the occupancy packed
+ *                         into the visibility's bit image, the rows a run of 256 cells can touch kept in LDS where the frame's image
+ *                         fits 128 KiB, a rise fetched from global memory only where a bit is set; "0" (default): what
+ *                         tools/viewshed_cost.py decided -- "2" for a call with max_range 0, "1" under a max_range.  The same bytes
+ *                         for every value.
  *   "costmap_path"        how the costmap's fold is dealt (pwpp_costmap_grid, pwpp_costmap_obstacles): "1": a lane per cell, the inflation
  *                         curve read from global memory (the yardstick); "2": the curve staged once per workgroup into LDS, four
  *                         consecutive cells a lane, the byte images as one dword where their address allows; "0" (default): what

@@ -35,6 +35,7 @@
 #include "pwpp_footprint.h"
 #include "pwpp_terrain.h"
 #include "pwpp_tracks.h"
+#include "pwpp_viewshed.h"
 #include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
@@ -258,6 +259,7 @@ struct pwpp_handle {
     int clusters_path = 0;          // option "clusters_path": 0 = tiles in LDS, then their borders; 1 = the global union-find alone (yardstick)
     int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
+    int viewshed_path = 0;          // option "viewshed_path": 0 = what tools/viewshed_cost.py decided (pwpp_viewshed_path_of: 2 for an unlimited call, 1 under a max_range); 1 = count and block in global memory (yardstick); 2 = the bit image, in LDS where it fits, a rise fetched only where a bit is set
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
@@ -1280,6 +1282,7 @@ constexpr PathOption kPathOptions[] = {
     {"clusters_path", &pwpp_handle::clusters_path, 1},
     {"distance_path", &pwpp_handle::distance_path, 1},
     {"visibility_path", &pwpp_handle::visibility_path, 1},
+    {"viewshed_path", &pwpp_handle::viewshed_path, 2},
     {"fusion_path", &pwpp_handle::fusion_path, 1},
     {"elevation_path", &pwpp_handle::elevation_path, 2},
     {"terrain_path", &pwpp_handle::terrain_path, 2},
@@ -2861,6 +2864,127 @@ int pwpp_visibility_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h
     return run_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, -1, [&](const PwppObstacleScan &) {
         return visibility_launch(h, st, s, g->nx, g->ny, frames, min_count, org, max_range);
     });
+}
+
+// ---- viewshed: the visibility's walk with heights -- the nearest cell that hides, the lowest height seen, the tri-state byte ---------
+namespace {
+static_assert(PWPP_VIEW_NO_HEIGHT == PWPP_VIEW_NONE_HEIGHT && PWPP_VIEW_MAX_RISE == PWPP_VIEW_RISE_MAX && PWPP_VIEW_UNITS_PER_M == PWPP_VIEW_UNITS,
+              "the kernels' heights");
+constexpr const char *kViewshedWho = "the viewshed takes";
+
+// (the kernels' bit image and the origins first; `org`: n_origins x {ox, oy, eye}, checked.  One origin travels as arguments.)
+struct ViewshedSections {
+    int work, org, count, block, target, seen, first, shadow, occ;
+};
+void viewshed_out_sections(pwpp_handle *h, Staging &st, int nx, int ny, int frames, int max_range, const std::vector<int32_t> &org, ViewshedSections &s) {
+    s.work = st.add(pwpp_viewshed_work_words(nx, ny, frames, h->viewshed_path, max_range), nullptr, Staging::kKept);
+    s.org = org.size() > 3 ? st.add_upload(std::vector<uint32_t>(org.begin(), org.end())) : st.add(0, nullptr, Staging::kKept);
+}
+int viewshed_launch(pwpp_handle *h, const Staging &st, const ViewshedSections &s, int nx, int ny, int frames, int min_count, int min_seen,
+                    const std::vector<int32_t> &org, int max_range) {
+    return pwpp_launch_viewshed_grid(nx, ny, frames, st.dev<const int32_t>(s.count), min_count, st.dev<const int32_t>(s.block), st.dev<const int32_t>(s.target),
+                                     st.dev<const int32_t>(s.seen), min_seen, org[0], org[1], org[2], org.size() > 3 ? st.dev<const int32_t>(s.org) : nullptr,
+                                     max_range, h->viewshed_path, st.dev<int32_t>(s.first), st.dev<int32_t>(s.shadow), st.dev<int8_t>(s.occ),
+                                     st.dev<uint32_t>(s.work), h->stream);
+}
+}  // namespace
+
+int32_t pwpp_viewshed_units(double metres) { return pwpp_view_units(metres); }
+
+int pwpp_viewshed_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *count, int min_count, const int32_t *block, const int32_t *target,
+                       const int32_t *seen, int min_seen, const int32_t *origin, int n_origins, int max_range, int32_t *first, int32_t *shadow,
+                       int8_t *occupancy) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!count || !first || !origin) return fail(PWPP_E_ARG, "null %s", !count ? "count image" : (!first ? "first image" : "origin"));
+    size_t cells = 0;
+    int rc = image_args(nx, ny, frames, kViewshedWho, cells);
+    if (rc) return rc;
+    if ((rc = visibility_param_args(min_count, max_range))) return rc;
+    if (seen && min_seen < 1) return fail(PWPP_E_ARG, "min_seen %d with a seen image: at least 1 expected", min_seen);
+    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
+    for (int i = 0; i < n_origins; ++i)
+        if (origin[3 * i] < 0 || origin[3 * i] >= nx || origin[3 * i + 1] < 0 || origin[3 * i + 1] >= ny)
+            return fail(PWPP_E_ARG, "origin %d, cell (%d, %d), lies outside the %d x %d cells", i, origin[3 * i], origin[3 * i + 1], nx, ny);
+    for (int i = 0; i < n_origins; ++i)
+        if (origin[3 * i + 2] == PWPP_VIEW_NO_HEIGHT) return fail(PWPP_E_ARG, "origin %d: its eye is PWPP_VIEW_NO_HEIGHT", i);
+    if ((rc = mem_args(mem, kViewshedWho))) return rc;
+    const std::vector<int32_t> org(origin, origin + 3 * (size_t)n_origins);
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    ViewshedSections s;
+    viewshed_out_sections(h, st, nx, ny, frames, max_range, org, s);
+    s.count = add_image(st, cells, count, false), s.block = add_image(st, cells, block, false), s.target = add_image(st, cells, target, false);
+    s.seen = add_image(st, cells, seen, false);
+    s.first = st.add(cells, first, Staging::kOut), s.shadow = st.add(shadow ? cells : 0, shadow, Staging::kOut);
+    s.occ = st.add_bytes(cells, occupancy, Staging::kOut);
+    return run_on_image(h, st, [&] { return viewshed_launch(h, st, s, nx, ny, frames, min_count, min_seen, org, max_range); });
+}
+
+// The ground list of the last call per cell of the grid.
+int pwpp_rasterize_ground_returns(pwpp_handle *h, const pwpp_ground_grid *g, int frame_first, int frames, int mem, int32_t *seen) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !seen) return fail(PWPP_E_ARG, "null %s", g ? "seen image" : "grid");
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: 0 expected by the ground returns", g->flags);
+    size_t cells = 0;
+    int rc = ground_grid_args(h, g, frame_first, frames, mem, cells);
+    if (rc) return rc;
+    Staging st(h, h->d_ground_stage, mem);
+    const int s_seen = st.add(cells, seen, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, 0.0f, 0.0f, frame_first, frames, scan))) return rc;
+    int max_ground = 0;
+    for (int f = frame_first; f < frame_first + frames; ++f) max_ground = std::max(max_ground, h->h_results.p[f].n_ground);
+    const int lrc = pwpp_launch_ground_returns(&scan, max_ground, st.dev<int32_t>(s_seen), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// Both rasters, the quantiser, the ground returns and the viewshed, one enqueued sequence.
+int pwpp_viewshed_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int min_count, int min_seen, const double *origin_xyz,
+                            int n_origins, int max_range, int frame_first, int frames, int mem, int32_t *first, int32_t *shadow, int8_t *occupancy,
+                            int32_t *count) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !first || !origin_xyz) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!first ? "first image" : "origin"));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc || (rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
+    if ((rc = side_args(g->nx, g->ny, kViewshedWho))) return rc;
+    if ((rc = visibility_param_args(min_count, max_range))) return rc;
+    if (min_seen < 0) return fail(PWPP_E_ARG, "min_seen %d: 0 (no ground returns) or more expected", min_seen);
+    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
+    std::vector<int32_t> org(3 * (size_t)n_origins, 0);
+    for (int i = 0; i < n_origins; ++i) {
+        const double x = origin_xyz[3 * i], y = origin_xyz[3 * i + 1], z = origin_xyz[3 * i + 2];
+        int ox = 0, oy = 0;
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(PWPP_E_ARG, "origin %d, (%g, %g, %g), is not finite", i, x, y, z);
+        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
+            return fail(PWPP_E_ARG, "origin %d, (%g, %g) m, lies outside the grid", i, x, y);
+        org[3 * i] = ox, org[3 * i + 1] = oy, org[3 * i + 2] = pwpp_view_units(z);
+    }
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    const int nx = g->nx, ny = g->ny;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    ViewshedSections s;
+    viewshed_out_sections(h, st, nx, ny, frames, max_range, org, s);
+    s.count = add_image(st, cells, count, true);
+    const int s_top = st.add(cells, nullptr, Staging::kKept), s_ground = st.add(cells, nullptr, Staging::kKept);
+    s.block = st.add(cells, nullptr, Staging::kKept), s.target = st.add(cells, nullptr, Staging::kKept);
+    s.seen = min_seen > 0 ? st.add(cells, nullptr, Staging::kKept) : st.add(0, nullptr, Staging::kIn);  // (an absent array: a null device pointer)
+    s.first = st.add(cells, first, Staging::kOut), s.shadow = st.add(shadow ? cells : 0, shadow, Staging::kOut);
+    s.occ = st.add_bytes(cells, occupancy, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    rc = enqueue_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s_top, [&](const PwppObstacleScan &scan) {
+        if (min_seen <= 0) return 0;
+        int max_ground = 0;
+        for (int f = frame_first; f < frame_first + frames; ++f) max_ground = std::max(max_ground, h->h_results.p[f].n_ground);
+        return pwpp_launch_ground_returns(&scan, max_ground, st.dev<int32_t>(s.seen), h->stream);
+    });
+    if (rc) return rc;
+    rc = enqueue_on_ground(h, st, g, frame_first, frames, s_ground, -1, [&] {
+        const int lrc = pwpp_launch_viewshed_quantise(cells, st.dev<const float>(s_ground), st.dev<const float>(s_top), st.dev<int32_t>(s.target),
+                                                      st.dev<int32_t>(s.block), h->stream);
+        return lrc != 0 ? lrc : viewshed_launch(h, st, s, nx, ny, frames, min_count, min_seen, org, max_range);
+    });
+    return rc ? rc : st.end();
 }
 
 // ---- occupancy fusion: per-frame occupancy bytes, under a pose per frame, into persistent int16 log-odds maps --------------------

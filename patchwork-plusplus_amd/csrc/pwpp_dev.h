@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_footprint.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_viewshed.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_footprint.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -314,6 +314,7 @@ int pwpp_launch_ground_query(const PwppGroundView *view, const float *xyz, const
 int pwpp_launch_ground_raster(const PwppGroundView *view, const PwppGroundGrid *grid, int frame_first, int frames, float *height, int32_t *patch,
                               hipStream_t stream);
 int pwpp_launch_obstacle_raster(const PwppObstacleScan *scan, int32_t *count, float *top, int32_t *unref, hipStream_t stream);
+int pwpp_launch_ground_returns(const PwppObstacleScan *scan, int max_ground, int32_t *seen, hipStream_t stream);
 int pwpp_launch_point_cluster(const PwppObstacleScan *scan, const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
 int pwpp_launch_box_pass(int pass, int combine, const PwppObstacleScan *scan, const PwppBoxRows *rows, hipStream_t stream);
 // pwpp_fit.hip
@@ -333,6 +334,13 @@ int pwpp_launch_distance_grid(int nx, int ny, int frames, const int32_t *count, 
 size_t pwpp_visibility_work_words(int nx, int ny, int frames, int path);
 int pwpp_launch_visibility_grid(int nx, int ny, int frames, const int32_t *count, int min_count, int ox, int oy, const int32_t *origins, int max_range,
                                 int path, int32_t *first, int8_t *occupancy, uint32_t *work, hipStream_t stream);
+// pwpp_viewshed.hip (k_view_walk<1>: "viewshed_path" 1; k_view_pack, k_view_walk<2>: 2)
+int pwpp_viewshed_path_of(int path, int max_range);  // what "viewshed_path" resolves to for a call: 1 or 2
+size_t pwpp_viewshed_work_words(int nx, int ny, int frames, int path, int max_range);
+int pwpp_launch_viewshed_grid(int nx, int ny, int frames, const int32_t *count, int min_count, const int32_t *block, const int32_t *target,
+                              const int32_t *seen, int min_seen, int ox, int oy, int eye, const int32_t *origins, int max_range, int path,
+                              int32_t *first, int32_t *shadow, int8_t *occupancy, uint32_t *work, hipStream_t stream);
+int pwpp_launch_viewshed_quantise(size_t cells, const float *ground, const float *top, int32_t *target, int32_t *block, hipStream_t stream);
 // pwpp_fusion.hip
 int pwpp_launch_fuse_grid(const struct PwppFusionGeometry *G, const struct PwppFusionParams *P, int frames, const int8_t *occupancy, const double *poses,
                           int n_poses, int n_maps, const int32_t *begin, const int32_t *list, int listed, const int32_t *shift, const int16_t *map_in,

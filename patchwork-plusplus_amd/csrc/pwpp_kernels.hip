@@ -3135,6 +3135,26 @@ __global__ __launch_bounds__(kObBlock) void k_obstacle_raster(PwppObstacleScan S
     if (top) atomicMax(top + p.o, height_key(p.hgt));
 }
 
+// pwpp_rasterize_ground_returns: the same grid over the frame's GROUND list -- per cell the points that list names, by the same cell
+// rule, with no reference, height or band: a return from the cell's ground is a return.  grid (tiles of kObBlock entries over the
+// longest ground list of the range, frames); `seen` was zeroed by k_obstacle_fill.  Integer adds only.
+__global__ __launch_bounds__(kObBlock) void k_ground_returns(PwppObstacleScan S, int32_t *seen) {
+    const int fr = blockIdx.y, f = S.frame_first + fr;
+    if ((unsigned)f >= (unsigned)S.Q.num_frames) return;
+    const PwppFrameDesc fd = S.descs[f];
+    const int64_t n = fd.n, e = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    const int32_t g = S.results[f].n_ground;
+    const int64_t ng = g < 0 ? 0 : (g > n ? n : (int64_t)g);  // (the count clamped to the frame, as obstacle_point clamps it)
+    if (e >= ng) return;
+    const int i = S.out_idx[fd.base + e];
+    if ((unsigned)i >= (unsigned)fd.n) return;
+    float x, y, z, w;
+    load_point<true>(fd, i, x, y, z, w);
+    int ix, iy;
+    if (!grid_cell(x, S.G.x0, S.G.cell, S.G.nx, ix) || !grid_cell(y, S.G.y0, S.G.cell, S.G.ny, iy)) return;
+    atomicAdd(seen + ((size_t)fr * (size_t)S.G.ny + (size_t)iy) * (size_t)S.G.nx + (size_t)ix, 1);
+}
+
 // pwpp_label_obstacles' per-point cluster id: the scan of k_obstacle_raster again, and every COUNTED point takes the label of its
 // cell (-1 where the cell stayed below min_count).  point_cluster was filled with -1 and starts at the first point of S.frame_first
 // (`base_first`: that frame's fd.base); a point is named by at most one list entry, so every word has one writer.
@@ -3387,6 +3407,17 @@ extern "C" int pwpp_launch_obstacle_raster(const PwppObstacleScan *scan, int32_t
     dim3 g;
     if (scan_grid(*scan, g)) hipLaunchKernelGGL(k_obstacle_raster, g, dim3(kObBlock), 0, stream, *scan, count, keys, unref);
     if (top) hipLaunchKernelGGL(k_obstacle_top, dim3(quads), dim3(kObBlock), 0, stream, cells, keys);
+    return (int)hipGetLastError();
+}
+
+// pwpp_rasterize_ground_returns: fill, points (max_ground: the longest ground list of the range; 0: only the fill runs).
+extern "C" int pwpp_launch_ground_returns(const PwppObstacleScan *scan, int max_ground, int32_t *seen, hipStream_t stream) {
+    const int64_t cells = (int64_t)scan->G.nx * (int64_t)scan->G.ny * (int64_t)scan->frames;  // (<= 2^31: checked by the caller)
+    const unsigned quads = (unsigned)(((cells + 2) / 4 + 1 + kObBlock - 1) / kObBlock);
+    hipLaunchKernelGGL(k_obstacle_fill, dim3(quads), dim3(kObBlock), 0, stream, cells, reinterpret_cast<uint32_t *>(seen), nullptr, nullptr);
+    if (max_ground > 0)
+        hipLaunchKernelGGL(k_ground_returns, dim3((unsigned)(((int64_t)max_ground + kObBlock - 1) / kObBlock), (unsigned)scan->frames), dim3(kObBlock), 0, stream,
+                           *scan, seen);
     return (int)hipGetLastError();
 }
 

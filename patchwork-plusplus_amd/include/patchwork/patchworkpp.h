@@ -425,6 +425,32 @@ public:
                                         any ? v.occupancy.data() : &none_o, nullptr));
         return v;
     }
+    // ... the same with heights (pwpp_viewshed_obstacles): an obstacle hides a cell only where the ray from the sensor at (origin_x,
+    // origin_y, origin_z) metres to the cell's ground passes through it, and a cell whose ground sent min_seen returns back is free
+    // (min_seen 0: ground returns are not used).  first: the nearest cell that hides; shadow: the lowest height seen at the cell in
+    // units of 1 / PWPP_VIEW_UNITS_PER_M m (PWPP_VIEW_NO_HEIGHT: no obstacle on the line; INT32_MAX: behind an opaque one).
+    struct ObstacleViewshed {
+        int nx = 0, ny = 0;
+        std::vector<int32_t> first;     // ny x nx, row-major: row iy, column ix
+        std::vector<int32_t> shadow;    // same shape
+        std::vector<int8_t> occupancy;  // same shape
+    };
+    ObstacleViewshed getObstacleViewshed(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count = 1, int min_seen = 1,
+                                         int max_range = 0, double origin_x = 0.0, double origin_y = 0.0, double origin_z = 0.0, bool ground_only = false) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        ObstacleViewshed v;
+        v.nx = nx > 0 ? nx : 0, v.ny = ny > 0 ? ny : 0;
+        v.first.assign((size_t)v.nx * (size_t)v.ny, PWPP_VIS_NONE);
+        v.shadow.assign(v.first.size(), PWPP_VIEW_NO_HEIGHT);
+        v.occupancy.assign(v.first.size(), (int8_t)PWPP_OCC_UNKNOWN);
+        int32_t none_f = 0, none_s = 0;
+        int8_t none_o = 0;
+        const double origin[3] = {origin_x, origin_y, origin_z};
+        const bool any = !v.first.empty();
+        check(pwpp_viewshed_obstacles(h_, &g, h_min, h_max, min_count, min_seen, origin, 1, max_range, 0, 1, PWPP_MEM_HOST, any ? v.first.data() : &none_f,
+                                      any ? v.shadow.data() : &none_s, any ? v.occupancy.data() : &none_o, nullptr));
+        return v;
+    }
     // ... and the scans accumulated over time (pwpp_fuse_obstacles): a persistent map in a FIXED frame, the caller's own.  log_odds
     // holds an int16 per cell, occupancy the byte derived from it (PWPP_OCC_OCCUPIED where log_odds >= occupied_at, PWPP_OCC_FREE
     // where <= free_at, else PWPP_OCC_UNKNOWN).  updateObstacleMap resamples the last frame's visibility bytes on the grid (x0, y0,

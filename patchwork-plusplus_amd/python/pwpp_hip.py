@@ -128,6 +128,7 @@ class FootprintParams(ctypes.Structure):  # pwpp_footprint_params (24 bytes): th
 FOOT_FREE, FOOT_HIT, FOOT_SKIPPED = 0, 1, 2  # PWPP_FOOT_*: the status of a pose
 FOOT_OUTSIDE_BLOCKS = 1  # PWPP_FOOT_OUTSIDE_BLOCKS: a covered cell outside the image makes the pose a HIT
 FOOT_SUB = 16  # PWPP_FOOT_SUB: ticks per cell side
+VIEW_NO_HEIGHT, VIEW_MAX_RISE, VIEW_UNITS_PER_M = -2 ** 31, 1 << 20, 1024  # PWPP_VIEW_*: no height, the clamp of a rise, units per metre
 FOOT_POSE_DTYPE = np.dtype([(n, "<i4") for n in ("status", "covered", "outside", "blocked", "unknown", "max_term", "min_dist2", "hit")])  # pwpp_footprint_pose_row (32 bytes)
 FOOT_TRAJ_DTYPE = np.dtype([(n, "<i4") for n in ("first_hit", "free_steps", "last", "max_term", "sum_term", "unknown", "min_dist2", "reach_last")])  # pwpp_footprint_traj_row (32 bytes)
 
@@ -305,6 +306,13 @@ def load():
             L.pwpp_footprint_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, rp, fp, vp, ci, ci, ci, vp, vp]
             L.pwpp_footprint_covers.argtypes = [fp, i32p, ci, ci]
             L.pwpp_footprint_pose.argtypes = [ctypes.POINTER(GroundGrid), ctypes.c_double, ctypes.c_double, ctypes.c_double, i32p]
+        if hasattr(L, "pwpp_viewshed_grid"):  # (as above: an older build has no viewshed)
+            gp, cf = ctypes.POINTER(GroundGrid), ctypes.c_float
+            L.pwpp_viewshed_grid.argtypes = [vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, vp, vp, vp]
+            L.pwpp_rasterize_ground_returns.argtypes = [vp, gp, ci, ci, ci, vp]
+            L.pwpp_viewshed_obstacles.argtypes = [vp, gp, cf, cf, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+            L.pwpp_viewshed_units.argtypes = [ctypes.c_double]
+            L.pwpp_viewshed_units.restype = ctypes.c_int32
         if hasattr(L, "pwpp_costmap_grid"):  # (as above: an older build has no costmap)
             gp, tp, cp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams), ctypes.POINTER(CostmapParams)
             cf, cd, i32 = ctypes.c_float, ctypes.c_double, ctypes.c_int32
@@ -357,6 +365,12 @@ def costmap_curve(cell, inscribed, radius, decay, peak, capacity=COSTMAP_MAX_CUR
     if n < 0:
         raise PwppError("pwpp error %d: %s" % (n, L.pwpp_last_error().decode()))
     return out[:n].copy()
+
+
+def viewshed_units(metres):
+    """A height in metres in the viewshed's units (pwpp_viewshed_units): VIEW_NO_HEIGHT for a NaN, otherwise
+    floor(clamp(metres * 1024, -2^30, 2^30) + 0.5); needs no device."""
+    return int(load().pwpp_viewshed_units(float(metres)))
 
 
 def footprint_covers(foot_params, pose, ix, iy):
@@ -1365,6 +1379,78 @@ class Handle:
         self._check(self._L.pwpp_visibility_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count),
                                                       _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
                                                       _dp(first_ptr), _dp(occupancy_ptr), _dp(count_ptr)))
+
+    def viewshed_grid(self, count, origin, block=None, target=None, seen=None, min_count=1, min_seen=1, max_range=0, want_shadow=True,
+                      want_occupancy=True):
+        """The height-aware line of sight of a (frames, ny, nx) or (ny, nx) int32 count image: visibility_grid's walk, in which an
+        occupied cell hides a cell behind it only where the ray from the eye to that cell passes through it.  block, target, seen:
+        int32 images of count's shape or None -- the height of an occupied cell's top (None or VIEW_NO_HEIGHT: opaque), the height
+        of a cell's ground (None or VIEW_NO_HEIGHT: hidden by any blocker) and its ground returns (seen >= min_seen: free whatever
+        the line says).  origin: (ox, oy, eye) for every frame, or (frames, 3).  Works before any estimate call.  Returns (first,
+        shadow, occupancy) of count's shape: the int32 index of the nearest cell that hides (VIS_NONE, VIS_BEYOND as
+        visibility_grid), the int32 lowest height seen at the cell (VIEW_NO_HEIGHT: no blocker; INT32_MAX: behind an opaque one)
+        and the int8 byte; None for an image that is not wanted.  The rules: include/pwpp.h."""
+        c3, shape = _count_image(count)
+        frames, ny, nx = c3.shape
+        imgs = [None if a is None else np.ascontiguousarray(np.asarray(a, np.int32).reshape(c3.shape)) for a in (block, target, seen)]
+        org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 3))
+        first = np.empty(c3.shape, np.int32)
+        shadow = np.empty(c3.shape, np.int32) if want_shadow else None
+        occupancy = np.empty(c3.shape, np.int8) if want_occupancy else None
+        self._check(self._L.pwpp_viewshed_grid(self._h, nx, ny, frames, MEM_HOST, _hp(c3), int(min_count), _hp(imgs[0]), _hp(imgs[1]), _hp(imgs[2]),
+                                               int(min_seen), _hp(org), len(org), int(max_range), _hp(first), _hp(shadow), _hp(occupancy)))
+        return tuple(None if a is None else a.reshape(shape) for a in (first, shadow, occupancy))
+
+    def viewshed_grid_device(self, nx, ny, frames, count_ptr, origin, min_count, max_range, first_ptr, shadow_ptr=0, occupancy_ptr=0, block_ptr=0,
+                             target_ptr=0, seen_ptr=0, min_seen=1):
+        """viewshed_grid on device memory: addresses of the (frames, ny, nx) int32 images, 4-byte aligned, and of the int8 occupancy
+        image (0: none / not wanted); origin stays a host array, (ox, oy, eye) or (frames, 3).  Enqueued on the handle's stream;
+        complete after synchronize()."""
+        org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 3))
+        self._check(self._L.pwpp_viewshed_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(count_ptr), int(min_count), _dp(block_ptr),
+                                               _dp(target_ptr), _dp(seen_ptr), int(min_seen), _vp(org) if org.size else None, len(org), int(max_range),
+                                               _dp(first_ptr), _dp(shadow_ptr), _dp(occupancy_ptr)))
+
+    def rasterize_ground_returns(self, x0, y0, cell, nx, ny, frame_first=0, frames=None):
+        """The last call's GROUND points on the grid of rasterize_obstacles: (frames, ny, nx) int32 counts of the points the frame's
+        ground list names, by the same cell rule."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        seen = np.empty(self._grid_shape(g, frames), np.int32)
+        self._check(self._L.pwpp_rasterize_ground_returns(self._h, ctypes.byref(g), int(frame_first), frames, MEM_HOST, _hp(seen)))
+        return seen
+
+    def rasterize_ground_returns_device(self, x0, y0, cell, nx, ny, seen_ptr, frame_first=0, frames=None):
+        """rasterize_ground_returns into device memory: the address of the (frames, ny, nx) int32 image.  Enqueued on the handle's
+        stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        self._check(self._L.pwpp_rasterize_ground_returns(self._h, ctypes.byref(g), int(frame_first), frames, MEM_DEVICE, _dp(seen_ptr)))
+
+    def viewshed_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, origin_xyz=(0.0, 0.0, 0.0), min_count=1, min_seen=1, max_range=0, frame_first=0,
+                           frames=None, ground_only=False, want_shadow=True, want_occupancy=True, want_count=False):
+        """rasterize_obstacles, rasterize_ground, rasterize_ground_returns (min_seen > 0) and viewshed_grid in one call, for frames
+        of the last estimate call: target = units(ground), block = units(ground + top), eye = units(z).  origin_xyz: the sensor's
+        position in metres in the model's frame, (x, y, z) for every frame or (frames, 3).  Returns (first, shadow, occupancy) as
+        viewshed_grid does; want_count: then the int32 count image too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = _host(origin_xyz, np.float64, -1, 3)
+        shape = self._grid_shape(g, frames)
+        first = np.empty(shape, np.int32)
+        shadow = np.empty(shape, np.int32) if want_shadow else None
+        occupancy = np.empty(shape, np.int8) if want_occupancy else None
+        count = np.empty(shape, np.int32) if want_count else None
+        self._check(self._L.pwpp_viewshed_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(min_seen), _hp(org), len(org),
+                                                    int(max_range), int(frame_first), frames, MEM_HOST, _hp(first), _hp(shadow), _hp(occupancy), _hp(count)))
+        return (first, shadow, occupancy) + ((count,) if want_count else ())
+
+    def viewshed_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, origin_xyz, min_count, min_seen, max_range, first_ptr, shadow_ptr=0,
+                                  occupancy_ptr=0, count_ptr=0, frame_first=0, frames=None, ground_only=False):
+        """viewshed_obstacles into device memory: addresses as in viewshed_grid_device, count_ptr the int32 count image (0: not
+        wanted); origin_xyz stays a host array.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = _host(origin_xyz, np.float64, -1, 3)
+        self._check(self._L.pwpp_viewshed_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(min_seen),
+                                                    _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
+                                                    _dp(first_ptr), _dp(shadow_ptr), _dp(occupancy_ptr), _dp(count_ptr)))
 
     @staticmethod
     def _fusion_host(pose, map_of_frame, shift):

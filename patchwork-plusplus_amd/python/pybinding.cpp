@@ -333,6 +333,22 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0, py::arg("ground_only") = false)
+        .def("getObstacleViewshed",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int min_count, int min_seen, int max_range,
+                double origin_x, double origin_y, double origin_z, bool ground_only) {
+                 const PatchWorkpp::ObstacleViewshed v =
+                     s.getObstacleViewshed(x0, y0, cell, nx, ny, h_min, h_max, min_count, min_seen, max_range, origin_x, origin_y, origin_z, ground_only);
+                 py::array_t<int32_t> first({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 py::array_t<int32_t> shadow({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 py::array_t<int8_t> occupancy({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 if (!v.first.empty()) std::memcpy(first.mutable_data(), v.first.data(), v.first.size() * sizeof(int32_t));
+                 if (!v.shadow.empty()) std::memcpy(shadow.mutable_data(), v.shadow.data(), v.shadow.size() * sizeof(int32_t));
+                 if (!v.occupancy.empty()) std::memcpy(occupancy.mutable_data(), v.occupancy.data(), v.occupancy.size());
+                 return py::make_tuple(first, shadow, occupancy);
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("min_count") = 1, py::arg("min_seen") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0,
+             py::arg("origin_z") = 0.0, py::arg("ground_only") = false)
         .def("updateObstacleMap",
              [](PatchWorkpp &s, PatchWorkpp::FusedObstacleMap &map, const std::array<double, 6> &pose, double x0, double y0, double cell, int nx, int ny,
                 float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y, int shift_x, int shift_y) {
