@@ -592,6 +592,77 @@ PWPP_API int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float
 PWPP_API int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz /* (m,3) */, const float *hgt /* m */,
                              const int32_t *row /* m */, int64_t m, pwpp_obstacle_box *boxes, int max_boxes);
 
+/* ---- the outline of every cluster: its convex hull and its tightest rectangle (pwpp_hull_obstacles, pwpp_hull_points) --------------
+ * The box of pwpp_box_obstacles stands on the principal axis of the points, which is the wrong axis for the clusters a lidar sees
+ * most: a car seen from a corner is an L whose principal axis is its diagonal, a wall with one return at its end is swung round by
+ * it.  Here every row gets the exact convex hull of its counted points on the 1/1024 m grid of the boxes, and from the hull the
+ * enclosing rectangle of least area, chosen by exact integer comparison -- without point_cluster and the coordinates of a batch
+ * leaving the device.  Integers first, six floats derived once.
+ *   points    Exactly the counted points of pwpp_box_obstacles (one device function decides), the same rule of a row: a point of
+ *             frame f in cell c belongs to row label[f][c] iff 0 <= row < max_hulls.  A point is the integer pair (qx, qy) =
+ *             (llrint(dx * 1024), llrint(dy * 1024)) of the boxes' step 1, 0 <= q <= 2^20 + 1; the extent limit of the boxes applies
+ *             (nx * cell <= 1024, ny * cell <= 1024).  A row's input is the SET of its distinct pairs: duplicates count once for
+ *             the hull and every time for `points`.
+ *   hull      The vertices of the strict convex hull.  cross(a, b, c) = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax) in int64 (|cross| < 2^43,
+ *             exact).  Consecutive vertices a, b, c have cross > 0 (counter-clockwise, y up); no vertex lies on the segment between
+ *             two others.  The list starts at the vertex with the smallest (qy, qx).  One distinct point: 1 vertex.  A collinear set:
+ *             2 vertices, the smallest then the largest under (qy, qx).  n_vertices is the TRUE count; stored = min(n_vertices,
+ *             max_vertices); the first `stored` vertices are written to vertices[f][row][k] = {qx, qy}, entries from `stored` on are
+ *             unspecified.  area2 = the shoelace sum over all n_vertices edges, twice the area in (1/1024 m)^2 -- exact also for
+ *             a truncated list.  qx_min .. qy_max: the bounds of the row's points (= of its vertices).
+ *   rectangle Defined iff 1 <= n_vertices <= max_vertices.  For edge i, from vertex i to vertex i + 1 mod n, let e = (ex, ey) be its
+ *             vector, negated when ex < 0 or (ex == 0 and ey < 0); e = (1, 0) for a row of 1 vertex.  Over all vertices v: p = ex*vx +
+ *             ey*vy, q = ex*vy - ey*vx in int64; W = pmax - pmin, H = qmax - qmin, L2 = ex*ex + ey*ey.  Edge i is better than edge j iff
+ *             W_i*H_i*L2_j < W_j*H_j*L2_i in unsigned 128-bit integers: with diam the diameter of the set, diam^2 <= 2 (2^20 + 1)^2 <
+ *             2^41 + 2^23, W*H <= diam^2 * L2 and L2 <= diam^2, so both sides are at most diam^6 < 2^124.  Ties go to the lower i;
+ *             rect_edge is that i.  Floats as for the boxes, only + - * / sqrt, no FMA, every integer exact in a double or rounded
+ *             to one ONCE: L = sqrt((double)L2); ax = (float)((double)ex / L), ay alike; length = (float)(((double)W / L) / 1024),
+ *             width alike from H; U = (pmin+pmax)*ex - (qmin+qmax)*ey and V = (pmin+pmax)*ey + (qmin+qmax)*ex in 128-bit integers,
+ *             each rounded once to a double u, v; cx = (float)(x0 + (u / (2.0 * (double)L2)) / 1024), cy alike from v and y0.
+ *             length is NOT forced >= width.
+ *   rows      A row no counted point named: every integer 0 except rect_edge = -1, every float the quiet NaN (0x7fc00000).  A
+ *             truncated row (n_vertices > max_vertices): the integers filled, rect_edge = -1, the six floats NaN.
+ *   invariants   Every counted point of a row has cross >= 0 against every hull edge.  Where both are defined, the rectangle is
+ *             no larger than the box of the same row: the exact rational W*H/L2 of the chosen edge is <= the area of the
+ *             rectangle that encloses the row's integer points along the box's float axis (ax, ay), (pmax - pmin)(qmax - qmin) /
+ *             (ax^2 + ay^2) in exact arithmetic -- the least enclosing rectangle has a side on a hull edge.  The floats length *
+ *             width of the two rows differ from those rationals by their own roundings only.  The bytes depend on the input, the
+ *             grid, the band and the label image alone: not on output order, schedule, memory kind or the option "hulls_path".
+ *   when, mem, lifetime, errors   Those of pwpp_box_obstacles.  PWPP_MEM_DEVICE: hulls 8-byte aligned (like pwpp_obstacle_cluster), label and
+ *             vertices 4-byte.  PWPP_E_ARG, named before the device is touched, also for max_hulls < 1, max_vertices outside 1 ..
+ *             1024, frames * max_hulls > 2^24, frames * max_hulls * max_vertices > 2^28.  vertices may be NULL: the rows are the
+ *             same bytes.  In the cluster buffer (allocated on first use, counted by pwpp_get_workspace_bytes, freed by
+ *             pwpp_trim_workspace): 80 bytes of accumulators per row, and the candidate arena -- the points that lie not
+ *             strictly inside the octagon of their row's eight extreme points, 8 bytes each, laid out per row by an exclusive scan
+ *             of the rows' point counts: 8 * frames * (the longest non-ground list of the frame range) bytes.
+ *   hull_points   Host only, no handle, no device: the same rows for a caller's own points, compiled from the same functions as the
+ *             kernels; hulls[max_hulls], vertices[max_hulls][max_vertices][2] or NULL.  Skipped: a row outside [0, max_hulls), a
+ *             point outside the grid (the cell rule of pwpp_box_points), a NaN z (its height over ground is a NaN: never counted).
+ *             m <= 2^22.
+ *   hull_vertex_xy   Host only: out[0] = (double)(x0 + q[0] / 1024.0), out[1] = (double)(y0 + q[1] / 1024.0).
+ * With none of the three called nothing is allocated or launched, and no result, state or timing of any other entry point changes. */
+#define PWPP_HAS_OBSTACLE_HULLS 1
+#define PWPP_HULL_VERTICES_MAX 1024
+typedef struct pwpp_obstacle_hull {     /* 64 bytes, 8-byte aligned */
+    int32_t points;                     /* counted points that named this row, duplicates included; 0: the empty row */
+    int32_t n_vertices;                 /* vertices of the strict hull: the true count */
+    int32_t stored;                     /* min(n_vertices, max_vertices): how many of them the list holds */
+    int32_t rect_edge;                  /* the edge the rectangle stands on; -1: no rectangle (empty or truncated row) */
+    int64_t area2;                      /* twice the hull's area, (1/1024 m)^2 */
+    int32_t qx_min, qx_max, qy_min, qy_max; /* bounds of the points on the 1/1024 m grid */
+    float cx, cy;                       /* centre of the rectangle, metres */
+    float ax, ay;                       /* unit vector of the chosen edge; ax > 0, or ax == 0 and ay > 0 */
+    float length, width;                /* extent along the edge / across it, metres */
+} pwpp_obstacle_hull;
+PWPP_API int pwpp_hull_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max,
+                                 int frame_first, int frames, int mem,
+                                 const int32_t *label /* [frames][ny][nx] */,
+                                 pwpp_obstacle_hull *hulls /* [frames][max_hulls] */, int max_hulls,
+                                 int32_t *vertices /* [frames][max_hulls][max_vertices][2], may be NULL */, int max_vertices);
+PWPP_API int pwpp_hull_points(const pwpp_ground_grid *g, const float *xyz /* (m,3) */, const int32_t *row /* m */, int64_t m,
+                              pwpp_obstacle_hull *hulls, int max_hulls, int32_t *vertices /* may be NULL */, int max_vertices);
+PWPP_API int pwpp_hull_vertex_xy(const pwpp_ground_grid *g, const int32_t *q /* {qx, qy} */, double *out /* {x, y} */);
+
 /* ---- the distance of every cell to the nearest occupied cell (pwpp_distance_grid, pwpp_distance_obstacles) ------------------------
  * What a costmap, a planner and a collision check start from: for every cell of an obstacle grid, occupied or free, how far the
  * nearest occupied cell is and which one it is -- an exact Euclidean distance transform on the device, each frame on its own,
@@ -1786,6 +1857,11 @@ PWPP_API int pwpp_pipe_destroy(pwpp_pipe *pipe);
  *                         two by tools/obstacle_boxes_cost.py; "1": every counted lane issues its atomics on its row (the yardstick);
  *                         "2": the lanes of a wave that name the same row are summed first, one set of atomics per distinct row.
  *                         The results are identical bytes.
+ *   "hulls_path"          how a row's hull and rectangle are computed from its candidates (pwpp_hull_obstacles): "1": a lane per row,
+ *                         serial gift wrapping, then every edge's rectangle in turn (the yardstick); "2": a wave per row -- a march
+ *                         step is one strided sweep by 64 lanes and a butterfly under the march's total order, the hull lies in
+ *                         LDS, the edges are dealt to the lanes; "0" (default): what tools/obstacle_hulls_cost.py decided.  The
+ *                         same bytes for every value.
  *   "distance_path"       how the column pass of the obstacle distances runs (pwpp_distance_grid, pwpp_distance_obstacles): "0"
  *                         (default) the strip's rows in LDS where they fit, outward from the cell's own row with the exact early
  *                         exit; "1": every row from global memory, no LDS, no early exit (the yardstick of

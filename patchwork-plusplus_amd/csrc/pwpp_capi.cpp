@@ -23,6 +23,7 @@
 
 #include "../../include/pwpp.h"
 #include "pwpp_boxes.h"
+#include "pwpp_hull.h"
 #include "pwpp_dev.h"
 #include "pwpp_distance.h"
 #include "pwpp_elevation.h"
@@ -271,6 +272,7 @@ struct pwpp_handle {
     int match_path = 0;             // option "match_path": 0 = what tools/scan_match_cost.py decided; 1 = every map read from global memory (yardstick); 2 = the map's rectangle staged in LDS where it fits
     std::vector<std::vector<uint32_t>> uploads;  // the tables the last call that uploaded any built for its kernels: the sources of their copies (Staging::add_upload)
     int boxes_path = 0;             // option "boxes_path": 0 = kBoxesDefaultCombine decides; 1 = every lane its own atomics (yardstick); 2 = equal rows of a wave combined
+    int hulls_path = 0;             // option "hulls_path": 0 = pwpp_hull_path_of decides; 1 = a lane per row, serial (yardstick); 2 = a wave per row
     bool ground_rows_valid = false;   // d_ground_rows holds the table of the last call (cleared by every estimate call and pwpp_trim_workspace)
     bool ground_query_queued = false;  // a PWPP_MEM_DEVICE query was enqueued on the main stream and nothing has waited for it yet
     DevBuf<uint32_t> d_bins{bufs, kPerBatch};  // 4 slabs of frames*(B+2): bin_count, bin_off, dst_a, dst_b
@@ -1293,6 +1295,7 @@ constexpr PathOption kPathOptions[] = {
     {"match_path", &pwpp_handle::match_path, 2},
     {"evidence_path", &pwpp_handle::evidence_path, 2},
     {"boxes_path", &pwpp_handle::boxes_path, 2},
+    {"hulls_path", &pwpp_handle::hulls_path, 2},
 };
 const PathOption *path_option(const std::string &name) {
     for (const PathOption &o : kPathOptions)
@@ -4445,6 +4448,110 @@ int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz, const float *hg
             }
         }
     }
+    return PWPP_OK;
+}
+
+// ---- obstacle hulls: the counted points of every label as a convex hull and its tightest rectangle ---------------------------------
+namespace {
+static_assert(sizeof(pwpp_obstacle_hull) == 64 && alignof(pwpp_obstacle_hull) == 8 && offsetof(pwpp_obstacle_hull, area2) == 16 &&
+                  offsetof(pwpp_obstacle_hull, qx_min) == 24 && offsetof(pwpp_obstacle_hull, cx) == 40,
+              "pwpp_obstacle_hull is the sixteen words of pwpp_hull_row");
+static_assert(sizeof(pwpp_obstacle_hull) / 4 == PWPP_HULL_ROW_WORDS && PWPP_HULL_VERTICES_MAX == PWPP_HULL_MAX_VERTICES, "the kernels' row and vertex limit");
+
+int hull_table_args(int64_t frames, int max_hulls, int max_vertices) {
+    if (max_hulls < 1) return fail(PWPP_E_ARG, "max_hulls %d: at least 1 expected", max_hulls);
+    if (max_vertices < 1 || max_vertices > PWPP_HULL_MAX_VERTICES) return fail(PWPP_E_ARG, "max_vertices %d: 1 .. %d expected", max_vertices, PWPP_HULL_MAX_VERTICES);
+    if (frames > 0 && frames * (int64_t)max_hulls > ((int64_t)1 << 24)) return fail(PWPP_E_ARG, "%lld frames x %d hulls exceed 2^24 rows", (long long)frames, max_hulls);
+    if (frames > 0 && frames * (int64_t)max_hulls * (int64_t)max_vertices > ((int64_t)1 << 28))
+        return fail(PWPP_E_ARG, "%lld frames x %d hulls x %d vertices exceed 2^28", (long long)frames, max_hulls, max_vertices);
+    return PWPP_OK;
+}
+}  // namespace
+
+// Init, first pass, offsets, second pass, rows: five launches on the handle's stream.  The accumulators, the candidate arena, the
+// vertex lists nobody asked for (path 1 reads them back) and for PWPP_MEM_HOST the caller's arrays live in the cluster buffer.
+int pwpp_hull_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem, const int32_t *label,
+                        pwpp_obstacle_hull *hulls, int max_hulls, int32_t *vertices, int max_vertices) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label || !hulls) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!label ? "label image" : "hull table"));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc) return rc;
+    if ((rc = hull_table_args(frames, max_hulls, max_vertices))) return rc;
+    if ((rc = box_extent_args(g))) return rc;
+    if ((rc = mem_args(mem, "the obstacle hulls take"))) return rc;
+    if ((rc = alignment_args(mem, {{hulls, 7u, "hull table"}}))) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
+    const int path = pwpp_hull_path_of(h->hulls_path, (int64_t)frames * (int64_t)max_hulls);
+    const size_t rows = (size_t)frames * (size_t)max_hulls, lists = rows * (size_t)max_vertices * 2;
+    const size_t arena = (size_t)frames * (size_t)scan.max_nonground * 2;  // (8 bytes an entry: PWPP_HULL_ARENA_BYTES of the header)
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    const int s_acc = st.add(rows * PWPP_HULL_ACC_WORDS, nullptr, Staging::kKept), s_arena = st.add(arena, nullptr, Staging::kKept);
+    const int s_label = st.add(cells, label, Staging::kIn), s_rows = st.add(rows * PWPP_HULL_ROW_WORDS, hulls, Staging::kOut);
+    const int s_lists = vertices ? st.add(lists, vertices, Staging::kOut) : st.add(path == 1 ? lists : 0, nullptr, Staging::kKept);
+    if ((rc = st.begin())) return rc;
+    const PwppHullRows table = {st.dev<const int32_t>(s_label), max_hulls, st.dev<uint32_t>(s_acc), st.dev<unsigned long long>(s_arena), (int64_t)scan.max_nonground};
+    int32_t *d_lists = (vertices || path == 1) ? st.dev<int32_t>(s_lists) : nullptr;
+    int lrc = pwpp_launch_hull_rows(0, path, frames, &table, g->x0, g->y0, st.dev<void>(s_rows), d_lists, max_vertices, h->stream);
+    for (int pass = 0; pass < 2 && lrc == 0; ++pass) {
+        lrc = pwpp_launch_hull_pass(pass, &scan, &table, h->stream);
+        if (lrc == 0) lrc = pwpp_launch_hull_rows(1 + pass, path, frames, &table, g->x0, g->y0, st.dev<void>(s_rows), d_lists, max_vertices, h->stream);
+    }
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+// The same rows on the host, from the functions the kernels compile (pwpp_hull.h): every point of a row is a candidate.
+int pwpp_hull_points(const pwpp_ground_grid *g, const float *xyz, const int32_t *row, int64_t m, pwpp_obstacle_hull *hulls, int max_hulls, int32_t *vertices,
+                     int max_vertices) {
+    if (!g || !hulls) return fail(PWPP_E_ARG, "null %s", g ? "hull table" : "grid");
+    int rc = hull_table_args(1, max_hulls, max_vertices);
+    if (rc) return rc;
+    if (m < 0 || m > ((int64_t)1 << 22)) return fail(PWPP_E_ARG, "%lld points (0..2^22 supported)", (long long)m);
+    if (m > 0 && (!xyz || !row)) return fail(PWPP_E_ARG, "null %s", !xyz ? "positions" : "rows");
+    if ((rc = grid_geometry_args(g)) || (rc = box_extent_args(g))) return rc;
+    const auto inside = [](double d, double cell, int n) {  // (the grid_cell rule of the kernels, as in pwpp_box_points)
+        const double u = d / cell;
+        return u >= 0.0 && u < (double)n;
+    };
+    try {
+        std::vector<int64_t> first((size_t)max_hulls + 1, 0);
+        std::vector<int32_t> of;  // the row of every counted point, -1: skipped
+        of.assign((size_t)m, -1);
+        std::vector<pwpp_hull_pt> pt((size_t)m, 0);
+        for (int64_t i = 0; i < m; ++i) {
+            const int32_t r = row[i];
+            if (r < 0 || r >= max_hulls || xyz[3 * i + 2] != xyz[3 * i + 2]) continue;
+            const double dx = (double)xyz[3 * i] - g->x0, dy = (double)xyz[3 * i + 1] - g->y0;
+            if (!inside(dx, g->cell, g->nx) || !inside(dy, g->cell, g->ny)) continue;
+            of[(size_t)i] = r, pt[(size_t)i] = pwpp_hull_pack(pwpp_box_quantise(dx), pwpp_box_quantise(dy));
+            first[(size_t)r + 1] += 1;
+        }
+        for (int r = 0; r < max_hulls; ++r) first[(size_t)r + 1] += first[(size_t)r];
+        std::vector<pwpp_hull_pt> cand((size_t)first[(size_t)max_hulls], 0);
+        std::vector<int64_t> at(first.begin(), first.end() - 1);
+        for (int64_t i = 0; i < m; ++i)
+            if (of[(size_t)i] >= 0) cand[(size_t)at[(size_t)of[(size_t)i]]++] = pt[(size_t)i];
+        std::vector<int32_t> own(vertices ? 0 : (size_t)max_vertices * 2, 0);
+        for (int r = 0; r < max_hulls; ++r) {
+            const int64_t n = first[(size_t)r + 1] - first[(size_t)r];
+            uint32_t out[PWPP_HULL_ROW_WORDS];
+            pwpp_hull_row_serial(cand.data() + first[(size_t)r], n, (int32_t)n, max_vertices, vertices ? vertices + (size_t)r * (size_t)max_vertices * 2 : own.data(), g->x0,
+                                 g->y0, out);
+            std::memcpy(&hulls[r], out, sizeof(out));
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(PWPP_E_NOMEM, "no host memory for %lld points and %d rows", (long long)m, max_hulls);
+    }
+    return PWPP_OK;
+}
+
+int pwpp_hull_vertex_xy(const pwpp_ground_grid *g, const int32_t *q, double *out) {
+    if (!g || !q || !out) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!q ? "vertex" : "output"));
+    out[0] = (double)(g->x0 + (double)q[0] / 1024.0);
+    out[1] = (double)(g->y0 + (double)q[1] / 1024.0);
     return PWPP_OK;
 }
 

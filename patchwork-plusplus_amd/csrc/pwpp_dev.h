@@ -277,7 +277,7 @@ struct PwppGroundGrid {  // = pwpp_ground_grid
 };
 
 // "The non-ground lists of frames [frame_first, frame_first + frames) of the LAST call over a grid": what every kernel that walks
-// those lists reads (k_obstacle_raster, k_point_cluster, k_box_moments, k_box_extents), by value in the kernarg segment.  Filled in
+// those lists reads (k_obstacle_raster, k_point_cluster, k_box_moments, k_box_extents, k_hull_extremes, k_hull_candidates), by value in the kernarg segment.  Filled in
 // one place on the host (obstacle_scan, pwpp_capi.cpp).
 struct PwppObstacleScan {
     PwppGroundView Q;
@@ -296,6 +296,15 @@ struct PwppBoxRows {
     int32_t max_boxes;     // rows per frame
     uint32_t *acc;         // [frames][max_boxes][PWPP_BOX_ACC_WORDS] the accumulators (pwpp_boxes.h), 8-byte aligned
     const float *boxes;    // [frames][max_boxes][16] the rows themselves: the second pass reads the axes k_box_solve left in them
+};
+
+// The rows of pwpp_hull_obstacles as the two point passes see them (pwpp_hull.h has the accumulators).
+struct PwppHullRows {
+    const int32_t *label;       // [frames][ny][nx] the row of every cell (-1: none)
+    int32_t max_hulls;          // rows per frame
+    uint32_t *acc;              // [frames][max_hulls][PWPP_HULL_ACC_WORDS] the accumulators, 8-byte aligned
+    unsigned long long *arena;  // [frames][arena_stride] the candidates, packed points; a row's lie from its word PWPP_HULL_ACC_FIRST on
+    int64_t arena_stride;       // entries per frame: the longest non-ground list of the range
 };
 
 // ---- the launchers: every extern "C" function one translation unit of the library calls in another, declared ONCE ----------------
@@ -317,6 +326,10 @@ int pwpp_launch_obstacle_raster(const PwppObstacleScan *scan, int32_t *count, fl
 int pwpp_launch_ground_returns(const PwppObstacleScan *scan, int max_ground, int32_t *seen, hipStream_t stream);
 int pwpp_launch_point_cluster(const PwppObstacleScan *scan, const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
 int pwpp_launch_box_pass(int pass, int combine, const PwppObstacleScan *scan, const PwppBoxRows *rows, hipStream_t stream);
+int pwpp_launch_hull_pass(int pass, const PwppObstacleScan *scan, const PwppHullRows *rows, hipStream_t stream);
+// pwpp_hull.hip (step 0: the accumulators' initial values; 1: the rows' first candidates, between the passes; 2: the rows, path 1 or 2)
+int pwpp_launch_hull_rows(int step, int path, int frames, const PwppHullRows *rows, double x0, double y0, void *hulls, int32_t *vertices, int max_vertices,
+                          hipStream_t stream);
 // pwpp_fit.hip
 int pwpp_launch_fit(const PwppBatch *batch, hipStream_t stream, hipEvent_t *ev);
 int pwpp_launch_fixup(const PwppBatch *batch, hipStream_t stream);

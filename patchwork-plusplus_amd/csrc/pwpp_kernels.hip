@@ -23,8 +23,10 @@
 // cloud points (pwpp_query_ground, pwpp_rasterize_ground); k_obstacle_fill / k_obstacle_raster / k_obstacle_top count the non-ground
 // points per cell of the same grid (pwpp_rasterize_obstacles), k_point_cluster gives every counted point the cluster of its cell
 // (pwpp_label_obstacles; the image kernels of the clusters are pwpp_clusters.hip), k_box_moments / k_box_extents reduce the counted
-// points of every label to an oriented box (pwpp_box_obstacles; pwpp_boxes.h has the arithmetic).  The four kernels that walk the
-// non-ground lists take one PwppObstacleScan (pwpp_dev.h).  They write nothing the pipeline reads.
+// points of every label to an oriented box (pwpp_box_obstacles; pwpp_boxes.h has the arithmetic), k_hull_extremes / k_hull_candidates
+// find every label's extreme points and the candidates of its convex hull (pwpp_hull_obstacles; pwpp_hull.h has the arithmetic, the
+// row kernels are pwpp_hull.hip).  The kernels that walk the non-ground lists take one PwppObstacleScan (pwpp_dev.h).  They write
+// nothing the pipeline reads.
 //
 // All reference citations are /root/reference/cpp/patchworkpp/src/patchworkpp.cpp unless a
 // header is named.  This is integer + scalar-float work bound by HBM traffic (binning, emit) and by
@@ -45,6 +47,7 @@
 
 #include "pwpp_common.hpp"
 #include "pwpp_boxes.h"
+#include "pwpp_hull.h"
 #include "pwpp_unionfind.h"
 
 namespace {
@@ -3308,6 +3311,106 @@ __global__ __launch_bounds__(kObBlock) void k_box_extents(PwppObstacleScan S, Pw
     }
 }
 
+// ---- obstacle hulls (pwpp_hull_obstacles): two more passes over the same scan, by the same rule of a row (box_point) ---------------
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// the lane's entry as a point of a hull row: row and packed point
+__device__ __forceinline__ bool hull_point(const PwppObstacleScan &S, const float4 *s_zt, const ScanEntry &t, const PwppHullRows &R, int &row, long long &qx, long long &qy) {
+    const PwppBoxRows B = {R.label, R.max_hulls, nullptr, nullptr};
+    double dx = 0.0, dy = 0.0;
+    float hgt, z;
+    if (!box_point(S, s_zt, t, B, row, dx, dy, hgt, z)) return false;
+    qx = pwpp_box_quantise(dx), qy = pwpp_box_quantise(dy);  // (0 .. 2^20 + 1)
+    return true;
+}
+
+// First pass: per row the count of its points and the 64-bit minima and maxima of their four keys (pwpp_hull.h): the eight extreme
+// points.  The lanes of a wave that name one row are combined first, as in k_box_moments<true>; minima, maxima and a sum: the same bytes.
+__global__ __launch_bounds__(kObBlock) void k_hull_extremes(PwppObstacleScan S, PwppHullRows R) {
+    __shared__ float4 s_zt[8];
+    ScanEntry t;
+    if (!scan_entry(S, s_zt, t)) return;
+    int row = -1;
+    long long qx = 0, qy = 0;
+    const bool counted = hull_point(S, s_zt, t, R, row, qx, qy);
+    uint32_t *acc = R.acc + ((size_t)t.fr * (size_t)R.max_hulls + (size_t)(counted ? row : 0)) * PWPP_HULL_ACC_WORDS;
+    unsigned long long k[4] = {0ull, 0ull, 0ull, 0ull};
+    if (counted) pwpp_hull_keys(qx, qy, k);
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(counted);
+    for (int round = 0; round < 64 && todo; ++round) {
+        bool mine;
+        const int leader = box_next_row(todo, counted, row, mine);
+        const uint32_t n = (uint32_t)__popcll(__ballot(mine));
+        unsigned long long lo[4], hi[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            lo[j] = wave_min64(mine ? k[j] : PWPP_HULL_KEY_NO_MIN);
+            hi[j] = wave_max64(mine ? k[j] : PWPP_HULL_KEY_NO_MAX);
+        }
+        if (lane == leader) {  // (a counted lane: `acc` is its row)
+            unsigned long long *keys = reinterpret_cast<unsigned long long *>(acc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                atomicMin(keys + 2 * j, lo[j]);
+                atomicMax(keys + 2 * j + 1, hi[j]);
+            }
+            atomicAdd(acc + PWPP_HULL_ACC_POINTS, n);
+        }
+    }
+}
+
+// Second pass: the rows' keys are final and k_hull_offsets has laid the rows of a frame out in its part of the arena, `points`
+// entries each.  A point strictly inside its row's octagon is no vertex and is dropped; every other one is written as a candidate.
+// The lanes of a wave that name one row take their places with one atomic; the order inside a row is free.
+__global__ __launch_bounds__(kObBlock) void k_hull_candidates(PwppObstacleScan S, PwppHullRows R) {
+    __shared__ float4 s_zt[8];
+    ScanEntry t;
+    if (!scan_entry(S, s_zt, t)) return;
+    int row = -1;
+    long long qx = 0, qy = 0;
+    const bool counted = hull_point(S, s_zt, t, R, row, qx, qy);
+    uint32_t *acc = R.acc + ((size_t)t.fr * (size_t)R.max_hulls + (size_t)(counted ? row : 0)) * PWPP_HULL_ACC_WORDS;
+    const pwpp_hull_pt p = pwpp_hull_pack(qx, qy);
+    bool keep = false;
+    if (counted) {
+        unsigned long long keys[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) keys[j] = reinterpret_cast<const unsigned long long *>(acc)[j];
+        keep = !pwpp_hull_inside_octagon(keys, p);
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(keep);
+    for (int round = 0; round < 64 && todo; ++round) {
+        bool mine;
+        const int leader = box_next_row(todo, keep, row, mine);
+        const unsigned long long who = __ballot(mine);
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(acc + PWPP_HULL_ACC_CANDS, (uint32_t)__popcll(who));
+        base = __shfl(base, leader, 64);
+        if (mine) {
+            const uint32_t at = base + (uint32_t)__popcll(who & ((1ull << lane) - 1ull));
+            // (at < points of the row: every candidate is one of them; first + points <= the frame's counted points <= arena_stride)
+            if (at < acc[PWPP_HULL_ACC_POINTS]) R.arena[(size_t)t.fr * (size_t)R.arena_stride + (size_t)acc[PWPP_HULL_ACC_FIRST] + at] = p;
+        }
+    }
+}
+
 // the keys of `top` as floats, in place: empty = the quiet NaN.  Quads as in k_obstacle_fill.
 __global__ __launch_bounds__(kObBlock) void k_obstacle_top(int64_t cells, uint32_t *top) {
     const int64_t t = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
@@ -3439,6 +3542,18 @@ extern "C" int pwpp_launch_box_pass(int pass, int combine, const PwppObstacleSca
         hipLaunchKernelGGL(combine ? k_box_moments<true> : k_box_moments<false>, g, dim3(kObBlock), 0, stream, *scan, *rows);
     else
         hipLaunchKernelGGL(combine ? k_box_extents<true> : k_box_extents<false>, g, dim3(kObBlock), 0, stream, *scan, *rows);
+    return (int)hipGetLastError();
+}
+
+// The two point passes of pwpp_hull_obstacles.  pass 0: the rows' counts and extreme points into rows->acc (initialised by
+// pwpp_launch_hull_rows, step 0); pass 1: the candidates into rows->arena, behind step 1 of pwpp_launch_hull_rows.
+extern "C" int pwpp_launch_hull_pass(int pass, const PwppObstacleScan *scan, const PwppHullRows *rows, hipStream_t stream) {
+    dim3 g;
+    if (!scan_grid(*scan, g)) return (int)hipGetLastError();
+    if (pass == 0)
+        hipLaunchKernelGGL(k_hull_extremes, g, dim3(kObBlock), 0, stream, *scan, *rows);
+    else
+        hipLaunchKernelGGL(k_hull_candidates, g, dim3(kObBlock), 0, stream, *scan, *rows);
     return (int)hipGetLastError();
 }
 

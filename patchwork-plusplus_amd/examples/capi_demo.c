@@ -100,6 +100,23 @@ int main(int argc, char **argv) {
             printf("footprint along %s: first hit at step %d, %d free steps, the last one %d\n", k ? "column 1" : "row 2", (int)rows[k].first_hit, (int)rows[k].free_steps,
                    (int)rows[k].last);
     }
+
+    /* An outline (pwpp_hull_points, host only, no reference counterpart; pwpp_hull_obstacles does the same for every cluster of a
+     * frame on the device): a car seen from a corner is an L of two walls -- its hull is a triangle and the tightest rectangle
+     * stands on a wall, where the box of the principal axis would stand on the diagonal. */
+    {
+        const pwpp_ground_grid grid = {0.0, 0.0, 0.5, 32, 32, 0, 0};
+        float wall[9][3];
+        int32_t row[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, vertices[8][2];
+        pwpp_obstacle_hull hull;
+        double xy[2];
+        int k;
+        for (k = 0; k < 9; ++k) wall[k][0] = k < 5 ? 2.0f + (float)k : 2.0f, wall[k][1] = k < 5 ? 3.0f : 3.0f + 0.5f * (float)(k - 4), wall[k][2] = 0.5f;
+        if (pwpp_hull_points(&grid, &wall[0][0], row, 9, &hull, 1, &vertices[0][0], 8) != PWPP_OK) return fail("pwpp_hull_points");
+        if (pwpp_hull_vertex_xy(&grid, vertices[0], xy) != PWPP_OK) return fail("pwpp_hull_vertex_xy");
+        printf("outline of an L: %d points, %d vertices from (%.1f, %.1f), rectangle %.1f x %.1f m on edge %d, heading (%.0f, %.0f)\n", (int)hull.points,
+               (int)hull.n_vertices, xy[0], xy[1], (double)hull.length, (double)hull.width, (int)hull.rect_edge, (double)hull.ax, (double)hull.ay);
+    }
     pwpp_destroy(h);
 
     /* A tilted sensor (pwpp_set_input_transforms, no reference counterpart): the same frame as a LiDAR pitched by 5 degrees and

@@ -792,6 +792,38 @@ public:
         b.clusters = std::move(c.clusters);
         return b;
     }
+    // ... and every cluster's outline (pwpp_hull_obstacles on the labels above): the convex hull of its points on the grid's 1/1024 m
+    // lattice and the enclosing rectangle of least area -- centre, unit vector of the side it stands on, length and width in metres.
+    // hulls[r] belongs to clusters[r]; vertices holds max_vertices {qx, qy} pairs per row, the first hulls[r].stored written
+    // (vertexXY gives one in metres).  A hull of more than max_vertices vertices has its true count, its area and no rectangle.
+    struct ObstacleHulls {
+        std::vector<int32_t> label;                   // ny x nx, row-major
+        std::vector<pwpp_obstacle_cluster> clusters;  // one row per cluster
+        std::vector<pwpp_obstacle_hull> hulls;        // one row per cluster
+        std::vector<int32_t> vertices;                // count x max_vertices x 2
+        int count = 0, max_vertices = 0;
+        double x0 = 0.0, y0 = 0.0;
+        void vertexXY(int row, int k, double &x, double &y) const {
+            const int32_t *q = &vertices[((size_t)row * (size_t)max_vertices + (size_t)k) * 2];
+            x = (double)(x0 + (double)q[0] / 1024.0), y = (double)(y0 + (double)q[1] / 1024.0);
+        }
+    };
+    ObstacleHulls getObstacleHulls(double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int max_vertices = 32, int min_count = 1,
+                                   int connectivity = 8, bool ground_only = false) {
+        ObstacleClusters c = getObstacleClusters(x0, y0, cell, nx, ny, h_min, h_max, min_count, connectivity, ground_only);
+        ObstacleHulls o;
+        o.count = c.count, o.max_vertices = max_vertices, o.x0 = x0, o.y0 = y0;
+        if (c.count > 0) {
+            const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+            o.hulls.resize((size_t)c.count);
+            o.vertices.assign((size_t)c.count * (size_t)(max_vertices > 0 ? max_vertices : 0) * 2, 0);
+            check(pwpp_hull_obstacles(h_, &g, h_min, h_max, 0, 1, PWPP_MEM_HOST, c.label.data(), o.hulls.data(), c.count, o.vertices.empty() ? nullptr : o.vertices.data(),
+                                      max_vertices));
+        }
+        o.label = std::move(c.label);
+        o.clusters = std::move(c.clusters);
+        return o;
+    }
     // ... and which cluster is which cluster of the call before (pwpp_track_obstacles): the labelling as getObstacleClusters gives it,
     // associated with the label image this object kept from its previous call on a grid of the same sides, under the pose {a, b, tx,
     // c, d, ty} that says where a position of the previous frame lies in this one (the identity: null).  ids[r] is the persistent

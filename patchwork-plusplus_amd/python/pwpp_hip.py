@@ -82,6 +82,10 @@ class ObstacleBox(ctypes.Structure):  # pwpp_obstacle_box (64 bytes)
 
 
 OBSTACLE_BOX_DTYPE = np.dtype([("points", "<i4"), ("pad_", "<i4")] + [(n, "<f4") for n in _BOX_FLOATS])
+OBSTACLE_HULL_DTYPE = np.dtype([("points", "<i4"), ("n_vertices", "<i4"), ("stored", "<i4"), ("rect_edge", "<i4"), ("area2", "<i8"),  # pwpp_obstacle_hull (64 bytes)
+                                ("qx_min", "<i4"), ("qx_max", "<i4"), ("qy_min", "<i4"), ("qy_max", "<i4")] +
+                               [(n, "<f4") for n in ("cx", "cy", "ax", "ay", "length", "width")])
+HULL_VERTICES_MAX = 1024  # PWPP_HULL_VERTICES_MAX
 GROUND_SAMPLE_DTYPE = np.dtype([("patch", "<i4"), ("decision", "<i4"), ("ground_z", "<f4"), ("distance", "<f4")])
 GRID_GROUND_ONLY = 1
 DIST_BEYOND = 0x7fffffff  # PWPP_DIST_BEYOND: dist2 where no occupied cell is in reach (nearest -1, metres +inf)
@@ -269,6 +273,10 @@ def load():
         if hasattr(L, "pwpp_box_obstacles"):  # (as above: an older build has no obstacle boxes)
             L.pwpp_box_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, ci]
             L.pwpp_box_points.argtypes = [ctypes.POINTER(GroundGrid), vp, vp, vp, ctypes.c_int64, vp, ci]
+        if hasattr(L, "pwpp_hull_obstacles"):  # (as above: an older build has no obstacle hulls)
+            L.pwpp_hull_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, ci, vp, ci]
+            L.pwpp_hull_points.argtypes = [ctypes.POINTER(GroundGrid), vp, vp, ctypes.c_int64, vp, ci, vp, ci]
+            L.pwpp_hull_vertex_xy.argtypes = [ctypes.POINTER(GroundGrid), vp, vp]
         if hasattr(L, "pwpp_distance_grid"):  # (as above: an older build has no obstacle distances)
             L.pwpp_distance_grid.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ctypes.c_double, vp, vp, vp]
             L.pwpp_distance_obstacles.argtypes = [vp, ctypes.POINTER(GroundGrid), ctypes.c_float, ctypes.c_float, ci, ci, ci, ci, ci, vp, vp, vp, vp]
@@ -551,6 +559,41 @@ def box_points(x0, y0, cell, nx, ny, xyz, hgt, row, max_boxes):
     if L.pwpp_box_points(ctypes.byref(g), ptr(xyz), ptr(hgt), ptr(row), len(xyz), ptr(boxes), int(max_boxes)) < 0:
         raise PwppError(L.pwpp_last_error().decode())
     return boxes
+
+
+def hull_points(x0, y0, cell, nx, ny, xyz, row, max_hulls, max_vertices, with_vertices=True):
+    """pwpp_hull_points: the (max_hulls,) rows (OBSTACLE_HULL_DTYPE) of pwpp_hull_obstacles' arithmetic for a caller's own points, and
+    the (max_hulls, max_vertices, 2) int32 vertex lists (None without with_vertices: the library is given no list) -- xyz (m, 3)
+    float32, row (m,) int32.  Skipped: a row outside [0, max_hulls), a NaN z, a point outside the grid.  Host only; no GPU needed."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("xyz: an (m, 3) array expected")
+    row = np.ascontiguousarray(row, np.int32).reshape(-1)
+    if len(row) != len(xyz):
+        raise ValueError("row: one value per point expected")
+    g = GroundGrid(float(x0), float(y0), float(cell), int(nx), int(ny), 0, 0)
+    hulls = np.zeros(max(int(max_hulls), 0), OBSTACLE_HULL_DTYPE)
+    lists = np.zeros((max(int(max_hulls), 0), min(max(int(max_vertices), 0), HULL_VERTICES_MAX), 2), np.int32) if with_vertices else None
+    L = load()
+    ptr = lambda a: _vp(a) if a is not None and a.size else None
+    if L.pwpp_hull_points(ctypes.byref(g), ptr(xyz), ptr(row), len(xyz), ptr(hulls), int(max_hulls), ptr(lists), int(max_vertices)) < 0:
+        raise PwppError(L.pwpp_last_error().decode())
+    return hulls, lists
+
+
+def hull_vertex_xy(x0, y0, cell, nx, ny, q):
+    """pwpp_hull_vertex_xy: the (..., 2) float64 metres of (..., 2) int32 hull vertices on the grid's 1/1024 m lattice.  Host only."""
+    q = np.ascontiguousarray(q, np.int32)
+    if q.shape[-1:] != (2,):
+        raise ValueError("q: (..., 2) vertices expected")
+    g = GroundGrid(float(x0), float(y0), float(cell), int(nx), int(ny), 0, 0)
+    flat, out = q.reshape(-1, 2), np.zeros((q.size // 2, 2), np.float64)
+    L = load()
+    for k in range(len(flat)):
+        pair = np.ascontiguousarray(flat[k])
+        if L.pwpp_hull_vertex_xy(ctypes.byref(g), _vp(pair), _vp(out[k:k + 1])) < 0:
+            raise PwppError(L.pwpp_last_error().decode())
+    return out.reshape(q.shape)
 
 
 class Handle:
@@ -1951,6 +1994,31 @@ class Handle:
         g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
         self._check(self._L.pwpp_box_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
                                                _dp(label_ptr), _dp(boxes_ptr), int(max_boxes)))
+
+    def hull_obstacles(self, x0, y0, cell, nx, ny, h_min, h_max, label, max_hulls, max_vertices, frame_first=0, frames=None, ground_only=False, with_vertices=True):
+        """The counted points of every label of a (frames, ny, nx) or (ny, nx) int32 label image on the obstacle grid as convex hulls
+        with their least enclosing rectangles, for frames of the last estimate call: the (frames, max_hulls) structured table
+        (OBSTACLE_HULL_DTYPE) and the (frames, max_hulls, max_vertices, 2) int32 vertex lists, of which a row's first `stored` are
+        written (None without with_vertices: the library is given no list).  Rows as in box_obstacles (include/pwpp.h has the arithmetic)."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        label = np.ascontiguousarray(label, np.int32)
+        if label.size != max(frames, 0) * int(nx) * int(ny):
+            raise ValueError("label: %d frames of %d x %d cells expected" % (frames, ny, nx))
+        hulls = np.zeros((max(frames, 0), max(int(max_hulls), 0)), OBSTACLE_HULL_DTYPE)
+        lists = np.zeros(hulls.shape + (min(max(int(max_vertices), 0), HULL_VERTICES_MAX), 2), np.int32) if with_vertices else None
+        self._check(self._L.pwpp_hull_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_HOST,
+                                                _vp(label) if label.size else None, _vp(hulls) if hulls.size else None, int(max_hulls),
+                                                _vp(lists) if lists is not None and lists.size else None, int(max_vertices)))
+        return hulls, lists
+
+    def hull_obstacles_device(self, x0, y0, cell, nx, ny, h_min, h_max, label_ptr, hulls_ptr, max_hulls, vertices_ptr, max_vertices, frame_first=0, frames=None,
+                              ground_only=False):
+        """hull_obstacles on device memory: addresses of the (frames, ny, nx) int32 label image (4-byte aligned), of the (frames,
+        max_hulls) table of 64-byte rows (8-byte aligned) and of the vertex lists (4-byte aligned; 0 or None: no lists).  Enqueued on
+        the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        self._check(self._L.pwpp_hull_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(frame_first), frames, MEM_DEVICE,
+                                                _dp(label_ptr), _dp(hulls_ptr), int(max_hulls), _dp(vertices_ptr) if vertices_ptr else None, int(max_vertices)))
 
     def frame_base(self):
         """(frames + 1,) int64: where every frame starts in the batch-wide arrays (indices, labels)."""

@@ -207,6 +207,7 @@ PYBIND11_MODULE(pypatchworkpp, m) {
     PYBIND11_NUMPY_DTYPE(pwpp_cluster_evidence, sum, cells, landed, occupied, free, unknown, verdict);
     PYBIND11_NUMPY_DTYPE(pwpp_obstacle_box, points, pad_, mean_x, mean_y, cx, cy, ax, ay, length, width, sigma_long, sigma_short, h_min, h_max, z_min,
                          z_max);
+    PYBIND11_NUMPY_DTYPE(pwpp_obstacle_hull, points, n_vertices, stored, rect_edge, area2, qx_min, qx_max, qy_min, qy_max, cx, cy, ax, ay, length, width);
 
     py::class_<PatchWorkpp::FusedObstacleMap>(m, "FusedObstacleMap")  // the caller's persistent map of updateObstacleMap
         .def(py::init<>())
@@ -487,6 +488,22 @@ PYBIND11_MODULE(pypatchworkpp, m) {
                  return py::make_tuple(label, table, boxes, b.count);
              },
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
+             py::arg("min_count") = 1, py::arg("connectivity") = 8, py::arg("ground_only") = false)
+        .def("getObstacleHulls",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, int max_vertices, int min_count, int connectivity,
+                bool ground_only) {
+                 const PatchWorkpp::ObstacleHulls o = s.getObstacleHulls(x0, y0, cell, nx, ny, h_min, h_max, max_vertices, min_count, connectivity, ground_only);
+                 py::array_t<int32_t> label({(py::ssize_t)(ny > 0 ? ny : 0), (py::ssize_t)(nx > 0 ? nx : 0)});
+                 if (!o.label.empty()) std::memcpy(label.mutable_data(), o.label.data(), o.label.size() * sizeof(int32_t));
+                 py::array_t<pwpp_obstacle_cluster> table((py::ssize_t)o.clusters.size());
+                 if (!o.clusters.empty()) std::memcpy(table.mutable_data(), o.clusters.data(), o.clusters.size() * sizeof(pwpp_obstacle_cluster));
+                 py::array_t<pwpp_obstacle_hull> hulls((py::ssize_t)o.hulls.size());
+                 if (!o.hulls.empty()) std::memcpy(hulls.mutable_data(), o.hulls.data(), o.hulls.size() * sizeof(pwpp_obstacle_hull));
+                 py::array_t<int32_t> vertices({(py::ssize_t)o.hulls.size(), (py::ssize_t)(max_vertices > 0 ? max_vertices : 0), (py::ssize_t)2});
+                 if (!o.vertices.empty()) std::memcpy(vertices.mutable_data(), o.vertices.data(), o.vertices.size() * sizeof(int32_t));
+                 return py::make_tuple(label, table, hulls, vertices, o.count);
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"), py::arg("max_vertices") = 32,
              py::arg("min_count") = 1, py::arg("connectivity") = 8, py::arg("ground_only") = false)
         .def("trackObstacleClusters",
              [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, float h_min, float h_max, const std::array<double, 6> &pose, int min_count,
