@@ -2353,11 +2353,12 @@ int per_frame_count_args(int n, int frames, const char *noun) {
     return PWPP_OK;
 }
 
-// ... and of such a list of cells, n x {x, y}, on an image of nx x ny cells (`noun`: "origin", "source"): the first one outside is named
-int cells_inside_args(const int32_t *xy, int n, int nx, int ny, const char *noun) {
+// ... and of such a list of cells, n rows of `stride` words that begin {x, y} (3: the viewshed's, with an eye), on an image of
+// nx x ny cells (`noun`: "origin", "source"): the first one outside is named
+int cells_inside_args(const int32_t *xy, int n, int nx, int ny, const char *noun, int stride = 2) {
     for (int i = 0; i < n; ++i)
-        if (xy[2 * i] < 0 || xy[2 * i] >= nx || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= ny)
-            return fail(PWPP_E_ARG, "%s %d, cell (%d, %d), lies outside the %d x %d cells", noun, i, xy[2 * i], xy[2 * i + 1], nx, ny);
+        if (const int32_t *c = xy + stride * i; c[0] < 0 || c[0] >= nx || c[1] < 0 || c[1] >= ny)
+            return fail(PWPP_E_ARG, "%s %d, cell (%d, %d), lies outside the %d x %d cells", noun, i, c[0], c[1], nx, ny);
     return PWPP_OK;
 }
 
@@ -2486,6 +2487,8 @@ int obstacle_scan(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float 
 // Stated once for all of them: a count given "1 or one per frame" (per_frame_count_args) and a list of cells inside the image (cells_inside_args), a byte
 // image's section (Staging::add_bytes), the first checks of a labelling (label_first_args) and of a reach on a caller's image (reach_image_args), the
 // terrain analysis as a stage for its cost bytes alone (terrain_cost_sections), the reach's sections for the field and for the routes (reach_sections).
+// The two lines of sight share the checks of their chained calls (visibility_origin_args), origins with or without a height (cells_inside_args, frame_cells_of, frame_cells_section)
+// and the ground returns' launch (enqueue_ground_returns); boxes and hulls, the row tables of a label image: row_table_args, row_table_obstacle_args, row_table_launches, counted_points.
 
 // The section of an operator's input image (count, top).  From the caller (pwpp_*_grid): read, and absent without a pointer.
 // From the raster (pwpp_*_obstacles): written for the caller who asks for it, else kept in the buffer.
@@ -2762,36 +2765,39 @@ int visibility_param_args(int min_count, int max_range) {
 }
 
 // Positions in metres, one per frame or one for all (the visibility's origins, the reach's sources; `what` names one), as cells of
-// the checked grid by the raster's cell rule: `out`: n x {ix, iy}.
-int frame_cells_of(const pwpp_ground_grid *g, const double *xy, int n, const char *what, std::vector<int32_t> &out) {
-    out.assign(2 * (size_t)n, 0);
+// the checked grid by the raster's cell rule: `out`: n x {ix, iy}.  `cols` 3 (the viewshed's origins): n x {x, y, z}, z finite too -> {ix, iy, pwpp_view_units(z)}.
+int frame_cells_of(const pwpp_ground_grid *g, const double *xy, int n, const char *what, std::vector<int32_t> &out, int cols = 2) {
+    out.assign((size_t)cols * (size_t)n, 0);
     for (int i = 0; i < n; ++i) {
-        const double x = xy[2 * i], y = xy[2 * i + 1];
+        const double x = xy[cols * i], y = xy[cols * i + 1], z = cols == 3 ? xy[cols * i + 2] : 0.0;
         int ox = 0, oy = 0;
-        if (!std::isfinite(x) || !std::isfinite(y)) return fail(PWPP_E_ARG, "%s %d, (%g, %g), is not finite", what, i, x, y);
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z))
+            return cols == 3 ? fail(PWPP_E_ARG, "%s %d, (%g, %g, %g), is not finite", what, i, x, y, z) : fail(PWPP_E_ARG, "%s %d, (%g, %g), is not finite", what, i, x, y);
         if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
             return fail(PWPP_E_ARG, "%s %d, (%g, %g) m, lies outside the grid", what, i, x, y);
-        out[2 * i] = ox, out[2 * i + 1] = oy;
+        out[cols * i] = ox, out[cols * i + 1] = oy;
+        if (cols == 3) out[cols * i + 2] = pwpp_view_units(z);
     }
     return PWPP_OK;
 }
 
-// What the entry points that rasterise first check of the band, the grid, min_count, max_range and the origins in metres, which
-// they turn into cells (`org`: n_origins x {ox, oy}).
-int visibility_origin_args(const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin_xy, int n_origins, int max_range,
-                           int frames, std::vector<int32_t> &org) {
+// What the entry points that rasterise first check of the band, the grid, min_count, max_range and the origins in metres, which they turn into cells (`org`:
+// n_origins x {ox, oy}).  With `min_seen` the call is the viewshed's (`who`): min_seen is checked in its place, the origins carry a height ({ox, oy, eye}).
+int visibility_origin_args(const pwpp_ground_grid *g, float h_min, float h_max, int min_count, const double *origin, int n_origins, int max_range, int frames,
+                           std::vector<int32_t> &org, const char *who = kVisibilityWho, const int *min_seen = nullptr) {
     int rc = obstacle_band_args(g, h_min, h_max);
     if (rc || (rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
-    if ((rc = side_args(g->nx, g->ny, kVisibilityWho))) return rc;
+    if ((rc = side_args(g->nx, g->ny, who))) return rc;
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
+    if (min_seen && *min_seen < 0) return fail(PWPP_E_ARG, "min_seen %d: 0 (no ground returns) or more expected", *min_seen);
     if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
-    return frame_cells_of(g, origin_xy, n_origins, "origin", org);
+    return frame_cells_of(g, origin, n_origins, "origin", org, min_seen ? 3 : 2);
 }
 
-// The section of the cells given one per frame (the visibility's origins, the reach's sources): n x {x, y} as an upload; one cell
-// travels as an argument of the launch and has no words.
-int frame_cells_section(Staging &st, const std::vector<int32_t> &xy) {
-    return xy.size() > 2 ? st.add_upload(std::vector<uint32_t>(xy.begin(), xy.end())) : st.add(0, nullptr, Staging::kKept);
+// The section of the cells given one per frame (the visibility's and the viewshed's origins, the reach's sources): n rows of
+// `cols` words as an upload; one row travels as arguments of the launch and has no words.
+int frame_cells_section(Staging &st, const std::vector<int32_t> &xy, size_t cols = 2) {
+    return xy.size() > cols ? st.add_upload(std::vector<uint32_t>(xy.begin(), xy.end())) : st.add(0, nullptr, Staging::kKept);
 }
 
 // (the kernels' bit image and the origins first; `org`: the origin cells, n_origins x {ox, oy}, checked; `keep`: an image the
@@ -2881,7 +2887,7 @@ struct ViewshedSections {
 };
 void viewshed_out_sections(pwpp_handle *h, Staging &st, int nx, int ny, int frames, int max_range, const std::vector<int32_t> &org, ViewshedSections &s) {
     s.work = st.add(pwpp_viewshed_work_words(nx, ny, frames, h->viewshed_path, max_range), nullptr, Staging::kKept);
-    s.org = org.size() > 3 ? st.add_upload(std::vector<uint32_t>(org.begin(), org.end())) : st.add(0, nullptr, Staging::kKept);
+    s.org = frame_cells_section(st, org, 3);
 }
 int viewshed_launch(pwpp_handle *h, const Staging &st, const ViewshedSections &s, int nx, int ny, int frames, int min_count, int min_seen,
                     const std::vector<int32_t> &org, int max_range) {
@@ -2889,6 +2895,15 @@ int viewshed_launch(pwpp_handle *h, const Staging &st, const ViewshedSections &s
                                      st.dev<const int32_t>(s.seen), min_seen, org[0], org[1], org[2], org.size() > 3 ? st.dev<const int32_t>(s.org) : nullptr,
                                      max_range, h->viewshed_path, st.dev<int32_t>(s.first), st.dev<int32_t>(s.shadow), st.dev<int8_t>(s.occ),
                                      st.dev<uint32_t>(s.work), h->stream);
+}
+// The longest ground list of a frame range of the last call, and the ground returns of a scan's frames into `seen` (a HIP error code)
+int longest_ground_list(const pwpp_handle *h, int frame_first, int frames) {
+    int max_ground = 0;
+    for (int f = frame_first; f < frame_first + frames; ++f) max_ground = std::max(max_ground, h->h_results.p[f].n_ground);
+    return max_ground;
+}
+int enqueue_ground_returns(pwpp_handle *h, const PwppObstacleScan &scan, int32_t *seen) {
+    return pwpp_launch_ground_returns(&scan, longest_ground_list(h, scan.frame_first, scan.frames), seen, h->stream);
 }
 }  // namespace
 
@@ -2905,9 +2920,7 @@ int pwpp_viewshed_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, cons
     if ((rc = visibility_param_args(min_count, max_range))) return rc;
     if (seen && min_seen < 1) return fail(PWPP_E_ARG, "min_seen %d with a seen image: at least 1 expected", min_seen);
     if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
-    for (int i = 0; i < n_origins; ++i)
-        if (origin[3 * i] < 0 || origin[3 * i] >= nx || origin[3 * i + 1] < 0 || origin[3 * i + 1] >= ny)
-            return fail(PWPP_E_ARG, "origin %d, cell (%d, %d), lies outside the %d x %d cells", i, origin[3 * i], origin[3 * i + 1], nx, ny);
+    if ((rc = cells_inside_args(origin, n_origins, nx, ny, "origin", 3))) return rc;
     for (int i = 0; i < n_origins; ++i)
         if (origin[3 * i + 2] == PWPP_VIEW_NO_HEIGHT) return fail(PWPP_E_ARG, "origin %d: its eye is PWPP_VIEW_NO_HEIGHT", i);
     if ((rc = mem_args(mem, kViewshedWho))) return rc;
@@ -2935,9 +2948,7 @@ int pwpp_rasterize_ground_returns(pwpp_handle *h, const pwpp_ground_grid *g, int
     if ((rc = st.begin())) return rc;
     PwppObstacleScan scan;
     if ((rc = obstacle_scan(h, g, 0.0f, 0.0f, frame_first, frames, scan))) return rc;
-    int max_ground = 0;
-    for (int f = frame_first; f < frame_first + frames; ++f) max_ground = std::max(max_ground, h->h_results.p[f].n_ground);
-    const int lrc = pwpp_launch_ground_returns(&scan, max_ground, st.dev<int32_t>(s_seen), h->stream);
+    const int lrc = enqueue_ground_returns(h, scan, st.dev<int32_t>(s_seen));
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
@@ -2947,23 +2958,10 @@ int pwpp_viewshed_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_m
                             int32_t *count) {
     if (!h) return fail(PWPP_E_ARG, "null handle");
     if (!g || !first || !origin_xyz) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!first ? "first image" : "origin"));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc || (rc = grid_geometry_args(g))) return rc;  // (the origins need the grid)
-    if ((rc = side_args(g->nx, g->ny, kViewshedWho))) return rc;
-    if ((rc = visibility_param_args(min_count, max_range))) return rc;
-    if (min_seen < 0) return fail(PWPP_E_ARG, "min_seen %d: 0 (no ground returns) or more expected", min_seen);
-    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
-    std::vector<int32_t> org(3 * (size_t)n_origins, 0);
-    for (int i = 0; i < n_origins; ++i) {
-        const double x = origin_xyz[3 * i], y = origin_xyz[3 * i + 1], z = origin_xyz[3 * i + 2];
-        int ox = 0, oy = 0;
-        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(PWPP_E_ARG, "origin %d, (%g, %g, %g), is not finite", i, x, y, z);
-        if (!pwpp_vis_cell_of(x, g->x0, g->cell, g->nx, ox) || !pwpp_vis_cell_of(y, g->y0, g->cell, g->ny, oy))
-            return fail(PWPP_E_ARG, "origin %d, (%g, %g) m, lies outside the grid", i, x, y);
-        org[3 * i] = ox, org[3 * i + 1] = oy, org[3 * i + 2] = pwpp_view_units(z);
-    }
+    std::vector<int32_t> org;
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    int rc = visibility_origin_args(g, h_min, h_max, min_count, origin_xyz, n_origins, max_range, frames, org, kViewshedWho, &min_seen);
+    if (rc || (rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
     const int nx = g->nx, ny = g->ny;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     ViewshedSections s;
@@ -2976,10 +2974,7 @@ int pwpp_viewshed_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_m
     s.occ = st.add_bytes(cells, occupancy, Staging::kOut);
     if ((rc = st.begin())) return rc;
     rc = enqueue_on_obstacles(h, st, g, h_min, h_max, frame_first, frames, s.count, s_top, [&](const PwppObstacleScan &scan) {
-        if (min_seen <= 0) return 0;
-        int max_ground = 0;
-        for (int f = frame_first; f < frame_first + frames; ++f) max_ground = std::max(max_ground, h->h_results.p[f].n_ground);
-        return pwpp_launch_ground_returns(&scan, max_ground, st.dev<int32_t>(s.seen), h->stream);
+        return min_seen > 0 ? enqueue_ground_returns(h, scan, st.dev<int32_t>(s.seen)) : 0;
     });
     if (rc) return rc;
     rc = enqueue_on_ground(h, st, g, frame_first, frames, s_ground, -1, [&] {
@@ -4360,24 +4355,66 @@ int box_extent_args(const pwpp_ground_grid *g) {
         return fail(PWPP_E_ARG, "grid of %d x %d cells of %g m: the obstacle boxes take an extent of at most 1024 m", g->nx, g->ny, g->cell);
     return PWPP_OK;
 }
+
+// ---- the rows of a label image, boxes or hulls: stated once for both tables -----------------------------------------------------------
+struct RowTableNouns {
+    const char *table, *rows, *who;
+};
+constexpr RowTableNouns kBoxNouns = {"box table", "boxes", "the obstacle boxes take"}, kHullNouns = {"hull table", "hulls", "the obstacle hulls take"};
+
+// What a table of max_rows rows a frame may be; `max_vertices`: the length of the hulls' vertex lists (null: a table without lists)
+int row_table_args(int64_t frames, int max_rows, const char *rows, const int *max_vertices) {
+    if (max_rows < 1) return fail(PWPP_E_ARG, "max_%s %d: at least 1 expected", rows, max_rows);
+    if (max_vertices && (*max_vertices < 1 || *max_vertices > PWPP_HULL_MAX_VERTICES))
+        return fail(PWPP_E_ARG, "max_vertices %d: 1 .. %d expected", *max_vertices, PWPP_HULL_MAX_VERTICES);
+    if (frames > 0 && frames * (int64_t)max_rows > ((int64_t)1 << 24)) return fail(PWPP_E_ARG, "%lld frames x %d %s exceed 2^24 rows", (long long)frames, max_rows, rows);
+    if (max_vertices && frames > 0 && frames * (int64_t)max_rows * (int64_t)*max_vertices > ((int64_t)1 << 28))
+        return fail(PWPP_E_ARG, "%lld frames x %d %s x %d vertices exceed 2^28", (long long)frames, max_rows, rows, *max_vertices);
+    return PWPP_OK;
+}
+
+// What pwpp_box_obstacles and pwpp_hull_obstacles check first, in this order (the hulls' table, of 64-bit words: its alignment too); lands the call in flight.
+int row_table_obstacle_args(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem, const int32_t *label,
+                            const void *table, int max_rows, const int *max_vertices, const RowTableNouns &n, size_t &cells) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !label || !table) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!label ? "label image" : n.table));
+    int rc = obstacle_band_args(g, h_min, h_max);
+    if (rc || (rc = row_table_args(frames, max_rows, n.rows, max_vertices)) || (rc = box_extent_args(g)) || (rc = mem_args(mem, n.who))) return rc;
+    if (max_vertices && (rc = alignment_args(mem, {{table, 7u, n.table}}))) return rc;
+    return (rc = ground_grid_args(h, g, frame_first, frames, mem, cells)) ? rc : frame_cells_args(g->nx, g->ny);
+}
+
+// The five launches both end in: the rows' step 0, then for each of the two point passes the pass and the rows' step 1 + pass; the first failing code.
+extern "C++" template <class Rows, class Pass>  // (the entry points' extern "C" block is open around this namespace)
+int row_table_launches(Rows rows, Pass pass) {
+    int lrc = rows(0);
+    for (int p = 0; p < 2 && lrc == 0; ++p)
+        if ((lrc = pass(p)) == 0) lrc = rows(1 + p);
+    return lrc;
+}
+
+// Whether the raster counts a point at (x, y): the cell rule as pwpp_vis_cell_of states it (grid_cell of pwpp_kernels.hip: the same rule with a float input) ...
+bool grid_counts(const pwpp_ground_grid *g, float x, float y) {
+    int cell = 0;
+    return pwpp_vis_cell_of((double)x, g->x0, g->cell, g->nx, cell) && pwpp_vis_cell_of((double)y, g->y0, g->cell, g->ny, cell);
+}
+// ... and the points of a caller's list a table's host form counts: the row in [0, max_rows), counted(i) (its NaN rule), inside the
+// grid.  visit(i, row, dx, dy): the point's offsets from the grid's origin, in double.
+extern "C++" template <class Counted, class Visit>
+void counted_points(const pwpp_ground_grid *g, const float *xyz, const int32_t *row, int64_t m, int max_rows, Counted counted, Visit visit) {
+    for (int64_t i = 0; i < m; ++i)
+        if (row[i] >= 0 && row[i] < max_rows && counted(i) && grid_counts(g, xyz[3 * i], xyz[3 * i + 1]))
+            visit(i, row[i], (double)xyz[3 * i] - g->x0, (double)xyz[3 * i + 1] - g->y0);
+}
 }  // namespace
 
 // Init, first pass, solve, second pass, finish: five launches on the handle's stream.  The accumulators, and for PWPP_MEM_HOST the
 // label image and the rows, live in the cluster buffer.
 int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem, const int32_t *label,
                        pwpp_obstacle_box *boxes, int max_boxes) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    if (!g || !label || !boxes) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!label ? "label image" : "box table"));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
-    if (max_boxes < 1) return fail(PWPP_E_ARG, "max_boxes %d: at least 1 expected", max_boxes);
-    if (frames > 0 && (int64_t)frames * (int64_t)max_boxes > ((int64_t)1 << 24))
-        return fail(PWPP_E_ARG, "%d frames x %d boxes exceed 2^24 rows", frames, max_boxes);
-    if ((rc = box_extent_args(g))) return rc;
-    if ((rc = mem_args(mem, "the obstacle boxes take"))) return rc;
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
+    int rc = row_table_obstacle_args(h, g, h_min, h_max, frame_first, frames, mem, label, boxes, max_boxes, nullptr, kBoxNouns, cells);
+    if (rc) return rc;
     const size_t rows = (size_t)frames * (size_t)max_boxes;
     Staging st(h, h->d_clusters, mem, kClusterAlign);
     const int s_acc = st.add(rows * PWPP_BOX_ACC_WORDS, nullptr, Staging::kKept);
@@ -4387,11 +4424,8 @@ int pwpp_box_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, f
     if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
     const PwppBoxRows table = {st.dev<const int32_t>(s_label), max_boxes, st.dev<uint32_t>(s_acc), st.dev<const float>(s_rows)};
     const int combine = h->boxes_path == 0 ? (kBoxesDefaultCombine ? 1 : 0) : (h->boxes_path == 2 ? 1 : 0);
-    int lrc = pwpp_launch_box_rows(0, (int64_t)rows, table.acc, g->x0, g->y0, st.dev<void>(s_rows), h->stream);
-    for (int pass = 0; pass < 2 && lrc == 0; ++pass) {
-        lrc = pwpp_launch_box_pass(pass, combine, &scan, &table, h->stream);
-        if (lrc == 0) lrc = pwpp_launch_box_rows(1 + pass, (int64_t)rows, table.acc, g->x0, g->y0, st.dev<void>(s_rows), h->stream);
-    }
+    const int lrc = row_table_launches([&](int step) { return pwpp_launch_box_rows(step, (int64_t)rows, table.acc, g->x0, g->y0, st.dev<void>(s_rows), h->stream); },
+                                       [&](int pass) { return pwpp_launch_box_pass(pass, combine, &scan, &table, h->stream); });
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
@@ -4412,17 +4446,8 @@ int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz, const float *hg
     for (int j = 0; j < PWPP_BOX_KEYS; ++j) empty.k[j] = (j & 1) ? PWPP_BOX_KEY_NO_MAX : PWPP_BOX_KEY_NO_MIN;
     std::vector<Acc> acc((size_t)max_boxes, empty);
     std::vector<PwppBoxAxis> axis((size_t)max_boxes, PwppBoxAxis{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f});
-    // the grid_cell rule of the kernels: u = (c - c0) / cell in double, kept iff 0 <= u < n (a NaN: not)
-    const auto inside = [](double d, double cell, int n) {
-        const double u = d / cell;
-        return u >= 0.0 && u < (double)n;
-    };
     for (int pass = 0; pass < 2; ++pass) {
-        for (int64_t i = 0; i < m; ++i) {
-            const int32_t r = row[i];
-            if (r < 0 || r >= max_boxes || hgt[i] != hgt[i]) continue;
-            const double dx = (double)xyz[3 * i] - g->x0, dy = (double)xyz[3 * i + 1] - g->y0;
-            if (!inside(dx, g->cell, g->nx) || !inside(dy, g->cell, g->ny)) continue;
+        counted_points(g, xyz, row, m, max_boxes, [&](int64_t i) { return hgt[i] == hgt[i]; }, [&](int64_t i, int32_t r, double dx, double dy) {
             Acc &a = acc[(size_t)r];
             if (pass == 0) {
                 const long long qx = pwpp_box_quantise(dx), qy = pwpp_box_quantise(dy);
@@ -4436,7 +4461,7 @@ int pwpp_box_points(const pwpp_ground_grid *g, const float *xyz, const float *hg
                     a.k[2 * j + 1] = std::max(a.k[2 * j + 1], k[j]);
                 }
             }
-        }
+        });
         for (int r = 0; r < max_boxes; ++r) {
             const Acc &a = acc[(size_t)r];
             if (pass == 0) {
@@ -4457,32 +4482,15 @@ static_assert(sizeof(pwpp_obstacle_hull) == 64 && alignof(pwpp_obstacle_hull) ==
                   offsetof(pwpp_obstacle_hull, qx_min) == 24 && offsetof(pwpp_obstacle_hull, cx) == 40,
               "pwpp_obstacle_hull is the sixteen words of pwpp_hull_row");
 static_assert(sizeof(pwpp_obstacle_hull) / 4 == PWPP_HULL_ROW_WORDS && PWPP_HULL_VERTICES_MAX == PWPP_HULL_MAX_VERTICES, "the kernels' row and vertex limit");
-
-int hull_table_args(int64_t frames, int max_hulls, int max_vertices) {
-    if (max_hulls < 1) return fail(PWPP_E_ARG, "max_hulls %d: at least 1 expected", max_hulls);
-    if (max_vertices < 1 || max_vertices > PWPP_HULL_MAX_VERTICES) return fail(PWPP_E_ARG, "max_vertices %d: 1 .. %d expected", max_vertices, PWPP_HULL_MAX_VERTICES);
-    if (frames > 0 && frames * (int64_t)max_hulls > ((int64_t)1 << 24)) return fail(PWPP_E_ARG, "%lld frames x %d hulls exceed 2^24 rows", (long long)frames, max_hulls);
-    if (frames > 0 && frames * (int64_t)max_hulls * (int64_t)max_vertices > ((int64_t)1 << 28))
-        return fail(PWPP_E_ARG, "%lld frames x %d hulls x %d vertices exceed 2^28", (long long)frames, max_hulls, max_vertices);
-    return PWPP_OK;
-}
 }  // namespace
 
 // Init, first pass, offsets, second pass, rows: five launches on the handle's stream.  The accumulators, the candidate arena, the
 // vertex lists nobody asked for (path 1 reads them back) and for PWPP_MEM_HOST the caller's arrays live in the cluster buffer.
 int pwpp_hull_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, float h_max, int frame_first, int frames, int mem, const int32_t *label,
                         pwpp_obstacle_hull *hulls, int max_hulls, int32_t *vertices, int max_vertices) {
-    if (!h) return fail(PWPP_E_ARG, "null handle");
-    if (!g || !label || !hulls) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!label ? "label image" : "hull table"));
-    int rc = obstacle_band_args(g, h_min, h_max);
-    if (rc) return rc;
-    if ((rc = hull_table_args(frames, max_hulls, max_vertices))) return rc;
-    if ((rc = box_extent_args(g))) return rc;
-    if ((rc = mem_args(mem, "the obstacle hulls take"))) return rc;
-    if ((rc = alignment_args(mem, {{hulls, 7u, "hull table"}}))) return rc;
     size_t cells = 0;
-    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
-    if ((rc = frame_cells_args(g->nx, g->ny))) return rc;
+    int rc = row_table_obstacle_args(h, g, h_min, h_max, frame_first, frames, mem, label, hulls, max_hulls, &max_vertices, kHullNouns, cells);
+    if (rc) return rc;
     PwppObstacleScan scan;
     if ((rc = obstacle_scan(h, g, h_min, h_max, frame_first, frames, scan))) return rc;
     const int path = pwpp_hull_path_of(h->hulls_path, (int64_t)frames * (int64_t)max_hulls);
@@ -4495,11 +4503,9 @@ int pwpp_hull_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, 
     if ((rc = st.begin())) return rc;
     const PwppHullRows table = {st.dev<const int32_t>(s_label), max_hulls, st.dev<uint32_t>(s_acc), st.dev<unsigned long long>(s_arena), (int64_t)scan.max_nonground};
     int32_t *d_lists = (vertices || path == 1) ? st.dev<int32_t>(s_lists) : nullptr;
-    int lrc = pwpp_launch_hull_rows(0, path, frames, &table, g->x0, g->y0, st.dev<void>(s_rows), d_lists, max_vertices, h->stream);
-    for (int pass = 0; pass < 2 && lrc == 0; ++pass) {
-        lrc = pwpp_launch_hull_pass(pass, &scan, &table, h->stream);
-        if (lrc == 0) lrc = pwpp_launch_hull_rows(1 + pass, path, frames, &table, g->x0, g->y0, st.dev<void>(s_rows), d_lists, max_vertices, h->stream);
-    }
+    const int lrc = row_table_launches(
+        [&](int step) { return pwpp_launch_hull_rows(step, path, frames, &table, g->x0, g->y0, st.dev<void>(s_rows), d_lists, max_vertices, h->stream); },
+        [&](int pass) { return pwpp_launch_hull_pass(pass, &scan, &table, h->stream); });
     return lrc != 0 ? launch_failed(h, lrc) : st.end();
 }
 
@@ -4507,28 +4513,20 @@ int pwpp_hull_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, float h_min, 
 int pwpp_hull_points(const pwpp_ground_grid *g, const float *xyz, const int32_t *row, int64_t m, pwpp_obstacle_hull *hulls, int max_hulls, int32_t *vertices,
                      int max_vertices) {
     if (!g || !hulls) return fail(PWPP_E_ARG, "null %s", g ? "hull table" : "grid");
-    int rc = hull_table_args(1, max_hulls, max_vertices);
+    int rc = row_table_args(1, max_hulls, kHullNouns.rows, &max_vertices);
     if (rc) return rc;
     if (m < 0 || m > ((int64_t)1 << 22)) return fail(PWPP_E_ARG, "%lld points (0..2^22 supported)", (long long)m);
     if (m > 0 && (!xyz || !row)) return fail(PWPP_E_ARG, "null %s", !xyz ? "positions" : "rows");
     if ((rc = grid_geometry_args(g)) || (rc = box_extent_args(g))) return rc;
-    const auto inside = [](double d, double cell, int n) {  // (the grid_cell rule of the kernels, as in pwpp_box_points)
-        const double u = d / cell;
-        return u >= 0.0 && u < (double)n;
-    };
     try {
         std::vector<int64_t> first((size_t)max_hulls + 1, 0);
         std::vector<int32_t> of;  // the row of every counted point, -1: skipped
         of.assign((size_t)m, -1);
         std::vector<pwpp_hull_pt> pt((size_t)m, 0);
-        for (int64_t i = 0; i < m; ++i) {
-            const int32_t r = row[i];
-            if (r < 0 || r >= max_hulls || xyz[3 * i + 2] != xyz[3 * i + 2]) continue;
-            const double dx = (double)xyz[3 * i] - g->x0, dy = (double)xyz[3 * i + 1] - g->y0;
-            if (!inside(dx, g->cell, g->nx) || !inside(dy, g->cell, g->ny)) continue;
+        counted_points(g, xyz, row, m, max_hulls, [&](int64_t i) { return xyz[3 * i + 2] == xyz[3 * i + 2]; }, [&](int64_t i, int32_t r, double dx, double dy) {
             of[(size_t)i] = r, pt[(size_t)i] = pwpp_hull_pack(pwpp_box_quantise(dx), pwpp_box_quantise(dy));
             first[(size_t)r + 1] += 1;
-        }
+        });
         for (int r = 0; r < max_hulls; ++r) first[(size_t)r + 1] += first[(size_t)r];
         std::vector<pwpp_hull_pt> cand((size_t)first[(size_t)max_hulls], 0);
         std::vector<int64_t> at(first.begin(), first.end() - 1);

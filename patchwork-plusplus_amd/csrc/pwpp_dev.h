@@ -1,5 +1,5 @@
 // pwpp_dev.h -- structures shared by the host side (pwpp_capi.cpp) and the gfx950 kernels
-// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_viewshed.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_footprint.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
+// (pwpp_kernels.hip, pwpp_fit.hip, pwpp_clusters.hip, pwpp_distance.hip, pwpp_visibility.hip, pwpp_fusion.hip, pwpp_elevation.hip, pwpp_terrain.hip, pwpp_reach.hip, pwpp_route.hip, pwpp_footprint.hip, pwpp_tracks.hip, pwpp_evidence.hip), and the prototypes of the launchers they call across files.
 // Internal; the public boundary is include/pwpp.h.
 #ifndef PWPP_DEV_H
 #define PWPP_DEV_H
@@ -347,7 +347,7 @@ int pwpp_launch_distance_grid(int nx, int ny, int frames, const int32_t *count, 
 size_t pwpp_visibility_work_words(int nx, int ny, int frames, int path);
 int pwpp_launch_visibility_grid(int nx, int ny, int frames, const int32_t *count, int min_count, int ox, int oy, const int32_t *origins, int max_range,
                                 int path, int32_t *first, int8_t *occupancy, uint32_t *work, hipStream_t stream);
-// pwpp_viewshed.hip (k_view_walk<1>: "viewshed_path" 1; k_view_pack, k_view_walk<2>: 2)
+// the viewshed, in pwpp_visibility.hip too (k_view_walk<1>: "viewshed_path" 1; k_vis_pack, k_view_walk<2>: 2)
 int pwpp_viewshed_path_of(int path, int max_range);  // what "viewshed_path" resolves to for a call: 1 or 2
 size_t pwpp_viewshed_work_words(int nx, int ny, int frames, int path, int max_range);
 int pwpp_launch_viewshed_grid(int nx, int ny, int frames, const int32_t *count, int min_count, const int32_t *block, const int32_t *target,

@@ -1,5 +1,5 @@
 // pwpp_viewshed.h -- the arithmetic of the height-aware line of sight (pwpp_viewshed_grid, pwpp_viewshed_obstacles), one text for
-// the kernels (pwpp_viewshed.hip), for the host side's quantiser and origins (pwpp_capi.cpp) and for the host program that deals
+// the kernels (pwpp_visibility.hip), for the host side's quantiser and origins (pwpp_capi.cpp) and for the host program that deals
 // the same pack and walk against a brute force of its own (tools/viewshed_check.cpp).  Internal; include/pwpp.h has the contract.
 //
 // THE WALK is the visibility's own: pwpp_vis_line and pwpp_vis_step of pwpp_visibility.h are called, the points P_k, the cells A
@@ -33,7 +33,6 @@
 #define PWPP_VIEW_UNITS 1024              // = PWPP_VIEW_UNITS_PER_M
 #define PWPP_VIEW_OPAQUE INT32_MAX        // the rise of an occupied cell without a height: above every rise
 #define PWPP_VIEW_BELOW INT32_MIN         // the rise of a target without a height: under every rise
-#define PWPP_VIEW_LDS_BYTES (128 * 1024)  // the largest bit image of a frame path 2 keeps in LDS: 1024 x 1024 cells, of the CU's 160 KiB
 
 // ---- the quantiser: metres -> units.  NaN: no height.  One multiplication, one clamp, one addition, one floor, in double.
 PWPP_HD inline int32_t pwpp_view_units(double metres) {

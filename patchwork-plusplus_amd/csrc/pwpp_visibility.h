@@ -31,6 +31,7 @@
 #define PWPP_VIS_OCCUPIED 100
 #define PWPP_VIS_UNKNOWN (-1)
 #define PWPP_VIS_MAX_SIDE 32768  // nx, ny and max_range
+#define PWPP_VIS_LDS_BYTES (128 * 1024)  // the largest bit image of a frame a walk (the visibility's, the viewshed's) keeps in LDS: 1024 x 1024 cells, of the CU's 160 KiB
 
 // ---- the origin's cell: the cell rule of the obstacle raster, u = (c - c0) / cell in double (one subtraction, one IEEE division),
 // inside iff 0 <= u < n (a NaN: not), the cell floor(u)

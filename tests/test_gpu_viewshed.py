@@ -4,7 +4,7 @@ to full, random block and target heights with a tenth PWPP_VIEW_NO_HEIGHT and ri
 corners, on an edge, in the middle and on an occupied cell with an eye per frame, from host and from device memory, on both values
 of the option "viewshed_path", with and without shadow, seen and occupancy -- degenerate input against pwpp_visibility_grid itself,
 the subset theorem, the kerb, max_range, the independence of the frames of a batch, witnessed cells, one image on either side of the
-LDS path's limit, misaligned device images, the ground-returns raster against numpy, the chained call against its four stages on
+LDS path's limit, the window of rows in LDS and the launch plan that both operators share, misaligned device images, the ground-returns raster against numpy, the chained call against its four stages on
 KITTI frames, and that asking changes nothing else."""
 import ctypes
 import functools
@@ -18,7 +18,7 @@ import obstacle_visibility_ref as ov
 import pwpp_hip
 import viewshed_ref as vr
 from test_gpu_obstacle_grid import _everything, small_cloud, three_frames
-from test_gpu_obstacle_visibility import FILLS, SHAPES, origin_kinds, shape_ids
+from test_gpu_obstacle_visibility import FILLS, SHAPES, from_device as vis_from_device, origin_kinds, shape_ids
 
 pytestmark = pytest.mark.gpu
 
@@ -222,8 +222,8 @@ def test_a_batch_is_its_frames(handle):
 
 # ---- the LDS limit ----------------------------------------------------------------------------------------------------------------
 def lds_bytes():
-    text = open(os.path.join(ROOT, "patchwork-plusplus_amd", "csrc", "pwpp_viewshed.h")).read()
-    a, b = re.search(r"#define PWPP_VIEW_LDS_BYTES \((\d+) \* (\d+)\)", text).groups()
+    text = open(os.path.join(ROOT, "patchwork-plusplus_amd", "csrc", "pwpp_visibility.h")).read()
+    a, b = re.search(r"#define PWPP_VIS_LDS_BYTES \((\d+) \* (\d+)\)", text).groups()
     return int(a) * int(b)
 
 
@@ -247,6 +247,46 @@ def test_either_side_of_the_lds_limit(handle, side):
     assert np.array_equal(gs, ws)
     assert np.array_equal(occ[0][cells[:, 1], cells[:, 0]], vr.occupancy_of(count[0], wf, cells=cells))
     assert (wf == vr.NONE).sum() > 100 and (wf >= 0).sum() > 100 and ((ws != vr.NO_HEIGHT) & (wf == vr.NONE)).sum() > 100
+
+
+# ---- the window of rows in LDS and the launch plan, which both operators share ------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def window_case():
+    """Three frames of 70 x 37 cells: a row of three words, the last ragged; a run of 256 cells spans four rows; eleven runs, the last
+    ragged.  An origin in the first row, in the last and in the middle: the window of a run grows upward, downward and both ways."""
+    nx, ny = 70, 37
+    count = np.stack([ov.random_count(nx, ny, 0.05, 1, 4100 + f) for f in range(3)])
+    origins = np.array([[12, 0, 1700], [55, ny - 1, -350], [35, ny // 2, 12000]], np.int32)
+    block, target = vr.random_heights(count.shape, 1700, 4111), vr.random_heights(count.shape, 1700, 4112)
+    want = {r: (ov.visibility_frames(count, origins[:, :2], 1, r), vr.viewshed_frames(count, origins, block, target, max_range=r)) for r in (0, 9)}
+    for a in [count, origins, block, target] + [x for pair in want.values() for res in pair for x in res]:
+        a.setflags(write=False)
+    return count, origins, block, target, want
+
+
+def test_the_shared_window_and_plan(handle):
+    count, origins, block, target, want = window_case()
+    try:
+        for vis_path, view_path in ((0, 1), (1, 2)):
+            handle.set_option("visibility_path", vis_path)
+            handle.set_option("viewshed_path", view_path)
+            for max_range in (0, 9):
+                for mem in ("host", "device"):
+                    what = "visibility_path %d, viewshed_path %d, max_range %d, %s memory" % (vis_path, view_path, max_range, mem)
+                    if mem == "host":
+                        two = handle.visibility_grid(count, origins[:, :2], 1, max_range)
+                        three = handle.viewshed_grid(count, origins, block, target, max_range=max_range)
+                        flat = handle.viewshed_grid(count, origins, max_range=max_range)
+                    else:
+                        two = vis_from_device(handle, count, origins[:, :2], 1, max_range)
+                        three = from_device(handle, count, origins, block, target, max_range=max_range)
+                        flat = from_device(handle, count, origins, max_range=max_range)
+                    assert all(g.tobytes() == w.tobytes() for g, w in zip(two, want[max_range][0])), what + ": the visibility differs from the brute force"
+                    check(three, want[max_range][1], what)
+                    assert flat[0].tobytes() == two[0].tobytes() and flat[2].tobytes() == two[1].tobytes(), what + ": without heights it is not the visibility"
+    finally:
+        handle.set_option("visibility_path", 0)
+        handle.set_option("viewshed_path", 0)
 
 
 # ---- alignment --------------------------------------------------------------------------------------------------------------------

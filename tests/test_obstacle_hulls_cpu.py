@@ -269,6 +269,37 @@ def test_random_sets_on_a_sub_lattice_and_the_invariants(lib):
     assert sets == 2000
 
 
+def test_boxes_and_hulls_count_the_same_points(lib):
+    """include/pwpp.h: pwpp_box_points and pwpp_hull_points count the same points (heights equal to z: both NaN rules agree).
+    The cell rule written out: u = ((double)x - x0) / cell, kept iff 0 <= u < n."""
+    x0, y0, cell, nx, ny, rows = 0.1, 0.0, 0.5, 8, 5, 6  # (x0 is no binary fraction: no float32 x makes dx zero)
+    below, above = lambda v: np.nextafter(F32(v), F32(-np.inf)), lambda v: np.nextafter(F32(v), F32(np.inf))
+    far = F32(x0 + nx * cell)
+    edge = [(F32(x0), 1.0), (below(x0), 1.0),             # the float32 at x0 (just right of the double) and the one before it
+            (far, 1.0), (below(far), 1.0), (above(far), 1.0),
+            (1.0, -0.0), (1.0, below(0.0)), (1.0, F32(ny * cell)), (1.0, below(ny * cell)),
+            (np.nan, 1.0), (1.0, np.inf), (-np.inf, 1.0)]
+    rng = np.random.default_rng(17)
+    xy = np.concatenate([np.array(edge, F32), (rng.random((40, 2)) * [nx * cell + 1.0, ny * cell + 1.0] + [x0 - 0.5, y0 - 0.5]).astype(F32)])
+    xy = np.concatenate([xy, np.tile(np.array([[1.3, 0.8]], F32), (4, 1))])  # four points inside, for the rows at the table's ends
+    z = rng.normal(0.0, 1.0, len(xy)).astype(F32)
+    z[[14, 21, 30]] = np.nan
+    row = rng.integers(-1, rows + 1, len(xy)).astype(np.int32)
+    row[:len(edge)] = np.arange(len(edge)) % rows
+    row[-4:] = [-1, 0, rows - 1, rows]
+    xyz = np.concatenate([xy, z[:, None]], 1)
+    with np.errstate(invalid="ignore"):
+        u, v = (xy[:, 0].astype(np.float64) - x0) / cell, (xy[:, 1].astype(np.float64) - y0) / cell
+        inside = (u >= 0.0) & (u < nx) & (v >= 0.0) & (v < ny)
+    assert inside[:len(edge)].tolist() == [True, False, True, True, False, True, False, False, True, False, False, False]
+    keep = inside & (row >= 0) & (row < rows) & ~np.isnan(z)
+    want = np.bincount(row[keep], minlength=rows)
+    assert 0 < keep.sum() < len(xy) and (want > 0).all() and (~keep[[14, 21, 30]]).all()
+    boxes = pwpp_hip.box_points(x0, y0, cell, nx, ny, xyz, z, row, rows)
+    hulls, _ = pwpp_hip.hull_points(x0, y0, cell, nx, ny, xyz, row, rows, 8)
+    assert boxes["points"].tolist() == hulls["points"].tolist() == want.tolist()
+
+
 def test_vertex_xy(lib):
     q = np.array([[0, 0], [1, 1024], [QTOP, 5]], np.int32)
     xy = pwpp_hip.hull_vertex_xy(-3.5, 2.25, 1.0, 8, 8, q)

@@ -49,10 +49,10 @@ def test_symbols_macro_constants_and_prototypes(lib):
         assert callable(getattr(pwpp_hip.Handle, name)), name
     import pypatchworkpp
     assert hasattr(pypatchworkpp.patchworkpp, "getObstacleViewshed")
-    # the one text, its translation unit, and the kernels' constant the GPU test computes the LDS limit from
-    assert os.path.exists(os.path.join(PKG, "csrc", "pwpp_viewshed.hip"))
-    assert "#define PWPP_VIEW_LDS_BYTES (128 * 1024)" in open(os.path.join(PKG, "csrc", "pwpp_viewshed.h")).read()
-    assert "csrc/pwpp_viewshed.hip" in open(os.path.join(PKG, "Makefile")).read()
+    # the one text, its translation unit (the visibility's: the walk with heights), and the kernels' constant the GPU test computes the LDS limit from
+    assert os.path.exists(os.path.join(PKG, "csrc", "pwpp_viewshed.h")) and os.path.exists(os.path.join(PKG, "csrc", "pwpp_visibility.hip"))
+    assert "#define PWPP_VIS_LDS_BYTES (128 * 1024)" in open(os.path.join(PKG, "csrc", "pwpp_visibility.h")).read()
+    assert "csrc/pwpp_visibility.hip" in open(os.path.join(PKG, "Makefile")).read()
 
 
 def test_the_quantiser(lib):
@@ -163,6 +163,51 @@ def test_every_argument_is_named_before_the_device_is_touched_and_in_order(lib):
     gg = pwpp_hip.GroundGrid(-2.0, -2.0, 0.0, 4, 4, 0, 0)
     assert returns(gr=ctypes.byref(gg)) == E_ARG and b"finite" in err()
     assert lib.pwpp_rasterize_ground_returns(fake, ctypes.byref(g), 0, 1, 2, vp(first)) == E_ARG and b"PWPP_MEM_HOST or PWPP_MEM_DEVICE" in err()
+
+
+def test_an_origin_is_refused_in_the_visibilitys_words(lib):
+    """The 2-D operator and the viewshed refuse the same origin with the same sentence; only the printed z is the viewshed's own."""
+    first = np.zeros(16, np.int32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # (never dereferenced: these checks come first)
+    H = pwpp_hip.MEM_HOST
+    err = lambda: lib.pwpp_last_error().decode()
+    g = pwpp_hip.GroundGrid(-2.0, -2.0, 1.0, 4, 4, 0, 0)
+
+    def metres(xyz, n=1, frames=1):
+        """the messages of (pwpp_visibility_obstacles, pwpp_viewshed_obstacles) for origins given as rows of x, y, z"""
+        xyz = np.array(xyz, np.float64).reshape(n, 3)
+        xy = np.ascontiguousarray(xyz[:, :2])
+        assert lib.pwpp_visibility_obstacles(fake, ctypes.byref(g), 0.2, 2.5, 1, vp(xy), n, 0, 0, frames, H, vp(first), None, None) == E_ARG
+        two = err()
+        assert lib.pwpp_viewshed_obstacles(fake, ctypes.byref(g), 0.2, 2.5, 1, 1, vp(xyz), n, 0, 0, frames, H, vp(first), None, None, None) == E_ARG
+        return two, err()
+
+    assert metres((np.nan, 0.5, 1.5)) == ("origin 0, (nan, 0.5), is not finite", "origin 0, (nan, 0.5, 1.5), is not finite")
+    assert metres((0.25, -np.inf, 1.5)) == ("origin 0, (0.25, -inf), is not finite", "origin 0, (0.25, -inf, 1.5), is not finite")
+    assert metres((2.0, 0.5, 1.5)) == ("origin 0, (2, 0.5) m, lies outside the grid",) * 2          # x0 + nx * cell: outside
+    assert metres((0.5, -2.0000001, 1.5)) == ("origin 0, (0.5, -2) m, lies outside the grid",) * 2  # (%g rounds the y)
+    assert metres((0.0, 0.0, 0.0, 1.0, 7.0, 0.0), n=2, frames=2) == ("origin 1, (1, 7) m, lies outside the grid",) * 2
+    assert metres((0.0, 0.0, 0.0, np.inf, 7.0, 0.0), n=2, frames=2) == ("origin 1, (inf, 7), is not finite", "origin 1, (inf, 7, 0), is not finite")
+    # the height alone is the viewshed's to refuse, in the same sentence
+    xyz = np.array((0.5, 0.5, np.nan), np.float64)
+    assert lib.pwpp_viewshed_obstacles(fake, ctypes.byref(g), 0.2, 2.5, 1, 1, vp(xyz), 1, 0, 0, 1, H, vp(first), None, None, None) == E_ARG
+    assert err() == "origin 0, (0.5, 0.5, nan), is not finite"
+
+    cnt = np.zeros(16, np.int32)
+
+    def cells(xy, n=1, frames=1):
+        """the messages of (pwpp_visibility_grid, pwpp_viewshed_grid) for origin cells given as rows of ox, oy (the eye: 1700)"""
+        two = np.array(xy, np.int32).reshape(n, 2)
+        three = np.ascontiguousarray(np.concatenate([two, np.full((n, 1), 1700, np.int32)], 1))
+        assert lib.pwpp_visibility_grid(fake, 4, 4, frames, H, vp(cnt), 1, vp(two), n, 0, vp(first), None) == E_ARG
+        a = err()
+        assert lib.pwpp_viewshed_grid(fake, 4, 4, frames, H, vp(cnt), 1, None, None, None, 1, vp(three), n, 0, vp(first), None, None) == E_ARG
+        return a, err()
+
+    assert cells((4, 0)) == ("origin 0, cell (4, 0), lies outside the 4 x 4 cells",) * 2
+    assert cells((0, -1)) == ("origin 0, cell (0, -1), lies outside the 4 x 4 cells",) * 2
+    assert cells((0, 0, 3, 3, 3, 4), n=3, frames=3) == ("origin 2, cell (3, 4), lies outside the 4 x 4 cells",) * 2
 
 
 CPP = r"""
