@@ -39,6 +39,7 @@
 #include "pwpp_boxes.h"
 #include "pwpp_dev.h"  // the launchers' prototypes
 #include "pwpp_unionfind.h"
+#include "pwpp_wave.h"
 
 namespace {
 
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(kClBlock) void k_cl_merge(ClImage I, int32_t *label
 // 3: grid (chunks * frames), one lane per cell of the chunk.  Other workgroups compress the words this one chases through: the
 // atomic-only rule again.  rank_in[cell] (a root's number of roots before it in its chunk) and chunk_count are this launch's own.
 __global__ __launch_bounds__(kClBlock) void k_cl_compress(ClImage I, int32_t *label, int32_t *rank_in, int32_t *chunk_count) {
-    __shared__ int s_wave[kClBlock / 64];
+    __shared__ unsigned s_wave[kClBlock / 64][1];
     const unsigned f = blockIdx.x / (unsigned)I.chunks, ch = blockIdx.x % (unsigned)I.chunks;
     const int64_t c64 = (int64_t)ch * PWPP_CL_CHUNK + threadIdx.x;
     const size_t fbase = (size_t)f * (size_t)I.per_frame;
@@ -183,48 +184,27 @@ __global__ __launch_bounds__(kClBlock) void k_cl_compress(ClImage I, int32_t *la
         const int32_t c = (int32_t)c64;
         if (m.load(c) >= 0) root = uf_compress(m, c, I.per_frame) == c;
     }
-    const unsigned long long mask = __ballot(root);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_wave[w] = __popcll(mask);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < kClBlock / 64; ++k) {
-        before += k < w ? s_wave[k] : 0;
-        total += s_wave[k];
-    }
-    if (root) rank_in[fbase + (size_t)c64] = before + __popcll(mask & ((1ull << lane) - 1ull));
-    if (threadIdx.x == 0) chunk_count[(size_t)f * (size_t)I.chunks + ch] = total;
+    unsigned before[1] = {root ? 1u : 0u}, total[1];
+    block_excl_scan<1, kClBlock / 64>(before, s_wave, total);  // (no thread has returned: every lane of every wave is active, as the DPP scan needs)
+    if (root) rank_in[fbase + (size_t)c64] = (int32_t)before[0];
+    if (threadIdx.x == 0) chunk_count[(size_t)f * (size_t)I.chunks + ch] = (int32_t)total[0];
 }
 
 // one workgroup per frame: chunk_count becomes its exclusive scan, n_clusters[f] the sum
 __global__ __launch_bounds__(kClBlock) void k_cl_scan(ClImage I, int32_t *chunk_count, int32_t *n_clusters) {
-    __shared__ int s_wave[kClBlock / 64];
+    __shared__ unsigned s_wave[kClBlock / 64][1];
     __shared__ int s_carry;
     const unsigned f = blockIdx.x;
     int32_t *cc = chunk_count + (size_t)f * (size_t)I.chunks;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (threadIdx.x == 0) s_carry = 0;
     __syncthreads();
-    for (int64_t base = 0; base < I.chunks; base += kClBlock) {
+    for (int64_t base = 0; base < I.chunks; base += kClBlock) {  // (the same trips for every thread: all lanes active at the scan, as its DPP steps need)
         const int64_t i = base + threadIdx.x;
-        const int v = i < I.chunks ? cc[i] : 0;
-        int incl = v;  // inclusive scan of the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) s_wave[w] = incl;
+        unsigned before[1] = {i < I.chunks ? (unsigned)cc[i] : 0u}, total[1];  // (counts: >= 0, a frame's sum below 2^31)
+        block_excl_scan<1, kClBlock / 64>(before, s_wave, total);
+        if (i < I.chunks) cc[i] = s_carry + (int32_t)before[0];
         __syncthreads();
-        int before = s_carry, total = 0;
-        for (int k = 0; k < kClBlock / 64; ++k) {
-            before += k < w ? s_wave[k] : 0;
-            total += s_wave[k];
-        }
-        if (i < I.chunks) cc[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry += total;
-        __syncthreads();
+        if (threadIdx.x == 0) s_carry += (int32_t)total[0];  // (read again behind the two barriers of the next trip's scan)
     }
     if (threadIdx.x == 0 && n_clusters) n_clusters[f] = s_carry;
 }

@@ -12,6 +12,7 @@
 
 #include "../../include/pwpp.h"
 #include "pwpp_dev.h"
+#include "pwpp_wave.h"  // lane_id, wave_id and every cross-lane primitive
 
 // (PWPP_LAYOUT_ROW_MAJOR / _COL_MAJOR / _FIELDS: include/pwpp.h)
 
@@ -20,20 +21,6 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // small helpers
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-__device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the floats of point i as they lie in the input (the sensor's frame)
 __device__ __forceinline__ void load_point_raw(const PwppFrameDesc &fd, int i, float &x, float &y, float &z, float &w) {
     if (fd.layout == PWPP_LAYOUT_ROW_MAJOR) {

@@ -25,6 +25,7 @@
 
 #include "pwpp_dev.h"  // the launcher's prototype
 #include "pwpp_evidence.h"
+#include "pwpp_wave.h"
 
 namespace {
 constexpr int kBlock = 256;
@@ -69,24 +70,17 @@ __device__ inline EvidLane evid_lane(const EvidCall &C, const int32_t *label_f, 
     return L;
 }
 
-// The lanes of a wave that hold the same row become one: the first of them hands the group's counters and sum to `add`.  Every
-// lane of the wave calls it (is_row = false: the lane holds no row); `pending` is the same in all of them, so the loop ends for
-// all at once.  |E| <= 2^15, so a wave's sum stays in an int32.
+// The lanes of a wave that hold the same row become one (wave_for_each_group, pwpp_wave.h; every lane of the wave calls it, is_row
+// = false: the lane holds no row): the first of them hands the group's counters and sum to `add`.  |E| <= 2^15, so a wave's sum
+// stays in an int32.
 template <class Add>
 __device__ inline void wave_rows(const EvidLane &L, Add add) {
-    const unsigned lane = threadIdx.x & 63u;
-    uint64_t pending = __ballot(L.is_row);
     const uint64_t m_landed = __ballot(L.landed), m_occupied = __ballot(L.occupied), m_free = __ballot(L.free_);
-    for (int it = 0; it < 64 && pending != 0; ++it) {
-        const int lead = __ffsll((unsigned long long)pending) - 1;
-        const int32_t r = __shfl(L.row, lead);
-        const uint64_t same = __ballot(L.is_row && L.row == r) & pending;
-        int32_t s = (L.landed && ((same >> lane) & 1ull)) ? L.E : 0;
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-        if ((int)lane == lead)
-            add(r, (int32_t)__popcll(same), (int32_t)__popcll(same & m_landed), (int32_t)__popcll(same & m_occupied), (int32_t)__popcll(same & m_free), (int64_t)s);
-        pending &= ~same;
-    }
+    wave_for_each_group(L.row, L.is_row, [&](int lead, unsigned long long same, bool mine) {
+        const int32_t s = wave_sum<int32_t>(L.landed && mine ? L.E : 0);
+        if (lane_id() == lead)  // (a lane of the group: L.row is the group's row)
+            add(L.row, (int32_t)__popcll(same), (int32_t)__popcll(same & m_landed), (int32_t)__popcll(same & m_occupied), (int32_t)__popcll(same & m_free), (int64_t)s);
+    });
 }
 
 __device__ inline void row_add(PwppClusterEvidence *row, int32_t cells, int32_t landed, int32_t occupied, int32_t free_, int64_t sum) {

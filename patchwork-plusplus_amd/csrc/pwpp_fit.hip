@@ -56,17 +56,9 @@ constexpr int kPPT = 8;  // points per lane held in registers
 // ------------------------------------------------------------------------------------------
 // row = G consecutive lanes of a wave working on one patch
 // ------------------------------------------------------------------------------------------
-// Cross-lane primitives.  The four steps inside a 16-lane DPP row are register-to-register
-// (v_*_dpp quad_perm / row_half_mirror / row_mirror, ~8 cycles each); 16 <-> 16 goes through
-// ds_swizzle(SWAP,16) and the two 32-lane halves are combined with v_readlane + scalar ALU.
+// Cross-lane primitives, on the controls of pwpp_wave.h.  The four steps inside a 16-lane DPP row are register-to-register;
+// 16 <-> 16 goes through ds_swizzle(SWAP,16) and the two 32-lane halves are combined with v_readlane + scalar ALU.
 // A 64-lane all-reduce is ~8 instructions instead of 6 dependent ds_bpermute round trips.
-#define PWPP_DPP(x, ctrl) __builtin_amdgcn_update_dpp(0, (x), (ctrl), 0xF, 0xF, true)
-#define PWPP_DPP_XOR1 0xB1   // quad_perm [1,0,3,2]
-#define PWPP_DPP_XOR2 0x4E   // quad_perm [2,3,0,1]
-#define PWPP_DPP_HMIR 0x141  // row_half_mirror
-#define PWPP_DPP_MIR 0x140   // row_mirror
-#define PWPP_SWZ16 0x401F    // ds_swizzle BITMASK_PERM xor 16
-
 template <int G>
 struct Row {
     static_assert(G == 8 || G == 16 || G == 32 || G == 64, "row width");
@@ -111,11 +103,7 @@ struct Row {
             case 3: tl = PWPP_DPP(lo, PWPP_DPP_MIR); th = PWPP_DPP(hi, PWPP_DPP_MIR); break;
             default: tl = __builtin_amdgcn_ds_swizzle(lo, PWPP_SWZ16); th = __builtin_amdgcn_ds_swizzle(hi, PWPP_SWZ16); break;
         }
-        // the two moved halves form the register pair of ONE 64-bit add (v_lshl_add_u64); written with
-        // shifts and ORs the compiler splits it into two 64-bit adds plus a move
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const v2i pair = {tl, th};
-        return v + __builtin_bit_cast(long long, pair);
+        return v + dpp_pair_i64(tl, th);  // (the two moved halves as the register pair of ONE 64-bit add)
     }
     // ---- sixteen 64-bit row sums at once, as a reduce-SCATTER ---------------------------------------
     // sum_i64 is a butterfly per value: every lane ends up with every total (16 x log2(G) exchanges).
@@ -135,12 +123,10 @@ struct Row {
         if (KIND == 0) { tl = PWPP_DPP(lo, PWPP_DPP_HMIR); th = PWPP_DPP(hi, PWPP_DPP_HMIR); }
         else if (KIND == 1) { tl = PWPP_DPP(lo, PWPP_DPP_XOR1); th = PWPP_DPP(hi, PWPP_DPP_XOR1); }
         else if (KIND == 2) { tl = PWPP_DPP(lo, PWPP_DPP_XOR2); th = PWPP_DPP(hi, PWPP_DPP_XOR2); }
-        else if (KIND == 3) { tl = __builtin_amdgcn_ds_swizzle(lo, 0x201F); th = __builtin_amdgcn_ds_swizzle(hi, 0x201F); }  // xor 8
+        else if (KIND == 3) { tl = __builtin_amdgcn_ds_swizzle(lo, PWPP_SWZ8); th = __builtin_amdgcn_ds_swizzle(hi, PWPP_SWZ8); }
         else if (KIND == 4) { tl = __builtin_amdgcn_ds_swizzle(lo, PWPP_SWZ16); th = __builtin_amdgcn_ds_swizzle(hi, PWPP_SWZ16); }
         else { const int a = (lane_id() ^ 32) << 2; tl = __builtin_amdgcn_ds_bpermute(a, lo); th = __builtin_amdgcn_ds_bpermute(a, hi); }
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const v2i pair = {tl, th};
-        return __builtin_bit_cast(long long, pair);
+        return dpp_pair_i64(tl, th);
     }
     __device__ static __forceinline__ long long reduce16_scatter(const long long (&v)[16], int &slot) {
         static_assert(G == 64 || G == 16, "rows of 64 or 16 lanes");  // (16: the first four steps are the whole reduction)
@@ -195,19 +181,14 @@ struct Row {
     // exclusive prefix sum over the row; total = row sum
     __device__ static __forceinline__ unsigned excl_scan(unsigned v, unsigned &total) {
         if constexpr (G == 16 || G == 64) {
-            // DPP scan: row_shr 1, 2, 4, 8 inside the 16-lane rows (lanes without a source add 0), then for a
-            // 64-lane row the two broadcasts of a row's last lane into the rows behind it -- six adds and no LDS
-            // round trips, where the shuffle version below waits for a ds_bpermute at every step
-            int x = (int)v;
-            x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);
-            x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);
-            x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);
-            x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);
+            // the DPP scans of pwpp_wave.h: four adds for a 16-lane row, six for the wave, and no LDS round trips,
+            // where the shuffle version below waits for a ds_bpermute at every step
+            int x;
             if constexpr (G == 64) {
-                x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
-                x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
+                x = (int)wave_incl_scan(v);
                 total = (unsigned)__builtin_amdgcn_readlane(x, 63);
             } else {
+                x = row16_incl_scan((int)v);
                 total = (unsigned)__shfl(x, G - 1, G);
             }
             return (unsigned)x - v;
@@ -224,13 +205,8 @@ struct Row {
     }
 };
 
+// (here and not in pwpp_wave.h: it is the DPP minimum of Row<64>, which stays in this file)
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) { return ~Row<64>::min_u32(~v); }
-// hand-over through LDS between the lanes of ONE wave (no workgroup barrier)
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // compare-exchange of two keys, ascending
 __device__ __forceinline__ void ce(unsigned &a, unsigned &b) {
@@ -719,10 +695,9 @@ __device__ __forceinline__ __int128 join_halves(long long lo, long long hi) { re
 // Lane distances 1, 2 (quad_perm), 4 (row_shl / row_shr under bank masks), 8 (row_ror:8), mirrors of 4, 8, 16 lanes (quad_perm [3,2,1,0],
 // row_half_mirror, row_mirror) are DPP moves inside the row -- 13 cross-lane steps of four registers and 8 in-lane ones, ~250 dependent-
 // chain-short VALU instructions where the extraction of the 20 lowest took 20 rounds of ~30 with a row reduction each (round 6).
-#define PWPP_DPPU(x, ctrl) ((unsigned)__builtin_amdgcn_update_dpp(0, (int)(x), (ctrl), 0xF, 0xF, true))
 __device__ __forceinline__ unsigned dpp_lane_xor4(unsigned x) {
-    int t = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x104 /* row_shl:4 */, 0xF, 0x5, false);  // lanes 0-3, 8-11 <- lane + 4
-    t = __builtin_amdgcn_update_dpp(t, (int)x, 0x114 /* row_shr:4 */, 0xF, 0xA, false);           // lanes 4-7, 12-15 <- lane - 4
+    int t = __builtin_amdgcn_update_dpp((int)x, (int)x, PWPP_DPP_SHL4, 0xF, 0x5, false);  // lanes 0-3, 8-11 <- lane + 4
+    t = __builtin_amdgcn_update_dpp(t, (int)x, PWPP_DPP_SHR4, 0xF, 0xA, false);           // lanes 4-7, 12-15 <- lane - 4
     return (unsigned)t;
 }
 __device__ __forceinline__ unsigned cex_keep(unsigned x, unsigned p, bool keep_min) { return keep_min ? (p < x ? p : x) : (p > x ? p : x); }
@@ -753,13 +728,13 @@ __device__ __forceinline__ void row16_sort64(unsigned &k0, unsigned &k1, unsigne
 #define PWPP_MV_X1(x) PWPP_DPPU(x, PWPP_DPP_XOR1)
 #define PWPP_MV_X2(x) PWPP_DPPU(x, PWPP_DPP_XOR2)
 #define PWPP_MV_X4(x) dpp_lane_xor4(x)
-#define PWPP_MV_X8(x) PWPP_DPPU(x, 0x128 /* row_ror:8 */)
+#define PWPP_MV_X8(x) PWPP_DPPU(x, PWPP_DPP_ROR8)
     const bool b0 = (l & 1) == 0, b1 = (l & 2) == 0, b2 = (l & 4) == 0, b3 = (l & 8) == 0;
     // pairs of lanes (8 elements)
     PWPP_MIRROR_STEP(PWPP_DPP_XOR1, b0)
     in_lane();
     // quads (16)
-    PWPP_MIRROR_STEP(0x1B /* quad_perm [3,2,1,0] */, b1)
+    PWPP_MIRROR_STEP(PWPP_DPP_QMIR, b1)
     PWPP_XOR_STEP(PWPP_MV_X1, b0)
     in_lane();
     // eights (32)
@@ -792,7 +767,7 @@ __device__ __forceinline__ void row16_clean64(unsigned &k0, unsigned &k1, unsign
         k2 = cex_keep(k2, p2, keep);
         k3 = cex_keep(k3, p3, keep);
     };
-    xstep([](unsigned x) { return PWPP_DPPU(x, 0x128 /* row_ror:8 */); }, b3);
+    xstep([](unsigned x) { return PWPP_DPPU(x, PWPP_DPP_ROR8); }, b3);
     xstep([](unsigned x) { return dpp_lane_xor4(x); }, b2);
     xstep([](unsigned x) { return PWPP_DPPU(x, PWPP_DPP_XOR2); }, b1);
     xstep([](unsigned x) { return PWPP_DPPU(x, PWPP_DPP_XOR1); }, b0);
@@ -1915,7 +1890,7 @@ __device__ void reduce_and_fit(FitShared &sh, const M &m, int shift, float ox, f
     const int wv = wave_id(), ln = lane_id();
 #pragma unroll
     for (int k = 0; k < 22; ++k) {
-        const long long t = wave_sum_i64(v[k]);
+        const long long t = wave_sum(v[k]);
         if (ln == 0) sh.part[wv][k] = t;
     }
     __syncthreads();
@@ -1994,7 +1969,7 @@ __device__ double block_lpr(FitShared &sh, const PatchRef &pts, bool use_cutoff,
         if (wv == 0) {
             const unsigned c0 = sh.hist[4 * ln], c1 = sh.hist[4 * ln + 1], c2 = sh.hist[4 * ln + 2], c3 = sh.hist[4 * ln + 3];
             const unsigned s = c0 + c1 + c2 + c3;
-            unsigned incl = s;
+            unsigned incl = s;  // (the shuffle scan, not wave_incl_scan: this kernel's instruction stream is not to move)
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
                 const unsigned t = __shfl_up(incl, o, 64);

@@ -16,6 +16,7 @@
 
 #include "pwpp_dev.h"  // the launchers' prototypes
 #include "pwpp_hull.h"
+#include "pwpp_wave.h"
 
 namespace {
 
@@ -36,12 +37,7 @@ __global__ __launch_bounds__(kHullBlock) void k_hull_offsets(int max_hulls, uint
         const int r = base + lane;
         const bool in = r < max_hulls;  // (base + 63 < 2^24 + 64: no overflow)
         const uint32_t v = in ? frame[(size_t)r * PWPP_HULL_ACC_WORDS + PWPP_HULL_ACC_POINTS] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d, 64);
-            incl += lane >= d ? o : 0u;
-        }
+        const uint32_t incl = wave_incl_scan(v);  // (one whole wave, no lane has left: all 64 active)
         if (in) frame[(size_t)r * PWPP_HULL_ACC_WORDS + PWPP_HULL_ACC_FIRST] = carry + incl - v;
         carry += __shfl(incl, 63, 64);
     }
@@ -76,15 +72,6 @@ __global__ __launch_bounds__(kHullBlock) void k_hull_rows_lane(int64_t rows, Pwp
     hull_store_row(hulls + (size_t)i * PWPP_HULL_ROW_WORDS, out);
 }
 
-__device__ __forceinline__ unsigned long long hull_wave_min(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // vertices: may be null (the lists are not asked for: the hull lives in LDS alone)
 __global__ __launch_bounds__(kHullBlock) void k_hull_rows_wave(PwppHullRows R, double x0, double y0, uint32_t *hulls, int32_t *vertices, int max_vertices) {
     __shared__ int32_t s_v[2 * PWPP_HULL_MAX_VERTICES];
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(kHullBlock) void k_hull_rows_wave(PwppHullRows R, d
     }
     pwpp_hull_pt start = PWPP_HULL_KEY_NO_MIN;
     for (int64_t k = lane; k < in.n_cand; k += kHullBlock) start = in.cand[k] < start ? in.cand[k] : start;
-    start = hull_wave_min(start);
+    start = wave_min(start);
     pwpp_hull_pt c = start, prev = start;
     for (int64_t step = 0; step < in.n_cand; ++step) {  // (a hull has at most n_cand vertices)
         pwpp_hull_march_add(M, prev, c);
@@ -121,11 +108,7 @@ __global__ __launch_bounds__(kHullBlock) void k_hull_rows_wave(PwppHullRows R, d
             const pwpp_hull_pt b = in.cand[k];
             best = pwpp_hull_beats(c, best, b) ? b : best;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const pwpp_hull_pt o = __shfl_xor(best, d, 64);
-            best = pwpp_hull_beats(c, best, o) ? o : best;
-        }
+        best = wave_reduce(best, [c](pwpp_hull_pt best, pwpp_hull_pt o) { return pwpp_hull_beats(c, best, o) ? o : best; });
         prev = c, c = best;
         if (c == start) break;
     }
@@ -144,15 +127,14 @@ __global__ __launch_bounds__(kHullBlock) void k_hull_rows_wave(PwppHullRows R, d
         const PwppHullEdge E = pwpp_hull_edge_of(s_v, M.n, e);
         if (pwpp_hull_edge_takes(best.WH, best.L2, best.i, E.WH, E.L2, E.i)) best = E;
     }
-    unsigned long long wh_lo = (unsigned long long)best.WH, wh_hi = (unsigned long long)(best.WH >> 64), l2 = best.L2;
-    int bi = best.i;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o_lo = __shfl_xor(wh_lo, d, 64), o_hi = __shfl_xor(wh_hi, d, 64), o_l2 = __shfl_xor(l2, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        const unsigned __int128 mine = ((unsigned __int128)wh_hi << 64) | wh_lo, theirs = ((unsigned __int128)o_hi << 64) | o_lo;
-        if (pwpp_hull_edge_takes(mine, l2, bi, theirs, o_l2, oi)) wh_lo = o_lo, wh_hi = o_hi, l2 = o_l2, bi = oi;
-    }
+    struct EdgeKey {  // what pwpp_hull_edge_takes orders the edges by (32 bytes: the four bytes of padding behind `i` move with it)
+        unsigned long long wh_lo, wh_hi, l2;
+        int i;
+    };
+    const int bi = wave_reduce(EdgeKey{(unsigned long long)best.WH, (unsigned long long)(best.WH >> 64), best.L2, best.i}, [](EdgeKey m, EdgeKey o) {
+                       const unsigned __int128 mine = ((unsigned __int128)m.wh_hi << 64) | m.wh_lo, theirs = ((unsigned __int128)o.wh_hi << 64) | o.wh_lo;
+                       return pwpp_hull_edge_takes(mine, m.l2, m.i, theirs, o.l2, o.i) ? o : m;
+                   }).i;
     if (bi >= 0 && best.i == bi) {  // (one lane: edge bi was dealt to lane bi % 64, and is that lane's best)
         pwpp_hull_row(in.points, M, &best, x0, y0, out);
         hull_store_row(row, out);

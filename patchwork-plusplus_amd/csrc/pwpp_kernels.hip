@@ -74,23 +74,7 @@ __device__ __forceinline__ double czm_atan2(double y, double x) {
     return atan2(y, x);
 }
 
-// Cross-lane moves on the VALU (DPP) instead of through the LDS crossbar (ds_bpermute): lane i reads lane
-// i - 1 of the wave (lane 0 gets `first`), and the inclusive prefix sum of a wave in six adds
-// (row_shr 1/2/4/8 inside the 16-lane rows, then the rows' last lanes broadcast into the rows behind).
-__device__ __forceinline__ unsigned wave_prev_lane(unsigned x, unsigned first) {
-    return (unsigned)__builtin_amdgcn_update_dpp((int)first, (int)x, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-}
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v) {
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);  // row_bcast:15
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);  // row_bcast:31
-    return (unsigned)x;
-}
-
+// (wave_prev_lane, wave_incl_scan and the other cross-lane primitives: pwpp_wave.h)
 // Consecutive points of a scan mostly fall into the same bin, so a wave's LDS atomics pile up
 // on one address (PMC: 78 % of the LDS cycles of k_czm_bin were bank-conflict cycles).  Lanes
 // are grouped into runs of equal code; only the first lane of a run touches the LDS counter,
@@ -300,7 +284,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_czm_bin(PwppBatch Bt) {  // (eigh
         const unsigned c = s_hist[b];
         if (c) atomicAdd(&gcount[b], c);  // one global atomic per non-empty part per 1024 points
     }
-    dropped = wave_sum_u32(dropped);
+    dropped = wave_sum(dropped);
     if (lane_id() == 0 && dropped) atomicAdd((unsigned *)&Bt.results[f].n_dropped, dropped);
 }
 
@@ -711,7 +695,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_czm_bin_scatter(PwppBatch Bt, int
             if (b < NB) s_cnt[b] = base[q];
         }
     }
-    dropped = wave_sum_u32(dropped);
+    dropped = wave_sum(dropped);
     if (lane_id() == 0 && dropped) atomicAdd((unsigned *)&Bt.results[f].n_dropped, dropped);
     __syncthreads();
     probe();  // 3: ranges reserved
@@ -1241,72 +1225,6 @@ __global__ __launch_bounds__(64) void k_gle_tgr_seq(PwppBatch Bt) {
 // Every double sum keeps the reference's summation order (sequential over <= one ring).
 // ------------------------------------------------------------------------------------------
 constexpr int kGlePer = PWPP_MAX_BINS / kBlock;  // consecutive bins per thread, largest model
-// the largest of the lanes' values in 0..255: a binary search over the bits with ballots (scalar work, no cross-lane data path)
-__device__ __forceinline__ int wave_max_u8(int v) {
-    int cur = 0;
-#pragma unroll
-    for (int bit = 7; bit >= 0; --bit) {
-        const int cand = cur | (1 << bit);
-        if (__ballot(v >= cand)) cur = cand;
-    }
-    return cur;
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-// Sum over the wave in butterfly order (quad_perm xor 1, xor 2, row_half_mirror, row_mirror, then the four rows): ONLY for sums
-// that are exact in every order (k_gle_tgr's first pass over a history).  The result is wave-uniform.
-__device__ __forceinline__ double wave_sum_f64_any_order(double v) {
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    v += dpp_f64<0x141>(v);
-    v += dpp_f64<0x140>(v);
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    double r[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, 16 * k), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 16 * k);
-        r[k] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-    }
-    return (r[0] + r[1]) + (r[2] + r[3]);
-}
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-template <int K>
-__device__ __forceinline__ void block_excl_scan(unsigned v[K], unsigned (*s_wave)[K], unsigned total[K]) {
-    // v[q]: this thread's sum of quantity q; returns the exclusive prefix over threads in v, block totals in total
-    const int ln = lane_id(), wv = wave_id();
-    unsigned incl[K];
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        incl[q] = wave_incl_scan(v[q]);
-        if (ln == 63) s_wave[wv][q] = incl[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        unsigned before = 0, all = 0;
-        for (int w = 0; w < kBlock / 64; ++w) {
-            const unsigned t = s_wave[w][q];
-            if (w < wv) before += t;
-            all += t;
-        }
-        v[q] = incl[q] - v[q] + before;
-        total[q] = all;
-    }
-    __syncthreads();
-}
 
 // LAT (a few dozen frames: every workgroup has a CU and its 160 KB of LDS to itself): the staging tile of
 // the threshold statistics holds a whole 1000-entry history per row, so each of the two passes is ONE
@@ -1491,10 +1409,10 @@ __global__ __launch_bounds__(kBlock) void k_gle_tgr(PwppBatch Bt) {
         if ((d & 0x7f) == 5) s_ring_cand[ci] = 1u;  // benign race: all writers store 1
     }
     {
-        const int wave_last = (int)wave_max_i32(my_last);
+        const int wave_last = wave_max(my_last);
         if (lane_id() == 0 && wave_last >= 0) atomicMax(&s_last_patch, wave_last);
         unsigned v[2] = {a_patch, a_push}, tot[2];
-        block_excl_scan<2>(v, reinterpret_cast<unsigned(*)[2]>(&s_wave[0][0]), tot);
+        block_excl_scan<2, kBlock / 64>(v, reinterpret_cast<unsigned(*)[2]>(&s_wave[0][0]), tot);
         unsigned p_patch = v[0], p_push = v[1];
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
@@ -1652,7 +1570,7 @@ __global__ __launch_bounds__(kBlock) void k_gle_tgr(PwppBatch Bt) {
         q4[3] += nt[j];
     }
     unsigned tot4[4];
-    block_excl_scan<4>(q4, s_wave, tot4);
+    block_excl_scan<4, kBlock / 64>(q4, s_wave, tot4);
     {
         unsigned run[4] = {q4[0], q4[1], q4[2], q4[3]};
 #pragma unroll
@@ -2068,7 +1986,7 @@ __global__ __launch_bounds__(kEmitBlock, 8) void k_emit(PwppBatch Bt, unsigned l
             unsigned c = 0;
             const uint32_t *w = reinterpret_cast<const uint32_t *>(area);
             for (unsigned i = threadIdx.x; i < (nbytes >> 2); i += kEmitBlock) c += (unsigned)__popc(w[i]);
-            return (unsigned)__builtin_amdgcn_readfirstlane((int)wave_sum_u32(c));
+            return (unsigned)__builtin_amdgcn_readfirstlane((int)wave_sum(c));
         };
         unsigned g_before = 0, next_b = 0;  // ground points in the blocks [0, next_b)
         const unsigned nb_end = nb < end_block ? nb : end_block;
@@ -2333,6 +2251,8 @@ __device__ __forceinline__ bool ord_bucket_sort(Load load, Store store, unsigned
         clo = c < clo ? c : clo;
         chi = c > chi ? c : chi;
     }
+    // (the butterfly of pwpp_wave.h, kept on its own text: as a wave_reduce over a struct of the four the compiler schedules
+    // k_order_sublists<256, 4096, 256> differently, and the estimate path's instruction streams are not to move)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const unsigned a = (unsigned)__shfl_xor((int)zlo, o, 64), b = (unsigned)__shfl_xor((int)zhi, o, 64);
@@ -2646,7 +2566,7 @@ __global__ __launch_bounds__(kLabelBlock) void k_label_tiles(PwppBatch Bt) {
     const int64_t lo = fd.base, end = fd.base + fd.n;
     unsigned gm, nm;
     label_masks(Bt.labels, (lo & ~(int64_t)15) + (int64_t)t * PWPP_LABEL_TILE + 16 * threadIdx.x, lo, end, gm, nm);
-    const unsigned s = wave_sum_u32((unsigned)__popc(gm) | ((unsigned)__popc(nm) << 16));  // (at most 4096 each: no carry)
+    const unsigned s = wave_sum((unsigned)__popc(gm) | ((unsigned)__popc(nm) << 16));  // (at most 4096 each: no carry)
     if (lane_id() == 0) s_tot[wave_id()] = s;
     __syncthreads();
     if (threadIdx.x == 0) Bt.label_tiles[(size_t)f * Bt.label_tile_stride + t] = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
@@ -2672,8 +2592,8 @@ __global__ __launch_bounds__(kLabelBlock) void k_label_compact(PwppBatch Bt) {
         gb += c & 0xffffu;
         nb += c >> 16;
     }
-    gb = wave_sum_u32(gb);
-    nb = wave_sum_u32(nb);
+    gb = wave_sum(gb);
+    nb = wave_sum(nb);
     const int64_t p0 = tile0 + (int64_t)w * 1024 + 16 * L;
     unsigned gm, nm;
     label_masks(Bt.labels, p0, lo, end, gm, nm);
@@ -3185,41 +3105,9 @@ __device__ __forceinline__ bool box_point(const PwppObstacleScan &S, const float
     return true;
 }
 
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = __shfl_xor(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// The lanes of a wave that still hold a contribution (`todo`, wave-uniform) and name the row of the first of them: `mine` for the
-// caller's lane, the lanes taken off `todo`.  Every lane of the wave calls this together.  Returns that first lane.
-__device__ __forceinline__ int box_next_row(unsigned long long &todo, bool counted, int row, bool &mine) {
-    const int leader = __ffsll((long long)todo) - 1;
-    mine = counted && row == __shfl(row, leader, 64);
-    todo &= ~__ballot(mine);
-    return leader;
-}
-
 // First pass: the six integer sums of every row (pwpp_boxes.h), 64-bit adds.  COMBINE false: every counted lane adds to its row.
 // COMBINE true: consecutive entries mostly name one row, so the lanes of a wave that name the same row are summed first and one
-// lane adds for them -- at most 64 rounds, one per distinct row of the wave; integer sums, so the same bytes.
+// lane adds for them (wave_for_each_group, pwpp_wave.h: one round per distinct row of the wave); integer sums, so the same bytes.
 template <bool COMBINE>
 __global__ __launch_bounds__(kObBlock) void k_box_moments(PwppObstacleScan S, PwppBoxRows R) {
     __shared__ float4 s_zt[8];
@@ -3242,17 +3130,13 @@ __global__ __launch_bounds__(kObBlock) void k_box_moments(PwppObstacleScan S, Pw
         atomicAdd(sums + 5, qy * qy);
         return;
     }
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(counted);
-    for (int round = 0; round < 64 && todo; ++round) {
-        bool mine;
-        const int leader = box_next_row(todo, counted, row, mine);
+    wave_for_each_group(row, counted, [&](int leader, unsigned long long, bool mine) {
         const uint32_t n = wave_sum<uint32_t>(mine ? 1u : 0u);  // (64 lanes of at most 2^20 + 1: below 2^27)
         const uint32_t sx = wave_sum<uint32_t>(mine ? (uint32_t)qx : 0u), sy = wave_sum<uint32_t>(mine ? (uint32_t)qy : 0u);
         const unsigned long long sxx = wave_sum<unsigned long long>(mine ? qx * qx : 0ull);
         const unsigned long long sxy = wave_sum<unsigned long long>(mine ? qx * qy : 0ull);
         const unsigned long long syy = wave_sum<unsigned long long>(mine ? qy * qy : 0ull);
-        if (lane == leader) {  // (a counted lane: `sums` is its row)
+        if (lane_id() == leader) {  // (a counted lane: `sums` is its row)
             atomicAdd(sums + 0, (unsigned long long)n);
             atomicAdd(sums + 1, (unsigned long long)sx);
             atomicAdd(sums + 2, (unsigned long long)sy);
@@ -3260,7 +3144,7 @@ __global__ __launch_bounds__(kObBlock) void k_box_moments(PwppObstacleScan S, Pw
             atomicAdd(sums + 4, sxy);
             atomicAdd(sums + 5, syy);
         }
-    }
+    });
 }
 
 // Second pass: the rows' axes stand in R.boxes (k_box_solve); minima and maxima of the keys of p, q, hgt and z.  COMBINE as above.
@@ -3290,45 +3174,24 @@ __global__ __launch_bounds__(kObBlock) void k_box_extents(PwppObstacleScan S, Pw
         }
         return;
     }
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(counted);
-    for (int round = 0; round < 64 && todo; ++round) {
-        bool mine;
-        const int leader = box_next_row(todo, counted, row, mine);
+    wave_for_each_group(row, counted, [&](int leader, unsigned long long, bool mine) {
         uint32_t lo[4], hi[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            lo[j] = wave_min(mine ? k[j] : PWPP_BOX_KEY_NO_MIN);
-            hi[j] = wave_max(mine ? k[j] : PWPP_BOX_KEY_NO_MAX);
+            lo[j] = wave_min<uint32_t>(mine ? k[j] : PWPP_BOX_KEY_NO_MIN);
+            hi[j] = wave_max<uint32_t>(mine ? k[j] : PWPP_BOX_KEY_NO_MAX);
         }
-        if (lane == leader) {
+        if (lane_id() == leader) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 atomicMin(keys + 2 * j, lo[j]);
                 atomicMax(keys + 2 * j + 1, hi[j]);
             }
         }
-    }
+    });
 }
 
 // ---- obstacle hulls (pwpp_hull_obstacles): two more passes over the same scan, by the same rule of a row (box_point) ---------------
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // the lane's entry as a point of a hull row: row and packed point
 __device__ __forceinline__ bool hull_point(const PwppObstacleScan &S, const float4 *s_zt, const ScanEntry &t, const PwppHullRows &R, int &row, long long &qx, long long &qy) {
     const PwppBoxRows B = {R.label, R.max_hulls, nullptr, nullptr};
@@ -3351,19 +3214,15 @@ __global__ __launch_bounds__(kObBlock) void k_hull_extremes(PwppObstacleScan S, 
     uint32_t *acc = R.acc + ((size_t)t.fr * (size_t)R.max_hulls + (size_t)(counted ? row : 0)) * PWPP_HULL_ACC_WORDS;
     unsigned long long k[4] = {0ull, 0ull, 0ull, 0ull};
     if (counted) pwpp_hull_keys(qx, qy, k);
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(counted);
-    for (int round = 0; round < 64 && todo; ++round) {
-        bool mine;
-        const int leader = box_next_row(todo, counted, row, mine);
-        const uint32_t n = (uint32_t)__popcll(__ballot(mine));
+    wave_for_each_group(row, counted, [&](int leader, unsigned long long same, bool mine) {
+        const uint32_t n = (uint32_t)__popcll(same);
         unsigned long long lo[4], hi[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            lo[j] = wave_min64(mine ? k[j] : PWPP_HULL_KEY_NO_MIN);
-            hi[j] = wave_max64(mine ? k[j] : PWPP_HULL_KEY_NO_MAX);
+            lo[j] = wave_min<unsigned long long>(mine ? k[j] : PWPP_HULL_KEY_NO_MIN);
+            hi[j] = wave_max<unsigned long long>(mine ? k[j] : PWPP_HULL_KEY_NO_MAX);
         }
-        if (lane == leader) {  // (a counted lane: `acc` is its row)
+        if (lane_id() == leader) {  // (a counted lane: `acc` is its row)
             unsigned long long *keys = reinterpret_cast<unsigned long long *>(acc);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -3372,7 +3231,7 @@ __global__ __launch_bounds__(kObBlock) void k_hull_extremes(PwppObstacleScan S, 
             }
             atomicAdd(acc + PWPP_HULL_ACC_POINTS, n);
         }
-    }
+    });
 }
 
 // Second pass: the rows' keys are final and k_hull_offsets has laid the rows of a frame out in its part of the arena, `points`
@@ -3394,12 +3253,8 @@ __global__ __launch_bounds__(kObBlock) void k_hull_candidates(PwppObstacleScan S
         for (int j = 0; j < 8; ++j) keys[j] = reinterpret_cast<const unsigned long long *>(acc)[j];
         keep = !pwpp_hull_inside_octagon(keys, p);
     }
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(keep);
-    for (int round = 0; round < 64 && todo; ++round) {
-        bool mine;
-        const int leader = box_next_row(todo, keep, row, mine);
-        const unsigned long long who = __ballot(mine);
+    const int lane = lane_id();
+    wave_for_each_group(row, keep, [&](int leader, unsigned long long who, bool mine) {
         uint32_t base = 0;
         if (lane == leader) base = atomicAdd(acc + PWPP_HULL_ACC_CANDS, (uint32_t)__popcll(who));
         base = __shfl(base, leader, 64);
@@ -3408,7 +3263,7 @@ __global__ __launch_bounds__(kObBlock) void k_hull_candidates(PwppObstacleScan S
             // (at < points of the row: every candidate is one of them; first + points <= the frame's counted points <= arena_stride)
             if (at < acc[PWPP_HULL_ACC_POINTS]) R.arena[(size_t)t.fr * (size_t)R.arena_stride + (size_t)acc[PWPP_HULL_ACC_FIRST] + at] = p;
         }
-    }
+    });
 }
 
 // the keys of `top` as floats, in place: empty = the quiet NaN.  Quads as in k_obstacle_fill.

@@ -29,6 +29,7 @@
 
 #include "pwpp_dev.h"  // the launcher's prototype
 #include "pwpp_match.h"
+#include "pwpp_wave.h"
 
 namespace {
 
@@ -133,10 +134,9 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_score(MatchCall C, const 
                 if (ix < C.G.nx && iy < C.G.ny && pwpp_match_landing<RECIP>(C.G, cand, ix, iy, Jx, Jy))
                     lo_x = min(lo_x, Jx), hi_x = max(hi_x, Jx), lo_y = min(lo_y, Jy), hi_y = max(hi_y, Jy);
             }
-            for (int d = 32; d > 0; d >>= 1)
-                lo_x = min(lo_x, __shfl_xor(lo_x, d)), hi_x = max(hi_x, __shfl_xor(hi_x, d)), lo_y = min(lo_y, __shfl_xor(lo_y, d)),
-                hi_y = max(hi_y, __shfl_xor(hi_y, d));
-            if ((t & 63u) == 0) box[t >> 6] = make_int4(lo_x, hi_x, lo_y, hi_y);
+            const int4 wave = wave_reduce(make_int4(lo_x, hi_x, lo_y, hi_y), [](int4 m, int4 o) { return make_int4(min(m.x, o.x), max(m.y, o.y), min(m.z, o.z), max(m.w, o.w)); });
+            lo_x = wave.x, hi_x = wave.y, lo_y = wave.z, hi_y = wave.w;
+            if (lane_id() == 0) box[wave_id()] = wave;
             __syncthreads();
             for (unsigned w = 0; w < kMatchBlock / 64; ++w)
                 lo_x = min(lo_x, box[w].x), hi_x = max(hi_x, box[w].y), lo_y = min(lo_y, box[w].z), hi_y = max(hi_y, box[w].w);

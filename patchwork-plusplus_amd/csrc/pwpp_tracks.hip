@@ -59,8 +59,10 @@ __global__ __launch_bounds__(kBlock) void k_tracks_init(TracksCall C, uint32_t *
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_link; i += stride) curr_links[i] = 0, prev_links[i] = 0;
 }
 
-// The lanes of a wave that hold the same key become one: the first of them gets their number, the others 0.  Every lane of the
-// wave calls it (valid = false: the lane holds no key); `pending` is the same in all of them, so the loop ends for all at once.
+// The lanes of a wave that hold the same key become one: the first of them gets their number, the others 0.  The group loop of
+// pwpp_wave.h under its contract, kept on its own text: as wave_for_each_group with the count in its body the compiler rotates the
+// three loops of k_tracks_count (27 scalar instructions more) and pwpp_associate_grid measured 1.4 to 3.1 % slower on 64 x 64 cells
+// in four sessions of four (profiles/wave_primitives_refactor_ab.txt).
 __device__ inline uint32_t wave_combine(uint64_t key, bool valid) {
     const unsigned lane = threadIdx.x & 63u;
     uint64_t pending = __ballot(valid);
