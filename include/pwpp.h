@@ -1735,6 +1735,98 @@ PWPP_API int pwpp_viewshed_obstacles(pwpp_handle *h, const pwpp_ground_grid *g, 
                                      int32_t *count /* may be NULL: kept */);
 PWPP_API int32_t pwpp_viewshed_units(double metres);   /* host only: the quantiser */
 
+/* ---- per-beam free space: every return's ray traced through the grid (pwpp_rasterize_beams, pwpp_beam_grid, pwpp_beam_ground) ----
+ * The two lines of sight above decide on the obstacle image whether a cell COULD be seen.  A return is stronger evidence: its whole
+ * beam, from the sensor to the point, went through empty air, so every cell under the beam has been measured empty above the beam's
+ * height at that cell.  This stage draws the beam of every endpoint cell along the visibility's digital line and reports, per crossed
+ * cell, how many beams passed and the lowest of them -- the free space behind a hedge the sensor saw over, or between two parked
+ * cars, which both lines of sight leave PWPP_OCC_UNKNOWN.  Integers only, each frame on its own, the same bytes whatever the
+ * schedule.  The upstream Patchwork++ has nothing of this kind.
+ *   rasterize_beams   the endpoints of the LAST call's beams on the grid g (flags must be 0): when, frame_first, frames, mem, the lifetime
+ *             rule of the input and the errors are those of pwpp_rasterize_ground_returns.  `which`: bit 1 selects the frame's ground
+ *             list, bit 2 its non-ground list; 0 or any other bit: PWPP_E_ARG.  hits[f][iy][ix] = the selected points that fall into
+ *             the cell, by the cell rule of pwpp_rasterize_obstacles on the same INPUT (input transforms apply); zmin = the smallest
+ *             pwpp_viewshed_units((double)z) among them, PWPP_VIEW_NO_HEIGHT where there is none.  A point whose z is a NaN is skipped
+ *             and not counted; a point outside the grid is skipped.  Integer adds and minima: a function of the input alone.
+ *             NOTE: the non-ground list also holds the points the reflected-noise removal rejected.  Their beams end BELOW the
+ *             ground -- they would clear cells the sensor never saw through -- so which = 1 is the safe default.
+ *   endpoints A cell e is an endpoint iff hits[e] >= 1 and zmin[e] != PWPP_VIEW_NO_HEIGHT; its beam has the weight hits[e] and the
+ *             height zmin[e].
+ *   origin    {ox, oy, eye} per frame, as pwpp_viewshed_grid takes it: HOST memory in both mem kinds, n_origins 1 or `frames`.  |eye| <=
+ *             2^30, so that `low` can never leave int32.
+ *   line      The points P_k, k = 0 .. n, from the origin's cell to e are those of pwpp_visibility_grid.  The beam CROSSES the interior
+ *             points P_1 .. P_{n-1}: the origin's cell holds the vehicle, the endpoint's cell the return.  An endpoint with n <= 1
+ *             crosses nothing.  Occupied cells do not stop a beam: a beam that returned did pass.
+ *   height    at a crossed cell P_k: r = clamp(zmin[e] - eye, -R, R) in 64 bits, R = PWPP_VIEW_MAX_RISE; D = 2k - 1 where r < 0, else
+ *             2k + 1 -- the end of the cell's stretch of the beam where the beam is highest, so that what the cell reports is an
+ *             upper bound over the whole cell; height = eye + ceil(r * D / (2n)), the division exact.  Every product stays below 2^37.
+ *             pwpp_beam_height(eye, z, k, n) is this rule on the host, compiled from the text the kernels are compiled from
+ *             (1 <= k < n <= 32768, |eye| <= 2^30, z a height; otherwise PWPP_VIEW_NO_HEIGHT and the error text).
+ *   passes    passes[c] = the sum of the weights of the beams that cross c, in unsigned 32-bit arithmetic (it wraps).
+ *   low       low[c] = the smallest height among those beams; PWPP_VIEW_NO_HEIGHT where passes[c] == 0.
+ *   THEOREM   For fixed k and n the height is non-decreasing in z.  So the lowest of many beams into one endpoint cell is the beam of
+ *             its lowest point, and tracing every POINT's beam from its own cell and z gives exactly these two images: hits and zmin
+ *             lose nothing.
+ *   max_range cells, Chebyshev, 0 .. 32768; 0: unlimited.  A beam is traced for k <= max_range only: a cell further than max_range
+ *             from the origin gets passes 0, low PWPP_VIEW_NO_HEIGHT and the base byte; every other cell gets exactly the unlimited
+ *             values.  Beams from beyond the range still cross the cells inside it: no endpoint is dropped by range.
+ *   occupancy (may be NULL) the base byte is occupancy_in[c], or PWPP_OCC_UNKNOWN when occupancy_in is NULL.  The output is
+ *             PWPP_OCC_FREE iff the base byte equals PWPP_OCC_UNKNOWN, and passes[c] >= min_pass (compared unsigned), and `target` is
+ *             NULL or target[c] != PWPP_VIEW_NO_HEIGHT and (int64)low[c] - (int64)target[c] <= clearance.  Everywhere else it is the
+ *             base byte verbatim, whatever its value.  THEOREMS: the FREE cells of the input are a subset of the FREE cells of the
+ *             output; no OCCUPIED or FREE byte of the input is changed.  occupancy == occupancy_in is allowed: the update in place.
+ *   THE PRICE The beam is drawn from cell to cell, not from point to point: a crossed cell can lie up to one cell away from the true
+ *             ray, and a single beam that grazes a wall's corner clears a cell the ray never entered.  min_pass >= 2 is the remedy:
+ *             two endpoint hits must agree.  `clearance` bounds how high above the ground (target) the lowest beam may have passed:
+ *             a beam three metres up says nothing about a bollard below it.
+ *   beam_ground   enqueues, on the handle's stream: pwpp_rasterize_beams(g with flags 0, which); the ground raster of
+ *             pwpp_rasterize_ground on the same grid (g->flags 0 or PWPP_GRID_GROUND_ONLY), quantised on the device by
+ *             pwpp_viewshed_units -- this is `target`; and pwpp_beam_grid.  The origins {x, y, z} in metres become {ox, oy, eye} as
+ *             pwpp_viewshed_obstacles turns them; clearance is in metres, finite and >= 0, through pwpp_viewshed_units.  occupancy_in
+ *             is the caller's (may be NULL); in PWPP_MEM_DEVICE typically the bytes pwpp_viewshed_obstacles just wrote.  hits and
+ *             zmin are returned where asked for, kept in the buffer otherwise.  The images are exactly what the three calls give one
+ *             after the other.
+ *   mem       PWPP_MEM_HOST stages every image through the handle's cluster buffer (pwpp_rasterize_beams: the ground-query staging
+ *             buffer), synchronous; PWPP_MEM_DEVICE: device memory, the int32 images 4-byte aligned and no more, the bytes byte
+ *             aligned, enqueued on the handle's stream.  PWPP_MEM_HOST_PINNED: PWPP_E_ARG.
+ *   errors    pwpp_beam_grid: PWPP_E_ARG, named before the device is touched, in this order: a null handle, hits, zmin, origin, passes
+ *             or low; nx, ny or frames < 1; nx or ny > 32768; nx * ny * frames beyond 2^31; max_range outside 0 .. 32768; min_pass <
+ *             1; clearance < 0; the number of origins; an origin outside the image; an eye outside +-2^30, naming the entry; arrays
+ *             that overlap (other than occupancy == occupancy_in); mem; in PWPP_MEM_DEVICE an int32 array below 4-byte alignment.
+ *             pwpp_beam_ground: a null handle, grid, origin, passes or low; the flags; `which`; the grid's geometry and sides; a
+ *             clearance that is not finite or negative; then as above from max_range to the overlaps, an origin that is not finite (z
+ *             included) or outside the grid; then what pwpp_rasterize_obstacles rejects of the frame range and mem; the alignment;
+ *             PWPP_E_STATE before any estimate call.
+ *   buffers   The origins where there is one per frame, in PWPP_MEM_HOST the staged images and in the chained call its intermediate
+ *             images lie in the cluster buffer: counted by pwpp_get_workspace_bytes, freed by pwpp_trim_workspace.
+ * pwpp_fuse_obstacles, pwpp_match_obstacles, pwpp_costmap_obstacles and pwpp_evidence_obstacles do not consume these bytes by
+ * themselves; feed them to pwpp_fuse_grid, pwpp_match_grid, pwpp_costmap_grid and pwpp_evidence_grid.  The same
+ * bytes for every mem, alignment and value of the option "beams_path".  With none of the functions called nothing is allocated or
+ * launched, and no result, state or timing of any other call changes. */
+#define PWPP_HAS_BEAMS 1
+#define PWPP_BEAMS_GROUND 1      /* `which`: the ground list */
+#define PWPP_BEAMS_NONGROUND 2   /* `which`: the non-ground list (with the points the reflected-noise removal rejected) */
+
+/* the endpoints of the beams of frames of the LAST estimate call -- like pwpp_rasterize_ground_returns */
+PWPP_API int pwpp_rasterize_beams(pwpp_handle *h, const pwpp_ground_grid *g, int which, int frame_first, int frames, int mem,
+                                  int32_t *hits /* [frames][ny][nx] */, int32_t *zmin /* same shape */);
+/* any images: needs a handle (stream, buffer), no estimate call -- like pwpp_viewshed_grid */
+PWPP_API int pwpp_beam_grid(pwpp_handle *h, int nx, int ny, int frames, int mem,
+                            const int32_t *hits /* [frames][ny][nx] */, const int32_t *zmin /* same shape */,
+                            const int32_t *target /* same shape, may be NULL */, const int8_t *occupancy_in /* same shape, may be NULL */,
+                            const int32_t *origin /* HOST memory, n_origins x {ox, oy, eye} */, int n_origins,
+                            int max_range /* cells, Chebyshev; 0: unlimited */, int min_pass, int clearance /* units, >= 0 */,
+                            int32_t *passes /* [frames][ny][nx] */, int32_t *low /* same shape */,
+                            int8_t *occupancy /* same shape, may be NULL, may be occupancy_in */);
+/* endpoints + ground raster + beams for frames of the LAST estimate call, one call -- like pwpp_viewshed_obstacles */
+PWPP_API int pwpp_beam_ground(pwpp_handle *h, const pwpp_ground_grid *g, int which,
+                              const double *origin_xyz /* HOST, n_origins x {x, y, z} metres */, int n_origins,
+                              int max_range, int min_pass, double clearance /* metres, >= 0 */, int frame_first, int frames, int mem,
+                              const int8_t *occupancy_in /* may be NULL */, int32_t *passes, int32_t *low,
+                              int8_t *occupancy /* may be NULL, may be occupancy_in */,
+                              int32_t *hits /* may be NULL: kept */, int32_t *zmin /* may be NULL: kept */);
+PWPP_API int32_t pwpp_beam_height(int32_t eye, int32_t z, int k, int n);   /* host only: the height of a beam at a crossed cell */
+
 /* ---- a per-frame affine transform of the input, applied while binning (pwpp_set_input_transforms) ----------------------------
  * The pipeline assumes what the reference assumes: a levelled frame centred on the sensor, z up, the ground near -sensor_height.
  * A tilted or rolled mount, several sensors in their own frames, a driver that delivers millimetres, a cloud levelled by the IMU

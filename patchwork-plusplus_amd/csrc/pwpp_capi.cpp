@@ -37,6 +37,7 @@
 #include "pwpp_terrain.h"
 #include "pwpp_tracks.h"
 #include "pwpp_viewshed.h"
+#include "pwpp_beams.h"
 #include "pwpp_visibility.h"
 
 static_assert(sizeof(pwpp_state) == sizeof(PwppStateScalar), "pwpp_state must mirror PwppStateScalar");
@@ -261,6 +262,7 @@ struct pwpp_handle {
     int distance_path = 0;          // option "distance_path": 0 = the strip's rows in LDS, outward with the early exit; 1 = global memory, every row (yardstick)
     int visibility_path = 0;        // option "visibility_path": 0 = the bit image, in LDS where it fits; 1 = count in global memory, no bit image (yardstick)
     int viewshed_path = 0;          // option "viewshed_path": 0 = what tools/viewshed_cost.py decided (pwpp_viewshed_path_of: 2 for an unlimited call, 1 under a max_range); 1 = count and block in global memory (yardstick); 2 = the bit image, in LDS where it fits, a rise fetched only where a bit is set
+    int beams_path = 0;             // option "beams_path": 0 = what tools/beams_cost.py decided (pwpp_beams_path_of: 2, which won every configuration); 1 = a lane per endpoint cell, atomics on the global images after a fill (yardstick); 2 = a workgroup per tile of 64 x 64 cells, the tile's passes and low in LDS
     int fusion_path = 0;            // option "fusion_path": 0 = the product with 1 / cell where the cell size is a power of two; 1 = always the division (yardstick)
     int elevation_path = 0;         // option "elevation_path": 0 = what tools/elevation_fusion_cost.py decided; 1 = the divisions as written (yardstick); 2 = the reciprocal of a power-of-two cell and the multiply-shift for the capped mean
     int terrain_path = 0;           // option "terrain_path": 0 = per radius what tools/terrain_cost.py decided; 1 = every lane walks its whole window (yardstick); 2 = separable, row sums first
@@ -1285,6 +1287,7 @@ constexpr PathOption kPathOptions[] = {
     {"distance_path", &pwpp_handle::distance_path, 1},
     {"visibility_path", &pwpp_handle::visibility_path, 1},
     {"viewshed_path", &pwpp_handle::viewshed_path, 2},
+    {"beams_path", &pwpp_handle::beams_path, 2},
     {"fusion_path", &pwpp_handle::fusion_path, 1},
     {"elevation_path", &pwpp_handle::elevation_path, 2},
     {"terrain_path", &pwpp_handle::terrain_path, 2},
@@ -4032,6 +4035,156 @@ int pwpp_costmap_curve(double cell, double inscribed, double radius, double deca
         curve[d] = r <= inscribed ? (uint8_t)100 : (uint8_t)(int)std::floor((double)peak * std::exp(-decay * (r - inscribed)));
     }
     return n;
+}
+
+// ---- per-beam free space: every return's beam traced from the sensor's cell, the beams that crossed a cell and the lowest of them ----
+namespace {
+static_assert(PWPP_BEAMS_EYE_MAX == (1 << 30) && PWPP_VIS_MAX_SIDE == 32768, "the limits of the messages");
+constexpr const char *kBeamsWho = "the beams take";
+
+// what both entry points check of max_range, min_pass and the clearance in units
+int beam_param_args(int max_range, int min_pass, int64_t clearance) {
+    if (max_range < 0 || max_range > PWPP_VIS_MAX_SIDE) return fail(PWPP_E_ARG, "max_range %d: 0 (unlimited) .. 32768 cells expected", max_range);
+    if (min_pass < 1) return fail(PWPP_E_ARG, "min_pass %d: at least 1 expected", min_pass);
+    if (clearance < 0) return fail(PWPP_E_ARG, "clearance %lld: at least 0 expected", (long long)clearance);
+    return PWPP_OK;
+}
+
+// ... and of the caller's arrays among each other: occupancy may be occupancy_in itself, nothing else may meet
+int beam_range_args(size_t cells, const int32_t *hits, const int32_t *zmin, const int32_t *target, const int8_t *occupancy_in, const int32_t *passes,
+                    const int32_t *low, const int8_t *occupancy) {
+    return range_args({{hits, cells * 4, "hits"}, {zmin, cells * 4, "zmin"}, {target, cells * 4, "target"}, {occupancy_in, cells, "occupancy_in"},
+                       {occupancy, cells, "occupancy"}, {passes, cells * 4, "passes"}, {low, cells * 4, "low"}},
+                      {{3, 4}}, false);
+}
+
+// (the origins first; `org`: n_origins x {ox, oy, eye}, checked.  One origin travels as arguments.)
+struct BeamSections {
+    int org, hits, zmin, target, occ_in, passes, low, occ;
+};
+void beam_out_sections(Staging &st, size_t cells, const int8_t *occupancy_in, int32_t *passes, int32_t *low, int8_t *occupancy, BeamSections &s) {
+    s.occ_in = st.add_bytes(cells, occupancy_in, Staging::kIn);
+    s.passes = st.add(cells, passes, Staging::kOut), s.low = st.add(cells, low, Staging::kOut);
+    s.occ = st.add_bytes(cells, occupancy, Staging::kOut);
+}
+int beam_launch(pwpp_handle *h, const Staging &st, const BeamSections &s, int nx, int ny, int frames, const std::vector<int32_t> &org, int max_range, int min_pass,
+                int clearance) {
+    return pwpp_launch_beam_grid(nx, ny, frames, st.dev<const int32_t>(s.hits), st.dev<const int32_t>(s.zmin), st.dev<const int32_t>(s.target),
+                                 st.dev<const int8_t>(s.occ_in), org[0], org[1], org[2], org.size() > 3 ? st.dev<const int32_t>(s.org) : nullptr, max_range, min_pass,
+                                 clearance, h->beams_path, st.dev<int32_t>(s.passes), st.dev<int32_t>(s.low), st.dev<int8_t>(s.occ), h->stream);
+}
+
+// The longest selection of a frame range of the last call: the ground list (which & 1), the non-ground list (which & 2) or both
+int longest_beam_list(const pwpp_handle *h, int which, int frame_first, int frames) {
+    int64_t longest = 0;
+    for (int f = frame_first; f < frame_first + frames; ++f) {
+        const auto &r = h->h_results.p[f];
+        longest = std::max(longest, ((which & 1) ? (int64_t)std::max(r.n_ground, 0) : 0) + ((which & 2) ? (int64_t)std::max(r.n_nonground, 0) : 0));
+    }
+    return (int)std::min<int64_t>(longest, INT32_MAX);
+}
+int beam_which_args(const pwpp_ground_grid *g, int which) {
+    if (g->flags != 0) return fail(PWPP_E_ARG, "grid flags %d: 0 expected by the beams' endpoints", g->flags);
+    if (which < 1 || which > 3) return fail(PWPP_E_ARG, "which %d: 1 (ground), 2 (non-ground) or 3 (both) expected", which);
+    return PWPP_OK;
+}
+}  // namespace
+
+// The rule for one crossed cell on the host: pwpp_beams_height, the function the kernels call.
+int32_t pwpp_beam_height(int32_t eye, int32_t z, int k, int n) {
+    if (n < 2 || k < 1 || k >= n || n > PWPP_VIS_MAX_SIDE || eye < -PWPP_BEAMS_EYE_MAX || eye > PWPP_BEAMS_EYE_MAX || z == PWPP_VIEW_NO_HEIGHT) {
+        fail(PWPP_E_ARG, "beam height at k %d of n %d, eye %d: 1 <= k < n <= 32768, |eye| <= 2^30 and a height expected", k, n, eye);
+        return PWPP_VIEW_NO_HEIGHT;
+    }
+    return pwpp_beams_height(eye, z, (uint32_t)k, (uint32_t)n);
+}
+
+// The selected index lists of the last call per cell of the grid: hits, then zmin.
+int pwpp_rasterize_beams(pwpp_handle *h, const pwpp_ground_grid *g, int which, int frame_first, int frames, int mem, int32_t *hits, int32_t *zmin) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !hits || !zmin) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!hits ? "hits image" : "zmin image"));
+    int rc = beam_which_args(g, which);
+    if (rc) return rc;
+    size_t cells = 0;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = range_args({{hits, cells * 4, "hits"}, {zmin, cells * 4, "zmin"}}, {}, false))) return rc;
+    Staging st(h, h->d_ground_stage, mem);
+    const int s_hits = st.add(cells, hits, Staging::kOut), s_zmin = st.add(cells, zmin, Staging::kOut);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    if ((rc = obstacle_scan(h, g, 0.0f, 0.0f, frame_first, frames, scan))) return rc;
+    const int lrc = pwpp_launch_beam_ends(&scan, which, longest_beam_list(h, which, frame_first, frames), st.dev<int32_t>(s_hits), st.dev<int32_t>(s_zmin), h->stream);
+    return lrc != 0 ? launch_failed(h, lrc) : st.end();
+}
+
+int pwpp_beam_grid(pwpp_handle *h, int nx, int ny, int frames, int mem, const int32_t *hits, const int32_t *zmin, const int32_t *target,
+                   const int8_t *occupancy_in, const int32_t *origin, int n_origins, int max_range, int min_pass, int clearance, int32_t *passes, int32_t *low,
+                   int8_t *occupancy) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!hits || !zmin || !origin || !passes || !low)
+        return fail(PWPP_E_ARG, "null %s", !hits ? "hits image" : (!zmin ? "zmin image" : (!origin ? "origin" : (!passes ? "passes image" : "low image"))));
+    size_t cells = 0;
+    int rc = image_args(nx, ny, frames, kBeamsWho, cells);
+    if (rc) return rc;
+    if ((rc = beam_param_args(max_range, min_pass, clearance))) return rc;
+    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
+    if ((rc = cells_inside_args(origin, n_origins, nx, ny, "origin", 3))) return rc;
+    for (int i = 0; i < n_origins; ++i)
+        if (origin[3 * i + 2] < -PWPP_BEAMS_EYE_MAX || origin[3 * i + 2] > PWPP_BEAMS_EYE_MAX)
+            return fail(PWPP_E_ARG, "origin %d: its eye %d lies outside +-2^30", i, origin[3 * i + 2]);
+    if ((rc = beam_range_args(cells, hits, zmin, target, occupancy_in, passes, low, occupancy))) return rc;
+    if ((rc = mem_args(mem, kBeamsWho))) return rc;
+    if ((rc = alignment_args(mem, {{hits, 3u, "hits image"}, {zmin, 3u, "zmin image"}, {target, 3u, "target image"}, {passes, 3u, "passes image"}, {low, 3u, "low image"}})))
+        return rc;
+    const std::vector<int32_t> org(origin, origin + 3 * (size_t)n_origins);
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    BeamSections s;
+    s.org = frame_cells_section(st, org, 3);
+    s.hits = st.add(cells, hits, Staging::kIn), s.zmin = st.add(cells, zmin, Staging::kIn), s.target = add_image(st, cells, target, false);
+    beam_out_sections(st, cells, occupancy_in, passes, low, occupancy, s);
+    return run_on_image(h, st, [&] { return beam_launch(h, st, s, nx, ny, frames, org, max_range, min_pass, clearance); });
+}
+
+// The endpoints' raster, the ground raster, the quantiser and the beams, one enqueued sequence.
+int pwpp_beam_ground(pwpp_handle *h, const pwpp_ground_grid *g, int which, const double *origin_xyz, int n_origins, int max_range, int min_pass, double clearance,
+                     int frame_first, int frames, int mem, const int8_t *occupancy_in, int32_t *passes, int32_t *low, int8_t *occupancy, int32_t *hits,
+                     int32_t *zmin) {
+    if (!h) return fail(PWPP_E_ARG, "null handle");
+    if (!g || !origin_xyz || !passes || !low) return fail(PWPP_E_ARG, "null %s", !g ? "grid" : (!origin_xyz ? "origin" : (!passes ? "passes image" : "low image")));
+    if (g->flags & ~(int32_t)PWPP_GRID_GROUND_ONLY) return fail(PWPP_E_ARG, "grid flags %d: 0 or PWPP_GRID_GROUND_ONLY", g->flags);
+    if (which < 1 || which > 3) return fail(PWPP_E_ARG, "which %d: 1 (ground), 2 (non-ground) or 3 (both) expected", which);
+    int rc = grid_geometry_args(g);  // (the origins need the grid)
+    if (rc || (rc = side_args(g->nx, g->ny, kBeamsWho))) return rc;
+    if (!(clearance >= 0.0) || !std::isfinite(clearance)) return fail(PWPP_E_ARG, "clearance %g m: finite and at least 0 expected", clearance);
+    const int32_t clear_units = pwpp_view_units(clearance);
+    if ((rc = beam_param_args(max_range, min_pass, clear_units))) return rc;
+    if ((rc = per_frame_count_args(n_origins, frames, "origins"))) return rc;
+    std::vector<int32_t> org;
+    if ((rc = frame_cells_of(g, origin_xyz, n_origins, "origin", org, 3))) return rc;  // (an eye is a quantised height: within +-2^30)
+    size_t cells = (size_t)g->nx * (size_t)g->ny * (size_t)(frames > 0 ? frames : 0);  // (the byte ranges of the overlap check; ground_grid_args names one beyond 2^31)
+    if ((rc = beam_range_args(cells, hits, zmin, nullptr, occupancy_in, passes, low, occupancy))) return rc;
+    if ((rc = ground_grid_args(h, g, frame_first, frames, mem, cells))) return rc;
+    if ((rc = alignment_args(mem, {{hits, 3u, "hits image"}, {zmin, 3u, "zmin image"}, {passes, 3u, "passes image"}, {low, 3u, "low image"}}))) return rc;
+    const int nx = g->nx, ny = g->ny;
+    Staging st(h, h->d_clusters, mem, kClusterAlign);
+    BeamSections s;
+    s.org = frame_cells_section(st, org, 3);
+    s.hits = add_image(st, cells, hits, true), s.zmin = add_image(st, cells, zmin, true);
+    const int s_ground = st.add(cells, nullptr, Staging::kKept);
+    s.target = st.add(cells, nullptr, Staging::kKept);
+    beam_out_sections(st, cells, occupancy_in, passes, low, occupancy, s);
+    if ((rc = st.begin())) return rc;
+    PwppObstacleScan scan;
+    pwpp_ground_grid ends = *g;
+    ends.flags = 0;  // (the endpoints' raster reads no flags)
+    if ((rc = obstacle_scan(h, &ends, 0.0f, 0.0f, frame_first, frames, scan))) return rc;
+    int lrc = pwpp_launch_beam_ends(&scan, which, longest_beam_list(h, which, frame_first, frames), st.dev<int32_t>(s.hits), st.dev<int32_t>(s.zmin), h->stream);
+    if (lrc != 0) return launch_failed(h, lrc);
+    rc = enqueue_on_ground(h, st, g, frame_first, frames, s_ground, -1, [&] {
+        lrc = pwpp_launch_viewshed_quantise(cells, st.dev<const float>(s_ground), nullptr, st.dev<int32_t>(s.target), nullptr, h->stream);
+        return lrc != 0 ? lrc : beam_launch(h, st, s, nx, ny, frames, org, max_range, min_pass, clear_units);
+    });
+    return rc ? rc : st.end();
 }
 
 // ---- cluster tracks: the rows of a current label image against those of the previous one, and ids that persist ------------------------

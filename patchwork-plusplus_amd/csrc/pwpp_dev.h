@@ -324,6 +324,7 @@ int pwpp_launch_ground_raster(const PwppGroundView *view, const PwppGroundGrid *
                               hipStream_t stream);
 int pwpp_launch_obstacle_raster(const PwppObstacleScan *scan, int32_t *count, float *top, int32_t *unref, hipStream_t stream);
 int pwpp_launch_ground_returns(const PwppObstacleScan *scan, int max_ground, int32_t *seen, hipStream_t stream);
+int pwpp_launch_beam_ends(const PwppObstacleScan *scan, int which, int max_entries, int32_t *hits, int32_t *zmin, hipStream_t stream);
 int pwpp_launch_point_cluster(const PwppObstacleScan *scan, const int32_t *label, int32_t *point_cluster, int64_t base_first, hipStream_t stream);
 int pwpp_launch_box_pass(int pass, int combine, const PwppObstacleScan *scan, const PwppBoxRows *rows, hipStream_t stream);
 int pwpp_launch_hull_pass(int pass, const PwppObstacleScan *scan, const PwppHullRows *rows, hipStream_t stream);
@@ -354,6 +355,11 @@ int pwpp_launch_viewshed_grid(int nx, int ny, int frames, const int32_t *count, 
                               const int32_t *seen, int min_seen, int ox, int oy, int eye, const int32_t *origins, int max_range, int path,
                               int32_t *first, int32_t *shadow, int8_t *occupancy, uint32_t *work, hipStream_t stream);
 int pwpp_launch_viewshed_quantise(size_t cells, const float *ground, const float *top, int32_t *target, int32_t *block, hipStream_t stream);
+// pwpp_beams.hip (k_beam_fill, k_beam_scatter, k_beam_finish: "beams_path" 1; k_beam_tile: 2)
+int pwpp_beams_path_of(int path);  // what "beams_path" resolves to: 1 or 2
+int pwpp_launch_beam_grid(int nx, int ny, int frames, const int32_t *hits, const int32_t *zmin, const int32_t *target, const int8_t *occ_in, int ox, int oy,
+                          int eye, const int32_t *origins, int max_range, int min_pass, int clearance, int path, int32_t *passes, int32_t *low,
+                          int8_t *occupancy, hipStream_t stream);
 // pwpp_fusion.hip
 int pwpp_launch_fuse_grid(const struct PwppFusionGeometry *G, const struct PwppFusionParams *P, int frames, const int8_t *occupancy, const double *poses,
                           int n_poses, int n_maps, const int32_t *begin, const int32_t *list, int listed, const int32_t *shift, const int16_t *map_in,

@@ -49,6 +49,7 @@
 #include "pwpp_boxes.h"
 #include "pwpp_hull.h"
 #include "pwpp_unionfind.h"
+#include "pwpp_viewshed.h"  // pwpp_view_units: the quantiser of k_beam_ends
 
 namespace {
 
@@ -3078,6 +3079,43 @@ __global__ __launch_bounds__(kObBlock) void k_ground_returns(PwppObstacleScan S,
     atomicAdd(seen + ((size_t)fr * (size_t)S.G.ny + (size_t)iy) * (size_t)S.G.nx + (size_t)ix, 1);
 }
 
+// pwpp_rasterize_beams: the endpoints of the frame's beams on the same grid -- per cell the points of the selected lists (`which`
+// bit 1: the ground list, entries [0, ng); bit 2: the non-ground list, entries [ng, ng + nn)) that fall into it, by the same cell rule
+// and the same reader as k_ground_returns, and the smallest pwpp_view_units((double)z) among them.  A point whose z is a NaN is
+// skipped and not counted.  grid (tiles of kObBlock entries over the longest selection of the range, frames).  k_beam_ends_fill
+// sets hits = 0 and zmin = INT32_MAX (above every quantised height: those end at 2^30), k_beam_ends_none turns the zmin of a cell
+// without a hit into PWPP_VIEW_NO_HEIGHT.  Integer adds and minima only.
+__global__ __launch_bounds__(kObBlock) void k_beam_ends_fill(int64_t cells, int32_t *hits, int32_t *zmin) {
+    const int64_t c = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    if (c >= cells) return;
+    hits[c] = 0;
+    zmin[c] = INT32_MAX;
+}
+__global__ __launch_bounds__(kObBlock) void k_beam_ends(PwppObstacleScan S, int which, int32_t *hits, int32_t *zmin) {
+    const int fr = blockIdx.y, f = S.frame_first + fr;
+    if ((unsigned)f >= (unsigned)S.Q.num_frames) return;
+    const PwppFrameDesc fd = S.descs[f];
+    const PwppFrameResult r = S.results[f];
+    const int64_t n = fd.n;  // (the two counts clamped to the frame, as obstacle_point clamps them)
+    const int64_t ng = r.n_ground < 0 ? 0 : (r.n_ground > n ? n : (int64_t)r.n_ground);
+    const int64_t nn = r.n_nonground < 0 ? 0 : (r.n_nonground > n - ng ? n - ng : (int64_t)r.n_nonground);
+    const int64_t e = ((which & 1) ? 0 : ng) + (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    if (e >= ((which & 2) ? ng + nn : ng)) return;
+    const int i = S.out_idx[fd.base + e];
+    if ((unsigned)i >= (unsigned)fd.n) return;
+    float x, y, z, w;
+    load_point<true>(fd, i, x, y, z, w);
+    int ix, iy;
+    if (z != z || !grid_cell(x, S.G.x0, S.G.cell, S.G.nx, ix) || !grid_cell(y, S.G.y0, S.G.cell, S.G.ny, iy)) return;
+    const size_t o = ((size_t)fr * (size_t)S.G.ny + (size_t)iy) * (size_t)S.G.nx + (size_t)ix;
+    atomicAdd(hits + o, 1);
+    atomicMin(zmin + o, pwpp_view_units((double)z));
+}
+__global__ __launch_bounds__(kObBlock) void k_beam_ends_none(int64_t cells, const int32_t *hits, int32_t *zmin) {
+    const int64_t c = (int64_t)blockIdx.x * kObBlock + threadIdx.x;
+    if (c < cells && hits[c] == 0) zmin[c] = PWPP_VIEW_NONE_HEIGHT;
+}
+
 // pwpp_label_obstacles' per-point cluster id: the scan of k_obstacle_raster again, and every COUNTED point takes the label of its
 // cell (-1 where the cell stayed below min_count).  point_cluster was filled with -1 and starts at the first point of S.frame_first
 // (`base_first`: that frame's fd.base); a point is named by at most one list entry, so every word has one writer.
@@ -3376,6 +3414,18 @@ extern "C" int pwpp_launch_ground_returns(const PwppObstacleScan *scan, int max_
     if (max_ground > 0)
         hipLaunchKernelGGL(k_ground_returns, dim3((unsigned)(((int64_t)max_ground + kObBlock - 1) / kObBlock), (unsigned)scan->frames), dim3(kObBlock), 0, stream,
                            *scan, seen);
+    return (int)hipGetLastError();
+}
+
+// pwpp_rasterize_beams: fill, points, the cells without one (max_entries: the longest selection of the range; 0: no point kernel runs).
+extern "C" int pwpp_launch_beam_ends(const PwppObstacleScan *scan, int which, int max_entries, int32_t *hits, int32_t *zmin, hipStream_t stream) {
+    const int64_t cells = (int64_t)scan->G.nx * (int64_t)scan->G.ny * (int64_t)scan->frames;  // (<= 2^31: checked by the caller)
+    const unsigned flat = (unsigned)((cells + kObBlock - 1) / kObBlock);
+    hipLaunchKernelGGL(k_beam_ends_fill, dim3(flat), dim3(kObBlock), 0, stream, cells, hits, zmin);
+    if (max_entries > 0)
+        hipLaunchKernelGGL(k_beam_ends, dim3((unsigned)(((int64_t)max_entries + kObBlock - 1) / kObBlock), (unsigned)scan->frames), dim3(kObBlock), 0, stream, *scan,
+                           which, hits, zmin);
+    hipLaunchKernelGGL(k_beam_ends_none, dim3(flat), dim3(kObBlock), 0, stream, cells, hits, zmin);
     return (int)hipGetLastError();
 }
 

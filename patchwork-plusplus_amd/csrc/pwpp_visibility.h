@@ -96,6 +96,14 @@ PWPP_HD inline bool pwpp_vis_step(PwppVisLine &L) {
     return mx && my;
 }
 
+// P_0 -> P_k in one move, by the closed form itself: only on a line as pwpp_vis_line left it, with n >= 1 and k <= n.  The same
+// state k calls of pwpp_vis_step leave (tools/beams_check.cpp compares them).  2k|d| + n < 2^31: sides are at most 32768.
+PWPP_HD inline void pwpp_vis_jump(PwppVisLine &L, uint32_t k) {
+    const uint32_t tx = k * L.ax2 + L.n, ty = k * L.ay2 + L.n;
+    L.x += L.sx * (int32_t)(tx / L.n2), L.ex = tx % L.n2;
+    L.y += L.sy * (int32_t)(ty / L.n2), L.ey = ty % L.n2;
+}
+
 // first of the cell c = (cx, cy) seen from o = (ox, oy), both inside the image of nx columns: the index jy * nx + jx of the first
 // occupied cell on the line by the rules (a) and (b), PWPP_VIS_FIRST_NONE when there is none, PWPP_VIS_FIRST_BEYOND when
 // n > max_range > 0 (nothing is read then).  The loop is bounded by n <= max(nx, ny).

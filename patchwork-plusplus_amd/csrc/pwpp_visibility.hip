@@ -133,12 +133,13 @@ __global__ __launch_bounds__(kWalkBlock) void k_view_walk(ViewImage I, const int
 }
 
 // The chained call's height images from its float rasters: target = units(ground), block = units((double)ground + (double)top).
+// Without `block` (the beams' chain) `top` is not read.
 __global__ __launch_bounds__(256) void k_view_quantise(int64_t cells, const float *ground, const float *top, int32_t *target, int32_t *block) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= cells) return;
     const float g = ground[c];
     target[c] = pwpp_view_units((double)g);
-    block[c] = pwpp_view_units((double)g + (double)top[c]);
+    if (block) block[c] = pwpp_view_units((double)g + (double)top[c]);
 }
 
 // Words of the handle's cluster buffer a walk on PATH needs for an image of nx * ny * frames cells: the bit image (none on path 1).

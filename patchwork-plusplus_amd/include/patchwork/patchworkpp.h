@@ -451,6 +451,37 @@ public:
                                       any ? v.shadow.data() : &none_s, any ? v.occupancy.data() : &none_o, nullptr));
         return v;
     }
+
+    // ... and the free space the returns themselves prove (pwpp_beam_ground): the beam of every selected return (which:
+    // PWPP_BEAMS_GROUND, PWPP_BEAMS_NONGROUND or both) is drawn from the sensor's cell to the return's cell.  passes: the beams that
+    // crossed the cell; low: the lowest height, in units of 1 / PWPP_VIEW_UNITS_PER_M m, at which one crossed it (PWPP_VIEW_NO_HEIGHT:
+    // none); occupancy: occupancy_in (empty: all unknown; else ny x nx bytes, typically getObstacleViewshed's) with every unknown
+    // cell free that min_pass beams crossed no more than `clearance` metres above its ground.
+    struct BeamClearance {
+        int nx = 0, ny = 0;
+        std::vector<uint32_t> passes;   // ny x nx, row-major: row iy, column ix
+        std::vector<int32_t> low;       // same shape
+        std::vector<int8_t> occupancy;  // same shape
+    };
+    BeamClearance getBeamClearance(double x0, double y0, double cell, int nx, int ny, int min_pass = 1, double clearance = 0.3, int max_range = 0,
+                                   double origin_x = 0.0, double origin_y = 0.0, double origin_z = 0.0, int which = PWPP_BEAMS_GROUND, bool ground_only = false,
+                                   const std::vector<int8_t> &occupancy_in = std::vector<int8_t>()) {
+        const pwpp_ground_grid g = {x0, y0, cell, nx, ny, ground_only ? (int32_t)PWPP_GRID_GROUND_ONLY : 0, 0};
+        BeamClearance v;
+        v.nx = nx > 0 ? nx : 0, v.ny = ny > 0 ? ny : 0;
+        v.passes.assign((size_t)v.nx * (size_t)v.ny, 0u);
+        v.low.assign(v.passes.size(), PWPP_VIEW_NO_HEIGHT);
+        v.occupancy.assign(v.passes.size(), (int8_t)PWPP_OCC_UNKNOWN);
+        if (!occupancy_in.empty() && occupancy_in.size() != v.passes.size()) throw std::invalid_argument("getBeamClearance: occupancy_in must be ny x nx bytes");
+        int32_t none_p = 0, none_l = 0;
+        int8_t none_o = 0;
+        const double origin[3] = {origin_x, origin_y, origin_z};
+        const bool any = !v.passes.empty();
+        check(pwpp_beam_ground(h_, &g, which, origin, 1, max_range, min_pass, clearance, 0, 1, PWPP_MEM_HOST, occupancy_in.empty() ? nullptr : occupancy_in.data(),
+                               any ? reinterpret_cast<int32_t *>(v.passes.data()) : &none_p, any ? v.low.data() : &none_l, any ? v.occupancy.data() : &none_o,
+                               nullptr, nullptr));
+        return v;
+    }
     // ... and the scans accumulated over time (pwpp_fuse_obstacles): a persistent map in a FIXED frame, the caller's own.  log_odds
     // holds an int16 per cell, occupancy the byte derived from it (PWPP_OCC_OCCUPIED where log_odds >= occupied_at, PWPP_OCC_FREE
     // where <= free_at, else PWPP_OCC_UNKNOWN).  updateObstacleMap resamples the last frame's visibility bytes on the grid (x0, y0,

@@ -133,6 +133,7 @@ FOOT_FREE, FOOT_HIT, FOOT_SKIPPED = 0, 1, 2  # PWPP_FOOT_*: the status of a pose
 FOOT_OUTSIDE_BLOCKS = 1  # PWPP_FOOT_OUTSIDE_BLOCKS: a covered cell outside the image makes the pose a HIT
 FOOT_SUB = 16  # PWPP_FOOT_SUB: ticks per cell side
 VIEW_NO_HEIGHT, VIEW_MAX_RISE, VIEW_UNITS_PER_M = -2 ** 31, 1 << 20, 1024  # PWPP_VIEW_*: no height, the clamp of a rise, units per metre
+BEAMS_GROUND, BEAMS_NONGROUND = 1, 2  # PWPP_BEAMS_*: the index lists rasterize_beams selects (`which`, a bit set)
 FOOT_POSE_DTYPE = np.dtype([(n, "<i4") for n in ("status", "covered", "outside", "blocked", "unknown", "max_term", "min_dist2", "hit")])  # pwpp_footprint_pose_row (32 bytes)
 FOOT_TRAJ_DTYPE = np.dtype([(n, "<i4") for n in ("first_hit", "free_steps", "last", "max_term", "sum_term", "unknown", "min_dist2", "reach_last")])  # pwpp_footprint_traj_row (32 bytes)
 
@@ -321,6 +322,13 @@ def load():
             L.pwpp_viewshed_obstacles.argtypes = [vp, gp, cf, cf, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
             L.pwpp_viewshed_units.argtypes = [ctypes.c_double]
             L.pwpp_viewshed_units.restype = ctypes.c_int32
+        if hasattr(L, "pwpp_beam_grid"):  # (as above: an older build has no beams)
+            gp, i32 = ctypes.POINTER(GroundGrid), ctypes.c_int32
+            L.pwpp_rasterize_beams.argtypes = [vp, gp, ci, ci, ci, ci, vp, vp]
+            L.pwpp_beam_grid.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
+            L.pwpp_beam_ground.argtypes = [vp, gp, ci, vp, ci, ci, ci, ctypes.c_double, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+            L.pwpp_beam_height.argtypes = [i32, i32, ci, ci]
+            L.pwpp_beam_height.restype = i32
         if hasattr(L, "pwpp_costmap_grid"):  # (as above: an older build has no costmap)
             gp, tp, cp = ctypes.POINTER(GroundGrid), ctypes.POINTER(TerrainParams), ctypes.POINTER(CostmapParams)
             cf, cd, i32 = ctypes.c_float, ctypes.c_double, ctypes.c_int32
@@ -379,6 +387,16 @@ def viewshed_units(metres):
     """A height in metres in the viewshed's units (pwpp_viewshed_units): VIEW_NO_HEIGHT for a NaN, otherwise
     floor(clamp(metres * 1024, -2^30, 2^30) + 0.5); needs no device."""
     return int(load().pwpp_viewshed_units(float(metres)))
+
+
+def beam_height(eye, z, k, n):
+    """The height, in the viewshed's units, at the crossed cell P_k (1 <= k < n) of a beam from an eye at `eye` into an endpoint n
+    steps away whose lowest return is at z: pwpp_beam_height, the function the kernels use, on the host; needs no device."""
+    L = load()
+    v = int(L.pwpp_beam_height(int(eye), int(z), int(k), int(n)))
+    if v == VIEW_NO_HEIGHT:
+        raise PwppError("pwpp error: %s" % L.pwpp_last_error().decode())
+    return v
 
 
 def footprint_covers(foot_params, pose, ix, iy):
@@ -1494,6 +1512,79 @@ class Handle:
         self._check(self._L.pwpp_viewshed_obstacles(self._h, ctypes.byref(g), float(h_min), float(h_max), int(min_count), int(min_seen),
                                                     _vp(org) if org.size else None, len(org), int(max_range), int(frame_first), frames, MEM_DEVICE,
                                                     _dp(first_ptr), _dp(shadow_ptr), _dp(occupancy_ptr), _dp(count_ptr)))
+
+    def rasterize_beams(self, x0, y0, cell, nx, ny, which=BEAMS_GROUND, frame_first=0, frames=None):
+        """The endpoints of the last call's beams on the grid of rasterize_obstacles: (hits, zmin), (frames, ny, nx) int32 -- the
+        points of the selected index lists (which: BEAMS_GROUND, BEAMS_NONGROUND or both) per cell, and the smallest
+        viewshed_units(z) among them (VIEW_NO_HEIGHT: none).  The non-ground list also holds the points the reflected-noise removal
+        rejected, whose beams end below the ground: BEAMS_GROUND is the safe default."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        hits, zmin = np.empty(self._grid_shape(g, frames), np.int32), np.empty(self._grid_shape(g, frames), np.int32)
+        self._check(self._L.pwpp_rasterize_beams(self._h, ctypes.byref(g), int(which), int(frame_first), frames, MEM_HOST, _hp(hits), _hp(zmin)))
+        return hits, zmin
+
+    def rasterize_beams_device(self, x0, y0, cell, nx, ny, hits_ptr, zmin_ptr, which=BEAMS_GROUND, frame_first=0, frames=None):
+        """rasterize_beams into device memory: the addresses of the two (frames, ny, nx) int32 images.  Enqueued on the handle's
+        stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, False)
+        self._check(self._L.pwpp_rasterize_beams(self._h, ctypes.byref(g), int(which), int(frame_first), frames, MEM_DEVICE, _dp(hits_ptr), _dp(zmin_ptr)))
+
+    def beam_grid(self, hits, zmin, origin, target=None, occupancy_in=None, max_range=0, min_pass=1, clearance=0, want_occupancy=True):
+        """The per-beam free space of (frames, ny, nx) or (ny, nx) int32 endpoint images: every cell with hits >= 1 and a zmin is the
+        end of a beam of weight hits from the origin's cell, drawn along visibility_grid's line; it crosses the cells strictly between.
+        origin: (ox, oy, eye) for every frame, or (frames, 3).  target: int32 ground heights or None; occupancy_in: int8 base bytes or
+        None (all OCC_UNKNOWN).  Works before any estimate call.  Returns (passes, low, occupancy) of hits' shape: the uint32 sum of
+        the weights of the beams that crossed the cell, the int32 lowest of their heights there (VIEW_NO_HEIGHT: none) and the int8
+        byte -- OCC_FREE where the base byte is OCC_UNKNOWN, passes >= min_pass and (with a target) low - target <= clearance, else
+        the base byte; None when it is not wanted.  The rules: include/pwpp.h."""
+        h3, shape = _count_image(hits)
+        frames, ny, nx = h3.shape
+        z3 = np.ascontiguousarray(np.asarray(zmin, np.int32).reshape(h3.shape))
+        tg = None if target is None else np.ascontiguousarray(np.asarray(target, np.int32).reshape(h3.shape))
+        base = None if occupancy_in is None else np.ascontiguousarray(np.asarray(occupancy_in, np.int8).reshape(h3.shape))
+        org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 3))
+        passes, low = np.empty(h3.shape, np.uint32), np.empty(h3.shape, np.int32)
+        occupancy = np.empty(h3.shape, np.int8) if want_occupancy else None
+        self._check(self._L.pwpp_beam_grid(self._h, nx, ny, frames, MEM_HOST, _hp(h3), _hp(z3), _hp(tg), _hp(base), _hp(org), len(org), int(max_range),
+                                           int(min_pass), int(clearance), _hp(passes), _hp(low), _hp(occupancy)))
+        return tuple(None if a is None else a.reshape(shape) for a in (passes, low, occupancy))
+
+    def beam_grid_device(self, nx, ny, frames, hits_ptr, zmin_ptr, origin, max_range, min_pass, clearance, passes_ptr, low_ptr, occupancy_ptr=0,
+                         target_ptr=0, occupancy_in_ptr=0):
+        """beam_grid on device memory: addresses of the (frames, ny, nx) int32 images, 4-byte aligned, and of the int8 images (0: none
+        / not wanted; occupancy_ptr may equal occupancy_in_ptr); origin stays a host array, (ox, oy, eye) or (frames, 3).  Enqueued on
+        the handle's stream; complete after synchronize()."""
+        org = np.ascontiguousarray(np.asarray(origin, np.int32).reshape(-1, 3))
+        self._check(self._L.pwpp_beam_grid(self._h, int(nx), int(ny), int(frames), MEM_DEVICE, _dp(hits_ptr), _dp(zmin_ptr), _dp(target_ptr),
+                                           _dp(occupancy_in_ptr), _vp(org) if org.size else None, len(org), int(max_range), int(min_pass), int(clearance),
+                                           _dp(passes_ptr), _dp(low_ptr), _dp(occupancy_ptr)))
+
+    def beam_ground(self, x0, y0, cell, nx, ny, origin_xyz=(0.0, 0.0, 0.0), which=BEAMS_GROUND, occupancy_in=None, max_range=0, min_pass=1, clearance=0.0,
+                    frame_first=0, frames=None, ground_only=False, want_occupancy=True, want_ends=False):
+        """rasterize_beams, rasterize_ground and beam_grid in one call, for frames of the last estimate call: target =
+        units(ground), eye = units(z) of the sensor's position origin_xyz in metres, (x, y, z) for every frame or (frames, 3);
+        clearance in metres.  occupancy_in: (frames, ny, nx) int8 base bytes -- typically viewshed_obstacles' -- or None.  Returns
+        (passes, low, occupancy) as beam_grid does; want_ends: then the int32 hits and zmin images too."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = _host(origin_xyz, np.float64, -1, 3)
+        shape = self._grid_shape(g, frames)
+        base = None if occupancy_in is None else np.ascontiguousarray(np.asarray(occupancy_in, np.int8).reshape(shape))
+        passes, low = np.empty(shape, np.uint32), np.empty(shape, np.int32)
+        occupancy = np.empty(shape, np.int8) if want_occupancy else None
+        hits, zmin = (np.empty(shape, np.int32), np.empty(shape, np.int32)) if want_ends else (None, None)
+        self._check(self._L.pwpp_beam_ground(self._h, ctypes.byref(g), int(which), _hp(org), len(org), int(max_range), int(min_pass), float(clearance),
+                                             int(frame_first), frames, MEM_HOST, _hp(base), _hp(passes), _hp(low), _hp(occupancy), _hp(hits), _hp(zmin)))
+        return (passes, low, occupancy) + ((hits, zmin) if want_ends else ())
+
+    def beam_ground_device(self, x0, y0, cell, nx, ny, origin_xyz, which, max_range, min_pass, clearance, passes_ptr, low_ptr, occupancy_ptr=0,
+                           occupancy_in_ptr=0, hits_ptr=0, zmin_ptr=0, frame_first=0, frames=None, ground_only=False):
+        """beam_ground into device memory: addresses as in beam_grid_device, hits_ptr and zmin_ptr the endpoint images (0: not
+        wanted); origin_xyz stays a host array.  Enqueued on the handle's stream; complete after synchronize()."""
+        g, frames = self._grid(x0, y0, cell, nx, ny, frame_first, frames, ground_only)
+        org = _host(origin_xyz, np.float64, -1, 3)
+        self._check(self._L.pwpp_beam_ground(self._h, ctypes.byref(g), int(which), _vp(org) if org.size else None, len(org), int(max_range), int(min_pass),
+                                             float(clearance), int(frame_first), frames, MEM_DEVICE, _dp(occupancy_in_ptr), _dp(passes_ptr), _dp(low_ptr),
+                                             _dp(occupancy_ptr), _dp(hits_ptr), _dp(zmin_ptr)))
 
     @staticmethod
     def _fusion_host(pose, map_of_frame, shift):

@@ -350,6 +350,28 @@ PYBIND11_MODULE(pypatchworkpp, m) {
              py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("h_min"), py::arg("h_max"),
              py::arg("min_count") = 1, py::arg("min_seen") = 1, py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0,
              py::arg("origin_z") = 0.0, py::arg("ground_only") = false)
+        .def("getBeamClearance",
+             [](PatchWorkpp &s, double x0, double y0, double cell, int nx, int ny, int min_pass, double clearance, int max_range, double origin_x,
+                double origin_y, double origin_z, int which, bool ground_only, py::object occupancy_in) {
+                 std::vector<int8_t> base;
+                 if (!occupancy_in.is_none()) {
+                     const auto a = py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(occupancy_in);
+                     if (!a) throw std::invalid_argument("getBeamClearance: occupancy_in must be an int8 array");
+                     base.assign(a.data(), a.data() + a.size());
+                 }
+                 const PatchWorkpp::BeamClearance v =
+                     s.getBeamClearance(x0, y0, cell, nx, ny, min_pass, clearance, max_range, origin_x, origin_y, origin_z, which, ground_only, base);
+                 py::array_t<uint32_t> passes({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 py::array_t<int32_t> low({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 py::array_t<int8_t> occupancy({(py::ssize_t)v.ny, (py::ssize_t)v.nx});
+                 if (!v.passes.empty()) std::memcpy(passes.mutable_data(), v.passes.data(), v.passes.size() * sizeof(uint32_t));
+                 if (!v.low.empty()) std::memcpy(low.mutable_data(), v.low.data(), v.low.size() * sizeof(int32_t));
+                 if (!v.occupancy.empty()) std::memcpy(occupancy.mutable_data(), v.occupancy.data(), v.occupancy.size());
+                 return py::make_tuple(passes, low, occupancy);
+             },
+             py::arg("x0"), py::arg("y0"), py::arg("cell"), py::arg("nx"), py::arg("ny"), py::arg("min_pass") = 1, py::arg("clearance") = 0.3,
+             py::arg("max_range") = 0, py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0, py::arg("origin_z") = 0.0, py::arg("which") = 1,
+             py::arg("ground_only") = false, py::arg("occupancy_in") = py::none())
         .def("updateObstacleMap",
              [](PatchWorkpp &s, PatchWorkpp::FusedObstacleMap &map, const std::array<double, 6> &pose, double x0, double y0, double cell, int nx, int ny,
                 float h_min, float h_max, int min_count, int max_range, double origin_x, double origin_y, int shift_x, int shift_y) {
